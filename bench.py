@@ -14,7 +14,13 @@ fixes the total work instead (strong scaling, SURVEY.md §8e: 8192 pairs over 1/
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         bench.py --gpus 8 --steps 10 --warmup 3
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline figure (`value`,
+`ms_per_step`); --dump-outputs DIR also writes the last timed step's poses (DIR/poses.npy).  --full adds, after the timed
+region, everything else this program measures or checks: the event-bracketed and compute-only steps (`roofline`), the
+`streaming`, `single_pair_latency`, `arith_sets` and `h2d_inclusive` figures, the CPU baselines and the `parity` of every
+distinct pair with the CPU oracle.
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
 """
 import argparse
 import faulthandler
@@ -72,7 +78,7 @@ def parse_args(argv=None):
     ap.add_argument("--total-pairs", type=int, default=0,
                     help="total pairs of the job, split round-robin over the GPUs (strong scaling); overrides --pairs")
     ap.add_argument("--unique", type=int, default=128, help="distinct synthetic pairs generated per rank (tiled to its shard); "
-                    "every one of them is checked against the CPU oracle after the timed region")
+                    "with --full every one of them is checked against the CPU oracle after the timed region")
     ap.add_argument("--generator", choices=["cpp", "numpy"], default="cpp",
                     help="cpp: the deterministic C++ generator shared with tools/uwt_bench (tools/uwt_gen.h through "
                          "tools/libuwt_gen.so; SURVEY.md §8d); numpy: uw-slam_amd/synth.py")
@@ -97,13 +103,20 @@ def parse_args(argv=None):
     ap.add_argument("--tuning", default="", help="launch-shape switches for A/B runs: comma-separated uwt_tuning fields, e.g. "
                     "typed_loads=0,split=1 (never changes results; include/uwt.h)")
     ap.add_argument("--dump-poses", default="", help="rank 0 writes the last step's poses of the whole job, global pair order, [total, 7] float32 (.npy)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed, as a caller of the timed path receives it: DIR/poses.npy, "
+                         "the poses of the whole job in global pair order, [total, 7] float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beside the headline figure: the event-bracketed "
+                         "and compute-only steps (roofline), streaming and one-pair latency, the other arithmetic set, the upload "
+                         "figure, the CPU baselines and the parity of every distinct pair with the CPU oracle")
     ap.add_argument("--n1-value", type=float, default=0.0,
                     help="alignments/s of the same workload on ONE GPU (a line of this program at --gpus 1): a multi-GPU line then "
                          "carries efficiency_vs_n1 = value / (n_gpus x this) beside per_rank_ms")
     ap.add_argument("--cpu-pairs", type=int, default=96,
-                    help="alignments timed on the CPU oracle, 1 thread (rank 0, N=1 only; 0 = skip); ~10 s at 640x480")
+                    help="with --full: alignments timed on the CPU oracle, 1 thread (rank 0, N=1 only; 0 = skip); ~10 s at 640x480")
     ap.add_argument("--no-profile", action="store_true",
-                    help="skip the event-bracketed step, the compute-only step and the secondary figures after the timed region")
+                    help="with --full: skip the event-bracketed step, the compute-only step and the secondary figures after the timed region")
     return ap.parse_args(argv)
 
 
@@ -389,7 +402,7 @@ def main(args, standin=None):
     gpu_poses = (pipe.last_local() if use_dist else single_buf).cpu().numpy()
     all_poses = pipe.gathered.cpu().numpy() if use_dist else gpu_poses
 
-    # ---- after the timed region: one step with HIP events around every residual launch (each event pair drains the
+    # ---- after the timed region, with --full: one step with HIP events around every residual launch (each event pair drains the
     # stream, so it is kept out of `value`), then one step of the kernel's compute-only twin (its instruction-issue
     # floor).  Each is preceded by untimed steps of the same kind: the chip holds a lower clock for the first
     # milliseconds after the pause of the copy above, and the durations should be those of the sustained state.
@@ -398,7 +411,8 @@ def main(args, standin=None):
     co_ms = 0.0
     clock_ghz = co_clock_ghz = 0.0
     t_p = time.perf_counter()
-    if not args.no_profile:
+    extras = args.full and not args.no_profile             # a plain run stops at the headline figure
+    if extras:
         for _ in range(max(2, args.warmup)):
             step()
         ctx.profile_enable(1)
@@ -424,19 +438,19 @@ def main(args, standin=None):
     # (not under a profiler: its launches carry the residual kernel's name and, running beside the copies, would blur the
     # per-kernel statistics that are compared with roofline.avg_launch_ms)
     Ps = min(P, 1024)                                       # pairs of the secondary legs (their own contexts hold 4 Ps and 2 Ps slots)
-    if not args.no_profile and world == 1 and not args.reference_schedule and not _under_profiler():
+    if extras and world == 1 and not args.reference_schedule and not _under_profiler():
         fr, dp = pair_block(0, Ps)
         streaming = streaming_figure(capi, params, fr, dp, Ps, max(3, args.steps // 2), gpu_poses[:Ps])   # 2 batches per round
         del fr, dp
     latency = None
-    if not args.no_profile and world == 1 and not args.bilinear and args.weights == "identity" and not _under_profiler():
+    if extras and world == 1 and not args.bilinear and args.weights == "identity" and not _under_profiler():
         fr, dp = pair_block(0, 1)
         latency = latency_figure(capi, params, fr, dp, None if args.reference_schedule else gpu_poses[0])
     # The same workload under the OTHER arithmetic set, measured in this run on a context of its own (never `value`): the default
     # set (opencv: what OpenCV's generic code paths compute) costs ~19 % of the throughput the legacy set (f32 FMA chains) has,
     # and which of the two a given reference build computes is unpinned — so both are reported, side by side.
     other = None
-    if not args.no_profile and world == 1 and not _under_profiler():
+    if extras and world == 1 and not _under_profiler():
         other = other_arith_figure(capi, params, pair_block, Ps, args.steps, args.warmup, dev)
 
     value = total * args.steps / dt
@@ -478,6 +492,9 @@ def main(args, standin=None):
     if rank == 0:
         if args.dump_poses:
             np.save(args.dump_poses, all_poses)
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "poses.npy"), np.ascontiguousarray(all_poses, np.float32))
         if use_dist:
             # every rank's block must have arrived in global pair order: rank 0's own pairs sit at i = rank + k * world,
             # and pairs that repeat a distinct input (same seed modulo the tiling) must carry identical poses
@@ -493,9 +510,10 @@ def main(args, standin=None):
                 out["efficiency_vs_n1"] = round(value / (world * args.n1_value), 4)
                 out["n1_value"] = args.n1_value
         # SURVEY §8(d) secondary figure: the same step with the batch's frames crossing PCIe first (never `value`)
-        out["h2d_inclusive"] = {"value": round(P / (upload_s + dt / args.steps), 2), "unit": "alignments/s per GPU",
-                                "upload_ms": round(upload_s * 1e3, 2), "upload_GBs": round(upload_bytes / upload_s / 1e9, 2),
-                                "note": "one blocking upload of the rank's resident batch from pageable host memory + one step"}
+        if args.full:
+            out["h2d_inclusive"] = {"value": round(P / (upload_s + dt / args.steps), 2), "unit": "alignments/s per GPU",
+                                    "upload_ms": round(upload_s * 1e3, 2), "upload_GBs": round(upload_bytes / upload_s / 1e9, 2),
+                                    "note": "one blocking upload of the rank's resident batch from pageable host memory + one step"}
         if streaming:
             out["streaming"] = streaming
         if latency:
@@ -575,7 +593,7 @@ def main(args, standin=None):
                     e["algorithmic_GBs"] = None
                 roof["note"] = "early-exit schedule: launches whose pairs have left the level fall through; no meaningful bytes per launch"
             out["roofline"] = roof
-        if world == 1 and args.cpu_pairs > 0:
+        if args.full and world == 1 and args.cpu_pairs > 0:
             from oracle import oracle as O          # test infrastructure, used here only as the timed CPU baseline/checker
             po = O.default_params(w, h, *intr, **{k: v for k, v in over.items() if k != "accumulate_f64"})
             n_cpu = args.cpu_pairs                  # cycles over the U distinct pairs

@@ -119,9 +119,12 @@ def _run(world, argv, tmp_path):
 def test_bench_rank_body_world2_over_gloo(tmp_path, mode):
     world, w, h = 2, 64, 48
     poses_path = str(tmp_path / "poses.npy")
+    outputs_dir = tmp_path / "outputs"
     argv = ["--gpus", "2", "--steps", "3", "--warmup", "2", "--width", str(w), "--height", str(h), "--levels", "3", "--unique", "5",
-            "--no-profile", "--cpu-pairs", "0", "--dump-poses", poses_path, "--n1-value", "100.0", "--generator", "numpy", "--tuning", "split=1"]
-    argv += ["--pairs", "6"] if mode == "weak" else ["--total-pairs", "11"]
+            "--no-profile", "--cpu-pairs", "0", "--dump-poses", poses_path, "--dump-outputs", str(outputs_dir), "--n1-value", "100.0",
+            "--generator", "numpy", "--tuning", "split=1"]
+    # the weak run is a plain one; the strong one adds --full (with --no-profile and no CPU pairs, only the upload figure remains)
+    argv += ["--pairs", "6"] if mode == "weak" else ["--total-pairs", "11", "--full"]
     total = 12 if mode == "weak" else 11
     res, out_path = _run(world, argv, tmp_path)
     assert res == {0: "ok", 1: "ok"}
@@ -137,6 +140,7 @@ def test_bench_rank_body_world2_over_gloo(tmp_path, mode):
     assert abs(d["ms_per_step"] - max(d["per_rank_ms"])) <= 1e-3 * max(d["per_rank_ms"]) + 1e-3
     assert abs(d["value"] - total / (d["ms_per_step"] * 1e-3)) <= 2e-3 * d["value"]
     assert abs(d["efficiency_vs_n1"] - d["value"] / 200.0) < 1e-3 and d["n1_value"] == 100.0
+    assert ("h2d_inclusive" in d) == (mode != "weak")
     # the gathered poses, in GLOBAL pair order: pair i lives on rank i mod 2 as its local pair i // 2, and carries the signatures of
     # the frames generated for global id (rank's u-th distinct pair repeats: local pair k shows distinct pair k mod U of that rank)
     synth = importlib.import_module("uw-slam_amd.synth")
@@ -144,6 +148,9 @@ def test_bench_rank_body_world2_over_gloo(tmp_path, mode):
     intr = (f, f, w / 2 - 0.5, h / 2 - 0.5)
     poses = np.load(poses_path)
     assert poses.shape == (total, 7)
+    # --dump-outputs: the same poses, as the timed path's caller receives them
+    dumped = np.load(outputs_dir / "poses.npy")
+    assert dumped.dtype == np.float32 and np.array_equal(dumped.view(np.uint32), poses.view(np.uint32))
     for i in range(total):
         r, k = i % world, i // world
         n_local = len(range(r, total, world))

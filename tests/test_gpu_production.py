@@ -359,7 +359,7 @@ def test_bench_refuses_more_gpus_than_visible():
 
 
 def test_bench_strong_scaling_mode_single_gpu():
-    r = _run([sys.executable, "bench.py", "--gpus", "1", "--total-pairs", "24"] + SMALL_BENCH)
+    r = _run([sys.executable, "bench.py", "--gpus", "1", "--total-pairs", "24", "--full"] + SMALL_BENCH)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     d = json.loads(r.stdout.decode().strip().splitlines()[-1])
     assert d["scaling"] == "strong" and d["n_gpus"] == 1 and d["config"]["total_pairs"] == 24
@@ -367,6 +367,26 @@ def test_bench_strong_scaling_mode_single_gpu():
     assert d["roofline"]["bound"] == "hbm" and d["roofline"]["limited_by"] == "valu" and 0 < d["roofline"]["valu"]["valu_issue_frac"] <= 2.0
     assert set(d["arith_sets"]) >= {"opencv", "legacy"} and d["arith_sets"]["legacy"]["value"] > 0
     assert d["roofline"]["valu"]["shader_clock_GHz"] > 0.5
+
+
+@pytest.mark.one_arith
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline figure and nothing measured after the timed region; --dump-outputs writes the poses
+    of the last timed step, and a --full run of the same arguments (same inputs) computes them bit for bit the same."""
+    args = [sys.executable, "bench.py", "--gpus", "1", "--total-pairs", "24"] + SMALL_BENCH
+    r = _run(args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    d = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert d["unit"] == "alignments/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 2
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 24 / (d["ms_per_step"] * 1e-3)) <= 2e-3 * d["value"]
+    assert not set(d) & {"roofline", "arith_sets", "streaming", "single_pair_latency", "h2d_inclusive", "cpu_baseline", "parity"}
+    poses = np.load(tmp_path / "plain" / "poses.npy")
+    assert poses.dtype == np.float32 and poses.shape == (24, 7) and np.isfinite(poses).all()
+    assert (np.abs(np.linalg.norm(poses[:, :4], axis=1) - 1.0) < 1e-3).all()
+    r = _run(args + ["--full", "--dump-outputs", str(tmp_path / "full")])
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    assert "roofline" in json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert np.array_equal(np.load(tmp_path / "full" / "poses.npy").view(np.uint32), poses.view(np.uint32))
 
 
 def test_bench_rccl_world_of_one_gathers_on_the_context_stream():

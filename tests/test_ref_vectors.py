@@ -3,7 +3,7 @@
 The reference holds no test vectors of its own and cannot be built in this image (no OpenCV / Eigen), so no such file is
 committed yet — parity with the reference stays unpinned until a maintainer runs tools/ref_dump against an OpenCV-3.2 build
 (README there) and commits the result.  What runs here regardless: the insertion points of the instrumentation are found
-in the reference's Tracker.cpp (when /root/reference is present), the input export round-trips, and the whole
+in a Tracker.cpp-shaped source (built here from the tool's own patterns), the input export round-trips, and the whole
 dump -> loader -> comparison pipeline is exercised on a dump fabricated from the oracle in the reference-side format.
 """
 import glob
@@ -16,7 +16,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REF_SRC = "/root/reference/src/Tracker.cpp"
 
 
 def _tool(name):
@@ -268,15 +267,59 @@ def fabricate_dump(O, pair, name, out_dir):
     return pose
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SRC), reason="reference checkout not present")
+# A source shaped like the reference's src/Tracker.cpp around Tracker::EstimatePose, written for this test: one statement for
+# each insertion point of tools/ref_dump/instrument.py, and decoys it must leave alone (a commented-out statement inside the
+# function, the same statements in the definitions before and after it).
+HOOK_STATEMENTS = ["error = errorMat.at<float>(0, 0);", "if (error >= last_error) {", "deltaMat = A.inv() * b;",
+                   "current_pose = current_pose * SE3::exp(deltaVector);", "_previous_frame->rigid_transformation_ = current_pose;"]
+TRACKER_SHAPED = """#include "Tracker.h"
+void Tracker::WarpFunction(Mat points, SE3 rigid, int lvl) {
+    deltaMat = A.inv() * b;
+}
+void Tracker::EstimatePose(Frame* _previous_frame, Frame* _current_frame) {
+    SE3 current_pose = SE3(_previous_frame->rigid_transformation_);
+    for (int lvl = 4; lvl >= 1; lvl--) {
+        float last_error = FLT_MAX;
+        for (int k = 0; k < 50; k++) {
+            // error = errorMat.at<float>(0, 0);
+            %s
+            %s
+                break;
+            }
+            Mat A = J.t() * J;
+            Mat b = -J.t() * Residuals;
+            %s
+            %s
+            last_error = error;
+        }
+    }
+    %s
+}
+Mat Tracker::AddPatchPointsFeatures(Mat candidatePoints, int lvl) {
+    current_pose = current_pose * SE3::exp(deltaVector);
+}
+""" % tuple(HOOK_STATEMENTS)
+
+
 def test_instrumentation_finds_every_insertion_point():
     ins = _tool("instrument")
-    text = open(REF_SRC).read()
+    text = TRACKER_SHAPED
+    assert len(HOOK_STATEMENTS) == len(ins.HOOKS)
     out = ins.instrument(text)
     added = [l for l in out.split("\n") if "tools/ref_dump" in l]
     assert len(added) == len(ins.HOOKS) + 1                      # the hooks and the #include
     # nothing else changes: removing the added lines gives the file back
     assert "\n".join(l for l in out.split("\n") if "tools/ref_dump" not in l) == text
+    # each hook right behind its statement inside EstimatePose, at the statement's indentation
+    lines = out.split("\n")
+    for stmt, (_, hook) in zip(HOOK_STATEMENTS, ins.HOOKS):
+        i = next(i for i, l in enumerate(lines) if l.strip() == stmt and "EstimatePose" in "".join(lines[:i]) and "AddPatchPointsFeatures" not in "".join(lines[:i]))
+        assert lines[i + 1] == lines[i][:len(lines[i]) - len(lines[i].lstrip())] + hook + "   // tools/ref_dump", (stmt, lines[i + 1])
+    # an insertion point that is missing (or found twice) is an error, not a silently uninstrumented copy
+    with pytest.raises(SystemExit):
+        ins.instrument(text.replace(HOOK_STATEMENTS[2], "deltaMat = solve(A, b);"))
+    with pytest.raises(SystemExit):
+        ins.instrument(text.replace("last_error = error;", HOOK_STATEMENTS[0]))
 
 
 def test_driver_passes_a_syntax_check_against_interface_stubs():

@@ -13,8 +13,8 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 stats() {  # name, bench args...
   name=$1; shift
-  (cd $R && rocprofv3 --kernel-trace --stats -d $out/stats_$name --output-format csv -- python3 bench.py "$@" > $out/bench_$name.json 2> $out/bench_$name.err)
-  (cd $R && python3 bench.py "$@" > $out/bench_${name}_no_profiler.json 2> $out/bench_${name}_no_profiler.err)   # the same line without the profiler
+  (cd $R && rocprofv3 --kernel-trace --stats -d $out/stats_$name --output-format csv -- python3 bench.py --full "$@" > $out/bench_$name.json 2> $out/bench_$name.err)
+  (cd $R && python3 bench.py --full "$@" > $out/bench_${name}_no_profiler.json 2> $out/bench_${name}_no_profiler.err)   # the same line without the profiler
 }
 stats default_p1024
 stats legacy_default_p1024 --arith legacy
@@ -37,7 +37,7 @@ stats roi_733x471_l5_p1024 --width 733 --height 471 --intrinsics $E736 --levels 
 stats roi_725x465_l5_p1024 --width 725 --height 465 --intrinsics $E736 --levels 5 --no-depth --unique 64 --cpu-pairs 16
 stats roi_735x479_l5_p1024 --width 735 --height 479 --intrinsics $E736 --levels 5 --no-depth --unique 64 --cpu-pairs 16
 stats roi_733x471_refsched_p1024 --width 733 --height 471 --intrinsics $E736 --reference-schedule --no-depth --unique 64 --cpu-pairs 16
-(cd $R && python3 bench.py --gpus 1 --total-pairs 8192 --steps 5 --warmup 2 > $out/bench_total8192_g1.json 2> $out/bench_total8192_g1.err)
+(cd $R && python3 bench.py --full --gpus 1 --total-pairs 8192 --steps 5 --warmup 2 > $out/bench_total8192_g1.json 2> $out/bench_total8192_g1.err)
 (cd $R && python3 tools/exp/latency_general.py 200 > $out/latency_single_pair.txt 2>/dev/null)
 (cd $R && python3 tools/exp/latency_identity.py 300 > $out/latency_identity_by_level.txt 2>/dev/null)
 (cd $R && python3 tools/exp/call_overhead.py > $out/call_overhead.txt 2>/dev/null)

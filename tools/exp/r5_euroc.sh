@@ -3,7 +3,7 @@
 E=458.654,457.296,367.215,248.375
 E736=458.654,457.296,359.215,248.375     # principal point moved by the 8 columns cropped on the left (752 -> 736)
 out=gpurun_out/${1:-r5_euroc}; mkdir -p $out
-run() { name=$1; shift; python bench.py --cpu-pairs 0 --steps 20 --warmup 5 "$@" > $out/$name.json 2> $out/$name.err; python - <<PY
+run() { name=$1; shift; python bench.py --full --cpu-pairs 0 --steps 20 --warmup 5 "$@" > $out/$name.json 2> $out/$name.err; python - <<PY
 import json
 d=json.load(open("$out/$name.json"))
 r=d.get("roofline",{})

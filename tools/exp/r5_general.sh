@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 5: the general path's bench lines (robust weights / bilinear sampler), optionally with the residual plane off: r5_general.sh <out> [plane]
 out=gpurun_out/${1:-r5_general}; mkdir -p $out
-run() { name=$1; shift; python bench.py --cpu-pairs 0 --steps 20 --warmup 5 "$@" > $out/$name.json 2> $out/$name.err; python - <<PY
+run() { name=$1; shift; python bench.py --full --cpu-pairs 0 --steps 20 --warmup 5 "$@" > $out/$name.json 2> $out/$name.err; python - <<PY
 import json
 d=json.load(open("$out/$name.json"))
 r=d.get("roofline",{})

@@ -6,7 +6,7 @@
 out=gpurun_out/${1:-verify}; mkdir -p $out
 python -c "import ctypes; h = ctypes.CDLL('uw-slam_amd/libuwt_hip.so'); h.uwt_source_id.restype = ctypes.c_char_p; print(h.uwt_source_id().decode())" > $out/library_source_id.txt
 python -m pytest tests -m gpu -q 2>&1 | tail -2 > $out/pytest_gpu.txt
-python bench.py --steps 20 --warmup 5 > $out/bench_default_p1024_final.json 2> $out/bench_final.err
+python bench.py --full --steps 20 --warmup 5 > $out/bench_default_p1024_final.json 2> $out/bench_final.err
 bash tools/parity_survey.sh ${1:-verify}/parity_survey > /dev/null 2>&1
 bash tools/exp/odd_shapes.sh ${1:-verify}/odd_shapes > /dev/null 2>&1
 bash tools/exp/roi_shapes.sh ${1:-verify}/roi_shapes > /dev/null 2>&1     # frame sizes the resize chain does not divide (round 6)
