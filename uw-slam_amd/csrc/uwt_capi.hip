@@ -94,17 +94,13 @@ struct uwt_ctx {
                                         // was cut short, halved again after kSpecCalm calls in a row that were not
   int spec_calm = 0;
   static constexpr int kSpecCalm = 64;
-  bool speculate = false;               // set by the synchronous entry for one or two pairs: launch a level's usual number of
-                                        // iterations without reading back, check once at the end, redo conservatively if cut short
   // the synchronous small-batch call: results and the cut-short flag are written by the last kernel straight into this
-  // page-locked block (no device-to-host copies), and one or two pairs travel in the kernel arguments (no pair list upload)
+  // page-locked block (no device-to-host copies)
   static constexpr int kSmallBatch = 8;
   struct SmallResults { float poses[kSmallBatch * 7]; StatsOut stats[kSmallBatch]; int cut; };
   SmallResults* h_small = nullptr;      // pinned, device-visible
   SmallResults* d_small = nullptr;      // its device address
-  bool inline_pairs = false;
   bool deferred = false;                // uwt_set_deferred: stage calls return once enqueued
-  int pair_slots[4] = {0, 0, 0, 0};
   unsigned poll_seq = 0;                // batch path: read-backs alternate between two counters / events (taken one evaluation late)
   hipEvent_t ev_poll[2] = {};
   const uint32_t* prof_records = nullptr;
@@ -387,8 +383,8 @@ LaunchSel launch_sel(const uwt_ctx* c) {
   return sel;
 }
 
-int launch_residual(uwt_ctx* c, const ResidualArgs& a, int n_pairs, bool dump) {
-  uwt::launch_residual(c->stream, launch_sel(c), a, n_pairs, dump);
+int launch_residual(uwt_ctx* c, hipStream_t s, const ResidualArgs& a, int n_pairs, bool dump) {
+  uwt::launch_residual(s, launch_sel(c), a, n_pairs, dump);
   HIPCHK(c, hipGetLastError());
   return UWT_OK;
 }
@@ -457,8 +453,8 @@ GeneralArgs general_args(uwt_ctx* c) {
 
 // One residual evaluation on the general path (robust weights and/or bilinear sampler): with weights on, one histogram pass
 // estimates the scale first (MedianMat / MedianAbsoluteDeviation, src/Tracker.cpp:1571-1619), then the weighted accumulation runs.
-int launch_general(uwt_ctx* c, const ResidualArgs& ra, int n_pairs) {
-  uwt::launch_general(c->stream, launch_sel(c), ra, n_pairs, c->p.sampler, c->p.weights, c->hist, c->scale);
+int launch_general(uwt_ctx* c, hipStream_t s, const ResidualArgs& ra, int n_pairs) {
+  uwt::launch_general(s, launch_sel(c), ra, n_pairs, c->p.sampler, c->p.weights, c->hist, c->scale);
   HIPCHK(c, hipGetLastError());
   return UWT_OK;
 }
@@ -512,52 +508,123 @@ void arm_tail(uwt_ctx* c, ResidualArgs& ra, const UpdateArgs& ua) {
   ra.tail.gain = ua.gain;
 }
 
-int launch_iterate(uwt_ctx* c, const ResidualArgs& a, const IterArgs& ia, int n_pairs) {
-  uwt::launch_iterate(c->stream, launch_sel(c), a, ia, n_pairs);
-  HIPCHK(c, hipGetLastError());
+// Reference-mode early exit, read back synchronously: the launch handed c->d_active counts the pairs still iterating on its
+// level.  poll_arm clears the counter ahead of that launch; poll_any_left copies the count back behind it, waits for the
+// stream and tells whether any pair is left.
+int poll_arm(uwt_ctx* c) {
+  HIPCHK(c, hipMemsetAsync(c->d_active, 0, sizeof(int), c->stream));
   return UWT_OK;
 }
 
-// The chained form of Tracker::EstimatePose for a batch (dense points, nearest-neighbour sampler, identity weights, any level
-// size): one k_iterate launch per iteration — each block first applies the update of the previous
-// evaluation (and the level hand-off when a level begins), then evaluates — and one k_finish at the end; levels x
-// iterations + 1 launches instead of 2 x levels x iterations + levels + 2.
-int enqueue_estimate_chained(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats, const hipEvent_t* level_ready) {
+int poll_any_left(uwt_ctx* c, bool* left) {
+  HIPCHK(c, hipMemcpyAsync(c->h_active, c->d_active, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *left = *c->h_active != 0;
+  return UWT_OK;
+}
+
+// Slicing follows the batch: the create-time slicing (kGroupsPerThread) gives a single pair enough blocks to spread over the
+// chip; a batch that fills it alone runs fewer, longer blocks (less reduction overhead per pixel, fewer records to fold),
+// still at least target_blocks per launch.
+// fixed (fixed schedules of the batch path, every pair stays to the level's end): a block should also be long enough to carry
+// its fixed costs — the matrix set-up, the two-pass LDS fold, the record, the ticket — i.e. 16 groups per thread, as long as
+// the launch still fills the chip once (1024 resident blocks).  Level 2 of a 1024-pair batch: 1 slice of 19 groups per thread
+// instead of 4 of 5, +4.6 % on that level's launches.  Early-exit schedules keep the finer slicing: pairs leave a level at
+// different evaluations and the blocks of those that stay have to fill the chip (coarser: 437 k -> 314 k alignments/s, measured).
+void level_slicing(const uwt_ctx* c, int lvl, int n_pairs, int target_blocks, bool fixed, int& groups_per_block, int& slices) {
+  const int n_groups = c->lv[lvl].ng / c->vecl[lvl];
+  int want = (target_blocks + n_pairs - 1) / n_pairs;
+  want = std::max(1, std::min(want, c->slices[lvl]));
+  if (fixed) {
+    const int by_work = std::max(1, n_groups / (kBlock * 16));
+    want = std::min(want, std::max(by_work, (1024 + n_pairs - 1) / n_pairs));
+  }
+  const int gpt = (n_groups + want * kBlock - 1) / (want * kBlock);
+  groups_per_block = gpt * kBlock;
+  slices = (n_groups + groups_per_block - 1) / groups_per_block;
+}
+
+// Which chained form a call takes, if any.
+// Identity weights: the chained flow pays where an alignment is bound by kernel boundaries and dependent round trips, not by
+// arithmetic: a few pairs on their own (the drop-in call).  In a batch every block would repeat its pair's update.  Measured at
+// 640x480 (round 2, profiles/r03/DESIGN_lab_notes_r01-r03.md): ahead up to 6 pairs in fixed schedules, up to 16 in early-exit
+// schedules (half the launches between two read-backs), level from there on (uwt_tuning::chained = 1 / 0 force it on / off).
+// Robust weights (round 6): a few pairs per call — the drop-in use with the Tukey / Huber weighting on.
+enum class Chained { none, identity, robust };
+
+Chained chained_form(const uwt_ctx* c, int n_pairs) {
+  const uwt_params& p = c->p;
+  const int chained = c->tn.chained;
+  if (p.accumulate_f64 == 0) return Chained::none;
+  if (p.sampler == 0 && p.weights == 0 && (chained > 0 || (chained < 0 && n_pairs <= (p.early_exit ? 16 : 6))))
+    return Chained::identity;
+  if (p.weights != 0 && !c->profiling && !c->compute_only && (chained > 0 || (chained < 0 && n_pairs <= 4)))
+    return Chained::robust;
+  return Chained::none;
+}
+
+// What the synchronous small call (uwt_estimate_pose_batch) asks of the identity-weight chained flow for one call
+struct CallOpts {
+  bool speculate = false;              // launch a level's usual number of evaluations without reading back, check once at the
+                                       // end, redo conservatively if cut short
+  bool inline_pairs = false;           // the (at most two) pairs' slots travel in the kernel arguments: no pair list upload
+  int pair_slots[4] = {0, 0, 0, 0};    // ref 0, tgt 0, ref 1, tgt 1
+};
+
+// The chained form of Tracker::EstimatePose for a few pairs (dense points, any level size): one launch step per evaluation —
+// each block first applies the update of the previous evaluation (and the level hand-off when a level begins), then
+// evaluates — and one k_finish at the end.
+// Identity weights (nearest sampler): one k_iterate launch per evaluation; levels x iterations + 1 launches instead of
+// 2 x levels x iterations + levels + 2.
+// Robust weights: an evaluation is two launches instead of three (scale pass, weighted sums, update): the update of
+// evaluation k — and the level hand-off where a level ends — runs at the head of evaluation k + 1's scale pass
+// (k_hist_iterate), the weighted sums behind it.  640 x 480, one pair, 4 x 10: 91 launches -> 61.  Same device functions as
+// the launches it replaces: the same poses bit for bit.
+int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_poses, StatsOut* d_stats,
+                             const hipEvent_t* level_ready, const CallOpts& opt) {
   const uwt_params& p = c->p;
   uint32_t* recs[2] = {c->partials, c->partials2};
   PairState* states[2] = {c->state, c->state2};
-  int rp = 0, sp = 0;            // parity of the records / states the NEXT launch writes
+  int rp = 0, sp = 0;            // parity of the records / states the NEXT evaluation writes
   IterArgs ia;
   std::memset(&ia, 0, sizeof(ia));
   ia.u.max_iters = p.max_iters;
   ia.u.early_exit = p.early_exit;
   ia.u.epsilon = p.epsilon;
   ia.u.gain = p.gain;
+  ia.u.general = robust ? 1 : 0;
   ia.u.legacy_solve = p.arith == UWT_ARITH_LEGACY ? 1 : 0;
   ia.scale_t = p.handoff_scale_t;
   ia.initial_error = p.initial_error;
-  bool first = true;
-  int prev_slices = 0, prev_k = 0, prev_lvl = p.first_level;
-  // Speculative launching (early-exit schedules, the synchronous one- or two-pair call): every read-back of "who is still
-  // iterating" costs a host round trip of about two evaluations; instead each level gets the evaluations levels usually
-  // take plus one, nothing is read back, and the level switch notes on the device whether a pair was cut short — the
+  // Speculative launching (identity weights, early-exit schedules, the synchronous one- or two-pair call): every read-back of
+  // "who is still iterating" costs a host round trip of about two evaluations; instead each level gets the evaluations levels
+  // usually take plus one, nothing is read back, and the level switch notes on the device whether a pair was cut short — the
   // caller looks once, behind the results, and redoes the alignment the careful way in that (rare) case.
-  const bool speculate = c->speculate && p.early_exit;
-  const int spec_iters = std::min(p.max_iters, std::max(c->spec_budget, c->tn.first_poll + 1));
+  const bool speculate = opt.speculate && p.early_exit;
+  const int evals = speculate ? std::min(p.max_iters, std::max(c->spec_budget, c->tn.first_poll + 1)) : p.max_iters;
   ia.cut_short = speculate ? &c->d_small->cut : nullptr;
   if (speculate) c->h_small->cut = 0;   // host store into page-locked memory, ahead of the launches that may set it
-  ia.inline_pairs = c->inline_pairs ? 1 : 0;
-  for (int i = 0; i < 4; i++) ia.pair_slots[i] = c->pair_slots[i];
-  // The coarsest levels — those a single block evaluates — run to their end in one launch (k_coarse), at least one finer level
-  // left for k_iterate.
+  ia.inline_pairs = opt.inline_pairs ? 1 : 0;
+  for (int i = 0; i < 4; i++) ia.pair_slots[i] = opt.pair_slots[i];
+  // robust weights: the per-pair residual histograms (and the ticket word of each) start an alignment all-zero; every scale
+  // pass leaves them so
+  if (robust) HIPCHK(c, hipMemsetAsync(c->hist, 0, sizeof(unsigned int) * kHistBins * n_pairs, c->stream));
+  // The coarsest levels — those a single block evaluates — run to their end in one launch, at least one finer level left for
+  // the chained launches.
   int start_lvl = p.first_level;
   bool after_coarse = false;
-  {
+  CoarseArgs ca;
+  std::memset(&ca, 0, sizeof(ca));
+  ca.u = ia.u;
+  ca.state_out = states[sp ^ 1];     // where the first chained launch looks for its state
+  ca.scale_t = ia.scale_t;
+  ca.initial_error = ia.initial_error;
+  ca.inline_pairs = ia.inline_pairs;
+  for (int i = 0; i < 4; i++) ca.pair_slots[i] = ia.pair_slots[i];
+  if (!robust) {   // identity weights: up to kCoarseMaxLevels levels in one k_coarse launch
     int nc = 0;
     while (nc < kCoarseMaxLevels && start_lvl - nc > p.last_level && c->lv[start_lvl - nc].ng <= kCoarseMaxPixels) nc++;
     if (nc > 0 && c->tn.coarse && !c->profiling && !c->compute_only) {
-      CoarseArgs ca;
-      std::memset(&ca, 0, sizeof(ca));
       for (int i = 0; i < nc; i++) {
         const int lvl = p.first_level - i;
         if (level_ready && lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(c->stream, level_ready[lvl], 0));  // its gradients
@@ -566,33 +633,34 @@ int enqueue_estimate_chained(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* 
         ca.level_id[i] = lvl;
       }
       ca.n_levels = nc;
-      ca.u = ia.u;
-      ca.state_out = states[sp ^ 1];     // where the first k_iterate launch looks for its state
-      ca.scale_t = ia.scale_t;
-      ca.initial_error = ia.initial_error;
-      ca.inline_pairs = ia.inline_pairs;
-      for (int i = 0; i < 4; i++) ca.pair_slots[i] = ia.pair_slots[i];
       uwt::launch_coarse_chain(c->stream, launch_sel(c), ca, n_pairs);
       HIPCHK(c, hipGetLastError());
-      start_lvl = p.first_level - nc;
+      start_lvl -= nc;
+      after_coarse = true;
+    }
+  } else {   // robust weights over the nearest sampler: one k_coarse_weighted launch per level
+    while (c->tn.coarse_weighted && p.sampler == 0 && start_lvl > p.last_level && c->lv[start_lvl].ng <= kCoarseMaxPixels) {
+      if (level_ready && start_lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(c->stream, level_ready[start_lvl], 0));  // its gradients
+      ca.lv[0] = residual_args(c, start_lvl);
+      ca.lv[0].state = nullptr;
+      ca.level_id[0] = start_lvl;
+      ca.n_levels = 1;
+      ca.resume = after_coarse ? 1 : 0;
+      uwt::launch_coarse_level(c->stream, launch_sel(c), ca, n_pairs, p.weights);
+      HIPCHK(c, hipGetLastError());
+      start_lvl--;
       after_coarse = true;
     }
   }
+  bool first = true;
+  int prev_slices = 0, prev_k = 0, prev_lvl = p.first_level;
   for (int lvl = start_lvl; lvl >= p.last_level; lvl--) {
     if (level_ready && lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(c->stream, level_ready[lvl], 0));  // its gradients
     ResidualArgs ra = residual_args(c, lvl);
     ra.state = nullptr;
-    {  // slicing follows the batch, as in enqueue_estimate
-      const int n_groups = c->lv[lvl].ng / c->vecl[lvl];
-      int want = ((c->tn.target_blocks ? c->tn.target_blocks : 4096) + n_pairs - 1) / n_pairs;
-      want = std::max(1, std::min(want, c->slices[lvl]));
-      const int gpt = (n_groups + want * kBlock - 1) / (want * kBlock);
-      ra.groups_per_block = gpt * kBlock;
-      ra.slices = (n_groups + ra.groups_per_block - 1) / ra.groups_per_block;
-    }
+    level_slicing(c, lvl, n_pairs, c->tn.target_blocks ? c->tn.target_blocks : 4096, false, ra.groups_per_block, ra.slices);
     int next_poll = c->tn.first_poll;   // see enqueue_estimate
-    int k = 0;
-    for (; k < (speculate ? spec_iters : p.max_iters); k++) {
+    for (int k = 0; k < evals; k++) {
       ia.mode = first ? (after_coarse ? 3 : 0) : (k == 0 ? 2 : 1);
       ia.u.partials = recs[rp ^ 1];
       ia.u.slices = prev_slices;
@@ -601,22 +669,29 @@ int enqueue_estimate_chained(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* 
       ia.state_in = states[sp ^ 1];
       ia.state_out = states[sp];
       ra.partials = recs[rp];
+      if (robust) ra.state = states[sp];   // the weighted launch reads the state the scale pass has just published
       // the update inside launch k belongs to evaluation k - 1: a poll at launch k sees what the separate-kernel flow saw
       // after its update k - 1
       const bool poll = p.early_exit && !speculate && k == next_poll && k < p.max_iters;
       ia.u.active = poll ? c->d_active : nullptr;
-      if (poll) HIPCHK(c, hipMemsetAsync(c->d_active, 0, sizeof(int), c->stream));
+      int st = poll ? poll_arm(c) : UWT_OK;
+      if (st) return st;
       size_t ev = 0;
-      if (c->profiling) {
-        int st = prof_begin(c, &ev, lvl);
+      if (c->profiling) {   // (identity weights: the robust form is not taken in a profiled call)
+        st = prof_begin(c, &ev, lvl);
         if (st) return st;
         ra.probe = 1;
         c->prof_slices = ra.slices;
         c->prof_pairs = n_pairs;
         c->prof_records = recs[rp];
       }
-      int st = launch_iterate(c, ra, ia, n_pairs);
-      if (st) return st;
+      if (robust) {
+        uwt::launch_hist_iterate(c->stream, launch_sel(c), ra, ia, n_pairs, p.sampler, p.weights, c->hist, c->scale);
+        uwt::launch_weighted(c->stream, launch_sel(c), ra, n_pairs, p.sampler, p.weights);
+      } else {
+        uwt::launch_iterate(c->stream, launch_sel(c), ra, ia, n_pairs);
+      }
+      HIPCHK(c, hipGetLastError());
       if (c->profiling) {
         HIPCHK(c, hipEventRecord(c->ev_pool[ev + 1], c->stream));
         c->prof_launches += 1;
@@ -628,10 +703,11 @@ int enqueue_estimate_chained(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* 
       prev_lvl = lvl;
       rp ^= 1;
       sp ^= 1;
-      if (poll) {  // reference-mode early exit: stop launching once every pair has left this level
-        HIPCHK(c, hipMemcpyAsync(c->h_active, c->d_active, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (*c->h_active == 0) { k++; break; }
+      if (poll) {  // stop launching once every pair has left this level
+        bool left = true;
+        st = poll_any_left(c, &left);
+        if (st) return st;
+        if (!left) break;
         next_poll *= 2;
       }
     }
@@ -653,151 +729,24 @@ int enqueue_estimate_chained(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* 
 }
 
 // Tracker::EstimatePose for a batch, enqueued on the context's stream (src/Tracker.cpp:362-597)
-// The chained flow pays where an alignment is bound by kernel boundaries and dependent round trips, not by arithmetic: a
-// few pairs on their own (the drop-in call).  In a batch every block would repeat its pair's update.  Measured at 640x480
-// (round 2, profiles/r03/DESIGN_lab_notes_r01-r03.md): ahead up to 6 pairs in fixed schedules, up to 16 in early-exit schedules
-// (half the launches between two read-backs), level from there on (uwt_tuning::chained = 1 / 0 force it on / off).
-static bool takes_chained_flow(const uwt_ctx* c, int n_pairs) {
-  const int few = c->p.early_exit ? 16 : 6;
-  return c->p.accumulate_f64 != 0 && c->p.sampler == 0 && c->p.weights == 0 && (c->tn.chained > 0 || (c->tn.chained < 0 && n_pairs <= few));
-}
-
-// The chained flow under robust weights (round 6): a few pairs per call — the drop-in use with the Tukey / Huber weighting on.  An
-// evaluation is two launches instead of three (scale pass, weighted sums, update): the update of evaluation k — and the level
-// hand-off where a level ends — runs at the head of evaluation k + 1's scale pass (k_hist_iterate), the last one in k_finish.
-// 640 x 480, one pair, 4 x 10: 91 launches -> 61.  Same device functions as the launches it replaces: the same poses bit for bit.
-static bool takes_chained_general(const uwt_ctx* c, int n_pairs) {
-  return c->p.accumulate_f64 != 0 && c->p.weights != 0 && !c->profiling && !c->compute_only &&
-         (c->tn.chained > 0 || (c->tn.chained < 0 && n_pairs <= 4));
-}
-
-int enqueue_estimate_chained_general(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats, const hipEvent_t* level_ready) {
+int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats, const hipEvent_t* level_ready = nullptr,
+                     const CallOpts& opt = CallOpts()) {
   const uwt_params& p = c->p;
-  uint32_t* recs[2] = {c->partials, c->partials2};
-  PairState* states[2] = {c->state, c->state2};
-  int rp = 0, sp = 0;            // parity of the records / states the NEXT evaluation writes
-  IterArgs ia;
-  std::memset(&ia, 0, sizeof(ia));
-  ia.u.max_iters = p.max_iters;
-  ia.u.early_exit = p.early_exit;
-  ia.u.epsilon = p.epsilon;
-  ia.u.gain = p.gain;
-  ia.u.general = 1;
-  ia.u.legacy_solve = p.arith == UWT_ARITH_LEGACY ? 1 : 0;
-  ia.scale_t = p.handoff_scale_t;
-  ia.initial_error = p.initial_error;
-  // the per-pair residual histograms (and the ticket word of each) start an alignment all-zero; every scale pass leaves them so
-  HIPCHK(c, hipMemsetAsync(c->hist, 0, sizeof(unsigned int) * kHistBins * n_pairs, c->stream));
-  bool first = true, after_coarse = false;
-  int prev_slices = 0, prev_k = 0, prev_lvl = p.first_level;
-  int start_lvl = p.first_level;
-  // the coarsest levels a single block evaluates, each to its end in one launch (k_coarse_weighted), one finer level at least
-  // left for the chained launches
-  while (c->tn.coarse_weighted && p.sampler == 0 && start_lvl > p.last_level && c->lv[start_lvl].ng <= kCoarseMaxPixels) {
-    if (level_ready && start_lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(c->stream, level_ready[start_lvl], 0));  // its gradients
-    CoarseArgs ca;
-    std::memset(&ca, 0, sizeof(ca));
-    ca.lv[0] = residual_args(c, start_lvl);
-    ca.lv[0].state = nullptr;
-    ca.level_id[0] = start_lvl;
-    ca.n_levels = 1;
-    ca.u = ia.u;
-    ca.state_out = states[sp ^ 1];     // where the first k_hist_iterate launch looks for its state
-    ca.scale_t = ia.scale_t;
-    ca.initial_error = ia.initial_error;
-    ca.resume = after_coarse ? 1 : 0;
-    uwt::launch_coarse_level(c->stream, launch_sel(c), ca, n_pairs, p.weights);
-    HIPCHK(c, hipGetLastError());
-    start_lvl--;
-    after_coarse = true;
-  }
-  for (int lvl = start_lvl; lvl >= p.last_level; lvl--) {
-    if (level_ready && lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(c->stream, level_ready[lvl], 0));  // its gradients
-    ResidualArgs ra = residual_args(c, lvl);
-    {  // slicing follows the batch, as in enqueue_estimate
-      const int n_groups = c->lv[lvl].ng / c->vecl[lvl];
-      int want = ((c->tn.target_blocks ? c->tn.target_blocks : 4096) + n_pairs - 1) / n_pairs;
-      want = std::max(1, std::min(want, c->slices[lvl]));
-      const int gpt = (n_groups + want * kBlock - 1) / (want * kBlock);
-      ra.groups_per_block = gpt * kBlock;
-      ra.slices = (n_groups + ra.groups_per_block - 1) / ra.groups_per_block;
-    }
-    int next_poll = c->tn.first_poll;
-    for (int k = 0; k < p.max_iters; k++) {
-      ia.mode = first ? (after_coarse ? 3 : 0) : (k == 0 ? 2 : 1);
-      ia.u.partials = recs[rp ^ 1];
-      ia.u.slices = prev_slices;
-      ia.u.k = prev_k;
-      ia.prev_lvl = prev_lvl;
-      ia.state_in = states[sp ^ 1];
-      ia.state_out = states[sp];
-      ra.partials = recs[rp];
-      ra.state = states[sp];           // the weighted launch reads the state the scale pass has just published
-      // the update inside launch k belongs to evaluation k - 1 (see enqueue_estimate_chained)
-      const bool poll = p.early_exit && k == next_poll && k < p.max_iters;
-      ia.u.active = poll ? c->d_active : nullptr;
-      if (poll) HIPCHK(c, hipMemsetAsync(c->d_active, 0, sizeof(int), c->stream));
-      uwt::launch_hist_iterate(c->stream, launch_sel(c), ra, ia, n_pairs, p.sampler, p.weights, c->hist, c->scale);
-      uwt::launch_weighted(c->stream, launch_sel(c), ra, n_pairs, p.sampler, p.weights);
-      HIPCHK(c, hipGetLastError());
-      first = false;
-      prev_slices = ra.slices;
-      prev_k = k;
-      prev_lvl = lvl;
-      rp ^= 1;
-      sp ^= 1;
-      if (poll) {  // reference-mode early exit: stop launching once every pair has left this level
-        HIPCHK(c, hipMemcpyAsync(c->h_active, c->d_active, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (*c->h_active == 0) break;
-        next_poll *= 2;
-      }
-    }
-  }
-  // the last evaluation's update, the last level's hand-off, results
-  ia.mode = 2;
-  ia.u.partials = recs[rp ^ 1];
-  ia.u.slices = prev_slices;
-  ia.u.k = prev_k;
-  ia.u.active = nullptr;
-  ia.prev_lvl = prev_lvl;
-  ia.state_in = states[sp ^ 1];
-  ia.state_out = ia.state_in == c->state ? c->state2 : c->state;
-  uwt::launch_finish(c->stream, ia, n_pairs, d_poses, d_stats);
-  HIPCHK(c, hipGetLastError());
-  return UWT_OK;
-}
-
-int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats, const hipEvent_t* level_ready = nullptr) {
-  const uwt_params& p = c->p;
-  if (takes_chained_flow(c, n_pairs)) return enqueue_estimate_chained(c, n_pairs, d_poses, d_stats, level_ready);
-  if (takes_chained_general(c, n_pairs)) return enqueue_estimate_chained_general(c, n_pairs, d_poses, d_stats, level_ready);
+  const Chained form = chained_form(c, n_pairs);
+  if (form != Chained::none)
+    return enqueue_estimate_chained(c, form == Chained::robust, n_pairs, d_poses, d_stats, level_ready, opt);
   const int tb = 128;
   const bool general = p.sampler != 0 || p.weights != 0;
-  // Slicing follows the batch: the create-time slicing (kGroupsPerThread) gives a single pair enough blocks to spread
-  // over the chip; a batch that fills it alone runs fewer, longer blocks (less reduction overhead per pixel, fewer
-  // records to fold), still at least target_blocks per launch.
-  // (early-exit schedules stay on one stream: interleaving the two halves' read-backs was built and gave +1.7 %)
+  // A batch is cut into parts that run the same schedule on streams of their own (fixed schedules; 16 pairs and the pixels of
+  // 32 640x480 pairs or more): the launches of one part run in the gaps of the other's — the tail of a residual launch, the
+  // update launch, the kernel boundaries: +2..4 % at 256..1024 pairs, +7..9 % at 32..64 in a pipeline of calls; three parts gain
+  // nothing more, four lose (measured).  Results do not depend on it (a pair's blocks, records and state are its own; the
+  // slicing is the whole batch's).  Part 0 runs on the context's stream.
+  // (early-exit schedules stay on one stream: interleaving the two halves' read-backs was built and gave +1.7 %; so do profiled
+  // calls: the read-backs and the events around launches exist with one part only)
   const int parts = (p.early_exit || c->profiling || (long long)n_pairs * c->lv[0].ng < c->tn.split_min_px)
-                        ? 1 : std::min(c->tn.split, n_pairs / std::max(1, c->tn.split_min));
+                        ? 1 : std::max(1, std::min(c->tn.split, n_pairs / std::max(1, c->tn.split_min)));
   const int target_blocks = c->tn.target_blocks ? c->tn.target_blocks : (parts >= 2 ? 1024 : 4096);
-  auto slicing = [&](int lvl, int& groups_per_block, int& slices) {
-    const int n_groups = c->lv[lvl].ng / c->vecl[lvl];
-    int want = (target_blocks + n_pairs - 1) / n_pairs;
-    want = std::max(1, std::min(want, c->slices[lvl]));
-    // Fixed schedules (every pair stays to the level's end): a block should also be long enough to carry its fixed costs — the
-    // matrix set-up, the two-pass LDS fold, the record, the ticket — i.e. 16 groups per thread, as long as the launch still fills
-    // the chip once (1024 resident blocks).  Level 2 of a 1024-pair batch: 1 slice of 19 groups per thread instead of 4 of 5,
-    // +4.6 % on that level's launches.  Early-exit schedules keep the finer slicing: pairs leave a level at different
-    // evaluations and the blocks of those that stay have to fill the chip (coarser: 437 k -> 314 k alignments/s, measured).
-    if (!p.early_exit) {
-      const int by_work = std::max(1, n_groups / (kBlock * 16));
-      want = std::min(want, std::max(by_work, (1024 + n_pairs - 1) / n_pairs));
-    }
-    const int gpt = (n_groups + want * kBlock - 1) / (want * kBlock);
-    groups_per_block = gpt * kBlock;
-    slices = (n_groups + groups_per_block - 1) / groups_per_block;
-  };
   // the accumulation kernels stream a level's reference planes past the caches (ResidualArgs::stream_planes) when the batch's
   // planes of that level — u8 + 2 x i16 [+ u16] per reference pixel, the target's u8 — exceed what the 256 MB memory-side cache
   // holds across an evaluation; a smaller batch finds them there again at the next evaluation (uwt_tuning::stream_bytes)
@@ -807,7 +756,7 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
   int smax = 1;
   for (int lvl = p.first_level; lvl >= p.last_level; lvl--) {
     int gpb, sl;
-    slicing(lvl, gpb, sl);
+    level_slicing(c, lvl, n_pairs, target_blocks, !p.early_exit, gpb, sl);
     smax = std::max(smax, sl);
   }
   // robust weights: the per-pair residual histograms (and the ticket word of each) start an alignment all-zero; every scale
@@ -854,148 +803,49 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
     }
     return UWT_OK;
   };
-  // the schedule for pairs [base, base + cnt) of a batch of n_pairs, on c->stream
-  auto run = [&](int base, int cnt) -> int {
-    if (!coarse_lvl[p.first_level]) {
-      hipLaunchKernelGGL(k_init_state, dim3((cnt + tb - 1) / tb), dim3(tb), 0, c->stream, c->state + base, cnt, p.initial_error);
-      HIPCHK(c, hipGetLastError());
-    }
-    for (int lvl = p.first_level; lvl >= p.last_level; lvl--) {
-      if (level_ready && lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(c->stream, level_ready[lvl], 0));  // its gradients
-      if (coarse_lvl[lvl]) {
-        int stc = run_coarse(base, cnt, c->stream, lvl, lvl != p.first_level);
-        if (stc) return stc;
-        continue;
-      }
-      ResidualArgs ra = residual_args(c, lvl);
-      UpdateArgs ua = update_args(c, lvl);
-      ra.pair_base = base;
-      ua.pair_base = base;
-      ra.stream_planes = streams(lvl);
-      slicing(lvl, ra.groups_per_block, ra.slices);
-      ua.slices = ra.slices;
-      // A pair's records sit at (pair * slices + slice): the place depends on the level's slice count, and the parts of a
-      // split batch are at different levels at times.  Part `base` is shifted so that its records start at base * smax
-      // whatever the level — behind everything the parts before it can touch, inside the buffer (slices <= smax).
-      const size_t shift = (size_t)base * (size_t)(smax - ra.slices) * kRecWords;
-      ra.partials = c->partials + shift;
-      ua.partials = c->partials + shift;
-      // Early exit: the host reads back how many pairs are still iterating after the update of evaluation first_poll - 1,
-      // then after twice as many, ...  With the reference's constants a level ends at its third evaluation as a rule
-      // (error rises or stalls, src/Tracker.cpp:508), so the first look comes after three (uwt_tuning::first_poll).
-      // The read-back is taken one evaluation late (round 3): the count of evaluation k is copied to page-locked memory
-      // behind its update, evaluation k + 1 is enqueued, and only then does the host wait for the copy — the GPU works on
-      // k + 1 meanwhile instead of idling for the host's round trip (~25 us per look).  When the count says "nobody left",
-      // evaluation k + 1 has been enqueued for nothing: its blocks see level_done and return at once (a few us).
-      int next_poll = c->tn.first_poll;
-      int pending = -1;   // slot of the look not yet taken
-      for (int k = 0; k < p.max_iters; k++) {
-        size_t ev = 0;
-        if (c->profiling) {
-          int st = prof_begin(c, &ev, lvl);
-          if (st) return st;
-          ra.probe = 1;
-          c->prof_slices = ra.slices;
-          c->prof_pairs = cnt;
-          c->prof_records = c->partials;
-        }
-        if (general) ua.general = 1;
-        ua.k = k;
-        const bool poll = p.early_exit && (k + 1 == next_poll) && (k + 1 < p.max_iters);
-        const int slot = c->poll_seq & 1;
-        ua.active = poll ? c->d_active + slot : nullptr;
-        if (poll) HIPCHK(c, hipMemsetAsync(c->d_active + slot, 0, sizeof(int), c->stream));
-        const bool tail = c->tn.tail_update >= 2 && !c->compute_only;   // (one stream: only when forced, see tail_update)
-        if (tail) arm_tail(c, ra, ua);
-        int st = general ? launch_general(c, ra, cnt) : launch_residual(c, ra, cnt, false);
-        if (st) return st;
-        if (c->profiling) {
-          HIPCHK(c, hipEventRecord(c->ev_pool[ev + 1], c->stream));
-          c->prof_launches += 1;
-          c->prof_pixels += (long long)cnt * c->lv[lvl].gw * c->lv[lvl].gh;
-        }
-        if (!tail) {
-          hipLaunchKernelGGL(k_gn_update, dim3(cnt), dim3(kUpdateBlock), 0, c->stream, ua);
-          HIPCHK(c, hipGetLastError());
-        }
-        if (pending >= 0) {   // the look at the evaluation before this one, taken while this one runs
-          HIPCHK(c, hipEventSynchronize(c->ev_poll[pending]));
-          const bool nobody_left = c->h_active[pending] == 0;
-          pending = -1;
-          if (nobody_left) break;   // reference-mode early exit: every pair has left this level
-        }
-        if (poll) {
-          HIPCHK(c, hipMemcpyAsync(c->h_active + slot, c->d_active + slot, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-          HIPCHK(c, hipEventRecord(c->ev_poll[slot], c->stream));
-          pending = slot;
-          c->poll_seq++;
-          next_poll *= 2;
-        }
-      }
-      hipLaunchKernelGGL(k_level_end, dim3((cnt + tb - 1) / tb), dim3(tb), 0, c->stream, c->state + base, cnt, lvl,
-                         p.handoff_scale_t, p.initial_error);
-      HIPCHK(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_write_out, dim3((cnt + tb - 1) / tb), dim3(tb), 0, c->stream, c->state + base, cnt, d_poses + 7 * (size_t)base,
-                       d_stats ? d_stats + base : nullptr);
-    HIPCHK(c, hipGetLastError());
-    return UWT_OK;
-  };
-  // A batch is cut into two parts that run the same schedule on streams of their own (fixed schedules; 16 pairs and the
-  // pixels of 32 640x480 pairs or more): the launches of one part run in the gaps of the other's — the tail of a residual
-  // launch, the update launch, the kernel boundaries: +2..4 % at 256..1024 pairs, +7..9 % at 32..64 in a pipeline of calls;
-  // three parts gain nothing more, four lose (measured).  Results do not depend on it (a pair's blocks, records and state
-  // are its own; the slicing is the whole batch's).
-  if (parts < 2) {
-    if (c->tn.tail_update >= 2) HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
-    return run(0, n_pairs);
-  }
-  // (fixed schedule, not profiled: no read-backs, no events around launches).  The parts' launches are enqueued in turns,
-  // iteration by iteration, so that both streams have work from the start.
+  // tn.tail_update: the update in the tail of the evaluation's launch where the batch runs as parts, on one stream only when
+  // forced (see tail_update).  The pairs' ticket counters are zero between launches by construction; a call that an error
+  // cut short may have left some.
+  const bool tickets = c->tn.tail_update >= (parts > 1 ? 1 : 2);
+  const bool tail = tickets && !c->compute_only;
+  if (tickets) HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
   struct Part { int base, cnt; hipStream_t s; ResidualArgs ra; UpdateArgs ua; };
   Part pt[uwt_ctx::kMaxParts];
-  hipStream_t main_stream = c->stream;
   // every early return below (a failed launch or event call) leaves part streams forked and not joined: drain them before
-  // the error reaches the caller, so that uwt_sync / uwt_destroy on the main stream really mean "nothing is running"
+  // the error reaches the caller, so that uwt_sync / uwt_destroy on the context stream really mean "nothing is running"
   struct JoinGuard {
-    uwt_ctx* c; int parts; hipStream_t main; bool joined = false;
+    uwt_ctx* c; int parts; bool joined = false;
     ~JoinGuard() {
       if (joined) return;
-      c->stream = main;
       for (int i = 1; i < parts; i++) (void)hipStreamSynchronize(c->part_stream[i]);
     }
-  } guard{c, parts, main_stream};
-  // (the pairs' ticket counters are zero between launches by construction; a call that an error cut short may have left some)
-  if (c->tn.tail_update >= 1) HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, main_stream));
-  HIPCHK(c, hipEventRecord(c->ev_fork, main_stream));
+  } guard{c, parts};
+  if (parts > 1) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
   for (int i = 0; i < parts; i++) {
     Part& q = pt[i];
     q.base = (int)((long long)n_pairs * i / parts);
     q.cnt = (int)((long long)n_pairs * (i + 1) / parts) - q.base;
-    q.s = i ? c->part_stream[i] : main_stream;
+    q.s = i ? c->part_stream[i] : c->stream;
     if (i) HIPCHK(c, hipStreamWaitEvent(q.s, c->ev_fork, 0));
-    if (!coarse_lvl[p.first_level])
+    if (!coarse_lvl[p.first_level]) {
       hipLaunchKernelGGL(k_init_state, dim3((q.cnt + tb - 1) / tb), dim3(tb), 0, q.s, c->state + q.base, q.cnt, p.initial_error);
-  }
-  HIPCHK(c, hipGetLastError());
-  int st = UWT_OK;
-  for (int lvl = p.first_level; lvl >= p.last_level && st == UWT_OK; lvl--) {
-    if (coarse_lvl[lvl]) {
-      for (int i = 0; i < parts; i++) {
-        if (level_ready && lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(pt[i].s, level_ready[lvl], 0));  // its gradients
-        int stc = run_coarse(pt[i].base, pt[i].cnt, pt[i].s, lvl, lvl != p.first_level);
-        if (stc) return stc;
-      }
-      continue;
+      HIPCHK(c, hipGetLastError());
     }
+  }
+  for (int lvl = p.first_level; lvl >= p.last_level; lvl--) {
     for (int i = 0; i < parts; i++) {
       Part& q = pt[i];
       if (level_ready && lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(q.s, level_ready[lvl], 0));  // its gradients
+      if (coarse_lvl[lvl]) {
+        int st = run_coarse(q.base, q.cnt, q.s, lvl, lvl != p.first_level);
+        if (st) return st;
+        continue;
+      }
       q.ra = residual_args(c, lvl);
       q.ua = update_args(c, lvl);
       q.ra.pair_base = q.ua.pair_base = q.base;
       q.ra.stream_planes = streams(lvl);
-      slicing(lvl, q.ra.groups_per_block, q.ra.slices);
+      level_slicing(c, lvl, n_pairs, target_blocks, !p.early_exit, q.ra.groups_per_block, q.ra.slices);
       q.ua.slices = q.ra.slices;
       // A pair's records sit at (pair * slices + slice): the place depends on the level's slice count, and the parts are at
       // different levels at times.  A part's records are shifted so that they start at base * smax whatever the level —
@@ -1005,34 +855,76 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
       q.ua.partials = c->partials + shift;
       if (general) q.ua.general = 1;
     }
-    for (int k = 0; k < p.max_iters && st == UWT_OK; k++)
-      for (int i = 0; i < parts && st == UWT_OK; i++) {
+    if (coarse_lvl[lvl]) continue;
+    // Early exit (one part): the host reads back how many pairs are still iterating after the update of evaluation
+    // first_poll - 1, then after twice as many, ...  With the reference's constants a level ends at its third evaluation as a
+    // rule (error rises or stalls, src/Tracker.cpp:508), so the first look comes after three (uwt_tuning::first_poll).
+    // The read-back is taken one evaluation late (round 3): the count of evaluation k is copied to page-locked memory
+    // behind its update, evaluation k + 1 is enqueued, and only then does the host wait for the copy — the GPU works on
+    // k + 1 meanwhile instead of idling for the host's round trip (~25 us per look).  When the count says "nobody left",
+    // evaluation k + 1 has been enqueued for nothing: its blocks see level_done and return at once (a few us).
+    // Several parts: their launches are enqueued in turns, evaluation by evaluation, so that every stream has work from the start.
+    int next_poll = c->tn.first_poll;
+    int pending = -1;   // slot of the look not yet taken
+    bool level_done = false;
+    for (int k = 0; k < p.max_iters && !level_done; k++)
+      for (int i = 0; i < parts; i++) {
         Part& q = pt[i];
+        size_t ev = 0;
+        if (c->profiling) {   // (one part)
+          int st = prof_begin(c, &ev, lvl);
+          if (st) return st;
+          q.ra.probe = 1;
+          c->prof_slices = q.ra.slices;
+          c->prof_pairs = q.cnt;
+          c->prof_records = c->partials;
+        }
         q.ua.k = k;
-        q.ua.active = nullptr;
-        const bool tail = c->tn.tail_update >= 1 && !c->compute_only;   // the update in the tail of the evaluation's launch
+        const bool poll = p.early_exit && (k + 1 == next_poll) && (k + 1 < p.max_iters);   // (one part)
+        const int slot = c->poll_seq & 1;
+        q.ua.active = poll ? c->d_active + slot : nullptr;
+        if (poll) HIPCHK(c, hipMemsetAsync(c->d_active + slot, 0, sizeof(int), q.s));
         if (tail) arm_tail(c, q.ra, q.ua);
-        c->stream = q.s;      // every launch helper enqueues on c->stream
-        st = general ? launch_general(c, q.ra, q.cnt) : launch_residual(c, q.ra, q.cnt, false);
-        c->stream = main_stream;
-        if (st) break;
-        if (!tail) hipLaunchKernelGGL(k_gn_update, dim3(q.cnt), dim3(kUpdateBlock), 0, q.s, q.ua);
+        int st = general ? launch_general(c, q.s, q.ra, q.cnt) : launch_residual(c, q.s, q.ra, q.cnt, false);
+        if (st) return st;
+        if (c->profiling) {
+          HIPCHK(c, hipEventRecord(c->ev_pool[ev + 1], q.s));
+          c->prof_launches += 1;
+          c->prof_pixels += (long long)q.cnt * c->lv[lvl].gw * c->lv[lvl].gh;
+        }
+        if (!tail) {
+          hipLaunchKernelGGL(k_gn_update, dim3(q.cnt), dim3(kUpdateBlock), 0, q.s, q.ua);
+          HIPCHK(c, hipGetLastError());
+        }
+        if (pending >= 0) {   // the look at the evaluation before this one, taken while this one runs
+          HIPCHK(c, hipEventSynchronize(c->ev_poll[pending]));
+          level_done = c->h_active[pending] == 0;   // reference-mode early exit: every pair has left this level
+          pending = -1;
+          if (level_done) break;
+        }
+        if (poll) {
+          HIPCHK(c, hipMemcpyAsync(c->h_active + slot, c->d_active + slot, sizeof(int), hipMemcpyDeviceToHost, q.s));
+          HIPCHK(c, hipEventRecord(c->ev_poll[slot], q.s));
+          pending = slot;
+          c->poll_seq++;
+          next_poll *= 2;
+        }
       }
-    if (st) return st;
-    for (int i = 0; i < parts; i++)
+    for (int i = 0; i < parts; i++) {
       hipLaunchKernelGGL(k_level_end, dim3((pt[i].cnt + tb - 1) / tb), dim3(tb), 0, pt[i].s, c->state + pt[i].base, pt[i].cnt, lvl,
                          p.handoff_scale_t, p.initial_error);
-    HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipGetLastError());
+    }
   }
   for (int i = 0; i < parts; i++) {
     hipLaunchKernelGGL(k_write_out, dim3((pt[i].cnt + tb - 1) / tb), dim3(tb), 0, pt[i].s, c->state + pt[i].base, pt[i].cnt,
                        d_poses + 7 * (size_t)pt[i].base, d_stats ? d_stats + pt[i].base : nullptr);
+    HIPCHK(c, hipGetLastError());
     if (i) {
       HIPCHK(c, hipEventRecord(c->ev_join[i], pt[i].s));
-      HIPCHK(c, hipStreamWaitEvent(main_stream, c->ev_join[i], 0));
+      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[i], 0));
     }
   }
-  HIPCHK(c, hipGetLastError());
   guard.joined = true;
   return UWT_OK;
 }
@@ -1588,22 +1480,22 @@ int uwt_estimate_pose_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slot
   if (!ref_slots || !tgt_slots || n_pairs < 1) return fail(c, UWT_ERR_INVALID_ARG, "null pair lists or n_pairs < 1");
   if (n_pairs > c->p.max_pairs) return fail(c, UWT_ERR_CAPACITY, "n_pairs exceeds max_pairs");
   int st;
-  c->inline_pairs = n_pairs <= 2 && takes_chained_flow(c, n_pairs);
-  if (c->inline_pairs) {   // the slots travel in the kernel arguments
+  const bool chained = chained_form(c, n_pairs) == Chained::identity;
+  CallOpts opt;
+  opt.inline_pairs = n_pairs <= 2 && chained;
+  if (opt.inline_pairs) {   // the slots travel in the kernel arguments
     for (int i = 0; i < n_pairs; i++) {
-      if (ref_slots[i] < 0 || ref_slots[i] >= c->p.max_frames || tgt_slots[i] < 0 || tgt_slots[i] >= c->p.max_frames) {
-        c->inline_pairs = false;
+      if (ref_slots[i] < 0 || ref_slots[i] >= c->p.max_frames || tgt_slots[i] < 0 || tgt_slots[i] >= c->p.max_frames)
         return fail(c, UWT_ERR_INVALID_ARG, "pair slot out of range");
-      }
-      c->pair_slots[2 * i] = ref_slots[i];
-      c->pair_slots[2 * i + 1] = tgt_slots[i];
+      opt.pair_slots[2 * i] = ref_slots[i];
+      opt.pair_slots[2 * i + 1] = tgt_slots[i];
     }
   } else {
     st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
     if (st) return st;
   }
   st = compute_begin(c, 0, c->p.max_frames);
-  if (st) { c->inline_pairs = false; return st; }
+  if (st) return st;
   std::vector<uwt_stats> tmp(n_pairs);
   // A small batch has its results written by the last kernel straight into page-locked host memory: nothing to copy back.
   const bool small = n_pairs <= uwt_ctx::kSmallBatch;
@@ -1612,10 +1504,10 @@ int uwt_estimate_pose_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slot
   // inside the alignment, one look at the "cut short" flag behind the results.  If it is set the alignment is run again with
   // twice the evaluations per level (the budget stays: the next frames of a sequence tend to need what this one needed; it
   // comes down again after kSpecCalm calls that were not cut), and the careful way — read-backs — if that is cut short too.
-  c->speculate = n_pairs <= 2 && c->p.early_exit && !c->profiling && takes_chained_flow(c, n_pairs) && c->tn.speculation;
+  opt.speculate = n_pairs <= 2 && c->p.early_exit && !c->profiling && chained && c->tn.speculation;
   for (int attempt = 0; attempt < 3; attempt++) {
-    st = enqueue_estimate(c, n_pairs, small ? c->d_small->poses : c->d_poses, small ? c->d_small->stats : c->d_stats);
-    if (st) { c->speculate = false; c->inline_pairs = false; return st; }
+    st = enqueue_estimate(c, n_pairs, small ? c->d_small->poses : c->d_poses, small ? c->d_small->stats : c->d_stats, nullptr, opt);
+    if (st) return st;
     if (!small) {
       HIPCHK(c, hipMemcpyAsync(poses_out, c->d_poses, sizeof(float) * 7 * n_pairs, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_stats, sizeof(uwt_stats) * n_pairs, hipMemcpyDeviceToHost, c->stream));
@@ -1625,7 +1517,7 @@ int uwt_estimate_pose_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slot
       std::memcpy(poses_out, c->h_small->poses, sizeof(float) * 7 * n_pairs);
       std::memcpy(tmp.data(), c->h_small->stats, sizeof(uwt_stats) * n_pairs);
     }
-    if (!c->speculate) break;
+    if (!opt.speculate) break;
     const int base = c->tn.first_poll + 1;
     if (c->h_small->cut == 0) {
       if (c->spec_budget > base && ++c->spec_calm >= uwt_ctx::kSpecCalm) { c->spec_budget = std::max(base, c->spec_budget / 2); c->spec_calm = 0; }
@@ -1633,10 +1525,8 @@ int uwt_estimate_pose_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slot
     }
     c->spec_calm = 0;
     c->spec_budget = std::min(c->p.max_iters, 2 * std::max(c->spec_budget, base));
-    if (attempt == 1) c->speculate = false;   // cut short twice: the third run reads back
+    if (attempt == 1) opt.speculate = false;   // cut short twice: the third run reads back
   }
-  c->speculate = false;
-  c->inline_pairs = false;
   if (c->profiling) {
     st = prof_collect(c);
     if (st) return st;
@@ -1657,8 +1547,6 @@ static int track_batch_enqueue(uwt_ctx* c, int32_t first_slot, int32_t n_frames,
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
   if (!c || !d_poses_out || !slot_range_ok(c, first_slot, n_frames))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_track_batch_async: bad argument");
-  c->inline_pairs = false;   // (only the synchronous small call hands slots over in kernel arguments or speculates)
-  c->speculate = false;
   int st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
   if (st) return st;
   // The alignment reads every slot the pair lists name, and with grad_refs_only the reference slots lie "wherever they
@@ -1907,7 +1795,7 @@ int uwt_residual_jacobian(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, int32_
     a.dumpR = a.dumpJ + 6 * n;
     a.dumpV = (uint8_t*)(a.dumpR + n);
   }
-  st = launch_residual(c, a, 1, dump);
+  st = launch_residual(c, c->stream, a, 1, dump);
   if (st) return st;
   std::vector<uint32_t> recs((size_t)a.slices * kRecWords);
   HIPCHK(c, hipMemcpyAsync(recs.data(), c->partials, recs.size() * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2132,13 +2020,15 @@ int uwt_estimate_pose_points(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, con
       ua.k = k;
       const bool poll = p.early_exit && (k + 1 == next_poll) && (k + 1 < p.max_iters);
       ua.active = poll ? c->d_active : nullptr;
-      if (poll) HIPCHK(c, hipMemsetAsync(c->d_active, 0, sizeof(int), c->stream));
+      st = poll ? poll_arm(c) : UWT_OK;
+      if (st) return st;
       hipLaunchKernelGGL(k_gn_update, dim3(1), dim3(kUpdateBlock), 0, c->stream, ua);
       HIPCHK(c, hipGetLastError());
       if (poll) {
-        HIPCHK(c, hipMemcpyAsync(c->h_active, c->d_active, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (*c->h_active == 0) break;
+        bool left = true;
+        st = poll_any_left(c, &left);
+        if (st) return st;
+        if (!left) break;
         next_poll *= 2;
       }
     }
