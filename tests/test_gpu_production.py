@@ -134,8 +134,9 @@ def test_robust_weights_at_640x480_with_depth(capi, O, synth, mode):
 
 
 def test_per_stage_weighted_entry_on_a_level_larger_than_the_record_budget_assumed(capi, O, synth):
-    """1920x1088: the create-time slicing is coarser than the per-stage dump's 8192 pixels per record, so the dump has to
-    follow it (it used to need 255 records where 146 were allocated)."""
+    """1920x1088: a level so large that the create-time slicing gives every record more than the usual share of pixels; the
+    per-stage entry evaluates the level with that slicing, within the records the context allocated (an entry with a finer
+    slicing of its own once needed 255 records where 146 were allocated)."""
     w, h = 1920, 1088
     intr = (1500.0, 1500.0, 959.5, 543.5)
     over = dict(n_levels=1, first_level=0, last_level=0, max_iters=2, early_exit=0, weights=2)

@@ -67,41 +67,45 @@ def capi():
     return m
 
 
-def _setup(capi, synth, w, h, seed, depth=False, outlier=True, **over):
-    ref, tgt, dep, _, _ = synth.render_pair(w, h, *MID, seed=seed, with_depth=depth, z=1.1)
+def _setup(capi, synth, w, h, seed, depth=False, outlier=True, intr=MID, **over):
+    ref, tgt, dep, _, _ = synth.render_pair(w, h, *intr, seed=seed, with_depth=depth, z=1.1)
     tgt = tgt.copy()
     if outlier:
         tgt[20:40, 50:90] = 255
     if depth:
         over["has_depth"] = 1
-    ctx = capi.Context(capi.default_params(w, h, *MID, max_frames=2, max_pairs=1, **over))
+    ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=2, max_pairs=1, **over))
     ctx.upload_frames(0, np.stack([ref, tgt]), np.stack([dep, dep]) if depth else None)
     ctx.build_pyramids(0, 2)
     ctx.apply_gradient(0, 2)
     return ctx, ref, tgt, dep
 
 
+# 160x96 (square pixels): whole groups of four on every level; 155x93: every level's grid rows end inside a group (the
+# ragged mask); fx_ne_fy: 160x96 with fx != fy
+SHAPES = {"": (160, 96, MID), "155x93": (155, 93, (127.5, 127.5, 77.0, 46.0)), "fx_ne_fy": (160, 96, (131.25, 130.5, 79.5, 47.5))}
+WEIGHTED_MODES = ["tukey", "huber", "bilinear", "bilinear_huber", "tukey_depth"]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["tukey", "huber", "bilinear", "bilinear_huber", "tukey_depth"])
-def test_gpu_weighted_terms_bit_exact(capi, O, synth, mode):
-    w, h = 160, 96
+@pytest.mark.parametrize("mode,shape", [pytest.param(m, s, id="-".join(filter(None, (m, s)))) for s in SHAPES for m in WEIGHTED_MODES])
+def test_gpu_weighted_terms_bit_exact(capi, O, synth, mode, shape):
+    w, h, intr = SHAPES[shape]
     over = dict(tukey=dict(weights=1), huber=dict(weights=2), bilinear=dict(sampler=1),
                 bilinear_huber=dict(sampler=1, weights=2), tukey_depth=dict(weights=1))[mode]
     depth = mode.endswith("depth")
-    ctx, ref, tgt, dep = _setup(capi, synth, w, h, 72, depth, **over)
-    p = O.default_params(w, h, *MID, **over)
+    ctx, ref, tgt, dep = _setup(capi, synth, w, h, 72, depth, intr=intr, **over)
+    p = O.default_params(w, h, *intr, **over)
     rng = np.random.default_rng(4)
-    a_img, b_img, dp = ref, tgt, dep
+    a_pyr, b_pyr = O.pyramid(ref, 4), O.pyramid(tgt, 4)
+    d_pyr = O.pyramid(dep, 4) if depth else [None] * 4
     for lvl in range(4):
-        if lvl:
-            a_img, b_img = O.halve_u8(a_img), O.halve_u8(b_img)
-            dp = O.halve_u16(dp) if depth else None
         L = O.level_intrinsics(p, lvl)
-        gx, gy = O.scharr3(a_img)
-        pts = O.dense_points(dp, L.w, L.h, lvl)
+        gx, gy = O.scharr3(a_pyr[lvl])
+        pts = O.dense_points(d_pyr[lvl], L.w, L.h, lvl)
         pose = O.se3_exp((rng.normal(0, 1, 6) * [0.03, 0.03, 0.01, 0.005, 0.005, 0.02]).astype(np.float32))
         wp = O.warp(pts, pose, L)
-        J, r, idx = O.residual_jacobian_ex(a_img, b_img, gx, gy, pts, wp, L, sampler=over.get("sampler", 0))
+        J, r, idx = O.residual_jacobian_ex(a_pyr[lvl], b_pyr[lvl], gx, gy, pts, wp, L, sampler=over.get("sampler", 0))
         wts = {0: None, 1: O.tukey_weights, 2: O.huber_weights}[over.get("weights", 0)]
         W = wts(r) if wts else None
         out = ctx.residual_jacobian_weighted(0, 1, lvl, pose)

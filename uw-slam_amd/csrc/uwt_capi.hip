@@ -444,7 +444,6 @@ GeneralArgs general_args(uwt_ctx* c) {
   GeneralArgs ga;
   ga.sampler = c->p.sampler;
   ga.weights = c->p.weights;
-  ga.stage = 0;
   ga.gain = c->p.gain;
   ga.hist = c->hist;
   ga.scale = c->scale;
@@ -453,28 +452,8 @@ GeneralArgs general_args(uwt_ctx* c) {
 
 // One residual evaluation on the general path (robust weights and/or bilinear sampler): with weights on, one histogram pass
 // estimates the scale first (MedianMat / MedianAbsoluteDeviation, src/Tracker.cpp:1571-1619), then the weighted accumulation runs.
-int launch_general(uwt_ctx* c, hipStream_t s, const ResidualArgs& ra, int n_pairs) {
-  uwt::launch_general(s, launch_sel(c), ra, n_pairs, c->p.sampler, c->p.weights, c->hist, c->scale);
-  HIPCHK(c, hipGetLastError());
-  return UWT_OK;
-}
-
-// The per-stage (dump-capable) form of the same evaluation: k_residual_general, one pixel per thread step.  Records use one
-// pixel per point and 8192 per block.
-int launch_general_dump(uwt_ctx* c, ResidualArgs ra, int n_pairs, int* slices_out = nullptr) {
-  GeneralArgs ga = general_args(c);
-  // pixels per record: 8192, or more where the level's create-time slicing (whose record count sized `partials`) is
-  // coarser than that — very large levels, where init raises the groups per thread to stay under kMaxSlices
-  int lvl = 0;
-  while (lvl + 1 < c->p.n_levels && c->lv[lvl].n != ra.L.n) lvl++;
-  const int per_slice = (ra.L.ng + c->slices[lvl] - 1) / c->slices[lvl];
-  ra.groups_per_block = std::max(kBlock * 32, (per_slice + kBlock - 1) / kBlock * kBlock);
-  ra.slices = (ra.L.ng + ra.groups_per_block - 1) / ra.groups_per_block;
-  if ((size_t)ra.slices * n_pairs > c->partial_records) return fail(c, UWT_ERR_CAPACITY, "per-stage dump needs more partial records than the context holds");
-  if (slices_out) *slices_out = ra.slices;
-  if (ga.weights)
-    HIPCHK(c, hipMemsetAsync(c->hist + (size_t)ra.pair_base * kHistBins, 0, sizeof(unsigned int) * kHistBins * n_pairs, c->stream));
-  uwt::launch_general_dump(c->stream, launch_sel(c), ra, ga, n_pairs);
+int launch_general(uwt_ctx* c, hipStream_t s, const ResidualArgs& ra, int n_pairs, bool dump) {
+  uwt::launch_general(s, launch_sel(c), ra, n_pairs, c->p.sampler, c->p.weights, c->hist, c->scale, dump);
   HIPCHK(c, hipGetLastError());
   return UWT_OK;
 }
@@ -885,7 +864,7 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
         q.ua.active = poll ? c->d_active + slot : nullptr;
         if (poll) HIPCHK(c, hipMemsetAsync(c->d_active + slot, 0, sizeof(int), q.s));
         if (tail) arm_tail(c, q.ra, q.ua);
-        int st = general ? launch_general(c, q.s, q.ra, q.cnt) : launch_residual(c, q.s, q.ra, q.cnt, false);
+        int st = general ? launch_general(c, q.s, q.ra, q.cnt, false) : launch_residual(c, q.s, q.ra, q.cnt, false);
         if (st) return st;
         if (c->profiling) {
           HIPCHK(c, hipEventRecord(c->ev_pool[ev + 1], q.s));
@@ -1772,85 +1751,52 @@ int uwt_warp(uwt_ctx* c, int32_t lvl, const float* pts, int32_t n, const float p
   return UWT_OK;
 }
 
-int uwt_residual_jacobian(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, int32_t lvl, const float pose[7],
-                          uwt_accum* acc_out, float* J_out, float* r_out, uint8_t* valid_out) {
+// The two per-stage residual entries: one evaluation of the production kernel for pair (ref_slot, tgt_slot) at `pose`, with the
+// level's own slicing, its records folded like k_gn_update's.  general: the context's sampler / weights (the scale pass, then the
+// weighted sums' dump form, always taken: its sums do not depend on which dumps are asked for), else the identity path (its
+// dump form when a dump is asked for, the production kernel otherwise).
+static int residual_jacobian_entry(uwt_ctx* c, const char* name, bool general, int32_t ref_slot, int32_t tgt_slot, int32_t lvl,
+                                   const float pose[7], uwt_accum* acc_out, double* err_num_out, float* inv_mad_out, float* J_out,
+                                   float* r_out, uint8_t* valid_out, float* w_out) {
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
   if (!c || !pose || !acc_out || lvl < 0 || lvl >= c->p.n_levels || !slot_range_ok(c, ref_slot, 1) || !slot_range_ok(c, tgt_slot, 1))
-    return fail(c, UWT_ERR_INVALID_ARG, "uwt_residual_jacobian");
+    return fail(c, UWT_ERR_INVALID_ARG, name);
+  if (general && !c->p.sampler && !c->p.weights)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(name) + ": context uses the nearest/identity fast path");
   int st = upload_pairs(c, 1, &ref_slot, &tgt_slot);
   if (st) return st;
   const LevelK& L = c->lv[lvl];
   const size_t n = L.ng;   // device dumps are indexed like the planes (pitch x gh positions); the host receives the gw x gh grid
-  const bool dump = J_out || r_out || valid_out;
+  const bool dump = general || J_out || r_out || valid_out;
   if (dump) {
-    st = ensure_scratch(c, n * (6 * 4 + 4 + 1) + 512);
+    st = ensure_scratch(c, n * (6 * 4 + 4 + 4 + 1) + 512);
     if (st) return st;
   }
   ResidualArgs a = residual_args(c, lvl);
-  a.state = nullptr;
   for (int k = 0; k < 4; k++) a.pose.q[k] = pose[k];
   for (int k = 0; k < 3; k++) a.pose.t[k] = pose[4 + k];
+  if (general) {   // the scale pass reads the pose from the pair's state
+    hipLaunchKernelGGL(k_set_pose, dim3(1), dim3(64), 0, c->stream, c->state, a.pose, c->p.initial_error);
+    HIPCHK(c, hipGetLastError());
+  } else {
+    a.state = nullptr;
+  }
   if (dump) {
     a.dumpJ = (float*)c->scratch;
     a.dumpR = a.dumpJ + 6 * n;
-    a.dumpV = (uint8_t*)(a.dumpR + n);
+    a.dumpW = a.dumpR + n;
+    a.dumpV = (uint8_t*)(a.dumpW + n);
   }
-  st = launch_residual(c, c->stream, a, 1, dump);
+  if (general && c->p.weights)   // the pair's bins and ticket word: all-zero ahead of the scale pass
+    HIPCHK(c, hipMemsetAsync(c->hist, 0, sizeof(unsigned int) * kHistBins, c->stream));
+  st = general ? launch_general(c, c->stream, a, 1, true) : launch_residual(c, c->stream, a, 1, dump);
   if (st) return st;
   std::vector<uint32_t> recs((size_t)a.slices * kRecWords);
-  HIPCHK(c, hipMemcpyAsync(recs.data(), c->partials, recs.size() * 4, hipMemcpyDeviceToHost, c->stream));
-  if (J_out) HIPCHK(c, hipMemcpy2DAsync(J_out, (size_t)L.gw * 24, a.dumpJ, (size_t)L.pitch * 24, (size_t)L.gw * 24, L.gh, hipMemcpyDeviceToHost, c->stream));
-  if (r_out) HIPCHK(c, hipMemcpy2DAsync(r_out, (size_t)L.gw * 4, a.dumpR, (size_t)L.pitch * 4, (size_t)L.gw * 4, L.gh, hipMemcpyDeviceToHost, c->stream));
-  if (valid_out) HIPCHK(c, hipMemcpy2DAsync(valid_out, (size_t)L.gw, a.dumpV, (size_t)L.pitch, (size_t)L.gw, L.gh, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::memset(acc_out, 0, sizeof(*acc_out));
-  for (int s = 0; s < a.slices; s++) {  // same slice-ordered f64 fold as k_gn_update
-    const uint32_t* r = recs.data() + (size_t)s * kRecWords;
-    double d[27];
-    std::memcpy(d, r, sizeof(d));
-    for (int k = 0; k < 21; k++) acc_out->A[k] += d[k];
-    for (int k = 0; k < 6; k++) acc_out->jtr[k] += d[21 + k];
-    acc_out->n_valid += (int32_t)r[54];
-    int64_t sr2;
-    std::memcpy(&sr2, r + 56, 8);
-    acc_out->sum_r2 += sr2;
-  }
-  return UWT_OK;
-}
-
-int uwt_residual_jacobian_weighted(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, int32_t lvl, const float pose[7],
-                                   uwt_accum* acc_out, double* err_num_out, float* inv_mad_out, float* J_out, float* r_out,
-                                   uint8_t* valid_out, float* w_out) {
-  if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
-  if (!c || !pose || !acc_out || lvl < 0 || lvl >= c->p.n_levels || !slot_range_ok(c, ref_slot, 1) || !slot_range_ok(c, tgt_slot, 1))
-    return fail(c, UWT_ERR_INVALID_ARG, "uwt_residual_jacobian_weighted");
-  if (!c->p.sampler && !c->p.weights)
-    return fail(c, UWT_ERR_INVALID_ARG, "uwt_residual_jacobian_weighted: context uses the nearest/identity fast path");
-  int st = upload_pairs(c, 1, &ref_slot, &tgt_slot);
-  if (st) return st;
-  const LevelK& L = c->lv[lvl];
-  const size_t n = L.ng;   // see uwt_residual_jacobian
-  st = ensure_scratch(c, n * (6 * 4 + 4 + 4 + 1) + 512);
-  if (st) return st;
-  Pose P;
-  for (int k = 0; k < 4; k++) P.q[k] = pose[k];
-  for (int k = 0; k < 3; k++) P.t[k] = pose[4 + k];
-  hipLaunchKernelGGL(k_set_pose, dim3(1), dim3(64), 0, c->stream, c->state, P, c->p.initial_error);
-  HIPCHK(c, hipGetLastError());
-  ResidualArgs a = residual_args(c, lvl);
-  a.dumpJ = (float*)c->scratch;
-  a.dumpR = a.dumpJ + 6 * n;
-  a.dumpW = a.dumpR + n;
-  a.dumpV = (uint8_t*)(a.dumpW + n);
-  int slices = 0;
-  st = launch_general_dump(c, a, 1, &slices);
-  if (st) return st;
-  std::vector<uint32_t> recs((size_t)slices * kRecWords);
   HIPCHK(c, hipMemcpyAsync(recs.data(), c->partials, recs.size() * 4, hipMemcpyDeviceToHost, c->stream));
   PairScale sc;
   std::memset(&sc, 0, sizeof(sc));
   sc.inv_mad = 1.f;
-  if (c->p.weights) HIPCHK(c, hipMemcpyAsync(&sc, c->scale, sizeof(sc), hipMemcpyDeviceToHost, c->stream));
+  if (general && c->p.weights) HIPCHK(c, hipMemcpyAsync(&sc, c->scale, sizeof(sc), hipMemcpyDeviceToHost, c->stream));
   if (J_out) HIPCHK(c, hipMemcpy2DAsync(J_out, (size_t)L.gw * 24, a.dumpJ, (size_t)L.pitch * 24, (size_t)L.gw * 24, L.gh, hipMemcpyDeviceToHost, c->stream));
   if (r_out) HIPCHK(c, hipMemcpy2DAsync(r_out, (size_t)L.gw * 4, a.dumpR, (size_t)L.pitch * 4, (size_t)L.gw * 4, L.gh, hipMemcpyDeviceToHost, c->stream));
   if (w_out) HIPCHK(c, hipMemcpy2DAsync(w_out, (size_t)L.gw * 4, a.dumpW, (size_t)L.pitch * 4, (size_t)L.gw * 4, L.gh, hipMemcpyDeviceToHost, c->stream));
@@ -1858,13 +1804,13 @@ int uwt_residual_jacobian_weighted(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slo
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::memset(acc_out, 0, sizeof(*acc_out));
   double err = 0.0;
-  for (int s = 0; s < slices; s++) {
+  for (int s = 0; s < a.slices; s++) {  // same slice-ordered f64 fold as k_gn_update
     const uint32_t* r = recs.data() + (size_t)s * kRecWords;
     double d[30];
     std::memcpy(d, r, sizeof(d));
     for (int k = 0; k < 21; k++) acc_out->A[k] += d[k];
     for (int k = 0; k < 6; k++) acc_out->jtr[k] += d[21 + k];
-    err += d[29];
+    if (general) err += d[29];   // the error numerator of the general kind's records
     acc_out->n_valid += (int32_t)r[54];
     int64_t sr2;
     std::memcpy(&sr2, r + 56, 8);
@@ -1873,6 +1819,19 @@ int uwt_residual_jacobian_weighted(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slo
   if (err_num_out) *err_num_out = err;
   if (inv_mad_out) *inv_mad_out = sc.inv_mad;
   return UWT_OK;
+}
+
+int uwt_residual_jacobian(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, int32_t lvl, const float pose[7],
+                          uwt_accum* acc_out, float* J_out, float* r_out, uint8_t* valid_out) {
+  return residual_jacobian_entry(c, "uwt_residual_jacobian", false, ref_slot, tgt_slot, lvl, pose, acc_out, nullptr, nullptr, J_out,
+                                 r_out, valid_out, nullptr);
+}
+
+int uwt_residual_jacobian_weighted(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, int32_t lvl, const float pose[7],
+                                   uwt_accum* acc_out, double* err_num_out, float* inv_mad_out, float* J_out, float* r_out,
+                                   uint8_t* valid_out, float* w_out) {
+  return residual_jacobian_entry(c, "uwt_residual_jacobian_weighted", true, ref_slot, tgt_slot, lvl, pose, acc_out, err_num_out,
+                                 inv_mad_out, J_out, r_out, valid_out, w_out);
 }
 
 static int ls_accumulate_impl(uwt_ctx* c, const float* J, const float* r, const float* w, int32_t n, int32_t divide, bool sse,

@@ -13,10 +13,9 @@
 //   k_coarse       the coarsest levels of such a call — and the coarsest level of a batch — run to their end in one launch,
 //                  one block per pair
 //   k_resid_hist_v (scale pass with the scale stage in its tail) + k_residual<.., WEIGHTS>   robust weights in the alignment loop;
-//                  k_residual<.., SAMPLER = 1>: bilinear sampler
-//   k_residual_points, k_points_hist, k_points_general                   explicit point tables (identity / general path)
+//                  k_residual<.., SAMPLER = 1>: bilinear sampler; k_residual<.., DUMP = true, ..>: the per-stage dump forms
+//   k_residual_points, k_points_hist + k_scale_stage, k_points_general   explicit point tables (identity / general path)
 //   k_ls_sequential   the LS mirror (src/LeastSquares.cpp): every accumulator's f32 chain in the reference's order
-//   k_residual_general, k_resid_hist, k_scale_stage                      per-stage (dump) forms of the general path
 //   k_grad_mag*, k_candidates_batch, k_scan_counts, k_patch_points, k_add_patch_points, k_remap_crop, k_trajectory*   the rows
 //                  next to the path
 //   masked_sums_*  a pixel's 28 f64 sums under an EXEC mask of the valid lanes (no select anywhere in the loop)
@@ -554,7 +553,7 @@ __device__ __forceinline__ void warp_setup(const Pose& pose, WarpK& K) {
 // cycles for TWO pixels with or without a scalar operand, so the per-pixel float sequence is written over pairs of
 // adjacent pixels: the block-uniform operands stay in SGPRs (no VGPR cost, 4 waves/SIMD kept) and cost nothing extra.
 // Each component sees exactly the scalar IEEE operation (same rounding, no contraction), so results are bit-identical
-// to the one-pixel form (F = float), which the per-stage kernels (general_pixel, the point tables, k_warp_table) use.  (The
+// to the one-pixel form (F = float), which the per-stage kernels (the point tables, k_warp_table) use.  (The
 // templates below still take VEC = 1 — one pixel per step — but since round 6 nothing instantiates it: every level is walked in
 // groups of four, RAGGED where its grid rows are not whole groups.)
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -1486,8 +1485,9 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
   AccT err = (AccT)0;                                      // Σ r·(r·w), the error numerator on the general path
   float inv_mad = 1.f;
   if constexpr (WEIGHTS != 0) inv_mad = ov ? ov->scale->inv_mad : a.scale[pair].inv_mad;
-  // robust weights over integer residuals: the per-value table (see WeightEntry) in the bytes of the reduction's image
-  constexpr bool TABLE = WEIGHTS != 0 && SAMPLER == 0;
+  // robust weights over integer residuals: the per-value table (see WeightEntry) in the bytes of the reduction's image (the dump
+  // forms evaluate the weight per pixel: the general branch of phase 4, whose residual and weight they write out)
+  constexpr bool TABLE = WEIGHTS != 0 && SAMPLER == 0 && !DUMP;
   static_assert(!TABLE || EXT_LDS == 0, "the weighted path reduces in its own LDS");
   __shared__ __attribute__((aligned(16))) unsigned char tlds[TABLE ? kReduceLdsBytes : 16];
   static_assert(!TABLE || kWeightTabBytes <= kReduceLdsBytes, "table fits the reduction image");
@@ -1802,6 +1802,7 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
 #pragma unroll
       for (int k = 0; k < 6; k++) Jp[k] = get(J[j / N][k], j % N);
       int ri = 0;
+      float rf_dump = 0.f, w_dump = 0.f;   // DUMP on the general path: the pixel's float residual and its weight
       if constexpr (!GENERAL && MASKED) {
         ri = i2[j] - (int)i1[j];
         double Jd[6];
@@ -1832,16 +1833,28 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
         const float w = robust_weight(WEIGHTS, rf, inv_mad);
         accumulate_weighted(acc, err, Jp, rf, w, a.gain);
         ri = (int)rintf(rf);
+        if constexpr (DUMP) {
+          rf_dump = rf;
+          w_dump = w;
+        }
       }
       if constexpr (GENERAL || !MASKED) sum_r2 += (uint32_t)__mul24(ri, ri);  // |ri| <= 255 (masked path: r2d)
       n_valid_wave += (uint32_t)__builtin_popcountll(okm[j]);  // scalar
       if constexpr (DUMP) {
         if (active) {
           const size_t p = (size_t)pair * L.ng + idx + j;
-          if (a.dumpV) a.dumpV[p] = lane_bit(okm[j]) ? 1 : 0;
-          if (a.dumpR) a.dumpR[p] = (float)ri;
-          if (a.dumpJ)
-            for (int k = 0; k < 6; k++) a.dumpJ[p * 6 + k] = Jp[k];
+          const bool ok = lane_bit(okm[j]);
+          if (a.dumpV) a.dumpV[p] = ok ? 1 : 0;
+          if constexpr (GENERAL) {   // the float residual and the weight; every term of an invalid position reads 0
+            if (a.dumpR) a.dumpR[p] = ok ? rf_dump : 0.f;
+            if (a.dumpW) a.dumpW[p] = ok ? w_dump : 0.f;
+            if (a.dumpJ)
+              for (int k = 0; k < 6; k++) a.dumpJ[p * 6 + k] = ok ? Jp[k] : 0.f;
+          } else {
+            if (a.dumpR) a.dumpR[p] = (float)ri;
+            if (a.dumpJ)
+              for (int k = 0; k < 6; k++) a.dumpJ[p * 6 + k] = Jp[k];
+          }
         }
       }
     }
@@ -1918,69 +1931,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 
 // ------------------------------------------------------------------------------------------------------------
 // General residual path: robust weights (src/Tracker.cpp:495-496, 1571-1654) and the bilinear sampler extension.
-// Not the throughput path — one pixel per thread step, three passes per iteration when weights are on
-// (residual histogram -> median, deviation histogram -> MAD, weighted accumulation).
+// The scale from a pair's signed residual histogram (wave_scale): in the tail of the dense scale pass (k_resid_hist_v, below),
+// or as a launch of its own behind the point tables' scale pass (k_scale_stage).
 // ------------------------------------------------------------------------------------------------------------
 struct GeneralArgs {
   int sampler;            // 0 nearest, 1 bilinear
   int weights;            // kWeights*
-  int stage;              // unused (kept for layout)
   float gain;
   unsigned int* hist;     // [pair][kHistBins]: signed bins q + 255 of the rounded residuals
   PairScale* scale;       // [pair]
 };
-
-// one pixel of the dense table: warp, validity, residual (either sampler)
-template <int AR, bool DEPTH>
-__device__ __forceinline__ bool general_pixel(const LevelK& L, const WarpK& K, int sampler,
-                                              const uint8_t* I1, const uint8_t* I2, const uint16_t* DP, uint32_t idx,
-                                              float& x2, float& y2, float& iz, float& rf) {
-  const uint32_t y = __umulhi(idx, L.magic), x = idx - y * (uint32_t)L.pitch;
-  float z = 1.0f;
-  bool ok = x < (uint32_t)L.gw;   // positions of the pitched row beyond the point grid carry no point
-  if constexpr (DEPTH) {
-    const int d = (int)(int16_t)DP[idx];
-    ok = ok && d > 0;
-    z = (float)d * L.zscale;
-  }
-  uint32_t gidx;
-  bool valid;
-  unsigned long long okm;
-  const unsigned long long okin = __builtin_amdgcn_ballot_w64(ok);
-  pixel_warp<AR, float>(L, K, (float)x, (float)y, z, &okin, x2, y2, iz, &okm, &gidx);
-  valid = lane_bit(okm);
-  const int i1 = I1[idx];
-  rf = sampler ? sample_bilinear(I2, L, x2, y2) - (float)i1 : (float)((int)I2[gidx] - i1);
-  return valid;
-}
-
-template <int AR, bool DEPTH>
-__global__ __launch_bounds__(kBlock) void k_resid_hist(const ResidualArgs a, const GeneralArgs ga) {
-  const int pair = blockIdx.y + a.pair_base;
-  const PairState st = a.state[pair];
-  if (st.level_done || st.status) return;
-  __shared__ unsigned int h[kHistBins];
-  for (int i = threadIdx.x; i < kHistBins; i += kBlock) h[i] = 0;
-  __syncthreads();
-  WarpK K;
-  warp_setup<AR>(st.pose, K);
-  const LevelK L = a.L;
-  const size_t ref_off = (size_t)a.ref_slots[pair] * L.n, tgt_off = (size_t)a.tgt_slots[pair] * L.n;
-  const uint8_t* I1 = a.img + ref_off;
-  const uint8_t* I2 = a.img + tgt_off;
-  const uint16_t* DP = DEPTH ? a.depth + ref_off : nullptr;
-  const int p_begin = blockIdx.x * a.groups_per_block, p_end = min(p_begin + a.groups_per_block, L.ng);
-  for (int p = p_begin + (int)threadIdx.x; p < p_end; p += kBlock) {
-    float x2, y2, iz, rf;
-    if (!general_pixel<AR, DEPTH>(L, K, ga.sampler, I1, I2, DP, (uint32_t)p, x2, y2, iz, rf)) continue;
-    const int q = (int)rintf(rf);   // saturate_cast<uchar> / lrint: round half to even; |q| <= 255
-    atomicAdd(&h[q + 255], 1u);     // signed bins; integer atomics are order-independent
-  }
-  __syncthreads();
-  unsigned int* gh = ga.hist + (size_t)pair * kHistBins;
-  for (int i = threadIdx.x; i < kHistBins; i += kBlock)
-    if (h[i]) atomicAdd(&gh[i], h[i]);
-}
 
 // Scale from the signed residual histogram alone (residuals are integers, or are binned by their rounded value):
 //   median by the reference's rule (MedianMat, src/Tracker.cpp:1575-1591: first bin whose cumulative count exceeds
@@ -2304,72 +2264,6 @@ __global__ __launch_bounds__(kBlock) void k_resid_hist_v(const ResidualArgs a, u
   hist_block<AR, VEC, DEPTH, SAMPLER, RAGGED>(a, pair, st.pose, a.ref_slots[pair], a.tgt_slots[pair], hist, scale_out, weights);
 }
 
-// weighted / bilinear accumulation: J <- w·J, r <- gain·r, A = Σ(wJ)(wJ)ᵀ, jtr = Σ(wJ)·((gain r)·w) (src/Tracker.cpp:554-561),
-// error numerator Σ r·(r·w) (:499-502).  With identity weights this is the plain sum with float residuals.
-template <int AR, bool DEPTH, bool UNIT_FACTORS>
-__global__ __launch_bounds__(kBlock) void k_residual_general(const ResidualArgs a, const GeneralArgs ga) {
-  const int pair = blockIdx.y + a.pair_base;
-  Pose pose;
-  if (a.state) {
-    const PairState st = a.state[pair];
-    if (st.level_done || st.status) return;
-    pose = st.pose;
-  } else {
-    pose = a.pose;
-  }
-  WarpK K;
-  warp_setup<AR>(pose, K);
-  const LevelK L = a.L;
-  const size_t ref_off = (size_t)a.ref_slots[pair] * L.n, tgt_off = (size_t)a.tgt_slots[pair] * L.n;
-  const uint8_t* I1 = a.img + ref_off;
-  const uint8_t* I2 = a.img + tgt_off;
-  const int16_t* GX = a.gx + ref_off;
-  const int16_t* GY = a.gy + ref_off;
-  const uint16_t* DP = DEPTH ? a.depth + ref_off : nullptr;
-  const float inv_mad = ga.weights ? ga.scale[pair].inv_mad : 1.f;
-  double acc[kAccFloats];
-#pragma unroll
-  for (int i = 0; i < kAccFloats; i++) acc[i] = 0.0;
-  double err = 0.0;
-  uint32_t sum_r2 = 0, n_valid = 0;
-  const int p_begin = blockIdx.x * a.groups_per_block, p_end = min(p_begin + a.groups_per_block, L.ng);
-  for (int p = p_begin + (int)threadIdx.x; p < p_end; p += kBlock) {
-    float x2, y2, iz, rf;
-    const bool ok = general_pixel<AR, DEPTH>(L, K, ga.sampler, I1, I2, DP, (uint32_t)p, x2, y2, iz, rf);
-    float J[6], w = 1.f;
-    if (ok) {
-      pixel_jacobian<AR, UNIT_FACTORS, false, true>(L, a.zf, a.af, x2, y2, iz, (float)GX[p], (float)GY[p], J);
-      w = robust_weight(ga.weights, rf, inv_mad);
-      const float rw1 = rf * w;                 // Residuals.mul(W) for the error (:500)
-      err += (double)rf * (double)rw1;
-      float Jw[6];
-#pragma unroll
-      for (int k = 0; k < 6; k++) Jw[k] = w * J[k];   // :556
-      const float rg = rf * ga.gain;            // :559
-      const float rw = rg * w;                  // :561
-      double Jd[6];
-#pragma unroll
-      for (int k = 0; k < 6; k++) Jd[k] = (double)Jw[k];
-      int s = 0;
-#pragma unroll
-      for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = i; j < 6; j++, s++) acc[s] = __builtin_fma(Jd[i], Jd[j], acc[s]);
-#pragma unroll
-      for (int i = 0; i < 6; i++) acc[21 + i] = __builtin_fma(Jd[i], (double)rw, acc[21 + i]);
-      const int q = (int)rintf(rf);
-      sum_r2 += (uint32_t)(q * q);
-      n_valid += 1;
-    }
-    if (a.dumpV) a.dumpV[(size_t)pair * L.ng + p] = ok ? 1 : 0;
-    if (a.dumpR) a.dumpR[(size_t)pair * L.ng + p] = ok ? rf : 0.f;
-    if (a.dumpJ)
-      for (int k = 0; k < 6; k++) a.dumpJ[((size_t)pair * L.ng + p) * 6 + k] = ok ? J[k] : 0.f;
-    if (a.dumpW) a.dumpW[(size_t)pair * L.ng + p] = ok ? w : 0.f;
-  }
-  block_reduce_store<double, true>(acc, sum_r2, n_valid, a.partials + ((size_t)pair * a.slices + blockIdx.x) * kRecWords, err);
-}
-
 // ------------------------------------------------------------------------------------------------------------
 // The scalar tail of one Gauss-Newton iteration for one pair: fold the block partials of the evaluation in slice order
 // (f64), error (src/Tracker.cpp:499-502), exit test (:508), A/b (:554-561), A.inv()*b (:564), pose <- pose * exp(delta)
@@ -2387,7 +2281,7 @@ struct UpdateArgs {
   float epsilon;
   float gain;
   int pair_base;
-  int general;       // 1: records come from k_residual_general (gain already applied, error numerator in slot 29)
+  int general;       // 1: records of the general path (gain already applied, error numerator in slot 29)
   int* active;       // optional: counts the pairs still iterating after this update (early-exit polling)
   int legacy_solve;  // uwt_params::arith == UWT_ARITH_LEGACY: A.inv() formed, then multiplied (else cv::solve's LU on b)
 };
@@ -3072,7 +2966,35 @@ struct PointsArgs {
   int pts_per_block;
 };
 
-template <int AR, bool UNIT_FACTORS, bool DUMP, typename AccT>
+// One row of a table: WarpFunction with the table's own w (src/Tracker.cpp:1439-1467) and the validity tests; i1x: the index
+// of the reference value, iz clamped at 0 (:452-453).  False: the row is not valid (x2, y2, iz, i1x are then of no use).
+template <int AR>
+__device__ __forceinline__ bool table_row(const LevelK& L, const float* T, const float4 P, float& x2, float& y2, float& iz, uint32_t& i1x) {
+  float o[3], wq;
+  warp_table_point<AR>(L, T, P, o, wq);
+  x2 = o[0] * L.fx; x2 = x2 / o[2]; x2 = x2 + L.cx; x2 = x2 * wq;
+  y2 = o[1] * L.fy; y2 = y2 / o[2]; y2 = y2 + L.cy; y2 = y2 * wq;
+  const float z2 = o[2];
+  iz = 1.0f / z2;
+  bool ok = (y2 > 0.f) && (y2 < (float)L.ih) && (x2 > 0.f) && (x2 < (float)L.iw) && (z2 != 0.f);
+  const int ix1 = (int)P.x, iy1 = (int)P.y;
+  ok = ok && ix1 >= 0 && ix1 < L.iw && iy1 >= 0 && iy1 < L.ih;  // the reference would read out of bounds
+  i1x = 0;
+  if (!ok) return false;
+  if (iz < 0.f) iz = 0.f;
+  i1x = (uint32_t)(iy1 * L.pitch + ix1);
+  return true;
+}
+
+// the index of a valid row's nearest-neighbour sample (:472), clamped to the image like pixel_gather_index
+__device__ __forceinline__ int table_gather_index(const LevelK& L, float x2, float y2) {
+  int ix2 = round_pos(x2), iy2 = round_pos(y2);
+  ix2 = min(ix2, L.iw - 1);
+  iy2 = min(iy2, L.ih - 1);
+  return iy2 * L.pitch + ix2;
+}
+
+template <int AR, bool UNIT_FACTORS, typename AccT>
 __global__ __launch_bounds__(kBlock) void k_residual_points(const ResidualArgs a, const PointsArgs pa) {
   const int pair = a.pair_base;
   Pose pose;
@@ -3098,75 +3020,35 @@ __global__ __launch_bounds__(kBlock) void k_residual_points(const ResidualArgs a
   const int p_begin = blockIdx.x * pa.pts_per_block;
   const int p_end = min(p_begin + pa.pts_per_block, pa.n_pts);
   for (int q = p_begin + (int)threadIdx.x; q < p_end; q += kBlock) {
-    const float4 P = pa.pts[q];
-    // WarpFunction with the table's own w (src/Tracker.cpp:1439-1467)
-    float o[3], wq;
-    warp_table_point<AR>(L, K.T, P, o, wq);
-    float x2 = o[0] * L.fx; x2 = x2 / o[2]; x2 = x2 + L.cx; x2 = x2 * wq;
-    float y2 = o[1] * L.fy; y2 = y2 / o[2]; y2 = y2 + L.cy; y2 = y2 * wq;
-    const float z2 = o[2];
-    float iz = 1.0f / z2;
-    bool ok = (y2 > 0.f) && (y2 < (float)L.ih) && (x2 > 0.f) && (x2 < (float)L.iw) && (z2 != 0.f);
-    const int ix1 = (int)P.x, iy1 = (int)P.y;
-    ok = ok && ix1 >= 0 && ix1 < L.iw && iy1 >= 0 && iy1 < L.ih;  // the reference would read out of bounds
+    float x2, y2, iz;
+    uint32_t i1x;
+    if (!table_row<AR>(L, K.T, pa.pts[q], x2, y2, iz, i1x)) continue;
+    const int ri = (int)I2[table_gather_index(L, x2, y2)] - (int)I1[i1x];
     float J[6];
-    int ri = 0;
-    if (ok) {
-      if (iz < 0.f) iz = 0.f;
-      const uint32_t i1x = (uint32_t)(iy1 * L.pitch + ix1);
-      int ix2 = round_pos(x2), iy2 = round_pos(y2);
-      ix2 = min(ix2, L.iw - 1);
-      iy2 = min(iy2, L.ih - 1);
-      ri = (int)I2[iy2 * L.pitch + ix2] - (int)I1[i1x];
-      pixel_jacobian<AR, UNIT_FACTORS, false, DUMP>(L, a.zf, a.af, x2, y2, iz, (float)GX[i1x], (float)GY[i1x], J);
-      accumulate(acc, J, ri);
-      sum_r2 += (uint32_t)(ri * ri);
-      n_valid += 1;
-    }
-    if constexpr (DUMP) {
-      if (a.dumpV) a.dumpV[q] = ok ? 1 : 0;
-      if (a.dumpR) a.dumpR[q] = ok ? (float)ri : 0.f;
-      if (a.dumpJ)
-        for (int k = 0; k < 6; k++) a.dumpJ[(size_t)q * 6 + k] = ok ? J[k] : 0.f;
-    }
+    pixel_jacobian<AR, UNIT_FACTORS>(L, a.zf, a.af, x2, y2, iz, (float)GX[i1x], (float)GY[i1x], J);
+    accumulate(acc, J, ri);
+    sum_r2 += (uint32_t)(ri * ri);
+    n_valid += 1;
   }
   block_reduce_store<AccT>(acc, sum_r2, n_valid, a.partials + ((size_t)pair * a.slices + blockIdx.x) * kRecWords);
 }
 
 // The same tables on the general path (robust weights and / or the bilinear sampler: uwt_params::weights, ::sampler): the
 // per-stage form of the dense path — k_points_hist, k_scale_stage, k_points_general per evaluation — over table rows.
-// One row: WarpFunction with the table's own w, the validity tests of k_residual_points, the residual of either sampler.
+// One row: table_row, then the residual of either sampler.
 template <int AR>
 __device__ __forceinline__ bool general_point(const LevelK& L, const float* T, int sampler, const uint8_t* __restrict__ I1,
                                               const uint8_t* __restrict__ I2, const float4 P, float& x2, float& y2, float& iz, float& rf,
                                               uint32_t& i1x) {
-  float o[3], wq;
-  warp_table_point<AR>(L, T, P, o, wq);
-  x2 = o[0] * L.fx; x2 = x2 / o[2]; x2 = x2 + L.cx; x2 = x2 * wq;
-  y2 = o[1] * L.fy; y2 = y2 / o[2]; y2 = y2 + L.cy; y2 = y2 * wq;
-  const float z2 = o[2];
-  iz = 1.0f / z2;
-  bool ok = (y2 > 0.f) && (y2 < (float)L.ih) && (x2 > 0.f) && (x2 < (float)L.iw) && (z2 != 0.f);
-  const int ix1 = (int)P.x, iy1 = (int)P.y;
-  ok = ok && ix1 >= 0 && ix1 < L.iw && iy1 >= 0 && iy1 < L.ih;  // the reference would read out of bounds
   rf = 0.f;
-  i1x = 0;
-  if (!ok) return false;
-  if (iz < 0.f) iz = 0.f;
-  i1x = (uint32_t)(iy1 * L.pitch + ix1);
+  if (!table_row<AR>(L, T, P, x2, y2, iz, i1x)) return false;
   const int i1 = I1[i1x];
-  if (sampler) {
-    rf = sample_bilinear(I2, L, x2, y2) - (float)i1;
-  } else {
-    int ix2 = round_pos(x2), iy2 = round_pos(y2);
-    ix2 = min(ix2, L.iw - 1);
-    iy2 = min(iy2, L.ih - 1);
-    rf = (float)((int)I2[iy2 * L.pitch + ix2] - i1);
-  }
+  if (sampler) rf = sample_bilinear(I2, L, x2, y2) - (float)i1;
+  else rf = (float)((int)I2[table_gather_index(L, x2, y2)] - i1);
   return true;
 }
 
-// the scale pass: every valid row's rounded residual into the pair's signed bins (k_resid_hist over a table)
+// the scale pass: every valid row's rounded residual into the pair's signed bins
 template <int AR>
 __global__ __launch_bounds__(kBlock) void k_points_hist(const ResidualArgs a, const PointsArgs pa, const GeneralArgs ga) {
   const int pair = a.pair_base;
@@ -3193,7 +3075,7 @@ __global__ __launch_bounds__(kBlock) void k_points_hist(const ResidualArgs a, co
     if (h[i]) atomicAdd(&gh[i], h[i]);
 }
 
-// the weighted / bilinear accumulation of k_residual_general over a table (records of the `general` kind)
+// the weighted / bilinear accumulation over a table (records of the `general` kind)
 template <int AR, bool UNIT_FACTORS>
 __global__ __launch_bounds__(kBlock) void k_points_general(const ResidualArgs a, const PointsArgs pa, const GeneralArgs ga) {
   const int pair = a.pair_base;

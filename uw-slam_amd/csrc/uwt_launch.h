@@ -23,11 +23,10 @@ inline bool level_plain(const ResidualArgs& a) { return a.zf == 1.0f && a.af == 
 
 // k_residual, identity weights / nearest sampler (and the per-stage dump form)
 void launch_residual(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, int n_pairs, bool dump);
-// the scale pass (weights != 0: k_resid_hist_v) and the weighted / bilinear k_residual of one evaluation
+// the scale pass (weights != 0: k_resid_hist_v) and the weighted / bilinear k_residual of one evaluation (dump: its per-stage dump
+// form)
 void launch_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, int n_pairs, int sampler, int weights,
-                    unsigned int* hist, PairScale* scale);
-// the per-stage (dump-capable) form: k_resid_hist + k_scale_stage (weights != 0), then k_residual_general
-void launch_general_dump(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const GeneralArgs& ga, int n_pairs);
+                    unsigned int* hist, PairScale* scale, bool dump);
 // explicit point tables (k_residual_points)
 void launch_points(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const PointsArgs& pa);
 // the same on the general path: k_points_hist + k_scale_stage (weights != 0; the caller cleared the pair's bins), k_points_general

@@ -1,5 +1,5 @@
 // uwt_launch_general.hip — dispatch of the general path: robust weights (scale pass k_resid_hist_v + weighted k_residual) and the
-// bilinear sampler, and the per-stage (dump-capable) form k_resid_hist / k_scale_stage / k_residual_general.
+// bilinear sampler, the per-stage dump form of the same evaluation, and the point tables' general path.
 #include "uwt_launch.h"
 
 namespace uwt {
@@ -46,6 +46,19 @@ void launch_general_t(hipStream_t s, const ResidualArgs& a, int n_pairs, int sam
   }
 }
 
+// The per-stage dump form of the weighted / bilinear sums: one instantiation per level shape — the general Jacobian form, RAGGED
+// (whose mask is a no-op where the grid rows are whole groups) — weights evaluated per pixel (no weight table under DUMP).
+template <int AR, bool DEPTH, bool UNIT>
+void launch_dump_t(hipStream_t s, const ResidualArgs& a, int n_pairs, int sampler, int weights) {
+  const dim3 grid(a.slices, n_pairs), blk(kBlock);
+  switch (sampler * 3 + weights) {
+    case 1: hipLaunchKernelGGL((k_residual<AR, 4, DEPTH, UNIT, true, double, false, 0, 1, false, 0, true>), grid, blk, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((k_residual<AR, 4, DEPTH, UNIT, true, double, false, 0, 2, false, 0, true>), grid, blk, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((k_residual<AR, 4, DEPTH, UNIT, true, double, false, 1, 0, false, 0, true>), grid, blk, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_residual<AR, 4, DEPTH, UNIT, true, double, false, 1, 2, false, 0, true>), grid, blk, 0, s, a); break;
+  }
+}
+
 template <int AR, bool RAGGED, bool DEPTH>
 void launch_hist_t(hipStream_t s, const ResidualArgs& a, int n_pairs, int sampler, int weights, unsigned int* hist, PairScale* scale) {
   const dim3 grid(a.slices, n_pairs), blk(kBlock);
@@ -57,9 +70,9 @@ void launch_hist_t(hipStream_t s, const ResidualArgs& a, int n_pairs, int sample
 
 // The alignment loop's launch on the general path: the scale pass (weights only: residual histograms per pair, the scale derived
 // in the tail of the pair's last block; the histograms are all-zero before and after — cleared once per alignment call), then
-// the dense kernel specialised for the sampler / weights.
+// the dense kernel specialised for the sampler / weights, or its dump form.
 void launch_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, int n_pairs, int sampler, int weights,
-                    unsigned int* hist, PairScale* scale) {
+                    unsigned int* hist, PairScale* scale, bool dump) {
   const bool ragged = level_ragged(a.L);
   if (weights) {
     UWT_WITH_AR(sel.arith,
@@ -71,7 +84,16 @@ void launch_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, 
         else launch_hist_t<AR, true, false>(s, a, n_pairs, sampler, weights, hist, scale);
       });
   }
-  launch_weighted(s, sel, a, n_pairs, sampler, weights);
+  if (!dump) {
+    launch_weighted(s, sel, a, n_pairs, sampler, weights);
+    return;
+  }
+  const bool unit = (a.zf == 1.0f && a.af == 1.0f);
+  UWT_WITH_AR(sel.arith,
+    if (sel.depth && unit) launch_dump_t<AR, true, true>(s, a, n_pairs, sampler, weights);
+    else if (sel.depth) launch_dump_t<AR, true, false>(s, a, n_pairs, sampler, weights);
+    else if (unit) launch_dump_t<AR, false, true>(s, a, n_pairs, sampler, weights);
+    else launch_dump_t<AR, false, false>(s, a, n_pairs, sampler, weights));
 }
 
 // the weighted / bilinear sums of one evaluation (the scale, where weights are on, is in place)
@@ -109,24 +131,6 @@ void launch_hist_iterate(hipStream_t s, const LaunchSel& sel, const ResidualArgs
       case 6: hipLaunchKernelGGL((k_hist_iterate<AR, true, 1, false>), grid, blk, 0, s, a, ia, hist, scale, weights); break;
       default: hipLaunchKernelGGL((k_hist_iterate<AR, true, 1, true>), grid, blk, 0, s, a, ia, hist, scale, weights); break;
     });
-}
-
-// The per-stage (dump-capable) form of the same evaluation: k_residual_general, one pixel per thread step; `a` carries the
-// dump form's slicing (one pixel per point), `ga.hist` is cleared by the caller.
-void launch_general_dump(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const GeneralArgs& ga, int n_pairs) {
-  const bool unit = (a.zf == 1.0f && a.af == 1.0f);
-  const dim3 grid(a.slices, n_pairs), blk(kBlock);
-  if (ga.weights) {
-    UWT_WITH_AR(sel.arith,
-      if (sel.depth) hipLaunchKernelGGL((k_resid_hist<AR, true>), grid, blk, 0, s, a, ga);
-      else hipLaunchKernelGGL((k_resid_hist<AR, false>), grid, blk, 0, s, a, ga));
-    hipLaunchKernelGGL(k_scale_stage, dim3((n_pairs + 3) / 4), dim3(256), 0, s, ga, a.state, n_pairs, a.pair_base);
-  }
-  UWT_WITH_AR(sel.arith,
-    if (sel.depth && unit) hipLaunchKernelGGL((k_residual_general<AR, true, true>), grid, blk, 0, s, a, ga);
-    else if (sel.depth) hipLaunchKernelGGL((k_residual_general<AR, true, false>), grid, blk, 0, s, a, ga);
-    else if (unit) hipLaunchKernelGGL((k_residual_general<AR, false, true>), grid, blk, 0, s, a, ga);
-    else hipLaunchKernelGGL((k_residual_general<AR, false, false>), grid, blk, 0, s, a, ga));
 }
 
 void launch_points_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const PointsArgs& pa, const GeneralArgs& ga) {

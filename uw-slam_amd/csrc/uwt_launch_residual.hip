@@ -93,10 +93,10 @@ void launch_points(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, c
   const bool unit = (a.zf == 1.0f && a.af == 1.0f);
   const dim3 grid(a.slices), blk(kBlock);
   UWT_WITH_AR(sel.arith,
-    if (unit && sel.acc64) hipLaunchKernelGGL((k_residual_points<AR, true, false, double>), grid, blk, 0, s, a, pa);
-    else if (unit) hipLaunchKernelGGL((k_residual_points<AR, true, false, float>), grid, blk, 0, s, a, pa);
-    else if (sel.acc64) hipLaunchKernelGGL((k_residual_points<AR, false, false, double>), grid, blk, 0, s, a, pa);
-    else hipLaunchKernelGGL((k_residual_points<AR, false, false, float>), grid, blk, 0, s, a, pa));
+    if (unit && sel.acc64) hipLaunchKernelGGL((k_residual_points<AR, true, double>), grid, blk, 0, s, a, pa);
+    else if (unit) hipLaunchKernelGGL((k_residual_points<AR, true, float>), grid, blk, 0, s, a, pa);
+    else if (sel.acc64) hipLaunchKernelGGL((k_residual_points<AR, false, double>), grid, blk, 0, s, a, pa);
+    else hipLaunchKernelGGL((k_residual_points<AR, false, float>), grid, blk, 0, s, a, pa));
 }
 
 }  // namespace uwt
