@@ -19,10 +19,12 @@
 // surfaces misuse as cv::Exception / SOPHUS_ENSURE aborts).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "uwt.h"
@@ -315,6 +317,40 @@ class Tracker {
     uwt_update_params(ctx(), &saved);
     check(st, "uwt_estimate_pose_points");
   }
+  // System::Tracking's live call (src/System.cpp:214-219: ObtainPatchesPoints(previous) + EstimatePoseFeatures(previous,
+  // current)) for many pairs at once: each previous frame's keypoints_ go in, its rigid_transformation_ comes out.  The patch
+  // tables are built and consumed on the device (previous->candidatePoints_ is left as it is); the reference's constants are
+  // the call's own, so the tracker's params are not touched.  At most max_pairs pairs, whose frames must all be bound at once
+  // (2 x pairs <= max_frames for distinct frames); per-pair stats in last_batch_stats().
+  void EstimatePoseFeaturesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs) {
+    const size_t n = _pairs.size();
+    if (n == 0) return;
+    std::vector<int32_t> a(n), b(n), counts(n);
+    std::vector<float> kp(n * 400, 0.f);
+    for (size_t i = 0; i < n; i++) {
+      a[i] = bind(_pairs[i].first);
+      b[i] = bind(_pairs[i].second);
+    }
+    for (size_t i = 0; i < n; i++) {   // binding a later pair's frame may have taken an earlier frame's slot
+      Frame* prev = _pairs[i].first;
+      if (!bound(prev) || !bound(_pairs[i].second))
+        throw std::runtime_error("EstimatePoseFeaturesBatch: more frames than slots (max_frames)");
+      if (!prev->obtained_gradients_)
+        throw std::runtime_error("EstimatePoseFeaturesBatch: ApplyGradient(previous) not called (or its slot was reused since)");
+      const size_t m = prev->keypoints_.size() / 2;
+      counts[i] = (int32_t)m;
+      std::copy(prev->keypoints_.begin(), prev->keypoints_.begin() + 2 * (m < 200 ? m : 200), kp.begin() + 400 * i);
+    }
+    std::vector<float> poses(n * 7);
+    last_batch_stats_.assign(n, uwt_stats{});
+    const int st = uwt_estimate_pose_features_batch(ctx(), (int32_t)n, a.data(), b.data(), kp.data(), counts.data(), poses.data(),
+                                                    last_batch_stats_.data());
+    if (st == UWT_OK || st == UWT_ERR_PAIR_FAILED)
+      for (size_t i = 0; i < n; i++) std::copy(poses.begin() + 7 * i, poses.begin() + 7 * (i + 1), _pairs[i].first->rigid_transformation_.data());
+    if (st == UWT_OK) last_stats_ = last_batch_stats_.back();
+    check(st, "uwt_estimate_pose_features_batch");
+  }
+  const std::vector<uwt_stats>& last_batch_stats() const { return last_batch_stats_; }
   // EstimatePose over the sparse tables a producer left in previous->candidatePoints_[lvl] (src/Tracker.cpp:401)
   void EstimatePoseOverCandidatePoints(Frame* _previous_frame, Frame* _current_frame) {
     const int32_t a = bind(_previous_frame), b = bind(_current_frame);
@@ -387,8 +423,9 @@ class Tracker {
   // System::AddFrame's pyramid loop (src/System.cpp:246-251): upload level 0, build the other levels on the GPU.
   // Slots are handed out least-recently-used first; the frame that held a reused slot is told so (slot_ = -1, its
   // gradient flag cleared): it uploads again when it is next used instead of silently reading another frame's planes.
+  bool bound(const Frame* f) const { return f->slot_ >= 0 && f->tracker_ == this && owner_[(size_t)f->slot_] == f; }
   int bind(Frame* f) {
-    if (f->slot_ >= 0 && f->tracker_ == this && owner_[(size_t)f->slot_] == f) {
+    if (bound(f)) {
       last_use_[(size_t)f->slot_] = ++use_clock_;
       return f->slot_;
     }
@@ -423,6 +460,7 @@ class Tracker {
   uwt_params params_{};
   uwt_ctx* ctx_ = nullptr;
   uwt_stats last_stats_{};
+  std::vector<uwt_stats> last_batch_stats_;
 };
 
 inline Frame::~Frame() {

@@ -361,6 +361,36 @@ int uwt_obtain_patch_points(uwt_ctx* ctx, int32_t slot, const float* keypoints_x
 int uwt_add_patch_points(uwt_ctx* ctx, int32_t lvl, const float* pts, int32_t n_pts, int32_t patch_size, float* pts_out,
                          int32_t cap, int32_t* count_out);
 
+/* ---- the live call for a batch of pairs (tables built and consumed on the device) ------------------------------------ */
+
+/* Tracker::ObtainPatchesPoints (src/Tracker.cpp:1178-1257) for n_frames frames at once (1 <= n_frames <= max_pairs).
+ * keypoints_xy: n_frames x 200 x 2 floats (frame f's key points at f*400); n_keypoints[f]: how many, only the first 200 used.
+ * pts_out: frame f's table at f * cap * 4 (min(count, cap) rows written); counts_out[f]: its full count.  Synchronous. */
+int uwt_obtain_patch_points_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const float* keypoints_xy,
+                                  const int32_t* n_keypoints, float* pts_out, int32_t cap, int32_t* counts_out);
+/* System::Tracking's live call (src/System.cpp:214-219) for n_pairs pairs: ObtainPatchesPoints(previous) then
+ * EstimatePoseFeatures(previous, current) with the reference's own constants (src/Tracker.cpp:634-640, 834, 856): level 0 only,
+ * 10 iterations, epsilon 1e-3, last_error 50000 (:661), gain 1, z_factor 0.002, no angle factor, the early exit of :782,
+ * identity weights (:769), round() sampling (:746).  previous = ref_slots[i] (its key points and its depth), current =
+ * tgt_slots[i]; key points as in uwt_obtain_patch_points_batch.
+ * Geometry, intrinsics, arith, has_depth and accumulate_f64 come from the context; its first_level, last_level, max_iters,
+ * epsilon, gain, z_factor, angle_factor, initial_error, early_exit, weights and sampler are ignored and left as they are (no
+ * uwt_update_params round trip).  1 <= n_pairs <= max_pairs, slots in range and every used key point inside level 0, or
+ * UWT_ERR_INVALID_ARG with nothing enqueued.  A pair with no valid point (no key points, every key point on zero depth) gets
+ * UWT_ERR_NO_VALID_POINTS in its own uwt_stats; the other pairs are unaffected.  The tables, their counts and the solver state
+ * never leave the device: one producer launch, then one launch per Gauss-Newton evaluation with the update in its tail.
+ * A pair's pose does not depend on the batch it runs in.  The caller may reuse every host array once the call returns.
+ * Results go to DEVICE memory, as in uwt_track_batch_async (d_poses_out: n_pairs x 7 floats, d_stats_out_or_null: n_pairs
+ * uwt_stats), ordered against uwt_upload_frames_async like it.  The call never waits for the device; uwt_sync() to wait. */
+int uwt_track_features_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                   const float* keypoints_xy, const int32_t* n_keypoints,
+                                   float* d_poses_out, uwt_stats* d_stats_out_or_null);
+/* The same, synchronous, results in host memory (the uwt_estimate_pose_batch counterpart: UWT_ERR_PAIR_FAILED when a pair
+ * failed, its status in its uwt_stats). */
+int uwt_estimate_pose_features_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                     const float* keypoints_xy, const int32_t* n_keypoints,
+                                     float* poses_out, uwt_stats* stats_out_or_null);
+
 /* ---- next to the path: frame ingest ---------------------------------------------------------------- */
 
 typedef struct uwt_ingest uwt_ingest;

@@ -69,6 +69,7 @@ SYMBOLS = [
     "uwt_ingest_create", "uwt_ingest_destroy", "uwt_ingest_maps", "uwt_ingest_undistort", "uwt_ingest_calculate_roi",
     "uwt_ingest_frame", "uwt_update_params", "uwt_get_params", "uwt_ls_accumulate_sse", "uwt_robust_weights",
     "uwt_get_tuning", "uwt_set_tuning",
+    "uwt_obtain_patch_points_batch", "uwt_track_features_batch_async", "uwt_estimate_pose_features_batch",
 ]
 
 _lib = None
@@ -547,6 +548,52 @@ class Context:
         self._chk(lib().uwt_obtain_patch_points(self._h, slot, _p(kp, C.c_float), kp.shape[0], _p(pts, C.c_float), cap,
                                                 C.byref(cnt)))
         return pts[:min(cnt.value, cap)].copy(), cnt.value
+
+    @staticmethod
+    def _keypoint_block(keypoints_list):
+        """A list of (n_i, 2) key point arrays as the batch calls take them: [P, 200, 2] float32 (the first 200 of each, zero
+        padded) and the counts n_i."""
+        kps = [np.ascontiguousarray(k, np.float32).reshape(-1, 2) for k in keypoints_list]
+        block = np.zeros((len(kps), 200, 2), np.float32)
+        n = np.zeros(len(kps), np.int32)
+        for i, k in enumerate(kps):
+            m = min(k.shape[0], 200)
+            block[i, :m] = k[:m]
+            n[i] = k.shape[0]
+        return block, n
+
+    def obtain_patch_points_batch(self, slots, keypoints_list, cap=200 * 144):
+        """Tracker::ObtainPatchesPoints for many frames at once.  Returns (list of [min(count_f, cap), 4] arrays, counts)."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        kp, n = self._keypoint_block(keypoints_list)
+        pts = np.empty((max(sl.size, 1), max(cap, 1), 4), np.float32)
+        cnt = np.zeros(max(sl.size, 1), np.int32)
+        self._chk(lib().uwt_obtain_patch_points_batch(self._h, sl.size, _p(sl, C.c_int32), _p(kp, C.c_float), _p(n, C.c_int32),
+                                                      _p(pts, C.c_float), cap, _p(cnt, C.c_int32)))
+        return [pts[f, :min(int(cnt[f]), cap)].copy() for f in range(sl.size)], cnt[:sl.size]
+
+    def estimate_pose_features_batch(self, ref_slots, tgt_slots, keypoints_list, raise_on_pair_failure=False):
+        """System::Tracking's live call for many pairs: keypoints_list[i] are the key points of the frame in ref_slots[i].
+        Returns (poses [P, 7], per-pair stats)."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        kp, n = self._keypoint_block(keypoints_list)
+        poses = np.empty((ref.size, 7), np.float32)
+        stats = (Stats * max(ref.size, 1))()
+        st = lib().uwt_estimate_pose_features_batch(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
+                                                    _p(n, C.c_int32), _p(poses, C.c_float), stats)
+        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+        return poses, [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
+
+    def track_features_batch_async(self, ref_slots, tgt_slots, keypoints_list, d_poses_ptr, d_stats_ptr=None):
+        """The same enqueued on the context stream, results in device memory (d_poses_ptr: P x 7 float32, d_stats_ptr: P x 4
+        int32-sized uwt_stats or None); sync() to wait."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        kp, n = self._keypoint_block(keypoints_list)
+        self._chk(lib().uwt_track_features_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
+                                                       _p(n, C.c_int32), C.c_void_p(d_poses_ptr),
+                                                       C.c_void_p(d_stats_ptr) if d_stats_ptr else None))
 
     def add_patch_points(self, lvl, pts, patch_size=5, cap=None):
         """Tracker::AddPatchPointsFeatures (src/Tracker.cpp:599-629).  Returns (table, full count)."""

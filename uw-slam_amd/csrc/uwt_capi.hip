@@ -87,6 +87,17 @@ struct uwt_ctx {
   int* h_active = nullptr;              // pinned
   void* scratch = nullptr;              // per-stage entry points
   size_t scratch_bytes = 0;
+  // the live call for a batch of pairs (uwt_track_features_batch_async, uwt_obtain_patch_points_batch), allocated on first use:
+  // max_pairs tables of kPatchMaxKeypoints x kPatchMaxRows rows and their counts, the key points as the device reads them, the
+  // evaluation's records (kFeatMaxSlices per pair), and a pinned staging ring for the caller's key points (as h_pairs)
+  float4* feat_tab = nullptr;
+  int* feat_cnt = nullptr;
+  float2* feat_kp = nullptr;
+  int* feat_nkp = nullptr;
+  uint32_t* feat_recs = nullptr;
+  float* h_feat = nullptr;              // kPairStages blocks of [n (max_pairs ints) | key points (max_pairs x 400 floats)]
+  hipEvent_t ev_feat[kPairStages] = {};
+  int feat_stage = 0;
   void* stage[2] = {nullptr, nullptr};  // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
   size_t stage_bytes[2] = {0, 0};
   bool profiling = false;
@@ -1173,6 +1184,14 @@ int uwt_destroy(uwt_ctx* c) {
   if (c->h_active) (void)hipHostFree(c->h_active);
   if (c->h_pairs) (void)hipHostFree(c->h_pairs);
   if (c->scratch) (void)hipFree(c->scratch);
+  if (c->feat_tab) (void)hipFree(c->feat_tab);
+  if (c->feat_cnt) (void)hipFree(c->feat_cnt);
+  if (c->feat_kp) (void)hipFree(c->feat_kp);
+  if (c->feat_nkp) (void)hipFree(c->feat_nkp);
+  if (c->feat_recs) (void)hipFree(c->feat_recs);
+  if (c->h_feat) (void)hipHostFree(c->h_feat);
+  for (hipEvent_t e : c->ev_feat)
+    if (e) (void)hipEventDestroy(e);
   for (void* p : c->stage)
     if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -2144,6 +2163,199 @@ int uwt_obtain_patch_points(uwt_ctx* c, int32_t slot, const float* kp, int32_t n
     HIPCHK(c, hipMemcpyAsync(pts_out, d_out, (size_t)m * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  return UWT_OK;
+}
+
+// ---- the live call for a batch of pairs: tables built and evaluated on the device --------------------------------
+namespace {
+
+constexpr int kFeatTableRows = kPatchMaxKeypoints * kPatchMaxRows;   // rows of one pair's table at most (its stride)
+constexpr int kFeatKpFloats = 2 * kPatchMaxKeypoints;                 // one frame's key points as the caller passes them
+// Tracker::EstimatePoseFeatures' locals (src/Tracker.cpp:633-640, 661, 834): level 0 only, 10 iterations, epsilon 1e-3,
+// last_error 50000, z_factor 0.002, no angle factor, gain 1 (Residuals.mul(1)); identity weights (:769), round() (:746).
+constexpr int kFeatMaxIters = 10;
+constexpr float kFeatEpsilon = 0.001f, kFeatInitialError = 50000.0f, kFeatZFactor = 0.002f, kFeatAngleFactor = 1.0f, kFeatGain = 1.0f;
+
+// the live call's device buffers and staging ring, allocated on the first call (uwt_destroy frees them); each piece is retried
+// on its own after a failed allocation
+int ensure_features(uwt_ctx* c) {
+  const size_t mp = (size_t)c->p.max_pairs;
+  if (!c->feat_tab) HIPCHK(c, hipMalloc((void**)&c->feat_tab, sizeof(float4) * kFeatTableRows * mp));
+  if (!c->feat_cnt) HIPCHK(c, hipMalloc((void**)&c->feat_cnt, sizeof(int) * mp));
+  if (!c->feat_kp) HIPCHK(c, hipMalloc((void**)&c->feat_kp, sizeof(float) * kFeatKpFloats * mp));
+  if (!c->feat_nkp) HIPCHK(c, hipMalloc((void**)&c->feat_nkp, sizeof(int) * mp));
+  if (!c->feat_recs) HIPCHK(c, hipMalloc((void**)&c->feat_recs, sizeof(uint32_t) * kRecWords * kFeatMaxSlices * mp));
+  for (int i = 0; i < uwt_ctx::kPairStages; i++)
+    if (!c->ev_feat[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_feat[i], hipEventDisableTiming));
+  if (!c->h_feat) HIPCHK(c, hipHostMalloc((void**)&c->h_feat, sizeof(float) * (1 + kFeatKpFloats) * mp * uwt_ctx::kPairStages));
+  return UWT_OK;
+}
+
+// every argument of a batch of frames / pairs, before anything is enqueued: n in 1..max_pairs, the slots in range, the first
+// min(n_keypoints[f], 200) key points of every frame inside level 0 (as uwt_obtain_patch_points)
+int check_features_args(uwt_ctx* c, const char* what, int n, const int32_t* slots_a, const int32_t* slots_b, const float* kp,
+                        const int32_t* n_kp) {
+  if (!slots_a || !slots_b || !kp || !n_kp) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  if (n < 1 || n > c->p.max_pairs) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": count outside 1..max_pairs");
+  const float w = (float)c->lv[0].gw, h = (float)c->lv[0].gh;   // level 0: grid = image
+  for (int f = 0; f < n; f++) {
+    if (slots_a[f] < 0 || slots_a[f] >= c->p.max_frames || slots_b[f] < 0 || slots_b[f] >= c->p.max_frames)
+      return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": slot out of range");
+    if (n_kp[f] < 0) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": negative key point count");
+    const float* k = kp + (size_t)f * kFeatKpFloats;
+    for (int i = 0; i < std::min(n_kp[f], kPatchMaxKeypoints); i++)
+      if (!(k[2 * i] >= 0.f && k[2 * i] < w && k[2 * i + 1] >= 0.f && k[2 * i + 1] < h))
+        return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key point outside the image");
+  }
+  return UWT_OK;
+}
+
+// the slot range a call reads, ordered behind the asynchronous uploads into it (compute_begin)
+int features_begin(uwt_ctx* c, int n, const int32_t* slots_a, const int32_t* slots_b) {
+  int lo = c->p.max_frames, hi = 0;
+  for (int i = 0; i < n; i++) {
+    lo = std::min(lo, std::min(slots_a[i], slots_b[i]));
+    hi = std::max(hi, std::max(slots_a[i], slots_b[i]) + 1);
+  }
+  c->dep_first = lo;
+  c->dep_n = hi - lo;
+  return compute_begin(c, c->dep_first, c->dep_n);
+}
+
+// The caller's key points and counts are copied before the call returns (into the next block of a pinned ring, as
+// upload_pairs does with the pair lists), then asynchronously to the device, and the batched producer builds frame f's table
+// at feat_tab + f * kFeatTableRows from the key points and the depth of slot d_slots[f].
+int enqueue_patch_tables(uwt_ctx* c, int n, const int* d_slots, const float* kp, const int32_t* n_kp) {
+  const size_t mp = (size_t)c->p.max_pairs;
+  const int stage = (c->feat_stage + 1) % uwt_ctx::kPairStages;
+  HIPCHK(c, hipEventSynchronize(c->ev_feat[stage]));   // the copy that last read this block (kPairStages calls ago)
+  float* block = c->h_feat + (size_t)stage * (1 + kFeatKpFloats) * mp;
+  int* h_n = reinterpret_cast<int*>(block);
+  float* h_kp = block + mp;
+  std::memcpy(h_n, n_kp, sizeof(int) * n);
+  std::memcpy(h_kp, kp, sizeof(float) * kFeatKpFloats * n);
+  c->feat_stage = stage;
+  HIPCHK(c, hipMemcpyAsync(c->feat_nkp, h_n, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->feat_kp, h_kp, sizeof(float) * kFeatKpFloats * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev_feat[stage], c->stream));
+  uwt::launch_patch_points_batch(c->stream, n, c->feat_kp, c->feat_nkp, d_slots, c->p.has_depth ? c->depth[0] : nullptr,
+                                 (size_t)c->lv[0].n, c->lv[0].pitch, c->lv[0].gw, c->lv[0].gh, c->feat_tab, kFeatTableRows,
+                                 c->feat_cnt);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
+// System::Tracking's live call for n_pairs pairs, enqueued on the context stream: k_init_state, the producer over the reference
+// frames, kFeatMaxIters k_table_eval launches (each evaluates every pair still iterating and updates it in its tail; a pair that
+// has left makes the later launches return at once), k_level_end, k_write_out.  No read-back, no wait for the device.
+int features_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, const float* kp,
+                     const int32_t* n_kp, float* d_poses, StatsOut* d_stats) {
+  int st = check_features_args(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp);
+  if (st) return st;
+  st = ensure_features(c);
+  if (st) return st;
+  st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
+  if (st) return st;
+  st = features_begin(c, n_pairs, ref_slots, tgt_slots);
+  if (st) return st;
+  // the grid's slices: the batch's bound on a table's rows (the producer's counts stay on the device); also the record stride
+  int rows = 0;
+  for (int i = 0; i < n_pairs; i++) rows = std::max(rows, std::min(n_kp[i], kPatchMaxKeypoints) * kPatchMaxRows);
+  const int slices = table_slices(rows);
+  const int tb = 128;
+  hipLaunchKernelGGL(k_init_state, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, kFeatInitialError);
+  HIPCHK(c, hipGetLastError());
+  st = enqueue_patch_tables(c, n_pairs, c->d_ref, kp, n_kp);
+  if (st) return st;
+  HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
+  ResidualArgs ra = residual_args(c, 0);
+  ra.zf = kFeatZFactor;
+  ra.af = kFeatAngleFactor;
+  ra.gain = kFeatGain;
+  ra.slices = slices;
+  ra.partials = c->feat_recs;
+  UpdateArgs ua = update_args(c, 0);
+  ua.partials = c->feat_recs;
+  ua.slices = slices;
+  ua.max_iters = kFeatMaxIters;
+  ua.early_exit = 1;
+  ua.epsilon = kFeatEpsilon;
+  ua.gain = kFeatGain;
+  TableArgs ta;
+  ta.tables = c->feat_tab;
+  ta.counts = c->feat_cnt;
+  ta.stride = kFeatTableRows;
+  for (int k = 0; k < kFeatMaxIters; k++) {
+    ua.k = k;
+    arm_tail(c, ra, ua);
+    uwt::launch_table_eval(c->stream, launch_sel(c), ra, ta, n_pairs);
+    HIPCHK(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_level_end, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, 0, 1, kFeatInitialError);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_write_out, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, d_poses, d_stats);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
+}  // namespace
+
+int uwt_obtain_patch_points_batch(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const float* kp, const int32_t* n_kp,
+                                  float* pts_out, int32_t cap, int32_t* counts_out) {
+  if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
+  if (!c || !counts_out || cap < 0 || (cap > 0 && !pts_out)) return fail(c, UWT_ERR_INVALID_ARG, "uwt_obtain_patch_points_batch");
+  int st = check_features_args(c, "uwt_obtain_patch_points_batch", n_frames, slots, slots, kp, n_kp);
+  if (st) return st;
+  st = ensure_features(c);
+  if (st) return st;
+  st = upload_pairs(c, n_frames, slots, slots);   // the slot list travels as the pair lists do
+  if (st) return st;
+  st = features_begin(c, n_frames, slots, slots);
+  if (st) return st;
+  st = enqueue_patch_tables(c, n_frames, c->d_ref, kp, n_kp);
+  if (st) return st;
+  std::vector<int> cnt((size_t)n_frames);
+  HIPCHK(c, hipMemcpyAsync(cnt.data(), c->feat_cnt, sizeof(int) * n_frames, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int f = 0; f < n_frames; f++) {
+    counts_out[f] = cnt[(size_t)f];
+    const int m = std::min(cnt[(size_t)f], cap);
+    if (m > 0)
+      HIPCHK(c, hipMemcpyAsync(pts_out + (size_t)f * cap * 4, c->feat_tab + (size_t)f * kFeatTableRows, (size_t)m * 16,
+                               hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return UWT_OK;
+}
+
+int uwt_track_features_batch_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                   const float* kp, const int32_t* n_kp, float* d_poses_out, uwt_stats* d_stats_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !d_poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_track_features_batch_async: null argument");
+  int st = features_enqueue(c, "uwt_track_features_batch_async", n_pairs, ref_slots, tgt_slots, kp, n_kp, d_poses_out,
+                            reinterpret_cast<StatsOut*>(d_stats_out));
+  if (st) return st;
+  return compute_end(c, c->dep_first, c->dep_n);
+}
+
+int uwt_estimate_pose_features_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                     const float* kp, const int32_t* n_kp, float* poses_out, uwt_stats* stats_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_features_batch: null argument");
+  int st = features_enqueue(c, "uwt_estimate_pose_features_batch", n_pairs, ref_slots, tgt_slots, kp, n_kp, c->d_poses, c->d_stats);
+  if (st) return st;
+  std::vector<uwt_stats> tmp((size_t)n_pairs);
+  HIPCHK(c, hipMemcpyAsync(poses_out, c->d_poses, sizeof(float) * 7 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_stats, sizeof(uwt_stats) * n_pairs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int worst = UWT_OK;
+  for (int i = 0; i < n_pairs; i++) {
+    if (stats_out) stats_out[i] = tmp[(size_t)i];
+    if (tmp[(size_t)i].status != UWT_OK && worst == UWT_OK) worst = tmp[(size_t)i].status;
+  }
+  if (worst)
+    return fail(c, UWT_ERR_PAIR_FAILED, std::string("uwt_estimate_pose_features_batch: at least one pair failed, first status: ") +
+                                            uwt_status_string(worst));
   return UWT_OK;
 }
 

@@ -15,13 +15,15 @@
 //   k_resid_hist_v (scale pass with the scale stage in its tail) + k_residual<.., WEIGHTS>   robust weights in the alignment loop;
 //                  k_residual<.., SAMPLER = 1>: bilinear sampler; k_residual<.., DUMP = true, ..>: the per-stage dump forms
 //   k_residual_points, k_points_hist + k_scale_stage, k_points_general   explicit point tables (identity / general path)
+//   k_patch_points_batch + k_table_eval   the live call for a batch of pairs: tables built and evaluated on the device, the update in
+//                  the evaluation's tail
 //   k_ls_sequential   the LS mirror (src/LeastSquares.cpp): every accumulator's f32 chain in the reference's order
 //   k_grad_mag*, k_candidates_batch, k_scan_counts, k_patch_points, k_add_patch_points, k_remap_crop, k_trajectory*   the rows
 //                  next to the path
 //   masked_sums_*  a pixel's 28 f64 sums under an EXEC mask of the valid lanes (no select anywhere in the loop)
 //   load_group_typed   the production loop's plane loads as typed buffer loads (the texture path converts int16 -> f32), every
 //                  vector-memory operation of that loop hand-written with its waits (tools/check_asm_loads.py)
-// The heavy templates are instantiated by the dispatchers of uwt_launch_{residual,general,flow}.hip (uwt_launch.h); the kernels
+// The heavy templates are instantiated by the dispatchers of uwt_launch_{residual,general,flow,points}.hip (uwt_launch.h); the kernels
 // that are not templates are `static`: each translation unit that launches one carries its own copy.
 //
 // Stencil + gather + reduction work with a 6-wide contraction: no MFMA.  Wave = 64 lanes, blocks of 256.
@@ -2341,27 +2343,30 @@ __device__ __forceinline__ void update_solve_wave(const UpdateArgs& a, PairState
 // Ordering without fences: see block_reduce_store_at; the ticket is drawn behind the returned exchanges in program order,
 // the loads are issued behind the returned ticket.
 constexpr int kTailRounds = 4;   // rounds of 8 records a lane has in flight per part (4 x 4 loads)
-__device__ __forceinline__ void tail_update_wave(const ResidualArgs& a, int pair) {
+// The body with the pair's record stride and record count apart: `stride` records per pair in a.partials, the first `count` of
+// them (the blocks that drew tickets) folded.  The order of the additions depends on `count` alone.  tail_update_wave: both are
+// the launch's slice count; k_table_eval: the launch's slice count and the pair's own.
+__device__ __forceinline__ void tail_fold_wave(const ResidualArgs& a, int pair, int stride, int count) {
   __shared__ __attribute__((aligned(16))) double t_sums[kAccFloats + 1];
   __shared__ long long t_isums[2];
   const int lane = (int)threadIdx.x;   // wave 0
   unsigned int ticket = 0;
   if (lane == 0) ticket = __hip_atomic_fetch_add(a.tail.tickets + pair, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   ticket = (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket);
-  if (ticket != (unsigned int)a.slices - 1u) return;
+  if (ticket != (unsigned int)count - 1u) return;
   if (lane == 0) __hip_atomic_store(a.tail.tickets + pair, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int slot = lane & 31, half = lane >> 5;
-  const unsigned long long* g8 = reinterpret_cast<const unsigned long long*>(a.partials + (size_t)pair * a.slices * kRecWords) + slot;
+  const unsigned long long* g8 = reinterpret_cast<const unsigned long long*>(a.partials + (size_t)pair * stride * kRecWords) + slot;
   double cs[4] = {0.0, 0.0, 0.0, 0.0};
   long long is[4] = {0, 0, 0, 0};
-  for (int q0 = 0; q0 < a.slices; q0 += 8 * kTailRounds) {
+  for (int q0 = 0; q0 < count; q0 += 8 * kTailRounds) {
     unsigned long long v[kTailRounds][4];
 #pragma unroll
     for (int r = 0; r < kTailRounds; r++)
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const int q = q0 + 8 * r + half + 2 * j;
-        v[r][j] = q < a.slices ? __hip_atomic_load(g8 + (size_t)q * (kRecWords / 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+        v[r][j] = q < count ? __hip_atomic_load(g8 + (size_t)q * (kRecWords / 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
       }
 #pragma unroll
     for (int r = 0; r < kTailRounds; r++)
@@ -2401,6 +2406,8 @@ __device__ __forceinline__ void tail_update_wave(const ResidualArgs& a, int pair
   update_solve_wave(u, st, t_sums, t_isums, true, lane);
   if (lane == 0) a.tail.state[pair] = st;
 }
+
+__device__ __forceinline__ void tail_update_wave(const ResidualArgs& a, int pair) { tail_fold_wave(a, pair, a.slices, a.slices); }
 
 __device__ __forceinline__ PairState update_compute(const UpdateArgs& a, const uint32_t* __restrict__ recs, const PairState* __restrict__ st_in,
                                                     unsigned char* __restrict__ lds, bool count_active) {
@@ -3122,6 +3129,87 @@ __global__ __launch_bounds__(kBlock) void k_points_general(const ResidualArgs a,
   block_reduce_store<double, true>(acc, sum_r2, n_valid, a.partials + ((size_t)pair * a.slices + blockIdx.x) * kRecWords, err);
 }
 
+// k_table_eval: one launch = one Gauss-Newton evaluation of device-resident tables for a batch of pairs, the update in the
+// launch's tail (the live call, uwt_track_features_batch_async).  grid = (slices, pairs): a.slices is the batch's bound (and the
+// pairs' record stride), pair p's own slice count S_p = max(1, ceil(count_p / kFeatPtsPerBlock)) comes from its producer's count
+// on the device.  Blocks beyond S_p and blocks of a pair that has left the level return at once, without a ticket; the pair's
+// last block folds exactly S_p records (tail_fold_wave) and solves.  The slicing therefore depends on kFeatPtsPerBlock and the
+// pair's own count only, never on the batch it runs in: a pair's pose is the same bits alone or in any batch.
+// Per row: table_row, the nearest sample at table_gather_index and pixel_jacobian — k_residual_points' terms; f64 sums under an
+// EXEC mask of the valid lanes (masked_sums_*), the record through block_reduce_store(.., coherent).
+constexpr int kPatchMaxKeypoints = 200;   // min(num_max_keypoints, 200), src/Tracker.cpp:1192
+constexpr int kPatchMaxRows = 144;        // table rows one key point can add at most (11 x 11 cells, 12 x 12 bound for the float loop)
+struct TableArgs {
+  const float4* tables;   // pair p's rows at tables + p * stride
+  const int* counts;      // pair p's row count (clamped to stride)
+  int stride;             // rows per pair's table
+};
+// rows per block: four per thread.  Measured at 640 x 480, 200 key points per pair: 256 / 512 / 1024 rows per block give 0.62 /
+// 0.86 / 1.07 M alignments/s at 1024 pairs and 0.27 / 0.37 / 0.43 M at 64 (fewer blocks, records and tickets per pair); one
+// pair takes 0.077-0.078 ms with each (profiles/r07/README.md)
+constexpr int kFeatPtsPerBlock = 1024;
+constexpr int kFeatMaxSlices = (kPatchMaxKeypoints * kPatchMaxRows + kFeatPtsPerBlock - 1) / kFeatPtsPerBlock;
+static_assert(kFeatPtsPerBlock % kBlock == 0, "whole rows per thread");
+__host__ __device__ __forceinline__ int table_slices(int rows) { return rows > kFeatPtsPerBlock ? (rows + kFeatPtsPerBlock - 1) / kFeatPtsPerBlock : 1; }
+
+template <int AR, bool UNIT_FACTORS, typename AccT>
+__global__ __launch_bounds__(kBlock) void k_table_eval(const ResidualArgs a, const TableArgs ta) {
+  constexpr bool MASKED = std::is_same<AccT, double>::value;
+  const int pair = (int)blockIdx.y + a.pair_base;
+  const int count = min(ta.counts[pair], ta.stride);
+  const int slices = min(table_slices(count), a.slices);
+  if ((int)blockIdx.x >= slices) return;
+  const PairState st = a.state[pair];
+  if (st.level_done || st.status) return;
+  WarpK K;
+  pose_to_T12(st.pose, K.T);
+  const LevelK L = a.L;
+  const size_t ref_off = (size_t)a.ref_slots[pair] * L.n, tgt_off = (size_t)a.tgt_slots[pair] * L.n;
+  const uint8_t* __restrict__ I1 = a.img + ref_off;
+  const uint8_t* __restrict__ I2 = a.img + tgt_off;
+  const int16_t* __restrict__ GX = a.gx + ref_off;
+  const int16_t* __restrict__ GY = a.gy + ref_off;
+  const float4* __restrict__ tab = ta.tables + (size_t)pair * ta.stride;
+  AccT acc[kAccFloats];
+#pragma unroll
+  for (int i = 0; i < kAccFloats; i++) acc[i] = (AccT)0;
+  double r2d = 0.0;        // MASKED: Σ r² as a 28th f64 sum
+  uint32_t sum_r2 = 0, n_valid = 0;
+#pragma unroll
+  for (int r = 0; r < kFeatPtsPerBlock / kBlock; r++) {
+    const int q = (int)blockIdx.x * kFeatPtsPerBlock + r * kBlock + (int)threadIdx.x;
+    float x2 = 0.f, y2 = 0.f, iz = 0.f;
+    uint32_t i1x = 0;
+    bool ok = q < count;
+    if (ok) ok = table_row<AR>(L, K.T, tab[q], x2, y2, iz, i1x);
+    int ri = 0;
+    float g0 = 0.f, g1 = 0.f;
+    if (ok) {
+      ri = (int)I2[table_gather_index(L, x2, y2)] - (int)I1[i1x];
+      g0 = (float)GX[i1x];
+      g1 = (float)GY[i1x];
+    }
+    float J[6];
+    pixel_jacobian<AR, UNIT_FACTORS>(L, a.zf, a.af, x2, y2, iz, g0, g1, J);
+    if constexpr (MASKED) {
+      const unsigned long long m = __ballot(ok);
+      double Jd[6];
+#pragma unroll
+      for (int k = 0; k < 6; k++) Jd[k] = (double)J[k];
+      masked_sums_lo(acc, Jd, m);
+      masked_sums_hi<0>(acc, r2d, Jd, (double)ri, 0.0, m);
+    } else if (ok) {
+      accumulate(acc, J, ri);
+      sum_r2 += (uint32_t)(ri * ri);
+    }
+    n_valid += ok ? 1u : 0u;
+  }
+  uint32_t* rec = a.partials + ((size_t)pair * a.slices + blockIdx.x) * kRecWords;
+  if constexpr (MASKED) block_reduce_store<AccT, false, double>(acc, r2d, n_valid, rec, (AccT)0, true);
+  else block_reduce_store<AccT>(acc, sum_r2, n_valid, rec, (AccT)0, true);
+  if (threadIdx.x < 64) tail_fold_wave(a, pair, a.slices, slices);   // wave 0 wrote the block's record
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // sparse point producers
 // ------------------------------------------------------------------------------------------------------------
@@ -3241,9 +3329,10 @@ static __global__ __launch_bounds__(1024) void k_scan_counts(const int* __restri
 
 // Tracker::ObtainPatchesPoints (src/Tracker.cpp:1178-1257): level 0, <= 200 key points, 11x11 patches
 // ("patch_size_ - 1 / 2" = 5), x-major inside a patch, key points in order.  One thread per key point counts, a
-// serial prefix orders, the thread then writes its patch.
-static __global__ __launch_bounds__(256) void k_patch_points(const float2* __restrict__ kp, int n_kp, const uint16_t* __restrict__ depth0,
-                                                      int pitch, int w, int h, float4* __restrict__ out, int cap, int* __restrict__ count) {
+// serial prefix orders, the thread then writes its patch.  One block of 256 threads per frame: k_patch_points (one frame),
+// k_patch_points_batch (one block per frame of a batch).
+__device__ __forceinline__ void patch_points_block(const float2* __restrict__ kp, int n_kp, const uint16_t* __restrict__ depth0,
+                                                   int pitch, int w, int h, float4* __restrict__ out, int cap, int* __restrict__ count) {
   __shared__ int cnt[256];
   const int q = threadIdx.x;
   const int start_point = 5;
@@ -3278,6 +3367,23 @@ static __global__ __launch_bounds__(256) void k_patch_points(const float2* __res
           if (o < cap) out[o] = make_float4((float)i, (float)j, z, 1.0f);
           o++;
         }
+}
+
+static __global__ __launch_bounds__(256) void k_patch_points(const float2* __restrict__ kp, int n_kp, const uint16_t* __restrict__ depth0,
+                                                      int pitch, int w, int h, float4* __restrict__ out, int cap, int* __restrict__ count) {
+  patch_points_block(kp, n_kp, depth0, pitch, w, h, out, cap, count);
+}
+
+// The same for a batch of frames, one block each: frame f's key points at kp + f * kPatchMaxKeypoints, its depth plane that of
+// slot slots[f] (depth0: level 0 of slot 0, slot_elems apart; nullptr without depth), its table at out + f * stride (at most
+// stride rows written), its full count at counts[f].
+static __global__ __launch_bounds__(256) void k_patch_points_batch(const float2* __restrict__ kp, const int* __restrict__ n_kp,
+                                                            const int* __restrict__ slots, const uint16_t* __restrict__ depth0,
+                                                            size_t slot_elems, int pitch, int w, int h, float4* __restrict__ out,
+                                                            int stride, int* __restrict__ counts) {
+  const int f = (int)blockIdx.x;
+  patch_points_block(kp + (size_t)f * kPatchMaxKeypoints, n_kp[f], depth0 ? depth0 + (size_t)slots[f] * slot_elems : nullptr, pitch, w,
+                     h, out + (size_t)f * stride, stride, counts + f);
 }
 
 

@@ -1,5 +1,5 @@
 // uwt_launch.h — internal: the launch dispatchers of the heavy kernel templates, one translation unit per family so that the
-// library builds in parallel (uwt_launch_residual.hip, uwt_launch_general.hip, uwt_launch_flow.hip).
+// library builds in parallel (uwt_launch_residual.hip, uwt_launch_general.hip, uwt_launch_flow.hip, uwt_launch_points.hip).
 // A dispatcher picks the instantiation from run-time facts (arithmetic set, depth plane, level width, intrinsics, factors) and
 // enqueues it; it reports nothing — the caller checks hipGetLastError().
 #pragma once
@@ -31,6 +31,13 @@ void launch_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, 
 void launch_points(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const PointsArgs& pa);
 // the same on the general path: k_points_hist + k_scale_stage (weights != 0; the caller cleared the pair's bins), k_points_general
 void launch_points_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const PointsArgs& pa, const GeneralArgs& ga);
+
+// the live call's device-resident tables (uwt_launch_points.hip): ObtainPatchesPoints for a batch of frames, one block each
+// (k_patch_points_batch), and one evaluation of a batch of tables with the update in its tail (k_table_eval; grid a.slices x n_pairs)
+void launch_patch_points_batch(hipStream_t s, int n_frames, const float2* kp, const int* n_kp, const int* slots,
+                               const uint16_t* depth0, size_t slot_elems, int pitch, int w, int h, float4* out, int stride,
+                               int* counts);
+void launch_table_eval(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, int n_pairs);
 
 // the chained flow of a few pairs: k_iterate, k_coarse (up to kCoarseMaxLevels levels in one launch), k_finish
 void launch_iterate(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const IterArgs& ia, int n_pairs);
