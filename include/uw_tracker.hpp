@@ -350,6 +350,34 @@ class Tracker {
     if (st == UWT_OK) last_stats_ = last_batch_stats_.back();
     check(st, "uwt_estimate_pose_features_batch");
   }
+  // Semi-dense tracking for many pairs at once: ObtainCandidatePoints(previous) (src/Tracker.cpp:1314-1362) on the levels the
+  // tracker iterates, then EstimatePose(previous, current) (:362-597) over those tables, under the tracker's params.  Each
+  // previous frame's rigid_transformation_ comes out.  The candidate tables are built and consumed on the device
+  // (previous->candidatePoints_ is left as it is).  At most max_pairs pairs, whose frames must all be bound at once (2 x pairs <=
+  // max_frames for distinct frames); per-pair stats in last_batch_stats().
+  void EstimatePoseCandidatesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, double gradient_threshold = 20.0) {
+    const size_t n = _pairs.size();
+    if (n == 0) return;
+    std::vector<int32_t> a(n), b(n);
+    for (size_t i = 0; i < n; i++) {
+      a[i] = bind(_pairs[i].first);
+      b[i] = bind(_pairs[i].second);
+    }
+    for (size_t i = 0; i < n; i++) {   // binding a later pair's frame may have taken an earlier frame's slot
+      if (!bound(_pairs[i].first) || !bound(_pairs[i].second))
+        throw std::runtime_error("EstimatePoseCandidatesBatch: more frames than slots (max_frames)");
+      if (!_pairs[i].first->obtained_gradients_)
+        throw std::runtime_error("EstimatePoseCandidatesBatch: ApplyGradient(previous) not called (or its slot was reused since)");
+    }
+    std::vector<float> poses(n * 7);
+    last_batch_stats_.assign(n, uwt_stats{});
+    const int st = uwt_estimate_pose_candidates_batch(ctx(), (int32_t)n, a.data(), b.data(), gradient_threshold, poses.data(),
+                                                      last_batch_stats_.data());
+    if (st == UWT_OK || st == UWT_ERR_PAIR_FAILED)
+      for (size_t i = 0; i < n; i++) std::copy(poses.begin() + 7 * i, poses.begin() + 7 * (i + 1), _pairs[i].first->rigid_transformation_.data());
+    if (st == UWT_OK) last_stats_ = last_batch_stats_.back();
+    check(st, "uwt_estimate_pose_candidates_batch");
+  }
   const std::vector<uwt_stats>& last_batch_stats() const { return last_batch_stats_; }
   // EstimatePose over the sparse tables a producer left in previous->candidatePoints_[lvl] (src/Tracker.cpp:401)
   void EstimatePoseOverCandidatePoints(Frame* _previous_frame, Frame* _current_frame) {

@@ -391,7 +391,39 @@ int uwt_estimate_pose_features_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_
                                      const float* keypoints_xy, const int32_t* n_keypoints,
                                      float* poses_out, uwt_stats* stats_out_or_null);
 
-/* ---- next to the path: frame ingest ---------------------------------------------------------------- */
+/* ---- semi-dense tracking for a batch of pairs (candidate tables built and consumed on the device) --------------------- */
+
+/* Tracker::ObtainCandidatePoints(previous) (src/Tracker.cpp:1314-1362) on levels last_level..first_level, then
+ * Tracker::EstimatePose(previous, current) (:362-597) over those tables (read at :401), for n_pairs pairs.  previous =
+ * ref_slots[i], current = tgt_slots[i]; the reference frames must have had uwt_build_pyramids and uwt_apply_gradient, as
+ * uwt_obtain_candidate_points requires.  threshold: GRADIENT_THRESHOLD (20, src/Options.cpp:27).
+ * Tables are built for the iterated levels alone, each on the gw x gh grid the reference's loops walk, with the depth test and
+ * z of uwt_obtain_candidate_points (the reference's at<uchar> read of the 16-bit plane).  The call runs under the context's
+ * first_level, last_level, max_iters, epsilon, gain, z_factor, angle_factor, initial_error, early_exit, handoff_scale_t, arith and
+ * accumulate_f64 — the constants uwt_estimate_pose_points honours — and reads the params without changing them.
+ * weights != 0 or sampler != 0: UWT_ERR_INVALID_ARG with nothing enqueued (robust weights and the bilinear sampler over
+ * candidate tables: uwt_obtain_candidate_points + uwt_estimate_pose_points).  So are 1 <= n_pairs <= max_pairs violated, a slot
+ * out of range, a null list and a non-finite threshold.
+ * For every pair, pose and uwt_stats are the bits uwt_obtain_candidate_points per level followed by uwt_estimate_pose_points
+ * give on the same context (f64 sums, accumulate_f64 = 1; the f32 sums of accumulate_f64 = 0 are grouped by 1024 rows here,
+ * by 8192 there).  A pair's pose depends neither on the batch it runs in, nor on its place there, nor on uwt_tuning.  A pair
+ * with no valid point on a level (a flat reference frame, every candidate on a zero depth byte) gets its status in its own
+ * uwt_stats, as uwt_estimate_pose_points reports it; the other pairs are unaffected.
+ * The tables, their counts and the solver state never leave the device: per level a producer pass (gradient_ and its mean,
+ * per-column counts, an exclusive scan, the ordered write), then per level one launch per Gauss-Newton evaluation with the
+ * update in its tail, k_level_end between levels.  The caller may reuse the pair lists once the call returns.
+ * Results go to DEVICE memory, as in uwt_track_batch_async (d_poses_out: n_pairs x 7 floats, d_stats_out_or_null: n_pairs
+ * uwt_stats), ordered against uwt_upload_frames_async like it.  With early_exit = 0 the call never waits for the device.  With
+ * early_exit = 1 it waits at the early-exit polls as uwt_track_batch_async does (after evaluations first_poll, then twice as
+ * many, ..., of each level, each look taken while the next evaluation runs; no launch for a level once every pair has left
+ * it).  uwt_sync() to wait for the results. */
+int uwt_track_candidates_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                     double threshold, float* d_poses_out, uwt_stats* d_stats_out_or_null);
+/* The same, synchronous, results in host memory (UWT_ERR_PAIR_FAILED when a pair failed, its status in its uwt_stats). */
+int uwt_estimate_pose_candidates_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                       double threshold, float* poses_out, uwt_stats* stats_out_or_null);
+
+/* ---- next to the path: frame ingest---------------------------------------------------------------- */
 
 typedef struct uwt_ingest uwt_ingest;
 

@@ -70,6 +70,7 @@ SYMBOLS = [
     "uwt_ingest_frame", "uwt_update_params", "uwt_get_params", "uwt_ls_accumulate_sse", "uwt_robust_weights",
     "uwt_get_tuning", "uwt_set_tuning",
     "uwt_obtain_patch_points_batch", "uwt_track_features_batch_async", "uwt_estimate_pose_features_batch",
+    "uwt_track_candidates_batch_async", "uwt_estimate_pose_candidates_batch",
 ]
 
 _lib = None
@@ -594,6 +595,26 @@ class Context:
         self._chk(lib().uwt_track_features_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
                                                        _p(n, C.c_int32), C.c_void_p(d_poses_ptr),
                                                        C.c_void_p(d_stats_ptr) if d_stats_ptr else None))
+
+    def estimate_pose_candidates_batch(self, ref_slots, tgt_slots, threshold=20.0, raise_on_pair_failure=False):
+        """Semi-dense tracking for many pairs: Tracker::ObtainCandidatePoints(previous) on every iterated level, then EstimatePose
+        (previous, current) over those tables, under the context's params.  Returns (poses [P, 7], per-pair stats)."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        poses = np.empty((max(ref.size, 1), 7), np.float32)
+        stats = (Stats * max(ref.size, 1))()
+        st = lib().uwt_estimate_pose_candidates_batch(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.c_double(threshold),
+                                                      _p(poses, C.c_float), stats)
+        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+        return poses[:ref.size], [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
+
+    def track_candidates_batch_async(self, ref_slots, tgt_slots, d_poses_ptr, d_stats_ptr=None, threshold=20.0):
+        """The same enqueued on the context stream, results in device memory (d_poses_ptr: P x 7 float32, d_stats_ptr: P x 4
+        int32-sized uwt_stats or None); sync() to wait."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        self._chk(lib().uwt_track_candidates_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.c_double(threshold),
+                                                         C.c_void_p(d_poses_ptr), C.c_void_p(d_stats_ptr) if d_stats_ptr else None))
 
     def add_patch_points(self, lvl, pts, patch_size=5, cap=None):
         """Tracker::AddPatchPointsFeatures (src/Tracker.cpp:599-629).  Returns (table, full count)."""

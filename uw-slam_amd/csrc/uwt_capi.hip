@@ -98,6 +98,17 @@ struct uwt_ctx {
   float* h_feat = nullptr;              // kPairStages blocks of [n (max_pairs ints) | key points (max_pairs x 400 floats)]
   hipEvent_t ev_feat[kPairStages] = {};
   int feat_stage = 0;
+  // semi-dense tracking for a batch of pairs (uwt_track_candidates_batch_async), each buffer grown on use to what a call needs:
+  // every iterated level's tables (gw x gh rows per pair and level) and counts (UWT_MAX_LEVELS x pairs), the producer's work
+  // area for its finest level, and the evaluations' records (the largest level's slice bound per pair)
+  float4* cand_tab = nullptr;
+  size_t cand_tab_bytes = 0;
+  int* cand_cnt = nullptr;
+  size_t cand_cnt_bytes = 0;
+  void* cand_work = nullptr;
+  size_t cand_work_bytes = 0;
+  uint32_t* cand_recs = nullptr;
+  size_t cand_recs_bytes = 0;
   void* stage[2] = {nullptr, nullptr};  // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
   size_t stage_bytes[2] = {0, 0};
   bool profiling = false;
@@ -1189,6 +1200,10 @@ int uwt_destroy(uwt_ctx* c) {
   if (c->feat_kp) (void)hipFree(c->feat_kp);
   if (c->feat_nkp) (void)hipFree(c->feat_nkp);
   if (c->feat_recs) (void)hipFree(c->feat_recs);
+  if (c->cand_tab) (void)hipFree(c->cand_tab);
+  if (c->cand_cnt) (void)hipFree(c->cand_cnt);
+  if (c->cand_work) (void)hipFree(c->cand_work);
+  if (c->cand_recs) (void)hipFree(c->cand_recs);
   if (c->h_feat) (void)hipHostFree(c->h_feat);
   for (hipEvent_t e : c->ev_feat)
     if (e) (void)hipEventDestroy(e);
@@ -2193,14 +2208,23 @@ int ensure_features(uwt_ctx* c) {
 
 // every argument of a batch of frames / pairs, before anything is enqueued: n in 1..max_pairs, the slots in range, the first
 // min(n_keypoints[f], 200) key points of every frame inside level 0 (as uwt_obtain_patch_points)
-int check_features_args(uwt_ctx* c, const char* what, int n, const int32_t* slots_a, const int32_t* slots_b, const float* kp,
-                        const int32_t* n_kp) {
-  if (!slots_a || !slots_b || !kp || !n_kp) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+// the pair lists of a batch call: not null, n in 1..max_pairs, every slot in range
+int check_pair_lists(uwt_ctx* c, const char* what, int n, const int32_t* slots_a, const int32_t* slots_b) {
+  if (!slots_a || !slots_b) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
   if (n < 1 || n > c->p.max_pairs) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": count outside 1..max_pairs");
-  const float w = (float)c->lv[0].gw, h = (float)c->lv[0].gh;   // level 0: grid = image
-  for (int f = 0; f < n; f++) {
+  for (int f = 0; f < n; f++)
     if (slots_a[f] < 0 || slots_a[f] >= c->p.max_frames || slots_b[f] < 0 || slots_b[f] >= c->p.max_frames)
       return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": slot out of range");
+  return UWT_OK;
+}
+
+int check_features_args(uwt_ctx* c, const char* what, int n, const int32_t* slots_a, const int32_t* slots_b, const float* kp,
+                        const int32_t* n_kp) {
+  if (!kp || !n_kp) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  const int st = check_pair_lists(c, what, n, slots_a, slots_b);
+  if (st) return st;
+  const float w = (float)c->lv[0].gw, h = (float)c->lv[0].gh;   // level 0: grid = image
+  for (int f = 0; f < n; f++) {
     if (n_kp[f] < 0) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": negative key point count");
     const float* k = kp + (size_t)f * kFeatKpFloats;
     for (int i = 0; i < std::min(n_kp[f], kPatchMaxKeypoints); i++)
@@ -2355,6 +2379,177 @@ int uwt_estimate_pose_features_batch(uwt_ctx* c, int32_t n_pairs, const int32_t*
   }
   if (worst)
     return fail(c, UWT_ERR_PAIR_FAILED, std::string("uwt_estimate_pose_features_batch: at least one pair failed, first status: ") +
+                                            uwt_status_string(worst));
+  return UWT_OK;
+}
+
+// ---- semi-dense tracking for a batch of pairs: candidate tables built and evaluated on the device ------------------------
+namespace {
+
+// one of the call's device buffers, at least `bytes` (its contents are not kept).  The context stream is drained first: an
+// asynchronous call enqueued before may still read the old buffer.
+int grow(uwt_ctx* c, void** buf, size_t* have, size_t bytes) {
+  if (bytes <= *have) return UWT_OK;
+  if (*buf) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipFree(*buf));
+  }
+  *buf = nullptr;
+  *have = 0;
+  HIPCHK(c, hipMalloc(buf, bytes));
+  *have = bytes;
+  return UWT_OK;
+}
+
+// The candidate producer's work area for n frames on one level, sliced as uwt_obtain_candidate_points_batch slices a batch:
+// row bands enough for a lone frame to spread over the chip, a few rows per thread at least.  [sums | gradient_ planes |
+// (x, band) counts | their offsets]
+struct CandidatesLayout {
+  int bands;
+  size_t o_mag, o_cells, o_off, total;
+};
+CandidatesLayout candidates_work_layout(const LevelK& L, int n) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  CandidatesLayout o;
+  const int col_blocks = (L.gw + kBlock - 1) / kBlock;
+  o.bands = std::max(1, std::min(L.gh / 8, 512 / std::max(1, col_blocks * n)));
+  const size_t m = (size_t)L.gw * o.bands * n;
+  o.o_mag = up(8 * (size_t)n);
+  o.o_cells = o.o_mag + up((size_t)L.n * n);
+  o.o_off = o.o_cells + up(4 * m);
+  o.total = o.o_off + up(4 * m);
+  return o;
+}
+
+// Tracker::ObtainCandidatePoints(previous) on levels last_level..first_level, then Tracker::EstimatePose(previous, current) over
+// those tables, for n_pairs pairs, enqueued on the context stream: k_init_state; per level the slot-list producer (pair i's table
+// at cand_tab + level offset + i * gw * gh, its count at cand_cnt[lvl * n_pairs + i]); per level up to max_iters k_table_eval
+// launches with the update in their tails, then k_level_end; k_write_out.  The only waits are the early-exit polls.
+int candidates_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
+                       float* d_poses, StatsOut* d_stats) {
+  const uwt_params& p = c->p;
+  int st = check_pair_lists(c, what, n_pairs, ref_slots, tgt_slots);
+  if (st) return st;
+  if (!std::isfinite(threshold)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": threshold is not finite");
+  if (p.weights || p.sampler)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": identity weights and the nearest sampler only; robust weights or the "
+                                                            "bilinear sampler over candidate tables: uwt_estimate_pose_points");
+  size_t rows = 0, work = 0, tab_off[UWT_MAX_LEVELS] = {};
+  int smax = 1;
+  for (int l = p.last_level; l <= p.first_level; l++) {
+    const LevelK& L = c->lv[l];
+    tab_off[l] = rows;
+    rows += (size_t)L.gw * L.gh * n_pairs;
+    work = std::max(work, candidates_work_layout(L, n_pairs).total);
+    smax = std::max(smax, table_slices(L.gw * L.gh));
+  }
+  st = grow(c, (void**)&c->cand_tab, &c->cand_tab_bytes, rows * sizeof(float4));
+  if (!st) st = grow(c, (void**)&c->cand_cnt, &c->cand_cnt_bytes, sizeof(int) * UWT_MAX_LEVELS * (size_t)n_pairs);
+  if (!st) st = grow(c, &c->cand_work, &c->cand_work_bytes, work);
+  if (!st) st = grow(c, (void**)&c->cand_recs, &c->cand_recs_bytes, sizeof(uint32_t) * kRecWords * (size_t)smax * n_pairs);
+  if (st) return st;
+  st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
+  if (st) return st;
+  st = features_begin(c, n_pairs, ref_slots, tgt_slots);
+  if (st) return st;
+  const int tb = 128;
+  hipLaunchKernelGGL(k_init_state, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, p.initial_error);
+  HIPCHK(c, hipGetLastError());
+  uint8_t* base = (uint8_t*)c->cand_work;
+  for (int l = p.last_level; l <= p.first_level; l++) {
+    const LevelK& L = c->lv[l];
+    const CandidatesLayout o = candidates_work_layout(L, n_pairs);
+    uwt::CandidatesWork w;
+    w.sums = (unsigned long long*)base;
+    w.mag = base + o.o_mag;
+    w.cells = (int*)(base + o.o_cells);
+    w.offsets = (int*)(base + o.o_off);
+    w.bands = o.bands;
+    HIPCHK(c, hipMemsetAsync(w.sums, 0, 8 * (size_t)n_pairs, c->stream));
+    uwt::launch_candidates_slots(c->stream, L, n_pairs, c->d_ref, c->gx[l], c->gy[l], p.has_depth ? c->depth[l] : nullptr, threshold, w,
+                                 c->cand_tab + tab_off[l], c->cand_cnt + (size_t)l * n_pairs);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
+  for (int lvl = p.first_level; lvl >= p.last_level; lvl--) {
+    const LevelK& L = c->lv[lvl];
+    // the grid's slices: the bound every pair's count obeys, gw x gh rows (the counts stay on the device); also the record stride.
+    // The blocks beyond a pair's own slice count return at once.
+    ResidualArgs ra = residual_args(c, lvl);
+    ra.slices = table_slices(L.gw * L.gh);
+    ra.partials = c->cand_recs;
+    UpdateArgs ua = update_args(c, lvl);
+    ua.slices = ra.slices;
+    ua.partials = c->cand_recs;
+    TableArgs ta;
+    ta.tables = c->cand_tab + tab_off[lvl];
+    ta.counts = c->cand_cnt + (size_t)lvl * n_pairs;
+    ta.stride = L.gw * L.gh;
+    // early exit: the dense batch's schedule (enqueue_estimate) — the count of pairs still on the level after evaluation
+    // first_poll - 1, then after twice as many, ..., each read one evaluation late; no launch once none is left
+    int next_poll = c->tn.first_poll;
+    int pending = -1;
+    for (int k = 0; k < p.max_iters; k++) {
+      ua.k = k;
+      const bool poll = p.early_exit && (k + 1 == next_poll) && (k + 1 < p.max_iters);
+      const int slot = c->poll_seq & 1;
+      ua.active = poll ? c->d_active + slot : nullptr;
+      if (poll) HIPCHK(c, hipMemsetAsync(c->d_active + slot, 0, sizeof(int), c->stream));
+      arm_tail(c, ra, ua);
+      uwt::launch_table_eval(c->stream, launch_sel(c), ra, ta, n_pairs);
+      HIPCHK(c, hipGetLastError());
+      if (pending >= 0) {
+        HIPCHK(c, hipEventSynchronize(c->ev_poll[pending]));
+        const bool none_left = c->h_active[pending] == 0;
+        pending = -1;
+        if (none_left) break;
+      }
+      if (poll) {
+        HIPCHK(c, hipMemcpyAsync(c->h_active + slot, c->d_active + slot, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_poll[slot], c->stream));
+        pending = slot;
+        c->poll_seq++;
+        next_poll *= 2;
+      }
+    }
+    hipLaunchKernelGGL(k_level_end, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, lvl, p.handoff_scale_t,
+                       p.initial_error);
+    HIPCHK(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_write_out, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, d_poses, d_stats);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
+}  // namespace
+
+int uwt_track_candidates_batch_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
+                                     float* d_poses_out, uwt_stats* d_stats_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !d_poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_track_candidates_batch_async: null argument");
+  int st = candidates_enqueue(c, "uwt_track_candidates_batch_async", n_pairs, ref_slots, tgt_slots, threshold, d_poses_out,
+                              reinterpret_cast<StatsOut*>(d_stats_out));
+  if (st) return st;
+  return compute_end(c, c->dep_first, c->dep_n);
+}
+
+int uwt_estimate_pose_candidates_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
+                                       float* poses_out, uwt_stats* stats_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_candidates_batch: null argument");
+  int st = candidates_enqueue(c, "uwt_estimate_pose_candidates_batch", n_pairs, ref_slots, tgt_slots, threshold, c->d_poses, c->d_stats);
+  if (st) return st;
+  std::vector<uwt_stats> tmp((size_t)n_pairs);
+  HIPCHK(c, hipMemcpyAsync(poses_out, c->d_poses, sizeof(float) * 7 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_stats, sizeof(uwt_stats) * n_pairs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int worst = UWT_OK;
+  for (int i = 0; i < n_pairs; i++) {
+    if (stats_out) stats_out[i] = tmp[(size_t)i];
+    if (tmp[(size_t)i].status != UWT_OK && worst == UWT_OK) worst = tmp[(size_t)i].status;
+  }
+  if (worst)
+    return fail(c, UWT_ERR_PAIR_FAILED, std::string("uwt_estimate_pose_candidates_batch: at least one pair failed, first status: ") +
                                             uwt_status_string(worst));
   return UWT_OK;
 }

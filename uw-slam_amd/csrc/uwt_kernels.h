@@ -17,6 +17,7 @@
 //   k_residual_points, k_points_hist + k_scale_stage, k_points_general   explicit point tables (identity / general path)
 //   k_patch_points_batch + k_table_eval   the live call for a batch of pairs: tables built and evaluated on the device, the update in
 //                  the evaluation's tail
+//   k_grad_mag_slots + k_candidates_slots + k_scan_counts, then k_table_eval per level   semi-dense tracking for a batch of pairs
 //   k_ls_sequential   the LS mirror (src/LeastSquares.cpp): every accumulator's f32 chain in the reference's order
 //   k_grad_mag*, k_candidates_batch, k_scan_counts, k_patch_points, k_add_patch_points, k_remap_crop, k_trajectory*   the rows
 //                  next to the path
@@ -3240,13 +3241,15 @@ static __global__ __launch_bounds__(kBlock) void k_grad_mag(const int16_t* __res
   if (threadIdx.x == 0) atomicAdd(sum, (unsigned long long)red[0]);  // integer: order-independent
 }
 
-// Tracker::ObtainCandidatePoints (src/Tracker.cpp:1314-1362) for a batch of frames, many blocks per frame, three passes:
+// Tracker::ObtainCandidatePoints (src/Tracker.cpp:1314-1362) for a batch of frames, many blocks per frame, three passes.
+// Frame f's planes are those of slot first_slot + f (k_grad_mag_batch, k_candidates_batch) or, with a slot list, of slot
+// slots[f] (k_grad_mag_slots, k_candidates_slots: the reference frames of a batch of pairs, uwt_track_candidates_batch_async).
 // gradient_ and its per-frame sum: grid (blocks, frames)
-static __global__ __launch_bounds__(kBlock) void k_grad_mag_batch(const int16_t* __restrict__ gx, const int16_t* __restrict__ gy, int n,
-                                                           int pitch, int iw, int first_slot, uint8_t* __restrict__ mag,
-                                                           unsigned long long* __restrict__ sums) {
+__device__ __forceinline__ void grad_mag_frames(const int16_t* __restrict__ gx, const int16_t* __restrict__ gy, int n, int pitch, int iw,
+                                                const int* __restrict__ slots, int first_slot, uint8_t* __restrict__ mag,
+                                                unsigned long long* __restrict__ sums) {
   const int f = blockIdx.y;
-  const size_t src = (size_t)(first_slot + f) * n, dst = (size_t)f * n;
+  const size_t src = (size_t)(slots ? slots[f] : first_slot + f) * n, dst = (size_t)f * n;
   unsigned int local = 0;
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     const int ax = min(abs((int)gx[src + i]), 255), ay = min(abs((int)gy[src + i]), 255);
@@ -3264,6 +3267,18 @@ static __global__ __launch_bounds__(kBlock) void k_grad_mag_batch(const int16_t*
     __syncthreads();
   }
   if (threadIdx.x == 0) atomicAdd(&sums[f], (unsigned long long)red[0]);  // integer: order-independent
+}
+
+static __global__ __launch_bounds__(kBlock) void k_grad_mag_batch(const int16_t* __restrict__ gx, const int16_t* __restrict__ gy, int n,
+                                                           int pitch, int iw, int first_slot, uint8_t* __restrict__ mag,
+                                                           unsigned long long* __restrict__ sums) {
+  grad_mag_frames(gx, gy, n, pitch, iw, nullptr, first_slot, mag, sums);
+}
+
+static __global__ __launch_bounds__(kBlock) void k_grad_mag_slots(const int16_t* __restrict__ gx, const int16_t* __restrict__ gy, int n,
+                                                           int pitch, int iw, const int* __restrict__ slots, uint8_t* __restrict__ mag,
+                                                           unsigned long long* __restrict__ sums) {
+  grad_mag_frames(gx, gy, n, pitch, iw, slots, 0, mag, sums);
 }
 
 // One thread owns one column x of one row band of one frame and walks its rows top to bottom (a row of the block's
@@ -3299,6 +3314,38 @@ __global__ __launch_bounds__(kBlock) void k_candidates_batch(const uint8_t* __re
     if (WRITE) {
       if (k < cap) o[k] = make_float4((float)x, (float)y, z, 1.0f);
     }
+    k++;
+  }
+  if (!WRITE) counts[(size_t)f * w * bands + (size_t)x * bands + band] = k;
+}
+
+// k_candidates_batch over the pairs' reference frames: frame f's depth plane that of slot slots[f], its table at out + f * w * h,
+// room for every cell of the grid (the bound is never reached).  The body is k_candidates_batch's, written out again so that that
+// kernel's code stays as it is.
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void k_candidates_slots(const uint8_t* __restrict__ mag, const uint16_t* __restrict__ depth,
+                                                             const int* __restrict__ slots, int pitch, int iw, int ih, int w, int h,
+                                                             int bands, const unsigned long long* __restrict__ sums, double threshold,
+                                                             int* __restrict__ counts, const int* __restrict__ offsets,
+                                                             float4* __restrict__ out) {
+  const int f = blockIdx.z, band = blockIdx.y, x = blockIdx.x * kBlock + threadIdx.x;
+  if (x >= w) return;
+  const size_t n = (size_t)pitch * ih;
+  const double thres = (double)sums[f] / (double)((size_t)iw * ih) + threshold;
+  const uint8_t* m = mag + (size_t)f * n;
+  const uint16_t* dp = depth ? depth + (size_t)slots[f] * n : nullptr;
+  const int rows = (h + bands - 1) / bands, y0 = band * rows, y1 = min(y0 + rows, h);
+  int k = WRITE ? offsets[(size_t)f * w * bands + (size_t)x * bands + band] : 0;
+  float4* o = WRITE ? out + (size_t)f * w * h : nullptr;
+  for (int y = y0; y < y1; y++) {
+    if (!((double)m[(size_t)y * pitch + x] > thres)) continue;
+    float z = 1.0f;
+    if (dp) {
+      const uint8_t b = reinterpret_cast<const uint8_t*>(dp + (size_t)y * pitch)[x];
+      if (b == 0) continue;
+      z = (float)b * 0.0002f;
+    }
+    if (WRITE && k < w * h) o[k] = make_float4((float)x, (float)y, z, 1.0f);
     k++;
   }
   if (!WRITE) counts[(size_t)f * w * bands + (size_t)x * bands + band] = k;

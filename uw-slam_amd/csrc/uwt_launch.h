@@ -38,6 +38,18 @@ void launch_patch_points_batch(hipStream_t s, int n_frames, const float2* kp, co
                                const uint16_t* depth0, size_t slot_elems, int pitch, int w, int h, float4* out, int stride,
                                int* counts);
 void launch_table_eval(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, int n_pairs);
+// Tracker::ObtainCandidatePoints on one level for the reference frames of a batch of pairs (frame f = slots[f]): k_grad_mag_slots,
+// k_candidates_slots<false>, k_scan_counts, k_candidates_slots<true>.  w: the producer's work area (candidates_work_layout; its
+// per-frame sums cleared by the caller), frame f's table at out + f * gw * gh, its count at counts[f]
+struct CandidatesWork {
+  unsigned long long* sums;   // n_frames
+  uint8_t* mag;               // n_frames x L.n: gradient_
+  int* cells;                 // n_frames x gw x bands: the (x, band) counts ...
+  int* offsets;               // ... and their exclusive scan
+  int bands;                  // row bands per column
+};
+void launch_candidates_slots(hipStream_t s, const LevelK& L, int n_frames, const int* slots, const int16_t* gx, const int16_t* gy,
+                             const uint16_t* depth, double threshold, const CandidatesWork& w, float4* out, int* counts);
 
 // the chained flow of a few pairs: k_iterate, k_coarse (up to kCoarseMaxLevels levels in one launch), k_finish
 void launch_iterate(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const IterArgs& ia, int n_pairs);

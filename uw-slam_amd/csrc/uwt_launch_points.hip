@@ -1,5 +1,6 @@
-// uwt_launch_points.hip — dispatch of the live call's device-resident tables: the batched patch producer
-// (k_patch_points_batch) and the batched table evaluation (k_table_eval).
+// uwt_launch_points.hip — dispatch of device-resident point tables: the batched patch producer (k_patch_points_batch), the
+// batched candidate producer over a slot list (k_grad_mag_slots, k_candidates_slots, k_scan_counts) and the batched table
+// evaluation (k_table_eval).
 #include "uwt_launch.h"
 
 namespace uwt {
@@ -9,6 +10,18 @@ void launch_patch_points_batch(hipStream_t s, int n_frames, const float2* kp, co
                                int* counts) {
   hipLaunchKernelGGL(k_patch_points_batch, dim3(n_frames), dim3(256), 0, s, kp, n_kp, slots, depth0, slot_elems, pitch, w, h, out,
                      stride, counts);
+}
+
+void launch_candidates_slots(hipStream_t s, const LevelK& L, int n_frames, const int* slots, const int16_t* gx, const int16_t* gy,
+                             const uint16_t* depth, double threshold, const CandidatesWork& w, float4* out, int* counts) {
+  const int mag_blocks = (int)std::min<size_t>(256, ((size_t)L.n + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(k_grad_mag_slots, dim3(mag_blocks, n_frames), dim3(kBlock), 0, s, gx, gy, L.n, L.pitch, L.iw, slots, w.mag, w.sums);
+  const dim3 grid((L.gw + kBlock - 1) / kBlock, w.bands, n_frames);
+  hipLaunchKernelGGL(k_candidates_slots<false>, grid, dim3(kBlock), 0, s, w.mag, depth, slots, L.pitch, L.iw, L.ih, L.gw, L.gh, w.bands,
+                     w.sums, threshold, w.cells, (const int*)nullptr, (float4*)nullptr);
+  hipLaunchKernelGGL(k_scan_counts, dim3(n_frames), dim3(1024), 0, s, w.cells, L.gw * w.bands, w.offsets, counts);
+  hipLaunchKernelGGL(k_candidates_slots<true>, grid, dim3(kBlock), 0, s, w.mag, depth, slots, L.pitch, L.iw, L.ih, L.gw, L.gh, w.bands,
+                     w.sums, threshold, (int*)nullptr, (const int*)w.offsets, out);
 }
 
 void launch_table_eval(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, int n_pairs) {
