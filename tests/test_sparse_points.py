@@ -100,27 +100,38 @@ def _ctx_pair(capi, synth, w, h, seed, depth=False, **over):
 def test_gpu_producers_bit_exact(capi, O, synth, depth):
     w, h = 160, 96
     ctx, ref, tgt, dep = _ctx_pair(capi, synth, w, h, 62, depth)
-    img, dp = ref, dep
-    for lvl in range(5):
-        if lvl:
-            img = O.halve_u8(img)
-            dp = O.halve_u16(dp) if depth else None
-        gx, gy = O.scharr3(img)
-        mag = O.gradient_mag(gx, gy)
-        assert np.array_equal(ctx.gradient_magnitude(0, lvl), mag)
-        for thr in (20.0, 0.0, 300.0):
-            a, na = ctx.obtain_candidate_points(0, lvl, thr)
-            b, nb = O.candidate_points(mag, dp, thr)
-            assert na == nb and np.array_equal(a, b)
-    a, na = ctx.obtain_candidate_points(0, 0, 20.0, cap=10)
-    assert a.shape == (10, 4) and na > 10
+    tdep = None
+    if depth:   # the target frame gets a depth plane of its own (holes elsewhere): a wrong slot offset shows
+        tdep = np.roll(dep, (3, 5), axis=(0, 1))
+        ctx.upload_frames(1, tgt[None], tdep[None])
+        ctx.build_pyramids(1, 1)
+        ctx.apply_gradient(1, 1)
     rng = np.random.default_rng(5)
     kp = np.concatenate([rng.uniform(0, [w - 0.01, h - 0.01], (230, 2)),
                          [[0, 0], [w - 1, h - 1], [4.5, 4.5], [5, 5], [w - 5.5, h - 5.5]]]).astype(np.float32)
-    for k in (kp, kp[:7], kp[:0]):
-        a, na = ctx.obtain_patch_points(0, k)
-        b, nb = O.patch_points(k, dep if depth else None, w, h)
-        assert na == nb and np.array_equal(a, b)
+    for slot, img, dp in ((0, ref, dep), (1, tgt, tdep)):
+        dp0 = dp
+        for lvl in range(5):
+            if lvl:
+                img = O.halve_u8(img)
+                dp = O.halve_u16(dp) if depth else None
+            gx, gy = O.scharr3(img)
+            mag = O.gradient_mag(gx, gy)
+            assert np.array_equal(ctx.gradient_magnitude(slot, lvl), mag)
+            for thr in (20.0, 0.0, 300.0):
+                a, na = ctx.obtain_candidate_points(slot, lvl, thr)
+                b, nb = O.candidate_points(mag, dp, thr)
+                assert na == nb and np.array_equal(a, b)
+        for k in (kp, kp[:7], kp[:0]):
+            a, na = ctx.obtain_patch_points(slot, k)
+            b, nb = O.patch_points(k, dp0, w, h)
+            assert na == nb and np.array_equal(a, b)
+        b, nb = O.patch_points(kp, dp0, w, h)
+        a, na = ctx.obtain_patch_points(slot, kp, cap=10)
+        assert a.shape == (10, 4) and na == nb and np.array_equal(a, b[:10])
+    full, nfull = ctx.obtain_candidate_points(0, 0, 20.0)
+    a, na = ctx.obtain_candidate_points(0, 0, 20.0, cap=10)
+    assert a.shape == (10, 4) and na == nfull > 10 and np.array_equal(a, full[:10])
     with pytest.raises(capi.UwtError):
         ctx.obtain_patch_points(0, np.array([[w + 1.0, 2.0]], np.float32))
 

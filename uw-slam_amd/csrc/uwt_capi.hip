@@ -985,6 +985,25 @@ int upload_pairs(uwt_ctx* c, int n_pairs, const int32_t* ref_slots, const int32_
   return UWT_OK;
 }
 
+// UWT_ERR_PAIR_FAILED, naming the first failing pair's status, when any of a batch call's n pairs failed
+int first_failure(uwt_ctx* c, const char* what, const uwt_stats* stats, int n) {
+  for (int i = 0; i < n; i++)
+    if (stats[i].status != UWT_OK)
+      return fail(c, UWT_ERR_PAIR_FAILED, std::string(what) + ": at least one pair failed, first status: " +
+                                              uwt_status_string(stats[i].status));
+  return UWT_OK;
+}
+
+// the synchronous form of a batch call enqueued with the context's d_poses / d_stats: both copied back, the stream drained
+int read_back_pairs(uwt_ctx* c, const char* what, int n, float* poses_out, uwt_stats* stats_out) {
+  std::vector<uwt_stats> tmp((size_t)n);
+  HIPCHK(c, hipMemcpyAsync(poses_out, c->d_poses, sizeof(float) * 7 * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_stats, sizeof(uwt_stats) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (stats_out) std::copy(tmp.begin(), tmp.end(), stats_out);
+  return first_failure(c, what, tmp.data(), n);
+}
+
 int run_se3_op(uwt_ctx* c, int op, const float* a, int na, const float* b, int nb, float* out, int nout, int* flag) {
   if (!c) return UWT_ERR_INVALID_ARG;
   int st = ensure_scratch(c, 4096);
@@ -1544,15 +1563,8 @@ int uwt_estimate_pose_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slot
     st = prof_collect(c);
     if (st) return st;
   }
-  int worst = UWT_OK;
-  for (int i = 0; i < n_pairs; i++) {
-    if (stats_out) stats_out[i] = tmp[i];
-    if (tmp[i].status != UWT_OK && worst == UWT_OK) worst = tmp[i].status;
-  }
-  if (worst)
-    return fail(c, UWT_ERR_PAIR_FAILED, std::string("uwt_estimate_pose_batch: at least one pair failed, first status: ") +
-                                            uwt_status_string(worst));
-  return UWT_OK;
+  if (stats_out) std::copy(tmp.begin(), tmp.end(), stats_out);
+  return first_failure(c, "uwt_estimate_pose_batch", tmp.data(), n_pairs);
 }
 
 static int track_batch_enqueue(uwt_ctx* c, int32_t first_slot, int32_t n_frames, int32_t grad_refs_only, int32_t n_pairs,
@@ -2040,20 +2052,6 @@ int uwt_estimate_pose_points(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, con
   return UWT_OK;
 }
 
-static int mag_to_scratch(uwt_ctx* c, int slot, int lvl, uint8_t** d_mag, unsigned long long** d_sum) {
-  const size_t n = c->lv[lvl].n;
-  int st = ensure_scratch(c, n + 64 + (size_t)c->lv[lvl].n * 16 + 64);
-  if (st) return st;
-  *d_sum = (unsigned long long*)c->scratch;
-  *d_mag = (uint8_t*)c->scratch + 64;
-  HIPCHK(c, hipMemsetAsync(*d_sum, 0, 8, c->stream));
-  const int blocks = (int)std::min<size_t>(1024, (n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_grad_mag, dim3(blocks), dim3(kBlock), 0, c->stream, c->gx[lvl] + slot * n, c->gy[lvl] + slot * n, (int)n,
-                     c->lv[lvl].pitch, c->lv[lvl].iw, *d_mag, *d_sum);
-  HIPCHK(c, hipGetLastError());
-  return UWT_OK;
-}
-
 int uwt_robust_weights(uwt_ctx* c, const float* residuals, int32_t n, int32_t kind, float* weights_out, float* median_out,
                        float* mad_out) {
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
@@ -2077,15 +2075,81 @@ int uwt_robust_weights(uwt_ctx* c, const float* residuals, int32_t n, int32_t ki
   return UWT_OK;
 }
 
+// ---- the sparse point producers: per-stage entries over a slot list in the scratch ------------------------------------
+namespace {
+
+// the first min(n, 200) key points (x, y) inside level 0 (its grid is its image)
+int check_keypoints(uwt_ctx* c, const char* what, const float* kp, int n) {
+  const float w = (float)c->lv[0].gw, h = (float)c->lv[0].gh;
+  for (int i = 0; i < std::min(n, kPatchMaxKeypoints); i++)
+    if (!(kp[2 * i] >= 0.f && kp[2 * i] < w && kp[2 * i + 1] >= 0.f && kp[2 * i + 1] < h))
+      return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key point outside the image");
+  return UWT_OK;
+}
+
+// The candidate producer's work area for n frames on one level: row bands enough for a lone frame to spread over the chip, a few
+// rows per thread at least.  [sums | gradient_ planes | (x, band) counts | their offsets]
+struct CandidatesLayout {
+  int bands;
+  size_t o_mag, o_cells, o_off, total;
+};
+CandidatesLayout candidates_work_layout(const LevelK& L, int n) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  CandidatesLayout o;
+  const int col_blocks = (L.gw + kBlock - 1) / kBlock;
+  o.bands = std::max(1, std::min(L.gh / 8, 512 / std::max(1, col_blocks * n)));
+  const size_t m = (size_t)L.gw * o.bands * n;
+  o.o_mag = up(8 * (size_t)n);
+  o.o_cells = o.o_mag + up((size_t)L.n * n);
+  o.o_off = o.o_cells + up(4 * m);
+  o.total = o.o_off + up(4 * m);
+  return o;
+}
+
+// the device slot list first .. first + n - 1 at d (a fill per slot: no host buffer, no staging copy)
+int stage_slots(uwt_ctx* c, int* d, int first, int n) {
+  for (int f = 0; f < n; f++) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(d + f), first + f, 1, c->stream));
+  return UWT_OK;
+}
+
+// Tracker::ObtainCandidatePoints on level lvl for the frames of the device slot list d_slots (n), enqueued on the context stream:
+// the work area at `work` (candidates_work_layout), frame f's table at out + f * gw * gh, its full count at counts[f]
+int enqueue_candidates(uwt_ctx* c, int lvl, int n, const int* d_slots, double threshold, void* work, float4* out, int* counts) {
+  const LevelK& L = c->lv[lvl];
+  const CandidatesLayout o = candidates_work_layout(L, n);
+  uint8_t* base = (uint8_t*)work;
+  uwt::CandidatesWork w;
+  w.sums = (unsigned long long*)base;
+  w.mag = base + o.o_mag;
+  w.cells = (int*)(base + o.o_cells);
+  w.offsets = (int*)(base + o.o_off);
+  w.bands = o.bands;
+  HIPCHK(c, hipMemsetAsync(w.sums, 0, 8 * (size_t)n, c->stream));
+  uwt::launch_candidates_slots(c->stream, L, n, d_slots, c->gx[lvl], c->gy[lvl], c->p.has_depth ? c->depth[lvl] : nullptr, threshold, w,
+                               out, counts);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
+}  // namespace
+
 int uwt_gradient_magnitude(uwt_ctx* c, int32_t slot, int32_t lvl, uint8_t* mag_out) {
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
   if (!c || !mag_out || !slot_range_ok(c, slot, 1) || lvl < 0 || lvl >= c->p.n_levels)
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_gradient_magnitude");
-  uint8_t* d_mag;
-  unsigned long long* d_sum;
-  int st = mag_to_scratch(c, slot, lvl, &d_mag, &d_sum);
-  if (st) return st;
   const LevelK& L = c->lv[lvl];   // gradient_[lvl]: the level's image, img_w x img_h
+  int st = ensure_scratch(c, 256 + (size_t)L.n);
+  if (st) return st;
+  st = compute_begin(c, slot, 1);
+  if (st) return st;
+  // scratch: [sum (not read) | slot list | the plane]
+  unsigned long long* d_sum = (unsigned long long*)c->scratch;
+  int* d_slot = (int*)((uint8_t*)c->scratch + 64);
+  uint8_t* d_mag = (uint8_t*)c->scratch + 256;
+  st = stage_slots(c, d_slot, slot, 1);
+  if (st) return st;
+  uwt::launch_grad_mag(c->stream, L, 1, d_slot, c->gx[lvl], c->gy[lvl], d_mag, d_sum);
+  HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpy2DAsync(mag_out, L.iw, d_mag, L.pitch, L.iw, L.ih, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return UWT_OK;
@@ -2098,46 +2162,28 @@ int uwt_obtain_candidate_points_batch(uwt_ctx* c, int32_t first_slot, int32_t n_
       lvl >= c->p.n_levels)
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_obtain_candidate_points_batch");
   const LevelK& L = c->lv[lvl];
-  const int w = L.gw, h = L.gh;   // the point grid the reference's loops walk (src/Tracker.cpp:1334-1335)
-  const size_t n = L.n;
-  const int kcap = (int)std::min<size_t>((size_t)cap, (size_t)w * h);
-  // row bands: enough blocks for a lone frame to spread over the chip, a few rows per thread at least
-  const int col_blocks = (w + kBlock - 1) / kBlock;
-  int bands = std::max(1, std::min(h / 8, 512 / std::max(1, col_blocks * n_frames)));
-  const size_t m = (size_t)w * bands;
+  const size_t rows = (size_t)L.gw * L.gh;   // a frame's table: a row for every cell of the point grid (the bound is never reached)
+  // scratch: [the producer's work area | slot list | counts | tables]
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_sums = 0, o_mag = up(8 * (size_t)n_frames), o_cnt = o_mag + up(n * n_frames), o_off = o_cnt + up(4 * m * n_frames),
-               o_tot = o_off + up(4 * m * n_frames), o_out = o_tot + up(4 * (size_t)n_frames),
-               total = o_out + (size_t)n_frames * kcap * 16 + 256;
-  int st = ensure_scratch(c, total);
+  const size_t o_slots = candidates_work_layout(L, n_frames).total, o_cnt = o_slots + up(4 * (size_t)n_frames),
+               o_tab = o_cnt + up(4 * (size_t)n_frames);
+  int st = ensure_scratch(c, o_tab + (size_t)n_frames * rows * sizeof(float4));
   if (st) return st;
   st = compute_begin(c, first_slot, n_frames);
   if (st) return st;
   uint8_t* base = (uint8_t*)c->scratch;
-  unsigned long long* d_sums = (unsigned long long*)(base + o_sums);
-  uint8_t* d_mag = base + o_mag;
+  int* d_slots = (int*)(base + o_slots);
   int* d_cnt = (int*)(base + o_cnt);
-  int* d_off = (int*)(base + o_off);
-  int* d_tot = (int*)(base + o_tot);
-  float4* d_out = (float4*)(base + o_out);
-  const uint16_t* d_depth = c->p.has_depth ? c->depth[lvl] : nullptr;
-  HIPCHK(c, hipMemsetAsync(d_sums, 0, 8 * (size_t)n_frames, c->stream));
-  const int mag_blocks = (int)std::min<size_t>(256, (n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_grad_mag_batch, dim3(mag_blocks, n_frames), dim3(kBlock), 0, c->stream, c->gx[lvl], c->gy[lvl], (int)n, L.pitch,
-                     L.iw, first_slot, d_mag, d_sums);
-  const dim3 grid(col_blocks, bands, n_frames);
-  hipLaunchKernelGGL(k_candidates_batch<false>, grid, dim3(kBlock), 0, c->stream, d_mag, d_depth, first_slot, L.pitch, L.iw, L.ih, w, h, bands,
-                     d_sums, threshold, d_cnt, (const int*)nullptr, (float4*)nullptr, 0);
-  hipLaunchKernelGGL(k_scan_counts, dim3(n_frames), dim3(1024), 0, c->stream, d_cnt, (int)m, d_off, d_tot);
-  hipLaunchKernelGGL(k_candidates_batch<true>, grid, dim3(kBlock), 0, c->stream, d_mag, d_depth, first_slot, L.pitch, L.iw, L.ih, w, h, bands,
-                     d_sums, threshold, (int*)nullptr, d_off, d_out, kcap);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(counts_out, d_tot, 4 * (size_t)n_frames, hipMemcpyDeviceToHost, c->stream));
+  float4* d_tab = (float4*)(base + o_tab);
+  st = stage_slots(c, d_slots, first_slot, n_frames);
+  if (!st) st = enqueue_candidates(c, lvl, n_frames, d_slots, threshold, base, d_tab, d_cnt);
+  if (st) return st;
+  HIPCHK(c, hipMemcpyAsync(counts_out, d_cnt, sizeof(int) * n_frames, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int f = 0; f < n_frames; f++) {   // each frame's points are packed at f * cap in the caller's buffer
-    const int k = std::min(counts_out[f], kcap);
+    const int k = std::min(counts_out[f], cap);
     if (k > 0)
-      HIPCHK(c, hipMemcpyAsync(pts_out + (size_t)f * cap * 4, d_out + (size_t)f * kcap, (size_t)k * 16, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(pts_out + (size_t)f * cap * 4, d_tab + (size_t)f * rows, (size_t)k * 16, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return UWT_OK;
@@ -2154,28 +2200,33 @@ int uwt_obtain_patch_points(uwt_ctx* c, int32_t slot, const float* kp, int32_t n
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
   if (!c || !count_out || n_kp < 0 || (n_kp > 0 && !kp) || cap < 0 || (cap > 0 && !pts_out) || !slot_range_ok(c, slot, 1))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_obtain_patch_points");
-  const int w = c->lv[0].gw, h = c->lv[0].gh;   // level 0: grid = image
-  for (int i = 0; i < std::min(n_kp, 200); i++)
-    if (!(kp[2 * i] >= 0.f && kp[2 * i] < (float)w && kp[2 * i + 1] >= 0.f && kp[2 * i + 1] < (float)h))
-      return fail(c, UWT_ERR_INVALID_ARG, "uwt_obtain_patch_points: key point outside the image");
-  const int nk = std::min(n_kp, 200);
-  const int kcap = std::min(cap, 200 * 144);
-  int st = ensure_scratch(c, 4096 + (size_t)kcap * 16 + 64);
+  int st = check_keypoints(c, "uwt_obtain_patch_points", kp, n_kp);
   if (st) return st;
+  const int stride = std::min(cap, kPatchMaxKeypoints * kPatchMaxRows);   // rows written at most
+  st = ensure_scratch(c, 4096 + (size_t)stride * sizeof(float4));
+  if (st) return st;
+  st = compute_begin(c, slot, 1);
+  if (st) return st;
+  // scratch: [key point count | slot list | row count | key points at 64 | table at 4096]; the count, the slot and the key points
+  // go down in one copy
+  int* d_hdr = (int*)c->scratch;
   float2* d_kp = (float2*)((uint8_t*)c->scratch + 64);
-  float4* d_out = (float4*)((uint8_t*)c->scratch + 4096);
-  int* d_cnt = (int*)c->scratch;
-  if (nk) HIPCHK(c, hipMemcpyAsync(d_kp, kp, (size_t)nk * 8, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_patch_points, dim3(1), dim3(256), 0, c->stream, d_kp, nk,
-                     c->p.has_depth ? c->depth[0] + (size_t)slot * c->lv[0].n : nullptr, c->lv[0].pitch, w, h, d_out, kcap, d_cnt);
+  float4* d_tab = (float4*)((uint8_t*)c->scratch + 4096);
+  const int hdr[2] = {std::min(n_kp, kPatchMaxKeypoints), slot};
+  std::vector<uint8_t> in(64 + sizeof(float2) * hdr[0]);
+  std::memcpy(in.data(), hdr, sizeof(hdr));
+  if (hdr[0]) std::memcpy(in.data() + 64, kp, sizeof(float2) * hdr[0]);
+  HIPCHK(c, hipMemcpyAsync(d_hdr, in.data(), in.size(), hipMemcpyHostToDevice, c->stream));
+  uwt::launch_patch_points_batch(c->stream, 1, d_kp, d_hdr, d_hdr + 1, c->p.has_depth ? c->depth[0] : nullptr, (size_t)c->lv[0].n,
+                                 c->lv[0].pitch, c->lv[0].gw, c->lv[0].gh, d_tab, stride, d_hdr + 2);
   HIPCHK(c, hipGetLastError());
   int cnt = 0;
-  HIPCHK(c, hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&cnt, d_hdr + 2, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   *count_out = cnt;
-  const int m = std::min(cnt, kcap);
+  const int m = std::min(cnt, stride);
   if (m > 0) {
-    HIPCHK(c, hipMemcpyAsync(pts_out, d_out, (size_t)m * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pts_out, d_tab, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return UWT_OK;
@@ -2186,10 +2237,23 @@ namespace {
 
 constexpr int kFeatTableRows = kPatchMaxKeypoints * kPatchMaxRows;   // rows of one pair's table at most (its stride)
 constexpr int kFeatKpFloats = 2 * kPatchMaxKeypoints;                 // one frame's key points as the caller passes them
-// Tracker::EstimatePoseFeatures' locals (src/Tracker.cpp:633-640, 661, 834): level 0 only, 10 iterations, epsilon 1e-3,
-// last_error 50000, z_factor 0.002, no angle factor, gain 1 (Residuals.mul(1)); identity weights (:769), round() (:746).
-constexpr int kFeatMaxIters = 10;
-constexpr float kFeatEpsilon = 0.001f, kFeatInitialError = 50000.0f, kFeatZFactor = 0.002f, kFeatAngleFactor = 1.0f, kFeatGain = 1.0f;
+
+// the context's params with Tracker::EstimatePoseFeatures' locals (src/Tracker.cpp:633-640, 661, 834, 856): level 0 only, 10
+// iterations, epsilon 1e-3, last_error 50000, z_factor 0.002, no angle factor, gain 1 (Residuals.mul(1)), the early exit of :782,
+// the hand-off of :856; identity weights (:769), round() (:746)
+uwt_params feature_params(const uwt_ctx* c) {
+  uwt_params q = c->p;
+  q.first_level = q.last_level = 0;
+  q.max_iters = 10;
+  q.epsilon = 0.001f;
+  q.initial_error = 50000.0f;
+  q.z_factor = 0.002f;
+  q.angle_factor = 1.0f;
+  q.gain = 1.0f;
+  q.early_exit = 1;
+  q.handoff_scale_t = 1;
+  return q;
+}
 
 // the live call's device buffers and staging ring, allocated on the first call (uwt_destroy frees them); each piece is retried
 // on its own after a failed allocation
@@ -2206,8 +2270,6 @@ int ensure_features(uwt_ctx* c) {
   return UWT_OK;
 }
 
-// every argument of a batch of frames / pairs, before anything is enqueued: n in 1..max_pairs, the slots in range, the first
-// min(n_keypoints[f], 200) key points of every frame inside level 0 (as uwt_obtain_patch_points)
 // the pair lists of a batch call: not null, n in 1..max_pairs, every slot in range
 int check_pair_lists(uwt_ctx* c, const char* what, int n, const int32_t* slots_a, const int32_t* slots_b) {
   if (!slots_a || !slots_b) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
@@ -2221,21 +2283,19 @@ int check_pair_lists(uwt_ctx* c, const char* what, int n, const int32_t* slots_a
 int check_features_args(uwt_ctx* c, const char* what, int n, const int32_t* slots_a, const int32_t* slots_b, const float* kp,
                         const int32_t* n_kp) {
   if (!kp || !n_kp) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  const int st = check_pair_lists(c, what, n, slots_a, slots_b);
+  int st = check_pair_lists(c, what, n, slots_a, slots_b);
   if (st) return st;
-  const float w = (float)c->lv[0].gw, h = (float)c->lv[0].gh;   // level 0: grid = image
   for (int f = 0; f < n; f++) {
     if (n_kp[f] < 0) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": negative key point count");
-    const float* k = kp + (size_t)f * kFeatKpFloats;
-    for (int i = 0; i < std::min(n_kp[f], kPatchMaxKeypoints); i++)
-      if (!(k[2 * i] >= 0.f && k[2 * i] < w && k[2 * i + 1] >= 0.f && k[2 * i + 1] < h))
-        return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key point outside the image");
+    st = check_keypoints(c, what, kp + (size_t)f * kFeatKpFloats, n_kp[f]);
+    if (st) return st;
   }
   return UWT_OK;
 }
 
-// the slot range a call reads, ordered behind the asynchronous uploads into it (compute_begin)
-int features_begin(uwt_ctx* c, int n, const int32_t* slots_a, const int32_t* slots_b) {
+// the slot range the pair lists of a call name, ordered behind the asynchronous uploads into it (compute_begin) and kept as the
+// range the call depends on (compute_end)
+int compute_begin_pairs(uwt_ctx* c, int n, const int32_t* slots_a, const int32_t* slots_b) {
   int lo = c->p.max_frames, hi = 0;
   for (int i = 0; i < n; i++) {
     lo = std::min(lo, std::min(slots_a[i], slots_b[i]));
@@ -2269,9 +2329,75 @@ int enqueue_patch_tables(uwt_ctx* c, int n, const int* d_slots, const float* kp,
   return UWT_OK;
 }
 
-// System::Tracking's live call for n_pairs pairs, enqueued on the context stream: k_init_state, the producer over the reference
-// frames, kFeatMaxIters k_table_eval launches (each evaluates every pair still iterating and updates it in its tail; a pair that
-// has left makes the later launches return at once), k_level_end, k_write_out.  No read-back, no wait for the device.
+// One level of device-resident tables: pair i's rows at ta.tables + i * ta.stride, its count at ta.counts[i]; slices: the grid's
+// bound on a table's slices, which every pair's count obeys (the counts stay on the device), and the record stride
+struct TableLevel {
+  TableArgs ta;
+  int slices;
+};
+
+// EstimatePose over device-resident tables for n_pairs pairs (their lists on the device), enqueued on the context stream under
+// the solver constants q, levels q.first_level .. q.last_level (lv[lvl] each): k_init_state, then per level up to q.max_iters
+// k_table_eval launches (each evaluates every pair still iterating and updates it in its tail; a pair that has left the level
+// makes the later launches return at once) and k_level_end; k_write_out.  The blocks beyond a pair's own slice count return at
+// once.  polls: the host reads the early exits back on the dense batch's schedule (enqueue_estimate) — the count
+// of pairs still on the level after evaluation first_poll - 1, then after twice as many, ..., each read one evaluation late; no
+// launch once none is left.  Without, nothing here waits for the device.
+int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const TableLevel* lv, uint32_t* recs, bool polls,
+                           float* d_poses, StatsOut* d_stats) {
+  const int tb = 128, blocks = (n_pairs + tb - 1) / tb;
+  hipLaunchKernelGGL(k_init_state, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, q.initial_error);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
+  for (int lvl = q.first_level; lvl >= q.last_level; lvl--) {
+    ResidualArgs ra = residual_args(c, lvl);
+    ra.zf = q.z_factor;
+    ra.af = q.angle_factor;
+    ra.gain = q.gain;
+    ra.slices = lv[lvl].slices;
+    ra.partials = recs;
+    UpdateArgs ua = update_args(c, lvl);
+    ua.partials = recs;
+    ua.slices = ra.slices;
+    ua.max_iters = q.max_iters;
+    ua.early_exit = q.early_exit;
+    ua.epsilon = q.epsilon;
+    ua.gain = q.gain;
+    int next_poll = c->tn.first_poll;
+    int pending = -1;
+    for (int k = 0; k < q.max_iters; k++) {
+      ua.k = k;
+      const bool poll = polls && (k + 1 == next_poll) && (k + 1 < q.max_iters);
+      const int slot = c->poll_seq & 1;
+      ua.active = poll ? c->d_active + slot : nullptr;
+      if (poll) HIPCHK(c, hipMemsetAsync(c->d_active + slot, 0, sizeof(int), c->stream));
+      arm_tail(c, ra, ua);
+      uwt::launch_table_eval(c->stream, launch_sel(c), ra, lv[lvl].ta, n_pairs);
+      HIPCHK(c, hipGetLastError());
+      if (pending >= 0) {
+        HIPCHK(c, hipEventSynchronize(c->ev_poll[pending]));
+        const bool none_left = c->h_active[pending] == 0;
+        pending = -1;
+        if (none_left) break;
+      }
+      if (poll) {
+        HIPCHK(c, hipMemcpyAsync(c->h_active + slot, c->d_active + slot, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_poll[slot], c->stream));
+        pending = slot;
+        c->poll_seq++;
+        next_poll *= 2;
+      }
+    }
+    hipLaunchKernelGGL(k_level_end, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, lvl, q.handoff_scale_t, q.initial_error);
+    HIPCHK(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_write_out, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, d_poses, d_stats);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
+// System::Tracking's live call for n_pairs pairs, enqueued on the context stream: the producer over the reference frames, then
+// enqueue_table_estimate under feature_params, which the host never polls.  No read-back, no wait for the device.
 int features_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, const float* kp,
                      const int32_t* n_kp, float* d_poses, StatsOut* d_stats) {
   int st = check_features_args(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp);
@@ -2280,46 +2406,15 @@ int features_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* r
   if (st) return st;
   st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
   if (st) return st;
-  st = features_begin(c, n_pairs, ref_slots, tgt_slots);
+  st = compute_begin_pairs(c, n_pairs, ref_slots, tgt_slots);
   if (st) return st;
-  // the grid's slices: the batch's bound on a table's rows (the producer's counts stay on the device); also the record stride
-  int rows = 0;
-  for (int i = 0; i < n_pairs; i++) rows = std::max(rows, std::min(n_kp[i], kPatchMaxKeypoints) * kPatchMaxRows);
-  const int slices = table_slices(rows);
-  const int tb = 128;
-  hipLaunchKernelGGL(k_init_state, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, kFeatInitialError);
-  HIPCHK(c, hipGetLastError());
   st = enqueue_patch_tables(c, n_pairs, c->d_ref, kp, n_kp);
   if (st) return st;
-  HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
-  ResidualArgs ra = residual_args(c, 0);
-  ra.zf = kFeatZFactor;
-  ra.af = kFeatAngleFactor;
-  ra.gain = kFeatGain;
-  ra.slices = slices;
-  ra.partials = c->feat_recs;
-  UpdateArgs ua = update_args(c, 0);
-  ua.partials = c->feat_recs;
-  ua.slices = slices;
-  ua.max_iters = kFeatMaxIters;
-  ua.early_exit = 1;
-  ua.epsilon = kFeatEpsilon;
-  ua.gain = kFeatGain;
-  TableArgs ta;
-  ta.tables = c->feat_tab;
-  ta.counts = c->feat_cnt;
-  ta.stride = kFeatTableRows;
-  for (int k = 0; k < kFeatMaxIters; k++) {
-    ua.k = k;
-    arm_tail(c, ra, ua);
-    uwt::launch_table_eval(c->stream, launch_sel(c), ra, ta, n_pairs);
-    HIPCHK(c, hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_level_end, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, 0, 1, kFeatInitialError);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_write_out, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, d_poses, d_stats);
-  HIPCHK(c, hipGetLastError());
-  return UWT_OK;
+  // the grid's slices: the batch's bound on a table's rows
+  int rows = 0;
+  for (int i = 0; i < n_pairs; i++) rows = std::max(rows, std::min(n_kp[i], kPatchMaxKeypoints) * kPatchMaxRows);
+  const TableLevel lv0 = {{c->feat_tab, c->feat_cnt, kFeatTableRows}, table_slices(rows)};
+  return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, d_poses, d_stats);
 }
 
 }  // namespace
@@ -2334,7 +2429,7 @@ int uwt_obtain_patch_points_batch(uwt_ctx* c, int32_t n_frames, const int32_t* s
   if (st) return st;
   st = upload_pairs(c, n_frames, slots, slots);   // the slot list travels as the pair lists do
   if (st) return st;
-  st = features_begin(c, n_frames, slots, slots);
+  st = compute_begin_pairs(c, n_frames, slots, slots);
   if (st) return st;
   st = enqueue_patch_tables(c, n_frames, c->d_ref, kp, n_kp);
   if (st) return st;
@@ -2366,21 +2461,10 @@ int uwt_estimate_pose_features_batch(uwt_ctx* c, int32_t n_pairs, const int32_t*
                                      const float* kp, const int32_t* n_kp, float* poses_out, uwt_stats* stats_out) {
   if (c) (void)hipSetDevice(c->p.device);
   if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_features_batch: null argument");
-  int st = features_enqueue(c, "uwt_estimate_pose_features_batch", n_pairs, ref_slots, tgt_slots, kp, n_kp, c->d_poses, c->d_stats);
+  const char* what = "uwt_estimate_pose_features_batch";
+  int st = features_enqueue(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp, c->d_poses, c->d_stats);
   if (st) return st;
-  std::vector<uwt_stats> tmp((size_t)n_pairs);
-  HIPCHK(c, hipMemcpyAsync(poses_out, c->d_poses, sizeof(float) * 7 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_stats, sizeof(uwt_stats) * n_pairs, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  int worst = UWT_OK;
-  for (int i = 0; i < n_pairs; i++) {
-    if (stats_out) stats_out[i] = tmp[(size_t)i];
-    if (tmp[(size_t)i].status != UWT_OK && worst == UWT_OK) worst = tmp[(size_t)i].status;
-  }
-  if (worst)
-    return fail(c, UWT_ERR_PAIR_FAILED, std::string("uwt_estimate_pose_features_batch: at least one pair failed, first status: ") +
-                                            uwt_status_string(worst));
-  return UWT_OK;
+  return read_back_pairs(c, what, n_pairs, poses_out, stats_out);
 }
 
 // ---- semi-dense tracking for a batch of pairs: candidate tables built and evaluated on the device ------------------------
@@ -2401,30 +2485,10 @@ int grow(uwt_ctx* c, void** buf, size_t* have, size_t bytes) {
   return UWT_OK;
 }
 
-// The candidate producer's work area for n frames on one level, sliced as uwt_obtain_candidate_points_batch slices a batch:
-// row bands enough for a lone frame to spread over the chip, a few rows per thread at least.  [sums | gradient_ planes |
-// (x, band) counts | their offsets]
-struct CandidatesLayout {
-  int bands;
-  size_t o_mag, o_cells, o_off, total;
-};
-CandidatesLayout candidates_work_layout(const LevelK& L, int n) {
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  CandidatesLayout o;
-  const int col_blocks = (L.gw + kBlock - 1) / kBlock;
-  o.bands = std::max(1, std::min(L.gh / 8, 512 / std::max(1, col_blocks * n)));
-  const size_t m = (size_t)L.gw * o.bands * n;
-  o.o_mag = up(8 * (size_t)n);
-  o.o_cells = o.o_mag + up((size_t)L.n * n);
-  o.o_off = o.o_cells + up(4 * m);
-  o.total = o.o_off + up(4 * m);
-  return o;
-}
-
 // Tracker::ObtainCandidatePoints(previous) on levels last_level..first_level, then Tracker::EstimatePose(previous, current) over
-// those tables, for n_pairs pairs, enqueued on the context stream: k_init_state; per level the slot-list producer (pair i's table
-// at cand_tab + level offset + i * gw * gh, its count at cand_cnt[lvl * n_pairs + i]); per level up to max_iters k_table_eval
-// launches with the update in their tails, then k_level_end; k_write_out.  The only waits are the early-exit polls.
+// those tables, for n_pairs pairs, enqueued on the context stream: per level the slot-list producer (pair i's table at cand_tab +
+// level offset + i * gw * gh, its count at cand_cnt[lvl * n_pairs + i]), then enqueue_table_estimate under the context's params,
+// polled under early_exit.  The only waits are the early-exit polls.
 int candidates_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
                        float* d_poses, StatsOut* d_stats) {
   const uwt_params& p = c->p;
@@ -2450,75 +2514,18 @@ int candidates_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t*
   if (st) return st;
   st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
   if (st) return st;
-  st = features_begin(c, n_pairs, ref_slots, tgt_slots);
+  st = compute_begin_pairs(c, n_pairs, ref_slots, tgt_slots);
   if (st) return st;
-  const int tb = 128;
-  hipLaunchKernelGGL(k_init_state, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, p.initial_error);
-  HIPCHK(c, hipGetLastError());
-  uint8_t* base = (uint8_t*)c->cand_work;
+  TableLevel lv[UWT_MAX_LEVELS];
   for (int l = p.last_level; l <= p.first_level; l++) {
-    const LevelK& L = c->lv[l];
-    const CandidatesLayout o = candidates_work_layout(L, n_pairs);
-    uwt::CandidatesWork w;
-    w.sums = (unsigned long long*)base;
-    w.mag = base + o.o_mag;
-    w.cells = (int*)(base + o.o_cells);
-    w.offsets = (int*)(base + o.o_off);
-    w.bands = o.bands;
-    HIPCHK(c, hipMemsetAsync(w.sums, 0, 8 * (size_t)n_pairs, c->stream));
-    uwt::launch_candidates_slots(c->stream, L, n_pairs, c->d_ref, c->gx[l], c->gy[l], p.has_depth ? c->depth[l] : nullptr, threshold, w,
-                                 c->cand_tab + tab_off[l], c->cand_cnt + (size_t)l * n_pairs);
-    HIPCHK(c, hipGetLastError());
+    float4* tab = c->cand_tab + tab_off[l];
+    int* cnt = c->cand_cnt + (size_t)l * n_pairs;
+    st = enqueue_candidates(c, l, n_pairs, c->d_ref, threshold, c->cand_work, tab, cnt);
+    if (st) return st;
+    const int cells = c->lv[l].gw * c->lv[l].gh;   // the bound every pair's count obeys
+    lv[l] = {{tab, cnt, cells}, table_slices(cells)};
   }
-  HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
-  for (int lvl = p.first_level; lvl >= p.last_level; lvl--) {
-    const LevelK& L = c->lv[lvl];
-    // the grid's slices: the bound every pair's count obeys, gw x gh rows (the counts stay on the device); also the record stride.
-    // The blocks beyond a pair's own slice count return at once.
-    ResidualArgs ra = residual_args(c, lvl);
-    ra.slices = table_slices(L.gw * L.gh);
-    ra.partials = c->cand_recs;
-    UpdateArgs ua = update_args(c, lvl);
-    ua.slices = ra.slices;
-    ua.partials = c->cand_recs;
-    TableArgs ta;
-    ta.tables = c->cand_tab + tab_off[lvl];
-    ta.counts = c->cand_cnt + (size_t)lvl * n_pairs;
-    ta.stride = L.gw * L.gh;
-    // early exit: the dense batch's schedule (enqueue_estimate) — the count of pairs still on the level after evaluation
-    // first_poll - 1, then after twice as many, ..., each read one evaluation late; no launch once none is left
-    int next_poll = c->tn.first_poll;
-    int pending = -1;
-    for (int k = 0; k < p.max_iters; k++) {
-      ua.k = k;
-      const bool poll = p.early_exit && (k + 1 == next_poll) && (k + 1 < p.max_iters);
-      const int slot = c->poll_seq & 1;
-      ua.active = poll ? c->d_active + slot : nullptr;
-      if (poll) HIPCHK(c, hipMemsetAsync(c->d_active + slot, 0, sizeof(int), c->stream));
-      arm_tail(c, ra, ua);
-      uwt::launch_table_eval(c->stream, launch_sel(c), ra, ta, n_pairs);
-      HIPCHK(c, hipGetLastError());
-      if (pending >= 0) {
-        HIPCHK(c, hipEventSynchronize(c->ev_poll[pending]));
-        const bool none_left = c->h_active[pending] == 0;
-        pending = -1;
-        if (none_left) break;
-      }
-      if (poll) {
-        HIPCHK(c, hipMemcpyAsync(c->h_active + slot, c->d_active + slot, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_poll[slot], c->stream));
-        pending = slot;
-        c->poll_seq++;
-        next_poll *= 2;
-      }
-    }
-    hipLaunchKernelGGL(k_level_end, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, lvl, p.handoff_scale_t,
-                       p.initial_error);
-    HIPCHK(c, hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_write_out, dim3((n_pairs + tb - 1) / tb), dim3(tb), 0, c->stream, c->state, n_pairs, d_poses, d_stats);
-  HIPCHK(c, hipGetLastError());
-  return UWT_OK;
+  return enqueue_table_estimate(c, n_pairs, p, lv, c->cand_recs, p.early_exit != 0, d_poses, d_stats);
 }
 
 }  // namespace
@@ -2537,21 +2544,10 @@ int uwt_estimate_pose_candidates_batch(uwt_ctx* c, int32_t n_pairs, const int32_
                                        float* poses_out, uwt_stats* stats_out) {
   if (c) (void)hipSetDevice(c->p.device);
   if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_candidates_batch: null argument");
-  int st = candidates_enqueue(c, "uwt_estimate_pose_candidates_batch", n_pairs, ref_slots, tgt_slots, threshold, c->d_poses, c->d_stats);
+  const char* what = "uwt_estimate_pose_candidates_batch";
+  int st = candidates_enqueue(c, what, n_pairs, ref_slots, tgt_slots, threshold, c->d_poses, c->d_stats);
   if (st) return st;
-  std::vector<uwt_stats> tmp((size_t)n_pairs);
-  HIPCHK(c, hipMemcpyAsync(poses_out, c->d_poses, sizeof(float) * 7 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_stats, sizeof(uwt_stats) * n_pairs, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  int worst = UWT_OK;
-  for (int i = 0; i < n_pairs; i++) {
-    if (stats_out) stats_out[i] = tmp[(size_t)i];
-    if (tmp[(size_t)i].status != UWT_OK && worst == UWT_OK) worst = tmp[(size_t)i].status;
-  }
-  if (worst)
-    return fail(c, UWT_ERR_PAIR_FAILED, std::string("uwt_estimate_pose_candidates_batch: at least one pair failed, first status: ") +
-                                            uwt_status_string(worst));
-  return UWT_OK;
+  return read_back_pairs(c, what, n_pairs, poses_out, stats_out);
 }
 
 int uwt_add_patch_points(uwt_ctx* c, int32_t lvl, const float* pts, int32_t n_pts, int32_t patch_size, float* pts_out,

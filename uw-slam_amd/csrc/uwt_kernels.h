@@ -18,9 +18,9 @@
 //   k_patch_points_batch + k_table_eval   the live call for a batch of pairs: tables built and evaluated on the device, the update in
 //                  the evaluation's tail
 //   k_grad_mag_slots + k_candidates_slots + k_scan_counts, then k_table_eval per level   semi-dense tracking for a batch of pairs
+//                  (the producers of these two calls also serve the per-stage entries, over a slot list of their own)
 //   k_ls_sequential   the LS mirror (src/LeastSquares.cpp): every accumulator's f32 chain in the reference's order
-//   k_grad_mag*, k_candidates_batch, k_scan_counts, k_patch_points, k_add_patch_points, k_remap_crop, k_trajectory*   the rows
-//                  next to the path
+//   k_add_patch_points, k_remap_crop, k_trajectory*   the rows next to the path
 //   masked_sums_*  a pixel's 28 f64 sums under an EXEC mask of the valid lanes (no select anywhere in the loop)
 //   load_group_typed   the production loop's plane loads as typed buffer loads (the texture path converts int16 -> f32), every
 //                  vector-memory operation of that loop hand-written with its waits (tools/check_asm_loads.py)
@@ -3215,41 +3215,17 @@ __global__ __launch_bounds__(kBlock) void k_table_eval(const ResidualArgs a, con
 // sparse point producers
 // ------------------------------------------------------------------------------------------------------------
 
-// gradient_ = addWeighted(convertScaleAbs(gx), 0.5, convertScaleAbs(gy), 0.5) (src/Tracker.cpp:1139-1142), u8,
-// plus its integer sum for cuda::meanStdDev (:1325).  (a + b)/2 with cvRound's round-half-to-even.
-// n = pitch * ih plane elements, laid out like the gradient planes; the sum runs over the image's iw columns alone (the pad
-// columns of a pitched row hold nothing of the image).
-static __global__ __launch_bounds__(kBlock) void k_grad_mag(const int16_t* __restrict__ gx, const int16_t* __restrict__ gy, int n,
-                                                     int pitch, int iw, uint8_t* __restrict__ mag,
-                                                     unsigned long long* __restrict__ sum) {
-  unsigned int local = 0;
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-    const int ax = min(abs((int)gx[i]), 255), ay = min(abs((int)gy[i]), 255);
-    const int s = ax + ay;
-    int m = s >> 1;
-    if (s & 1) m += (m & 1);
-    mag[i] = (uint8_t)m;
-    if (i % pitch < iw) local += (unsigned int)m;
-  }
-  __shared__ unsigned int red[kBlock];
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int st = kBlock / 2; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(sum, (unsigned long long)red[0]);  // integer: order-independent
-}
-
-// Tracker::ObtainCandidatePoints (src/Tracker.cpp:1314-1362) for a batch of frames, many blocks per frame, three passes.
-// Frame f's planes are those of slot first_slot + f (k_grad_mag_batch, k_candidates_batch) or, with a slot list, of slot
-// slots[f] (k_grad_mag_slots, k_candidates_slots: the reference frames of a batch of pairs, uwt_track_candidates_batch_async).
-// gradient_ and its per-frame sum: grid (blocks, frames)
-__device__ __forceinline__ void grad_mag_frames(const int16_t* __restrict__ gx, const int16_t* __restrict__ gy, int n, int pitch, int iw,
-                                                const int* __restrict__ slots, int first_slot, uint8_t* __restrict__ mag,
-                                                unsigned long long* __restrict__ sums) {
+// Tracker::ObtainCandidatePoints (src/Tracker.cpp:1314-1362) for a batch of frames, many blocks per frame, three passes;
+// frame f's planes are those of slot slots[f].
+// gradient_ = addWeighted(convertScaleAbs(gx), 0.5, convertScaleAbs(gy), 0.5) (src/Tracker.cpp:1139-1142), u8, plus its
+// integer sum for cuda::meanStdDev (:1325).  (a + b)/2 with cvRound's round-half-to-even.  n = pitch * ih plane elements, laid
+// out like the gradient planes; the sum runs over the image's iw columns alone (the pad columns of a pitched row hold nothing of
+// the image).  Grid (blocks, frames).
+static __global__ __launch_bounds__(kBlock) void k_grad_mag_slots(const int16_t* __restrict__ gx, const int16_t* __restrict__ gy, int n,
+                                                           int pitch, int iw, const int* __restrict__ slots, uint8_t* __restrict__ mag,
+                                                           unsigned long long* __restrict__ sums) {
   const int f = blockIdx.y;
-  const size_t src = (size_t)(slots ? slots[f] : first_slot + f) * n, dst = (size_t)f * n;
+  const size_t src = (size_t)slots[f] * n, dst = (size_t)f * n;
   unsigned int local = 0;
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     const int ax = min(abs((int)gx[src + i]), 255), ay = min(abs((int)gy[src + i]), 255);
@@ -3269,59 +3245,13 @@ __device__ __forceinline__ void grad_mag_frames(const int16_t* __restrict__ gx, 
   if (threadIdx.x == 0) atomicAdd(&sums[f], (unsigned long long)red[0]);  // integer: order-independent
 }
 
-static __global__ __launch_bounds__(kBlock) void k_grad_mag_batch(const int16_t* __restrict__ gx, const int16_t* __restrict__ gy, int n,
-                                                           int pitch, int iw, int first_slot, uint8_t* __restrict__ mag,
-                                                           unsigned long long* __restrict__ sums) {
-  grad_mag_frames(gx, gy, n, pitch, iw, nullptr, first_slot, mag, sums);
-}
-
-static __global__ __launch_bounds__(kBlock) void k_grad_mag_slots(const int16_t* __restrict__ gx, const int16_t* __restrict__ gy, int n,
-                                                           int pitch, int iw, const int* __restrict__ slots, uint8_t* __restrict__ mag,
-                                                           unsigned long long* __restrict__ sums) {
-  grad_mag_frames(gx, gy, n, pitch, iw, slots, 0, mag, sums);
-}
-
 // One thread owns one column x of one row band of one frame and walks its rows top to bottom (a row of the block's
 // columns is one coalesced read); a cell is kept iff gradient_ > mean + threshold and, with a depth plane, the byte the
 // reference reads there is not zero (src/Tracker.cpp:1336-1347).  WRITE = false: counts[f][x * bands + band];
 // WRITE = true: the points, at the offsets an exclusive scan of the counts in that (x, band) order gives — which is the
-// reference's order, x outer, y inner (src/Tracker.cpp:1334-1335).
-template <bool WRITE>
-__global__ __launch_bounds__(kBlock) void k_candidates_batch(const uint8_t* __restrict__ mag, const uint16_t* __restrict__ depth,
-                                                             int first_slot, int pitch, int iw, int ih, int w, int h, int bands,
-                                                             const unsigned long long* __restrict__ sums, double threshold,
-                                                             int* __restrict__ counts, const int* __restrict__ offsets,
-                                                             float4* __restrict__ out, int cap) {
-  // w x h: the level's point grid (w_[lvl] x h_[lvl], the loops of :1334-1335); iw x ih: its image (the mean of :1324 runs over
-  // the whole gradient_ Mat); rows of `pitch` elements
-  const int f = blockIdx.z, band = blockIdx.y, x = blockIdx.x * kBlock + threadIdx.x;
-  if (x >= w) return;
-  const size_t n = (size_t)pitch * ih;
-  const double thres = (double)sums[f] / (double)((size_t)iw * ih) + threshold;  // cuda::meanStdDev mean + GRADIENT_THRESHOLD (:1325-1327)
-  const uint8_t* m = mag + (size_t)f * n;
-  const uint16_t* dp = depth ? depth + (size_t)(first_slot + f) * n : nullptr;
-  const int rows = (h + bands - 1) / bands, y0 = band * rows, y1 = min(y0 + rows, h);
-  int k = WRITE ? offsets[(size_t)f * w * bands + (size_t)x * bands + band] : 0;
-  float4* o = WRITE ? out + (size_t)f * cap : nullptr;
-  for (int y = y0; y < y1; y++) {
-    if (!((double)m[(size_t)y * pitch + x] > thres)) continue;
-    float z = 1.0f;
-    if (dp) {  // the reference indexes the 16-bit plane through at<uchar> (:1339, :1344): byte x of row y
-      const uint8_t b = reinterpret_cast<const uint8_t*>(dp + (size_t)y * pitch)[x];
-      if (b == 0) continue;
-      z = (float)b * 0.0002f;
-    }
-    if (WRITE) {
-      if (k < cap) o[k] = make_float4((float)x, (float)y, z, 1.0f);
-    }
-    k++;
-  }
-  if (!WRITE) counts[(size_t)f * w * bands + (size_t)x * bands + band] = k;
-}
-
-// k_candidates_batch over the pairs' reference frames: frame f's depth plane that of slot slots[f], its table at out + f * w * h,
-// room for every cell of the grid (the bound is never reached).  The body is k_candidates_batch's, written out again so that that
-// kernel's code stays as it is.
+// reference's order, x outer, y inner (src/Tracker.cpp:1334-1335).  w x h: the level's point grid (w_[lvl] x h_[lvl], the loops
+// of :1334-1335); iw x ih: its image (the mean of :1324 runs over the whole gradient_ Mat); rows of `pitch` elements.  Frame f's
+// table at out + f * w * h: room for every cell of the grid (the bound is never reached).
 template <bool WRITE>
 __global__ __launch_bounds__(kBlock) void k_candidates_slots(const uint8_t* __restrict__ mag, const uint16_t* __restrict__ depth,
                                                              const int* __restrict__ slots, int pitch, int iw, int ih, int w, int h,
@@ -3331,7 +3261,7 @@ __global__ __launch_bounds__(kBlock) void k_candidates_slots(const uint8_t* __re
   const int f = blockIdx.z, band = blockIdx.y, x = blockIdx.x * kBlock + threadIdx.x;
   if (x >= w) return;
   const size_t n = (size_t)pitch * ih;
-  const double thres = (double)sums[f] / (double)((size_t)iw * ih) + threshold;
+  const double thres = (double)sums[f] / (double)((size_t)iw * ih) + threshold;  // cuda::meanStdDev mean + GRADIENT_THRESHOLD (:1325-1327)
   const uint8_t* m = mag + (size_t)f * n;
   const uint16_t* dp = depth ? depth + (size_t)slots[f] * n : nullptr;
   const int rows = (h + bands - 1) / bands, y0 = band * rows, y1 = min(y0 + rows, h);
@@ -3340,7 +3270,7 @@ __global__ __launch_bounds__(kBlock) void k_candidates_slots(const uint8_t* __re
   for (int y = y0; y < y1; y++) {
     if (!((double)m[(size_t)y * pitch + x] > thres)) continue;
     float z = 1.0f;
-    if (dp) {
+    if (dp) {  // the reference indexes the 16-bit plane through at<uchar> (:1339, :1344): byte x of row y
       const uint8_t b = reinterpret_cast<const uint8_t*>(dp + (size_t)y * pitch)[x];
       if (b == 0) continue;
       z = (float)b * 0.0002f;
@@ -3376,8 +3306,7 @@ static __global__ __launch_bounds__(1024) void k_scan_counts(const int* __restri
 
 // Tracker::ObtainPatchesPoints (src/Tracker.cpp:1178-1257): level 0, <= 200 key points, 11x11 patches
 // ("patch_size_ - 1 / 2" = 5), x-major inside a patch, key points in order.  One thread per key point counts, a
-// serial prefix orders, the thread then writes its patch.  One block of 256 threads per frame: k_patch_points (one frame),
-// k_patch_points_batch (one block per frame of a batch).
+// serial prefix orders, the thread then writes its patch.  One block of 256 threads per frame.
 __device__ __forceinline__ void patch_points_block(const float2* __restrict__ kp, int n_kp, const uint16_t* __restrict__ depth0,
                                                    int pitch, int w, int h, float4* __restrict__ out, int cap, int* __restrict__ count) {
   __shared__ int cnt[256];
@@ -3416,12 +3345,7 @@ __device__ __forceinline__ void patch_points_block(const float2* __restrict__ kp
         }
 }
 
-static __global__ __launch_bounds__(256) void k_patch_points(const float2* __restrict__ kp, int n_kp, const uint16_t* __restrict__ depth0,
-                                                      int pitch, int w, int h, float4* __restrict__ out, int cap, int* __restrict__ count) {
-  patch_points_block(kp, n_kp, depth0, pitch, w, h, out, cap, count);
-}
-
-// The same for a batch of frames, one block each: frame f's key points at kp + f * kPatchMaxKeypoints, its depth plane that of
+// A batch of frames, one block each: frame f's key points at kp + f * kPatchMaxKeypoints, its depth plane that of
 // slot slots[f] (depth0: level 0 of slot 0, slot_elems apart; nullptr without depth), its table at out + f * stride (at most
 // stride rows written), its full count at counts[f].
 static __global__ __launch_bounds__(256) void k_patch_points_batch(const float2* __restrict__ kp, const int* __restrict__ n_kp,

@@ -32,15 +32,21 @@ void launch_points(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, c
 // the same on the general path: k_points_hist + k_scale_stage (weights != 0; the caller cleared the pair's bins), k_points_general
 void launch_points_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const PointsArgs& pa, const GeneralArgs& ga);
 
-// the live call's device-resident tables (uwt_launch_points.hip): ObtainPatchesPoints for a batch of frames, one block each
-// (k_patch_points_batch), and one evaluation of a batch of tables with the update in its tail (k_table_eval; grid a.slices x n_pairs)
+// The sparse point producers and device-resident tables (uwt_launch_points.hip); the only launches of the producers, for the
+// batched calls and the per-stage entries alike.  Frame f of a producer is slot slots[f] (a device list).
+// ObtainPatchesPoints for a batch of frames, one block each (k_patch_points_batch), and one evaluation of a batch of tables with the
+// update in its tail (k_table_eval; grid a.slices x n_pairs)
 void launch_patch_points_batch(hipStream_t s, int n_frames, const float2* kp, const int* n_kp, const int* slots,
                                const uint16_t* depth0, size_t slot_elems, int pitch, int w, int h, float4* out, int stride,
                                int* counts);
 void launch_table_eval(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, int n_pairs);
-// Tracker::ObtainCandidatePoints on one level for the reference frames of a batch of pairs (frame f = slots[f]): k_grad_mag_slots,
-// k_candidates_slots<false>, k_scan_counts, k_candidates_slots<true>.  w: the producer's work area (candidates_work_layout; its
-// per-frame sums cleared by the caller), frame f's table at out + f * gw * gh, its count at counts[f]
+// gradient_ of one level for a batch of frames (k_grad_mag_slots): frame f's plane at mag + f * L.n, its sum added to sums[f]
+// (cleared by the caller)
+void launch_grad_mag(hipStream_t s, const LevelK& L, int n_frames, const int* slots, const int16_t* gx, const int16_t* gy, uint8_t* mag,
+                     unsigned long long* sums);
+// Tracker::ObtainCandidatePoints on one level for a batch of frames: launch_grad_mag, k_candidates_slots<false>, k_scan_counts,
+// k_candidates_slots<true>.  w: the producer's work area (candidates_work_layout; its per-frame sums cleared by the caller), frame
+// f's table at out + f * gw * gh, its count at counts[f]
 struct CandidatesWork {
   unsigned long long* sums;   // n_frames
   uint8_t* mag;               // n_frames x L.n: gradient_

@@ -1,6 +1,6 @@
-// uwt_launch_points.hip — dispatch of device-resident point tables: the batched patch producer (k_patch_points_batch), the
-// batched candidate producer over a slot list (k_grad_mag_slots, k_candidates_slots, k_scan_counts) and the batched table
-// evaluation (k_table_eval).
+// uwt_launch_points.hip — dispatch of the sparse point producers over a slot list, for the batched calls and the per-stage entries:
+// the patch producer (k_patch_points_batch), gradient_ (k_grad_mag_slots) and the candidate producer (k_candidates_slots,
+// k_scan_counts); and of the batched table evaluation (k_table_eval).
 #include "uwt_launch.h"
 
 namespace uwt {
@@ -12,10 +12,15 @@ void launch_patch_points_batch(hipStream_t s, int n_frames, const float2* kp, co
                      stride, counts);
 }
 
+void launch_grad_mag(hipStream_t s, const LevelK& L, int n_frames, const int* slots, const int16_t* gx, const int16_t* gy, uint8_t* mag,
+                     unsigned long long* sums) {
+  const int blocks = (int)std::min<size_t>(256, ((size_t)L.n + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(k_grad_mag_slots, dim3(blocks, n_frames), dim3(kBlock), 0, s, gx, gy, L.n, L.pitch, L.iw, slots, mag, sums);
+}
+
 void launch_candidates_slots(hipStream_t s, const LevelK& L, int n_frames, const int* slots, const int16_t* gx, const int16_t* gy,
                              const uint16_t* depth, double threshold, const CandidatesWork& w, float4* out, int* counts) {
-  const int mag_blocks = (int)std::min<size_t>(256, ((size_t)L.n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_grad_mag_slots, dim3(mag_blocks, n_frames), dim3(kBlock), 0, s, gx, gy, L.n, L.pitch, L.iw, slots, w.mag, w.sums);
+  launch_grad_mag(s, L, n_frames, slots, gx, gy, w.mag, w.sums);
   const dim3 grid((L.gw + kBlock - 1) / kBlock, w.bands, n_frames);
   hipLaunchKernelGGL(k_candidates_slots<false>, grid, dim3(kBlock), 0, s, w.mag, depth, slots, L.pitch, L.iw, L.ih, L.gw, L.gh, w.bands,
                      w.sums, threshold, w.cells, (const int*)nullptr, (float4*)nullptr);
