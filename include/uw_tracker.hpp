@@ -20,6 +20,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -152,6 +153,7 @@ class Frame {
   bool obtained_candidatePoints_ = false;
   SE3 rigid_transformation_;
   std::vector<float> keypoints_;                         // x0 y0 x1 y1 ... (cv::KeyPoint::pt of Frame::keypoints_)
+  int n_matches_ = 0;                                    // include/System.h:93
   std::vector<float> candidatePoints_[PYRAMID_LEVELS];   // N x 4 [x y z w] per level when a sparse producer ran
   int slot_ = -1;                 // device frame slot while bound; -1 again once the slot has gone to another frame
   Tracker* tracker_ = nullptr;    // the tracker that holds the slot
@@ -494,6 +496,73 @@ class Tracker {
 inline Frame::~Frame() {
   if (tracker_) tracker_->forget(this);
 }
+
+// include/Tracker.h:65-88 — the matching half of RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258): knnMatch in both
+// directions, ratioTest twice and symmetryTest on the GPU (uwt_match_descriptors_batch); getGoodKeypoints and the assignment of
+// :247-254 on the host.  NOT here, the caller's: detection and description (cuda::SURF_CUDA / cuda::ORB — descriptors are an
+// argument) and ransacTest (cv::findFundamentalMat draws from OpenCV's RNG), which the caller runs, or skips, between
+// MatchDescriptors and MatchAndSetKeypoints and hands over as an inlier mask.
+class RobustMatcher {
+ public:
+  explicit RobustMatcher(Tracker* tracker) : tracker_(tracker) {}
+
+  // symMatches of one pair (:202-236), ascending queryIdx.  float rows (n x dim, m x dim) are matched under L2 (SURF, :199), byte
+  // rows under Hamming (ORB, :221).
+  std::vector<uwt_match> MatchDescriptors(const float* desc_prev, int n, const float* desc_cur, int m, int dim) {
+    return match(UWT_NORM_L2, desc_prev, n, desc_cur, m, dim, sizeof(float));
+  }
+  std::vector<uwt_match> MatchDescriptors(const uint8_t* desc_prev, int n, const uint8_t* desc_cur, int m, int dim) {
+    return match(UWT_NORM_HAMMING, desc_prev, n, desc_cur, m, dim, 1);
+  }
+  // :260-270; keypoints as Frame::keypoints_ holds them (x0 y0 x1 y1 ...): [0] the previous frame's, [1] the current one's
+  static std::array<std::vector<float>, 2> getGoodKeypoints(const std::vector<uwt_match>& goodMatches,
+                                                            const std::array<std::vector<float>, 2>& keypoints) {
+    std::array<std::vector<float>, 2> good;
+    for (const uwt_match& mt : goodMatches) {
+      const size_t q = (size_t)mt.query_idx, t = (size_t)mt.train_idx;
+      if (2 * q + 1 >= keypoints[0].size() || 2 * t + 1 >= keypoints[1].size()) throw std::out_of_range("getGoodKeypoints: match index");
+      good[0].insert(good[0].end(), {keypoints[0][2 * q], keypoints[0][2 * q + 1]});
+      good[1].insert(good[1].end(), {keypoints[1][2 * t], keypoints[1][2 * t + 1]});
+    }
+    return good;
+  }
+  // :247-254 after the caller's optional ransacTest: goodMatches (symMatches, or their inliers), getGoodKeypoints, then keypoints_
+  // and n_matches_ of both frames.  Tracker::EstimatePoseFeaturesBatch can follow directly.  n_matches_ feeds the caller's
+  // `n_matches_ < 110` rule (src/System.cpp:208), which stays with the caller.
+  static void SetKeypoints(Frame* _previous_frame, Frame* _current_frame, const std::vector<uwt_match>& goodMatches,
+                           const std::array<std::vector<float>, 2>& keypoints) {
+    std::array<std::vector<float>, 2> good = getGoodKeypoints(goodMatches, keypoints);
+    _previous_frame->n_matches_ = _current_frame->n_matches_ = (int)goodMatches.size();
+    _previous_frame->keypoints_ = std::move(good[0]);
+    _current_frame->keypoints_ = std::move(good[1]);
+  }
+  template <typename T>
+  void MatchAndSetKeypoints(Frame* _previous_frame, Frame* _current_frame, const T* desc_prev, int n, const T* desc_cur, int m, int dim,
+                            const std::array<std::vector<float>, 2>& keypoints) {
+    SetKeypoints(_previous_frame, _current_frame, MatchDescriptors(desc_prev, n, desc_cur, m, dim), keypoints);
+  }
+
+  float ratio_ = 0.65f;   // include/Tracker.h:80
+
+ private:
+  std::vector<uwt_match> match(int norm, const void* a, int n, const void* b, int m, int dim, size_t elem) {
+    if (n < 0 || m < 0 || dim < 1) throw std::invalid_argument("MatchDescriptors: negative count or dim < 1");
+    const int cap = std::max(1, std::max(n, m));
+    const size_t row = (size_t)dim * elem;
+    std::vector<unsigned char> q((size_t)cap * row, 0), t((size_t)cap * row, 0);   // one fixed-stride block per set
+    if (n) std::memcpy(q.data(), a, (size_t)n * row);
+    if (m) std::memcpy(t.data(), b, (size_t)m * row);
+    std::vector<uwt_match> out((size_t)cap);
+    int32_t count = 0;
+    const int32_t nq = n, nt = m;
+    const int st = uwt_match_descriptors_batch(tracker_->ctx(), 1, norm, dim, q.data(), &nq, t.data(), &nt, cap, ratio_, out.data(), &count);
+    if (st != UWT_OK)
+      throw std::runtime_error(std::string("uwt_match_descriptors_batch: ") + uwt_status_string(st) + " (" + uwt_last_error(tracker_->ctx()) + ")");
+    out.resize((size_t)count);
+    return out;
+  }
+  Tracker* tracker_;
+};
 
 // Four packed floats in place of __m128 where SSE is absent (LS::updateSSE's operands, include/LeastSquares.h:42).
 struct f4 {

@@ -423,6 +423,66 @@ int uwt_track_candidates_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_
 int uwt_estimate_pose_candidates_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
                                        double threshold, float* poses_out, uwt_stats* stats_out_or_null);
 
+/* ---- descriptor matching for a batch of pairs: the matching half of RobustMatcher::DetectAndTrackFeatures -------------- */
+
+/* System::Tracking's second call, robust_matcher_->DetectAndTrackFeatures(previous, current, usekeypoints) (src/System.cpp:203,
+ * src/Tracker.cpp:171-258), has four parts.  Built here: matcher->knnMatch(.., 2) in both directions (:202-203, :224-225), the two
+ * ratioTest calls and symmetryTest (:52-102, :229-236).  NOT built, the caller's: detection and description (cuda::SURF_CUDA /
+ * cuda::ORB, :184-222 — descriptors come from the caller) and ransacTest (:106-169, cv::findFundamentalMat draws from OpenCV's RNG);
+ * getGoodKeypoints (:260-270) is a host gather in the mirrors (include/uw_tracker.hpp, uw-slam_amd/tracker.py).
+ *
+ * Per pair: a query set A (n rows, the previous frame) and a train set B (m rows, the current frame) of descriptors of `dim`
+ * elements.
+ * Distance, as cv::DMatch::distance, a float:
+ *   UWT_NORM_L2       dim floats per row (SURF: 64, extended 128):  s = 0.f; for k = 0 .. dim-1 { d = a[k] - b[k]; s = s + d * d; }
+ *                     dist = sqrtf(s) — every step in f32, in that order, no FMA, sqrtf correctly rounded.  OpenCV's CUDA
+ *                     brute-force matcher sums the same squared differences in an order of its own, which is not pinned here (no
+ *                     OpenCV build is): its distances may differ from these in the last bits.  The |a|^2 + |b|^2 - 2ab
+ *                     expansion is NOT used: on real descriptors it is a different function.
+ *   UWT_NORM_HAMMING  dim bytes per row (ORB: 32): the popcount of the XOR, converted to float.  Exact.
+ * 2-NN, knnMatch(query, train, k = 2): for query row i, idx0 = argmin_j dist(i, j), idx1 = argmin_{j != idx0} dist(i, j); a tie goes
+ * to the LOWEST j in both (a sequential scan with <).  With m < 2 the row has fewer than two neighbours: idx1 = -1, d1 = 0 (and
+ * idx0 = -1, d0 = 0 when m = 0).  dist(i, j) is the same bits seen from either direction.  Non-finite distances (NaN or infinite
+ * descriptors, squares that overflow) are the caller's error: unspecified.
+ * Ratio test: a row survives iff it has two neighbours and !(d0 / d1 > ratio), an f32 division (the reference's ratio_ is 0.65f).
+ * The negated form matters: a row whose two nearest are both at distance 0 (0 / 0 is NaN) SURVIVES, as in the reference.
+ * Symmetry test: (i, j, d0) for every surviving forward row i with idx0 = j whose backward row j (query B, train A) survives with
+ * idx0 = i; ascending i, at most one entry per i; distance is the forward d0.
+ *
+ * query / train: HOST arrays of n_pairs x cap x dim elements, pair p's rows from p * cap * dim on (the fixed-stride layout of
+ * keypoints_xy); n_query[p], n_train[p] in 0..cap.  A pair with n < 2 or m < 2 has no match (count 0: one direction has no second
+ * neighbour); that is no error.
+ * UWT_ERR_INVALID_ARG with nothing enqueued and the outputs untouched: n_pairs < 1, cap < 1, a null list, a count outside 0..cap,
+ * dim < 1, a dim that is not a multiple of 4 (floats for L2, bytes for Hamming), a non-finite ratio, an unknown norm.
+ * UWT_ERR_CAPACITY likewise: cap > UWT_MATCH_MAX_ROWS or a row longer than UWT_MATCH_MAX_ROW_BYTES.  n_pairs is NOT bounded by
+ * max_pairs.  The calls are independent of the context's frame geometry and params and change neither.  Scratch (both descriptor
+ * sets, the 2-NN records of both directions) belongs to the context, grows on demand and is freed by uwt_destroy.  Uploads and
+ * launches go on the context's stream in order.  A pair's output depends neither on the batch it runs in, nor on its place there,
+ * nor on uwt_tuning. */
+enum uwt_norm { UWT_NORM_L2 = 0, UWT_NORM_HAMMING = 1 };
+#define UWT_MATCH_MAX_ROWS 4096       /* descriptors per set (cap) at most */
+#define UWT_MATCH_MAX_ROW_BYTES 512   /* bytes per descriptor at most: 128 floats (SURF extended), 512 bytes of a binary descriptor */
+
+typedef struct uwt_match { int32_t query_idx, train_idx; float distance; } uwt_match;   /* cv::DMatch without imgIdx */
+typedef struct uwt_knn2 { int32_t idx0, idx1; float d0, d1; } uwt_knn2;                 /* -1: no such neighbour */
+
+/* matcher->knnMatch(descQ, descT, matches, 2) for n_pairs pairs — the per-stage entry.  out: n_pairs x cap records, pair p's row i
+ * at out[p * cap + i]; the rows past n_query[p] are not written. */
+int uwt_knn_match_batch(uwt_ctx* ctx, int32_t n_pairs, int32_t norm, int32_t dim, const void* query, const int32_t* n_query,
+                        const void* train, const int32_t* n_train, int32_t cap, uwt_knn2* out);
+/* knnMatch both ways + ratioTest both ways + symmetryTest (src/Tracker.cpp:202-236).  matches_out: n_pairs x cap, pair p's
+ * counts_out[p] matches from matches_out[p * cap] on; the rows past the count are not written. */
+int uwt_match_descriptors_batch(uwt_ctx* ctx, int32_t n_pairs, int32_t norm, int32_t dim, const void* query, const int32_t* n_query,
+                                const void* train, const int32_t* n_train, int32_t cap, float ratio, uwt_match* matches_out,
+                                int32_t* counts_out);
+/* The same without waiting: results in DEVICE memory (d_matches_out: n_pairs x cap uwt_match, d_counts_out: n_pairs), on the
+ * context's stream; uwt_sync() to wait.  Host arrays from uwt_host_alloc are read when the copy runs and must stay untouched until
+ * then; any other host array may be reused once the call returns (the runtime has staged it).  The context's scratch is reused by
+ * the next matching call, which the stream orders behind this one. */
+int uwt_match_descriptors_batch_async(uwt_ctx* ctx, int32_t n_pairs, int32_t norm, int32_t dim, const void* query,
+                                      const int32_t* n_query, const void* train, const int32_t* n_train, int32_t cap, float ratio,
+                                      uwt_match* d_matches_out, int32_t* d_counts_out);
+
 /* ---- next to the path: frame ingest---------------------------------------------------------------- */
 
 typedef struct uwt_ingest uwt_ingest;

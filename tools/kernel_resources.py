@@ -28,7 +28,7 @@ def main():
         text = open(a.remarks).read()
     else:
         text = ""
-        for unit in ("uwt_capi", "uwt_launch_residual", "uwt_launch_general", "uwt_launch_flow", "uwt_launch_points"):   # one object per kernel family
+        for unit in ("uwt_capi", "uwt_launch_residual", "uwt_launch_general", "uwt_launch_flow", "uwt_launch_points", "uwt_launch_match"):   # one object per kernel family
             r = subprocess.run(["make", "-C", os.path.join(ROOT, "uw-slam_amd", "csrc"), "asm", "UNIT=" + unit], capture_output=True, text=True)
             text += r.stdout + r.stderr
             if r.returncode:

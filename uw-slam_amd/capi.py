@@ -14,6 +14,10 @@ OK, ERR_INVALID_ARG, ERR_NO_VALID_POINTS, ERR_HIP, ERR_NO_DEVICE, ERR_CAPACITY, 
 PLANE_IMAGE, PLANE_DEPTH, PLANE_GRADX, PLANE_GRADY = range(4)
 MAX_LEVELS = 8
 ARITH_OPENCV, ARITH_LEGACY = 0, 1   # uwt_params.arith (include/uwt.h: enum uwt_arith)
+NORM_L2, NORM_HAMMING = 0, 1        # enum uwt_norm
+MATCH_MAX_ROWS, MATCH_MAX_ROW_BYTES = 4096, 512
+KNN2 = np.dtype([("idx0", "<i4"), ("idx1", "<i4"), ("d0", "<f4"), ("d1", "<f4")])           # uwt_knn2
+MATCH = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("distance", "<f4")])          # uwt_match
 
 
 class Params(C.Structure):
@@ -69,6 +73,7 @@ SYMBOLS = [
     "uwt_ingest_create", "uwt_ingest_destroy", "uwt_ingest_maps", "uwt_ingest_undistort", "uwt_ingest_calculate_roi",
     "uwt_ingest_frame", "uwt_update_params", "uwt_get_params", "uwt_ls_accumulate_sse", "uwt_robust_weights",
     "uwt_get_tuning", "uwt_set_tuning",
+    "uwt_knn_match_batch", "uwt_match_descriptors_batch", "uwt_match_descriptors_batch_async",
     "uwt_obtain_patch_points_batch", "uwt_track_features_batch_async", "uwt_estimate_pose_features_batch",
     "uwt_track_candidates_batch_async", "uwt_estimate_pose_candidates_batch",
 ]
@@ -615,6 +620,61 @@ class Context:
         tgt = np.ascontiguousarray(tgt_slots, np.int32)
         self._chk(lib().uwt_track_candidates_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.c_double(threshold),
                                                          C.c_void_p(d_poses_ptr), C.c_void_p(d_stats_ptr) if d_stats_ptr else None))
+
+    @staticmethod
+    def _descriptor_block(pairs, packed, cap):
+        """The matching calls' inputs: either `pairs`, a list of per-pair (A [n, dim], B [m, dim]) arrays, packed here into the
+        fixed-stride form, or `packed` = (query [P, cap, dim], n_query [P], train [P, cap, dim], n_train [P]) as it is.  dtype
+        decides the norm: float32 is L2, uint8 is Hamming.  Returns (norm, dim, cap, query, n_query, train, n_train)."""
+        if packed is not None:
+            q, nq, t, nt = packed
+            if q.dtype not in (np.float32, np.uint8) or t.dtype != q.dtype or q.ndim != 3 or q.shape != t.shape:
+                raise ValueError("packed descriptors: two [P, cap, dim] arrays of float32 (L2) or uint8 (Hamming)")
+            q, t = np.ascontiguousarray(q), np.ascontiguousarray(t)
+            nq, nt = np.ascontiguousarray(nq, np.int32), np.ascontiguousarray(nt, np.int32)
+            return (NORM_L2 if q.dtype == np.float32 else NORM_HAMMING), q.shape[2], q.shape[1], q, nq, t, nt
+        pairs = [(np.asarray(a), np.asarray(b)) for a, b in pairs]
+        dtype = pairs[0][0].dtype
+        if dtype not in (np.float32, np.uint8) or any(a.dtype != dtype or b.dtype != dtype or a.ndim != 2 or b.ndim != 2 or
+                                                      a.shape[1] != pairs[0][0].shape[1] or b.shape[1] != a.shape[1] for a, b in pairs):
+            raise ValueError("descriptor pairs: (A [n, dim], B [m, dim]) arrays of one dim, all float32 (L2) or all uint8 (Hamming)")
+        dim = pairs[0][0].shape[1]
+        cap = max([cap or 1] + [max(a.shape[0], b.shape[0]) for a, b in pairs])
+        q, t = np.zeros((len(pairs), cap, dim), dtype), np.zeros((len(pairs), cap, dim), dtype)
+        nq, nt = np.zeros(len(pairs), np.int32), np.zeros(len(pairs), np.int32)
+        for i, (a, b) in enumerate(pairs):
+            q[i, :a.shape[0]], t[i, :b.shape[0]] = a, b
+            nq[i], nt[i] = a.shape[0], b.shape[0]
+        return (NORM_L2 if dtype == np.float32 else NORM_HAMMING), dim, cap, q, nq, t, nt
+
+    def knn_match_batch(self, pairs=None, cap=None, packed=None):
+        """matcher->knnMatch(A, B, matches, 2) for many pairs (uwt_knn_match_batch).  Returns one KNN2 record array per pair, a row
+        per query descriptor: idx0, idx1 (-1: no such neighbour), d0, d1."""
+        norm, dim, cap, q, nq, t, nt = self._descriptor_block(pairs, packed, cap)
+        out = np.zeros((nq.size, cap), KNN2)
+        self._chk(lib().uwt_knn_match_batch(self._h, nq.size, norm, dim, C.c_void_p(q.ctypes.data), _p(nq, C.c_int32),
+                                            C.c_void_p(t.ctypes.data), _p(nt, C.c_int32), cap, C.c_void_p(out.ctypes.data)))
+        return [out[i, :nq[i]].copy() for i in range(nq.size)]
+
+    def match_descriptors_batch(self, pairs=None, ratio=0.65, cap=None, packed=None):
+        """knnMatch both ways, ratioTest both ways and symmetryTest for many pairs (uwt_match_descriptors_batch).  Returns one MATCH
+        record array per pair (query_idx, train_idx, distance), ascending query_idx."""
+        norm, dim, cap, q, nq, t, nt = self._descriptor_block(pairs, packed, cap)
+        out = np.zeros((nq.size, cap), MATCH)
+        cnt = np.zeros(nq.size, np.int32)
+        self._chk(lib().uwt_match_descriptors_batch(self._h, nq.size, norm, dim, C.c_void_p(q.ctypes.data), _p(nq, C.c_int32),
+                                                    C.c_void_p(t.ctypes.data), _p(nt, C.c_int32), cap, C.c_float(ratio),
+                                                    C.c_void_p(out.ctypes.data), _p(cnt, C.c_int32)))
+        return [out[i, :cnt[i]].copy() for i in range(nq.size)]
+
+    def match_descriptors_batch_async(self, d_matches_ptr, d_counts_ptr, pairs=None, ratio=0.65, cap=None, packed=None):
+        """The same enqueued on the context stream, results in device memory (d_matches_ptr: P x cap MATCH records, d_counts_ptr: P
+        int32); sync() to wait.  Returns cap.  Packed arrays from pinned_empty must stay untouched until the copy has run."""
+        norm, dim, cap, q, nq, t, nt = self._descriptor_block(pairs, packed, cap)
+        self._chk(lib().uwt_match_descriptors_batch_async(self._h, nq.size, norm, dim, C.c_void_p(q.ctypes.data), _p(nq, C.c_int32),
+                                                          C.c_void_p(t.ctypes.data), _p(nt, C.c_int32), cap, C.c_float(ratio),
+                                                          C.c_void_p(d_matches_ptr), C.c_void_p(d_counts_ptr)))
+        return cap
 
     def add_patch_points(self, lvl, pts, patch_size=5, cap=None):
         """Tracker::AddPatchPointsFeatures (src/Tracker.cpp:599-629).  Returns (table, full count)."""

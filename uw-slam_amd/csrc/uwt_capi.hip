@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "uwt_launch.h"
+#include "uwt_match.h"
 
 using namespace uwt;
 
@@ -109,6 +110,16 @@ struct uwt_ctx {
   size_t cand_work_bytes = 0;
   uint32_t* cand_recs = nullptr;
   size_t cand_recs_bytes = 0;
+  // descriptor matching (uwt_knn_match_batch, uwt_match_descriptors_batch*), each buffer grown on use to what a call needs: both
+  // descriptor sets of every pair, their counts (query | train), the 2-NN parts of both directions, and the synchronous calls' results
+  void* match_desc = nullptr;
+  size_t match_desc_bytes = 0;
+  int* match_cnt = nullptr;
+  size_t match_cnt_bytes = 0;
+  Knn2* match_part = nullptr;
+  size_t match_part_bytes = 0;
+  void* match_out = nullptr;
+  size_t match_out_bytes = 0;
   void* stage[2] = {nullptr, nullptr};  // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
   size_t stage_bytes[2] = {0, 0};
   bool profiling = false;
@@ -1223,6 +1234,10 @@ int uwt_destroy(uwt_ctx* c) {
   if (c->cand_cnt) (void)hipFree(c->cand_cnt);
   if (c->cand_work) (void)hipFree(c->cand_work);
   if (c->cand_recs) (void)hipFree(c->cand_recs);
+  if (c->match_desc) (void)hipFree(c->match_desc);
+  if (c->match_cnt) (void)hipFree(c->match_cnt);
+  if (c->match_part) (void)hipFree(c->match_part);
+  if (c->match_out) (void)hipFree(c->match_out);
   if (c->h_feat) (void)hipHostFree(c->h_feat);
   for (hipEvent_t e : c->ev_feat)
     if (e) (void)hipEventDestroy(e);
@@ -2548,6 +2563,134 @@ int uwt_estimate_pose_candidates_batch(uwt_ctx* c, int32_t n_pairs, const int32_
   int st = candidates_enqueue(c, what, n_pairs, ref_slots, tgt_slots, threshold, c->d_poses, c->d_stats);
   if (st) return st;
   return read_back_pairs(c, what, n_pairs, poses_out, stats_out);
+}
+
+// ---- descriptor matching: 2-NN both ways, ratio test, symmetry test (RobustMatcher, src/Tracker.cpp:52-102, 202-236) -----------
+namespace {
+
+static_assert(sizeof(Knn2) == sizeof(uwt_knn2) && sizeof(MatchOut) == sizeof(uwt_match), "uwt_knn2 / uwt_match layout");
+static_assert(kMatchMaxRows == UWT_MATCH_MAX_ROWS && kMatchMaxWords * 4 == UWT_MATCH_MAX_ROW_BYTES, "matching limits of include/uwt.h");
+static_assert(kMatchL2 == UWT_NORM_L2 && kMatchHamming == UWT_NORM_HAMMING, "uwt_norm");
+
+// Checks the arguments, grows the scratch, uploads both descriptor sets and their counts on the context stream and enqueues
+// k_knn2 behind them (dirs = 1: query -> train alone; 2: both directions).  Nothing is enqueued when a check fails.  The train
+// range of a (pair, query tile, direction) is cut into parts until the launch has kMatchTargetBlocks blocks: one pair of
+// 2000 x 2000 fills the chip as 1024 pairs of 500 x 500 do; the merge of the parts is exact, so the cut shows in no bit.
+int match_enqueue(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, const void* query, const int32_t* n_query,
+                  const void* train, const int32_t* n_train, int cap, int dirs, MatchArgs* out) {
+  if (n_pairs < 1 || !query || !n_query || !train || !n_train) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null list or n_pairs < 1");
+  if (norm != UWT_NORM_L2 && norm != UWT_NORM_HAMMING) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": unknown norm");
+  if (dim < 1 || (dim & 3)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": dim must be a positive multiple of 4");
+  if (cap < 1) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": cap < 1");
+  int max_q = 0, max_t = 0;
+  for (int p = 0; p < n_pairs; p++) {
+    if (n_query[p] < 0 || n_query[p] > cap || n_train[p] < 0 || n_train[p] > cap)
+      return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": descriptor count outside 0..cap");
+    max_q = std::max(max_q, n_query[p]);
+    max_t = std::max(max_t, n_train[p]);
+  }
+  const int words = norm == UWT_NORM_L2 ? dim : dim / 4;
+  if (cap > kMatchMaxRows || words > kMatchMaxWords)
+    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS or a row above UWT_MATCH_MAX_ROW_BYTES");
+  const int rows = dirs == 2 ? std::max(max_q, max_t) : max_q, train_rows = dirs == 2 ? rows : max_t;
+  const int tiles = (rows + kMatchTile - 1) / kMatchTile, train_tiles = (train_rows + kMatchTile - 1) / kMatchTile;
+  const size_t blocks = (size_t)n_pairs * std::max(tiles, 1) * dirs;
+  const int splits = (int)std::min<size_t>(std::min(kMatchMaxSplits, std::max(train_tiles, 1)), (kMatchTargetBlocks + blocks - 1) / blocks);
+  const size_t set_bytes = sizeof(uint32_t) * words * (size_t)cap * n_pairs;
+  int st = grow(c, &c->match_desc, &c->match_desc_bytes, 2 * set_bytes);
+  if (!st) st = grow(c, (void**)&c->match_cnt, &c->match_cnt_bytes, sizeof(int) * 2 * (size_t)n_pairs);
+  if (!st) st = grow(c, (void**)&c->match_part, &c->match_part_bytes, sizeof(Knn2) * cap * (size_t)splits * n_pairs * dirs);
+  if (st) return st;
+  MatchArgs a;
+  a.desc[0] = (const uint32_t*)c->match_desc;
+  a.desc[1] = (const uint32_t*)((const unsigned char*)c->match_desc + set_bytes);
+  a.cnt[0] = c->match_cnt;
+  a.cnt[1] = c->match_cnt + n_pairs;
+  a.cap = cap; a.words = words; a.n_pairs = n_pairs; a.splits = splits;
+  a.part = c->match_part;
+  HIPCHK(c, hipMemcpyAsync(c->match_desc, query, set_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync((unsigned char*)c->match_desc + set_bytes, train, set_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->match_cnt, n_query, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->match_cnt + n_pairs, n_train, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
+  if (rows > 0) {
+    launch_knn2(c->stream, norm, a, dirs, rows);
+    HIPCHK(c, hipGetLastError());
+  }
+  *out = a;
+  return UWT_OK;
+}
+
+int match_descriptors_enqueue(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, const void* query, const int32_t* n_query,
+                              const void* train, const int32_t* n_train, int cap, float ratio, MatchOut* d_matches, int* d_counts) {
+  if (!std::isfinite(ratio)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": ratio is not finite");
+  MatchArgs a;
+  int st = match_enqueue(c, what, n_pairs, norm, dim, query, n_query, train, n_train, cap, 2, &a);
+  if (st) return st;
+  launch_match_filter(c->stream, a, ratio, d_matches, d_counts);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
+}  // namespace
+
+int uwt_knn_match_batch(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32_t dim, const void* query, const int32_t* n_query,
+                        const void* train, const int32_t* n_train, int32_t cap, uwt_knn2* out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_knn_match_batch: null argument");
+  MatchArgs a;
+  int st = match_enqueue(c, "uwt_knn_match_batch", n_pairs, norm, dim, query, n_query, train, n_train, cap, 1, &a);
+  if (st) return st;
+  const size_t recs = (size_t)n_pairs * cap;
+  st = grow(c, &c->match_out, &c->match_out_bytes, sizeof(Knn2) * recs);
+  if (st) return st;
+  int rows = 0;
+  for (int p = 0; p < n_pairs; p++) rows = std::max(rows, n_query[p]);
+  if (rows == 0) return UWT_OK;
+  launch_knn2_merge(c->stream, a, rows, (Knn2*)c->match_out);
+  HIPCHK(c, hipGetLastError());
+  std::vector<uwt_knn2> tmp(recs);
+  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->match_out, sizeof(Knn2) * recs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int p = 0; p < n_pairs; p++)   // the rows past a pair's count stay as the caller left them
+    std::copy(tmp.begin() + (size_t)p * cap, tmp.begin() + (size_t)p * cap + n_query[p], out + (size_t)p * cap);
+  return UWT_OK;
+}
+
+int uwt_match_descriptors_batch_async(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32_t dim, const void* query, const int32_t* n_query,
+                                      const void* train, const int32_t* n_train, int32_t cap, float ratio, uwt_match* d_matches_out,
+                                      int32_t* d_counts_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !d_matches_out || !d_counts_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_match_descriptors_batch_async: null argument");
+  return match_descriptors_enqueue(c, "uwt_match_descriptors_batch_async", n_pairs, norm, dim, query, n_query, train, n_train, cap, ratio,
+                                   reinterpret_cast<MatchOut*>(d_matches_out), d_counts_out);
+}
+
+int uwt_match_descriptors_batch(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32_t dim, const void* query, const int32_t* n_query,
+                                const void* train, const int32_t* n_train, int32_t cap, float ratio, uwt_match* matches_out,
+                                int32_t* counts_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !matches_out || !counts_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_match_descriptors_batch: null argument");
+  const char* what = "uwt_match_descriptors_batch";
+  // (the checks of match_enqueue that the size of the result area depends on)
+  if (n_pairs < 1 || cap < 1) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_pairs < 1 or cap < 1");
+  if (cap > kMatchMaxRows) return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS");
+  const size_t recs = (size_t)n_pairs * cap, cnt_off = (sizeof(MatchOut) * recs + 15) & ~(size_t)15;
+  int st = grow(c, &c->match_out, &c->match_out_bytes, cnt_off + sizeof(int) * n_pairs);
+  if (st) return st;
+  MatchOut* d_matches = (MatchOut*)c->match_out;
+  int* d_counts = (int*)((unsigned char*)c->match_out + cnt_off);
+  st = match_descriptors_enqueue(c, what, n_pairs, norm, dim, query, n_query, train, n_train, cap, ratio, d_matches, d_counts);
+  if (st) return st;
+  std::vector<uwt_match> tmp(recs);
+  std::vector<int32_t> cnt((size_t)n_pairs);
+  HIPCHK(c, hipMemcpyAsync(cnt.data(), d_counts, sizeof(int) * n_pairs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tmp.data(), d_matches, sizeof(MatchOut) * recs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int p = 0; p < n_pairs; p++) {   // the rows past a pair's count stay as the caller left them
+    counts_out[p] = cnt[(size_t)p];
+    std::copy(tmp.begin() + (size_t)p * cap, tmp.begin() + (size_t)p * cap + cnt[(size_t)p], matches_out + (size_t)p * cap);
+  }
+  return UWT_OK;
 }
 
 int uwt_add_patch_points(uwt_ctx* c, int32_t lvl, const float* pts, int32_t n_pts, int32_t patch_size, float* pts_out,

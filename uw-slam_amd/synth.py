@@ -208,3 +208,29 @@ def write_euroc_layout(root, frames, abs_poses, gt_per_frame=10, lead_rows=600):
             fh.write("%d,%.9f,%.9f,%.9f,%.9f,%.9f,%.9f,%.9f,0,0,0,0,0,0,0,0,0\n"
                      % (1403636579763555584 + r * 5000000, p[4], p[5], p[6], p[3], p[0], p[1], p[2]))
     return img, path
+
+
+def descriptor_pair(seed, n, m, dim, kind="l2", overlap=0.6, noise=0.08):
+    """Two descriptor sets with known correspondences, for the matching calls: A [n, dim] (the previous frame), B [m, dim] (the
+    current one), and (dst, src): B[dst[k]] is a noisy copy of A[src[k]] for overlap * min(n, m) rows at random places; every
+    other row of B is unrelated.
+    kind "l2": float32, unit-norm Gaussian rows; a copy is A[src] + noise * N(0, 1), normalised again (SURF-like).
+    kind "hamming": uint8, dim random bytes per row; a copy is A[src] with each bit flipped with probability `noise` (ORB-like)."""
+    rng = np.random.default_rng(seed)
+    k = int(overlap * min(n, m))
+    dst, src = rng.permutation(m)[:k], rng.permutation(n)[:k]
+    if kind == "l2":
+        def rows(r):
+            g = rng.standard_normal((r, dim)).astype(np.float32)
+            return g / np.maximum(np.linalg.norm(g, axis=1, keepdims=True), np.float32(1e-12)).astype(np.float32)
+        A, B = rows(n), rows(m)
+        c = A[src] + np.float32(noise) * rng.standard_normal((k, dim)).astype(np.float32)
+        B[dst] = c / np.maximum(np.linalg.norm(c, axis=1, keepdims=True), np.float32(1e-12)).astype(np.float32)
+    elif kind == "hamming":
+        A = rng.integers(0, 256, (n, dim), dtype=np.uint8)
+        B = rng.integers(0, 256, (m, dim), dtype=np.uint8)
+        flips = np.packbits(rng.random((k, dim * 8)) < noise, axis=1)
+        B[dst] = A[src] ^ flips
+    else:
+        raise ValueError(kind)
+    return np.ascontiguousarray(A), np.ascontiguousarray(B), dst, src

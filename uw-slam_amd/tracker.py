@@ -31,6 +31,7 @@ class Frame:
         self.obtained_candidatePoints_ = False
         self.rigid_transformation_ = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)  # qx qy qz qw tx ty tz
         self.keypoints_ = np.zeros((0, 2), np.float32)       # cv::KeyPoint::pt of Frame::keypoints_
+        self.n_matches_ = 0                                  # include/System.h:93
         self.candidatePoints_ = {}                           # level -> N x 4 [x y z w] when a sparse producer ran
         self._slot = None
 
@@ -175,6 +176,23 @@ class Tracker:
         _previous_frame.rigid_transformation_ = pose
         return st
 
+    def EstimatePoseFeaturesBatch(self, _pairs):
+        """System::Tracking's live call (src/System.cpp:214-219) for a list of (previous, current) frame pairs in one call
+        (uwt_estimate_pose_features_batch, as uw::Tracker::EstimatePoseFeaturesBatch): each previous frame's keypoints_ go in,
+        its rigid_transformation_ comes out.  The reference's constants are the call's own; the tracker's params are not touched.
+        Returns the per-pair stats."""
+        slots = [(self._bind(a), self._bind(b)) for a, b in _pairs]
+        for (a, b), (sa, sb) in zip(_pairs, slots):   # binding a later pair's frame may have taken an earlier frame's slot
+            if a._slot != sa or b._slot != sb:
+                raise RuntimeError("EstimatePoseFeaturesBatch: more frames than slots (max_frames)")
+            if not a.obtained_gradients_:
+                raise RuntimeError("ApplyGradient(previous_frame) must run before EstimatePoseFeaturesBatch (or its slot was reused since)")
+        poses, stats = self._ctx.estimate_pose_features_batch([s[0] for s in slots], [s[1] for s in slots],
+                                                              [a.keypoints_ for a, _ in _pairs])
+        for (a, _), pose in zip(_pairs, poses):
+            a.rigid_transformation_ = pose.copy()
+        return stats
+
     def ObtainGradientXY(self, _inputImage):
         """include/Tracker.h:197 — (gradientX, gradientY) = 3 x Scharr of a u8 image, CV_16S (src/Tracker.cpp:1133-1134)."""
         return self._ctx.scharr3(_inputImage)
@@ -197,6 +215,57 @@ class Tracker:
 
     def GetFrameData(self, _frame, lvl, plane):
         return self._ctx.get_plane(self._bind(_frame), lvl, plane)
+
+
+class RobustMatcher:
+    """include/Tracker.h:65-88 — the matching half of RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258): knnMatch in
+    both directions, ratioTest twice and symmetryTest, on the GPU over the C ABI (uwt_match_descriptors_batch); getGoodKeypoints and
+    the assignment of :247-254 on the host.  NOT here, the caller's: detection and description (cuda::SURF_CUDA / cuda::ORB — the
+    descriptors are an argument) and ransacTest (cv::findFundamentalMat draws from OpenCV's RNG), which the caller runs, or skips,
+    between MatchDescriptors and MatchAndSetKeypoints and hands over as an inlier mask.
+    float32 descriptors are matched under L2 (SURF), uint8 under Hamming (ORB), as createBFMatcher is set up at :199 / :221."""
+
+    def __init__(self, ctx_or_tracker, ratio=0.65):
+        self._src = ctx_or_tracker
+        self.ratio_ = float(np.float32(ratio))   # include/Tracker.h:80
+
+    @property
+    def _ctx(self):
+        ctx = getattr(self._src, "_ctx", self._src)   # a Tracker (after InitializePyramid) or a capi.Context
+        if ctx is None:
+            raise RuntimeError("RobustMatcher: the Tracker has no context yet (InitializePyramid first)")
+        return ctx
+
+    def MatchDescriptors(self, desc_prev, desc_cur):
+        """symMatches of one pair (src/Tracker.cpp:202-236): a capi.MATCH record array (query_idx into desc_prev, train_idx into
+        desc_cur, distance), ascending query_idx."""
+        return self.MatchDescriptorsBatch([(desc_prev, desc_cur)])[0]
+
+    def MatchDescriptorsBatch(self, pairs):
+        """The same for a list of (desc_prev, desc_cur) pairs in one call."""
+        return self._ctx.match_descriptors_batch(pairs, ratio=self.ratio_)
+
+    @staticmethod
+    def getGoodKeypoints(goodMatches, keypoints):
+        """src/Tracker.cpp:260-270: keypoints = (previous [n, 2], current [m, 2]); returns the matched rows of each, in match order."""
+        k0, k1 = (np.asarray(k, np.float32).reshape(-1, 2) for k in keypoints)
+        return k0[goodMatches["query_idx"]], k1[goodMatches["train_idx"]]
+
+    def MatchAndSetKeypoints(self, _previous_frame, _current_frame, desc_prev, desc_cur, keypoints, inlier_mask=None):
+        """DetectAndTrackFeatures from the matcher on (src/Tracker.cpp:224-254) with the caller's detector output: symmetric
+        matches, the caller's optional RANSAC inlier mask over them (or a callable matches -> mask), getGoodKeypoints, then
+        keypoints_ and n_matches_ of both frames (:247-254).  Tracker::EstimatePoseFeatures / the batched live call can follow
+        directly.  n_matches_ feeds the caller's `n_matches_ < 110` rule (src/System.cpp:208), which stays with the caller.
+        Returns the matches kept."""
+        matches = self.MatchDescriptors(desc_prev, desc_cur)
+        if callable(inlier_mask):
+            inlier_mask = inlier_mask(matches)
+        if inlier_mask is not None:
+            matches = matches[np.asarray(inlier_mask, bool)]
+        good = self.getGoodKeypoints(matches, keypoints)
+        _previous_frame.n_matches_ = _current_frame.n_matches_ = len(matches)
+        _previous_frame.keypoints_, _current_frame.keypoints_ = good
+        return matches
 
 
 class LS:
