@@ -497,11 +497,12 @@ inline Frame::~Frame() {
   if (tracker_) tracker_->forget(this);
 }
 
-// include/Tracker.h:65-88 — the matching half of RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258): knnMatch in both
-// directions, ratioTest twice and symmetryTest on the GPU (uwt_match_descriptors_batch); getGoodKeypoints and the assignment of
-// :247-254 on the host.  NOT here, the caller's: detection and description (cuda::SURF_CUDA / cuda::ORB — descriptors are an
-// argument) and ransacTest (cv::findFundamentalMat draws from OpenCV's RNG), which the caller runs, or skips, between
-// MatchDescriptors and MatchAndSetKeypoints and hands over as an inlier mask.
+// include/Tracker.h:65-88 — RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258) from the matcher on: knnMatch in both
+// directions, ratioTest twice and symmetryTest on the GPU (uwt_match_descriptors_batch), ransacTest as the inlier selection of
+// uwt_ransac_inliers_batch (the contract: include/uwt.h — cv::findFundamentalMat draws from OpenCV's RNG and is not pinned);
+// getGoodKeypoints and the assignment of :247-254 on the host.  NOT here, the caller's: detection and description
+// (cuda::SURF_CUDA / cuda::ORB — descriptors are an argument).  A caller with a RANSAC of their own passes its inliers to
+// SetKeypoints instead.
 class RobustMatcher {
  public:
   explicit RobustMatcher(Tracker* tracker) : tracker_(tracker) {}
@@ -526,7 +527,7 @@ class RobustMatcher {
     }
     return good;
   }
-  // :247-254 after the caller's optional ransacTest: goodMatches (symMatches, or their inliers), getGoodKeypoints, then keypoints_
+  // :247-254 after ransacTest (below, or the caller's own): goodMatches (symMatches, or their inliers), getGoodKeypoints, then keypoints_
   // and n_matches_ of both frames.  Tracker::EstimatePoseFeaturesBatch can follow directly.  n_matches_ feeds the caller's
   // `n_matches_ < 110` rule (src/System.cpp:208), which stays with the caller.
   static void SetKeypoints(Frame* _previous_frame, Frame* _current_frame, const std::vector<uwt_match>& goodMatches,
@@ -541,8 +542,53 @@ class RobustMatcher {
                             const std::array<std::vector<float>, 2>& keypoints) {
     SetKeypoints(_previous_frame, _current_frame, MatchDescriptors(desc_prev, n, desc_cur, m, dim), keypoints);
   }
+  // :105-169: the matches that survive the epipolar test, in their order, into outMatches — the inlier selection of
+  // uwt_ransac_inliers_batch (the contract: include/uwt.h).  The reference returns an empty Mat (the local of :124 shadows the
+  // matrix it declares at :110); this returns the selection's record, whose F is the hypothesis chosen.  keypoints1 / keypoints2:
+  // x0 y0 x1 y1 ... of the previous / current frame.
+  uwt_ransac_info ransacTest(const std::vector<uwt_match>& matches, const std::vector<float>& keypoints1,
+                             const std::vector<float>& keypoints2, std::vector<uwt_match>& outMatches) {
+    const int32_t n = (int32_t)matches.size(), n1 = (int32_t)(keypoints1.size() / 2), n2 = (int32_t)(keypoints2.size() / 2);
+    const int32_t cap = std::max(1, n), kp_cap = std::max(1, std::max(n1, n2));
+    std::vector<uwt_match> in((size_t)cap), good((size_t)cap);
+    std::copy(matches.begin(), matches.end(), in.begin());
+    std::vector<float> k1((size_t)kp_cap * 2, 0.f), k2((size_t)kp_cap * 2, 0.f);
+    std::copy(keypoints1.begin(), keypoints1.begin() + (size_t)n1 * 2, k1.begin());
+    std::copy(keypoints2.begin(), keypoints2.begin() + (size_t)n2 * 2, k2.begin());
+    std::vector<uint8_t> mask((size_t)cap);
+    uwt_ransac_params rp;
+    uwt_default_ransac_params(&rp);
+    rp.distance = distance_;
+    rp.confidence = confidence_;
+    rp.max_hypotheses = max_hypotheses_;
+    rp.seed = seed_;
+    int32_t count = 0;
+    uwt_ransac_info info;
+    const int st = uwt_ransac_inliers_batch(tracker_->ctx(), 1, in.data(), &n, cap, k1.data(), &n1, k2.data(), &n2, kp_cap, &rp, mask.data(),
+                                            good.data(), &count, &info);
+    if (st != UWT_OK)
+      throw std::runtime_error(std::string("uwt_ransac_inliers_batch: ") + uwt_status_string(st) + " (" + uwt_last_error(tracker_->ctx()) + ")");
+    good.resize((size_t)count);
+    outMatches = std::move(good);
+    return info;
+  }
+  // :171-258 from the matcher on, with the caller's detector output: symmetric matches -> ransacTest -> getGoodKeypoints ->
+  // keypoints_ and n_matches_ of both frames.  Returns the matches kept.
+  template <typename T>
+  std::vector<uwt_match> DetectAndTrackFeatures(Frame* _previous_frame, Frame* _current_frame, const T* desc_prev, int n, const T* desc_cur,
+                                                int m, int dim, const std::array<std::vector<float>, 2>& keypoints) {
+    std::vector<uwt_match> good;
+    ransacTest(MatchDescriptors(desc_prev, n, desc_cur, m, dim), keypoints[0], keypoints[1], good);
+    SetKeypoints(_previous_frame, _current_frame, good, keypoints);
+    return good;
+  }
 
-  float ratio_ = 0.65f;   // include/Tracker.h:80
+  float ratio_ = 0.65f;      // include/Tracker.h:80
+  bool refineF_ = true;      // include/Tracker.h:81 — a no-op here: the refit's result is discarded by the reference (:124, :141-166)
+  double distance_ = 3.0;    // include/Tracker.h:82
+  double confidence_ = 0.99; // include/Tracker.h:83
+  int32_t max_hypotheses_ = 1000;   // no reference member: the budget of the selection (uwt_ransac_params)
+  uint32_t seed_ = 0;
 
  private:
   std::vector<uwt_match> match(int norm, const void* a, int n, const void* b, int m, int dim, size_t elem) {

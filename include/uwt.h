@@ -427,9 +427,11 @@ int uwt_estimate_pose_candidates_batch(uwt_ctx* ctx, int32_t n_pairs, const int3
 
 /* System::Tracking's second call, robust_matcher_->DetectAndTrackFeatures(previous, current, usekeypoints) (src/System.cpp:203,
  * src/Tracker.cpp:171-258), has four parts.  Built here: matcher->knnMatch(.., 2) in both directions (:202-203, :224-225), the two
- * ratioTest calls and symmetryTest (:52-102, :229-236).  NOT built, the caller's: detection and description (cuda::SURF_CUDA /
- * cuda::ORB, :184-222 — descriptors come from the caller) and ransacTest (:106-169, cv::findFundamentalMat draws from OpenCV's RNG);
- * getGoodKeypoints (:260-270) is a host gather in the mirrors (include/uw_tracker.hpp, uw-slam_amd/tracker.py).
+ * ratioTest calls and symmetryTest (:52-102, :229-236), and, since round 10, ransacTest (:106-169) as the inlier selection of
+ * uwt_ransac_inliers_batch below — under a contract of this library's own, because cv::findFundamentalMat draws from OpenCV's RNG
+ * and cannot be pinned.  NOT built, the caller's: detection and description (cuda::SURF_CUDA / cuda::ORB, :184-222 — descriptors
+ * come from the caller); getGoodKeypoints (:260-270) is a host gather in the mirrors (include/uw_tracker.hpp,
+ * uw-slam_amd/tracker.py).
  *
  * Per pair: a query set A (n rows, the previous frame) and a train set B (m rows, the current frame) of descriptors of `dim`
  * elements.
@@ -482,6 +484,87 @@ int uwt_match_descriptors_batch(uwt_ctx* ctx, int32_t n_pairs, int32_t norm, int
 int uwt_match_descriptors_batch_async(uwt_ctx* ctx, int32_t n_pairs, int32_t norm, int32_t dim, const void* query,
                                       const int32_t* n_query, const void* train, const int32_t* n_train, int32_t cap, float ratio,
                                       uwt_match* d_matches_out, int32_t* d_counts_out);
+
+/* ---- RANSAC inlier selection for a batch of pairs: RobustMatcher::ransacTest -------------------------------------------- */
+
+/* RobustMatcher::ransacTest(symMatches, keypoints1, keypoints2, goodMatches) (src/Tracker.cpp:105-169, called at :237).  The only
+ * output of ransacTest that reaches the tracker is the INLIER SUBSET of the matches (goodMatches, :131-140): the fundamental matrix
+ * it computes goes to a local that shadows the returned one (:110 / :124), and so does the 8-point refit of refineF_ (:141-166) —
+ * the refit therefore has no device form, and the hypothesis solver only has to rank hypotheses by their inlier count.  The
+ * semantics and constants of ransacTest are kept: distance_ = 3.0 to the epipolar line, confidence_ = 0.99 (include/Tracker.h:82-83),
+ * the larger of the two squared point-to-line distances as the error, the adaptive iteration count, "a model needs more than
+ * modelPoints - 1 inliers and strictly more than the best so far".  Which samples OpenCV draws and how its 7-point solver rounds is
+ * not pinned (no OpenCV build is); instead this is the contract, complete, in which EVERY operation on the device is an
+ * IEEE f64 add, subtract, multiply, divide or compare, or integer arithmetic (no square root, no SVD, no transcendental; no FMA),
+ * so that tests/ransac_ref.py restates it in numpy and the device agrees with it bit for bit.
+ *
+ * Per pair: N matches (q_i, t_i); (x_i, y_i) = kp_prev[q_i], (x'_i, y'_i) = kp_cur[t_i], f32 converted to f64.  Parameters:
+ * uwt_ransac_params.  N < 8: no inliers (OpenCV's 7-point solver would take N = 7; this contract does not).
+ * Sample of hypothesis h (h = 0, 1, ...): mix(x) on uint32 is x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b;
+ *   x ^= x >> 16.  For slot s = 0..7: u = mix(seed ^ mix(8 * h + s)), j = (u * (N - s)) >> 32 (64-bit product), then j steps past
+ *   the indices already taken, in ascending order (for e in sorted(taken): if j >= e: j += 1).  Eight distinct indices that depend
+ *   on (seed, h, N) alone.
+ * Hypothesis: the 8 x 9 matrix M with rows [x'x, x'y, x', y'x, y'y, y', x, y, 1] (each product one multiply).  Gauss-Jordan
+ *   elimination with full pivoting, at most eight steps.  A step scans the rows and columns not yet used, rows outermost, both
+ *   ascending, from best = 0; an entry v takes over iff |v| > best (ties: lowest row, then lowest column; a NaN never wins).  If no
+ *   entry takes over, the elimination ends early (the sample is rank-deficient).  An infinite pivot makes the hypothesis invalid
+ *   (inlier count 0).  Otherwise the pivot's row is divided by the pivot (all nine columns), and from EVERY other row r — used or
+ *   not — g * row is subtracted, g = M[r, c] read before the row changes: element by element one multiply, one subtract.  Then the
+ *   free column c* is the lowest unused column: f[c*] = 1, f = 0 in the other unused columns, f[c] = -M[r_c, c*] for each pivot
+ *   (r_c, c).  F = f, row-major 3 x 3.  No rank-2 enforcement, no normalisation.
+ * Error of match i under F, every expression left to right:
+ *   a = F0*x + F1*y + F2;  b = F3*x + F4*y + F5;  c = F6*x + F7*y + F8;  s2 = x'*a + y'*b + c;  d2 = s2*s2 / (a*a + b*b);
+ *   a1 = F0*x' + F3*y' + F6;  b1 = F1*x' + F4*y' + F7;  c1 = F2*x' + F5*y' + F8;  s1 = x*a1 + y*b1 + c1;  d1 = s1*s1 / (a1*a1 + b1*b1);
+ *   t2 = distance * distance;  inlier iff d1 <= t2 && d2 <= t2 (a NaN is not an inlier).  count_h = the number of inliers.
+ * Selection, sequential by definition: best = 0; limit = H; for h = 0, 1, ... while h < limit: if count_h > max(best, 7):
+ *   best = count_h, best_h = h, limit = min(limit, need(best)).  need(k) = uwt_ransac_iterations(confidence, N, k, H), computed on
+ *   the host.  hypotheses_run = the h at which the loop stops.
+ * Output per pair: the inlier mask of best_h (one byte per match: 1 / 0), the matches it keeps in their order, their count, and a
+ *   uwt_ransac_info.  N < 8 or no hypothesis accepted: mask all 0, count 0, best_hypothesis -1, F all 0, status UWT_OK (the
+ *   reference's inliers vector is zero-initialised, :122: goodMatches is empty there too); hypotheses_run is 0 for N < 8. */
+#define UWT_RANSAC_MAX_HYPOTHESES 65536
+typedef struct uwt_ransac_params {
+  double distance;          /* distance_, pixels to the epipolar line (3.0); finite, >= 0        */
+  double confidence;        /* confidence_ (0.99); in (0, 1]; 1: every one of max_hypotheses runs */
+  int32_t max_hypotheses;   /* H: 1..UWT_RANSAC_MAX_HYPOTHESES (1000)                             */
+  uint32_t seed;            /* of the sample sequence (0)                                         */
+} uwt_ransac_params;
+typedef struct uwt_ransac_info {
+  int32_t status;           /* uwt_status_code of this pair */
+  int32_t n_inliers, best_hypothesis, hypotheses_run;
+  double F[9];              /* of best_hypothesis, row-major, scaled as the elimination leaves it (one entry is 1) */
+} uwt_ransac_info;
+
+/* {3.0, 0.99, 1000, 0}: distance_ and confidence_ of include/Tracker.h:82-83; 1000 hypotheses at most */
+int uwt_default_ransac_params(uwt_ransac_params* p);
+/* need(k) of the contract above: a host function, no context, no device.  H = max_hypotheses.  Returns H if confidence == 1 or
+ * inliers <= 0 or n <= 0; else, in double: w = inliers / n, w8 = ((w*w)^2)^2 by three squarings, num = log(1 - confidence),
+ * den = log(1 - w8), taken as -infinity when w8 >= 1; H if den >= 0 or -num >= H * (-den); else rint(num / den) (half to even;
+ * 0 when every match is an inlier).  The shape of OpenCV's RANSACUpdateNumIters. */
+int32_t uwt_ransac_iterations(double confidence, int32_t n, int32_t inliers, int32_t max_hypotheses);
+/* ransacTest for n_pairs pairs, host in, host out, synchronous.  matches: n_pairs x cap uwt_match, pair p's n_matches[p] matches
+ * from matches[p * cap] on (what uwt_match_descriptors_batch wrote); kp_prev / kp_cur: n_pairs x kp_cap x 2 floats (x, y), pair
+ * p's n_kp_prev[p] / n_kp_cur[p] key points from p * kp_cap * 2 on; params: null for the defaults.  mask_out: n_pairs x cap
+ * bytes, pair p's first n_matches[p] written; good_out: n_pairs x cap uwt_match, the first counts_out[p] written; info_out:
+ * n_pairs records.  UWT_ERR_INVALID_ARG with nothing enqueued and the outputs untouched: n_pairs < 1, cap < 1, kp_cap < 1, a null
+ * pointer, a count outside 0..cap / 0..kp_cap, a match index outside its key-point count, a parameter outside its range.
+ * UWT_ERR_CAPACITY likewise: cap or kp_cap above UWT_MATCH_MAX_ROWS.  n_pairs is NOT bounded by max_pairs; the call is independent
+ * of the context's geometry and params.  A pair's output depends neither on the batch it runs in nor on its place there.  The
+ * table of need(k) is built on the host per distinct N, kept by the context and handed to the kernel. */
+int uwt_ransac_inliers_batch(uwt_ctx* ctx, int32_t n_pairs, const uwt_match* matches, const int32_t* n_matches, int32_t cap,
+                             const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur, const int32_t* n_kp_cur,
+                             int32_t kp_cap, const uwt_ransac_params* params, uint8_t* mask_out, uwt_match* good_out,
+                             int32_t* counts_out, uwt_ransac_info* info_out);
+/* The same without waiting: d_matches / d_n_matches are read from DEVICE memory (what uwt_match_descriptors_batch_async wrote)
+ * and the four results are left in DEVICE memory, on the context's stream; uwt_sync() to wait.  Key points and their counts are
+ * host arrays, staged as in uwt_match_descriptors_batch_async.  The match indices cannot be checked on the host: the kernel checks
+ * them, and a pair with an index outside its key-point count (or a match count outside 0..cap) gets UWT_ERR_INVALID_ARG in its
+ * own info.status and no inliers; the other pairs are unaffected.  need(k) is not known per pair on the host here: the context
+ * builds it for every N up to cap the first time these parameters are used (cap * cap / 2 logarithms, once). */
+int uwt_ransac_inliers_batch_async(uwt_ctx* ctx, int32_t n_pairs, const uwt_match* d_matches, const int32_t* d_n_matches,
+                                   int32_t cap, const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur,
+                                   const int32_t* n_kp_cur, int32_t kp_cap, const uwt_ransac_params* params, uint8_t* d_mask_out,
+                                   uwt_match* d_good_out, int32_t* d_counts_out, uwt_ransac_info* d_info_out);
 
 /* ---- next to the path: frame ingest---------------------------------------------------------------- */
 

@@ -18,6 +18,9 @@ NORM_L2, NORM_HAMMING = 0, 1        # enum uwt_norm
 MATCH_MAX_ROWS, MATCH_MAX_ROW_BYTES = 4096, 512
 KNN2 = np.dtype([("idx0", "<i4"), ("idx1", "<i4"), ("d0", "<f4"), ("d1", "<f4")])           # uwt_knn2
 MATCH = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("distance", "<f4")])          # uwt_match
+RANSAC_MAX_HYPOTHESES = 65536
+RANSAC_INFO = np.dtype([("status", "<i4"), ("n_inliers", "<i4"), ("best_hypothesis", "<i4"), ("hypotheses_run", "<i4"),
+                        ("F", "<f8", (9,))])                                                 # uwt_ransac_info
 
 
 class Params(C.Structure):
@@ -42,6 +45,11 @@ class Tuning(C.Structure):
         ("speculation", C.c_int32), ("fused_stages", C.c_int32), ("pyramid_batch", C.c_int32), ("typed_loads", C.c_int32),
         ("reserved", C.c_int32 * 4),
     ]
+
+
+class RansacParams(C.Structure):
+    """uwt_ransac_params: distance_ / confidence_ of RobustMatcher (include/Tracker.h:82-83), the hypothesis budget, the seed"""
+    _fields_ = [("distance", C.c_double), ("confidence", C.c_double), ("max_hypotheses", C.c_int32), ("seed", C.c_uint32)]
 
 
 class Level(C.Structure):
@@ -74,6 +82,7 @@ SYMBOLS = [
     "uwt_ingest_frame", "uwt_update_params", "uwt_get_params", "uwt_ls_accumulate_sse", "uwt_robust_weights",
     "uwt_get_tuning", "uwt_set_tuning",
     "uwt_knn_match_batch", "uwt_match_descriptors_batch", "uwt_match_descriptors_batch_async",
+    "uwt_default_ransac_params", "uwt_ransac_iterations", "uwt_ransac_inliers_batch", "uwt_ransac_inliers_batch_async",
     "uwt_obtain_patch_points_batch", "uwt_track_features_batch_async", "uwt_estimate_pose_features_batch",
     "uwt_track_candidates_batch_async", "uwt_estimate_pose_candidates_batch",
 ]
@@ -116,6 +125,8 @@ def lib():
         _lib.uwt_source_id.restype = C.c_char_p
         _lib.uwt_source_id.argtypes = []
         _lib.uwt_last_error.argtypes = [C.c_void_p]
+        _lib.uwt_ransac_iterations.restype = C.c_int32
+        _lib.uwt_ransac_iterations.argtypes = [C.c_double, C.c_int32, C.c_int32, C.c_int32]
     return _lib
 
 
@@ -143,6 +154,24 @@ def default_params(width, height, fx, fy, cx, cy, **over):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def default_ransac_params(**over):
+    """uwt_default_ransac_params: distance 3.0, confidence 0.99, max_hypotheses 1000, seed 0"""
+    p = RansacParams()
+    st = lib().uwt_default_ransac_params(C.byref(p))
+    if st:
+        raise UwtError(st, "uwt_default_ransac_params")
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def ransac_iterations(confidence, n, inliers, max_hypotheses):
+    """uwt_ransac_iterations: need(k) of the RANSAC contract, on the host (no context, no device)"""
+    return int(lib().uwt_ransac_iterations(confidence, n, inliers, max_hypotheses))
 
 
 class _Pinned:
@@ -675,6 +704,50 @@ class Context:
                                                           C.c_void_p(t.ctypes.data), _p(nt, C.c_int32), cap, C.c_float(ratio),
                                                           C.c_void_p(d_matches_ptr), C.c_void_p(d_counts_ptr)))
         return cap
+
+    @staticmethod
+    def _ransac_block(pairs, cap, kp_cap):
+        """A list of per-pair (matches, kp_prev [n, 2], kp_cur [m, 2]) in the fixed-stride form of the RANSAC calls: (cap, kp_cap,
+        matches [P, cap] MATCH, n_matches [P], kp_prev [P, kp_cap, 2], n_kp_prev [P], kp_cur [P, kp_cap, 2], n_kp_cur [P])."""
+        pairs = [(np.ascontiguousarray(m, MATCH).reshape(-1), np.ascontiguousarray(a, np.float32).reshape(-1, 2),
+                  np.ascontiguousarray(b, np.float32).reshape(-1, 2)) for m, a, b in pairs]
+        cap = max([cap or 1] + [len(m) for m, _, _ in pairs])
+        kp_cap = max([kp_cap or 1] + [max(len(a), len(b)) for _, a, b in pairs])
+        P = len(pairs)
+        mt, nm = np.zeros((P, cap), MATCH), np.zeros(P, np.int32)
+        k0, k1 = np.zeros((P, kp_cap, 2), np.float32), np.zeros((P, kp_cap, 2), np.float32)
+        n0, n1 = np.zeros(P, np.int32), np.zeros(P, np.int32)
+        for i, (m, a, b) in enumerate(pairs):
+            mt[i, :len(m)], k0[i, :len(a)], k1[i, :len(b)] = m, a, b
+            nm[i], n0[i], n1[i] = len(m), len(a), len(b)
+        return cap, kp_cap, mt, nm, k0, n0, k1, n1
+
+    def ransac_inliers_batch(self, pairs, params=None, cap=None, kp_cap=None):
+        """RobustMatcher::ransacTest for many pairs (uwt_ransac_inliers_batch): pairs is a list of (matches, kp_prev, kp_cur).
+        Returns one (mask uint8 [n], good matches MATCH [count], info RANSAC_INFO record) per pair."""
+        cap, kp_cap, mt, nm, k0, n0, k1, n1 = self._ransac_block(pairs, cap, kp_cap)
+        P = nm.size
+        mask, good = np.zeros((P, cap), np.uint8), np.zeros((P, cap), MATCH)
+        cnt, info = np.zeros(P, np.int32), np.zeros(P, RANSAC_INFO)
+        self._chk(lib().uwt_ransac_inliers_batch(self._h, P, C.c_void_p(mt.ctypes.data), _p(nm, C.c_int32), cap, _p(k0, C.c_float),
+                                                 _p(n0, C.c_int32), _p(k1, C.c_float), _p(n1, C.c_int32), kp_cap,
+                                                 C.byref(params) if params is not None else None, C.c_void_p(mask.ctypes.data),
+                                                 C.c_void_p(good.ctypes.data), _p(cnt, C.c_int32), C.c_void_p(info.ctypes.data)))
+        return [(mask[i, :nm[i]].copy(), good[i, :cnt[i]].copy(), info[i].copy()) for i in range(P)]
+
+    def ransac_inliers_batch_async(self, d_matches_ptr, d_n_matches_ptr, cap, keypoints, d_mask_ptr, d_good_ptr, d_counts_ptr,
+                                   d_info_ptr, params=None, kp_cap=None):
+        """The same with the matches and their counts in device memory (d_matches_ptr: P x cap MATCH, d_n_matches_ptr: P int32, as
+        match_descriptors_batch_async left them) and the results left there (d_mask_ptr: P x cap bytes, d_good_ptr: P x cap MATCH,
+        d_counts_ptr: P int32, d_info_ptr: P RANSAC_INFO); keypoints: a list of per-pair (kp_prev, kp_cur).  sync() to wait.
+        Returns kp_cap."""
+        _, kp_cap, _, _, k0, n0, k1, n1 = self._ransac_block([(np.zeros(0, MATCH), a, b) for a, b in keypoints], None, kp_cap)
+        self._chk(lib().uwt_ransac_inliers_batch_async(self._h, n0.size, C.c_void_p(d_matches_ptr), C.c_void_p(d_n_matches_ptr), cap,
+                                                       _p(k0, C.c_float), _p(n0, C.c_int32), _p(k1, C.c_float), _p(n1, C.c_int32),
+                                                       kp_cap, C.byref(params) if params is not None else None,
+                                                       C.c_void_p(d_mask_ptr), C.c_void_p(d_good_ptr), C.c_void_p(d_counts_ptr),
+                                                       C.c_void_p(d_info_ptr)))
+        return kp_cap
 
     def add_patch_points(self, lvl, pts, patch_size=5, cap=None):
         """Tracker::AddPatchPointsFeatures (src/Tracker.cpp:599-629).  Returns (table, full count)."""

@@ -15,6 +15,7 @@
 
 #include "uwt_launch.h"
 #include "uwt_match.h"
+#include "uwt_ransac.h"
 
 using namespace uwt;
 
@@ -120,6 +121,17 @@ struct uwt_ctx {
   size_t match_part_bytes = 0;
   void* match_out = nullptr;
   size_t match_out_bytes = 0;
+  // RANSAC inlier selection (uwt_ransac_inliers_batch*): the staged key points of both frames, their counts, the (x, y, x', y')
+  // table of every match and, for the synchronous call, its inputs and results — grown on use; and need(k) of the contract for
+  // every N in 8..UWT_MATCH_MAX_ROWS, k in 8..N (allocated whole on first use, 33 MB; a row is filled the first time a call can
+  // meet its N under the parameters the rows were computed for)
+  void* ransac_buf = nullptr;
+  size_t ransac_buf_bytes = 0;
+  int* ransac_need = nullptr;
+  std::vector<int> ransac_need_host;
+  std::vector<unsigned char> ransac_row_done;
+  double ransac_need_confidence = 0.0;
+  int ransac_need_hypotheses = 0;
   void* stage[2] = {nullptr, nullptr};  // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
   size_t stage_bytes[2] = {0, 0};
   bool profiling = false;
@@ -1238,6 +1250,8 @@ int uwt_destroy(uwt_ctx* c) {
   if (c->match_cnt) (void)hipFree(c->match_cnt);
   if (c->match_part) (void)hipFree(c->match_part);
   if (c->match_out) (void)hipFree(c->match_out);
+  if (c->ransac_buf) (void)hipFree(c->ransac_buf);
+  if (c->ransac_need) (void)hipFree(c->ransac_need);
   if (c->h_feat) (void)hipHostFree(c->h_feat);
   for (hipEvent_t e : c->ev_feat)
     if (e) (void)hipEventDestroy(e);
@@ -2689,6 +2703,208 @@ int uwt_match_descriptors_batch(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32
   for (int p = 0; p < n_pairs; p++) {   // the rows past a pair's count stay as the caller left them
     counts_out[p] = cnt[(size_t)p];
     std::copy(tmp.begin() + (size_t)p * cap, tmp.begin() + (size_t)p * cap + cnt[(size_t)p], matches_out + (size_t)p * cap);
+  }
+  return UWT_OK;
+}
+
+// ---- RANSAC inlier selection (RobustMatcher::ransacTest, src/Tracker.cpp:105-169; the contract: include/uwt.h) -------------------
+int uwt_default_ransac_params(uwt_ransac_params* p) {
+  if (!p) return UWT_ERR_INVALID_ARG;
+  p->distance = 3.0;      // distance_, include/Tracker.h:82
+  p->confidence = 0.99;   // confidence_, include/Tracker.h:83
+  p->max_hypotheses = 1000;
+  p->seed = 0;
+  return UWT_OK;
+}
+
+int32_t uwt_ransac_iterations(double confidence, int32_t n, int32_t inliers, int32_t max_hypotheses) {
+  const int32_t H = max_hypotheses;
+  if (confidence == 1.0 || inliers <= 0 || n <= 0) return H;
+  const double w = (double)inliers / (double)n;
+  const double w2 = w * w, w4 = w2 * w2, w8 = w4 * w4;
+  const double num = std::log(1.0 - confidence);
+  const double den = w8 >= 1.0 ? -HUGE_VAL : std::log(1.0 - w8);
+  if (den >= 0.0 || -num >= (double)H * (-den)) return H;
+  return (int32_t)std::rint(num / den);
+}
+
+namespace {
+
+static_assert(sizeof(RansacInfo) == sizeof(uwt_ransac_info) && sizeof(uwt_ransac_info) == 88, "uwt_ransac_info layout");
+static_assert(sizeof(uwt_ransac_params) == 24, "uwt_ransac_params layout");
+static_assert(kRansacMaxHypotheses == UWT_RANSAC_MAX_HYPOTHESES, "RANSAC limits of include/uwt.h");
+
+size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// The checks both forms share; *rp: the parameters in force.  Nothing is enqueued when a check fails.
+int ransac_check(uwt_ctx* c, const char* what, int n_pairs, int cap, const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur,
+                 const int32_t* n_kp_cur, int kp_cap, const uwt_ransac_params* params, uwt_ransac_params* rp) {
+  if (n_pairs < 1 || cap < 1 || kp_cap < 1 || !kp_prev || !n_kp_prev || !kp_cur || !n_kp_cur)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null list, n_pairs < 1, cap < 1 or kp_cap < 1");
+  if (params) *rp = *params;
+  else uwt_default_ransac_params(rp);
+  if (!std::isfinite(rp->distance) || rp->distance < 0.0 || !(rp->confidence > 0.0 && rp->confidence <= 1.0) || rp->max_hypotheses < 1 ||
+      rp->max_hypotheses > UWT_RANSAC_MAX_HYPOTHESES)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": distance, confidence or max_hypotheses outside its range");
+  for (int p = 0; p < n_pairs; p++)
+    if (n_kp_prev[p] < 0 || n_kp_prev[p] > kp_cap || n_kp_cur[p] < 0 || n_kp_cur[p] > kp_cap)
+      return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key-point count outside 0..kp_cap");
+  if (cap > kMatchMaxRows || kp_cap > kMatchMaxRows) return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap or kp_cap above UWT_MATCH_MAX_ROWS");
+  return UWT_OK;
+}
+
+// need(k) on the device for every N of `ns` (ascending, distinct, each in 8..kMatchMaxRows): the rows that are missing under
+// these parameters are computed and uploaded on the context stream, one copy per run of neighbouring rows.
+int ransac_need_rows(uwt_ctx* c, const uwt_ransac_params& rp, const std::vector<int>& ns) {
+  if (!c->ransac_need) {
+    HIPCHK(c, hipMalloc((void**)&c->ransac_need, sizeof(int) * kRansacNeedEntries));
+    c->ransac_need_host.assign(kRansacNeedEntries, 0);
+    c->ransac_row_done.assign((size_t)kMatchMaxRows + 1, 0);
+  }
+  if (c->ransac_need_confidence != rp.confidence || c->ransac_need_hypotheses != rp.max_hypotheses) {
+    std::fill(c->ransac_row_done.begin(), c->ransac_row_done.end(), 0);
+    c->ransac_need_confidence = rp.confidence;
+    c->ransac_need_hypotheses = rp.max_hypotheses;
+  }
+  int run_first = 0, run_last = -1;
+  auto flush = [&]() -> hipError_t {
+    if (run_last < run_first) return hipSuccess;
+    const size_t b = ransac_need_row(run_first), e = ransac_need_row(run_last + 1);
+    return hipMemcpyAsync(c->ransac_need + b, c->ransac_need_host.data() + b, sizeof(int) * (e - b), hipMemcpyHostToDevice, c->stream);
+  };
+  for (int n : ns) {
+    if (c->ransac_row_done[(size_t)n]) continue;
+    int* row = c->ransac_need_host.data() + ransac_need_row(n);
+    for (int k = 8; k <= n; k++) row[k - 8] = uwt_ransac_iterations(rp.confidence, n, k, rp.max_hypotheses);
+    c->ransac_row_done[(size_t)n] = 1;
+    if (run_last >= run_first && n == run_last + 1) { run_last = n; continue; }
+    HIPCHK(c, flush());
+    run_first = run_last = n;
+  }
+  HIPCHK(c, flush());
+  return UWT_OK;
+}
+
+// Stages the key points, fills the rows of need(k) and enqueues k_ransac_gather + k_ransac on the context stream.  The matches and
+// their counts are in device memory already; `rows`: a bound of the counts (sizes the gather's grid); ns: the values of N the call
+// can meet.  `extra` bytes behind the call's own scratch are the caller's (*extra_out).
+int ransac_enqueue(uwt_ctx* c, int n_pairs, int cap, const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur,
+                   const int32_t* n_kp_cur, int kp_cap, const uwt_ransac_params& rp, int rows, const std::vector<int>& ns, size_t extra,
+                   unsigned char** extra_out, RansacArgs* a) {
+  const size_t kp_bytes = align16(sizeof(float2) * (size_t)kp_cap * n_pairs), cnt_bytes = align16(sizeof(int) * (size_t)n_pairs);
+  const size_t quad_bytes = sizeof(float4) * (size_t)cap * n_pairs;
+  int st = grow(c, &c->ransac_buf, &c->ransac_buf_bytes, 2 * kp_bytes + 2 * cnt_bytes + quad_bytes + extra);
+  if (!st) st = ransac_need_rows(c, rp, ns);
+  if (st) return st;
+  unsigned char* b = (unsigned char*)c->ransac_buf;
+  a->kp_prev = (const float2*)b;
+  a->kp_cur = (const float2*)(b + kp_bytes);
+  a->n_kp_prev = (const int*)(b + 2 * kp_bytes);
+  a->n_kp_cur = (const int*)(b + 2 * kp_bytes + cnt_bytes);
+  a->quads = (float4*)(b + 2 * kp_bytes + 2 * cnt_bytes);
+  *extra_out = b + 2 * kp_bytes + 2 * cnt_bytes + quad_bytes;
+  a->need = c->ransac_need;
+  a->cap = cap; a->kp_cap = kp_cap; a->n_pairs = n_pairs;
+  a->max_hypotheses = rp.max_hypotheses;
+  a->seed = rp.seed;
+  a->t2 = rp.distance * rp.distance;
+  a->invalid_status = UWT_ERR_INVALID_ARG;
+  const size_t kp_raw = sizeof(float2) * (size_t)kp_cap * n_pairs;
+  HIPCHK(c, hipMemcpyAsync((void*)a->kp_prev, kp_prev, kp_raw, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync((void*)a->kp_cur, kp_cur, kp_raw, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync((void*)a->n_kp_prev, n_kp_prev, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync((void*)a->n_kp_cur, n_kp_cur, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
+  return UWT_OK;
+}
+
+}  // namespace
+
+int uwt_ransac_inliers_batch_async(uwt_ctx* c, int32_t n_pairs, const uwt_match* d_matches, const int32_t* d_n_matches, int32_t cap,
+                                   const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur, const int32_t* n_kp_cur,
+                                   int32_t kp_cap, const uwt_ransac_params* params, uint8_t* d_mask_out, uwt_match* d_good_out,
+                                   int32_t* d_counts_out, uwt_ransac_info* d_info_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  const char* what = "uwt_ransac_inliers_batch_async";
+  if (!c || !d_matches || !d_n_matches || !d_mask_out || !d_good_out || !d_counts_out || !d_info_out)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  uwt_ransac_params rp;
+  int st = ransac_check(c, what, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, params, &rp);
+  if (st) return st;
+  std::vector<int> ns;   // the counts are on the device: any N up to cap
+  for (int n = kRansacMinSample; n <= cap; n++) ns.push_back(n);
+  RansacArgs a;
+  unsigned char* extra = nullptr;
+  st = ransac_enqueue(c, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, rp, cap, ns, 0, &extra, &a);
+  if (st) return st;
+  a.matches = reinterpret_cast<const MatchOut*>(d_matches);
+  a.n_matches = d_n_matches;
+  a.mask = d_mask_out;
+  a.good = reinterpret_cast<MatchOut*>(d_good_out);
+  a.counts = d_counts_out;
+  a.info = reinterpret_cast<RansacInfo*>(d_info_out);
+  launch_ransac(c->stream, a, cap);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
+int uwt_ransac_inliers_batch(uwt_ctx* c, int32_t n_pairs, const uwt_match* matches, const int32_t* n_matches, int32_t cap,
+                             const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur, const int32_t* n_kp_cur, int32_t kp_cap,
+                             const uwt_ransac_params* params, uint8_t* mask_out, uwt_match* good_out, int32_t* counts_out,
+                             uwt_ransac_info* info_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  const char* what = "uwt_ransac_inliers_batch";
+  if (!c || !matches || !n_matches || !mask_out || !good_out || !counts_out || !info_out)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  uwt_ransac_params rp;
+  int st = ransac_check(c, what, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, params, &rp);
+  if (st) return st;
+  int rows = 0;
+  std::vector<int> ns;
+  for (int p = 0; p < n_pairs; p++) {
+    const int n = n_matches[p];
+    if (n < 0 || n > cap) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": match count outside 0..cap");
+    const uwt_match* m = matches + (size_t)p * cap;
+    for (int i = 0; i < n; i++)
+      if (m[i].query_idx < 0 || m[i].query_idx >= n_kp_prev[p] || m[i].train_idx < 0 || m[i].train_idx >= n_kp_cur[p])
+        return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": match index outside its key-point count");
+    rows = std::max(rows, n);
+    if (n >= kRansacMinSample) ns.push_back(n);
+  }
+  std::sort(ns.begin(), ns.end());
+  ns.erase(std::unique(ns.begin(), ns.end()), ns.end());
+  const size_t recs = (size_t)n_pairs * cap;
+  const size_t match_bytes = align16(sizeof(MatchOut) * recs), cnt_bytes = align16(sizeof(int) * (size_t)n_pairs), mask_bytes = align16(recs);
+  const size_t info_bytes = align16(sizeof(RansacInfo) * (size_t)n_pairs);
+  RansacArgs a;
+  unsigned char* x = nullptr;
+  st = ransac_enqueue(c, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, rp, rows, ns,
+                      2 * match_bytes + 2 * cnt_bytes + mask_bytes + info_bytes, &x, &a);
+  if (st) return st;
+  a.matches = (const MatchOut*)x;
+  a.good = (MatchOut*)(x + match_bytes);
+  a.info = (RansacInfo*)(x + 2 * match_bytes);
+  a.n_matches = (const int*)(x + 2 * match_bytes + info_bytes);
+  a.counts = (int*)(x + 2 * match_bytes + info_bytes + cnt_bytes);
+  a.mask = x + 2 * match_bytes + info_bytes + 2 * cnt_bytes;
+  HIPCHK(c, hipMemcpyAsync((void*)a.matches, matches, sizeof(MatchOut) * recs, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync((void*)a.n_matches, n_matches, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
+  launch_ransac(c->stream, a, rows);
+  HIPCHK(c, hipGetLastError());
+  std::vector<uwt_match> good(recs);
+  std::vector<uint8_t> mask(recs);
+  std::vector<int32_t> cnt((size_t)n_pairs);
+  std::vector<uwt_ransac_info> info((size_t)n_pairs);
+  HIPCHK(c, hipMemcpyAsync(cnt.data(), a.counts, sizeof(int) * n_pairs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(info.data(), a.info, sizeof(RansacInfo) * n_pairs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(mask.data(), a.mask, recs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(good.data(), a.good, sizeof(MatchOut) * recs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int p = 0; p < n_pairs; p++) {   // the rows past a pair's counts stay as the caller left them
+    const size_t r0 = (size_t)p * cap;
+    counts_out[p] = cnt[(size_t)p];
+    info_out[p] = info[(size_t)p];
+    std::copy(mask.begin() + r0, mask.begin() + r0 + n_matches[p], mask_out + r0);
+    std::copy(good.begin() + r0, good.begin() + r0 + cnt[(size_t)p], good_out + r0);
   }
   return UWT_OK;
 }

@@ -219,15 +219,22 @@ class Tracker:
 
 class RobustMatcher:
     """include/Tracker.h:65-88 — the matching half of RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258): knnMatch in
-    both directions, ratioTest twice and symmetryTest, on the GPU over the C ABI (uwt_match_descriptors_batch); getGoodKeypoints and
-    the assignment of :247-254 on the host.  NOT here, the caller's: detection and description (cuda::SURF_CUDA / cuda::ORB — the
-    descriptors are an argument) and ransacTest (cv::findFundamentalMat draws from OpenCV's RNG), which the caller runs, or skips,
-    between MatchDescriptors and MatchAndSetKeypoints and hands over as an inlier mask.
+    both directions, ratioTest twice and symmetryTest, on the GPU over the C ABI (uwt_match_descriptors_batch), ransacTest as the
+    inlier selection of uwt_ransac_inliers_batch (the contract: include/uwt.h; cv::findFundamentalMat itself draws from OpenCV's RNG
+    and is not pinned); getGoodKeypoints and the assignment of :247-254 on the host.  NOT here, the caller's: detection and
+    description (cuda::SURF_CUDA / cuda::ORB — the descriptors are an argument).  A caller with a RANSAC of their own still hands
+    its inlier mask to MatchAndSetKeypoints.
     float32 descriptors are matched under L2 (SURF), uint8 under Hamming (ORB), as createBFMatcher is set up at :199 / :221."""
 
-    def __init__(self, ctx_or_tracker, ratio=0.65):
+    def __init__(self, ctx_or_tracker, ratio=0.65, distance=3.0, confidence=0.99, refineF=True):
         self._src = ctx_or_tracker
         self.ratio_ = float(np.float32(ratio))   # include/Tracker.h:80
+        self.distance_ = float(distance)         # include/Tracker.h:82
+        self.confidence_ = float(confidence)     # include/Tracker.h:83
+        self.refineF_ = bool(refineF)            # include/Tracker.h:81; a documented no-op: the refit's result is discarded by the
+                                                 # reference (src/Tracker.cpp:124, 141-166), so there is nothing to compute
+        self.max_hypotheses_ = 1000              # no reference member: the budget of the selection (uwt_ransac_params)
+        self.seed_ = 0
 
     @property
     def _ctx(self):
@@ -244,6 +251,39 @@ class RobustMatcher:
     def MatchDescriptorsBatch(self, pairs):
         """The same for a list of (desc_prev, desc_cur) pairs in one call."""
         return self._ctx.match_descriptors_batch(pairs, ratio=self.ratio_)
+
+    def _ransac_params(self):
+        return capi.default_ransac_params(distance=self.distance_, confidence=self.confidence_, max_hypotheses=self.max_hypotheses_,
+                                          seed=self.seed_)
+
+    def ransacTest(self, matches, keypoints1, keypoints2, outMatches=None):
+        """src/Tracker.cpp:105-169: the matches that survive the epipolar test, in their order (goodMatches).  outMatches: an
+        optional list that receives them, as the reference's output argument.  Returns (outMatches, inlier mask, info): what the
+        reference returns, the fundamental matrix, is an empty Mat there (the local of :124 shadows it); info["F"] has the one the
+        selection chose."""
+        mask, good, info = self.ransacTestBatch([(matches, keypoints1, keypoints2)])[0]
+        if outMatches is not None:
+            outMatches[:] = list(good)
+        return good, mask, info
+
+    def ransacTestBatch(self, pairs):
+        """The same for a list of (matches, keypoints1, keypoints2) in one call."""
+        return self._ctx.ransac_inliers_batch(pairs, params=self._ransac_params())
+
+    def DetectAndTrackFeatures(self, _previous_frame, _current_frame, desc_prev, desc_cur, keypoints, usekeypoints=True):
+        """src/Tracker.cpp:171-258 from the matcher on, with the caller's detector output (descriptors and key points of both
+        frames): symmetric matches -> ransacTest -> getGoodKeypoints -> keypoints_ and n_matches_ of both frames.  Returns the
+        matches kept."""
+        matches = self.MatchDescriptors(desc_prev, desc_cur)
+        good, _, _ = self.ransacTest(matches, keypoints[0], keypoints[1])
+        return self.SetKeypoints(_previous_frame, _current_frame, good, keypoints)
+
+    def SetKeypoints(self, _previous_frame, _current_frame, goodMatches, keypoints):
+        """getGoodKeypoints and the assignment of src/Tracker.cpp:241-254"""
+        good = self.getGoodKeypoints(goodMatches, keypoints)
+        _previous_frame.n_matches_ = _current_frame.n_matches_ = len(goodMatches)
+        _previous_frame.keypoints_, _current_frame.keypoints_ = good
+        return goodMatches
 
     @staticmethod
     def getGoodKeypoints(goodMatches, keypoints):
