@@ -154,12 +154,18 @@ class Frame {
   SE3 rigid_transformation_;
   std::vector<float> keypoints_;                         // x0 y0 x1 y1 ... (cv::KeyPoint::pt of Frame::keypoints_)
   int n_matches_ = 0;                                    // include/System.h:93
+  std::vector<uwt_keypoint> surf_keypoints_;             // the same key points as cv::KeyPoint holds them (size, response, direction,
+                                                         // octave): what useProvidedKeypoints describes again in the next call
   std::vector<float> candidatePoints_[PYRAMID_LEVELS];   // N x 4 [x y z w] per level when a sparse producer ran
   int slot_ = -1;                 // device frame slot while bound; -1 again once the slot has gone to another frame
   Tracker* tracker_ = nullptr;    // the tracker that holds the slot
 };
 
+class RobustMatcher;
+
 class Tracker {
+  friend class RobustMatcher;   // DetectAndTrackFeatures binds both frames
+
  public:
   // include/Tracker.h:97.  `overrides` lets a caller change the constants the reference hard-codes as locals of
   // EstimatePose (src/Tracker.cpp:364-372); by default they are exactly those.
@@ -500,9 +506,11 @@ inline Frame::~Frame() {
 // include/Tracker.h:65-88 — RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258) from the matcher on: knnMatch in both
 // directions, ratioTest twice and symmetryTest on the GPU (uwt_match_descriptors_batch), ransacTest as the inlier selection of
 // uwt_ransac_inliers_batch (the contract: include/uwt.h — cv::findFundamentalMat draws from OpenCV's RNG and is not pinned);
-// getGoodKeypoints and the assignment of :247-254 on the host.  NOT here, the caller's: detection and description
-// (cuda::SURF_CUDA / cuda::ORB — descriptors are an argument).  A caller with a RANSAC of their own passes its inliers to
-// SetKeypoints instead.
+// getGoodKeypoints and the assignment of :247-254 on the host.  Detection and description with cuda::SURF_CUDA (:186-206) are
+// uwt_surf_detect_describe_batch / uwt_surf_describe_batch, SURF under the contract of include/uwt.h:
+// DetectAndTrackFeatures(previous, current, usekeypoints) is the reference's whole method.  The overloads that take the caller's
+// descriptors stay (cuda::ORB is not built; a caller brings ORB descriptors).  A caller with a RANSAC of their own passes its inliers
+// to SetKeypoints instead.
 class RobustMatcher {
  public:
   explicit RobustMatcher(Tracker* tracker) : tracker_(tracker) {}
@@ -583,14 +591,69 @@ class RobustMatcher {
     return good;
   }
 
+  // :171-258 whole, the reference's own signature: SURF on both frames on the device — the previous frame described at the key
+  // points it kept when usekeypoints is set and it has some (:192-195), the current one detected — then symmetric matches ->
+  // ransacTest -> getGoodKeypoints -> keypoints_, surf_keypoints_ and n_matches_ of both frames.  Returns the matches kept.
+  std::vector<uwt_match> DetectAndTrackFeatures(Frame* _previous_frame, Frame* _current_frame, bool usekeypoints) {
+    const int a = tracker_->bind(_previous_frame), b = tracker_->bind(_current_frame);
+    if (!tracker_->bound(_previous_frame) || _previous_frame->slot_ != a)
+      throw std::runtime_error("DetectAndTrackFeatures: more frames than slots (max_frames)");
+    uwt_surf_params sp;
+    uwt_default_surf_params(&sp);
+    sp.hessian_threshold = hessian_threshold_;
+    sp.n_octaves = n_octaves_;
+    sp.n_octave_layers = n_octave_layers_;
+    sp.upright = upright_ ? 1 : 0;
+    std::vector<uwt_keypoint> kp[2];
+    std::vector<float> desc[2];
+    if (usekeypoints && !_previous_frame->surf_keypoints_.empty()) {
+      const int32_t n = (int32_t)_previous_frame->surf_keypoints_.size();
+      kp[0].resize((size_t)n);
+      desc[0].resize((size_t)n * 64);
+      surf_check(uwt_surf_describe_batch(tracker_->ctx(), 1, &a, &sp, _previous_frame->surf_keypoints_.data(), &n, n, kp[0].data(),
+                                         desc[0].data()), "uwt_surf_describe_batch");
+    } else {
+      surf_detect(a, sp, kp[0], desc[0]);
+    }
+    surf_detect(b, sp, kp[1], desc[1]);
+    std::array<std::vector<float>, 2> xy;
+    for (int f = 0; f < 2; f++)
+      for (const uwt_keypoint& k : kp[f]) xy[(size_t)f].insert(xy[(size_t)f].end(), {k.x, k.y});
+    std::vector<uwt_match> good = DetectAndTrackFeatures(_previous_frame, _current_frame, desc[0].data(), (int)kp[0].size(), desc[1].data(),
+                                                         (int)kp[1].size(), 64, xy);
+    _previous_frame->surf_keypoints_.clear();
+    _current_frame->surf_keypoints_.clear();
+    for (const uwt_match& mt : good) {
+      _previous_frame->surf_keypoints_.push_back(kp[0][(size_t)mt.query_idx]);
+      _current_frame->surf_keypoints_.push_back(kp[1][(size_t)mt.train_idx]);
+    }
+    return good;
+  }
+
   float ratio_ = 0.65f;      // include/Tracker.h:80
   bool refineF_ = true;      // include/Tracker.h:81 — a no-op here: the refit's result is discarded by the reference (:124, :141-166)
   double distance_ = 3.0;    // include/Tracker.h:82
   double confidence_ = 0.99; // include/Tracker.h:83
   int32_t max_hypotheses_ = 1000;   // no reference member: the budget of the selection (uwt_ransac_params)
   uint32_t seed_ = 0;
+  double hessian_threshold_ = 100.0;   // cuda::SURF_CUDA's defaults (`cuda::SURF_CUDA surf;`, :188)
+  int32_t n_octaves_ = 4, n_octave_layers_ = 2;
+  bool upright_ = false;
+  int32_t surf_cap_ = UWT_MATCH_MAX_ROWS;   // key points of a frame at most: what the matcher takes
 
  private:
+  void surf_check(int st, const char* what) {
+    if (st != UWT_OK) throw std::runtime_error(std::string(what) + ": " + uwt_status_string(st) + " (" + uwt_last_error(tracker_->ctx()) + ")");
+  }
+  void surf_detect(int slot, const uwt_surf_params& sp, std::vector<uwt_keypoint>& kp, std::vector<float>& desc) {
+    kp.resize((size_t)surf_cap_);
+    desc.resize((size_t)surf_cap_ * 64);
+    int32_t count = 0;
+    surf_check(uwt_surf_detect_describe_batch(tracker_->ctx(), 1, &slot, &sp, surf_cap_, kp.data(), desc.data(), &count),
+               "uwt_surf_detect_describe_batch");
+    kp.resize((size_t)count);
+    desc.resize((size_t)count * 64);
+  }
   std::vector<uwt_match> match(int norm, const void* a, int n, const void* b, int m, int dim, size_t elem) {
     if (n < 0 || m < 0 || dim < 1) throw std::invalid_argument("MatchDescriptors: negative count or dim < 1");
     const int cap = std::max(1, std::max(n, m));

@@ -429,8 +429,9 @@ int uwt_estimate_pose_candidates_batch(uwt_ctx* ctx, int32_t n_pairs, const int3
  * src/Tracker.cpp:171-258), has four parts.  Built here: matcher->knnMatch(.., 2) in both directions (:202-203, :224-225), the two
  * ratioTest calls and symmetryTest (:52-102, :229-236), and, since round 10, ransacTest (:106-169) as the inlier selection of
  * uwt_ransac_inliers_batch below — under a contract of this library's own, because cv::findFundamentalMat draws from OpenCV's RNG
- * and cannot be pinned.  NOT built, the caller's: detection and description (cuda::SURF_CUDA / cuda::ORB, :184-222 — descriptors
- * come from the caller); getGoodKeypoints (:260-270) is a host gather in the mirrors (include/uw_tracker.hpp,
+ * and cannot be pinned.  Detection and description with cuda::SURF_CUDA (:184-206), since round 11, are uwt_surf_detect_describe_batch
+ * and uwt_surf_describe_batch further below, under a contract of the same kind.  NOT built: cuda::ORB (:207-222; Hamming matching
+ * serves callers who bring ORB descriptors).  getGoodKeypoints (:260-270) is a host gather in the mirrors (include/uw_tracker.hpp,
  * uw-slam_amd/tracker.py).
  *
  * Per pair: a query set A (n rows, the previous frame) and a train set B (m rows, the current frame) of descriptors of `dim`
@@ -565,6 +566,131 @@ int uwt_ransac_inliers_batch_async(uwt_ctx* ctx, int32_t n_pairs, const uwt_matc
                                    int32_t cap, const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur,
                                    const int32_t* n_kp_cur, int32_t kp_cap, const uwt_ransac_params* params, uint8_t* d_mask_out,
                                    uwt_match* d_good_out, int32_t* d_counts_out, uwt_ransac_info* d_info_out);
+
+/* ---- SURF detection and description: the first part of RobustMatcher::DetectAndTrackFeatures --------------------------------- */
+
+/* cuda::SURF_CUDA surf; surf(img, mask, keypoints, descriptors, useProvided) (src/Tracker.cpp:186-206; the tracker is built with
+ * RobustMatcher(0), :273, so SURF is the live detector).  SURF_CUDA's internals (its scaled Haar patterns, fastAtan2, its own
+ * interpolation) are not reproducible from the reference tree and no OpenCV build is pinned; as with ransacTest this is
+ * SURF — Bay et al.'s fast-Hessian detector and 64-element descriptor — under a contract of this library's own, complete here, built
+ * only from integer arithmetic and IEEE f32 / f64 add, subtract, multiply, divide, compare, floorf and sqrtf (no FMA, no angle
+ * function), so that tests/surf_ref.py restates it in numpy and the device agrees with it bit for bit.  Parameters:
+ * uwt_surf_params, defaults those of SURF_CUDA (hessianThreshold 100, 4 octaves, 2 layers per octave, not extended, not upright).
+ * Not built: masks, the extended 128-element descriptor, ORB.
+ *
+ * Integral image.  From the level-0 u8 plane of a slot (w x h): I is (h + 1) x (w + 1) uint32, I[y][x] = the sum of the pixels
+ *   above and left of (x, y), modulo 2^32.  box(x0, y0, x1, y1) = I[y1][x1] - I[y0][x1] - I[y1][x0] + I[y0][x0] in uint32 arithmetic,
+ *   then widened to int64: the sum over [x0, x1) x [y0, y1).  A CLIPPED box first clamps x0, x1 to [0, w] and y0, y1 to [0, h].
+ * Layers.  L = n_octave_layers + 2 response layers per octave.  Octave o, layer i has filter size s = (9 + 6 i) << o on the grid of
+ *   step 1 << o: gw = w >> o by gh = h >> o points, point (gx, gy) centred on pixel (gx << o, gy << o).  Its window is the s x s
+ *   pixels from (cx - (s >> 1), cy - (s >> 1)) on (an even size has its centre at window pixel s / 2); a response exists only where
+ *   the whole window lies inside the image.  An octave whose largest filter, (9 + 6 (L - 1)) << o, exceeds min(w, h) is skipped.
+ * Response.  The 9 x 9 box patterns are scaled to the nearest pixel: pattern coordinate c = 0..9 is window coordinate
+ *   p(c) = (c s + 4) / 9 (integer division; s is a multiple of 3, so no tie arises).  In window coordinates (x0, y0, x1, y1):
+ *     Dxx = box(p0, p2, p9, p7) - 3 box(p3, p2, p6, p7)        Dyy = box(p2, p0, p7, p9) - 3 box(p2, p3, p7, p6)
+ *     Dxy = box(p1, p1, p4, p4) + box(p5, p5, p8, p8) - box(p5, p1, p8, p4) - box(p1, p5, p4, p8)
+ *   (32 corners) in int64; num = 100 Dxx Dyy - 81 Dxy Dxy in int64; response = (double)num / (100.0 * s2 * s2), s2 = (double)(s s):
+ *   one conversion, one f64 division (the denominator is exact).  Laplacian sign = the sign of Dxx + Dyy: 1, -1 or 0.
+ * Candidates.  A point of a middle layer (i = 1 .. L - 2) with response > hessian_threshold and strictly greater than all 26
+ *   neighbours (layers i - 1 .. i + 1, gx - 1 .. gx + 1, gy - 1 .. gy + 1), every one of which must exist.
+ * Refinement, in f64, R(dl, dy, dx) the neighbour's response, v = R(0, 0, 0), every expression left to right:
+ *     gx' = (R(0,0,1) - R(0,0,-1)) * 0.5    gy' = (R(0,1,0) - R(0,-1,0)) * 0.5    gs' = (R(1,0,0) - R(-1,0,0)) * 0.5
+ *     dxx = (R(0,0,1) - 2.0 * v) + R(0,0,-1)    dyy = (R(0,1,0) - 2.0 * v) + R(0,-1,0)    dss = (R(1,0,0) - 2.0 * v) + R(-1,0,0)
+ *     dxy = (((R(0,1,1) - R(0,1,-1)) - R(0,-1,1)) + R(0,-1,-1)) * 0.25
+ *     dxs = (((R(1,0,1) - R(1,0,-1)) - R(-1,0,1)) + R(-1,0,-1)) * 0.25
+ *     dys = (((R(1,1,0) - R(1,-1,0)) - R(-1,1,0)) + R(-1,-1,0)) * 0.25
+ *   and [dxx dxy dxs; dxy dyy dys; dxs dys dss] (ox, oy, os)^T = (b0, b1, b2) = (-gx', -gy', -gs') is solved by elimination without
+ *   pivoting in the order x, y, layer:
+ *     p0 = dxx;  m1 = dxy / p0;  m2 = dxs / p0;
+ *     a11 = dyy - m1 * dxy;  a12 = dys - m1 * dxs;  c1 = b1 - m1 * b0;  a21 = dys - m2 * dxy;  a22 = dss - m2 * dxs;  c2 = b2 - m2 * b0;
+ *     p1 = a11;  m3 = a21 / p1;  p2 = a22 - m3 * a12;  c2 = c2 - m3 * c1;
+ *     os = c2 / p2;  oy = (c1 - a12 * os) / p1;  ox = ((b0 - dxy * oy) - dxs * os) / p0.
+ *   The candidate is dropped if p0, p1 or p2 is 0 or unless |ox| <= 1, |oy| <= 1 and |os| <= 1 (a NaN drops it).  Then, each rounded
+ *   to f32 once: x = ((double)gx + ox) * (double)(1 << o), y likewise, size = (double)s + os * (double)(6 << o), response = v.
+ *   octave = o; laplacian = the Laplacian sign at (i, gx, gy).
+ * Order and capacity.  Survivors are ordered by (octave, layer i, gy, gx) ascending.  If there are more than cap, the cap first by
+ *   (the f32 response descending, order ascending) are kept, and reported in the order above.
+ * Orientation (upright: the direction is (1, 0)).  sc = size * 0.13333334f (1.2 / 9).  rnd(v) = (int)floorf(v + 0.5f).
+ *   haar(px, py, hh): dx = clipped box(px, py - hh, px + hh, py + hh) - clipped box(px - hh, py - hh, px, py + hh) (right minus left),
+ *   dy = clipped box(px - hh, py, px + hh, py + hh) - clipped box(px - hh, py - hh, px + hh, py) (bottom minus top), int64, each
+ *   converted to f32 once.  hh = max(1, rnd(2.0f * sc)) (side 4 sigma).  Samples: the grid points (i, j), -6 <= i, j <= 6,
+ *   i i + j j < 36, j outermost, both ascending (109 of them): (dx, dy) = haar(rnd(x + (float)i * sc), rnd(y + (float)j * sc), hh),
+ *   wx = W[|j|][|i|] * dx, wy = W[|j|][|i|] * dy with UWT_SURF_ORI_WEIGHT (exp(-(i i + j j) / 12.5): sigma 2.5), row-major 7 x 7:
+ *   1.0f, 0.923116326f, 0.726149023f, 0.486752242f, 0.27803731f, 0.135335281f, 0.0561347641f,
+ *   0.923116326f, 0.852143764f, 0.670320034f, 0.449328959f, 0.256660789f, 0.12493021f, 0.0518189184f,
+ *   0.726149023f, 0.670320034f, 0.52729243f, 0.353454679f, 0.201896518f, 0.0982735828f, 0.0407622047f,
+ *   0.486752242f, 0.449328959f, 0.353454679f, 0.236927763f, 0.135335281f, 0.0658747554f, 0.0273237228f,
+ *   0.27803731f, 0.256660789f, 0.201896518f, 0.135335281f, 0.0773047432f, 0.0376282558f, 0.0156075582f,
+ *   0.135335281f, 0.12493021f, 0.0982735828f, 0.0658747554f, 0.0376282558f, 0.0183156393f, 0.00759701384f,
+ *   0.0561347641f, 0.0518189184f, 0.0407622047f, 0.0273237228f, 0.0156075582f, 0.00759701384f, 0.00315111154f
+ *   Windows: UWT_SURF_ORI_DIR, U[k] = (cos, sin)(10 k degrees), k = 0..35:
+ *   1.0f, 0.0f, 0.98480773f, 0.173648179f, 0.939692616f, 0.342020154f, 0.866025388f, 0.5f,
+ *   0.766044438f, 0.642787635f, 0.642787635f, 0.766044438f, 0.5f, 0.866025388f, 0.342020154f, 0.939692616f,
+ *   0.173648179f, 0.98480773f, 0.0f, 1.0f, -0.173648179f, 0.98480773f, -0.342020154f, 0.939692616f,
+ *   -0.5f, 0.866025388f, -0.642787635f, 0.766044438f, -0.766044438f, 0.642787635f, -0.866025388f, 0.5f,
+ *   -0.939692616f, 0.342020154f, -0.98480773f, 0.173648179f, -1.0f, 0.0f, -0.98480773f, -0.173648179f,
+ *   -0.939692616f, -0.342020154f, -0.866025388f, -0.5f, -0.766044438f, -0.642787635f, -0.642787635f, -0.766044438f,
+ *   -0.5f, -0.866025388f, -0.342020154f, -0.939692616f, -0.173648179f, -0.98480773f, 0.0f, -1.0f,
+ *   0.173648179f, -0.98480773f, 0.342020154f, -0.939692616f, 0.5f, -0.866025388f, 0.642787635f, -0.766044438f,
+ *   0.766044438f, -0.642787635f, 0.866025388f, -0.5f, 0.939692616f, -0.342020154f, 0.98480773f, -0.173648179f
+ *   Sample (wx, wy) belongs to window k iff U[k].x * wy - U[k].y * wx >= 0 and wx * U[k+6].y - wy * U[k+6].x > 0 (k + 6 modulo 36;
+ *   each cross product two f32 multiplies and one subtract).  Per window, from 0: sx = sx + wx, sy = sy + wy over its samples in
+ *   sample order; n2 = sx * sx + sy * sy.  The window with the largest n2 wins, the lowest k on a tie.  n = sqrtf(sx * sx + sy * sy);
+ *   (dir_x, dir_y) = (sx / n, sy / n), or (1, 0) when n == 0.
+ * Descriptor.  (c, s) = (dir_x, dir_y); hh = max(1, rnd(sc)) (side 2 sigma).  Sample (tx, ty), 0 <= tx, ty < 20, of the 20 sigma
+ *   window: rx = ((float)tx - 9.5f) * sc, ry = ((float)ty - 9.5f) * sc; at pixel corner (rnd(x + (rx * c - ry * s)),
+ *   rnd(y + (rx * s + ry * c))) (dx, dy) = haar(.., hh); g = G[k(tx)] * G[k(ty)], k(t) = t < 10 ? 9 - t : t - 10, with
+ *   UWT_SURF_DESC_GAUSS (exp(-(k + 0.5)^2 / (2 * 3.3^2))):
+ *   0.988587201f, 0.901851177f, 0.750541389f, 0.569815516f, 0.394651532f,
+ *   0.249352202f, 0.143725067f, 0.0755738765f, 0.0362518989f, 0.0158638898f
+ *   wdx = g * dx, wdy = g * dy; rotated into the key point's frame: ex = wdx * c + wdy * s, ey = wdy * c - wdx * s.  Sub-region (a, b),
+ *   0 <= a, b < 4, holds tx = 5 a + u, ty = 5 b + v; from 0, over v outermost and u innermost: sum = sum + e for e = ex, ey, |ex|,
+ *   |ey|: elements 4 (4 b + a) + 0..3.  Norm: q[l] = d[l] * d[l]; for m = 32, 16, 8, 4, 2, 1: q[l] = q[l] + q[l ^ m] (all l at
+ *   once); n = sqrtf(q[0]); the descriptor is d[l] / n, or 64 zeros when n == 0.
+ * A frame's output depends neither on the batch it is in, nor on its place there, nor on uwt_tuning, nor on the order in which the
+ * device happens to find the candidates. */
+typedef struct uwt_keypoint {
+  float x, y, size, response, dir_x, dir_y;   /* pixels; the filter size; the Hessian response; the unit direction        */
+  int32_t octave, laplacian;                   /* 0..3; the sign of the Laplacian: 1, -1, 0                                */
+} uwt_keypoint;
+typedef struct uwt_surf_params {
+  double hessian_threshold;   /* 100; finite                                                 */
+  int32_t n_octaves;          /* 4; 1..4                                                     */
+  int32_t n_octave_layers;    /* 2; 1..4: n_octave_layers + 2 response layers per octave     */
+  int32_t upright;            /* 0; != 0: no orientation, every direction is (1, 0)          */
+} uwt_surf_params;
+
+/* {100.0, 4, 2, 0} */
+int uwt_default_surf_params(uwt_surf_params* p);
+/* cv::KeyPoint::angle of a direction: atan2(dir_y, dir_x) in double, in degrees in [0, 360).  A host function, outside the bit
+ * contract. */
+double uwt_keypoint_angle_deg(float dir_x, float dir_y);
+/* Detection and description of the frames resident in slots[0 .. n_frames), host out, synchronous.  params: null for the defaults.
+ * kp_out: n_frames x cap records, frame f's counts_out[f] key points from kp_out[f * cap] on; desc_out_or_null: n_frames x cap x 64
+ * floats, the fixed-stride layout uwt_match_descriptors_batch takes as query / train (null: detection only, directions included).
+ * The rows past a frame's count are not written.  A frame too small for octave 0, or a flat one, has count 0; that is no error.
+ * UWT_ERR_INVALID_ARG with nothing enqueued and the outputs untouched: n_frames < 1, cap < 1, a null list or output, a slot out of
+ * range, a non-finite threshold, n_octaves or n_octave_layers outside 1..4.  UWT_ERR_CAPACITY likewise: cap > UWT_MATCH_MAX_ROWS.
+ * n_frames is NOT bounded by max_frames (a slot may appear twice).  Scratch (integral images, the candidates, the results) belongs to
+ * the context, grows on demand and is sized per chunk of frames: a large batch runs as several chunks. */
+int uwt_surf_detect_describe_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_surf_params* params_or_null,
+                                   int32_t cap, uwt_keypoint* kp_out, float* desc_out_or_null, int32_t* counts_out);
+/* The same without waiting: results in DEVICE memory (d_kp_out: n_frames x cap, d_desc_out_or_null: n_frames x cap x 64,
+ * d_counts_out: n_frames) on the context's stream, ordered against uwt_upload_frames_async; uwt_sync() to wait. */
+int uwt_surf_detect_describe_batch_async(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_surf_params* params_or_null,
+                                         int32_t cap, uwt_keypoint* d_kp_out, float* d_desc_out_or_null, int32_t* d_counts_out);
+/* useProvidedKeypoints (src/Tracker.cpp:192-195): orientation and descriptors at the caller's key points.  keypoints_in: n_frames x
+ * cap records, frame f's n_in[f] (0..cap) from keypoints_in[f * cap] on; x, y and size are read (finite, |x|, |y| <= 1e6,
+ * 0 < size <= 4096, else UWT_ERR_INVALID_ARG), response, octave and laplacian pass through.  kp_out (may be keypoints_in): the same
+ * records with their directions; desc_out: n_frames x cap x 64 floats.  Errors as above. */
+int uwt_surf_describe_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_surf_params* params_or_null,
+                            const uwt_keypoint* keypoints_in, const int32_t* n_in, int32_t cap, uwt_keypoint* kp_out,
+                            float* desc_out);
+/* Per-stage entries.  The integral image of a slot: (h + 1) x (w + 1) uint32 to host memory. */
+int uwt_surf_integral(uwt_ctx* ctx, int32_t slot, uint32_t* out);
+/* One response layer (octave 0..3, layer 0..5) on its octave's grid: *gw x *gh doubles (w >> octave by h >> octave) to host
+ * memory, NaN where no response exists. */
+int uwt_surf_response_layer(uwt_ctx* ctx, int32_t slot, int32_t octave, int32_t layer, double* out, int32_t* gw, int32_t* gh);
 
 /* ---- next to the path: frame ingest---------------------------------------------------------------- */
 

@@ -1,0 +1,308 @@
+"""SURF detection and description on the device (uwt_surf_*): key points compared AS INTEGERS (f32 fields as uint32, then octave
+and laplacian) and descriptors as uint32 with the numpy restatement of the contract (tests/surf_ref.py) — no tolerance anywhere."""
+import importlib
+
+import numpy as np
+import pytest
+
+import match_ref as M
+import ransac_ref as R
+import surf_cases as K
+import surf_ref as S
+
+ARITH_INDEPENDENT = True   # SURF has no arithmetic set
+INVALID_ARG, CAPACITY = 1, 5   # uwt_status_code (include/uwt.h)
+INTR = {(160, 96): (131.25, 131.25, 79.5, 47.5), (97, 61): (80.0, 80.0, 48.0, 30.0), (256, 240): (210.0, 210.0, 127.5, 119.5),
+        (640, 480): (525.0, 525.0, 319.5, 239.5), (735, 479): (458.654, 457.296, 367.0, 239.0)}
+
+
+@pytest.fixture(scope="module")
+def capi():
+    m = importlib.import_module("uw-slam_amd.capi")
+    m.lib()
+    return m
+
+
+def make_ctx(capi, w, h, max_frames=2, **over):
+    over.setdefault("n_levels", 1)
+    over.setdefault("first_level", 0)
+    over.setdefault("last_level", 0)
+    return capi.Context(capi.default_params(w, h, *INTR[(w, h)], max_frames=max_frames, max_pairs=1, **over))
+
+
+_ref = {}
+
+
+def ref_of(name, img, cap=4096, **over):
+    """the restatement's (key points, descriptors) of a named frame, computed once"""
+    key = (name, cap, tuple(sorted(over.items())))
+    if key not in _ref:
+        p = S.default_params()
+        p.update(over)
+        _ref[key] = S.detect_describe(img, p, cap)
+    return _ref[key]
+
+
+def params_of(capi, **over):
+    return capi.default_surf_params(**over) if over else None
+
+
+def frame_of(name, w, h):
+    if name == "blobs":
+        return K.blob_image(w, h)
+    return K.texture(w, h, int(name[1:]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h,name", [(160, 96, "t3"), (97, 61, "t11"), (256, 240, "blobs"), (640, 480, "t11"), (735, 479, "t12")])
+def test_gpu_sizes_equal_restatement(capi, w, h, name):
+    img = frame_of(name, w, h)
+    ctx = make_ctx(capi, w, h)
+    ctx.upload_frames(0, img[None])
+    kp, desc = ctx.surf_detect_describe_batch([0])[0]
+    wk, wd = ref_of("%s_%dx%d" % (name, w, h), img)
+    print(w, h, name, "key points", len(wk), "per octave", np.bincount(wk["octave"], minlength=4))
+    assert len(wk) > 0
+    assert K.same_keypoints(kp, wk) is None, K.same_keypoints(kp, wk)
+    assert K.same_descriptors(desc, wd) is None, K.same_descriptors(desc, wd)
+    if name == "blobs":
+        assert set(kp["octave"].tolist()) == {0, 1, 2, 3}
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h,name", [(160, 96, "t3"), (97, 61, "t11"), (256, 240, "blobs")])
+def test_gpu_integral_equals_restatement(capi, w, h, name):
+    img = frame_of(name, w, h)
+    ctx = make_ctx(capi, w, h)
+    ctx.upload_frames(0, img[None])
+    got = ctx.surf_integral(0)
+    assert got.shape == (h + 1, w + 1) and got.dtype == np.uint32
+    assert np.array_equal(got, S.integral(img))
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h,name", [(160, 96, "t3"), (256, 240, "blobs")])
+def test_gpu_response_layers_equal_restatement(capi, w, h, name):
+    img = frame_of(name, w, h)
+    ctx = make_ctx(capi, w, h)
+    ctx.upload_frames(0, img[None])
+    I = S.integral(img)
+    for o in range(4):
+        for i in range(4):
+            got = ctx.surf_response_layer(0, o, i)
+            want, _ = S.response_layer(I, o, i)
+            assert got.shape == want.shape == (h >> o, w >> o)
+            # NaN marks "no response here": the same frame of absent responses, the same bits elsewhere
+            assert np.array_equal(np.isnan(got), np.isnan(want)), (o, i)
+            assert np.array_equal(got.view(np.uint64)[~np.isnan(want)], want.view(np.uint64)[~np.isnan(want)]), (o, i)
+    assert np.isnan(ctx.surf_response_layer(0, 3, 3)).all() == (min(w, h) < 216 + 8)   # 160 x 96: octave 3 does not fit
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_batch_of_six_slots(capi):
+    """a textured frame, the same again, a flat frame, a blob frame; then the overflowing call (cap = 32) and the upright one over the
+    same six slots: each frame equals its single-frame result and the restatement"""
+    w, h = 256, 240
+    tex, blobs = K.texture(w, h, 21), K.blob_image(w, h)
+    frames = np.stack([tex, tex, K.flat(w, h), blobs, K.texture(w, h, 22), K.texture(w, h, 23)])
+    names = ["t21", "t21", "flat", "blobs", "t22", "t23"]
+    ctx = make_ctx(capi, w, h, max_frames=6)
+    ctx.upload_frames(0, frames)
+    single = make_ctx(capi, w, h, max_frames=1)
+    for cap, over in ((4096, {}), (32, {}), (4096, {"upright": 1})):
+        got = ctx.surf_detect_describe_batch([0, 1, 2, 3, 4, 5], params=params_of(capi, **over), cap=cap)
+        for f in range(6):
+            wk, wd = ref_of(names[f] + "_256x240", frames[f], cap, **over)
+            assert K.same_keypoints(got[f][0], wk) is None, (cap, over, f, K.same_keypoints(got[f][0], wk))
+            assert K.same_descriptors(got[f][1], wd) is None, (cap, over, f, K.same_descriptors(got[f][1], wd))
+            single.upload_frames(0, frames[f][None])
+            alone = single.surf_detect_describe_batch([0], params=params_of(capi, **over), cap=cap)[0]
+            assert K.same_keypoints(got[f][0], alone[0]) is None and K.same_descriptors(got[f][1], alone[1]) is None, (cap, over, f)
+        assert len(got[2][0]) == 0                                         # the flat frame
+        assert got[0][0].tobytes() == got[1][0].tobytes() and got[0][1].tobytes() == got[1][1].tobytes()
+        if over:
+            assert all((g[0]["dir_x"] == 1).all() and (g[0]["dir_y"] == 0).all() for g in got)
+        if cap == 32:
+            full = ref_of("t21_256x240", tex)[0]
+            assert len(full) > 32 and len(got[0][0]) == 32
+            # exactly the 32 strongest, in contract order: the order of the full list
+            strongest = np.sort(np.lexsort((np.arange(len(full)), -full["response"].astype(np.float64)))[:32])
+            assert K.same_keypoints(got[0][0], full[strongest]) is None
+    # a permuted batch with a repeated slot: a frame's place does not matter
+    perm = ctx.surf_detect_describe_batch([3, 0, 3, 5])
+    want = ctx.surf_detect_describe_batch([0, 3, 5])
+    for a, b in ((0, 1), (1, 0), (2, 1), (3, 2)):
+        assert perm[a][0].tobytes() == want[b][0].tobytes() and perm[a][1].tobytes() == want[b][1].tobytes()
+    single.close()
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_detection_only_and_tuning_independent(capi):
+    w, h = 160, 96
+    img = K.texture(w, h, 3)
+    ctx = make_ctx(capi, w, h)
+    ctx.upload_frames(0, img[None])
+    wk, wd = ref_of("t3_160x96", img)
+    kp, desc = ctx.surf_detect_describe_batch([0], describe=False)[0]
+    assert desc is None and K.same_keypoints(kp, wk) is None
+    ctx.set_tuning(split=1, target_blocks=64, coarse=0)
+    kp, desc = ctx.surf_detect_describe_batch([0])[0]
+    assert K.same_keypoints(kp, wk) is None and K.same_descriptors(desc, wd) is None
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_describe_at_given_keypoints(capi):
+    w, h = 160, 96
+    frames = np.stack([K.texture(w, h, 3), K.texture(w, h, 4)])
+    ctx = make_ctx(capi, w, h)
+    ctx.upload_frames(0, frames)
+    det = ctx.surf_detect_describe_batch([0, 1])
+    # at the key points a detection returned: that detection's directions and descriptors
+    got = ctx.surf_describe_batch([0, 1], [det[0][0], det[1][0]])
+    for f in range(2):
+        assert len(det[f][0]) > 0
+        assert K.same_keypoints(got[f][0], det[f][0]) is None, K.same_keypoints(got[f][0], det[f][0])
+        assert K.same_descriptors(got[f][1], det[f][1]) is None, K.same_descriptors(got[f][1], det[f][1])
+    # hand-placed key points near all four borders (box clipping), with and without orientation; the second frame has none
+    border = K.border_keypoints(w, h)
+    for over in ({}, {"upright": 1}):
+        p = S.default_params()
+        p.update(over)
+        got = ctx.surf_describe_batch([1, 0], [border, border[:0]], params=params_of(capi, **over))
+        wk, wd = S.describe(frames[1], border, p)
+        assert K.same_keypoints(got[0][0], wk) is None, K.same_keypoints(got[0][0], wk)
+        assert K.same_descriptors(got[0][1], wd) is None, K.same_descriptors(got[0][1], wd)
+        assert len(got[1][0]) == 0
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_async_equals_sync_and_rows_past_count_untouched(capi):
+    import torch
+    w, h, cap = 160, 96, 256
+    frames = np.stack([K.texture(w, h, 3), K.flat(w, h)])
+    ctx = make_ctx(capi, w, h)
+    ctx.upload_frames(0, frames)
+    kp = np.zeros((2, cap), capi.KEYPOINT)
+    kp.view(np.uint8)[:] = 0xA5
+    desc = np.full((2, cap, 64), -7.0, np.float32)
+    cnt = np.full(2, -1, np.int32)
+    got = ctx.surf_detect_describe_batch([0, 1], cap=cap, out=(kp, desc, cnt))
+    n = int(cnt[0])
+    assert 0 < n < cap and cnt[1] == 0 and len(got[0][0]) == n
+    assert (kp[0, n:].view(np.uint8) == 0xA5).all() and (kp[1].view(np.uint8) == 0xA5).all()
+    assert (desc[0, n:] == -7.0).all() and (desc[1] == -7.0).all()
+    d_kp = torch.zeros((2, cap, 8), dtype=torch.int32, device="cuda")
+    d_desc = torch.zeros((2, cap, 64), dtype=torch.float32, device="cuda")
+    d_cnt = torch.full((2,), -1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()   # torch's fill kernels run on torch's stream, not on the context's
+    ctx.surf_detect_describe_batch_async([0, 1], d_kp.data_ptr(), d_desc.data_ptr(), d_cnt.data_ptr(), cap=cap)
+    ctx.sync()
+    a_cnt = d_cnt.cpu().numpy()
+    assert a_cnt.tolist() == cnt.tolist()
+    a_kp = d_kp.cpu().numpy().view(capi.KEYPOINT).reshape(2, cap)
+    assert a_kp[0, :n].tobytes() == kp[0, :n].tobytes()
+    assert d_desc.cpu().numpy()[0, :n].tobytes() == desc[0, :n].tobytes()
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_argument_errors_leave_outputs_untouched(capi):
+    w, h, cap = 160, 96, 64
+    ctx = make_ctx(capi, w, h)
+    ctx.upload_frames(0, K.texture(w, h, 3)[None])
+
+    def fresh(c=cap):
+        kp = np.zeros((1, min(c, 64)), capi.KEYPOINT)
+        kp.view(np.uint8)[:] = 0x5A
+        return kp, np.full((1, min(c, 64), 64), -3.0, np.float32), np.full(1, -9, np.int32)
+
+    bad = [(dict(slots=[2]), INVALID_ARG),
+           (dict(slots=[-1]), INVALID_ARG),
+           (dict(params=dict(hessian_threshold=float("nan"))), INVALID_ARG),
+           (dict(params=dict(hessian_threshold=float("inf"))), INVALID_ARG),
+           (dict(params=dict(n_octaves=0)), INVALID_ARG),
+           (dict(params=dict(n_octaves=5)), INVALID_ARG),
+           (dict(params=dict(n_octave_layers=0)), INVALID_ARG),
+           (dict(params=dict(n_octave_layers=5)), INVALID_ARG),
+           (dict(cap=0), INVALID_ARG),
+           (dict(cap=capi.UWT_MATCH_MAX_ROWS + 1), CAPACITY)]
+    for kw, status in bad:
+        c = kw.get("cap", cap)
+        out = fresh(c)
+        with pytest.raises(capi.UwtError) as e:
+            ctx.surf_detect_describe_batch(kw.get("slots", [0]), params=capi.default_surf_params(**kw.get("params", {})), cap=c, out=out)
+        assert e.value.status == status, (kw, e.value.status)
+        assert (out[0].view(np.uint8) == 0x5A).all() and (out[1] == -3.0).all() and out[2][0] == -9, kw
+    k = K.border_keypoints(w, h)[:2].copy()
+    k["size"][1] = 0.0
+    with pytest.raises(capi.UwtError):
+        ctx.surf_describe_batch([0], [k])
+    k["size"][1] = 10.0
+    k["x"][0] = np.nan
+    with pytest.raises(capi.UwtError):
+        ctx.surf_describe_batch([0], [k])
+    # the context still works
+    assert len(ctx.surf_detect_describe_batch([0])[0][0]) > 0
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_end_to_end_detect_match_ransac_pose(capi, synth):
+    """render a pair -> detect and describe both -> match -> ransac -> pose on the inlier key points; every intermediate equals the
+    CPU chain (surf_ref -> match_ref -> ransac_ref)"""
+    w, h = 256, 240
+    ref, tgt, _, _, _ = synth.render_pair(w, h, *INTR[(w, h)], seed=31)
+    ctx = make_ctx(capi, w, h, n_levels=5, first_level=0, last_level=0)
+    ctx.upload_frames(0, np.stack([ref, tgt]))
+    ctx.build_pyramids(0, 2)
+    ctx.apply_gradient(0, 2)
+    (k0, d0), (k1, d1) = ctx.surf_detect_describe_batch([0, 1])
+    (wk0, wd0), (wk1, wd1) = S.detect_describe(ref), S.detect_describe(tgt)
+    assert K.same_keypoints(k0, wk0) is None and K.same_keypoints(k1, wk1) is None
+    assert K.same_descriptors(d0, wd0) is None and K.same_descriptors(d1, wd1) is None
+    matches = ctx.match_descriptors_batch([(d0, d1)])[0]
+    want_m, _, _ = M.match(wd0, wd1, 0.65)
+    assert matches.tobytes() == want_m.tobytes()
+    xy0, xy1 = np.stack([k0["x"], k0["y"]], 1), np.stack([k1["x"], k1["y"]], 1)
+    mask, good, info = ctx.ransac_inliers_batch([(matches, xy0, xy1)])[0]
+    wmask, wgood, winfo = R.ransac(want_m, xy0, xy1)
+    assert mask.tobytes() == np.asarray(wmask, np.uint8).tobytes() and good.tobytes() == wgood.tobytes()
+    assert int(info["n_inliers"]) == int(winfo["n_inliers"]) >= 8
+    print("key points", len(k0), len(k1), "matches", len(matches), "inliers", len(good))
+    poses, stats = ctx.estimate_pose_features_batch([0], [1], [xy0[good["query_idx"]][:200]], raise_on_pair_failure=True)
+    assert stats[0]["status"] == 0 and np.isfinite(poses).all()
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_python_mirror_live_loop(capi, synth):
+    """System::Tracking through the Python mirror (uw-slam_amd.tracker.Tracking): DetectAndTrackFeatures(previous, current,
+    usekeypoints) keeps what the CPU chain keeps, and the pose call that follows succeeds"""
+    T = importlib.import_module("uw-slam_amd.tracker")
+    w, h = 256, 240
+    intr = INTR[(w, h)]
+    frames = synth.render_sequence(w, h, *intr, 3, seed=17)[0]
+    tracker = T.Tracker(False, max_frames=4)
+    tracker.InitializePyramid(w, h, np.array([[intr[0], 0, intr[2]], [0, intr[1], intr[3]], [0, 0, 1]], np.float32))
+    rm = T.RobustMatcher(tracker)
+    fr = [T.Frame(f, None, i) for i, f in enumerate(frames)]
+    st = T.Tracking(tracker, rm, fr[0], fr[1])
+    (k0, d0), (k1, d1) = S.detect_describe(frames[0]), S.detect_describe(frames[1])
+    m, _, _ = M.match(d0, d1, 0.65)
+    xy0, xy1 = np.stack([k0["x"], k0["y"]], 1), np.stack([k1["x"], k1["y"]], 1)
+    _, good, _ = R.ransac(m, xy0, xy1)
+    assert st["status"] == 0 and fr[0].n_matches_ == fr[1].n_matches_ == len(good) >= 8
+    assert fr[0].keypoints_.tobytes() == xy0[good["query_idx"]].tobytes() and fr[1].keypoints_.tobytes() == xy1[good["train_idx"]].tobytes()
+    assert K.same_keypoints(fr[1].surf_keypoints_, k1[good["train_idx"]]) is None
+    # the next pair: frame 1 is described at the key points it kept when it has 110 matches or more (src/System.cpp:208)
+    kept = fr[1].surf_keypoints_.copy()
+    st = T.Tracking(tracker, rm, fr[1], fr[2])
+    assert st["status"] == 0 and 8 <= fr[1].n_matches_ <= (len(kept) if len(kept) >= 110 else 4096)
+    assert np.isfinite(fr[1].rigid_transformation_).all()
+    tracker._ctx.close()

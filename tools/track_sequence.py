@@ -25,6 +25,26 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def track_live(w, h, intr, frames, depths, arith=0):
+    """System::Tracking over consecutive frames through the Python mirror: (poses [n - 1, 7], stats, matches kept per pair)"""
+    M = importlib.import_module("uw-slam_amd.tracker")
+    fx, fy, cx, cy = intr
+    tracker = M.Tracker(bool(depths), max_frames=4, arith=arith)
+    tracker.InitializePyramid(w, h, np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32))
+    rm = M.RobustMatcher(tracker)
+    mk = lambda i: M.Frame(frames[i], depths[i] if depths else None, i)
+    poses, stats, kept = [], [], []
+    prev = mk(0)
+    for i in range(1, len(frames)):
+        cur = mk(i)
+        st = M.Tracking(tracker, rm, prev, cur)
+        poses.append(np.array(prev.rigid_transformation_, np.float32))
+        stats.append(st)
+        kept.append(int(prev.n_matches_))
+        prev = cur
+    return np.array(poses, np.float32).reshape(-1, 7), stats, kept
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", required=True)
@@ -41,6 +61,8 @@ def main():
     ap.add_argument("--arith", choices=["opencv", "legacy"], default="opencv", help="arithmetic set (include/uwt.h uwt_arith)")
     ap.add_argument("--fixed-iters", type=int, default=0, help="0: the reference schedule (levels 4..1, early exit)")
     ap.add_argument("--groundtruth"); ap.add_argument("--euroc", action="store_true"); ap.add_argument("--tum", action="store_true")
+    ap.add_argument("--live", action="store_true", help="the reference's live loop, System::Tracking (src/System.cpp:193-223): SURF key "
+                    "points detected, described, matched and RANSAC-filtered on the device, then EstimatePoseFeatures on their patches")
     ap.add_argument("--out", default="trajectory")
     a = ap.parse_args()
     S = importlib.import_module("uw-slam_amd.sequence")
@@ -73,7 +95,10 @@ def main():
         over.update(n_levels=4, first_level=3, last_level=0, max_iters=a.fixed_iters, early_exit=0)
     trk = S.SequenceTracker(a.width, a.height, fx, fy, cx - x0, cy - y0, depth=bool(depths), **over)
     t0 = time.perf_counter()
-    poses, stats = trk.track(frames, depths)
+    if a.live:
+        poses, stats, n_matches = track_live(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"])
+    else:
+        poses, stats = trk.track(frames, depths)
     dt = time.perf_counter() - t0
     traj = trk.trajectory(poses)
     ref = trk.trajectory(poses, reference_visualiser=True)
@@ -81,6 +106,8 @@ def main():
     bad = sum(s["status"] != 0 for s in stats)
     metrics = dict(pairs=int(len(poses)), failed=int(bad), seconds=dt, crop_offset=[int(x0), int(y0)],
                    iterations=[int(s["iterations"]) for s in stats])
+    if a.live:
+        metrics["n_matches"] = n_matches
     if a.groundtruth:
         ts, gtp = (T.read_groundtruth_euroc if a.euroc else T.read_groundtruth_tum)(a.groundtruth)
         idx_all = np.clip(T.ground_truth_indices(len(gtp), len(names), a.start, euroc=a.euroc), 0, len(gtp) - 1)

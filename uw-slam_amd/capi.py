@@ -21,6 +21,9 @@ MATCH = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("distance", "<f4"
 RANSAC_MAX_HYPOTHESES = 65536
 RANSAC_INFO = np.dtype([("status", "<i4"), ("n_inliers", "<i4"), ("best_hypothesis", "<i4"), ("hypotheses_run", "<i4"),
                         ("F", "<f8", (9,))])                                                 # uwt_ransac_info
+UWT_MATCH_MAX_ROWS = 4096   # descriptors / key points per set at most (include/uwt.h)
+KEYPOINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("response", "<f4"), ("dir_x", "<f4"), ("dir_y", "<f4"),
+                     ("octave", "<i4"), ("laplacian", "<i4")])                                  # uwt_keypoint
 
 
 class Params(C.Structure):
@@ -50,6 +53,11 @@ class Tuning(C.Structure):
 class RansacParams(C.Structure):
     """uwt_ransac_params: distance_ / confidence_ of RobustMatcher (include/Tracker.h:82-83), the hypothesis budget, the seed"""
     _fields_ = [("distance", C.c_double), ("confidence", C.c_double), ("max_hypotheses", C.c_int32), ("seed", C.c_uint32)]
+
+
+class SurfParams(C.Structure):
+    """uwt_surf_params: SURF_CUDA's hessianThreshold, nOctaves, nOctaveLayers, upright"""
+    _fields_ = [("hessian_threshold", C.c_double), ("n_octaves", C.c_int32), ("n_octave_layers", C.c_int32), ("upright", C.c_int32)]
 
 
 class Level(C.Structure):
@@ -85,6 +93,8 @@ SYMBOLS = [
     "uwt_default_ransac_params", "uwt_ransac_iterations", "uwt_ransac_inliers_batch", "uwt_ransac_inliers_batch_async",
     "uwt_obtain_patch_points_batch", "uwt_track_features_batch_async", "uwt_estimate_pose_features_batch",
     "uwt_track_candidates_batch_async", "uwt_estimate_pose_candidates_batch",
+    "uwt_default_surf_params", "uwt_keypoint_angle_deg", "uwt_surf_detect_describe_batch", "uwt_surf_detect_describe_batch_async",
+    "uwt_surf_describe_batch", "uwt_surf_integral", "uwt_surf_response_layer",
 ]
 
 _lib = None
@@ -127,6 +137,8 @@ def lib():
         _lib.uwt_last_error.argtypes = [C.c_void_p]
         _lib.uwt_ransac_iterations.restype = C.c_int32
         _lib.uwt_ransac_iterations.argtypes = [C.c_double, C.c_int32, C.c_int32, C.c_int32]
+        _lib.uwt_keypoint_angle_deg.restype = C.c_double
+        _lib.uwt_keypoint_angle_deg.argtypes = [C.c_float, C.c_float]
     return _lib
 
 
@@ -167,6 +179,24 @@ def default_ransac_params(**over):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def default_surf_params(**over):
+    """uwt_default_surf_params: hessian_threshold 100, n_octaves 4, n_octave_layers 2, upright 0"""
+    p = SurfParams()
+    st = lib().uwt_default_surf_params(C.byref(p))
+    if st:
+        raise UwtError(st, "uwt_default_surf_params")
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def keypoint_angle_deg(dir_x, dir_y):
+    """uwt_keypoint_angle_deg: cv::KeyPoint::angle of a key point's direction, degrees in [0, 360), on the host"""
+    return float(lib().uwt_keypoint_angle_deg(C.c_float(dir_x), C.c_float(dir_y)))
 
 
 def ransac_iterations(confidence, n, inliers, max_hypotheses):
@@ -748,6 +778,57 @@ class Context:
                                                        C.c_void_p(d_mask_ptr), C.c_void_p(d_good_ptr), C.c_void_p(d_counts_ptr),
                                                        C.c_void_p(d_info_ptr)))
         return kp_cap
+
+    def surf_detect_describe_batch(self, slots, params=None, cap=UWT_MATCH_MAX_ROWS, describe=True, out=None):
+        """SURF key points and descriptors of the frames resident in `slots` (uwt_surf_detect_describe_batch).  Returns one
+        (key points KEYPOINT [n], descriptors float32 [n, 64] or None) per frame.  out: (kp [F, cap] KEYPOINT, desc [F, cap, 64]
+        float32 or None, counts [F] int32) to be written in place — the rows past a frame's count stay as they are."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        F = slots.size
+        if out is None:
+            out = (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, 64), np.float32) if describe else None, np.zeros(F, np.int32))
+        kp, desc, cnt = out
+        self._chk(lib().uwt_surf_detect_describe_batch(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None,
+                                                       cap, C.c_void_p(kp.ctypes.data),
+                                                       C.c_void_p(desc.ctypes.data) if desc is not None else None, _p(cnt, C.c_int32)))
+        return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy() if desc is not None else None) for i in range(F)]
+
+    def surf_detect_describe_batch_async(self, slots, d_kp_ptr, d_desc_ptr, d_counts_ptr, params=None, cap=UWT_MATCH_MAX_ROWS):
+        """The same enqueued on the context stream, results in device memory (d_kp_ptr: F x cap KEYPOINT, d_desc_ptr: F x cap x 64
+        float32 or None, d_counts_ptr: F int32); sync() to wait."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        self._chk(lib().uwt_surf_detect_describe_batch_async(self._h, slots.size, _p(slots, C.c_int32),
+                                                             C.byref(params) if params is not None else None, cap, C.c_void_p(d_kp_ptr),
+                                                             C.c_void_p(d_desc_ptr) if d_desc_ptr else None, C.c_void_p(d_counts_ptr)))
+
+    def surf_describe_batch(self, slots, keypoints_list, params=None, cap=None):
+        """Orientation and descriptors at the caller's key points (uwt_surf_describe_batch: useProvidedKeypoints): keypoints_list
+        holds one KEYPOINT array per frame (x, y, size are read).  Returns one (key points with directions, descriptors) per frame."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        kin = [np.ascontiguousarray(k, KEYPOINT).reshape(-1) for k in keypoints_list]
+        cap = max([cap or 1] + [len(k) for k in kin])
+        F = slots.size
+        kp, n = np.zeros((F, cap), KEYPOINT), np.zeros(F, np.int32)
+        for i, k in enumerate(kin):
+            kp[i, :len(k)], n[i] = k, len(k)
+        out, desc = np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, 64), np.float32)
+        self._chk(lib().uwt_surf_describe_batch(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None,
+                                                C.c_void_p(kp.ctypes.data), _p(n, C.c_int32), cap, C.c_void_p(out.ctypes.data),
+                                                C.c_void_p(desc.ctypes.data)))
+        return [(out[i, :n[i]].copy(), desc[i, :n[i]].copy()) for i in range(F)]
+
+    def surf_integral(self, slot):
+        """The integral image of a slot's level-0 plane (uwt_surf_integral): (h + 1) x (w + 1) uint32"""
+        out = np.zeros((self.params.height + 1, self.params.width + 1), np.uint32)
+        self._chk(lib().uwt_surf_integral(self._h, slot, _p(out, C.c_uint32)))
+        return out
+
+    def surf_response_layer(self, slot, octave, layer):
+        """One fast-Hessian response layer on its octave's grid (uwt_surf_response_layer): gh x gw float64, NaN where none exists"""
+        out = np.zeros(max(1, (self.params.height >> max(octave, 0)) * (self.params.width >> max(octave, 0))), np.float64)
+        gw, gh = C.c_int32(0), C.c_int32(0)
+        self._chk(lib().uwt_surf_response_layer(self._h, slot, octave, layer, _p(out, C.c_double), C.byref(gw), C.byref(gh)))
+        return out[:gw.value * gh.value].reshape(gh.value, gw.value)
 
     def add_patch_points(self, lvl, pts, patch_size=5, cap=None):
         """Tracker::AddPatchPointsFeatures (src/Tracker.cpp:599-629).  Returns (table, full count)."""

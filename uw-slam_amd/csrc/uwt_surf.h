@@ -1,0 +1,59 @@
+// uwt_surf.h — internal: the records, limits and launchers of SURF detection and description (uwt_surf_*; include/uwt.h states
+// the contract).  The kernels are in uwt_surf_kernels.h, their only launches in uwt_launch_surf.hip; uwt_capi.hip sees this header
+// alone.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace uwt {
+
+constexpr int kSurfMaxOctaves = 4;
+constexpr int kSurfMaxLayers = 6;      // response layers of an octave at most: n_octave_layers (1..4) + 2
+constexpr int kSurfTile = 32;          // grid points of a response tile along x and y; the tile in LDS has a one-point halo
+constexpr int kSurfBlock = 256;
+constexpr int kSurfSelectBlock = 1024;
+constexpr int kSurfDescWaves = 4;      // key points of a describe block: one wave each
+
+struct SurfKeypoint { float x, y, size, response, dir_x, dir_y; int octave, laplacian; };
+
+constexpr int surf_filter_size(int octave, int layer) { return (9 + 6 * layer) << octave; }
+
+// an upper bound on a frame's candidates: a strict maximum of its 3 x 3 has no candidate beside it, so a middle layer holds at most
+// ceil(gw / 2) x ceil(gh / 2) of them
+inline size_t surf_raw_bound(int w, int h, int n_octaves, int layers) {
+  size_t n = 0;
+  for (int o = 0; o < n_octaves; o++) n += (size_t)(layers - 2) * (size_t)(((w >> o) + 1) / 2) * (size_t)(((h >> o) + 1) / 2);
+  return n < 64 ? 64 : n;
+}
+
+struct SurfArgs {
+  const uint8_t* img;        // the level-0 image plane of slot 0
+  size_t frame_stride;       // bytes from one slot's plane to the next
+  int pitch, w, h;
+  const int* slots;          // the chunk's slots (device)
+  int n_frames;
+  uint32_t* integral;        // n_frames x (h + 1) x (w + 1)
+  double threshold;
+  int n_octaves, layers, upright;
+  SurfKeypoint* raw;         // n_frames x raw_cap: the refined candidates in the order they happened to arrive
+  unsigned long long* raw_key;   // their places in the contract's order: ((octave * 8 + layer) << 40) | (gy << 20) | gx
+  int* raw_count;            // n_frames, zero before the response launches
+  int raw_cap;               // surf_raw_bound: never exceeded
+  unsigned char* keep;       // n_frames x raw_cap: work area of the selection
+  SurfKeypoint* kp;          // n_frames x cap: the key points in contract order
+  float* desc;               // n_frames x cap x 64, or null
+  int* counts;               // n_frames
+  int cap;
+};
+
+// both passes of the integral image of every frame of the chunk
+void launch_surf_integral(hipStream_t s, const SurfArgs& a);
+// response + suppression + refinement of every octave that fits, then the ordered selection: a.kp, a.counts
+void launch_surf_detect(hipStream_t s, const SurfArgs& a);
+// one response layer of frame 0 of the chunk on the octave's (w >> octave) x (h >> octave) grid, NaN where none exists
+void launch_surf_response_layer(hipStream_t s, const SurfArgs& a, int octave, int layer, double* out);
+// orientation (unless a.upright) and descriptors of a.kp[f * cap .. + counts[f]); rows: the largest count the batch can hold
+void launch_surf_describe(hipStream_t s, const SurfArgs& a, int rows);
+
+}  // namespace uwt

@@ -32,6 +32,8 @@ class Frame:
         self.rigid_transformation_ = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)  # qx qy qz qw tx ty tz
         self.keypoints_ = np.zeros((0, 2), np.float32)       # cv::KeyPoint::pt of Frame::keypoints_
         self.n_matches_ = 0                                  # include/System.h:93
+        self.surf_keypoints_ = np.zeros(0, capi.KEYPOINT)    # the same key points as cv::KeyPoint holds them (size, response, direction,
+                                                             # octave): what useProvidedKeypoints describes again in the next call
         self.candidatePoints_ = {}                           # level -> N x 4 [x y z w] when a sparse producer ran
         self._slot = None
 
@@ -221,8 +223,10 @@ class RobustMatcher:
     """include/Tracker.h:65-88 — the matching half of RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258): knnMatch in
     both directions, ratioTest twice and symmetryTest, on the GPU over the C ABI (uwt_match_descriptors_batch), ransacTest as the
     inlier selection of uwt_ransac_inliers_batch (the contract: include/uwt.h; cv::findFundamentalMat itself draws from OpenCV's RNG
-    and is not pinned); getGoodKeypoints and the assignment of :247-254 on the host.  NOT here, the caller's: detection and
-    description (cuda::SURF_CUDA / cuda::ORB — the descriptors are an argument).  A caller with a RANSAC of their own still hands
+    and is not pinned); getGoodKeypoints and the assignment of :247-254 on the host.  Detection and description with
+    cuda::SURF_CUDA (:186-206) are uwt_surf_detect_describe_batch / uwt_surf_describe_batch, SURF under the contract of include/uwt.h:
+    DetectAndTrackFeatures(previous, current, usekeypoints) is the reference's whole method.  The forms that take the caller's
+    descriptors stay (cuda::ORB is not built; a caller brings ORB descriptors).  A caller with a RANSAC of their own still hands
     its inlier mask to MatchAndSetKeypoints.
     float32 descriptors are matched under L2 (SURF), uint8 under Hamming (ORB), as createBFMatcher is set up at :199 / :221."""
 
@@ -235,6 +239,8 @@ class RobustMatcher:
                                                  # reference (src/Tracker.cpp:124, 141-166), so there is nothing to compute
         self.max_hypotheses_ = 1000              # no reference member: the budget of the selection (uwt_ransac_params)
         self.seed_ = 0
+        self.hessian_threshold_ = 100.0          # cuda::SURF_CUDA's defaults (`cuda::SURF_CUDA surf;`, src/Tracker.cpp:188)
+        self.n_octaves_, self.n_octave_layers_, self.upright_ = 4, 2, False
 
     @property
     def _ctx(self):
@@ -270,10 +276,36 @@ class RobustMatcher:
         """The same for a list of (matches, keypoints1, keypoints2) in one call."""
         return self._ctx.ransac_inliers_batch(pairs, params=self._ransac_params())
 
-    def DetectAndTrackFeatures(self, _previous_frame, _current_frame, desc_prev, desc_cur, keypoints, usekeypoints=True):
-        """src/Tracker.cpp:171-258 from the matcher on, with the caller's detector output (descriptors and key points of both
-        frames): symmetric matches -> ransacTest -> getGoodKeypoints -> keypoints_ and n_matches_ of both frames.  Returns the
-        matches kept."""
+    def DetectAndTrackFeatures(self, _previous_frame, _current_frame, *args, usekeypoints=None):
+        """src/Tracker.cpp:171-258.  DetectAndTrackFeatures(previous, current, usekeypoints), the reference's signature: SURF on
+        both frames on the device (the previous frame is described at the key points it kept when usekeypoints is set and it has
+        some, :192-195; the current one is detected), symmetric matches -> ransacTest -> getGoodKeypoints -> keypoints_,
+        surf_keypoints_ and n_matches_ of both frames.  DetectAndTrackFeatures(previous, current, desc_prev, desc_cur, keypoints):
+        the same from the matcher on, with the caller's detector output.  Returns the matches kept."""
+        if len(args) >= 3:
+            return self._track_descriptors(_previous_frame, _current_frame, *args[:3])
+        if len(args) == 2:
+            raise TypeError("DetectAndTrackFeatures(previous, current, usekeypoints) or (previous, current, desc_prev, desc_cur, keypoints)")
+        usekeypoints = bool(args[0]) if args else bool(usekeypoints)
+        tracker = self._src
+        if not hasattr(tracker, "_bind"):
+            raise RuntimeError("DetectAndTrackFeatures(previous, current, usekeypoints) needs a RobustMatcher built over a Tracker")
+        a, b = tracker._bind(_previous_frame), tracker._bind(_current_frame)
+        if _previous_frame._slot != a:
+            raise RuntimeError("DetectAndTrackFeatures: more frames than slots (max_frames)")
+        params = capi.default_surf_params(hessian_threshold=self.hessian_threshold_, n_octaves=self.n_octaves_,
+                                          n_octave_layers=self.n_octave_layers_, upright=int(self.upright_))
+        if usekeypoints and len(_previous_frame.surf_keypoints_):
+            kp0, d0 = self._ctx.surf_describe_batch([a], [_previous_frame.surf_keypoints_], params=params)[0]
+            kp1, d1 = self._ctx.surf_detect_describe_batch([b], params=params)[0]
+        else:
+            (kp0, d0), (kp1, d1) = self._ctx.surf_detect_describe_batch([a, b], params=params)
+        xy = (np.stack([kp0["x"], kp0["y"]], 1), np.stack([kp1["x"], kp1["y"]], 1))
+        good = self._track_descriptors(_previous_frame, _current_frame, d0, d1, xy)
+        _previous_frame.surf_keypoints_, _current_frame.surf_keypoints_ = kp0[good["query_idx"]], kp1[good["train_idx"]]
+        return good
+
+    def _track_descriptors(self, _previous_frame, _current_frame, desc_prev, desc_cur, keypoints):
         matches = self.MatchDescriptors(desc_prev, desc_cur)
         good, _, _ = self.ransacTest(matches, keypoints[0], keypoints[1])
         return self.SetKeypoints(_previous_frame, _current_frame, good, keypoints)
@@ -306,6 +338,21 @@ class RobustMatcher:
         _previous_frame.n_matches_ = _current_frame.n_matches_ = len(matches)
         _previous_frame.keypoints_, _current_frame.keypoints_ = good
         return matches
+
+
+def Tracking(tracker, robust_matcher, previous_frame, current_frame):
+    """System::Tracking() (src/System.cpp:193-223), the live loop's body for one pair, every call on the device: ApplyGradient of both
+    frames, DetectAndTrackFeatures(previous, current, usekeypoints) with the `n_matches_ < 110` rule of :208, ObtainPatchesPoints,
+    EstimatePoseFeatures -> previous_frame.rigid_transformation_.  Returns the alignment's stats."""
+    usekeypoints = True
+    if not previous_frame.obtained_gradients_:
+        tracker.ApplyGradient(previous_frame)
+    tracker.ApplyGradient(current_frame)
+    if previous_frame.n_matches_ < 110:
+        usekeypoints = False
+    robust_matcher.DetectAndTrackFeatures(previous_frame, current_frame, usekeypoints)
+    tracker.ObtainPatchesPoints(previous_frame)
+    return tracker.EstimatePoseFeatures(previous_frame, current_frame)
 
 
 class LS:
