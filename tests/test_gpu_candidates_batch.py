@@ -340,6 +340,36 @@ def test_gpu_track_candidates_batch_async_equals_sync(capi, synth):
 
 
 @pytest.mark.gpu
+def test_gpu_candidates_growth_under_a_queued_async_call(capi, synth):
+    """A one-pair asynchronous call is still queued when a synchronous call of the same context for four pairs needs every buffer
+    of the stage larger: both give, as bytes, what the same two calls give on fresh contexts."""
+    import torch
+    size = (160, 96, (131.25, 131.25, 79.5, 47.5))
+    sc = scenes(synth, size, True)
+    ref, tgt = pair_list(4, seed=33)
+
+    def run(ctx_small, ctx_large):
+        d_poses = torch.zeros((1, 7), dtype=torch.float32, device="cuda")
+        d_stats = torch.zeros((1, 4), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()  # torch's fill kernels run on torch's stream, not on the context's
+        ctx_small.track_candidates_batch_async(ref[:1], tgt[:1], d_poses.data_ptr(), d_stats.data_ptr())
+        poses, stats = ctx_large.estimate_pose_candidates_batch(ref, tgt)     # no sync in between
+        ctx_small.sync()
+        assert d_stats.cpu().numpy()[0, 0] == 0 and all(s["status"] == 0 for s in stats)   # every alignment ran to its end
+        return (d_poses.cpu().numpy().tobytes() + d_stats.cpu().numpy().tobytes(),
+                poses.tobytes() + repr([sorted(s.items()) for s in stats]).encode())
+
+    ctxs = [make_ctx(capi, size, True, 2 * N_SCENES, 4) for _ in range(3)]
+    for c in ctxs:
+        load(c, sc, True)
+    got = run(ctxs[0], ctxs[0])
+    want = run(ctxs[1], ctxs[2])
+    for c in ctxs:
+        c.close()
+    assert got == want
+
+
+@pytest.mark.gpu
 def test_gpu_candidates_batch_cpp_mirror_matches_oracle(capi, O, synth, tmp_path, arith):
     """uw::Tracker::EstimatePoseCandidatesBatch at 640 x 480 on three pairs against the oracle (the tracker's defaults: the
     reference schedule)."""

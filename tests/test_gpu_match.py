@@ -151,6 +151,34 @@ def test_gpu_batch_independence_and_async(capi, synth, kind):
     ctx2.close()
 
 
+@pytest.mark.gpu
+def test_gpu_growth_under_a_queued_async_call(capi, synth):
+    """A small asynchronous call is still queued when a synchronous call of the same context needs every buffer of the stage
+    larger: both give, as bytes, what the same two calls give on fresh contexts."""
+    import torch
+    small = [synth.descriptor_pair(900, 40, 40, 64, "l2")[:2]]
+    large = [synth.descriptor_pair(901 + i, 300, 280, 64, "l2")[:2] for i in range(4)]
+
+    def run(ctx_small, ctx_large):
+        d_m = torch.full((1, 64, 3), -7, dtype=torch.int32, device="cuda")
+        d_c = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()   # torch's fill kernels run on torch's stream, not on the context's
+        ctx_small.match_descriptors_batch_async(d_m.data_ptr(), d_c.data_ptr(), small, cap=64)
+        big = ctx_large.match_descriptors_batch(large, cap=512)     # no sync in between
+        ctx_small.sync()
+        return d_c.cpu().numpy().tobytes() + d_m.cpu().numpy().tobytes(), [b.tobytes() for b in big]
+
+    ctx = small_ctx(capi)
+    got = run(ctx, ctx)
+    ctx.close()
+    a, b = small_ctx(capi), small_ctx(capi)
+    want = run(a, b)
+    a.close()
+    b.close()
+    assert np.frombuffer(got[0][:4], np.int32)[0] > 0 and sum(len(x) for x in got[1]) > 0
+    assert got[0] == want[0] and got[1] == want[1]
+
+
 def raw_call(capi, ctx, name, n_pairs, norm, dim, q, nq, t, nt, cap, ratio, out, cnt):
     def ptr(a):
         return C.c_void_p(a.ctypes.data) if a is not None else None

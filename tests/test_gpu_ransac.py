@@ -164,6 +164,41 @@ def test_gpu_batch_independence_and_async(capi):
 
 
 @pytest.mark.gpu
+def test_gpu_growth_under_a_queued_async_call(capi):
+    """A small asynchronous call is still queued when a synchronous call of the same context needs the stage's buffer larger:
+    both give, as bytes, what the same two calls give on fresh contexts."""
+    import torch
+    small = K.scene(700, 24, 0.0, 0.3)[:3]
+    large = mixed_pairs()[:4]
+    cap, kp_cap, mt, nm, *_ = capi.Context._ransac_block([small], 32, 32)
+
+    def run(ctx_small, ctx_large):
+        d_m = torch.from_numpy(mt.view(np.int32).reshape(1, cap, 3)).cuda()
+        d_n = torch.from_numpy(nm).cuda()
+        d_mask = torch.full((1, cap), 0x5A, dtype=torch.uint8, device="cuda")
+        d_good = torch.full((1, cap, 3), -7, dtype=torch.int32, device="cuda")
+        d_cnt = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        d_info = torch.full((1, 11), -7, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()   # torch's copies and fills run on torch's stream, not on the context's
+        ctx_small.ransac_inliers_batch_async(d_m.data_ptr(), d_n.data_ptr(), cap, [small[1:]], d_mask.data_ptr(), d_good.data_ptr(),
+                                             d_cnt.data_ptr(), d_info.data_ptr(), kp_cap=kp_cap)
+        big = ctx_large.ransac_inliers_batch(large, cap=1536, kp_cap=1536)     # no sync in between
+        ctx_small.sync()
+        first = b"".join(t.cpu().numpy().tobytes() for t in (d_cnt, d_mask, d_good, d_info))
+        return first, [m.tobytes() + g.tobytes() + i.tobytes() for m, g, i in big], int(d_cnt.cpu()[0])
+
+    ctx = small_ctx(capi)
+    got = run(ctx, ctx)
+    ctx.close()
+    a, b = small_ctx(capi), small_ctx(capi)
+    want = run(a, b)
+    a.close()
+    b.close()
+    assert got[2] >= 8   # the small call kept a model's inliers
+    assert got[0] == want[0] and got[1] == want[1]
+
+
+@pytest.mark.gpu
 def test_gpu_argument_errors_leave_the_outputs_untouched(capi):
     import ctypes as C
     ctx = small_ctx(capi)

@@ -212,6 +212,37 @@ def test_gpu_async_equals_sync_and_rows_past_count_untouched(capi):
 
 
 @pytest.mark.gpu
+def test_gpu_growth_under_a_queued_async_call(capi):
+    """A small asynchronous call is still queued when a synchronous call of the same context needs the stage's buffer larger:
+    both give, as bytes, what the same two calls give on fresh contexts."""
+    import torch
+    w, h = 160, 96
+    img = K.texture(w, h, 3)
+
+    def run(ctx_small, ctx_large):
+        d_kp = torch.zeros((1, 64, 8), dtype=torch.int32, device="cuda")
+        d_desc = torch.zeros((1, 64, 64), dtype=torch.float32, device="cuda")
+        d_cnt = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()   # torch's fill kernels run on torch's stream, not on the context's
+        ctx_small.surf_detect_describe_batch_async([0], d_kp.data_ptr(), d_desc.data_ptr(), d_cnt.data_ptr(), cap=64)
+        kp, desc = ctx_large.surf_detect_describe_batch([0], cap=2048)[0]     # no sync in between
+        ctx_small.sync()
+        n = int(d_cnt.cpu()[0])
+        first = d_kp.cpu().numpy()[0, :n].tobytes() + d_desc.cpu().numpy()[0, :n].tobytes()
+        return n, first, kp.tobytes() + desc.tobytes()
+
+    ctxs = [make_ctx(capi, w, h) for _ in range(3)]
+    for c in ctxs:
+        c.upload_frames(0, img[None])
+    got = run(ctxs[0], ctxs[0])
+    want = run(ctxs[1], ctxs[2])
+    for c in ctxs:
+        c.close()
+    assert 0 < got[0] <= 64 and len(got[2]) > 0
+    assert got == want
+
+
+@pytest.mark.gpu
 def test_gpu_argument_errors_leave_outputs_untouched(capi):
     w, h, cap = 160, 96, 64
     ctx = make_ctx(capi, w, h)

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Instruction histogram of one kernel's main loop in uw-slam_amd/csrc/uwt_capi.gfx950.s (`make -C uw-slam_amd/csrc asm`).
+"""Instruction histogram of one kernel's main loop in uw-slam_amd/csrc/uwt_launch_residual.gfx950.s (`make -C uw-slam_amd/csrc asm`; ISA_FILE names another unit's).
 usage: isa_hist.py <mangled-name-substring> [--loop | --f64loop]   (--loop: only the largest backward-branch loop body; --f64loop: the innermost loop with the f64 sums)"""
 import collections
 import re
 import sys
 
 import os
-path = os.environ.get("ISA_FILE", "uw-slam_amd/csrc/uwt_capi.gfx950.s")
+path = os.environ.get("ISA_FILE", "uw-slam_amd/csrc/uwt_launch_residual.gfx950.s")
 key = sys.argv[1]
 lines = open(path).read().splitlines()
 start = next(i for i, l in enumerate(lines) if l.startswith("_ZN3uwt") and ":" in l and key in l.split(":")[0])

@@ -28,8 +28,10 @@ def main():
         text = open(a.remarks).read()
     else:
         text = ""
-        for unit in ("uwt_capi", "uwt_launch_residual", "uwt_launch_general", "uwt_launch_flow", "uwt_launch_points", "uwt_launch_match"):   # one object per kernel family
-            r = subprocess.run(["make", "-C", os.path.join(ROOT, "uw-slam_amd", "csrc"), "asm", "UNIT=" + unit], capture_output=True, text=True)
+        csrc = os.path.join(ROOT, "uw-slam_amd", "csrc")
+        units = re.search(r"^UNITS\s*=\s*(.+)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()
+        for unit in units:   # every translation unit of the library, as the Makefile lists them
+            r = subprocess.run(["make", "-C", csrc, "asm", "UNIT=" + unit], capture_output=True, text=True)
             text += r.stdout + r.stderr
             if r.returncode:
                 sys.stderr.write(text[-4000:])

@@ -1,0 +1,235 @@
+// uwt_ctx.h — internal: the context behind the C ABI of include/uwt.h and what the host units of the library share (uwt_capi.hip
+// and uwt_capi_*.hip): the error path, the growable device buffer, the layout carver and the helpers more than one unit calls.
+#pragma once
+
+#include "../../include/uwt.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <algorithm>
+#include <initializer_list>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "uwt_launch.h"
+
+static_assert(sizeof(uwt::StatsOut) == sizeof(uwt_stats), "uwt_stats layout");
+
+namespace uwt {
+
+// A device buffer that grows on use (its contents are not kept).  reserve: nothing when it holds `bytes` already; else `stream` is
+// drained first — work enqueued before, an asynchronous call's included, may still read the old block — then the block is freed
+// and a new one allocated.  One buffer per stage: a stage's asynchronous call is never disturbed by another stage's growth.
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  int reserve(uwt_ctx* c, hipStream_t stream, size_t want);
+  hipError_t release();   // the only hipFree of a buffer that can grow
+};
+
+// Carves one allocation into arrays: take<T>(n) is the offset of n elements of T, each array starting on the next multiple of
+// `align` behind the one before (align may be changed between two takes); total() the bytes to reserve, the last array padded
+// like the others, tight() the same without that pad; at<T>(base, offset) the array's address.
+struct Carve {
+  size_t align, end = 0;
+  explicit Carve(size_t a) : align(a) {}
+  size_t up(size_t b) const { return (b + align - 1) & ~(align - 1); }
+  template <typename T> size_t take(size_t n) {
+    const size_t at = up(end);
+    end = at + sizeof(T) * n;
+    return at;
+  }
+  size_t total() const { return up(end); }
+  size_t tight() const { return end; }
+  template <typename T> static T* at(void* base, size_t offset) { return reinterpret_cast<T*>(static_cast<unsigned char*>(base) + offset); }
+};
+
+}  // namespace uwt
+
+using namespace uwt;
+
+struct uwt_ctx {
+  uwt_params p;
+  uwt_level info[UWT_MAX_LEVELS];
+  LevelK lv[UWT_MAX_LEVELS];
+  int vecl[UWT_MAX_LEVELS];             // pixels per vector group at each level: 4 (rows are pitched to whole groups of four)
+  bool whole = true;                    // the level-0 size is divisible by 2^(n_levels-1): every level's image is its grid, every cell of
+                                        // the resize chain whole (the one-launch pyramid forms apply)
+  int slices[UWT_MAX_LEVELS];
+  int groups_per_block[UWT_MAX_LEVELS];
+  hipStream_t stream = nullptr;
+  // Side stream of uwt_track_batch_async: the gradients of the finer levels (HBM-bound) run beside the first, coarse
+  // iterations of the alignment (VALU-bound), which only read the coarsest iterated level (uwt_tuning::overlap_gradients).
+  hipStream_t side = nullptr;
+  static constexpr int kMaxParts = 4;
+  int dep_first = 0, dep_n = 0;         // slot range the running tracker call depends on (track_batch_enqueue)
+  hipStream_t part_stream[kMaxParts] = {};   // compute streams of parts 1.. of a split batch (part 0: `stream`)
+  hipEvent_t ev_fork = nullptr, ev_join[kMaxParts] = {};
+  // launch-shape switches (uwt_tuning; defaults: default_tuning()).  split: parts a fixed-schedule batch is cut into (1 = one
+  // stream); split_min: pairs per part at least; stream_bytes: a level whose planes of the whole batch exceed this is read
+  // non-temporally; split_min_px: level-0 pixels of the batch at least — below, a launch is too short for a second stream to pay
+  // (the host enqueues twice as many)
+  uwt_tuning tn;
+  hipEvent_t ev_pyramids = nullptr, ev_side_done = nullptr, ev_level[UWT_MAX_LEVELS] = {};
+  uint8_t* img[UWT_MAX_LEVELS] = {};
+  uint16_t* depth[UWT_MAX_LEVELS] = {};
+  int16_t* gx[UWT_MAX_LEVELS] = {};
+  int16_t* gy[UWT_MAX_LEVELS] = {};
+  PairState* state = nullptr;
+  int* d_ref = nullptr;
+  int* d_tgt = nullptr;
+  // pinned staging of the pair lists, a ring of kPairStages [ref(max_pairs) | tgt(max_pairs)] blocks: a new list is
+  // written to the next block while the asynchronous copy of the previous one may still be reading its own
+  static constexpr int kPairStages = 4;
+  int* h_pairs = nullptr;
+  hipEvent_t ev_pairs[kPairStages] = {};
+  int pair_stage = 0;                   // block holding the lists that are on the device
+  int n_pairs_cached = 0;
+  // Copy stream + slot-range dependencies (uwt_upload_frames_async): `busy` = compute work enqueued on `stream` that
+  // reads or writes a slot range, `fresh` = uploads enqueued on `copy` into a slot range.  An upload waits for the busy
+  // entries it overlaps, a compute call for the fresh ones; both rings are in stream order, so once an entry has been
+  // dropped the oldest survivor stands for everything before it.
+  struct SlotDep { int first = 0, n = 0; hipEvent_t ev = nullptr; bool used = false; };
+  static constexpr int kDeps = 8;
+  hipStream_t copy = nullptr;
+  SlotDep busy[kDeps], fresh[kDeps];
+  int busy_next = 0, fresh_next = 0;
+  long long ticket_seq = 0;              // compute calls noted so far; busy_seq[i] = the call ring entry i stands for
+  long long busy_seq[kDeps] = {};
+  bool busy_dropped = false, fresh_dropped = false;
+  uint32_t* partials = nullptr;
+  uint32_t* partials2 = nullptr;        // the other parity of the chained (k_iterate) flow
+  PairState* state2 = nullptr;
+  size_t partial_records = 0;
+  float* d_poses = nullptr;
+  StatsOut* d_stats = nullptr;
+  unsigned int* hist = nullptr;         // general path: [pair][2][kHistBins]
+  PairScale* scale = nullptr;           // general path: [pair]
+  int* d_active = nullptr;              // early-exit polling counters
+  unsigned int* d_tickets = nullptr;    // tail update: one counter per pair, zero between launches
+  // tn.tail_update: the update in the tail of the residual launch instead of a k_gn_update launch: 1 = where a batch runs as
+  // parts on streams of their own (the tail's ~10 us of dependent round trips and the solve run under the other part's
+  // launches: +1.2 % at 1024 pairs, +3 % with Huber weights at 256; on one stream the tail is exposed at the end of every
+  // launch and loses ~3 us per evaluation to the update launch), 0 = never, 2 = always.  tn.target_blocks: blocks per residual
+  // launch the batch-dependent slicing aims at; 0: 1024 for a batch that runs as two halves (one block per slot of the chip),
+  // else 4096
+  int* h_active = nullptr;              // pinned
+  DevBuf scratch;                       // per-stage entry points
+  // the live call for a batch of pairs (uwt_track_features_batch_async, uwt_obtain_patch_points_batch), allocated on first use:
+  // max_pairs tables of kPatchMaxKeypoints x kPatchMaxRows rows and their counts, the key points as the device reads them, the
+  // evaluation's records (kFeatMaxSlices per pair), and a pinned staging ring for the caller's key points (as h_pairs)
+  float4* feat_tab = nullptr;
+  int* feat_cnt = nullptr;
+  float2* feat_kp = nullptr;
+  int* feat_nkp = nullptr;
+  uint32_t* feat_recs = nullptr;
+  float* h_feat = nullptr;              // kPairStages blocks of [n (max_pairs ints) | key points (max_pairs x 400 floats)]
+  hipEvent_t ev_feat[kPairStages] = {};
+  int feat_stage = 0;
+  // semi-dense tracking for a batch of pairs (uwt_track_candidates_batch_async), each buffer grown on use to what a call needs:
+  // every iterated level's tables (gw x gh rows per pair and level) and counts (UWT_MAX_LEVELS x pairs), the producer's work
+  // area for its finest level, and the evaluations' records (the largest level's slice bound per pair)
+  DevBuf cand_tab, cand_cnt, cand_work, cand_recs;
+  // descriptor matching (uwt_knn_match_batch, uwt_match_descriptors_batch*), each buffer grown on use to what a call needs: both
+  // descriptor sets of every pair, their counts (query | train), the 2-NN parts of both directions, and the synchronous calls' results
+  DevBuf match_desc, match_cnt, match_part, match_out;
+  // RANSAC inlier selection (uwt_ransac_inliers_batch*): the staged key points of both frames, their counts, the (x, y, x', y')
+  // table of every match and, for the synchronous call, its inputs and results — grown on use; and need(k) of the contract for
+  // every N in 8..UWT_MATCH_MAX_ROWS, k in 8..N (allocated whole on first use, 33 MB; a row is filled the first time a call can
+  // meet its N under the parameters the rows were computed for)
+  DevBuf ransac_buf;
+  int* ransac_need = nullptr;
+  std::vector<int> ransac_need_host;
+  std::vector<unsigned char> ransac_row_done;
+  double ransac_need_confidence = 0.0;
+  int ransac_need_hypotheses = 0;
+  // SURF detection and description (uwt_surf_*): per chunk of frames the slot list, the counts, the integral images, the raw
+  // candidates with their order keys, and the key points and descriptors before they go to the caller — grown on use
+  DevBuf surf_buf;
+  DevBuf stage[2];                      // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
+  bool profiling = false;
+  int spec_budget = 0;                  // speculative launching: evaluations a level gets (0: first_poll + 1); doubled when an alignment
+                                        // was cut short, halved again after kSpecCalm calls in a row that were not
+  int spec_calm = 0;
+  static constexpr int kSpecCalm = 64;
+  // the synchronous small-batch call: results and the cut-short flag are written by the last kernel straight into this
+  // page-locked block (no device-to-host copies)
+  static constexpr int kSmallBatch = 8;
+  struct SmallResults { float poses[kSmallBatch * 7]; StatsOut stats[kSmallBatch]; int cut; };
+  SmallResults* h_small = nullptr;      // pinned, device-visible
+  SmallResults* d_small = nullptr;      // its device address
+  bool deferred = false;                // uwt_set_deferred: stage calls return once enqueued
+  unsigned poll_seq = 0;                // batch path: read-backs alternate between two counters / events (taken one evaluation late)
+  hipEvent_t ev_poll[2] = {};
+  const uint32_t* prof_records = nullptr;
+  bool compute_only = false;            // uwt_profile_enable(ctx, 2): residual launches run their no-memory diagnostic twin
+  std::vector<hipEvent_t> ev_pool;      // start/stop pairs
+  size_t ev_used = 0;
+  double prof_ms = 0.0;
+  long long prof_launches = 0, prof_pixels = 0;
+  double prof_level_ms[UWT_MAX_LEVELS] = {};        // the same durations by pyramid level (uwt_profile_read_levels)
+  long long prof_level_launches[UWT_MAX_LEVELS] = {};
+  std::vector<int> prof_ev_level, prof_ev_evals;                      // level of the launch each event pair brackets
+  int prof_slices = 0, prof_pairs = 0;   // slicing of the last profiled residual launch (uwt_profile_clock)
+  std::string last_error;
+};
+
+namespace uwt {
+
+inline int fail(uwt_ctx* c, int code, const std::string& msg) {
+  if (c) c->last_error = msg;
+  return code;
+}
+
+#define HIPCHK(ctx, expr)                                                                                   \
+  do {                                                                                                      \
+    hipError_t e_ = (expr);                                                                                 \
+    if (e_ != hipSuccess)                                                                                   \
+      return fail(ctx, UWT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                     \
+  } while (0)
+
+// ---- helpers of uwt_capi.hip that the other host units call (described at their definitions) ------------------------------
+inline bool slot_range_ok(const uwt_ctx* c, int first, int n) { return first >= 0 && n >= 0 && (long long)first + n <= c->p.max_frames; }
+template <typename T>
+int launch_resize(uwt_ctx* c, const T* src, T* dst, int sw, int sh, int src_pitch, int dw, int dh, int dst_pitch, size_t sfs,
+                  size_t dfs, int n_frames, const int* d_slots = nullptr, int first_slot = 0);   // T: uint8_t, uint16_t
+int launch_scharr(uwt_ctx* c, const uint8_t* src, int16_t* gx, int16_t* gy, int w, int h, int pitch, size_t fs, int n_frames,
+                  const int* d_slots = nullptr, int first_slot = 0, hipStream_t on = nullptr);
+LaunchSel launch_sel(const uwt_ctx* c);
+int launch_residual(uwt_ctx* c, hipStream_t s, const ResidualArgs& a, int n_pairs, bool dump);
+int launch_general(uwt_ctx* c, hipStream_t s, const ResidualArgs& ra, int n_pairs, bool dump);
+ResidualArgs residual_args(uwt_ctx* c, int lvl);
+UpdateArgs update_args(uwt_ctx* c, int lvl);
+void arm_tail(uwt_ctx* c, ResidualArgs& ra, const UpdateArgs& ua);
+int poll_arm(uwt_ctx* c);
+int poll_any_left(uwt_ctx* c, bool* left);
+int dep_wait(uwt_ctx* c, const uwt_ctx::SlotDep* ring, int next, bool dropped, hipStream_t waiter, int first, int n);
+int compute_begin(uwt_ctx* c, int first, int n);
+int compute_end(uwt_ctx* c, int first, int n);
+int compute_begin_pairs(uwt_ctx* c, int n, const int32_t* slots_a, const int32_t* slots_b);
+int upload_pairs(uwt_ctx* c, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots);
+int read_back_pairs(uwt_ctx* c, const char* what, int n, float* poses_out, uwt_stats* stats_out);
+struct RowSet { const void* d_rows; size_t elem_bytes; const int32_t* counts; void* host_out; };   // (d_rows null: nothing to deliver)
+int rows_to_host(uwt_ctx* c, int cap, int n_items, std::initializer_list<RowSet> sets);
+int counted_rows_to_host(uwt_ctx* c, const float4* d_rows, size_t stride, const int* d_counts, int n_items, int cap, float* pts_out,
+                         int32_t* counts_out);
+
+// The early-exit look of the batch paths, taken one evaluation late (enqueue_estimate has the schedule and the reasons): the
+// launch of an evaluation that is due counts the pairs still on the level into one of two device counters; behind it the count
+// is copied to page-locked memory, and the host waits for that copy only once the next evaluation has been enqueued.
+struct LatePoll {
+  int next, pending = -1;   // evaluations before the next look; slot of the look not yet taken
+  bool due = false;
+  explicit LatePoll(int first_poll) : next(first_poll) {}
+  // ahead of evaluation k's launch: the counter its update adds to, cleared on s (null: no look at this evaluation)
+  int arm(uwt_ctx* c, hipStream_t s, bool polls, int k, int max_iters, int** active);
+  // behind it: the look at the evaluation before (*none_left: every pair has left the level; nothing more is queued then), then
+  // this evaluation's read-back on s
+  int look(uwt_ctx* c, hipStream_t s, bool* none_left);
+};
+
+}  // namespace uwt

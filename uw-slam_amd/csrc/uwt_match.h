@@ -1,6 +1,6 @@
 // uwt_match.h — internal: the records, limits and launchers of descriptor matching (uwt_knn_match_batch,
 // uwt_match_descriptors_batch*; include/uwt.h).  The kernels are in uwt_match_kernels.h, their only launches in
-// uwt_launch_match.hip; uwt_capi.hip sees this header alone.
+// uwt_launch_match.hip; uwt_capi_match.hip sees this header alone.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // uwt_ransac.h — internal: the records, limits and launchers of the RANSAC inlier selection (uwt_ransac_inliers_batch*;
 // include/uwt.h states the contract).  The kernels are in uwt_ransac_kernels.h, their only launches in uwt_launch_ransac.hip;
-// uwt_capi.hip sees this header alone.
+// uwt_capi_match.hip sees this header alone.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // uwt_surf.h — internal: the records, limits and launchers of SURF detection and description (uwt_surf_*; include/uwt.h states
-// the contract).  The kernels are in uwt_surf_kernels.h, their only launches in uwt_launch_surf.hip; uwt_capi.hip sees this header
+// the contract).  The kernels are in uwt_surf_kernels.h, their only launches in uwt_launch_surf.hip; uwt_capi_surf.hip sees this header
 // alone.
 #pragma once
 
