@@ -386,6 +386,15 @@ class Tracker {
     if (st == UWT_OK) last_stats_ = last_batch_stats_.back();
     check(st, "uwt_estimate_pose_candidates_batch");
   }
+  // System::Tracking() (src/System.cpp:193-223) for a list of (previous, current) pairs through the device-resident call
+  // (uwt_tracking_batch): SURF, the matcher, ransacTest, getGoodKeypoints and the live alignment run as one chain on the device,
+  // and keypoints_, surf_keypoints_, n_matches_ of both frames and previous->rigid_transformation_ end up exactly as the loop
+  // { ApplyGradient; DetectAndTrackFeatures(previous, current, n_matches_ >= 110); ObtainPatchesPoints; EstimatePoseFeatures } over
+  // the same list leaves them.  Pairs that share no frame go into one call; a pair that names a frame an earlier pair of the list
+  // has written (the next pair of a sequence) waits for that pair's results, as it does in the loop.  A pair without a good match
+  // has UWT_ERR_NO_VALID_POINTS in its stats and leaves its frames' lists empty; that does not throw.  Per-pair stats in
+  // last_batch_stats().  (Defined behind RobustMatcher, whose parameters it reads.)
+  void TrackingBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, RobustMatcher& _robust_matcher, int32_t cap = 2048);
   const std::vector<uwt_stats>& last_batch_stats() const { return last_batch_stats_; }
   // EstimatePose over the sparse tables a producer left in previous->candidatePoints_[lvl] (src/Tracker.cpp:401)
   void EstimatePoseOverCandidatePoints(Frame* _previous_frame, Frame* _current_frame) {
@@ -672,6 +681,80 @@ class RobustMatcher {
   }
   Tracker* tracker_;
 };
+
+inline void Tracker::TrackingBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, RobustMatcher& rm, int32_t cap) {
+  uwt_tracking_params tp;
+  uwt_default_tracking_params(&tp);
+  tp.surf.hessian_threshold = rm.hessian_threshold_;
+  tp.surf.n_octaves = rm.n_octaves_;
+  tp.surf.n_octave_layers = rm.n_octave_layers_;
+  tp.surf.upright = rm.upright_ ? 1 : 0;
+  tp.ransac.distance = rm.distance_;
+  tp.ransac.confidence = rm.confidence_;
+  tp.ransac.max_hypotheses = rm.max_hypotheses_;
+  tp.ransac.seed = rm.seed_;
+  tp.ratio = rm.ratio_;
+  tp.min_matches = 110;   // src/System.cpp:208
+  if (cap < 1) throw std::invalid_argument("TrackingBatch: cap < 1");
+  std::vector<uwt_stats> all;
+  for (size_t i = 0; i < _pairs.size();) {
+    // the run of pairs from i on that share no frame
+    std::vector<std::pair<Frame*, Frame*>> run;
+    std::vector<const Frame*> seen;
+    auto written = [&](const Frame* f) { return std::find(seen.begin(), seen.end(), f) != seen.end(); };
+    while (i < _pairs.size() && (int)run.size() < params_.max_pairs && !written(_pairs[i].first) && !written(_pairs[i].second) &&
+           _pairs[i].first != _pairs[i].second) {
+      run.push_back(_pairs[i]);
+      seen.push_back(_pairs[i].first);
+      seen.push_back(_pairs[i].second);
+      i++;
+    }
+    if (run.empty()) throw std::invalid_argument("TrackingBatch: a pair of one frame with itself");
+    const size_t n = run.size();
+    for (const auto& pr : run) {
+      if (!pr.first->obtained_gradients_ || !bound(pr.first)) ApplyGradient(pr.first);
+      ApplyGradient(pr.second);
+    }
+    std::vector<int32_t> a(n), b(n), n_prev(n);
+    std::vector<uwt_keypoint> prev(n * (size_t)cap);
+    for (size_t k = 0; k < n; k++) {
+      a[k] = bind(run[k].first);
+      b[k] = bind(run[k].second);
+    }
+    for (size_t k = 0; k < n; k++) {   // binding a later pair's frame may have taken an earlier frame's slot
+      Frame* f = run[k].first;
+      if (!bound(f) || !bound(run[k].second) || !f->obtained_gradients_ || !run[k].second->obtained_gradients_)
+        throw std::runtime_error("TrackingBatch: more frames than slots (max_frames)");
+      const size_t m = f->surf_keypoints_.size();
+      n_prev[k] = (int32_t)m;
+      std::copy(f->surf_keypoints_.begin(), f->surf_keypoints_.begin() + (m < (size_t)cap ? m : (size_t)cap), prev.begin() + k * (size_t)cap);
+    }
+    std::vector<float> poses(n * 7);
+    std::vector<uwt_stats> stats(n, uwt_stats{});
+    std::vector<uwt_tracking_info> info(n);
+    std::vector<uwt_match> good(n * (size_t)cap);
+    std::vector<uwt_keypoint> kept_prev(n * (size_t)cap), kept_cur(n * (size_t)cap);
+    const int st = uwt_tracking_batch(ctx(), (int32_t)n, a.data(), b.data(), &tp, cap, prev.data(), n_prev.data(), poses.data(), stats.data(),
+                                      info.data(), good.data(), kept_prev.data(), kept_cur.data());
+    if (st != UWT_OK && st != UWT_ERR_PAIR_FAILED) check(st, "uwt_tracking_batch");
+    for (size_t k = 0; k < n; k++) {
+      Frame* p = run[k].first;
+      Frame* c = run[k].second;
+      const size_t m = (size_t)info[k].n_matches;
+      p->n_matches_ = c->n_matches_ = (int)m;
+      p->surf_keypoints_.assign(kept_prev.begin() + k * (size_t)cap, kept_prev.begin() + k * (size_t)cap + m);
+      c->surf_keypoints_.assign(kept_cur.begin() + k * (size_t)cap, kept_cur.begin() + k * (size_t)cap + m);
+      p->keypoints_.clear();
+      c->keypoints_.clear();
+      for (const uwt_keypoint& q : p->surf_keypoints_) p->keypoints_.insert(p->keypoints_.end(), {q.x, q.y});
+      for (const uwt_keypoint& q : c->surf_keypoints_) c->keypoints_.insert(c->keypoints_.end(), {q.x, q.y});
+      std::copy(poses.begin() + 7 * k, poses.begin() + 7 * (k + 1), p->rigid_transformation_.data());
+    }
+    all.insert(all.end(), stats.begin(), stats.end());
+  }
+  last_batch_stats_ = all;
+  if (!all.empty()) last_stats_ = all.back();
+}
 
 // Four packed floats in place of __m128 where SSE is absent (LS::updateSSE's operands, include/LeastSquares.h:42).
 struct f4 {

@@ -692,6 +692,92 @@ int uwt_surf_integral(uwt_ctx* ctx, int32_t slot, uint32_t* out);
  * memory, NaN where no response exists. */
 int uwt_surf_response_layer(uwt_ctx* ctx, int32_t slot, int32_t octave, int32_t layer, double* out, int32_t* gw, int32_t* gh);
 
+/* ---- System::Tracking for a batch of pairs in one device-resident call ---------------------------------------------------------- */
+
+/* The five calls of System::Tracking() (src/System.cpp:193-223) for n_pairs pairs, chained on the device: nothing travels to the
+ * host between the stages and the asynchronous form never waits for the device.  previous = ref_slots[p], current = tgt_slots[p];
+ * the frames must be in the state uwt_track_features_batch_async expects (resident, pyramids built, gradients applied), and
+ * 1 <= n_pairs <= max_pairs as there.  cap: rows of every per-pair list (1..UWT_MATCH_MAX_ROWS).  Per pair p:
+ *   1. use = d_prev_kp != null && d_n_prev[p] >= 1 && d_n_prev[p] >= min_matches: `usekeypoints` of src/System.cpp:195-209 together
+ *      with the mirrors' "and it has some" (a frame's n_matches_ is the number of key points it kept, so the device count decides).
+ *   2. The query set Q: use ? what uwt_surf_describe_batch gives at the provided records (src/Tracker.cpp:192-195) : what
+ *      uwt_surf_detect_describe_batch gives on the previous frame with capacity cap.  The train set T: detection on the current
+ *      frame with capacity cap.  A per-frame predicate on the device picks the path: the blocks of the other path return at once.
+ *   3. symMatches = uwt_match_descriptors_batch(UWT_NORM_L2, 64, Q, T, cap, ratio).
+ *   4. goodMatches and uwt_ransac_info = uwt_ransac_inliers_batch on symMatches and the (x, y) of Q and T under params.ransac.
+ *   5. kept_prev[i] = Q.kp[good[i].query_idx], kept_cur[i] = T.kp[good[i].train_idx]: getGoodKeypoints (src/Tracker.cpp:260-270) on
+ *      whole uwt_keypoint records.
+ *   6. Pose and uwt_stats = uwt_estimate_pose_features_batch for (previous, current) with the (x, y) of the first
+ *      min(n_matches, 200) rows of kept_prev.  No good match: UWT_ERR_NO_VALID_POINTS in that pair's stats, as there; the other
+ *      pairs are unaffected.
+ * The contract: every output of pair p is bit for bit what that staged sequence of entry points gives on the same context — no new
+ * arithmetic contract.  A pair's outputs depend neither on the batch it is in, nor on its place there, nor on uwt_tuning, nor on
+ * scheduling.
+ * Hand-over: d_kept_cur / d_n_matches of one call are valid d_prev_kp / d_n_prev of the next call on the same context with the same
+ * cap; the stream orders the calls, no uwt_sync between them.  The inputs and outputs of ONE call must not overlap (the caller keeps
+ * two sets of buffers): d_prev_kp equal to d_kept_prev or d_kept_cur, or d_n_prev equal to d_n_matches, is UWT_ERR_INVALID_ARG.
+ * The asynchronous call performs no device-to-host copy; the only host waits are those for a block of a pinned staging ring (the
+ * pair lists), as in uwt_track_features_batch_async.
+ * UWT_ERR_INVALID_ARG with nothing enqueued and the outputs untouched: a null list or a null required output, n_pairs outside
+ * 1..max_pairs, a slot out of range, cap < 1, a SURF or RANSAC parameter outside the range its stage states, a non-finite ratio,
+ * min_matches < 0, exactly one of d_prev_kp / d_n_prev null.  UWT_ERR_CAPACITY likewise: cap > UWT_MATCH_MAX_ROWS.
+ * What only the device can see — a provided count outside 0..cap; a used provided record that is not finite or outside |x|, |y| <=
+ * 1e6, 0 < size <= 4096; one of the first 200 kept (x, y) outside level 0 — puts UWT_ERR_INVALID_ARG into that pair's info.status
+ * and uwt_stats; its n_matches is 0 and its pose the identity, as a failed pair's is.  (A pair refused for its provided list runs
+ * neither path on its previous frame: n_kp_prev = n_symmetric = 0, best_hypothesis = -1.)  Every other pair is unaffected, nothing
+ * faults, and uwt_tracking_batch returns UWT_ERR_PAIR_FAILED.
+ * Scratch (the key points, descriptors and counts of both sides of every pair, symMatches, the RANSAC records) belongs to the
+ * context, grows on demand — also under a queued asynchronous call, which is drained first — and is freed by uwt_destroy. */
+typedef struct uwt_tracking_params {
+  uwt_surf_params   surf;         /* uwt_default_surf_params                                         */
+  uwt_ransac_params ransac;       /* uwt_default_ransac_params                                       */
+  float             ratio;        /* ratio_, 0.65f (include/Tracker.h:80); finite                    */
+  int32_t           min_matches;  /* 110 (src/System.cpp:208); >= 0                                  */
+} uwt_tracking_params;            /* 56 bytes */
+
+typedef struct uwt_tracking_info {   /* per pair, 32 bytes */
+  int32_t status;                    /* uwt_status_code of the front end of this pair */
+  int32_t used_provided;             /* 1: the previous frame was described at the provided key points */
+  int32_t n_kp_prev, n_kp_cur;       /* rows of the query / train set */
+  int32_t n_symmetric;               /* symMatches.size() */
+  int32_t n_matches;                 /* goodMatches.size() = Frame::n_matches_ of both frames */
+  int32_t best_hypothesis, hypotheses_run;   /* of uwt_ransac_info */
+} uwt_tracking_info;
+
+typedef struct uwt_tracking_io {     /* every pointer is DEVICE memory */
+  const uwt_keypoint* d_prev_kp;     /* in, may be null: n_pairs x cap, what the previous frame kept */
+  const int32_t*      d_n_prev;      /* in, null iff d_prev_kp is: n_pairs counts */
+  float*              d_poses;       /* out: n_pairs x 7 */
+  uwt_stats*          d_stats;       /* out, may be null */
+  uwt_tracking_info*  d_info;        /* out: n_pairs */
+  uwt_match*          d_good;        /* out: n_pairs x cap, goodMatches */
+  uwt_keypoint*       d_kept_prev;   /* out: n_pairs x cap, previous->surf_keypoints_ after the call */
+  uwt_keypoint*       d_kept_cur;    /* out: n_pairs x cap, current->surf_keypoints_ after the call */
+  int32_t*            d_n_matches;   /* out: n_pairs (= info.n_matches; the count of both kept lists) */
+} uwt_tracking_io;
+
+/* {uwt_default_surf_params, uwt_default_ransac_params, 0.65f, 110} */
+int uwt_default_tracking_params(uwt_tracking_params* p);
+/* Enqueued on the context's stream, ordered against uwt_upload_frames_async as uwt_track_features_batch_async is; uwt_sync() to
+ * wait.  The rows past a pair's count in d_good / d_kept_prev / d_kept_cur are not written. */
+int uwt_tracking_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                             const uwt_tracking_params* params_or_null, int32_t cap, const uwt_tracking_io* io);
+/* The same, synchronous, HOST in and out (prev_kp_or_null: n_pairs x cap, n_prev_or_null: n_pairs, both or neither); the rows past
+ * a count are not written.  UWT_ERR_PAIR_FAILED when a pair failed, its status in its uwt_stats (and, for the front end, its info). */
+int uwt_tracking_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                       const uwt_tracking_params* params_or_null, int32_t cap,
+                       const uwt_keypoint* prev_kp_or_null, const int32_t* n_prev_or_null,
+                       float* poses_out, uwt_stats* stats_out_or_null, uwt_tracking_info* info_out, uwt_match* good_out,
+                       uwt_keypoint* kept_prev_out, uwt_keypoint* kept_cur_out);
+/* uwt_match_descriptors_batch_async with both descriptor sets and their counts already in DEVICE memory (d_query / d_train: n_pairs x
+ * cap x dim elements, d_n_query / d_n_train: n_pairs), read in place: nothing is uploaded.  The launch is bounded by cap instead of
+ * the counts (blocks past a pair's counts return at once; the merge of the train parts is exact, so the different cut shows in no
+ * bit): the results are those of uwt_match_descriptors_batch.  A device count outside 0..cap is taken as 0: that pair has count 0.
+ * Host-side errors as there (the counts cannot be checked on the host). */
+int uwt_match_descriptors_device_async(uwt_ctx* ctx, int32_t n_pairs, int32_t norm, int32_t dim, const void* d_query,
+                                       const int32_t* d_n_query, const void* d_train, const int32_t* d_n_train, int32_t cap, float ratio,
+                                       uwt_match* d_matches_out, int32_t* d_counts_out);
+
 /* ---- next to the path: frame ingest---------------------------------------------------------------- */
 
 typedef struct uwt_ingest uwt_ingest;

@@ -45,6 +45,42 @@ def track_live(w, h, intr, frames, depths, arith=0):
     return np.array(poses, np.float32).reshape(-1, 7), stats, kept
 
 
+def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048):
+    """The same loop as successive one-pair uwt_tracking_batch_async calls: what a frame kept goes to the next call in device memory
+    (two sets of buffers, taken in turn), nothing is read back between the calls and the host waits once, at the end.  Same returns."""
+    import torch
+    capi = importlib.import_module("uw-slam_amd.capi")
+    n = len(frames)
+    ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=4, max_pairs=1, has_depth=int(bool(depths)), arith=arith))
+    ctx.set_deferred(True)   # pyramids and gradients are enqueued only
+    i32 = dict(dtype=torch.int32, device="cuda")
+    poses, stats, info = torch.zeros((n - 1, 7), **i32), torch.zeros((n - 1, 4), **i32), torch.zeros((n - 1, 8), **i32)
+    sets = [dict(good=torch.zeros((cap, 3), **i32), kept_prev=torch.zeros((cap, 8), **i32), kept_cur=torch.zeros((cap, 8), **i32),
+                 n_matches=torch.zeros((1,), **i32)) for _ in range(2)]
+    torch.cuda.synchronize()   # torch's fills run on torch's stream
+
+    def load(i):
+        ctx.set_frame(i % 4, frames[i], depths[i] if depths else None)
+        ctx.build_pyramids(i % 4, 1)
+        ctx.apply_gradient(i % 4, 1)
+
+    load(0)
+    for k in range(n - 1):
+        load(k + 1)
+        io = {key: t.data_ptr() for key, t in sets[k % 2].items()}
+        io.update(poses=poses[k].data_ptr(), stats=stats[k].data_ptr(), info=info[k].data_ptr())
+        if k:
+            io.update(prev_kp=sets[(k - 1) % 2]["kept_cur"].data_ptr(), n_prev=sets[(k - 1) % 2]["n_matches"].data_ptr())
+        ctx.tracking_batch_async([k % 4], [(k + 1) % 4], io, cap=cap)
+    ctx.sync()
+    st = stats.cpu().numpy().view(capi.STATS).reshape(-1)
+    kept = info.cpu().numpy().view(capi.TRACKING_INFO).reshape(-1)["n_matches"]
+    out = poses.cpu().numpy().view(np.float32).reshape(-1, 7).copy()
+    ctx.close()
+    return out, [dict(status=int(s["status"]), iterations=int(s["iterations"]), n_valid=int(s["n_valid"]), error=float(s["error"])) for s in st], \
+        [int(v) for v in kept]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", required=True)
@@ -63,6 +99,8 @@ def main():
     ap.add_argument("--groundtruth"); ap.add_argument("--euroc", action="store_true"); ap.add_argument("--tum", action="store_true")
     ap.add_argument("--live", action="store_true", help="the reference's live loop, System::Tracking (src/System.cpp:193-223): SURF key "
                     "points detected, described, matched and RANSAC-filtered on the device, then EstimatePoseFeatures on their patches")
+    ap.add_argument("--chained", action="store_true", help="with --live: the loop as successive device-resident calls (uwt_tracking_batch_async) "
+                    "that hand their key points on in device memory, one wait at the end; the same trajectory")
     ap.add_argument("--out", default="trajectory")
     a = ap.parse_args()
     S = importlib.import_module("uw-slam_amd.sequence")
@@ -96,7 +134,7 @@ def main():
     trk = S.SequenceTracker(a.width, a.height, fx, fy, cx - x0, cy - y0, depth=bool(depths), **over)
     t0 = time.perf_counter()
     if a.live:
-        poses, stats, n_matches = track_live(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"])
+        poses, stats, n_matches = (track_live_chained if a.chained else track_live)(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"])
     else:
         poses, stats = trk.track(frames, depths)
     dt = time.perf_counter() - t0

@@ -24,6 +24,9 @@ RANSAC_INFO = np.dtype([("status", "<i4"), ("n_inliers", "<i4"), ("best_hypothes
 UWT_MATCH_MAX_ROWS = 4096   # descriptors / key points per set at most (include/uwt.h)
 KEYPOINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("response", "<f4"), ("dir_x", "<f4"), ("dir_y", "<f4"),
                      ("octave", "<i4"), ("laplacian", "<i4")])                                  # uwt_keypoint
+STATS = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("n_valid", "<i4"), ("error", "<f4")])   # uwt_stats
+TRACKING_INFO = np.dtype([("status", "<i4"), ("used_provided", "<i4"), ("n_kp_prev", "<i4"), ("n_kp_cur", "<i4"), ("n_symmetric", "<i4"),
+                          ("n_matches", "<i4"), ("best_hypothesis", "<i4"), ("hypotheses_run", "<i4")])   # uwt_tracking_info
 
 
 class Params(C.Structure):
@@ -58,6 +61,18 @@ class RansacParams(C.Structure):
 class SurfParams(C.Structure):
     """uwt_surf_params: SURF_CUDA's hessianThreshold, nOctaves, nOctaveLayers, upright"""
     _fields_ = [("hessian_threshold", C.c_double), ("n_octaves", C.c_int32), ("n_octave_layers", C.c_int32), ("upright", C.c_int32)]
+
+
+class TrackingParams(C.Structure):
+    """uwt_tracking_params: the SURF and RANSAC parameters, ratio_ and the `n_matches_ < 110` rule of System::Tracking"""
+    _fields_ = [("surf", SurfParams), ("ransac", RansacParams), ("ratio", C.c_float), ("min_matches", C.c_int32)]
+
+
+class TrackingIO(C.Structure):
+    """uwt_tracking_io: device pointers of one uwt_tracking_batch_async call"""
+    _fields_ = [("d_prev_kp", C.c_void_p), ("d_n_prev", C.c_void_p), ("d_poses", C.c_void_p), ("d_stats", C.c_void_p),
+                ("d_info", C.c_void_p), ("d_good", C.c_void_p), ("d_kept_prev", C.c_void_p), ("d_kept_cur", C.c_void_p),
+                ("d_n_matches", C.c_void_p)]
 
 
 class Level(C.Structure):
@@ -95,6 +110,7 @@ SYMBOLS = [
     "uwt_track_candidates_batch_async", "uwt_estimate_pose_candidates_batch",
     "uwt_default_surf_params", "uwt_keypoint_angle_deg", "uwt_surf_detect_describe_batch", "uwt_surf_detect_describe_batch_async",
     "uwt_surf_describe_batch", "uwt_surf_integral", "uwt_surf_response_layer",
+    "uwt_default_tracking_params", "uwt_tracking_batch_async", "uwt_tracking_batch", "uwt_match_descriptors_device_async",
 ]
 
 _lib = None
@@ -191,6 +207,21 @@ def default_surf_params(**over):
         if not hasattr(p, k):
             raise AttributeError(k)
         setattr(p, k, v)
+    return p
+
+
+def default_tracking_params(surf=None, ransac=None, **over):
+    """uwt_default_tracking_params: the SURF and RANSAC defaults, ratio 0.65, min_matches 110.  surf / ransac: dicts of fields of the
+    nested records to change; the other keywords are fields of the record itself."""
+    p = TrackingParams()
+    st = lib().uwt_default_tracking_params(C.byref(p))
+    if st:
+        raise UwtError(st, "uwt_default_tracking_params")
+    for rec, d in ((p.surf, surf or {}), (p.ransac, ransac or {}), (p, over)):
+        for k, v in d.items():
+            if not hasattr(rec, k):
+                raise AttributeError(k)
+            setattr(rec, k, v)
     return p
 
 
@@ -816,6 +847,58 @@ class Context:
                                                 C.c_void_p(kp.ctypes.data), _p(n, C.c_int32), cap, C.c_void_p(out.ctypes.data),
                                                 C.c_void_p(desc.ctypes.data)))
         return [(out[i, :n[i]].copy(), desc[i, :n[i]].copy()) for i in range(F)]
+
+    def tracking_batch(self, ref_slots, tgt_slots, prev=None, params=None, cap=2048, out=None, raise_on_pair_failure=False):
+        """System::Tracking for many pairs in one device-resident call (uwt_tracking_batch), host in and out.  prev: None, or one
+        KEYPOINT array per pair (what the previous frame kept; an empty one for a pair that has none), or the packed form
+        (kp [P, cap] KEYPOINT, n [P] int32).  out: (poses [P, 7] float32, stats [P] STATS, info [P] TRACKING_INFO, good [P, cap]
+        MATCH, kept_prev [P, cap] KEYPOINT, kept_cur [P, cap] KEYPOINT) to be written in place — the rows past a pair's count stay
+        as they are.  Returns a dict: status (OK or ERR_PAIR_FAILED), poses, stats, info, and per pair good, kept_prev, kept_cur."""
+        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
+        P = ref.size
+        kp = n = None
+        if isinstance(prev, tuple):
+            kp, n = np.ascontiguousarray(prev[0], KEYPOINT), np.ascontiguousarray(prev[1], np.int32)
+        elif prev is not None:
+            kin = [np.ascontiguousarray(k, KEYPOINT).reshape(-1) for k in prev]
+            kp, n = np.zeros((P, max(cap, 1)), KEYPOINT), np.zeros(P, np.int32)
+            for i, k in enumerate(kin):
+                kp[i, :len(k)], n[i] = k[:cap], len(k)
+        if out is None:
+            c = max(cap, 1)
+            out = (np.zeros((max(P, 1), 7), np.float32), np.zeros(max(P, 1), STATS), np.zeros(max(P, 1), TRACKING_INFO),
+                   np.zeros((max(P, 1), c), MATCH), np.zeros((max(P, 1), c), KEYPOINT), np.zeros((max(P, 1), c), KEYPOINT))
+        poses, stats, info, good, kept_prev, kept_cur = out
+        st = lib().uwt_tracking_batch(self._h, P, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.byref(params) if params is not None else None,
+                                      cap, C.c_void_p(kp.ctypes.data) if kp is not None else None,
+                                      _p(n, C.c_int32) if n is not None else None, _p(poses, C.c_float), C.c_void_p(stats.ctypes.data),
+                                      C.c_void_p(info.ctypes.data), C.c_void_p(good.ctypes.data), C.c_void_p(kept_prev.ctypes.data),
+                                      C.c_void_p(kept_cur.ctypes.data))
+        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+        cnt = info["n_matches"]
+        return dict(status=st, poses=poses[:P], stats=stats[:P], info=info[:P], good=[good[i, :cnt[i]].copy() for i in range(P)],
+                    kept_prev=[kept_prev[i, :cnt[i]].copy() for i in range(P)], kept_cur=[kept_cur[i, :cnt[i]].copy() for i in range(P)])
+
+    def tracking_batch_async(self, ref_slots, tgt_slots, io, params=None, cap=2048):
+        """The same enqueued on the context stream with every input and result in device memory (uwt_tracking_batch_async).  io: a
+        dict of device addresses — poses (P x 7 float32), info (P TRACKING_INFO), good (P x cap MATCH), kept_prev, kept_cur (P x cap
+        KEYPOINT), n_matches (P int32), optionally stats (P STATS) and prev_kp / n_prev (P x cap KEYPOINT, P int32: kept_cur /
+        n_matches of the call before, of ANOTHER set of buffers).  Never waits for the device; sync() to wait."""
+        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
+        rec = TrackingIO(*[io.get(k) or None for k in ("prev_kp", "n_prev", "poses", "stats", "info", "good", "kept_prev", "kept_cur",
+                                                        "n_matches")])
+        self._chk(lib().uwt_tracking_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
+                                                 C.byref(params) if params is not None else None, cap, C.byref(rec)))
+
+    def match_descriptors_device_async(self, n_pairs, dim, cap, d_query_ptr, d_n_query_ptr, d_train_ptr, d_n_train_ptr, d_matches_ptr,
+                                       d_counts_ptr, ratio=0.65, norm=NORM_L2):
+        """match_descriptors_batch_async with both descriptor sets (P x cap x dim) and their counts (P int32) already in device
+        memory, read in place (uwt_match_descriptors_device_async); a device count outside 0..cap is taken as 0.  sync() to wait."""
+        self._chk(lib().uwt_match_descriptors_device_async(self._h, n_pairs, norm, dim, C.c_void_p(d_query_ptr), C.c_void_p(d_n_query_ptr),
+                                                           C.c_void_p(d_train_ptr), C.c_void_p(d_n_train_ptr), cap, C.c_float(ratio),
+                                                           C.c_void_p(d_matches_ptr), C.c_void_p(d_counts_ptr)))
 
     def surf_integral(self, slot):
         """The integral image of a slot's level-0 plane (uwt_surf_integral): (h + 1) x (w + 1) uint32"""

@@ -599,6 +599,11 @@ int dep_note(uwt_ctx* c, uwt_ctx::SlotDep* ring, int& next, bool& dropped, hipSt
   return UWT_OK;
 }
 
+}  // namespace
+
+// ---- what the other host units call too (declared in uwt_ctx.h) -----------------------------------------------------------
+namespace uwt {
+
 // UWT_ERR_PAIR_FAILED, naming the first failing pair's status, when any of a batch call's n pairs failed
 int first_failure(uwt_ctx* c, const char* what, const uwt_stats* stats, int n) {
   for (int i = 0; i < n; i++)
@@ -608,10 +613,6 @@ int first_failure(uwt_ctx* c, const char* what, const uwt_stats* stats, int n) {
   return UWT_OK;
 }
 
-}  // namespace
-
-// ---- what the other host units call too (declared in uwt_ctx.h) -----------------------------------------------------------
-namespace uwt {
 
 hipError_t DevBuf::release() {
   const hipError_t e = p ? hipFree(p) : hipSuccess;
@@ -1059,7 +1060,7 @@ int uwt_destroy(uwt_ctx* c) {
   for (int i = 1; i < uwt_ctx::kMaxParts; i++)
     if (c->part_stream[i]) (void)hipStreamSynchronize(c->part_stream[i]);
   for (DevBuf* b : {&c->scratch, &c->stage[0], &c->stage[1], &c->cand_tab, &c->cand_cnt, &c->cand_work, &c->cand_recs, &c->match_desc,
-                    &c->match_cnt, &c->match_part, &c->match_out, &c->ransac_buf, &c->surf_buf})
+                    &c->match_cnt, &c->match_part, &c->match_out, &c->ransac_buf, &c->surf_buf, &c->track_buf})
     (void)b->release();
   // the fixed-size allocations of uwt_create, uwt_update_params, ensure_features and ransac_need_rows (null: nothing to free)
   for (int l = 0; l < UWT_MAX_LEVELS; l++)

@@ -2,6 +2,7 @@
 #include "uwt_ctx.h"
 #include "uwt_match.h"
 #include "uwt_ransac.h"
+#include "uwt_track.h"
 
 extern "C" {
 
@@ -70,7 +71,47 @@ int match_descriptors_enqueue(uwt_ctx* c, const char* what, int n_pairs, int nor
   return UWT_OK;
 }
 
+// The device-input form: both sets and their counts are in device memory and are read in place.  The counts are unknown here, so the
+// row bound, the tiles and the splits come from cap; the kernels read counts that k_match_counts has confined to 0..cap.
+int match_descriptors_device_enqueue(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, const void* d_query,
+                                     const int32_t* d_n_query, const void* d_train, const int32_t* d_n_train, int cap, float ratio,
+                                     MatchOut* d_matches, int* d_counts) {
+  if (n_pairs < 1 || !d_query || !d_n_query || !d_train || !d_n_train) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null list or n_pairs < 1");
+  if (norm != UWT_NORM_L2 && norm != UWT_NORM_HAMMING) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": unknown norm");
+  if (dim < 1 || (dim & 3)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": dim must be a positive multiple of 4");
+  if (cap < 1) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": cap < 1");
+  if (!std::isfinite(ratio)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": ratio is not finite");
+  const int words = norm == UWT_NORM_L2 ? dim : dim / 4;
+  if (cap > kMatchMaxRows || words > kMatchMaxWords)
+    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS or a row above UWT_MATCH_MAX_ROW_BYTES");
+  const int tiles = (cap + kMatchTile - 1) / kMatchTile;
+  const size_t blocks = (size_t)n_pairs * tiles * 2;
+  const int splits = (int)std::min<size_t>(std::min(kMatchMaxSplits, tiles), (kMatchTargetBlocks + blocks - 1) / blocks);
+  int st = c->match_cnt.reserve(c, c->stream, sizeof(int) * 2 * (size_t)n_pairs);
+  if (!st) st = c->match_part.reserve(c, c->stream, sizeof(Knn2) * cap * (size_t)splits * n_pairs * 2);
+  if (st) return st;
+  int* d_cnt[2] = {(int*)c->match_cnt.p, (int*)c->match_cnt.p + n_pairs};
+  MatchArgs a;
+  a.desc[0] = (const uint32_t*)d_query; a.desc[1] = (const uint32_t*)d_train; a.cnt[0] = d_cnt[0]; a.cnt[1] = d_cnt[1];
+  a.cap = cap; a.words = words; a.n_pairs = n_pairs; a.splits = splits;
+  a.part = (Knn2*)c->match_part.p;
+  launch_match_counts(c->stream, n_pairs, cap, d_n_query, d_n_train, d_cnt[0], d_cnt[1]);
+  launch_knn2(c->stream, norm, a, 2, cap);
+  launch_match_filter(c->stream, a, ratio, d_matches, d_counts);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
 }  // namespace
+
+int uwt_match_descriptors_device_async(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32_t dim, const void* d_query, const int32_t* d_n_query,
+                                       const void* d_train, const int32_t* d_n_train, int32_t cap, float ratio, uwt_match* d_matches_out,
+                                       int32_t* d_counts_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !d_matches_out || !d_counts_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_match_descriptors_device_async: null argument");
+  return match_descriptors_device_enqueue(c, "uwt_match_descriptors_device_async", n_pairs, norm, dim, d_query, d_n_query, d_train, d_n_train,
+                                          cap, ratio, reinterpret_cast<MatchOut*>(d_matches_out), d_counts_out);
+}
 
 int uwt_knn_match_batch(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32_t dim, const void* query, const int32_t* n_query,
                         const void* train, const int32_t* n_train, int32_t cap, uwt_knn2* out) {
@@ -166,8 +207,7 @@ int ransac_check(uwt_ctx* c, const char* what, int n_pairs, int cap, const float
     return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null list, n_pairs < 1, cap < 1 or kp_cap < 1");
   if (params) *rp = *params;
   else uwt_default_ransac_params(rp);
-  if (!std::isfinite(rp->distance) || rp->distance < 0.0 || !(rp->confidence > 0.0 && rp->confidence <= 1.0) || rp->max_hypotheses < 1 ||
-      rp->max_hypotheses > UWT_RANSAC_MAX_HYPOTHESES)
+  if (!ransac_params_ok(*rp))
     return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": distance, confidence or max_hypotheses outside its range");
   for (int p = 0; p < n_pairs; p++)
     if (n_kp_prev[p] < 0 || n_kp_prev[p] > kp_cap || n_kp_cur[p] < 0 || n_kp_cur[p] > kp_cap)
@@ -318,3 +358,44 @@ int uwt_ransac_inliers_batch(uwt_ctx* c, int32_t n_pairs, const uwt_match* match
 }
 
 }  // extern "C"
+
+// ---- what the chained tracking call uses of this unit (declared in uwt_ctx.h) -------------------------------------------------------
+bool uwt::ransac_params_ok(const uwt_ransac_params& rp) {
+  return std::isfinite(rp.distance) && rp.distance >= 0.0 && rp.confidence > 0.0 && rp.confidence <= 1.0 && rp.max_hypotheses >= 1 &&
+         rp.max_hypotheses <= UWT_RANSAC_MAX_HYPOTHESES;
+}
+
+// scratch: [(x, y, x', y') of every match | the inlier mask]; need(k) for every N up to cap, as in uwt_ransac_inliers_batch_async
+int uwt::ransac_device_enqueue(uwt_ctx* c, int n_pairs, int cap, const uwt_ransac_params& rp, const uwt_match* d_matches,
+                               const int32_t* d_n_matches, const uwt_keypoint* d_kp_prev, const int32_t* d_n_kp_prev,
+                               const uwt_keypoint* d_kp_cur, const int32_t* d_n_kp_cur, uwt_match* d_good, int32_t* d_counts,
+                               uwt_ransac_info* d_info) {
+  std::vector<int> ns;
+  for (int n = kRansacMinSample; n <= cap; n++) ns.push_back(n);
+  Carve cv(16);
+  const size_t o_quads = cv.take<float4>((size_t)cap * n_pairs), o_mask = cv.take<uint8_t>((size_t)cap * n_pairs);
+  int st = c->ransac_buf.reserve(c, c->stream, cv.total());
+  if (!st) st = ransac_need_rows(c, rp, ns);
+  if (st) return st;
+  RansacArgs a;
+  a.matches = reinterpret_cast<const MatchOut*>(d_matches);
+  a.n_matches = d_n_matches;
+  a.kp_prev = a.kp_cur = nullptr;
+  a.n_kp_prev = d_n_kp_prev;
+  a.n_kp_cur = d_n_kp_cur;
+  a.quads = Carve::at<float4>(c->ransac_buf.p, o_quads);
+  a.need = c->ransac_need;
+  a.cap = cap; a.kp_cap = cap; a.n_pairs = n_pairs;
+  a.max_hypotheses = rp.max_hypotheses;
+  a.seed = rp.seed;
+  a.t2 = rp.distance * rp.distance;
+  a.invalid_status = UWT_ERR_INVALID_ARG;
+  a.mask = Carve::at<uint8_t>(c->ransac_buf.p, o_mask);
+  a.good = reinterpret_cast<MatchOut*>(d_good);
+  a.counts = d_counts;
+  a.info = reinterpret_cast<RansacInfo*>(d_info);
+  static_assert(sizeof(uwt_keypoint) == 8 * sizeof(float), "uwt_keypoint: eight 32-bit fields, (x, y) first");
+  launch_ransac_records(c->stream, a, reinterpret_cast<const float*>(d_kp_prev), reinterpret_cast<const float*>(d_kp_cur), 8, cap);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}

@@ -30,22 +30,6 @@ namespace {
 constexpr size_t kSurfChunkBytes = 256u << 20;   // scratch a chunk of frames may take
 constexpr int kSurfMaxChunk = 4096;              // frames of a chunk at most (a launch's grid)
 
-int surf_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_surf_params* params,
-               uwt_surf_params* sp) {
-  if (n_frames < 1 || cap < 1 || !slots) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_frames < 1, cap < 1 or a null list");
-  if (cap > UWT_MATCH_MAX_ROWS) return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS");
-  for (int f = 0; f < n_frames; f++)
-    if (!slot_range_ok(c, slots[f], 1)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": slot out of range");
-  if (params) *sp = *params;
-  else uwt_default_surf_params(sp);
-  if (!std::isfinite(sp->hessian_threshold)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": threshold is not finite");
-  if (sp->n_octaves < 1 || sp->n_octaves > kSurfMaxOctaves || sp->n_octave_layers < 1 || sp->n_octave_layers > kSurfMaxLayers - 2)
-    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_octaves or n_octave_layers outside 1..4");
-  if (((long long)c->p.width + 1) * ((long long)c->p.height + 1) >= (1ll << 31))
-    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": the integral image has 2^31 entries or more");
-  return UWT_OK;
-}
-
 // the scratch of a chunk of nf frames: [slots | raw counts | counts | integral | raw | keys | keep | key points | descriptors | extra]
 struct SurfLayout {
   size_t slots, raw_count, counts, integral, raw, key, keep, kp, desc, extra, total;
@@ -252,3 +236,53 @@ int uwt_surf_response_layer(uwt_ctx* c, int32_t slot, int32_t octave, int32_t la
 }
 
 }  // extern "C"
+
+// ---- what the chained tracking call uses of this unit (declared in uwt_ctx.h) -------------------------------------------------------
+// Nothing is enqueued when a check fails.
+int uwt::surf_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_surf_params* params,
+                    uwt_surf_params* sp) {
+  if (n_frames < 1 || cap < 1 || !slots) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_frames < 1, cap < 1 or a null list");
+  if (cap > UWT_MATCH_MAX_ROWS) return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS");
+  for (int f = 0; f < n_frames; f++)
+    if (!slot_range_ok(c, slots[f], 1)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": slot out of range");
+  if (params) *sp = *params;
+  else uwt_default_surf_params(sp);
+  if (!std::isfinite(sp->hessian_threshold)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": threshold is not finite");
+  if (sp->n_octaves < 1 || sp->n_octaves > kSurfMaxOctaves || sp->n_octave_layers < 1 || sp->n_octave_layers > kSurfMaxLayers - 2)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_octaves or n_octave_layers outside 1..4");
+  if (((long long)c->p.width + 1) * ((long long)c->p.height + 1) >= (1ll << 31))
+    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": the integral image has 2^31 entries or more");
+  return UWT_OK;
+}
+
+
+// The tracking call's SURF: surf_run's chunks with the path of every frame decided on the device.  A chunk's extra scratch holds the
+// frames' modes; detection runs under them (the blocks of a frame on another path return at once), k_surf_take_provided has put the
+// provided records and counts where detection would have put its own, and the describe launch, sized by cap, serves both.
+int uwt::surf_track_enqueue(uwt_ctx* c, const uwt_surf_params& sp, int n_pairs, const int32_t* slots, int cap, const int* d_path,
+                            const uwt_keypoint* d_prev_kp, const int32_t* d_n_prev, uwt_keypoint* d_kp, float* d_desc, int* d_counts) {
+  const int n_frames = 2 * n_pairs;
+  int st = compute_begin_pairs(c, n_frames, slots, slots);
+  if (st) return st;
+  const size_t raw_cap = surf_raw_bound(c->p.width, c->p.height, sp.n_octaves, sp.n_octave_layers + 2);
+  const int chunk = surf_chunk_frames(c, n_frames, raw_cap, cap);
+  for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+    const int nf = std::min(chunk, n_frames - f0);
+    SurfArgs a;
+    unsigned char* x = nullptr;
+    st = surf_begin_chunk(c, sp, slots + f0, nf, raw_cap, cap, sizeof(int) * (size_t)nf, &a, &x);
+    if (st) return st;
+    int* mode = reinterpret_cast<int*>(x);
+    a.mode = mode;
+    launch_surf_take_provided(c->stream, a, f0, n_pairs, d_path, reinterpret_cast<const SurfKeypoint*>(d_prev_kp), d_n_prev, mode);
+    HIPCHK(c, hipMemsetAsync(a.raw_count, 0, sizeof(int) * (size_t)nf, c->stream));
+    launch_surf_detect(c->stream, a);
+    launch_surf_describe(c->stream, a, cap);
+    HIPCHK(c, hipGetLastError());
+    const size_t recs = (size_t)nf * cap, g0 = (size_t)f0 * cap;
+    HIPCHK(c, hipMemcpyAsync(d_counts + f0, a.counts, sizeof(int) * (size_t)nf, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_kp + g0, a.kp, sizeof(SurfKeypoint) * recs, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_desc + g0 * 64, a.desc, sizeof(float) * 64 * recs, hipMemcpyDeviceToDevice, c->stream));
+  }
+  return UWT_OK;
+}

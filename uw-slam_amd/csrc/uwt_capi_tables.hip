@@ -292,9 +292,18 @@ int check_features_args(uwt_ctx* c, const char* what, int n, const int32_t* slot
 }
 
 
+// the batched producer over feat_kp / feat_nkp as they are on the device: frame f's table at feat_tab + f * kFeatTableRows from its
+// key points and the depth of slot d_slots[f]
+int enqueue_patch_producer(uwt_ctx* c, int n, const int* d_slots) {
+  uwt::launch_patch_points_batch(c->stream, n, c->feat_kp, c->feat_nkp, d_slots, c->p.has_depth ? c->depth[0] : nullptr,
+                                 (size_t)c->lv[0].n, c->lv[0].pitch, c->lv[0].gw, c->lv[0].gh, c->feat_tab, kFeatTableRows,
+                                 c->feat_cnt);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
 // The caller's key points and counts are copied before the call returns (into the next block of a pinned ring, as
-// upload_pairs does with the pair lists), then asynchronously to the device, and the batched producer builds frame f's table
-// at feat_tab + f * kFeatTableRows from the key points and the depth of slot d_slots[f].
+// upload_pairs does with the pair lists), then asynchronously to the device, and the batched producer builds the tables.
 int enqueue_patch_tables(uwt_ctx* c, int n, const int* d_slots, const float* kp, const int32_t* n_kp) {
   const size_t mp = (size_t)c->p.max_pairs;
   const int stage = (c->feat_stage + 1) % uwt_ctx::kPairStages;
@@ -308,11 +317,7 @@ int enqueue_patch_tables(uwt_ctx* c, int n, const int* d_slots, const float* kp,
   HIPCHK(c, hipMemcpyAsync(c->feat_nkp, h_n, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->feat_kp, h_kp, sizeof(float) * kFeatKpFloats * n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipEventRecord(c->ev_feat[stage], c->stream));
-  uwt::launch_patch_points_batch(c->stream, n, c->feat_kp, c->feat_nkp, d_slots, c->p.has_depth ? c->depth[0] : nullptr,
-                                 (size_t)c->lv[0].n, c->lv[0].pitch, c->lv[0].gw, c->lv[0].gh, c->feat_tab, kFeatTableRows,
-                                 c->feat_cnt);
-  HIPCHK(c, hipGetLastError());
-  return UWT_OK;
+  return enqueue_patch_producer(c, n, d_slots);
 }
 
 // One level of device-resident tables: pair i's rows at ta.tables + i * ta.stride, its count at ta.counts[i]; slices: the grid's
@@ -502,3 +507,20 @@ int uwt_estimate_pose_candidates_batch(uwt_ctx* c, int32_t n_pairs, const int32_
 }
 
 }  // extern "C"
+
+// ---- what the chained tracking call uses of this unit (declared in uwt_ctx.h) -------------------------------------------------------
+int uwt::features_device_begin(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots) {
+  int st = check_pair_lists(c, what, n_pairs, ref_slots, tgt_slots);
+  if (!st) st = ensure_features(c);
+  if (!st) st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
+  return st;
+}
+
+// features_enqueue behind its staging: the key points and their counts are on the device already, so the grid's slices are the
+// bound of any table (a pair's own slice count comes from its producer's count: the bound shows in no bit)
+int uwt::features_device_enqueue(uwt_ctx* c, int n_pairs, float* d_poses, uwt_stats* d_stats) {
+  int st = enqueue_patch_producer(c, n_pairs, c->d_ref);
+  if (st) return st;
+  const TableLevel lv0 = {{c->feat_tab, c->feat_cnt, kFeatTableRows}, table_slices(kFeatTableRows)};
+  return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, d_poses, reinterpret_cast<StatsOut*>(d_stats));
+}

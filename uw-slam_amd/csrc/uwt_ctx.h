@@ -150,6 +150,9 @@ struct uwt_ctx {
   // SURF detection and description (uwt_surf_*): per chunk of frames the slot list, the counts, the integral images, the raw
   // candidates with their order keys, and the key points and descriptors before they go to the caller — grown on use
   DevBuf surf_buf;
+  // the chained tracking call (uwt_tracking_batch*): per pair and side the key points, descriptors and counts SURF leaves, the paths
+  // and flags of the previous frames, symMatches and the RANSAC records; behind them the synchronous form's inputs and results
+  DevBuf track_buf;
   DevBuf stage[2];                      // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
   bool profiling = false;
   int spec_budget = 0;                  // speculative launching: evaluations a level gets (0: first_poll + 1); doubled when an alignment
@@ -217,6 +220,31 @@ struct RowSet { const void* d_rows; size_t elem_bytes; const int32_t* counts; vo
 int rows_to_host(uwt_ctx* c, int cap, int n_items, std::initializer_list<RowSet> sets);
 int counted_rows_to_host(uwt_ctx* c, const float4* d_rows, size_t stride, const int* d_counts, int n_items, int cap, float* pts_out,
                          int32_t* counts_out);
+
+// ---- the stages of the chained tracking call (uwt_capi_tracking.hip), each in its stage's unit ---------------------------------
+// the checks of a SURF call (uwt_capi_surf.hip); *sp: the parameters in force
+int surf_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_surf_params* params,
+               uwt_surf_params* sp);
+// SURF for the 2 x n_pairs frames of a tracking call, job j < n_pairs the previous frame of pair j under d_path[j] (kSurfDetect /
+// kSurfProvided at d_prev_kp, d_n_prev / kSurfNone), the others the current frames, detected: in chunks, each chunk's rows delivered
+// to d_kp (2 n_pairs x cap records), d_desc (x 64 floats) and d_counts (2 n_pairs) on the context stream.  slots: the 2 n_pairs slots.
+int surf_track_enqueue(uwt_ctx* c, const uwt_surf_params& sp, int n_pairs, const int32_t* slots, int cap, const int* d_path,
+                       const uwt_keypoint* d_prev_kp, const int32_t* d_n_prev, uwt_keypoint* d_kp, float* d_desc, int* d_counts);
+// the range check of uwt_ransac_params
+bool ransac_params_ok(const uwt_ransac_params& rp);
+// ransacTest with every input in device memory: the matches and their counts, both key-point sets as n_pairs x cap uwt_keypoint
+// records and their counts (in 0..cap); results as uwt_ransac_inliers_batch_async leaves them (the mask stays in the scratch)
+int ransac_device_enqueue(uwt_ctx* c, int n_pairs, int cap, const uwt_ransac_params& rp, const uwt_match* d_matches,
+                          const int32_t* d_n_matches, const uwt_keypoint* d_kp_prev, const int32_t* d_n_kp_prev,
+                          const uwt_keypoint* d_kp_cur, const int32_t* d_n_kp_cur, uwt_match* d_good, int32_t* d_counts,
+                          uwt_ransac_info* d_info);
+// the live call from key points that are in device memory: features_device_begin checks the pair lists, makes the context's feat_kp
+// (max_pairs x 200 float2) / feat_nkp exist and sends the lists; once the caller's kernels have filled both, features_device_enqueue
+// runs the patch producer and the alignment from them
+int features_device_begin(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots);
+int features_device_enqueue(uwt_ctx* c, int n_pairs, float* d_poses, uwt_stats* d_stats);
+// UWT_ERR_PAIR_FAILED with the first failed pair's status in the message, or UWT_OK
+int first_failure(uwt_ctx* c, const char* what, const uwt_stats* stats, int n);
 
 // The early-exit look of the batch paths, taken one evaluation late (enqueue_estimate has the schedule and the reasons): the
 // launch of an evaluation that is due counts the pairs still on the level into one of two device counters; behind it the count

@@ -1,5 +1,5 @@
 // uwt_launch_surf.hip — the launches of SURF detection and description: k_surf_integral_rows / _cols, k_surf_response,
-// k_surf_select, k_surf_describe, k_surf_response_layer.
+// k_surf_select, k_surf_describe, k_surf_response_layer, k_surf_take_provided.
 #include "uwt_surf_kernels.h"
 
 namespace uwt {
@@ -30,6 +30,12 @@ void launch_surf_describe(hipStream_t s, const SurfArgs& a, int rows) {
   if (rows < 1) return;
   hipLaunchKernelGGL(k_surf_describe, dim3((unsigned)((rows + kSurfDescWaves - 1) / kSurfDescWaves), (unsigned)a.n_frames),
                      dim3(64 * kSurfDescWaves), 0, s, a);
+}
+
+void launch_surf_take_provided(hipStream_t s, const SurfArgs& a, int j0, int n_pairs, const int* path, const SurfKeypoint* prev_kp,
+                               const int* n_prev, int* mode) {
+  hipLaunchKernelGGL(k_surf_take_provided, dim3((unsigned)((a.cap + 255) / 256), (unsigned)a.n_frames), dim3(256), 0, s, a, j0, n_pairs,
+                     path, prev_kp, n_prev, mode);
 }
 
 }  // namespace uwt

@@ -42,5 +42,8 @@ struct RansacArgs {
 
 // k_ransac_gather over `rows` matches per pair at most, then k_ransac: one block per pair
 void launch_ransac(hipStream_t s, const RansacArgs& a, int rows);
+// the same with the key points read from records of rec_floats floats that begin with (x, y): rec_prev / rec_cur, n_pairs x a.kp_cap
+// records in device memory (a.kp_prev / a.kp_cur are not read); rows: the bound on a pair's matches (cap)
+void launch_ransac_records(hipStream_t s, const RansacArgs& a, const float* rec_prev, const float* rec_cur, int rec_floats, int rows);
 
 }  // namespace uwt

@@ -49,6 +49,22 @@ static __global__ __launch_bounds__(256) void k_ransac_gather(RansacArgs a, int 
   a.quads[(size_t)p * a.cap + i] = q;
 }
 
+// The same with both key-point sets as records of rec_floats floats that begin with (x, y) (uwt_keypoint), n_pairs x kp_cap of them.
+static __global__ __launch_bounds__(256) void k_ransac_gather_records(RansacArgs a, const float* __restrict__ rec_prev,
+                                                                      const float* __restrict__ rec_cur, int rec_floats, int chunks) {
+  const int p = blockIdx.x / chunks, i = (blockIdx.x - p * chunks) * 256 + threadIdx.x;
+  const int n = a.n_matches[p];
+  if (n < 0 || n > a.cap || i >= n) return;
+  const MatchOut m = a.matches[(size_t)p * a.cap + i];
+  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (ransac_match_ok(m, a.n_kp_prev[p], a.n_kp_cur[p], a.kp_cap)) {
+    const float* u = rec_prev + ((size_t)p * a.kp_cap + m.query_idx) * rec_floats;
+    const float* v = rec_cur + ((size_t)p * a.kp_cap + m.train_idx) * rec_floats;
+    q = make_float4(u[0], u[1], v[0], v[1]);
+  }
+  a.quads[(size_t)p * a.cap + i] = q;
+}
+
 // One block per pair, one hypothesis per lane, in rounds of kRansacBlock hypotheses.  A lane draws its sample, eliminates its
 // 8 x 9 matrix — which is indexed by run-time pivots and therefore lives in LDS, element-major (element e of lane t at
 // e * kRansacBlock + t: whatever element a lane addresses, its bank is its own) — and counts its inliers over the pair's matches,

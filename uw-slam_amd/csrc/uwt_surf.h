@@ -14,6 +14,7 @@ constexpr int kSurfTile = 32;          // grid points of a response tile along x
 constexpr int kSurfBlock = 256;
 constexpr int kSurfSelectBlock = 1024;
 constexpr int kSurfDescWaves = 4;      // key points of a describe block: one wave each
+constexpr int kSurfDetect = 0, kSurfProvided = 1, kSurfNone = 2;   // SurfArgs::mode: detection; the caller's key points; no key points
 
 struct SurfKeypoint { float x, y, size, response, dir_x, dir_y; int octave, laplacian; };
 
@@ -45,6 +46,8 @@ struct SurfArgs {
   float* desc;               // n_frames x cap x 64, or null
   int* counts;               // n_frames
   int cap;
+  const int* mode = nullptr; // n_frames, or null: every frame is detected.  Else the frame's path, decided on the device: only a
+                             // frame with kSurfDetect runs detection (k_surf_response, k_surf_select return at once for the others)
 };
 
 // both passes of the integral image of every frame of the chunk
@@ -55,5 +58,10 @@ void launch_surf_detect(hipStream_t s, const SurfArgs& a);
 void launch_surf_response_layer(hipStream_t s, const SurfArgs& a, int octave, int layer, double* out);
 // orientation (unless a.upright) and descriptors of a.kp[f * cap .. + counts[f]); rows: the largest count the batch can hold
 void launch_surf_describe(hipStream_t s, const SurfArgs& a, int rows);
+// The chunk's frames are jobs j0 .. j0 + n_frames - 1 of a tracking call over n_pairs pairs (job j < n_pairs: the previous frame of
+// pair j, whose path is path[j]; the others: current frames, always detected): writes a.mode, and for a frame that is not detected
+// its count (the provided one, or 0) and the provided records into a.kp.  a.mode must be set.
+void launch_surf_take_provided(hipStream_t s, const SurfArgs& a, int j0, int n_pairs, const int* path, const SurfKeypoint* prev_kp,
+                               const int* n_prev, int* mode);
 
 }  // namespace uwt

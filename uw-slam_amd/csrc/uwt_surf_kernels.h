@@ -148,6 +148,7 @@ __global__ __launch_bounds__(kSurfBlock) void k_surf_response(SurfArgs a, int oc
   extern __shared__ double lds_r[];
   constexpr int T = kSurfTile + 2;
   const int f = blockIdx.z;
+  if (a.mode && a.mode[f] != kSurfDetect) return;   // (uniform: ahead of every barrier)
   const uint32_t* I = a.integral + (size_t)f * (size_t)(a.h + 1) * (size_t)(a.w + 1);
   const int gx0 = blockIdx.x * kSurfTile - 1, gy0 = blockIdx.y * kSurfTile - 1;   // grid point of the tile's (0, 0), halo included
   const int L = a.layers;
@@ -230,6 +231,7 @@ __global__ __launch_bounds__(kSurfSelectBlock) void k_surf_select(SurfArgs a) {
   __shared__ float t_resp[kSurfSelectBlock];
   __shared__ unsigned char t_keep[kSurfSelectBlock];
   const int f = blockIdx.x, tid = threadIdx.x;
+  if (a.mode && a.mode[f] != kSurfDetect) return;   // (uniform) the frame's count and key points come from elsewhere
   const int n = min(a.raw_count[f], a.raw_cap);
   const SurfKeypoint* raw = a.raw + (size_t)f * a.raw_cap;
   const unsigned long long* key = a.raw_key + (size_t)f * a.raw_cap;
@@ -284,6 +286,7 @@ __global__ __launch_bounds__(64 * kSurfDescWaves) void k_surf_describe(SurfArgs 
   __shared__ float lds_n2[kSurfDescWaves][36], lds_sx[kSurfDescWaves][36], lds_sy[kSurfDescWaves][36];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, f = blockIdx.y;
   const int k = blockIdx.x * kSurfDescWaves + wv;
+  if ((int)blockIdx.x * kSurfDescWaves >= min(a.counts[f], a.cap)) return;   // (uniform) a launch sized by cap: no row of this block
   const bool live = k < min(a.counts[f], a.cap);
   const uint32_t* I = a.integral + (size_t)f * (size_t)(a.h + 1) * (size_t)(a.w + 1);
   SurfKeypoint* kp = a.kp + (size_t)f * a.cap + (live ? k : 0);
@@ -381,6 +384,21 @@ __global__ __launch_bounds__(64 * kSurfDescWaves) void k_surf_describe(SurfArgs 
   for (int m = 32; m > 0; m >>= 1) q = q + __shfl_xor(q, m, 64);
   const float n = sqrtf(q);
   a.desc[((size_t)f * a.cap + k) * 64 + lane] = n == 0.f ? 0.f : acc / n;
+}
+
+// ---- the caller's key points from device memory (the tracking call) --------------------------------------------------------------
+// grid (ceil(cap / 256), n_frames).  path[] holds kSurfDetect / kSurfProvided / kSurfNone per pair; a provided count is in 0..cap
+// (k_track_predicate refused the pair otherwise).
+__global__ __launch_bounds__(256) void k_surf_take_provided(SurfArgs a, int j0, int n_pairs, const int* __restrict__ path,
+                                                            const SurfKeypoint* __restrict__ prev_kp, const int* __restrict__ n_prev,
+                                                            int* __restrict__ mode) {
+  const int f = blockIdx.y, j = j0 + f, i = blockIdx.x * 256 + threadIdx.x;
+  const int m = j < n_pairs ? path[j] : kSurfDetect;
+  if (i == 0) mode[f] = m;
+  if (m == kSurfDetect) return;
+  const int n = m == kSurfProvided ? min(max(n_prev[j], 0), a.cap) : 0;
+  if (i == 0) a.counts[f] = n;
+  if (i < n) a.kp[(size_t)f * a.cap + i] = prev_kp[(size_t)j * a.cap + i];
 }
 
 }  // namespace uwt

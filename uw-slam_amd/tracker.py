@@ -355,6 +355,48 @@ def Tracking(tracker, robust_matcher, previous_frame, current_frame):
     return tracker.EstimatePoseFeatures(previous_frame, current_frame)
 
 
+def TrackingBatch(tracker, robust_matcher, pairs, cap=2048):
+    """System::Tracking() for a list of (previous_frame, current_frame) pairs through the device-resident call
+    (uwt_tracking_batch): SURF, the matcher, ransacTest, getGoodKeypoints and the live alignment run as one chain on the device,
+    and keypoints_, surf_keypoints_, n_matches_ of both frames and previous_frame.rigid_transformation_ end up exactly as the
+    Tracking loop over the same list leaves them.  Pairs that share no frame go into one call; a pair that names a frame an earlier
+    pair of the list has written (the next pair of a sequence) waits for that pair's results, as it does in the loop.  Returns
+    the per-pair stats; a pair without a good match has ERR_NO_VALID_POINTS there and its frames' lists empty."""
+    ctx = tracker._ctx
+    rm = robust_matcher
+    params = capi.default_tracking_params(
+        surf=dict(hessian_threshold=rm.hessian_threshold_, n_octaves=rm.n_octaves_, n_octave_layers=rm.n_octave_layers_,
+                  upright=int(rm.upright_)),
+        ransac=dict(distance=rm.distance_, confidence=rm.confidence_, max_hypotheses=rm.max_hypotheses_, seed=rm.seed_),
+        ratio=rm.ratio_, min_matches=110)
+    stats, i = [], 0
+    while i < len(pairs):
+        run, seen = [], set()
+        while i < len(pairs) and len(run) < ctx.params.max_pairs and not ({id(pairs[i][0]), id(pairs[i][1])} & seen):
+            run.append(pairs[i])
+            seen |= {id(pairs[i][0]), id(pairs[i][1])}
+            i += 1
+        for a, b in run:
+            if not a.obtained_gradients_:
+                tracker.ApplyGradient(a)
+            tracker.ApplyGradient(b)
+        slots = [(tracker._bind(a), tracker._bind(b)) for a, b in run]
+        for (a, b), (sa, sb) in zip(run, slots):   # binding a later pair's frame may have taken an earlier frame's slot
+            if a._slot != sa or b._slot != sb or not (a.obtained_gradients_ and b.obtained_gradients_):
+                raise RuntimeError("TrackingBatch: more frames than slots (max_frames)")
+        r = ctx.tracking_batch([s[0] for s in slots], [s[1] for s in slots], prev=[a.surf_keypoints_ for a, _ in run], params=params,
+                               cap=cap)
+        for k, (a, b) in enumerate(run):
+            kp0, kp1 = r["kept_prev"][k], r["kept_cur"][k]
+            a.n_matches_ = b.n_matches_ = len(kp0)
+            a.keypoints_, b.keypoints_ = np.stack([kp0["x"], kp0["y"]], 1), np.stack([kp1["x"], kp1["y"]], 1)
+            a.surf_keypoints_, b.surf_keypoints_ = kp0, kp1
+            a.rigid_transformation_ = r["poses"][k].copy()
+            st = r["stats"][k]
+            stats.append(dict(status=int(st["status"]), iterations=int(st["iterations"]), n_valid=int(st["n_valid"]), error=float(st["error"])))
+    return stats
+
+
 class LS:
     """include/LeastSquares.h:26-50 over the GPU reduction: rows are buffered by update() / updateSSE() and folded by
     finish*() — scalar rows through uwt_ls_accumulate, 4-wide rows through uwt_ls_accumulate_sse (the two forms associate
