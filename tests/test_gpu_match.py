@@ -224,6 +224,29 @@ def test_gpu_argument_errors_leave_the_outputs_untouched(capi):
 
 
 @pytest.mark.gpu
+def test_gpu_every_count_zero_runs_the_filter_alone(capi):
+    """Two pairs, dim 64, cap 8, every count 0: the batch has no row, so no k_knn2 launch is made (its grid would be empty) and
+    k_match_filter still runs.  The synchronous call delivers counts 0 and no match row; the asynchronous one, whose rows the test
+    reads in device memory, writes counts 0 and leaves every row as it was — though the rows behind the counts are equal sets"""
+    import torch
+    ctx = small_ctx(capi)
+    P, cap, dim = 2, 8, 64
+    rows = np.random.default_rng(21).normal(size=(P, cap, dim)).astype(np.float32)
+    none = np.zeros(P, np.int32)
+    out = np.full(P * cap * 3, 0x5A5A5A5A, np.uint32)
+    cnt = np.full(P, 0x5A5A5A5A, np.uint32)
+    assert raw_call(capi, ctx, "uwt_match_descriptors_batch", P, capi.NORM_L2, dim, rows, none, rows, none, cap, 0.65, out, cnt) == 0
+    assert cnt.tolist() == [0, 0] and np.all(out == 0x5A5A5A5A)
+    d_m = torch.full((P, cap, 3), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    d_c = torch.full((P,), -7, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()   # torch's fill kernels run on torch's stream, not on the context's
+    assert ctx.match_descriptors_batch_async(d_m.data_ptr(), d_c.data_ptr(), packed=(rows, none, rows, none)) == cap
+    ctx.sync()
+    assert d_c.cpu().tolist() == [0, 0] and bool((d_m.cpu() == 0x5A5A5A5A).all())
+    ctx.close()
+
+
+@pytest.mark.gpu
 def test_gpu_tracking_is_untouched_by_match_calls(capi, synth):
     """one live call before and after match calls on the same context: the same bits, the same params"""
     w, h, intr = VGA

@@ -93,6 +93,21 @@ def test_gpu_ragged_sizes_budgets_and_confidences(capi, seed):
     ctx.close()
 
 
+@pytest.mark.gpu
+def test_gpu_pair_without_matches_beside_the_minimum_sample(capi):
+    """A pair of 0 matches beside one of 8, the minimum sample, and the empty pair alone: then the batch has no row, no gather launch
+    is made, and k_ransac still writes the pair's record"""
+    empty, eight = K.scene(800, 0, 0.0, 0.2)[:3], K.scene(6, 8, 0.0, 0.2)[:3]
+    ctx = small_ctx(capi)
+    for pairs in ([empty, eight], [empty]):
+        got = ctx.ransac_inliers_batch(pairs)
+        for i, pr in enumerate(pairs):
+            assert same_result(got[i], run_ref(pr)) is None, (len(pairs), i, same_result(got[i], run_ref(pr)))
+        mask, good, info = got[0]
+        assert len(mask) == 0 and len(good) == 0 and info["status"] == 0 and info["best_hypothesis"] == -1 and not np.any(info["F"])
+    ctx.close()
+
+
 def mixed_pairs(count=64, seed=5):
     """pairs of mixed sizes: empty, below the sample size, around the wave and block edges, a large one; some with outliers"""
     rng = np.random.default_rng(seed)

@@ -501,6 +501,24 @@ def test_gpu_match_device_equals_host_form(capi, synth, torch):
 
 
 @pytest.mark.gpu
+def test_gpu_match_device_every_count_zero(capi, torch):
+    """Two pairs, dim 64, cap 8, every device count 0, then one of them cap + 1 (taken as 0): the device form sizes k_knn2 by cap and
+    launches it all the same; counts 0 and no match row written (device_match looks), which is what the host form gives, whose
+    batch has no row and which launches no k_knn2 at all"""
+    ctx = capi.Context(capi.default_params(64, 48, 64.0, 64.0, 31.5, 23.5, n_levels=1, first_level=0, last_level=0, max_frames=2, max_pairs=1))
+    P, cap, dim = 2, 8, 64
+    rows = np.random.default_rng(21).normal(size=(P, cap, dim)).astype(np.float32)
+    none = np.zeros(P, np.int32)
+    want = ctx.match_descriptors_batch(packed=(rows, none, rows, none))
+    assert [len(w) for w in want] == [0, 0]
+    pairs = [(rows[i], rows[i]) for i in range(P)]
+    for counts in (([0, 0], [0, 0]), ([0, cap + 1], [0, 0])):
+        got = device_match(ctx, capi, torch, pairs, cap, 0.65, counts=counts)
+        assert [g.tobytes() for g in got] == [w.tobytes() for w in want], counts
+    ctx.close()
+
+
+@pytest.mark.gpu
 def test_gpu_track_sequence_chained_equals_live(capi, synth, torch):
     """tools/track_sequence.py --live --chained walks the sequence without a wait and gives the trajectory of --live"""
     import os

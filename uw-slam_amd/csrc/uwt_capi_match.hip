@@ -13,16 +13,42 @@ static_assert(sizeof(Knn2) == sizeof(uwt_knn2) && sizeof(MatchOut) == sizeof(uwt
 static_assert(kMatchMaxRows == UWT_MATCH_MAX_ROWS && kMatchMaxWords * 4 == UWT_MATCH_MAX_ROW_BYTES, "matching limits of include/uwt.h");
 static_assert(kMatchL2 == UWT_NORM_L2 && kMatchHamming == UWT_NORM_HAMMING, "uwt_norm");
 
-// Checks the arguments, grows the scratch, uploads both descriptor sets and their counts on the context stream and enqueues
-// k_knn2 behind them (dirs = 1: query -> train alone; 2: both directions).  Nothing is enqueued when a check fails.  The train
-// range of a (pair, query tile, direction) is cut into parts until the launch has kMatchTargetBlocks blocks: one pair of
-// 2000 x 2000 fills the chip as 1024 pairs of 500 x 500 do; the merge of the parts is exact, so the cut shows in no bit.
-int match_enqueue(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, const void* query, const int32_t* n_query,
-                  const void* train, const int32_t* n_train, int cap, int dirs, MatchArgs* out) {
-  if (n_pairs < 1 || !query || !n_query || !train || !n_train) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null list or n_pairs < 1");
+// The checks both forms share; *words: the 32-bit words of a row.
+int match_shape_check(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, int cap, int* words) {
+  if (n_pairs < 1) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_pairs < 1");
   if (norm != UWT_NORM_L2 && norm != UWT_NORM_HAMMING) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": unknown norm");
   if (dim < 1 || (dim & 3)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": dim must be a positive multiple of 4");
   if (cap < 1) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": cap < 1");
+  *words = norm == UWT_NORM_L2 ? dim : dim / 4;
+  if (cap > kMatchMaxRows || *words > kMatchMaxWords)
+    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS or a row above UWT_MATCH_MAX_ROW_BYTES");
+  return UWT_OK;
+}
+
+// k_knn2 over sets and counts that are in device memory (`a` but its parts), enqueued on the context stream (dirs = 1: query ->
+// train alone; 2: both directions); rows / train_rows bound the rows the launch covers and the rows they are compared with.  The
+// train range of a (pair, query tile, direction) is cut into parts until the launch has kMatchTargetBlocks blocks: one pair of
+// 2000 x 2000 fills the chip as 1024 pairs of 500 x 500 do; the merge of the parts is exact, so the cut shows in no bit.
+int match_core(uwt_ctx* c, MatchArgs& a, int norm, int dirs, int rows, int train_rows) {
+  const int tiles = (rows + kMatchTile - 1) / kMatchTile, train_tiles = (train_rows + kMatchTile - 1) / kMatchTile;
+  const size_t blocks = (size_t)a.n_pairs * std::max(tiles, 1) * dirs;
+  a.splits = (int)std::min<size_t>(std::min(kMatchMaxSplits, std::max(train_tiles, 1)), (kMatchTargetBlocks + blocks - 1) / blocks);
+  int st = c->match_part.reserve(c, c->stream, sizeof(Knn2) * a.cap * (size_t)a.splits * a.n_pairs * dirs);
+  if (st) return st;
+  a.part = (Knn2*)c->match_part.p;
+  if (rows > 0) {
+    launch_knn2(c->stream, norm, a, dirs, rows);
+    HIPCHK(c, hipGetLastError());
+  }
+  return UWT_OK;
+}
+
+// The host form: both sets and their counts are uploaded on the context stream, the core's bounds are the largest counts.  Nothing is
+// enqueued when an argument check fails (a failed growth of the parts, in the core, leaves the uploads queued: they touch the stage's
+// scratch alone).  The counts are looked at first: one outside 0..cap is reported before a cap above the limit.
+int match_enqueue(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, const void* query, const int32_t* n_query,
+                  const void* train, const int32_t* n_train, int cap, int dirs, MatchArgs* a) {
+  if (!query || !n_query || !train || !n_train) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null list");
   int max_q = 0, max_t = 0;
   for (int p = 0; p < n_pairs; p++) {
     if (n_query[p] < 0 || n_query[p] > cap || n_train[p] < 0 || n_train[p] > cap)
@@ -30,76 +56,39 @@ int match_enqueue(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, 
     max_q = std::max(max_q, n_query[p]);
     max_t = std::max(max_t, n_train[p]);
   }
-  const int words = norm == UWT_NORM_L2 ? dim : dim / 4;
-  if (cap > kMatchMaxRows || words > kMatchMaxWords)
-    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS or a row above UWT_MATCH_MAX_ROW_BYTES");
-  const int rows = dirs == 2 ? std::max(max_q, max_t) : max_q, train_rows = dirs == 2 ? rows : max_t;
-  const int tiles = (rows + kMatchTile - 1) / kMatchTile, train_tiles = (train_rows + kMatchTile - 1) / kMatchTile;
-  const size_t blocks = (size_t)n_pairs * std::max(tiles, 1) * dirs;
-  const int splits = (int)std::min<size_t>(std::min(kMatchMaxSplits, std::max(train_tiles, 1)), (kMatchTargetBlocks + blocks - 1) / blocks);
-  const size_t set_bytes = sizeof(uint32_t) * words * (size_t)cap * n_pairs;
-  int st = c->match_desc.reserve(c, c->stream, 2 * set_bytes);
+  int st = match_shape_check(c, what, n_pairs, norm, dim, cap, &a->words);
+  if (st) return st;
+  const size_t set_bytes = sizeof(uint32_t) * a->words * (size_t)cap * n_pairs;
+  st = c->match_desc.reserve(c, c->stream, 2 * set_bytes);
   if (!st) st = c->match_cnt.reserve(c, c->stream, sizeof(int) * 2 * (size_t)n_pairs);
-  if (!st) st = c->match_part.reserve(c, c->stream, sizeof(Knn2) * cap * (size_t)splits * n_pairs * dirs);
   if (st) return st;
   uint32_t* d_desc[2] = {(uint32_t*)c->match_desc.p, Carve::at<uint32_t>(c->match_desc.p, set_bytes)};
   int* d_cnt[2] = {(int*)c->match_cnt.p, (int*)c->match_cnt.p + n_pairs};
-  MatchArgs a;
-  a.desc[0] = d_desc[0]; a.desc[1] = d_desc[1]; a.cnt[0] = d_cnt[0]; a.cnt[1] = d_cnt[1];
-  a.cap = cap; a.words = words; a.n_pairs = n_pairs; a.splits = splits;
-  a.part = (Knn2*)c->match_part.p;
+  a->desc[0] = d_desc[0]; a->desc[1] = d_desc[1]; a->cnt[0] = d_cnt[0]; a->cnt[1] = d_cnt[1];
+  a->cap = cap; a->n_pairs = n_pairs;
   HIPCHK(c, hipMemcpyAsync(d_desc[0], query, set_bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_desc[1], train, set_bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_cnt[0], n_query, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_cnt[1], n_train, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
-  if (rows > 0) {
-    launch_knn2(c->stream, norm, a, dirs, rows);
-    HIPCHK(c, hipGetLastError());
-  }
-  *out = a;
-  return UWT_OK;
+  const int rows = dirs == 2 ? std::max(max_q, max_t) : max_q;
+  return match_core(c, *a, norm, dirs, rows, dirs == 2 ? rows : max_t);
 }
 
-int match_descriptors_enqueue(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, const void* query, const int32_t* n_query,
-                              const void* train, const int32_t* n_train, int cap, float ratio, MatchOut* d_matches, int* d_counts) {
-  if (!std::isfinite(ratio)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": ratio is not finite");
-  MatchArgs a;
-  int st = match_enqueue(c, what, n_pairs, norm, dim, query, n_query, train, n_train, cap, 2, &a);
-  if (st) return st;
-  launch_match_filter(c->stream, a, ratio, d_matches, d_counts);
-  HIPCHK(c, hipGetLastError());
-  return UWT_OK;
-}
-
-// The device-input form: both sets and their counts are in device memory and are read in place.  The counts are unknown here, so the
-// row bound, the tiles and the splits come from cap; the kernels read counts that k_match_counts has confined to 0..cap.
-int match_descriptors_device_enqueue(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, const void* d_query,
-                                     const int32_t* d_n_query, const void* d_train, const int32_t* d_n_train, int cap, float ratio,
-                                     MatchOut* d_matches, int* d_counts) {
-  if (n_pairs < 1 || !d_query || !d_n_query || !d_train || !d_n_train) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null list or n_pairs < 1");
-  if (norm != UWT_NORM_L2 && norm != UWT_NORM_HAMMING) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": unknown norm");
-  if (dim < 1 || (dim & 3)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": dim must be a positive multiple of 4");
-  if (cap < 1) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": cap < 1");
-  if (!std::isfinite(ratio)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": ratio is not finite");
-  const int words = norm == UWT_NORM_L2 ? dim : dim / 4;
-  if (cap > kMatchMaxRows || words > kMatchMaxWords)
-    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS or a row above UWT_MATCH_MAX_ROW_BYTES");
-  const int tiles = (cap + kMatchTile - 1) / kMatchTile;
-  const size_t blocks = (size_t)n_pairs * tiles * 2;
-  const int splits = (int)std::min<size_t>(std::min(kMatchMaxSplits, tiles), (kMatchTargetBlocks + blocks - 1) / blocks);
-  int st = c->match_cnt.reserve(c, c->stream, sizeof(int) * 2 * (size_t)n_pairs);
-  if (!st) st = c->match_part.reserve(c, c->stream, sizeof(Knn2) * cap * (size_t)splits * n_pairs * 2);
+// The device form, both directions: the sets are read in place; the counts are unknown here, so k_match_counts confines them to
+// 0..cap and the core's bounds are cap.  (rows = train_rows = cap >= 1: tiles = train_tiles = ceil(cap / kMatchTile) >= 1, so the
+// core's formula gives the grid and the splits this form always had, and k_knn2 is always launched.)
+int match_device_enqueue(uwt_ctx* c, const char* what, int n_pairs, int norm, int dim, const void* d_query, const int32_t* d_n_query,
+                         const void* d_train, const int32_t* d_n_train, int cap, MatchArgs* a) {
+  if (!d_query || !d_n_query || !d_train || !d_n_train) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null list");
+  int st = match_shape_check(c, what, n_pairs, norm, dim, cap, &a->words);
+  if (!st) st = c->match_cnt.reserve(c, c->stream, sizeof(int) * 2 * (size_t)n_pairs);
   if (st) return st;
   int* d_cnt[2] = {(int*)c->match_cnt.p, (int*)c->match_cnt.p + n_pairs};
-  MatchArgs a;
-  a.desc[0] = (const uint32_t*)d_query; a.desc[1] = (const uint32_t*)d_train; a.cnt[0] = d_cnt[0]; a.cnt[1] = d_cnt[1];
-  a.cap = cap; a.words = words; a.n_pairs = n_pairs; a.splits = splits;
-  a.part = (Knn2*)c->match_part.p;
+  a->desc[0] = (const uint32_t*)d_query; a->desc[1] = (const uint32_t*)d_train; a->cnt[0] = d_cnt[0]; a->cnt[1] = d_cnt[1];
+  a->cap = cap; a->n_pairs = n_pairs;
   launch_match_counts(c->stream, n_pairs, cap, d_n_query, d_n_train, d_cnt[0], d_cnt[1]);
-  launch_knn2(c->stream, norm, a, 2, cap);
-  launch_match_filter(c->stream, a, ratio, d_matches, d_counts);
   HIPCHK(c, hipGetLastError());
-  return UWT_OK;
+  return match_core(c, *a, norm, 2, cap, cap);
 }
 
 }  // namespace
@@ -109,8 +98,8 @@ int uwt_match_descriptors_device_async(uwt_ctx* c, int32_t n_pairs, int32_t norm
                                        int32_t* d_counts_out) {
   if (c) (void)hipSetDevice(c->p.device);
   if (!c || !d_matches_out || !d_counts_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_match_descriptors_device_async: null argument");
-  return match_descriptors_device_enqueue(c, "uwt_match_descriptors_device_async", n_pairs, norm, dim, d_query, d_n_query, d_train, d_n_train,
-                                          cap, ratio, reinterpret_cast<MatchOut*>(d_matches_out), d_counts_out);
+  return match_descriptors_enqueue(c, "uwt_match_descriptors_device_async", MatchIn::device, n_pairs, norm, dim, d_query, d_n_query, d_train,
+                                   d_n_train, cap, ratio, d_matches_out, d_counts_out);
 }
 
 int uwt_knn_match_batch(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32_t dim, const void* query, const int32_t* n_query,
@@ -135,8 +124,8 @@ int uwt_match_descriptors_batch_async(uwt_ctx* c, int32_t n_pairs, int32_t norm,
                                       int32_t* d_counts_out) {
   if (c) (void)hipSetDevice(c->p.device);
   if (!c || !d_matches_out || !d_counts_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_match_descriptors_batch_async: null argument");
-  return match_descriptors_enqueue(c, "uwt_match_descriptors_batch_async", n_pairs, norm, dim, query, n_query, train, n_train, cap, ratio,
-                                   reinterpret_cast<MatchOut*>(d_matches_out), d_counts_out);
+  return match_descriptors_enqueue(c, "uwt_match_descriptors_batch_async", MatchIn::host, n_pairs, norm, dim, query, n_query, train, n_train, cap,
+                                   ratio, d_matches_out, d_counts_out);
 }
 
 int uwt_match_descriptors_batch(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32_t dim, const void* query, const int32_t* n_query,
@@ -152,12 +141,12 @@ int uwt_match_descriptors_batch(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32
   const size_t o_matches = cv.take<MatchOut>((size_t)n_pairs * cap), o_counts = cv.take<int>((size_t)n_pairs);
   int st = c->match_out.reserve(c, c->stream, cv.tight());
   if (st) return st;
-  MatchOut* d_matches = Carve::at<MatchOut>(c->match_out.p, o_matches);
+  uwt_match* d_matches = Carve::at<uwt_match>(c->match_out.p, o_matches);
   int* d_counts = Carve::at<int>(c->match_out.p, o_counts);
-  st = match_descriptors_enqueue(c, what, n_pairs, norm, dim, query, n_query, train, n_train, cap, ratio, d_matches, d_counts);
+  st = match_descriptors_enqueue(c, what, MatchIn::host, n_pairs, norm, dim, query, n_query, train, n_train, cap, ratio, d_matches, d_counts);
   if (st) return st;
   HIPCHK(c, hipMemcpyAsync(counts_out, d_counts, sizeof(int) * n_pairs, hipMemcpyDeviceToHost, c->stream));
-  return rows_to_host(c, cap, n_pairs, {{d_matches, sizeof(MatchOut), counts_out, matches_out}});
+  return rows_to_host(c, cap, n_pairs, {{d_matches, sizeof(uwt_match), counts_out, matches_out}});
 }
 
 // ---- RANSAC inlier selection (RobustMatcher::ransacTest, src/Tracker.cpp:105-169; the contract: include/uwt.h) -------------------
@@ -248,9 +237,21 @@ int ransac_need_rows(uwt_ctx* c, const uwt_ransac_params& rp, const std::vector<
   return UWT_OK;
 }
 
-// Stages the key points, fills the rows of need(k) and enqueues k_ransac_gather + k_ransac on the context stream.  The matches and
-// their counts are in device memory already; ns: the values of N the call
-// can meet.  o: the call's part of the scratch, `bytes` the whole of it (ransac_carve and what the caller carved behind it).
+// the arguments that do not depend on where a call's inputs and results live (after ransac_need_rows: the triangle exists)
+RansacArgs ransac_args(const uwt_ctx* c, const uwt_ransac_params& rp, int n_pairs, int cap, int kp_cap) {
+  RansacArgs a = {};
+  a.need = c->ransac_need;
+  a.cap = cap; a.kp_cap = kp_cap; a.n_pairs = n_pairs;
+  a.max_hypotheses = rp.max_hypotheses;
+  a.seed = rp.seed;
+  a.t2 = rp.distance * rp.distance;
+  a.invalid_status = UWT_ERR_INVALID_ARG;
+  return a;
+}
+
+// The staged forms: grows the scratch to `bytes` (ransac_carve at `o` and what the caller carved behind it), fills the rows of need(k)
+// for `ns`, the values of N the call can meet, and uploads the (x, y) tables and their counts.  The caller adds the matches and the
+// results, which are in device memory, and launches.
 int ransac_enqueue(uwt_ctx* c, int n_pairs, int cap, const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur,
                    const int32_t* n_kp_cur, int kp_cap, const uwt_ransac_params& rp, const std::vector<int>& ns, const RansacScratch& o,
                    size_t bytes, RansacArgs* a) {
@@ -258,17 +259,13 @@ int ransac_enqueue(uwt_ctx* c, int n_pairs, int cap, const float* kp_prev, const
   if (!st) st = ransac_need_rows(c, rp, ns);
   if (st) return st;
   void* b = c->ransac_buf.p;
-  a->kp_prev = Carve::at<float2>(b, o.kp_prev);
-  a->kp_cur = Carve::at<float2>(b, o.kp_cur);
+  *a = ransac_args(c, rp, n_pairs, cap, kp_cap);
+  a->kp_prev = Carve::at<float>(b, o.kp_prev);
+  a->kp_cur = Carve::at<float>(b, o.kp_cur);
+  a->rec_floats = 2;
   a->n_kp_prev = Carve::at<int>(b, o.n_kp_prev);
   a->n_kp_cur = Carve::at<int>(b, o.n_kp_cur);
   a->quads = Carve::at<float4>(b, o.quads);
-  a->need = c->ransac_need;
-  a->cap = cap; a->kp_cap = kp_cap; a->n_pairs = n_pairs;
-  a->max_hypotheses = rp.max_hypotheses;
-  a->seed = rp.seed;
-  a->t2 = rp.distance * rp.distance;
-  a->invalid_status = UWT_ERR_INVALID_ARG;
   const size_t kp_raw = sizeof(float2) * (size_t)kp_cap * n_pairs;
   HIPCHK(c, hipMemcpyAsync((void*)a->kp_prev, kp_prev, kp_raw, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync((void*)a->kp_cur, kp_cur, kp_raw, hipMemcpyHostToDevice, c->stream));
@@ -290,12 +287,10 @@ int uwt_ransac_inliers_batch_async(uwt_ctx* c, int32_t n_pairs, const uwt_match*
   uwt_ransac_params rp;
   int st = ransac_check(c, what, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, params, &rp);
   if (st) return st;
-  std::vector<int> ns;   // the counts are on the device: any N up to cap
-  for (int n = kRansacMinSample; n <= cap; n++) ns.push_back(n);
   RansacArgs a;
   Carve cv(16);
   const RansacScratch o = ransac_carve(cv, n_pairs, cap, kp_cap);
-  st = ransac_enqueue(c, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, rp, ns, o, cv.total(), &a);
+  st = ransac_enqueue(c, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, rp, ransac_all_rows(cap), o, cv.total(), &a);
   if (st) return st;
   a.matches = reinterpret_cast<const MatchOut*>(d_matches);
   a.n_matches = d_n_matches;
@@ -360,42 +355,51 @@ int uwt_ransac_inliers_batch(uwt_ctx* c, int32_t n_pairs, const uwt_match* match
 }  // extern "C"
 
 // ---- what the chained tracking call uses of this unit (declared in uwt_ctx.h) -------------------------------------------------------
+// symMatches of either form: the ratio test of both directions, the symmetry test and the ordered compaction behind the form's k_knn2
+int uwt::match_descriptors_enqueue(uwt_ctx* c, const char* what, MatchIn in, int n_pairs, int norm, int dim, const void* query,
+                                   const int32_t* n_query, const void* train, const int32_t* n_train, int cap, float ratio,
+                                   uwt_match* d_matches, int32_t* d_counts) {
+  if (!std::isfinite(ratio)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": ratio is not finite");
+  MatchArgs a;
+  int st = in == MatchIn::device ? match_device_enqueue(c, what, n_pairs, norm, dim, query, n_query, train, n_train, cap, &a)
+                     : match_enqueue(c, what, n_pairs, norm, dim, query, n_query, train, n_train, cap, 2, &a);
+  if (st) return st;
+  launch_match_filter(c->stream, a, ratio, reinterpret_cast<MatchOut*>(d_matches), d_counts);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
 bool uwt::ransac_params_ok(const uwt_ransac_params& rp) {
   return std::isfinite(rp.distance) && rp.distance >= 0.0 && rp.confidence > 0.0 && rp.confidence <= 1.0 && rp.max_hypotheses >= 1 &&
          rp.max_hypotheses <= UWT_RANSAC_MAX_HYPOTHESES;
 }
 
-// scratch: [(x, y, x', y') of every match | the inlier mask]; need(k) for every N up to cap, as in uwt_ransac_inliers_batch_async
+// The key points are the caller's uwt_keypoint records, read in place, kp_cap = cap; scratch: [(x, y, x', y') of every match | the
+// inlier mask]; need(k) for every N up to cap, as in uwt_ransac_inliers_batch_async
 int uwt::ransac_device_enqueue(uwt_ctx* c, int n_pairs, int cap, const uwt_ransac_params& rp, const uwt_match* d_matches,
                                const int32_t* d_n_matches, const uwt_keypoint* d_kp_prev, const int32_t* d_n_kp_prev,
                                const uwt_keypoint* d_kp_cur, const int32_t* d_n_kp_cur, uwt_match* d_good, int32_t* d_counts,
                                uwt_ransac_info* d_info) {
-  std::vector<int> ns;
-  for (int n = kRansacMinSample; n <= cap; n++) ns.push_back(n);
   Carve cv(16);
   const size_t o_quads = cv.take<float4>((size_t)cap * n_pairs), o_mask = cv.take<uint8_t>((size_t)cap * n_pairs);
   int st = c->ransac_buf.reserve(c, c->stream, cv.total());
-  if (!st) st = ransac_need_rows(c, rp, ns);
+  if (!st) st = ransac_need_rows(c, rp, ransac_all_rows(cap));
   if (st) return st;
-  RansacArgs a;
-  a.matches = reinterpret_cast<const MatchOut*>(d_matches);
-  a.n_matches = d_n_matches;
-  a.kp_prev = a.kp_cur = nullptr;
+  RansacArgs a = ransac_args(c, rp, n_pairs, cap, cap);
+  static_assert(sizeof(uwt_keypoint) == 8 * sizeof(float), "uwt_keypoint: eight 32-bit fields, (x, y) first");
+  a.kp_prev = reinterpret_cast<const float*>(d_kp_prev);
+  a.kp_cur = reinterpret_cast<const float*>(d_kp_cur);
+  a.rec_floats = 8;
   a.n_kp_prev = d_n_kp_prev;
   a.n_kp_cur = d_n_kp_cur;
+  a.matches = reinterpret_cast<const MatchOut*>(d_matches);
+  a.n_matches = d_n_matches;
   a.quads = Carve::at<float4>(c->ransac_buf.p, o_quads);
-  a.need = c->ransac_need;
-  a.cap = cap; a.kp_cap = cap; a.n_pairs = n_pairs;
-  a.max_hypotheses = rp.max_hypotheses;
-  a.seed = rp.seed;
-  a.t2 = rp.distance * rp.distance;
-  a.invalid_status = UWT_ERR_INVALID_ARG;
   a.mask = Carve::at<uint8_t>(c->ransac_buf.p, o_mask);
   a.good = reinterpret_cast<MatchOut*>(d_good);
   a.counts = d_counts;
   a.info = reinterpret_cast<RansacInfo*>(d_info);
-  static_assert(sizeof(uwt_keypoint) == 8 * sizeof(float), "uwt_keypoint: eight 32-bit fields, (x, y) first");
-  launch_ransac_records(c->stream, a, reinterpret_cast<const float*>(d_kp_prev), reinterpret_cast<const float*>(d_kp_cur), 8, cap);
+  launch_ransac(c->stream, a, cap);
   HIPCHK(c, hipGetLastError());
   return UWT_OK;
 }

@@ -95,26 +95,46 @@ int surf_begin_chunk(uwt_ctx* c, const uwt_surf_params& sp, const int32_t* slots
   return UWT_OK;
 }
 
-// Detection (kp_in null) or the caller's key points, then orientation and descriptors, for n_frames frames in chunks.  The results
-// of a chunk are in its scratch; `deliver` takes them (first frame of the chunk, the chunk's arguments) before the next chunk runs.
-int surf_run(uwt_ctx* c, const uwt_surf_params& sp, int n_frames, const int32_t* slots, int cap, const uwt_keypoint* kp_in,
-             const int32_t* n_in, bool want_desc, const std::function<int(int, const SurfArgs&)>& deliver) {
+// where a run's key points come from: nothing set, every frame is detected; else one of the two groups (kp_in wins if both are set)
+struct SurfSource {
+  const uwt_keypoint* kp_in = nullptr;   // the caller's lists in host memory (n_frames x cap): described as they are, no detection
+  const int32_t* n_in = nullptr;         // their counts
+  // the tracking call (n_frames = 2 n_pairs), a path per previous frame decided on the device: surf_track_enqueue's arguments (uwt_ctx.h)
+  const int* d_path = nullptr;
+  int n_pairs = 0;
+  const uwt_keypoint* d_prev_kp = nullptr;
+  const int32_t* d_n_prev = nullptr;
+};
+
+// Key points from `src`, then orientation and descriptors, for n_frames frames in chunks.  The results of a chunk are in its
+// scratch; `deliver` takes them (first frame of the chunk, the chunk's arguments) before the next chunk runs.  With device paths a
+// chunk's extra scratch holds the frames' modes: detection runs under them (the blocks of a frame on another path return at once),
+// k_surf_take_provided has put the provided records and counts where detection would have, and describe, sized by cap, serves both.
+int surf_run(uwt_ctx* c, const uwt_surf_params& sp, int n_frames, const int32_t* slots, int cap, const SurfSource& src, bool want_desc,
+             const std::function<int(int, const SurfArgs&)>& deliver) {
   int st = compute_begin_pairs(c, n_frames, slots, slots);
   if (st) return st;
-  const size_t raw_cap = kp_in ? 0 : surf_raw_bound(c->p.width, c->p.height, sp.n_octaves, sp.n_octave_layers + 2);
+  const size_t raw_cap = src.kp_in ? 0 : surf_raw_bound(c->p.width, c->p.height, sp.n_octaves, sp.n_octave_layers + 2);
   const int chunk = surf_chunk_frames(c, n_frames, raw_cap, cap);
   for (int f0 = 0; f0 < n_frames; f0 += chunk) {
     const int nf = std::min(chunk, n_frames - f0);
     SurfArgs a;
-    st = surf_begin_chunk(c, sp, slots + f0, nf, raw_cap, cap, 0, &a, nullptr);
+    unsigned char* x = nullptr;
+    st = surf_begin_chunk(c, sp, slots + f0, nf, raw_cap, cap, src.d_path ? sizeof(int) * (size_t)nf : 0, &a, &x);
     if (st) return st;
     int rows = cap;
-    if (kp_in) {
+    if (src.kp_in) {
       rows = 0;
-      for (int f = 0; f < nf; f++) rows = std::max(rows, n_in[f0 + f]);
-      HIPCHK(c, hipMemcpyAsync(a.counts, n_in + f0, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(a.kp, kp_in + (size_t)f0 * cap, sizeof(SurfKeypoint) * (size_t)cap * nf, hipMemcpyHostToDevice, c->stream));
+      for (int f = 0; f < nf; f++) rows = std::max(rows, src.n_in[f0 + f]);
+      HIPCHK(c, hipMemcpyAsync(a.counts, src.n_in + f0, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(a.kp, src.kp_in + (size_t)f0 * cap, sizeof(SurfKeypoint) * (size_t)cap * nf, hipMemcpyHostToDevice, c->stream));
     } else {
+      if (src.d_path) {
+        int* mode = reinterpret_cast<int*>(x);
+        a.mode = mode;
+        launch_surf_take_provided(c->stream, a, f0, src.n_pairs, src.d_path, reinterpret_cast<const SurfKeypoint*>(src.d_prev_kp),
+                                  src.d_n_prev, mode);
+      }
       HIPCHK(c, hipMemsetAsync(a.raw_count, 0, sizeof(int) * (size_t)nf, c->stream));
       launch_surf_detect(c->stream, a);
     }
@@ -124,6 +144,15 @@ int surf_run(uwt_ctx* c, const uwt_surf_params& sp, int n_frames, const int32_t*
     st = deliver(f0, a);
     if (st) return st;
   }
+  return UWT_OK;
+}
+
+// the chunk's results to the caller's device arrays, every row of the chunk (d_desc is not written when the chunk has no descriptors)
+int surf_deliver_device(uwt_ctx* c, int f0, const SurfArgs& a, uwt_keypoint* d_kp, float* d_desc, int32_t* d_counts) {
+  const size_t recs = (size_t)a.n_frames * a.cap, g0 = (size_t)f0 * a.cap;
+  HIPCHK(c, hipMemcpyAsync(d_counts + f0, a.counts, sizeof(int) * (size_t)a.n_frames, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_kp + g0, a.kp, sizeof(SurfKeypoint) * recs, hipMemcpyDeviceToDevice, c->stream));
+  if (a.desc) HIPCHK(c, hipMemcpyAsync(d_desc + g0 * 64, a.desc, sizeof(float) * 64 * recs, hipMemcpyDeviceToDevice, c->stream));
   return UWT_OK;
 }
 
@@ -149,7 +178,7 @@ int uwt_surf_detect_describe_batch(uwt_ctx* c, int32_t n_frames, const int32_t* 
   uwt_surf_params sp;
   int st = surf_check(c, what, n_frames, slots, cap, params, &sp);
   if (st) return st;
-  return surf_run(c, sp, n_frames, slots, cap, nullptr, nullptr, desc_out != nullptr,
+  return surf_run(c, sp, n_frames, slots, cap, SurfSource(), desc_out != nullptr,
                   [&](int f0, const SurfArgs& a) { return surf_deliver_host(c, f0, a, kp_out, desc_out, counts_out); });
 }
 
@@ -161,13 +190,8 @@ int uwt_surf_detect_describe_batch_async(uwt_ctx* c, int32_t n_frames, const int
   uwt_surf_params sp;
   int st = surf_check(c, what, n_frames, slots, cap, params, &sp);
   if (st) return st;
-  st = surf_run(c, sp, n_frames, slots, cap, nullptr, nullptr, d_desc_out != nullptr, [&](int f0, const SurfArgs& a) {
-    const size_t recs = (size_t)a.n_frames * a.cap, g0 = (size_t)f0 * a.cap;
-    HIPCHK(c, hipMemcpyAsync(d_counts_out + f0, a.counts, sizeof(int) * (size_t)a.n_frames, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_kp_out + g0, a.kp, sizeof(SurfKeypoint) * recs, hipMemcpyDeviceToDevice, c->stream));
-    if (a.desc) HIPCHK(c, hipMemcpyAsync(d_desc_out + g0 * 64, a.desc, sizeof(float) * 64 * recs, hipMemcpyDeviceToDevice, c->stream));
-    return (int)UWT_OK;
-  });
+  st = surf_run(c, sp, n_frames, slots, cap, SurfSource(), d_desc_out != nullptr,
+                [&](int f0, const SurfArgs& a) { return surf_deliver_device(c, f0, a, d_kp_out, d_desc_out, d_counts_out); });
   if (st) return st;
   return compute_end(c, c->dep_first, c->dep_n);
 }
@@ -184,11 +208,11 @@ int uwt_surf_describe_batch(uwt_ctx* c, int32_t n_frames, const int32_t* slots, 
     if (n_in[f] < 0 || n_in[f] > cap) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key-point count outside 0..cap");
     const uwt_keypoint* k = keypoints_in + (size_t)f * cap;
     for (int i = 0; i < n_in[f]; i++)
-      if (!(std::fabs(k[i].x) <= 1e6f && std::fabs(k[i].y) <= 1e6f && k[i].size > 0.f && k[i].size <= 4096.f))
+      if (!surf_keypoint_ok(k[i].x, k[i].y, k[i].size))
         return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key point outside |x|, |y| <= 1e6, 0 < size <= 4096");
   }
   // the device keeps every row of a chunk; only the rows below a frame's count come back
-  return surf_run(c, sp, n_frames, slots, cap, keypoints_in, n_in, true,
+  return surf_run(c, sp, n_frames, slots, cap, SurfSource{keypoints_in, n_in}, true,
                   [&](int f0, const SurfArgs& a) { return surf_deliver_host(c, f0, a, kp_out, desc_out, nullptr); });
 }
 
@@ -255,34 +279,9 @@ int uwt::surf_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* s
   return UWT_OK;
 }
 
-
-// The tracking call's SURF: surf_run's chunks with the path of every frame decided on the device.  A chunk's extra scratch holds the
-// frames' modes; detection runs under them (the blocks of a frame on another path return at once), k_surf_take_provided has put the
-// provided records and counts where detection would have put its own, and the describe launch, sized by cap, serves both.
+// The tracking call's SURF: the path of every previous frame decided on the device, delivered as the asynchronous call delivers.
 int uwt::surf_track_enqueue(uwt_ctx* c, const uwt_surf_params& sp, int n_pairs, const int32_t* slots, int cap, const int* d_path,
                             const uwt_keypoint* d_prev_kp, const int32_t* d_n_prev, uwt_keypoint* d_kp, float* d_desc, int* d_counts) {
-  const int n_frames = 2 * n_pairs;
-  int st = compute_begin_pairs(c, n_frames, slots, slots);
-  if (st) return st;
-  const size_t raw_cap = surf_raw_bound(c->p.width, c->p.height, sp.n_octaves, sp.n_octave_layers + 2);
-  const int chunk = surf_chunk_frames(c, n_frames, raw_cap, cap);
-  for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-    const int nf = std::min(chunk, n_frames - f0);
-    SurfArgs a;
-    unsigned char* x = nullptr;
-    st = surf_begin_chunk(c, sp, slots + f0, nf, raw_cap, cap, sizeof(int) * (size_t)nf, &a, &x);
-    if (st) return st;
-    int* mode = reinterpret_cast<int*>(x);
-    a.mode = mode;
-    launch_surf_take_provided(c->stream, a, f0, n_pairs, d_path, reinterpret_cast<const SurfKeypoint*>(d_prev_kp), d_n_prev, mode);
-    HIPCHK(c, hipMemsetAsync(a.raw_count, 0, sizeof(int) * (size_t)nf, c->stream));
-    launch_surf_detect(c->stream, a);
-    launch_surf_describe(c->stream, a, cap);
-    HIPCHK(c, hipGetLastError());
-    const size_t recs = (size_t)nf * cap, g0 = (size_t)f0 * cap;
-    HIPCHK(c, hipMemcpyAsync(d_counts + f0, a.counts, sizeof(int) * (size_t)nf, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_kp + g0, a.kp, sizeof(SurfKeypoint) * recs, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_desc + g0 * 64, a.desc, sizeof(float) * 64 * recs, hipMemcpyDeviceToDevice, c->stream));
-  }
-  return UWT_OK;
+  return surf_run(c, sp, 2 * n_pairs, slots, cap, SurfSource{nullptr, nullptr, d_path, n_pairs, d_prev_kp, d_n_prev}, true,
+                  [&](int f0, const SurfArgs& a) { return surf_deliver_device(c, f0, a, d_kp, d_desc, d_counts); });
 }

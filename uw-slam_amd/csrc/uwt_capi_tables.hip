@@ -1,6 +1,7 @@
 // uwt_capi_tables.hip — host side of libuwt_hip.so: alignment over point tables — the caller's tables, the candidate and patch
 // producers, and the batch calls that build the tables on the device and evaluate them there.
 #include "uwt_ctx.h"
+#include "uwt_track.h"
 
 extern "C" {
 
@@ -89,7 +90,7 @@ namespace {
 int check_keypoints(uwt_ctx* c, const char* what, const float* kp, int n) {
   const float w = (float)c->lv[0].gw, h = (float)c->lv[0].gh;
   for (int i = 0; i < std::min(n, kPatchMaxKeypoints); i++)
-    if (!(kp[2 * i] >= 0.f && kp[2 * i] < w && kp[2 * i + 1] >= 0.f && kp[2 * i + 1] < h))
+    if (!inside_level0(kp[2 * i], kp[2 * i + 1], w, h))
       return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key point outside the image");
   return UWT_OK;
 }

@@ -93,8 +93,8 @@ int tracking_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* r
   st = surf_track_enqueue(c, tp.surf, n_pairs, slots.data(), cap, d_path, io.d_prev_kp, io.d_n_prev, d_kp, d_desc, d_counts);
   if (st) return st;
   // 3. symMatches
-  st = uwt_match_descriptors_device_async(c, n_pairs, UWT_NORM_L2, 64, d_desc, d_counts, d_desc + side * 64, d_counts + n_pairs, cap, tp.ratio,
-                                          d_sym, d_n_sym);
+  st = match_descriptors_enqueue(c, what, MatchIn::device, n_pairs, UWT_NORM_L2, 64, d_desc, d_counts, d_desc + side * 64, d_counts + n_pairs, cap,
+                                 tp.ratio, d_sym, d_n_sym);
   if (st) return st;
   // 4. goodMatches
   st = ransac_device_enqueue(c, n_pairs, cap, tp.ransac, d_sym, d_n_sym, d_kp, d_counts, d_kp + side, d_counts + n_pairs, io.d_good,

@@ -221,15 +221,21 @@ int rows_to_host(uwt_ctx* c, int cap, int n_items, std::initializer_list<RowSet>
 int counted_rows_to_host(uwt_ctx* c, const float4* d_rows, size_t stride, const int* d_counts, int n_items, int cap, float* pts_out,
                          int32_t* counts_out);
 
-// ---- the stages of the chained tracking call (uwt_capi_tracking.hip), each in its stage's unit ---------------------------------
+// ---- the stages of the chained tracking call (uwt_capi_tracking.hip): each stage's device-input form, in the stage's unit -------
 // the checks of a SURF call (uwt_capi_surf.hip); *sp: the parameters in force
 int surf_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_surf_params* params,
                uwt_surf_params* sp);
 // SURF for the 2 x n_pairs frames of a tracking call, job j < n_pairs the previous frame of pair j under d_path[j] (kSurfDetect /
-// kSurfProvided at d_prev_kp, d_n_prev / kSurfNone), the others the current frames, detected: in chunks, each chunk's rows delivered
-// to d_kp (2 n_pairs x cap records), d_desc (x 64 floats) and d_counts (2 n_pairs) on the context stream.  slots: the 2 n_pairs slots.
+// kSurfProvided at d_prev_kp, d_n_prev / kSurfNone), the others the current frames, detected: the chunk loop of every SURF call, each
+// chunk's rows delivered to d_kp (2 n_pairs x cap records), d_desc (x 64 floats) and d_counts (2 n_pairs).  slots: the 2 n_pairs slots.
 int surf_track_enqueue(uwt_ctx* c, const uwt_surf_params& sp, int n_pairs, const int32_t* slots, int cap, const int* d_path,
                        const uwt_keypoint* d_prev_kp, const int32_t* d_n_prev, uwt_keypoint* d_kp, float* d_desc, int* d_counts);
+// symMatches: a matching call's checks, k_knn2 both ways and k_match_filter.  MatchIn::device: the sets and counts are device memory,
+// read in place, a count outside 0..cap taken as 0 (uwt_match_descriptors_device_async); host: host memory (uwt_match_descriptors_batch*)
+enum class MatchIn { host, device };
+int match_descriptors_enqueue(uwt_ctx* c, const char* what, MatchIn in, int n_pairs, int norm, int dim, const void* query,
+                              const int32_t* n_query, const void* train, const int32_t* n_train, int cap, float ratio, uwt_match* d_matches,
+                              int32_t* d_counts);
 // the range check of uwt_ransac_params
 bool ransac_params_ok(const uwt_ransac_params& rp);
 // ransacTest with every input in device memory: the matches and their counts, both key-point sets as n_pairs x cap uwt_keypoint

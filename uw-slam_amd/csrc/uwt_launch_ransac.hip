@@ -1,4 +1,4 @@
-// uwt_launch_ransac.hip — the launches of the RANSAC inlier selection: k_ransac_gather, k_ransac_gather_records, k_ransac.
+// uwt_launch_ransac.hip — the launches of the RANSAC inlier selection: k_ransac_gather, k_ransac.
 #include "uwt_ransac_kernels.h"
 
 namespace uwt {
@@ -6,14 +6,6 @@ namespace uwt {
 void launch_ransac(hipStream_t s, const RansacArgs& a, int rows) {
   const int chunks = (rows + 255) / 256;
   if (chunks > 0) hipLaunchKernelGGL(k_ransac_gather, dim3((unsigned)((size_t)a.n_pairs * chunks)), dim3(256), 0, s, a, chunks);
-  hipLaunchKernelGGL(k_ransac, dim3(a.n_pairs), dim3(kRansacBlock), 0, s, a);
-}
-
-void launch_ransac_records(hipStream_t s, const RansacArgs& a, const float* rec_prev, const float* rec_cur, int rec_floats, int rows) {
-  const int chunks = (rows + 255) / 256;
-  if (chunks > 0)
-    hipLaunchKernelGGL(k_ransac_gather_records, dim3((unsigned)((size_t)a.n_pairs * chunks)), dim3(256), 0, s, a, rec_prev, rec_cur,
-                       rec_floats, chunks);
   hipLaunchKernelGGL(k_ransac, dim3(a.n_pairs), dim3(kRansacBlock), 0, s, a);
 }
 

@@ -34,8 +34,9 @@ __device__ __forceinline__ bool ransac_match_ok(const MatchOut m, int nq, int nt
 }
 
 // grid: x = pair * chunks + chunk of 256 matches.  The (x, y, x', y') of every match in a table of its own: k_ransac reads it
-// at addresses that are the same for every lane (scalar loads).  A match with an index outside its key points reads nothing and
-// leaves zeros; k_ransac reports the pair.
+// at addresses that are the same for every lane (scalar loads).  Both key-point sets are records of a.rec_floats floats that begin
+// with (x, y): the staged tables (2) or uwt_keypoint (8).  A match with an index outside its key points reads nothing and leaves
+// zeros; k_ransac reports the pair.
 static __global__ __launch_bounds__(256) void k_ransac_gather(RansacArgs a, int chunks) {
   const int p = blockIdx.x / chunks, i = (blockIdx.x - p * chunks) * 256 + threadIdx.x;
   const int n = a.n_matches[p];
@@ -43,23 +44,8 @@ static __global__ __launch_bounds__(256) void k_ransac_gather(RansacArgs a, int 
   const MatchOut m = a.matches[(size_t)p * a.cap + i];
   float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
   if (ransac_match_ok(m, a.n_kp_prev[p], a.n_kp_cur[p], a.kp_cap)) {
-    const float2 u = a.kp_prev[(size_t)p * a.kp_cap + m.query_idx], v = a.kp_cur[(size_t)p * a.kp_cap + m.train_idx];
-    q = make_float4(u.x, u.y, v.x, v.y);
-  }
-  a.quads[(size_t)p * a.cap + i] = q;
-}
-
-// The same with both key-point sets as records of rec_floats floats that begin with (x, y) (uwt_keypoint), n_pairs x kp_cap of them.
-static __global__ __launch_bounds__(256) void k_ransac_gather_records(RansacArgs a, const float* __restrict__ rec_prev,
-                                                                      const float* __restrict__ rec_cur, int rec_floats, int chunks) {
-  const int p = blockIdx.x / chunks, i = (blockIdx.x - p * chunks) * 256 + threadIdx.x;
-  const int n = a.n_matches[p];
-  if (n < 0 || n > a.cap || i >= n) return;
-  const MatchOut m = a.matches[(size_t)p * a.cap + i];
-  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ransac_match_ok(m, a.n_kp_prev[p], a.n_kp_cur[p], a.kp_cap)) {
-    const float* u = rec_prev + ((size_t)p * a.kp_cap + m.query_idx) * rec_floats;
-    const float* v = rec_cur + ((size_t)p * a.kp_cap + m.train_idx) * rec_floats;
+    const float* u = a.kp_prev + ((size_t)p * a.kp_cap + m.query_idx) * a.rec_floats;
+    const float* v = a.kp_cur + ((size_t)p * a.kp_cap + m.train_idx) * a.rec_floats;
     q = make_float4(u[0], u[1], v[0], v[1]);
   }
   a.quads[(size_t)p * a.cap + i] = q;

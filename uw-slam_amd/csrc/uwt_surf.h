@@ -18,6 +18,12 @@ constexpr int kSurfDetect = 0, kSurfProvided = 1, kSurfNone = 2;   // SurfArgs::
 
 struct SurfKeypoint { float x, y, size, response, dir_x, dir_y; int octave, laplacian; };
 
+// the range of a key point a caller provides (host lists: uwt_surf_describe_batch; device lists: k_track_predicate): |x|, |y| <= 1e6,
+// 0 < size <= 4096.  Comparisons only, so a NaN fails.
+__host__ __device__ inline bool surf_keypoint_ok(float x, float y, float size) {
+  return fabsf(x) <= 1e6f && fabsf(y) <= 1e6f && size > 0.f && size <= 4096.f;
+}
+
 constexpr int surf_filter_size(int octave, int layer) { return (9 + 6 * layer) << octave; }
 
 // an upper bound on a frame's candidates: a strict maximum of its 3 x 3 has no candidate beside it, so a middle layer holds at most

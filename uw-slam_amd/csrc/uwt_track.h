@@ -11,12 +11,16 @@
 
 namespace uwt {
 
+// a key point (x, y) lies inside level 0 (w x h): what the live call asks of its key points (host lists: check_keypoints; the chain:
+// k_good_keypoints).  Comparisons only, so a NaN fails.
+__host__ __device__ inline bool inside_level0(float x, float y, float w, float h) { return x >= 0.f && x < w && y >= 0.f && y < h; }
+
 struct TrackInfo { int status, used_provided, n_kp_prev, n_kp_cur, n_symmetric, n_matches, best_hypothesis, hypotheses_run; };
 
 // `usekeypoints` per pair, on the device: path[p] = kSurfProvided when the previous frame is described at its provided key points
 // (prev_kp != null, n_prev[p] >= 1 and >= min_matches), kSurfDetect when it is detected, kSurfNone — and refused[p] = 1 — when the
-// provided list is unusable: a count outside 0..cap, or a record of a used list that is not finite or outside |x|, |y| <= 1e6,
-// 0 < size <= 4096 (the host checks of uwt_surf_describe_batch).  One block per pair.
+// provided list is unusable: a count outside 0..cap, or a record of a used list that fails surf_keypoint_ok (the host checks of
+// uwt_surf_describe_batch).  One block per pair.
 void launch_track_predicate(hipStream_t s, int n_pairs, const SurfKeypoint* prev_kp, const int* n_prev, int cap, int min_matches,
                             int* path, int* refused);
 // the counts of a device-input matching call as the kernels may use them: a count outside 0..cap is 0

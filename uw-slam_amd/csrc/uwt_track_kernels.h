@@ -19,10 +19,7 @@ static __global__ __launch_bounds__(256) void k_track_predicate(int n_pairs, con
   const bool use = !bad && prev_kp && n >= 1 && n >= min_matches;
   if (use) {
     const SurfKeypoint* k = prev_kp + (size_t)p * cap;
-    for (int i = tid; i < n; i += 256) {
-      const float x = k[i].x, y = k[i].y, sz = k[i].size;   // (a NaN fails every comparison)
-      bad |= (fabsf(x) <= 1e6f && fabsf(y) <= 1e6f && sz > 0.f && sz <= 4096.f) ? 0 : 1;
-    }
+    for (int i = tid; i < n; i += 256) bad |= surf_keypoint_ok(k[i].x, k[i].y, k[i].size) ? 0 : 1;
   }
   bad = __syncthreads_or(bad);
   if (tid == 0) {
@@ -53,8 +50,7 @@ static __global__ __launch_bounds__(256) void k_good_keypoints(GoodKeypointsArgs
   int out = 0;
   for (int i = tid; i < nf; i += 256) {   // the check the host makes on the live call's key points (check_keypoints)
     const SurfKeypoint* k = Q + good[i].query_idx;
-    const float x = k->x, y = k->y;
-    out |= (x >= 0.f && x < a.w && y >= 0.f && y < a.h) ? 0 : 1;
+    out |= inside_level0(k->x, k->y, a.w, a.h) ? 0 : 1;
   }
   out = __syncthreads_or(out);
   if (out) {
