@@ -612,18 +612,21 @@ __device__ __forceinline__ float rigid_row_f64(const double* Td, double Xd, doub
   return (float)__builtin_fma(Td[0], Xd, t);
 }
 
+// The ray of a pixel position along one axis: the unprojection at depth 1.  A function of the column (or the row) and the level alone.
 template <int AR, typename F>
-__device__ __forceinline__ void warp_point(const LevelK& L, const WarpK& K, F xf, F yf, F z, F& u, F& v, F& zp, F& iz) {
-  F X, Y, xp, yp;
+__device__ __forceinline__ F pixel_ray(F p, float c, float inv, float beta) {
   if constexpr (AR == kArithLegacy) {
-    X = (xf - bc<F>(L.cx)) * bc<F>(L.invfx);
-    Y = (yf - bc<F>(L.cy)) * bc<F>(L.invfy);
+    return (p - bc<F>(c)) * bc<F>(inv);
   } else {   // convertTo(alpha = invfx, beta = -cx * invfx) -> cvtScale32f: x * alpha + beta, two f32 operations
-    X = xf * bc<F>(L.invfx);
-    X = X + bc<F>(L.bx);
-    Y = yf * bc<F>(L.invfy);
-    Y = Y + bc<F>(L.by);
+    F r = p * bc<F>(inv);
+    return r + bc<F>(beta);
   }
+}
+
+// warp_point from the pixel's rays X0 = pixel_ray(x), Y0 = pixel_ray(y) on
+template <int AR, typename F>
+__device__ __forceinline__ void warp_ray(const LevelK& L, const WarpK& K, F X, F Y, F z, F& u, F& v, F& zp, F& iz) {
+  F xp, yp;
   X = X * z;
   Y = Y * z;
   if constexpr (AR == kArithLegacy) {
@@ -656,6 +659,11 @@ __device__ __forceinline__ void warp_point(const LevelK& L, const WarpK& K, F xf
   v = div_by(v, zp, r);
   v = v + bc<F>(L.cy);
   iz = r;  // inv_z2 = 1 / z2 (src/Tracker.cpp:447): the refined reciprocal IS the correctly rounded quotient (see refined_rcp)
+}
+
+template <int AR, typename F>
+__device__ __forceinline__ void warp_point(const LevelK& L, const WarpK& K, F xf, F yf, F z, F& u, F& v, F& zp, F& iz) {
+  warp_ray<AR, F>(L, K, pixel_ray<AR, F>(xf, L.cx, L.invfx, L.bx), pixel_ray<AR, F>(yf, L.cy, L.invfy, L.by), z, u, v, zp, iz);
 }
 
 // C round() (half away from zero) for the x >= 0 this path produces: v_cvt_rpi_i32_f32 = floor(x + 0.5) evaluated
@@ -692,12 +700,14 @@ constexpr int kFcmpOGT = 2, kFcmpOLT = 4, kFcmpUGE = 11, kFcmpUNE = 14, kIcmpULT
 __device__ __forceinline__ bool lane_bit(unsigned long long mask) { return (mask >> (threadIdx.x & 63u)) & 1ull; }
 
 // 1a: warp and validity masks; x2, y2, iz come back raw (possibly NaN / out of range where the mask is clear)
-template <int AR, typename F>
+// (RAYS: xf, yf are the pixel's rays, not its position — warp_ray)
+template <int AR, typename F, bool RAYS = false>
 __device__ __forceinline__ void pixel_warp_raw(const LevelK& L, const WarpK& K, F xf, F yf, F z,
                                                const unsigned long long* okin_mask, F& x2, F& y2, F& iz,
                                                unsigned long long* okm) {
   F z2;
-  warp_point<AR, F>(L, K, xf, yf, z, x2, y2, z2, iz);
+  if constexpr (RAYS) warp_ray<AR, F>(L, K, xf, yf, z, x2, y2, z2, iz);
+  else warp_point<AR, F>(L, K, xf, yf, z, x2, y2, z2, iz);
 #pragma unroll
   for (int c = 0; c < lanes<F>::n; c++) {
     const float uc = get(x2, c), vc = get(y2, c);
@@ -1299,6 +1309,7 @@ struct CoreOverride {
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef int i4v __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) double lds_f64;   // a double in LDS, addressed by its 32-bit LDS address
 // reference planes of one group of VEC pixels, as loaded (one vector load per plane)
 template <int VEC>
 struct RefGroup {
@@ -1398,6 +1409,33 @@ __device__ __forceinline__ void wait_planes_typed(RefGroup<4>& r) {
   else asm volatile("s_waitcnt vmcnt(0)" : "+v"(w), "+v"(r.gx4), "+v"(r.gy4));
 }
 
+// Pixel rays from block tables (the TYPED forms).  pixel_ray of a column and of a row are the same two floats for every pair and every
+// evaluation of a level, yet the loop re-derived them per pixel: 8 vector instructions per four pixels, plus the float walk that fed
+// them.  A block fills X0[0 .. pitch) and Y0[row - row_begin] for the rows its walk can reach — with pixel_ray itself, so the same
+// floats — into the bytes of the block reduction's image, which are idle until the loop ends (the arrangement of the weight table of
+// the weighted path).  A step then reads its group's four X0 (16 bytes) and its row's Y0 beside the rigid matrix and walks two byte
+// offsets into the tables instead of two float coordinates: same pixels in the same order, every sum sees the same additions.
+// Rows: a block's lanes start in rows row_begin .. and every lane — the inactive ones included, which run on past the slice and
+// past the level — takes `iters` steps of kBlock groups, so the last position read is group g_begin + iters * kBlock - 1:
+// Y0 is filled from row_begin to that group's row (never past the reduction's image: residual_core clamps the count), and the host
+// takes these forms only where pitch + rows fit (ray_tables_fit, from ray_table_rows_max: every supported size does by far).
+constexpr int kRayTabFloats = kReduceLdsBytes / 4;
+// upper bound on the rows a block of `groups_per_block` (a multiple of kBlock) groups of four reaches from the row its slice begins in
+__host__ __device__ inline int ray_table_rows_max(int pitch, int groups_per_block) {
+  const int steps = (groups_per_block + kBlock - 1) / kBlock;
+  // the span's rows, begun anywhere in its first one, and one more: the row an inactive lane past the level may read where the
+  // magic division is no longer exact (see residual_core)
+  return (steps * kBlock * 4 + pitch - 1) / pitch + 2;
+}
+__host__ __device__ inline bool ray_tables_fit(int pitch, int groups_per_block) {
+  return pitch > 0 && (long long)pitch + ray_table_rows_max(pitch, groups_per_block) <= kRayTabFloats;
+}
+template <int AR>
+__device__ __forceinline__ void fill_ray_tables(float* __restrict__ tab, const LevelK& L, uint32_t row_begin, uint32_t rows) {
+  for (uint32_t x = threadIdx.x; x < (uint32_t)L.pitch; x += kBlock) tab[x] = pixel_ray<AR, float>((float)x, L.cx, L.invfx, L.bx);
+  for (uint32_t r = threadIdx.x; r < rows; r += kBlock) tab[(uint32_t)L.pitch + r] = pixel_ray<AR, float>((float)(row_begin + r), L.cy, L.invfy, L.by);
+}
+
 // COMPUTE_ONLY (diagnostic, uwt_profile_enable(ctx, 2)): the same instruction stream with every load of the loop replaced
 // by register arithmetic — results are meaningless, its duration is the kernel's own instruction-issue floor.
 // residual_core evaluates one slice of one pair at `pose`; `lds` (optional) is the caller's buffer for the block reduction.
@@ -1492,7 +1530,11 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
   // forms evaluate the weight per pixel: the general branch of phase 4, whose residual and weight they write out)
   constexpr bool TABLE = WEIGHTS != 0 && SAMPLER == 0 && !DUMP;
   static_assert(!TABLE || EXT_LDS == 0, "the weighted path reduces in its own LDS");
-  __shared__ __attribute__((aligned(16))) unsigned char tlds[TABLE ? kReduceLdsBytes : 16];
+  // TYPED: the planes' 16-bit values arrive as floats (load_group_typed): no conversion on the vector ALU; pixel rays from block
+  // tables in the same bytes (fill_ray_tables; never both: TYPED has no weights)
+  constexpr bool TYPED = (STREAM & kLoadsTyped) != 0;
+  static_assert(!TYPED || EXT_LDS == 0, "the ray tables live in the block's own reduction image");
+  __shared__ __attribute__((aligned(16))) unsigned char tlds[TABLE || TYPED ? kReduceLdsBytes : 16];
   static_assert(!TABLE || kWeightTabBytes <= kReduceLdsBytes, "table fits the reduction image");
   if constexpr (TABLE) {
     fill_weight_table(reinterpret_cast<WeightEntry*>(tlds), WEIGHTS, inv_mad, a.gain);
@@ -1511,8 +1553,6 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
   // are needed last, for the residuals).
   RefGroup<VEC> rg;
   int g = g_begin + (int)threadIdx.x;
-  // TYPED: the planes' 16-bit values arrive as floats (load_group_typed): no conversion on the vector ALU
-  constexpr bool TYPED = (STREAM & kLoadsTyped) != 0;
   constexpr bool NT = (STREAM & kLoadsStream) != 0;
   // (measured on the weighted path and on the general Jacobian form too: no gain there — profiles/r05/EXPERIMENTS.md)
   static_assert(!TYPED || (VEC == 4 && std::is_same<AccT, double>::value && !DUMP && !COMPUTE_ONLY && SAMPLER == 0 && WEIGHTS == 0),
@@ -1536,6 +1576,29 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
   float yf = (float)y0, xf0 = (float)(idx0 - y0 * (uint32_t)L.pitch);
   const uint32_t step_y = __umulhi((uint32_t)(kBlock * VEC), L.magic);
   const float step_yf = (float)step_y, step_xf = (float)((uint32_t)(kBlock * VEC) - step_y * (uint32_t)L.pitch), wf = (float)L.pitch;
+  // TYPED: the same walk over integers — xo, yo: byte offsets of the thread's column in X0 and of its row in Y0 from the tables'
+  // first byte (fill_ray_tables); pe: the group's element index, which the active test and the next request are taken from (no
+  // group number is kept: `g` does not advance in the TYPED loop).  xo stays in [0, 4 pitch - 16] in every lane (one wrap per step
+  // suffices: step_x < pitch).  yo stays inside the rows filled in every lane whose first row the magic division gets right, the
+  // inactive ones included (fill_ray_tables: their last read is the row of group g_begin + iters * kBlock - 1).  The division is
+  // exact for idx * pitch < 2^32, which a context guarantees for the level's ng, not for the up to kBlock * VEC - VEC positions
+  // past it that inactive lanes start at: at a frame right on that limit such a lane's row may come out one high and its (masked,
+  // discarded) read fall one float behind the rows filled — still inside the reduction's image: ray_table_rows_max counts that row.
+  // (All of these are dead in the plain forms.)
+  uint32_t xo = 0, yo = 0, pe = idx0;
+  const lds_f64* td_lds = (const lds_f64*)s_td;   // (address-space cast: the matrix's doubles by their LDS address)
+  const uint32_t pitch4 = (uint32_t)L.pitch * 4u, step_yo = step_y * 4u, step_xo = ((uint32_t)(kBlock * VEC) - step_y * (uint32_t)L.pitch) * 4u;
+  const uint32_t pe_end = (uint32_t)g_end * VEC, pe_last = (uint32_t)(n_groups - 1) * VEC;
+  if constexpr (TYPED) {
+    const uint32_t row_begin = __umulhi((uint32_t)g_begin * VEC, L.magic);
+    const uint32_t row_last = __umulhi((uint32_t)(g_begin + iters * kBlock - 1) * VEC, L.magic);
+    // (the host dispatches here only where the tables fit — ray_tables_fit —; the clamp keeps the fill inside the image regardless)
+    const uint32_t rows = min(row_last - row_begin + 1u, (uint32_t)kRayTabFloats - (uint32_t)L.pitch);
+    fill_ray_tables<AR>(reinterpret_cast<float*>(tlds), L, row_begin, rows);
+    __syncthreads();
+    xo = (idx0 - y0 * (uint32_t)L.pitch) * 4u;
+    yo = ((uint32_t)L.pitch + y0 - row_begin) * 4u;
+  }
   // Pixels are processed in units of N adjacent ones (N = 2: the packed-f32 form, see v2f above), all VEC pixels of the
   // group in flight through four phases: warp + validity + gather index, gather, Jacobian, residual + accumulation.
   constexpr int N = (VEC % 2 == 0) ? 2 : 1;
@@ -1544,17 +1607,32 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
   // one step of the loop on the planes in `rg`, which are re-requested in place for the group `ahead` steps on
   // (`nxt`: where the next group's planes are requested — `rg` itself, or the other register set of the TYPED form)
   auto body = [&](RefGroup<VEC>& rg, const int ahead, RefGroup<VEC>& nxt) __attribute__((always_inline)) {
-    const bool active = g < g_end;
-    const unsigned long long active_mask = __builtin_amdgcn_sicmp(g, g_end, kIcmpSLT);
+    const bool active = !TYPED && g < g_end;   // (the dump forms' store guard; never TYPED, where g stands still)
+    const unsigned long long active_mask = TYPED ? __builtin_amdgcn_uicmp(pe, pe_end, kIcmpULT) : __builtin_amdgcn_sicmp(g, g_end, kIcmpSLT);
     constexpr bool TD_READ = TD_LDS;
-    if constexpr (TD_READ) {
+    if constexpr (TD_READ && TYPED) {
+      // the same reads off one address register carried through the loop (opaque at every step: the reads stay inside the loop),
+      // every double at an immediate offset from it.  The form below costs a zero and six address sums per step: s_td lies
+      // behind the reduction's image, beyond the reach of an immediate offset from nothing.
+      asm volatile("" : "+v"(td_lds));
+      const lds_f64* tdp = td_lds;
+#pragma unroll
+      for (int i = 0; i < 12; i++) K.Td[i] = tdp[i];
+    } else if constexpr (TD_READ) {
       unsigned off = 0;
       asm volatile("" : "+v"(off));   // an offset the compiler cannot see through: the reads stay inside the loop
       const double* tdp = reinterpret_cast<const double*>(reinterpret_cast<const unsigned char*>(s_td) + off);
 #pragma unroll
       for (int i = 0; i < 12; i++) K.Td[i] = tdp[i];
     }
-    const uint32_t idx = (uint32_t)min(g, n_groups - 1) * VEC;
+    // TYPED: the rays of the group's four columns and of its row, from the block's tables
+    f4v X0 = (f4v)(0.f);
+    float Y0 = 0.f;
+    if constexpr (TYPED) {
+      X0 = *reinterpret_cast<const f4v*>(tlds + xo);
+      Y0 = *reinterpret_cast<const float*>(tlds + yo);
+    }
+    const uint32_t idx = TYPED ? 0u : (uint32_t)min(g, n_groups - 1) * VEC;   // (where the dump forms store; never TYPED)
     if constexpr (TYPED) wait_planes_typed<DEPTH>(rg);   // this group's planes, requested a step ago, have landed
     uint8_t i1[VEC];
 #pragma unroll
@@ -1573,8 +1651,9 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
 #pragma unroll
     for (int j = 0; j < VEC; j++) colm[j] = active_mask;
     if constexpr (RAGGED) {
-      const unsigned long long m_in = active_mask & __builtin_amdgcn_fcmpf(xf0, (float)L.gw, kFcmpOLT);
-      const unsigned long long m_all = active_mask & __builtin_amdgcn_fcmpf(xf0, (float)(L.gw & ~3), kFcmpOLT);
+      // (TYPED: the column is xo / 4)
+      const unsigned long long m_in = active_mask & (TYPED ? __builtin_amdgcn_uicmp(xo, (uint32_t)L.gw * 4u, kIcmpULT) : __builtin_amdgcn_fcmpf(xf0, (float)L.gw, kFcmpOLT));
+      const unsigned long long m_all = active_mask & (TYPED ? __builtin_amdgcn_uicmp(xo, (uint32_t)(L.gw & ~3) * 4u, kIcmpULT) : __builtin_amdgcn_fcmpf(xf0, (float)(L.gw & ~3), kFcmpOLT));
       const int rem = L.gw & 3;
 #pragma unroll
       for (int j = 0; j < VEC; j++) colm[j] = (VEC == 1 || j < rem) ? m_in : m_all;
@@ -1599,10 +1678,10 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
           if constexpr (!MASKED) okin[c] &= __builtin_amdgcn_sicmp(d, 0, kIcmpSGT);
           put(z, c, dlow[c]);
         }
-        put(xf, c, (float)j);
+        put(xf, c, TYPED ? X0[j] : (float)j);
       }
       if constexpr (DEPTH) z = z * bc<F>(L.zscale);
-      xf = bc<F>(xf0) + xf;
+      if constexpr (!TYPED) xf = bc<F>(xf0) + xf;   // (TYPED: xf, Y0 are the rays — warp_ray)
       if constexpr (MASKED) {
         if constexpr (DEPTH) {
           // The three lower bounds — depth > 0 (:1268), y2 > 0, x2 > 0 (:450) — as ONE compare of their minimum.  A NaN position
@@ -1610,7 +1689,8 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
           // fails the ordered upper-bound compares below, as it fails every compare of the reference's test; -0 and +0 are not
           // greater than 0 either way.
           F z2;
-          warp_point<AR, F>(L, K, xf, bc<F>(yf), z, x2[u], y2[u], z2, iz[u]);
+          if constexpr (TYPED) warp_ray<AR, F>(L, K, xf, bc<F>(Y0), z, x2[u], y2[u], z2, iz[u]);
+          else warp_point<AR, F>(L, K, xf, bc<F>(yf), z, x2[u], y2[u], z2, iz[u]);
 #pragma unroll
           for (int c = 0; c < N; c++) {
             const float uc = get(x2[u], c), vc = get(y2[u], c);
@@ -1620,7 +1700,7 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
                              __builtin_amdgcn_fcmpf(uc, (float)L.iw, kFcmpOLT);
           }
         } else {
-          pixel_warp_raw<AR, F>(L, K, xf, bc<F>(yf), z, okin, x2[u], y2[u], iz[u], &okm[u * N]);
+          pixel_warp_raw<AR, F, TYPED>(L, K, xf, bc<F>(TYPED ? Y0 : yf), z, okin, x2[u], y2[u], iz[u], &okm[u * N]);
         }
 #pragma unroll
         for (int c = 0; c < N; c++) {
@@ -1675,7 +1755,7 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
     // behind the gathers.  The request is unconditional (the index is clamped): inside a branch, the compiler's wait for
     // the gathers would have to assume the branch not taken and count the plane loads in.
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TYPED) load_group_typed<DEPTH, NT>(nxt, TP, (uint32_t)min(g + ahead * kBlock, n_groups - 1) * VEC);
+    if constexpr (TYPED) load_group_typed<DEPTH, NT>(nxt, TP, min(pe + (uint32_t)(ahead * kBlock * VEC), pe_last));   // (the sum: the next step's pe)
     else load_group<VEC, DEPTH, COMPUTE_ONLY, STREAM>(nxt, I1, GX, GY, DP, (uint32_t)min(g + ahead * kBlock, n_groups - 1) * VEC);
     __builtin_amdgcn_sched_barrier(0);
     // TYPED: "the gathers have landed" = all but the plane loads issued behind them have (vmcnt retires in order)
@@ -1863,11 +1943,17 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
     }
     }
     }   // !DIRECT
-    xf0 += step_xf;
-    yf += step_yf;
-    const bool wrap = xf0 >= wf;
-    xf0 -= wrap ? wf : 0.f;
-    yf += wrap ? 1.f : 0.f;
+    if constexpr (TYPED) {
+      const uint32_t t = xo + step_xo;
+      yo += step_yo + (t >= pitch4 ? 4u : 0u);
+      xo = min(t, t - pitch4);   // (unsigned: t - pitch4 wraps to a huge value where t < pitch4)
+    } else {
+      xf0 += step_xf;
+      yf += step_yf;
+      const bool wrap = xf0 >= wf;
+      xf0 -= wrap ? wf : 0.f;
+      yf += wrap ? 1.f : 0.f;
+    }
   };
   if constexpr (TYPED) {
     // Two register sets take turns: while the floats of one are being consumed (the gradients live until the step's Jacobians)
@@ -1879,10 +1965,10 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
     rgB.gx4 = rgB.gy4 = rgB.dp4 = (f4v)(0.f);
     for (int it = 0; it < iters; it += 2) {
       body(rg, 1, rgB);
-      g += kBlock;
+      pe += kBlock * VEC;
       if (it + 1 < iters) {   // block-uniform
         body(rgB, 1, rg);
-        g += kBlock;
+        pe += kBlock * VEC;
       }
     }
     wait_planes_typed<DEPTH>(rg);    // the last step's request (a clamped, unused group) must not land in registers that have moved on
@@ -1899,6 +1985,9 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
   else if constexpr (TABLE) {
     __syncthreads();   // every wave has read its last table entry: the bytes become the reduction's image
     block_reduce_store_at<AccT, true>(tlds, acc, sum_r2, n_valid, out_rec, err, coherent);
+  } else if constexpr (TYPED) {
+    __syncthreads();   // every wave has read its last rays: the bytes become the reduction's image
+    block_reduce_store_at<AccT, false, kBatchPass, double>(tlds, acc, r2d, n_valid, out_rec, err, coherent);
   } else if constexpr (R2D) block_reduce_store<AccT, false, double>(acc, r2d, n_valid, out_rec, err, coherent);
   else block_reduce_store<AccT, GENERAL>(acc, sum_r2, n_valid, out_rec, err, coherent);
   if (a_probe && threadIdx.x == 0) {

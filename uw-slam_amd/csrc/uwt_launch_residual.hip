@@ -81,7 +81,11 @@ void launch_residual_vd(hipStream_t s, const ResidualArgs& a, int n_pairs, bool 
 
 }  // namespace
 
-void launch_residual(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, int n_pairs, bool dump) {
+void launch_residual(hipStream_t s, const LaunchSel& sel, const ResidualArgs& args, int n_pairs, bool dump) {
+  // the typed forms read pixel rays from block tables: a level whose pitch and rows exceed the table space (no supported size)
+  // takes the plain forms
+  ResidualArgs a = args;
+  if (!ray_tables_fit(a.L.pitch, a.groups_per_block)) a.typed_loads = 0;
   const bool unit = (a.zf == 1.0f && a.af == 1.0f);
   const bool co = sel.compute_only && !dump;
   UWT_WITH_AR(sel.arith,
