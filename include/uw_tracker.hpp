@@ -156,6 +156,7 @@ class Frame {
   int n_matches_ = 0;                                    // include/System.h:93
   std::vector<uwt_keypoint> surf_keypoints_;             // the same key points as cv::KeyPoint holds them (size, response, direction,
                                                          // octave): what useProvidedKeypoints describes again in the next call
+  std::vector<uwt_keypoint> orb_keypoints_;              // the same under RobustMatcher(tracker, 1): ORB's records
   std::vector<float> candidatePoints_[PYRAMID_LEVELS];   // N x 4 [x y z w] per level when a sparse producer ran
   int slot_ = -1;                 // device frame slot while bound; -1 again once the slot has gone to another frame
   Tracker* tracker_ = nullptr;    // the tracker that holds the slot
@@ -517,12 +518,16 @@ inline Frame::~Frame() {
 // uwt_ransac_inliers_batch (the contract: include/uwt.h — cv::findFundamentalMat draws from OpenCV's RNG and is not pinned);
 // getGoodKeypoints and the assignment of :247-254 on the host.  Detection and description with cuda::SURF_CUDA (:186-206) are
 // uwt_surf_detect_describe_batch / uwt_surf_describe_batch, SURF under the contract of include/uwt.h:
-// DetectAndTrackFeatures(previous, current, usekeypoints) is the reference's whole method.  The overloads that take the caller's
-// descriptors stay (cuda::ORB is not built; a caller brings ORB descriptors).  A caller with a RANSAC of their own passes its inliers
-// to SetKeypoints instead.
+// DetectAndTrackFeatures(previous, current, usekeypoints) is the reference's whole method.  RobustMatcher(tracker, 1), as
+// RobustMatcher(int detector) of src/Tracker.cpp:38-46, runs cuda::ORB's branch (:210-223) in the same method:
+// uwt_orb_detect_describe_batch / uwt_orb_describe_batch, ORB under the contract of include/uwt.h, matched under Hamming, the full
+// records kept in Frame::orb_keypoints_.  The overloads that take the caller's descriptors stay.  A caller with a RANSAC of their
+// own passes its inliers to SetKeypoints instead.
 class RobustMatcher {
  public:
-  explicit RobustMatcher(Tracker* tracker) : tracker_(tracker) {}
+  explicit RobustMatcher(Tracker* tracker, int detector = 0) : detector_(detector), tracker_(tracker) {
+    if (detector != 0 && detector != 1) throw std::invalid_argument("RobustMatcher: detector is 0 (SURF) or 1 (ORB)");
+  }
 
   // symMatches of one pair (:202-236), ascending queryIdx.  float rows (n x dim, m x dim) are matched under L2 (SURF, :199), byte
   // rows under Hamming (ORB, :221).
@@ -607,6 +612,7 @@ class RobustMatcher {
     const int a = tracker_->bind(_previous_frame), b = tracker_->bind(_current_frame);
     if (!tracker_->bound(_previous_frame) || _previous_frame->slot_ != a)
       throw std::runtime_error("DetectAndTrackFeatures: more frames than slots (max_frames)");
+    if (detector_ == 1) return track_orb(_previous_frame, _current_frame, a, b, usekeypoints);
     uwt_surf_params sp;
     uwt_default_surf_params(&sp);
     sp.hessian_threshold = hessian_threshold_;
@@ -649,8 +655,61 @@ class RobustMatcher {
   int32_t n_octaves_ = 4, n_octave_layers_ = 2;
   bool upright_ = false;
   int32_t surf_cap_ = UWT_MATCH_MAX_ROWS;   // key points of a frame at most: what the matcher takes
+  int detector_ = 0;                   // src/Tracker.cpp:38-46: 0 SURF, 1 ORB
+  int32_t n_features_ = 500, n_levels_ = 8, edge_threshold_ = 31, fast_threshold_ = 20;   // cuda::ORB::create()'s defaults (:212)
+  std::vector<int8_t> orb_pattern_;    // empty: the library's default pattern; else 256 x (x0, y0, x1, y1) (uwt_orb_set_pattern)
 
  private:
+  // :210-223 and on: ORB on both frames — the previous one described at the records it kept when usekeypoints is set and it has
+  // some (:216-218), the current one detected — then the matcher under Hamming, ransacTest and the assignment
+  std::vector<uwt_match> track_orb(Frame* _previous_frame, Frame* _current_frame, int a, int b, bool usekeypoints) {
+    uwt_orb_params op;
+    uwt_default_orb_params(&op);
+    op.n_features = n_features_;
+    op.n_levels = n_levels_;
+    op.edge_threshold = edge_threshold_;
+    op.fast_threshold = fast_threshold_;
+    op.upright = upright_ ? 1 : 0;
+    if (!orb_pattern_.empty() && orb_pattern_.size() != 1024) throw std::invalid_argument("RobustMatcher: orb_pattern_ holds 1024 entries");
+    if (orb_pattern_ != pattern_sent_) {   // (the context keeps a pattern until it is given another)
+      surf_check(uwt_orb_set_pattern(tracker_->ctx(), orb_pattern_.empty() ? nullptr : orb_pattern_.data()), "uwt_orb_set_pattern");
+      pattern_sent_ = orb_pattern_;
+    }
+    std::vector<uwt_keypoint> kp[2];
+    std::vector<uint8_t> desc[2];
+    if (usekeypoints && !_previous_frame->orb_keypoints_.empty()) {
+      const int32_t n = (int32_t)_previous_frame->orb_keypoints_.size();
+      kp[0].resize((size_t)n);
+      desc[0].resize((size_t)n * 32);
+      surf_check(uwt_orb_describe_batch(tracker_->ctx(), 1, &a, &op, _previous_frame->orb_keypoints_.data(), &n, n, kp[0].data(),
+                                        desc[0].data()), "uwt_orb_describe_batch");
+    } else {
+      orb_detect(a, op, kp[0], desc[0]);
+    }
+    orb_detect(b, op, kp[1], desc[1]);
+    std::array<std::vector<float>, 2> xy;
+    for (int f = 0; f < 2; f++)
+      for (const uwt_keypoint& k : kp[f]) xy[(size_t)f].insert(xy[(size_t)f].end(), {k.x, k.y});
+    std::vector<uwt_match> good = DetectAndTrackFeatures(_previous_frame, _current_frame, desc[0].data(), (int)kp[0].size(), desc[1].data(),
+                                                         (int)kp[1].size(), 32, xy);
+    _previous_frame->orb_keypoints_.clear();
+    _current_frame->orb_keypoints_.clear();
+    for (const uwt_match& mt : good) {
+      _previous_frame->orb_keypoints_.push_back(kp[0][(size_t)mt.query_idx]);
+      _current_frame->orb_keypoints_.push_back(kp[1][(size_t)mt.train_idx]);
+    }
+    return good;
+  }
+  void orb_detect(int slot, const uwt_orb_params& op, std::vector<uwt_keypoint>& kp, std::vector<uint8_t>& desc) {
+    kp.resize((size_t)surf_cap_);
+    desc.resize((size_t)surf_cap_ * 32);
+    int32_t count = 0;
+    surf_check(uwt_orb_detect_describe_batch(tracker_->ctx(), 1, &slot, &op, surf_cap_, kp.data(), desc.data(), &count),
+               "uwt_orb_detect_describe_batch");
+    kp.resize((size_t)count);
+    desc.resize((size_t)count * 32);
+  }
+  std::vector<int8_t> pattern_sent_;
   void surf_check(int st, const char* what) {
     if (st != UWT_OK) throw std::runtime_error(std::string(what) + ": " + uwt_status_string(st) + " (" + uwt_last_error(tracker_->ctx()) + ")");
   }

@@ -430,9 +430,9 @@ int uwt_estimate_pose_candidates_batch(uwt_ctx* ctx, int32_t n_pairs, const int3
  * ratioTest calls and symmetryTest (:52-102, :229-236), and, since round 10, ransacTest (:106-169) as the inlier selection of
  * uwt_ransac_inliers_batch below — under a contract of this library's own, because cv::findFundamentalMat draws from OpenCV's RNG
  * and cannot be pinned.  Detection and description with cuda::SURF_CUDA (:184-206), since round 11, are uwt_surf_detect_describe_batch
- * and uwt_surf_describe_batch further below, under a contract of the same kind.  NOT built: cuda::ORB (:207-222; Hamming matching
- * serves callers who bring ORB descriptors).  getGoodKeypoints (:260-270) is a host gather in the mirrors (include/uw_tracker.hpp,
- * uw-slam_amd/tracker.py).
+ * and uwt_surf_describe_batch further below, under a contract of the same kind, and with cuda::ORB (:207-222), since round 16,
+ * uwt_orb_detect_describe_batch and uwt_orb_describe_batch behind them, whose 32-byte rows are matched under UWT_NORM_HAMMING.
+ * getGoodKeypoints (:260-270) is a host gather in the mirrors (include/uw_tracker.hpp, uw-slam_amd/tracker.py).
  *
  * Per pair: a query set A (n rows, the previous frame) and a train set B (m rows, the current frame) of descriptors of `dim`
  * elements.
@@ -576,7 +576,7 @@ int uwt_ransac_inliers_batch_async(uwt_ctx* ctx, int32_t n_pairs, const uwt_matc
  * only from integer arithmetic and IEEE f32 / f64 add, subtract, multiply, divide, compare, floorf and sqrtf (no FMA, no angle
  * function), so that tests/surf_ref.py restates it in numpy and the device agrees with it bit for bit.  Parameters:
  * uwt_surf_params, defaults those of SURF_CUDA (hessianThreshold 100, 4 octaves, 2 layers per octave, not extended, not upright).
- * Not built: masks, the extended 128-element descriptor, ORB.
+ * Not built: masks, the extended 128-element descriptor.  ORB is the section after this one.
  *
  * Integral image.  From the level-0 u8 plane of a slot (w x h): I is (h + 1) x (w + 1) uint32, I[y][x] = the sum of the pixels
  *   above and left of (x, y), modulo 2^32.  box(x0, y0, x1, y1) = I[y1][x1] - I[y0][x1] - I[y1][x0] + I[y0][x0] in uint32 arithmetic,
@@ -691,6 +691,123 @@ int uwt_surf_integral(uwt_ctx* ctx, int32_t slot, uint32_t* out);
 /* One response layer (octave 0..3, layer 0..5) on its octave's grid: *gw x *gh doubles (w >> octave by h >> octave) to host
  * memory, NaN where no response exists. */
 int uwt_surf_response_layer(uwt_ctx* ctx, int32_t slot, int32_t octave, int32_t layer, double* out, int32_t* gw, int32_t* gh);
+
+/* ---- ORB detection and description: RobustMatcher(1) ------------------------------------------------------------------------ */
+
+/* cuda::ORB::create() and orb->detectAndCompute(img, mask, keypoints, descriptors, useProvided) on both frames, followed by a
+ * NORM_HAMMING brute-force matcher (src/Tracker.cpp:210-223; RobustMatcher(int detector), :38-46, chooses it with detector = 1).
+ * cuda::ORB cannot be pinned: no OpenCV build is, and its learned table of 256 sampling pairs is not in the reference
+ * tree.  As with ransacTest and SURF this is ORB — Rublee et al.'s FAST-9/16 corners on a 1.2 x scale pyramid, Harris ranking,
+ * intensity-centroid orientation and a 256-bit steered BRIEF descriptor — under a contract of this library's own, complete here,
+ * built only from integer arithmetic and IEEE f32 / f64 add, subtract, multiply, divide, compare, floorf and sqrtf (no FMA, no angle
+ * function), so that tests/orb_ref.py restates it in numpy and the device agrees with it bit for bit.  Parameters: uwt_orb_params,
+ * defaults those of cuda::ORB::create(): 500 features, scale 1.2, 8 levels, edge threshold 31, first level 0, WTA_K 2, Harris score,
+ * patch 31, FAST threshold 20, no blur before description.  The sampling pattern is DATA of the context (uwt_orb_set_pattern): the
+ * default is the recipe below, not OpenCV's table — the one distance from OpenCV a caller who has that table can close themselves.
+ * Not built: masks, WTA_K 3 / 4, FAST-score ranking, blur before description, a scale other than 1.2, a first level other than 0,
+ * and an ORB branch of uwt_tracking_batch (its params struct is pinned at 56 bytes and its contract is "bit for bit the staged
+ * sequence": the chain is a follow-up to this staged path).
+ *
+ * Scale pyramid.  Integer, every layer from the level-0 u8 plane of the slot (w x h) alone; independent of the context's tracking
+ *   pyramid.  The scale of layer l = 0 .. n_levels - 1 is the exact rational 6^l / 5^l.  Layer width w_l = (w 5^l + 6^l / 2) / 6^l
+ *   in int64, rounding down; h_l likewise from h (uwt_orb_layer_size).  Layer 0 is the plane itself.  Layer l > 0 is a bilinear
+ *   resampling with pixel-centre alignment and 11-bit weights: for destination x, N = (2 x + 1) w - w_l, x0 = N / (2 w_l),
+ *   fx = ((N mod 2 w_l) * 2048) / (2 w_l), x1 = min(x0 + 1, w - 1); y0, fy, y1 likewise from y, h, h_l (integer divisions); the value is
+ *   (I[y0][x0] (2048 - fx)(2048 - fy) + I[y0][x1] fx (2048 - fy) + I[y1][x0] (2048 - fx) fy + I[y1][x1] fx fy + 2^21) >> 22 in
+ *   uint32 (it cannot overflow).  With w_l = w the formula gives the pixel itself.
+ * Candidate band.  Only pixels at least edge_threshold from every border of their layer are candidates: e <= x < w_l - e and
+ *   e <= y < h_l - e.  A layer with w_l or h_l below 2 e + 1 (2 * 31 + 1 by default) has none.  edge_threshold is at least 16, so
+ *   every later read (ring, 7 x 7 Harris block plus 1, radius-15 patch, rotated pattern) is inside the layer by construction.
+ * FAST.  The Bresenham ring of 16 at radius 3, (dx, dy) clockwise from the top — UWT_ORB_RING:
+ *   (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3)
+ *   With p the pixel and r_i the ring, d_i = r_i - p (int).  bright = max over i = 0..15 of min(d_i, d_{i+1}, .., d_{i+8}) (indices
+ *   modulo 16: the 16 arcs of 9 contiguous ring pixels); dark = the same with -d_i; score = max(bright, dark).  A candidate is a
+ *   corner iff score > fast_threshold; the score map S holds the score of a corner and 0 everywhere else (non-corners, pixels
+ *   off the band): uwt_orb_fast_scores.  Non-maximum suppression keeps a corner iff S there is strictly greater than S at all 8
+ *   neighbours.
+ * Harris measure of a kept corner (x, y), in integers: at each of the 49 pixels (u, v) of the 7 x 7 block centred on it,
+ *   Ix = 2 (I[v][u+1] - I[v][u-1]) + (I[v-1][u+1] - I[v-1][u-1]) + (I[v+1][u+1] - I[v+1][u-1]),
+ *   Iy = 2 (I[v+1][u] - I[v-1][u]) + (I[v+1][u-1] - I[v-1][u-1]) + (I[v+1][u+1] - I[v-1][u+1]);  a = sum Ix Ix, b = sum Iy Iy,
+ *   c = sum Ix Iy;  H = 25 (a b - c c) - (a + b)(a + b) in int64 (|Ix|, |Iy| <= 1020: it cannot overflow; the factor is Harris
+ *   k = 0.04 = 1 / 25).  uwt_orb_harris.
+ * Quota.  Layer l keeps its n_l best corners by (H descending, y ascending, x ascending); n_l = uwt_orb_level_quota, a host
+ *   function in double with + - * / and rint (half to even) only: factor = 1.0 / 1.2; fp = 1.0, multiplied by factor n_levels
+ *   times; want = n_features * (1.0 - factor) / (1.0 - fp); for l = 0 .. n_levels - 2: n_l = rint(want), want = want * factor; the
+ *   last layer takes the remainder max(n_features - sum, 0).  The shape of OpenCV's geometric split.
+ * Order and capacity.  The survivors of all layers are ordered by (layer, y, x) ascending.  If there are more than cap, the cap
+ *   first by (H descending, then that order) are kept, and reported in that order (layer, y, x).
+ * Key-point record of layer position (gx, gy) on layer l, each f32 rounded once: x = (double)(gx 6^l) / (double)5^l, y likewise,
+ *   size = (double)(31 6^l) / (double)5^l, response = (double)H / (25.0 * 7140^4) (7140 = 7 * 1020: the denominator, 2^8 * 25 *
+ *   1785^4, is exact in double), octave = l, laplacian = 0, the direction below.
+ * Provided key points (useProvidedKeypoints, src/Tracker.cpp:216-218): x, y and octave are read; the layer position is
+ *   gx = (int)floor((double)x * (double)5^l / (double)6^l + 0.5), gy likewise — which returns the (gx, gy) of a record this
+ *   contract wrote.  Direction and descriptor are recomputed there; the other fields pass through.
+ * Orientation (upright: the direction is (1, 0)).  Over the circular patch of radius 15 around (gx, gy) — row v = -15 .. 15 holds
+ *   u = -U[|v|] .. U[|v|] with UWT_ORB_UMAX, U = 15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3 — the integer sums
+ *   m10 = sum u I[gy+v][gx+u], m01 = sum v I[gy+v][gx+u] (both below 2^24: the conversion to f32 is exact).  fx = (float)m10,
+ *   fy = (float)m01, n = sqrtf(fx * fx + fy * fy); (dir_x, dir_y) = (fx / n, fy / n), or (1, 0) when n == 0.  There is no angle;
+ *   uwt_keypoint_angle_deg stays the host convenience it is.
+ * Descriptor.  (c, s) = (dir_x, dir_y); rnd(v) = (int)floorf(v + 0.5f).  Test k = 0..255 has pattern entry (x0, y0, x1, y1), int8
+ *   converted to f32: p0 = (rnd(x0 * c - y0 * s), rnd(x0 * s + y0 * c)), p1 likewise from (x1, y1) (each two f32 multiplies and one
+ *   subtract or add); bit k = I[gy + p0.y][gx + p0.x] < I[gy + p1.y][gx + p1.x] on the layer image; it goes into byte k / 8 at
+ *   position k % 8.  32 bytes, the row layout uwt_match_descriptors_batch(UWT_NORM_HAMMING, 32, ..) takes.
+ * Pattern.  256 x 4 int8 held by the context; valid iff every point has x x + y y <= 225.  The default, uwt_orb_default_pattern:
+ *   with mix() of the RANSAC contract above and the counter n = 0, draw(n) = (int)((mix(0x6f726221 ^ mix(n)) * 21) >> 32) - 10
+ *   (64-bit product: a coordinate in [-10, 10]); entry k = 0..255 in turn takes (draw(n), draw(n + 1), draw(n + 2), draw(n + 3))
+ *   and n += 4, again while its two points coincide.
+ * A frame's output depends neither on the batch it is in, nor on its place there, nor on uwt_tuning, nor on the order in which the
+ * device happens to find the candidates. */
+typedef struct uwt_orb_params {
+  int32_t n_features;       /* 500; 1..65536: what the layers' quotas sum to (*)              */
+  int32_t n_levels;         /* 8; 1..8                                                         */
+  int32_t edge_threshold;   /* 31; 16..1024                                                    */
+  int32_t fast_threshold;   /* 20; 0..255                                                      */
+  int32_t upright;          /* 0; != 0: no orientation, every direction is (1, 0)              */
+} uwt_orb_params;
+
+/* (*) where the rounding of the first layers overshoots, the last layer's max(.., 0) leaves the sum one above n_features: of all
+ * n_features below 3000 and every n_levels this happens once, for 7 features over 8 layers (2, 1, 1, 1, 1, 1, 1, 0). */
+/* {500, 8, 31, 20, 0} */
+int uwt_default_orb_params(uwt_orb_params* p);
+/* Host functions of the contract above; no context, no device.  n_l for l = 0 .. n_levels - 1 (n_features >= 0, n_levels 1..8). */
+int uwt_orb_level_quota(int32_t n_features, int32_t n_levels, int32_t* out);
+/* the default pattern: 256 x (x0, y0, x1, y1) */
+int uwt_orb_default_pattern(int8_t* out_1024);
+/* (w_l, h_l) of layer `level` (0..7) of a w x h frame */
+int uwt_orb_layer_size(int32_t w, int32_t h, int32_t level, int32_t* lw, int32_t* lh);
+/* Loads another pattern into the context (OpenCV's, for a caller who has it), for every ORB call after this one; null restores
+ * the default.  UWT_ERR_INVALID_ARG, the pattern in force unchanged, if a point has x x + y y > 225. */
+int uwt_orb_set_pattern(uwt_ctx* ctx, const int8_t* pattern_1024_or_null);
+/* Detection and description of the frames resident in slots[0 .. n_frames), host out, synchronous.  params: null for the defaults.
+ * kp_out: n_frames x cap records, frame f's counts_out[f] key points from kp_out[f * cap] on; desc_out_or_null: n_frames x cap x 32
+ * bytes, the fixed-stride layout uwt_match_descriptors_batch takes as query / train (null: detection only, directions included).
+ * The rows past a frame's count are not written.  A frame too small for layer 0's band, or a flat one, has count 0; that is no
+ * error.  UWT_ERR_INVALID_ARG with nothing enqueued and the outputs untouched: n_frames < 1, cap < 1, a null list or output, a slot
+ * out of range, a parameter outside the range stated at uwt_orb_params.  UWT_ERR_CAPACITY likewise: cap > UWT_MATCH_MAX_ROWS, a
+ * frame wider or higher than 16384.  n_frames is NOT bounded by max_frames (a slot may appear twice).  Scratch (the layers, the
+ * candidates, the results) belongs to the context, grows on demand and is sized per chunk of frames: a large batch runs as several
+ * chunks.  Uploads and launches go on the context's stream in order. */
+int uwt_orb_detect_describe_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params_or_null,
+                                  int32_t cap, uwt_keypoint* kp_out, uint8_t* desc_out_or_null, int32_t* counts_out);
+/* The same without waiting: results in DEVICE memory (d_kp_out: n_frames x cap, d_desc_out_or_null: n_frames x cap x 32,
+ * d_counts_out: n_frames) on the context's stream, ordered against uwt_upload_frames_async; uwt_sync() to wait. */
+int uwt_orb_detect_describe_batch_async(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params_or_null,
+                                        int32_t cap, uwt_keypoint* d_kp_out, uint8_t* d_desc_out_or_null, int32_t* d_counts_out);
+/* useProvidedKeypoints: direction and descriptors at the caller's key points.  keypoints_in: n_frames x cap records, frame f's
+ * n_in[f] (0..cap) from keypoints_in[f * cap] on.  A record is UWT_ERR_INVALID_ARG, with nothing enqueued, if x or y is not finite
+ * or beyond 1e6 in magnitude, if its octave is outside 0 .. n_levels - 1, or if its layer position is closer than edge_threshold
+ * to a border of its layer; the key points a detection on a frame of the same size kept always pass.  kp_out (may be
+ * keypoints_in): the same records with their directions; desc_out: n_frames x cap x 32 bytes.  Errors as above. */
+int uwt_orb_describe_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params_or_null,
+                           const uwt_keypoint* keypoints_in, const int32_t* n_in, int32_t cap, uwt_keypoint* kp_out,
+                           uint8_t* desc_out);
+/* Per-stage entries, host out, synchronous, under the default parameters.  One layer (level 0..7) of a slot: *lw x *lh bytes, tight
+ * rows (at most w x h). */
+int uwt_orb_layer(uwt_ctx* ctx, int32_t slot, int32_t level, uint8_t* out, int32_t* lw, int32_t* lh);
+/* The dense score map S of a layer, after the border rule and before suppression: w_l x h_l int32. */
+int uwt_orb_fast_scores(uwt_ctx* ctx, int32_t slot, int32_t level, int32_t* out);
+/* H at n pixels of a layer; xy: n x (x, y), each at least 4 from every border of the layer (else UWT_ERR_INVALID_ARG). */
+int uwt_orb_harris(uwt_ctx* ctx, int32_t slot, int32_t level, const int32_t* xy, int32_t n, int64_t* H_out);
 
 /* ---- System::Tracking for a batch of pairs in one device-resident call ---------------------------------------------------------- */
 

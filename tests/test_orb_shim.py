@@ -1,0 +1,86 @@
+"""The C++ side of ORB (tests/cpp/shim_orb.cpp over include/uw_tracker.hpp and the C ABI): the mirror's RobustMatcher(tracker, 1)
+compiles and links, calls what the Python mirror calls, and on the GPU its key points and descriptors equal the restatement's bits
+and DetectAndTrackFeatures(previous, current, usekeypoints) keeps what the CPU chain keeps."""
+import importlib
+import os
+import re
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import match_ref as M
+import orb_cases as K
+import orb_ref as O
+import ransac_ref as R
+
+ARITH_INDEPENDENT = True
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_exe(path, native=True):
+    if native:
+        importlib.import_module("uw-slam_amd").build_native()
+    libdir = os.path.join(ROOT, "uw-slam_amd")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "shim_orb.cpp"), "-o", path,
+                           "-L", libdir, "-luwt_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    return path
+
+
+def test_shim_orb_compiles_and_links(tmp_path):
+    assert os.path.exists(build_exe(str(tmp_path / "shim_orb")))
+
+
+def test_cpp_mirror_calls_what_the_python_mirror_calls():
+    hpp = open(os.path.join(ROOT, "include", "uw_tracker.hpp")).read()
+    py = open(os.path.join(ROOT, "uw-slam_amd", "tracker.py")).read()
+    assert re.search(r"explicit RobustMatcher\(Tracker\* tracker, int detector = 0\)", hpp)
+    assert re.search(r"def __init__\(self, ctx_or_tracker, .*detector=0\)", py)
+    cpp_orb = hpp[hpp.index("track_orb(Frame* _previous_frame"):hpp.index("std::vector<int8_t> pattern_sent_;")]
+    py_orb = py[py.index("def _track_orb"):py.index("def _track_descriptors")]
+    # the same entries in the same order: the pattern, describe at the kept records or detect, detect the current frame
+    cpp_calls = re.findall(r"\b(uwt_orb_set_pattern|uwt_orb_describe_batch|orb_detect|uwt_orb_detect_describe_batch)\(", cpp_orb)
+    py_calls = re.findall(r"\.(orb_set_pattern|orb_describe_batch|orb_detect_describe_batch)\(", py_orb)
+    assert cpp_calls[:4] == ["uwt_orb_set_pattern", "uwt_orb_describe_batch", "orb_detect", "orb_detect"]
+    assert "uwt_orb_detect_describe_batch" in cpp_calls
+    assert py_calls == ["orb_set_pattern", "orb_describe_batch", "orb_detect_describe_batch", "orb_detect_describe_batch"]
+    for field in ("n_features", "n_levels", "edge_threshold", "fast_threshold", "upright"):
+        assert "op.%s = " % field in cpp_orb and "%s=" % field in py_orb, field
+    assert "orb_keypoints_" in cpp_orb and "orb_keypoints_" in py_orb and "surf_keypoints_" not in cpp_orb + py_orb
+    assert ", 32, xy)" in cpp_orb     # 32-byte rows: the uint8 overload, Hamming
+
+
+@pytest.mark.gpu
+def test_shim_orb_equals_restatement(synth, tmp_path):
+    exe = build_exe(str(tmp_path / "shim_orb"), native=False)   # against the library that is there: one g++ call
+    w, h = 160, 96
+    ref, tgt, _, _, _ = synth.render_pair(w, h, 131.25, 131.25, 79.5, 47.5, seed=5)
+    (tmp_path / "ref.u8").write_bytes(ref.tobytes())
+    (tmp_path / "tgt.u8").write_bytes(tgt.tobytes())
+    out = tmp_path / "out.bin"
+    r = subprocess.run([exe, str(w), str(h), str(tmp_path / "ref.u8"), str(tmp_path / "tgt.u8"), str(out)], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    b = out.read_bytes()
+    n = struct.unpack_from("<i", b, 0)[0]
+    o = 4
+    kp = np.frombuffer(b, O.KEYPOINT, n, o); o += 32 * n
+    desc = np.frombuffer(b, np.uint8, n * 32, o).reshape(n, 32); o += 32 * n
+    ng = struct.unpack_from("<i", b, o)[0]; o += 4
+    good = np.frombuffer(b, M.MATCH, ng, o); o += 12 * ng
+    kept = np.frombuffer(b, np.float32, ng * 2, o).reshape(ng, 2); o += 8 * ng
+    records = np.frombuffer(b, O.KEYPOINT, ng, o); o += 32 * ng
+    ng2 = struct.unpack_from("<i", b, o)[0]
+    (wk0, wd0), (wk1, wd1) = O.detect_describe(ref), O.detect_describe(tgt)
+    assert K.same_keypoints(kp, wk0) is None, K.same_keypoints(kp, wk0)
+    assert K.same_descriptors(desc, wd0) is None, K.same_descriptors(desc, wd0)
+    m, _, _ = M.match(wd0, wd1, 0.65)
+    xy0, xy1 = np.stack([wk0["x"], wk0["y"]], 1), np.stack([wk1["x"], wk1["y"]], 1)
+    _, wgood, _ = R.ransac(m, xy0, xy1)
+    assert good.tobytes() == wgood.tobytes() and len(good) >= 8
+    assert kept.tobytes() == xy0[wgood["query_idx"]].tobytes()
+    assert K.same_keypoints(records, wk0[wgood["query_idx"]]) is None
+    # the second call described the previous frame at its kept records: the same descriptors there; it cannot gain matches
+    assert 8 <= ng2 <= ng

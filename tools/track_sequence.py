@@ -25,13 +25,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def track_live(w, h, intr, frames, depths, arith=0):
-    """System::Tracking over consecutive frames through the Python mirror: (poses [n - 1, 7], stats, matches kept per pair)"""
+def track_live(w, h, intr, frames, depths, arith=0, detector=0):
+    """System::Tracking over consecutive frames through the Python mirror: (poses [n - 1, 7], stats, matches kept per pair).
+    detector: 0 SURF, 1 ORB (RobustMatcher(int detector), src/Tracker.cpp:38-46)"""
     M = importlib.import_module("uw-slam_amd.tracker")
     fx, fy, cx, cy = intr
     tracker = M.Tracker(bool(depths), max_frames=4, arith=arith)
     tracker.InitializePyramid(w, h, np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32))
-    rm = M.RobustMatcher(tracker)
+    rm = M.RobustMatcher(tracker, detector=detector)
     mk = lambda i: M.Frame(frames[i], depths[i] if depths else None, i)
     poses, stats, kept = [], [], []
     prev = mk(0)
@@ -99,6 +100,8 @@ def main():
     ap.add_argument("--groundtruth"); ap.add_argument("--euroc", action="store_true"); ap.add_argument("--tum", action="store_true")
     ap.add_argument("--live", action="store_true", help="the reference's live loop, System::Tracking (src/System.cpp:193-223): SURF key "
                     "points detected, described, matched and RANSAC-filtered on the device, then EstimatePoseFeatures on their patches")
+    ap.add_argument("--detector", choices=["surf", "orb"], default="surf", help="with --live: the detector of RobustMatcher(int detector) "
+                    "(src/Tracker.cpp:38-46); orb runs the staged path only (no --chained)")
     ap.add_argument("--chained", action="store_true", help="with --live: the loop as successive device-resident calls (uwt_tracking_batch_async) "
                     "that hand their key points on in device memory, one wait at the end; the same trajectory")
     ap.add_argument("--out", default="trajectory")
@@ -133,7 +136,11 @@ def main():
         over.update(n_levels=4, first_level=3, last_level=0, max_iters=a.fixed_iters, early_exit=0)
     trk = S.SequenceTracker(a.width, a.height, fx, fy, cx - x0, cy - y0, depth=bool(depths), **over)
     t0 = time.perf_counter()
-    if a.live:
+    if a.detector == "orb" and (a.chained or not a.live):
+        ap.error("--detector orb goes with --live and without --chained: uwt_tracking_batch has no ORB branch")
+    if a.live and a.detector == "orb":
+        poses, stats, n_matches = track_live(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"], detector=1)
+    elif a.live:
         poses, stats, n_matches = (track_live_chained if a.chained else track_live)(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"])
     else:
         poses, stats = trk.track(frames, depths)

@@ -63,6 +63,12 @@ class SurfParams(C.Structure):
     _fields_ = [("hessian_threshold", C.c_double), ("n_octaves", C.c_int32), ("n_octave_layers", C.c_int32), ("upright", C.c_int32)]
 
 
+class OrbParams(C.Structure):
+    """uwt_orb_params: cuda::ORB::create()'s nfeatures, nlevels, edgeThreshold, fastThreshold, and upright"""
+    _fields_ = [("n_features", C.c_int32), ("n_levels", C.c_int32), ("edge_threshold", C.c_int32), ("fast_threshold", C.c_int32),
+                ("upright", C.c_int32)]
+
+
 class TrackingParams(C.Structure):
     """uwt_tracking_params: the SURF and RANSAC parameters, ratio_ and the `n_matches_ < 110` rule of System::Tracking"""
     _fields_ = [("surf", SurfParams), ("ransac", RansacParams), ("ratio", C.c_float), ("min_matches", C.c_int32)]
@@ -110,6 +116,9 @@ SYMBOLS = [
     "uwt_track_candidates_batch_async", "uwt_estimate_pose_candidates_batch",
     "uwt_default_surf_params", "uwt_keypoint_angle_deg", "uwt_surf_detect_describe_batch", "uwt_surf_detect_describe_batch_async",
     "uwt_surf_describe_batch", "uwt_surf_integral", "uwt_surf_response_layer",
+    "uwt_default_orb_params", "uwt_orb_level_quota", "uwt_orb_default_pattern", "uwt_orb_layer_size", "uwt_orb_set_pattern",
+    "uwt_orb_detect_describe_batch", "uwt_orb_detect_describe_batch_async", "uwt_orb_describe_batch", "uwt_orb_layer",
+    "uwt_orb_fast_scores", "uwt_orb_harris",
     "uwt_default_tracking_params", "uwt_tracking_batch_async", "uwt_tracking_batch", "uwt_match_descriptors_device_async",
 ]
 
@@ -208,6 +217,46 @@ def default_surf_params(**over):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def default_orb_params(**over):
+    """uwt_default_orb_params: n_features 500, n_levels 8, edge_threshold 31, fast_threshold 20, upright 0"""
+    p = OrbParams()
+    st = lib().uwt_default_orb_params(C.byref(p))
+    if st:
+        raise UwtError(st, "uwt_default_orb_params")
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def orb_level_quota(n_features, n_levels):
+    """uwt_orb_level_quota: the key points each layer of the ORB pyramid may keep, on the host"""
+    out = np.zeros(max(n_levels, 1), np.int32)
+    st = lib().uwt_orb_level_quota(n_features, n_levels, _p(out, C.c_int32))
+    if st:
+        raise UwtError(st, "uwt_orb_level_quota")
+    return out
+
+
+def orb_default_pattern():
+    """uwt_orb_default_pattern: the default sampling pattern, int8 [256, 4] (x0, y0, x1, y1)"""
+    out = np.zeros((256, 4), np.int8)
+    st = lib().uwt_orb_default_pattern(_p(out, C.c_int8))
+    if st:
+        raise UwtError(st, "uwt_orb_default_pattern")
+    return out
+
+
+def orb_layer_size(w, h, level):
+    """uwt_orb_layer_size: (w_l, h_l) of a layer of the ORB pyramid"""
+    lw, lh = C.c_int32(0), C.c_int32(0)
+    st = lib().uwt_orb_layer_size(w, h, level, C.byref(lw), C.byref(lh))
+    if st:
+        raise UwtError(st, "uwt_orb_layer_size")
+    return lw.value, lh.value
 
 
 def default_tracking_params(surf=None, ransac=None, **over):
@@ -847,6 +896,72 @@ class Context:
                                                 C.c_void_p(kp.ctypes.data), _p(n, C.c_int32), cap, C.c_void_p(out.ctypes.data),
                                                 C.c_void_p(desc.ctypes.data)))
         return [(out[i, :n[i]].copy(), desc[i, :n[i]].copy()) for i in range(F)]
+
+    def orb_set_pattern(self, pattern=None):
+        """Loads a sampling pattern (int8 [256, 4]; uwt_orb_set_pattern) for the ORB calls that follow; None restores the default."""
+        if pattern is not None:
+            pattern = np.ascontiguousarray(pattern, np.int8).reshape(1024)
+        self._chk(lib().uwt_orb_set_pattern(self._h, _p(pattern, C.c_int8) if pattern is not None else None))
+
+    def orb_detect_describe_batch(self, slots, params=None, cap=UWT_MATCH_MAX_ROWS, describe=True, out=None):
+        """ORB key points and descriptors of the frames resident in `slots` (uwt_orb_detect_describe_batch).  Returns one
+        (key points KEYPOINT [n], descriptors uint8 [n, 32] or None) per frame.  out: (kp [F, cap] KEYPOINT, desc [F, cap, 32]
+        uint8 or None, counts [F] int32) to be written in place — the rows past a frame's count stay as they are."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        F = slots.size
+        if out is None:
+            out = (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, 32), np.uint8) if describe else None, np.zeros(F, np.int32))
+        kp, desc, cnt = out
+        self._chk(lib().uwt_orb_detect_describe_batch(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None,
+                                                      cap, C.c_void_p(kp.ctypes.data),
+                                                      C.c_void_p(desc.ctypes.data) if desc is not None else None, _p(cnt, C.c_int32)))
+        return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy() if desc is not None else None) for i in range(F)]
+
+    def orb_detect_describe_batch_async(self, slots, d_kp_ptr, d_desc_ptr, d_counts_ptr, params=None, cap=UWT_MATCH_MAX_ROWS):
+        """The same enqueued on the context stream, results in device memory (d_kp_ptr: F x cap KEYPOINT, d_desc_ptr: F x cap x 32
+        bytes or None, d_counts_ptr: F int32); sync() to wait."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        self._chk(lib().uwt_orb_detect_describe_batch_async(self._h, slots.size, _p(slots, C.c_int32),
+                                                            C.byref(params) if params is not None else None, cap, C.c_void_p(d_kp_ptr),
+                                                            C.c_void_p(d_desc_ptr) if d_desc_ptr else None, C.c_void_p(d_counts_ptr)))
+
+    def orb_describe_batch(self, slots, keypoints_list, params=None, cap=None, out=None):
+        """Direction and descriptors at the caller's key points (uwt_orb_describe_batch: useProvidedKeypoints): keypoints_list
+        holds one KEYPOINT array per frame (x, y, octave are read).  Returns one (key points with directions, descriptors) per
+        frame.  out: (kp [F, cap] KEYPOINT, desc [F, cap, 32] uint8) to be written in place."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        kin = [np.ascontiguousarray(k, KEYPOINT).reshape(-1) for k in keypoints_list]
+        cap = max([cap or 1] + [len(k) for k in kin])
+        F = slots.size
+        kp, n = np.zeros((F, cap), KEYPOINT), np.zeros(F, np.int32)
+        for i, k in enumerate(kin):
+            kp[i, :len(k)], n[i] = k, len(k)
+        res, desc = out if out is not None else (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, 32), np.uint8))
+        self._chk(lib().uwt_orb_describe_batch(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None,
+                                               C.c_void_p(kp.ctypes.data), _p(n, C.c_int32), cap, C.c_void_p(res.ctypes.data),
+                                               C.c_void_p(desc.ctypes.data)))
+        return [(res[i, :n[i]].copy(), desc[i, :n[i]].copy()) for i in range(F)]
+
+    def orb_layer(self, slot, level):
+        """One layer of the ORB scale pyramid of a slot (uwt_orb_layer): uint8 [h_l, w_l]"""
+        out = np.zeros(max(1, self.params.height * self.params.width), np.uint8)
+        lw, lh = C.c_int32(0), C.c_int32(0)
+        self._chk(lib().uwt_orb_layer(self._h, slot, level, _p(out, C.c_uint8), C.byref(lw), C.byref(lh)))
+        return out[:lw.value * lh.value].reshape(lh.value, lw.value)
+
+    def orb_fast_scores(self, slot, level):
+        """The dense FAST score map of a layer, after the border rule and before suppression (uwt_orb_fast_scores): int32 [h_l, w_l]"""
+        lw, lh = orb_layer_size(self.params.width, self.params.height, level)
+        out = np.zeros(max(1, lw * lh), np.int32)
+        self._chk(lib().uwt_orb_fast_scores(self._h, slot, level, _p(out, C.c_int32)))
+        return out[:lw * lh].reshape(lh, lw)
+
+    def orb_harris(self, slot, level, xy):
+        """The integer Harris measure at pixels (x, y) of a layer (uwt_orb_harris): int64 [n]"""
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        out = np.zeros(len(xy), np.int64)
+        self._chk(lib().uwt_orb_harris(self._h, slot, level, _p(xy, C.c_int32), len(xy), _p(out, C.c_int64)))
+        return out
 
     def tracking_batch(self, ref_slots, tgt_slots, prev=None, params=None, cap=2048, out=None, raise_on_pair_failure=False):
         """System::Tracking for many pairs in one device-resident call (uwt_tracking_batch), host in and out.  prev: None, or one

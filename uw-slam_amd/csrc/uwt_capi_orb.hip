@@ -1,0 +1,407 @@
+// uwt_capi_orb.hip — host side of libuwt_hip.so: ORB detection and description.
+#include <functional>
+
+#include "uwt_ctx.h"
+#include "uwt_orb.h"
+
+namespace {
+
+// mix() of the RANSAC contract (include/uwt.h)
+inline uint32_t orb_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+constexpr uint32_t kOrbPatternSeed = 0x6f726221u;
+
+bool orb_pattern_ok(const int8_t* p) {
+  for (int i = 0; i < 512; i++)
+    if ((int)p[2 * i] * p[2 * i] + (int)p[2 * i + 1] * p[2 * i + 1] > 225) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- ORB detection and description (cuda::ORB of src/Tracker.cpp:210-223; the contract: include/uwt.h) -----------------------------
+int uwt_default_orb_params(uwt_orb_params* p) {
+  if (!p) return UWT_ERR_INVALID_ARG;
+  p->n_features = 500;
+  p->n_levels = 8;
+  p->edge_threshold = 31;
+  p->fast_threshold = 20;
+  p->upright = 0;
+  return UWT_OK;
+}
+
+int uwt_orb_level_quota(int32_t n_features, int32_t n_levels, int32_t* out) {
+  if (!out || n_features < 0 || n_levels < 1 || n_levels > kOrbMaxLevels) return UWT_ERR_INVALID_ARG;
+  const double factor = 1.0 / 1.2;
+  double fp = 1.0;
+  for (int l = 0; l < n_levels; l++) fp = fp * factor;
+  double want = (double)n_features * (1.0 - factor) / (1.0 - fp);
+  int total = 0;
+  for (int l = 0; l < n_levels - 1; l++) {
+    out[l] = (int32_t)std::rint(want);
+    total += out[l];
+    want = want * factor;
+  }
+  out[n_levels - 1] = std::max(n_features - total, 0);
+  return UWT_OK;
+}
+
+int uwt_orb_default_pattern(int8_t* out) {
+  if (!out) return UWT_ERR_INVALID_ARG;
+  uint32_t n = 0;
+  for (int k = 0; k < 256; k++) {
+    int8_t e[4];
+    do {
+      for (uint32_t j = 0; j < 4; j++) e[j] = (int8_t)((int)(((uint64_t)orb_mix(kOrbPatternSeed ^ orb_mix(n + j)) * 21u) >> 32) - 10);
+      n += 4;
+    } while (e[0] == e[2] && e[1] == e[3]);
+    std::memcpy(out + 4 * k, e, 4);
+  }
+  return UWT_OK;
+}
+
+int uwt_orb_layer_size(int32_t w, int32_t h, int32_t level, int32_t* lw, int32_t* lh) {
+  if (!lw || !lh || w < 1 || h < 1 || level < 0 || level >= kOrbMaxLevels) return UWT_ERR_INVALID_ARG;
+  *lw = orb_layer_dim(w, level);
+  *lh = orb_layer_dim(h, level);
+  return UWT_OK;
+}
+
+int uwt_orb_set_pattern(uwt_ctx* c, const int8_t* pattern_or_null) {
+  if (!c) return UWT_ERR_INVALID_ARG;
+  if (pattern_or_null && !orb_pattern_ok(pattern_or_null))
+    return fail(c, UWT_ERR_INVALID_ARG, "uwt_orb_set_pattern: a point outside x^2 + y^2 <= 225");
+  if (pattern_or_null) std::memcpy(c->orb_pattern, pattern_or_null, sizeof(c->orb_pattern));
+  else uwt_orb_default_pattern(c->orb_pattern);
+  c->orb_pattern_state = 1;   // the next ORB call sends it, on the stream behind the calls before
+  return UWT_OK;
+}
+
+static_assert(sizeof(OrbKeypoint) == sizeof(uwt_keypoint), "uwt_keypoint layout");
+static_assert(sizeof(uwt_orb_params) == 20, "uwt_orb_params layout");
+
+namespace {
+
+constexpr size_t kOrbChunkBytes = 256u << 20;   // scratch a chunk of frames may take
+constexpr int kOrbMaxChunk = 4096;              // frames of a chunk at most (a launch's grid)
+
+// the geometry of a call: the layers, the quotas and, when the call detects, the bounds of the candidate lists
+void orb_plan(const uwt_ctx* c, const uwt_orb_params& op, bool detect, OrbArgs* a) {
+  const LevelK& L = c->lv[0];
+  a->img = c->img[0];
+  a->frame_stride = (size_t)L.n;
+  a->pitch = L.pitch;
+  a->w = c->p.width;
+  a->h = c->p.height;
+  a->n_levels = op.n_levels;
+  a->edge = op.edge_threshold;
+  a->fast_threshold = op.fast_threshold;
+  a->upright = op.upright ? 1 : 0;
+  int32_t quota[kOrbMaxLevels] = {};
+  uwt_orb_level_quota(op.n_features, op.n_levels, quota);
+  size_t loff = 0, roff = 0;
+  long long kept = 0;
+  for (int l = 0; l < kOrbMaxLevels; l++) {
+    const bool on = l < op.n_levels;
+    a->lw[l] = on ? orb_layer_dim(a->w, l) : 0;
+    a->lh[l] = on ? orb_layer_dim(a->h, l) : 0;
+    a->loff[l] = loff;
+    if (l > 0) loff += (size_t)a->lw[l] * (size_t)a->lh[l];
+    a->quota[l] = on && detect ? quota[l] : 0;
+    kept += a->quota[l];
+    a->raw_cap[l] = on && detect ? (int)orb_raw_bound(a->lw[l], a->lh[l], a->edge) : 0;
+    a->raw_off[l] = roff;
+    roff += (size_t)a->raw_cap[l];
+  }
+  a->layer_stride = (loff + 15) & ~(size_t)15;
+  a->raw_stride = roff;
+  a->kept_stride = (int)kept;
+}
+
+// the scratch of a chunk of nf frames: [slots | raw counts | counts | layers | raw keys | raw H | kept | keep | key points | descriptors | extra]
+struct OrbLayout {
+  size_t slots, raw_count, counts, layers, raw_key, raw_h, kept, keep, kp, desc, extra, total;
+};
+OrbLayout orb_layout(const OrbArgs& g, int nf, int cap, size_t extra) {
+  OrbLayout l;
+  Carve cv(16);
+  l.slots = cv.take<int>((size_t)nf);
+  l.raw_count = cv.take<int>((size_t)nf * kOrbMaxLevels);
+  l.counts = cv.take<int>((size_t)nf);
+  l.layers = cv.take<uint8_t>(g.layer_stride * nf);
+  l.raw_key = cv.take<unsigned long long>(g.raw_stride * nf);
+  l.raw_h = cv.take<long long>(g.raw_stride * nf);
+  l.kept = cv.take<OrbKept>((size_t)g.kept_stride * nf);
+  l.keep = cv.take<uint8_t>((size_t)g.kept_stride * nf);
+  l.kp = cv.take<OrbKeypoint>((size_t)cap * nf);
+  l.desc = cv.take<uint8_t>(32 * (size_t)cap * nf);
+  l.extra = cv.take<uint8_t>(extra);
+  l.total = cv.total();
+  return l;
+}
+
+// frames of a chunk: as many as kOrbChunkBytes hold, one at least
+int orb_chunk_frames(const OrbArgs& g, int n_frames, int cap) {
+  const size_t per = orb_layout(g, 1, cap, 0).total;
+  const size_t fit = std::max<size_t>(1, kOrbChunkBytes / per);
+  return (int)std::min<size_t>(fit, (size_t)std::min(n_frames, kOrbMaxChunk));
+}
+
+// the context's pattern on the device: the default one the first time, a new one behind uwt_orb_set_pattern
+int orb_pattern_ready(uwt_ctx* c) {
+  if (c->orb_pattern_state == 0) {
+    uwt_orb_default_pattern(c->orb_pattern);
+    c->orb_pattern_state = 1;
+  }
+  if (c->orb_pattern_state == 1) {
+    int st = c->orb_pat.reserve(c, c->stream, sizeof(c->orb_pattern));
+    if (st) return st;
+    HIPCHK(c, hipMemcpyAsync(c->orb_pat.p, c->orb_pattern, sizeof(c->orb_pattern), hipMemcpyHostToDevice, c->stream));
+    c->orb_pattern_state = 2;
+  }
+  return UWT_OK;
+}
+
+// Grows the scratch to a chunk of nf frames, sends the chunk's slot list and enqueues the layers.  g: the call's geometry; *a: the chunk.
+int orb_begin_chunk(uwt_ctx* c, const OrbArgs& g, const int32_t* slots, int nf, int cap, size_t extra, OrbArgs* a, unsigned char** extra_out) {
+  const OrbLayout l = orb_layout(g, nf, cap, extra);
+  int st = c->orb_buf.reserve(c, c->stream, l.total);
+  if (st) return st;
+  st = orb_pattern_ready(c);
+  if (st) return st;
+  unsigned char* b = (unsigned char*)c->orb_buf.p;
+  *a = g;
+  a->slots = (const int*)(b + l.slots);
+  a->n_frames = nf;
+  a->layers = b + l.layers;
+  a->raw_key = (unsigned long long*)(b + l.raw_key);
+  a->raw_h = (long long*)(b + l.raw_h);
+  a->raw_count = (int*)(b + l.raw_count);
+  a->kept = (OrbKept*)(b + l.kept);
+  a->keep = b + l.keep;
+  a->kp = (OrbKeypoint*)(b + l.kp);
+  a->desc = b + l.desc;
+  a->counts = (int*)(b + l.counts);
+  a->cap = cap;
+  a->pattern = (const signed char*)c->orb_pat.p;
+  if (extra_out) *extra_out = b + l.extra;
+  HIPCHK(c, hipMemcpyAsync((void*)a->slots, slots, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(a->raw_count, 0, sizeof(int) * (size_t)nf * kOrbMaxLevels, c->stream));
+  launch_orb_layers(c->stream, *a);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
+// The checks of an ORB call; *op: the parameters in force.  Nothing is enqueued when a check fails.
+int orb_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_orb_params* params, uwt_orb_params* op) {
+  if (n_frames < 1 || cap < 1 || !slots) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_frames < 1, cap < 1 or a null list");
+  if (cap > UWT_MATCH_MAX_ROWS) return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS");
+  for (int f = 0; f < n_frames; f++)
+    if (!slot_range_ok(c, slots[f], 1)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": slot out of range");
+  if (params) *op = *params;
+  else uwt_default_orb_params(op);
+  if (op->n_features < 1 || op->n_features > kOrbMaxFeatures || op->n_levels < 1 || op->n_levels > kOrbMaxLevels)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_features outside 1..65536 or n_levels outside 1..8");
+  if (op->edge_threshold < kOrbMinEdge || op->edge_threshold > kOrbMaxEdge || op->fast_threshold < 0 || op->fast_threshold > 255)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": edge_threshold outside 16..1024 or fast_threshold outside 0..255");
+  if (c->p.width > kOrbMaxDim || c->p.height > kOrbMaxDim)
+    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": a frame wider or higher than 16384");
+  return UWT_OK;
+}
+
+// Key points (detected, or the caller's host lists kp_in / n_in: n_frames x cap, described as they are), then directions and
+// descriptors, for n_frames frames in chunks.  The results of a chunk are in its scratch; `deliver` takes them (first frame of the
+// chunk, the chunk's arguments) before the next chunk runs.
+int orb_run(uwt_ctx* c, const uwt_orb_params& op, int n_frames, const int32_t* slots, int cap, const uwt_keypoint* kp_in, const int32_t* n_in,
+            bool want_desc, const std::function<int(int, const OrbArgs&)>& deliver) {
+  int st = compute_begin_pairs(c, n_frames, slots, slots);
+  if (st) return st;
+  OrbArgs g;
+  orb_plan(c, op, kp_in == nullptr, &g);
+  const int chunk = orb_chunk_frames(g, n_frames, cap);
+  for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+    const int nf = std::min(chunk, n_frames - f0);
+    OrbArgs a;
+    st = orb_begin_chunk(c, g, slots + f0, nf, cap, 0, &a, nullptr);
+    if (st) return st;
+    int rows = std::min(cap, std::max(g.kept_stride, 1));
+    if (kp_in) {
+      rows = 0;
+      for (int f = 0; f < nf; f++) rows = std::max(rows, n_in[f0 + f]);
+      HIPCHK(c, hipMemcpyAsync(a.counts, n_in + f0, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(a.kp, kp_in + (size_t)f0 * cap, sizeof(OrbKeypoint) * (size_t)cap * nf, hipMemcpyHostToDevice, c->stream));
+    } else {
+      launch_orb_detect(c->stream, a);
+    }
+    if (!want_desc) a.desc = nullptr;
+    launch_orb_describe(c->stream, a, rows);
+    HIPCHK(c, hipGetLastError());
+    st = deliver(f0, a);
+    if (st) return st;
+  }
+  return UWT_OK;
+}
+
+// the chunk's results to the caller's device arrays, every row of the chunk (d_desc is not written when the chunk has no descriptors)
+int orb_deliver_device(uwt_ctx* c, int f0, const OrbArgs& a, uwt_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts) {
+  const size_t recs = (size_t)a.n_frames * a.cap, g0 = (size_t)f0 * a.cap;
+  HIPCHK(c, hipMemcpyAsync(d_counts + f0, a.counts, sizeof(int) * (size_t)a.n_frames, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_kp + g0, a.kp, sizeof(OrbKeypoint) * recs, hipMemcpyDeviceToDevice, c->stream));
+  if (a.desc) HIPCHK(c, hipMemcpyAsync(d_desc + g0 * 32, a.desc, 32 * recs, hipMemcpyDeviceToDevice, c->stream));
+  return UWT_OK;
+}
+
+// the chunk's results to host memory: only the rows below each frame's count are written
+int orb_deliver_host(uwt_ctx* c, int f0, const OrbArgs& a, uwt_keypoint* kp_out, uint8_t* desc_out, int32_t* counts_out) {
+  std::vector<int32_t> cnt((size_t)a.n_frames);
+  HIPCHK(c, hipMemcpyAsync(cnt.data(), a.counts, sizeof(int) * (size_t)a.n_frames, hipMemcpyDeviceToHost, c->stream));
+  const size_t g0 = (size_t)f0 * a.cap;
+  int st = rows_to_host(c, a.cap, a.n_frames, {{a.kp, sizeof(OrbKeypoint), cnt.data(), kp_out + g0},
+                                                {a.desc, 32, cnt.data(), a.desc ? desc_out + g0 * 32 : nullptr}});
+  if (!st && counts_out)
+    for (int f = 0; f < a.n_frames; f++) counts_out[f0 + f] = std::min(std::max(cnt[(size_t)f], 0), a.cap);
+  return st;
+}
+
+// one frame's chunk for a per-stage entry: the checks, the stream order and the layers up to `level`
+int orb_stage_begin(uwt_ctx* c, const char* what, int32_t slot, int32_t level, bool detect, size_t extra, OrbArgs* a, unsigned char** x) {
+  if (level < 0 || level >= kOrbMaxLevels) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": level outside 0..7");
+  uwt_orb_params op;
+  int st = orb_check(c, what, 1, &slot, 1, nullptr, &op);
+  if (st) return st;
+  st = compute_begin(c, slot, 1);
+  if (st) return st;
+  OrbArgs g;
+  orb_plan(c, op, detect, &g);
+  return orb_begin_chunk(c, g, &slot, 1, 1, extra, a, x);
+}
+
+}  // namespace
+
+int uwt_orb_detect_describe_batch(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params, int32_t cap,
+                                  uwt_keypoint* kp_out, uint8_t* desc_out, int32_t* counts_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  const char* what = "uwt_orb_detect_describe_batch";
+  if (!c || !kp_out || !counts_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  uwt_orb_params op;
+  int st = orb_check(c, what, n_frames, slots, cap, params, &op);
+  if (st) return st;
+  return orb_run(c, op, n_frames, slots, cap, nullptr, nullptr, desc_out != nullptr,
+                 [&](int f0, const OrbArgs& a) { return orb_deliver_host(c, f0, a, kp_out, desc_out, counts_out); });
+}
+
+int uwt_orb_detect_describe_batch_async(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params, int32_t cap,
+                                        uwt_keypoint* d_kp_out, uint8_t* d_desc_out, int32_t* d_counts_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  const char* what = "uwt_orb_detect_describe_batch_async";
+  if (!c || !d_kp_out || !d_counts_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  uwt_orb_params op;
+  int st = orb_check(c, what, n_frames, slots, cap, params, &op);
+  if (st) return st;
+  st = orb_run(c, op, n_frames, slots, cap, nullptr, nullptr, d_desc_out != nullptr,
+               [&](int f0, const OrbArgs& a) { return orb_deliver_device(c, f0, a, d_kp_out, d_desc_out, d_counts_out); });
+  if (st) return st;
+  return compute_end(c, c->dep_first, c->dep_n);
+}
+
+int uwt_orb_describe_batch(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params, const uwt_keypoint* keypoints_in,
+                           const int32_t* n_in, int32_t cap, uwt_keypoint* kp_out, uint8_t* desc_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  const char* what = "uwt_orb_describe_batch";
+  if (!c || !keypoints_in || !n_in || !kp_out || !desc_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  uwt_orb_params op;
+  int st = orb_check(c, what, n_frames, slots, cap, params, &op);
+  if (st) return st;
+  for (int f = 0; f < n_frames; f++) {
+    if (n_in[f] < 0 || n_in[f] > cap) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key-point count outside 0..cap");
+    const uwt_keypoint* k = keypoints_in + (size_t)f * cap;
+    for (int i = 0; i < n_in[f]; i++) {
+      const int l = k[i].octave;
+      bool ok = std::fabs(k[i].x) <= 1e6f && std::fabs(k[i].y) <= 1e6f && l >= 0 && l < op.n_levels;   // (a NaN fails)
+      if (ok) {
+        const int gx = orb_layer_pos(k[i].x, l), gy = orb_layer_pos(k[i].y, l), e = op.edge_threshold;
+        ok = gx >= e && gx < orb_layer_dim(c->p.width, l) - e && gy >= e && gy < orb_layer_dim(c->p.height, l) - e;
+      }
+      if (!ok)
+        return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": a key point that is not finite, has an octave outside 0..n_levels-1 or "
+                                                                "lies closer than edge_threshold to a border of its layer");
+    }
+  }
+  // the device keeps every row of a chunk; only the rows below a frame's count come back
+  return orb_run(c, op, n_frames, slots, cap, keypoints_in, n_in, true,
+                 [&](int f0, const OrbArgs& a) { return orb_deliver_host(c, f0, a, kp_out, desc_out, nullptr); });
+}
+
+int uwt_orb_layer(uwt_ctx* c, int32_t slot, int32_t level, uint8_t* out, int32_t* lw, int32_t* lh) {
+  if (c) (void)hipSetDevice(c->p.device);
+  const char* what = "uwt_orb_layer";
+  if (!c || !out || !lw || !lh) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  OrbArgs a;
+  int st = orb_stage_begin(c, what, slot, level, false, 0, &a, nullptr);
+  if (st) return st;
+  const size_t w = (size_t)a.lw[level], h = (size_t)a.lh[level];
+  if (w && h) {
+    if (level == 0)
+      HIPCHK(c, hipMemcpy2DAsync(out, w, a.img + (size_t)slot * a.frame_stride, (size_t)a.pitch, w, h, hipMemcpyDeviceToHost, c->stream));
+    else
+      HIPCHK(c, hipMemcpyAsync(out, a.layers + a.loff[level], w * h, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *lw = (int32_t)w;
+  *lh = (int32_t)h;
+  return UWT_OK;
+}
+
+int uwt_orb_fast_scores(uwt_ctx* c, int32_t slot, int32_t level, int32_t* out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  const char* what = "uwt_orb_fast_scores";
+  if (!c || !out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  if (level < 0 || level >= kOrbMaxLevels) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": level outside 0..7");
+  const size_t n = (size_t)orb_layer_dim(c->p.width, level) * (size_t)orb_layer_dim(c->p.height, level);
+  OrbArgs a;
+  unsigned char* x = nullptr;
+  int st = orb_stage_begin(c, what, slot, level, true, sizeof(int) * n + 16, &a, &x);
+  if (st) return st;
+  if (n) {
+    HIPCHK(c, hipMemsetAsync(x, 0, sizeof(int) * n, c->stream));
+    a.score_out = (int*)x;
+    launch_orb_fast(c->stream, a, level);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, x, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return UWT_OK;
+}
+
+int uwt_orb_harris(uwt_ctx* c, int32_t slot, int32_t level, const int32_t* xy, int32_t n, int64_t* H_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  const char* what = "uwt_orb_harris";
+  if (!c || !xy || !H_out || n < 1) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument or n < 1");
+  if (level < 0 || level >= kOrbMaxLevels) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": level outside 0..7");
+  const int lw = orb_layer_dim(c->p.width, level), lh = orb_layer_dim(c->p.height, level);
+  for (int i = 0; i < n; i++)
+    if (xy[2 * i] < 4 || xy[2 * i] >= lw - 4 || xy[2 * i + 1] < 4 || xy[2 * i + 1] >= lh - 4)
+      return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": a pixel closer than 4 to a border of the layer");
+  OrbArgs a;
+  unsigned char* x = nullptr;
+  Carve cv(16);
+  const size_t at_xy = cv.take<int>(2 * (size_t)n), at_h = cv.take<long long>((size_t)n);
+  int st = orb_stage_begin(c, what, slot, level, false, cv.total(), &a, &x);
+  if (st) return st;
+  HIPCHK(c, hipMemcpyAsync(x + at_xy, xy, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  launch_orb_harris(c->stream, a, level, (const int*)(x + at_xy), n, (long long*)(x + at_h));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(H_out, x + at_h, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return UWT_OK;
+}
+
+}  // extern "C"

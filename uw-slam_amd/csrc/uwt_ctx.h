@@ -150,6 +150,13 @@ struct uwt_ctx {
   // SURF detection and description (uwt_surf_*): per chunk of frames the slot list, the counts, the integral images, the raw
   // candidates with their order keys, and the key points and descriptors before they go to the caller — grown on use
   DevBuf surf_buf;
+  // ORB detection and description (uwt_orb_*): per chunk of frames the slot list, the counts, the layers above 0, the raw candidates
+  // of every layer, the quota survivors, and the key points and descriptors before they go to the caller — grown on use; and the
+  // sampling pattern (256 x 4 int8): the host copy, its device copy, and which of them is current (0: neither yet — the default is
+  // made on first use; 1: the host copy, to be sent by the next call; 2: both)
+  DevBuf orb_buf, orb_pat;
+  int8_t orb_pattern[1024] = {};
+  int orb_pattern_state = 0;
   // the chained tracking call (uwt_tracking_batch*): per pair and side the key points, descriptors and counts SURF leaves, the paths
   // and flags of the previous frames, symMatches and the RANSAC records; behind them the synchronous form's inputs and results
   DevBuf track_buf;

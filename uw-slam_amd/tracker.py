@@ -34,6 +34,7 @@ class Frame:
         self.n_matches_ = 0                                  # include/System.h:93
         self.surf_keypoints_ = np.zeros(0, capi.KEYPOINT)    # the same key points as cv::KeyPoint holds them (size, response, direction,
                                                              # octave): what useProvidedKeypoints describes again in the next call
+        self.orb_keypoints_ = np.zeros(0, capi.KEYPOINT)     # the same under RobustMatcher(detector=1): ORB's records
         self.candidatePoints_ = {}                           # level -> N x 4 [x y z w] when a sparse producer ran
         self._slot = None
 
@@ -225,13 +226,18 @@ class RobustMatcher:
     inlier selection of uwt_ransac_inliers_batch (the contract: include/uwt.h; cv::findFundamentalMat itself draws from OpenCV's RNG
     and is not pinned); getGoodKeypoints and the assignment of :247-254 on the host.  Detection and description with
     cuda::SURF_CUDA (:186-206) are uwt_surf_detect_describe_batch / uwt_surf_describe_batch, SURF under the contract of include/uwt.h:
-    DetectAndTrackFeatures(previous, current, usekeypoints) is the reference's whole method.  The forms that take the caller's
-    descriptors stay (cuda::ORB is not built; a caller brings ORB descriptors).  A caller with a RANSAC of their own still hands
-    its inlier mask to MatchAndSetKeypoints.
+    DetectAndTrackFeatures(previous, current, usekeypoints) is the reference's whole method.  With detector=1, as
+    RobustMatcher(int detector) of src/Tracker.cpp:38-46, the same method runs cuda::ORB's branch (:210-223):
+    uwt_orb_detect_describe_batch / uwt_orb_describe_batch, ORB under the contract of include/uwt.h, matched under Hamming; the full
+    records are kept in Frame.orb_keypoints_.  The forms that take the caller's descriptors stay.  A caller with a RANSAC of their
+    own still hands its inlier mask to MatchAndSetKeypoints.
     float32 descriptors are matched under L2 (SURF), uint8 under Hamming (ORB), as createBFMatcher is set up at :199 / :221."""
 
-    def __init__(self, ctx_or_tracker, ratio=0.65, distance=3.0, confidence=0.99, refineF=True):
+    def __init__(self, ctx_or_tracker, ratio=0.65, distance=3.0, confidence=0.99, refineF=True, detector=0):
+        if detector not in (0, 1):
+            raise ValueError("RobustMatcher: detector is 0 (SURF) or 1 (ORB)")
         self._src = ctx_or_tracker
+        self.detector_ = int(detector)           # src/Tracker.cpp:38-46: 0 SURF, 1 ORB
         self.ratio_ = float(np.float32(ratio))   # include/Tracker.h:80
         self.distance_ = float(distance)         # include/Tracker.h:82
         self.confidence_ = float(confidence)     # include/Tracker.h:83
@@ -241,6 +247,10 @@ class RobustMatcher:
         self.seed_ = 0
         self.hessian_threshold_ = 100.0          # cuda::SURF_CUDA's defaults (`cuda::SURF_CUDA surf;`, src/Tracker.cpp:188)
         self.n_octaves_, self.n_octave_layers_, self.upright_ = 4, 2, False
+        self.n_features_, self.n_levels_ = 500, 8   # cuda::ORB::create()'s defaults (src/Tracker.cpp:212)
+        self.edge_threshold_, self.fast_threshold_ = 31, 20
+        self.orb_pattern_ = None                 # None: the library's default pattern; else int8 [256, 4] (uwt_orb_set_pattern)
+        self._pattern_sent = None
 
     @property
     def _ctx(self):
@@ -293,6 +303,8 @@ class RobustMatcher:
         a, b = tracker._bind(_previous_frame), tracker._bind(_current_frame)
         if _previous_frame._slot != a:
             raise RuntimeError("DetectAndTrackFeatures: more frames than slots (max_frames)")
+        if self.detector_ == 1:
+            return self._track_orb(_previous_frame, _current_frame, a, b, usekeypoints)
         params = capi.default_surf_params(hessian_threshold=self.hessian_threshold_, n_octaves=self.n_octaves_,
                                           n_octave_layers=self.n_octave_layers_, upright=int(self.upright_))
         if usekeypoints and len(_previous_frame.surf_keypoints_):
@@ -303,6 +315,24 @@ class RobustMatcher:
         xy = (np.stack([kp0["x"], kp0["y"]], 1), np.stack([kp1["x"], kp1["y"]], 1))
         good = self._track_descriptors(_previous_frame, _current_frame, d0, d1, xy)
         _previous_frame.surf_keypoints_, _current_frame.surf_keypoints_ = kp0[good["query_idx"]], kp1[good["train_idx"]]
+        return good
+
+    def _track_orb(self, _previous_frame, _current_frame, a, b, usekeypoints):
+        """src/Tracker.cpp:210-223 and on: ORB on both frames (the previous one described at the records it kept when
+        usekeypoints is set and it has some, :216-218), then the matcher under Hamming, ransacTest and the assignment"""
+        params = capi.default_orb_params(n_features=self.n_features_, n_levels=self.n_levels_, edge_threshold=self.edge_threshold_,
+                                         fast_threshold=self.fast_threshold_, upright=int(self.upright_))
+        if self.orb_pattern_ is not self._pattern_sent:   # (the context keeps a pattern until it is given another)
+            self._ctx.orb_set_pattern(self.orb_pattern_)
+            self._pattern_sent = self.orb_pattern_
+        if usekeypoints and len(_previous_frame.orb_keypoints_):
+            kp0, d0 = self._ctx.orb_describe_batch([a], [_previous_frame.orb_keypoints_], params=params)[0]
+            kp1, d1 = self._ctx.orb_detect_describe_batch([b], params=params)[0]
+        else:
+            (kp0, d0), (kp1, d1) = self._ctx.orb_detect_describe_batch([a, b], params=params)
+        xy = (np.stack([kp0["x"], kp0["y"]], 1), np.stack([kp1["x"], kp1["y"]], 1))
+        good = self._track_descriptors(_previous_frame, _current_frame, d0, d1, xy)
+        _previous_frame.orb_keypoints_, _current_frame.orb_keypoints_ = kp0[good["query_idx"]], kp1[good["train_idx"]]
         return good
 
     def _track_descriptors(self, _previous_frame, _current_frame, desc_prev, desc_cur, keypoints):
