@@ -612,37 +612,30 @@ class RobustMatcher {
     const int a = tracker_->bind(_previous_frame), b = tracker_->bind(_current_frame);
     if (!tracker_->bound(_previous_frame) || _previous_frame->slot_ != a)
       throw std::runtime_error("DetectAndTrackFeatures: more frames than slots (max_frames)");
-    if (detector_ == 1) return track_orb(_previous_frame, _current_frame, a, b, usekeypoints);
+    if (detector_ == 1) {   // :210-223: ORB, its rows matched under Hamming, its records kept in orb_keypoints_
+      uwt_orb_params op;
+      uwt_default_orb_params(&op);
+      op.n_features = n_features_;
+      op.n_levels = n_levels_;
+      op.edge_threshold = edge_threshold_;
+      op.fast_threshold = fast_threshold_;
+      op.upright = upright_ ? 1 : 0;
+      if (!orb_pattern_.empty() && orb_pattern_.size() != 1024) throw std::invalid_argument("RobustMatcher: orb_pattern_ holds 1024 entries");
+      if (orb_pattern_ != pattern_sent_) {   // (the context keeps a pattern until it is given another)
+        status(uwt_orb_set_pattern(tracker_->ctx(), orb_pattern_.empty() ? nullptr : orb_pattern_.data()), "uwt_orb_set_pattern");
+        pattern_sent_ = orb_pattern_;
+      }
+      return track(_previous_frame, _current_frame, a, b, usekeypoints, op, uwt_orb_detect_describe_batch, "uwt_orb_detect_describe_batch",
+                   uwt_orb_describe_batch, "uwt_orb_describe_batch", 32, &Frame::orb_keypoints_);
+    }
     uwt_surf_params sp;
     uwt_default_surf_params(&sp);
     sp.hessian_threshold = hessian_threshold_;
     sp.n_octaves = n_octaves_;
     sp.n_octave_layers = n_octave_layers_;
     sp.upright = upright_ ? 1 : 0;
-    std::vector<uwt_keypoint> kp[2];
-    std::vector<float> desc[2];
-    if (usekeypoints && !_previous_frame->surf_keypoints_.empty()) {
-      const int32_t n = (int32_t)_previous_frame->surf_keypoints_.size();
-      kp[0].resize((size_t)n);
-      desc[0].resize((size_t)n * 64);
-      surf_check(uwt_surf_describe_batch(tracker_->ctx(), 1, &a, &sp, _previous_frame->surf_keypoints_.data(), &n, n, kp[0].data(),
-                                         desc[0].data()), "uwt_surf_describe_batch");
-    } else {
-      surf_detect(a, sp, kp[0], desc[0]);
-    }
-    surf_detect(b, sp, kp[1], desc[1]);
-    std::array<std::vector<float>, 2> xy;
-    for (int f = 0; f < 2; f++)
-      for (const uwt_keypoint& k : kp[f]) xy[(size_t)f].insert(xy[(size_t)f].end(), {k.x, k.y});
-    std::vector<uwt_match> good = DetectAndTrackFeatures(_previous_frame, _current_frame, desc[0].data(), (int)kp[0].size(), desc[1].data(),
-                                                         (int)kp[1].size(), 64, xy);
-    _previous_frame->surf_keypoints_.clear();
-    _current_frame->surf_keypoints_.clear();
-    for (const uwt_match& mt : good) {
-      _previous_frame->surf_keypoints_.push_back(kp[0][(size_t)mt.query_idx]);
-      _current_frame->surf_keypoints_.push_back(kp[1][(size_t)mt.train_idx]);
-    }
-    return good;
+    return track(_previous_frame, _current_frame, a, b, usekeypoints, sp, uwt_surf_detect_describe_batch, "uwt_surf_detect_describe_batch",
+                 uwt_surf_describe_batch, "uwt_surf_describe_batch", 64, &Frame::surf_keypoints_);
   }
 
   float ratio_ = 0.65f;      // include/Tracker.h:80
@@ -660,67 +653,59 @@ class RobustMatcher {
   std::vector<int8_t> orb_pattern_;    // empty: the library's default pattern; else 256 x (x0, y0, x1, y1) (uwt_orb_set_pattern)
 
  private:
-  // :210-223 and on: ORB on both frames — the previous one described at the records it kept when usekeypoints is set and it has
-  // some (:216-218), the current one detected — then the matcher under Hamming, ransacTest and the assignment
-  std::vector<uwt_match> track_orb(Frame* _previous_frame, Frame* _current_frame, int a, int b, bool usekeypoints) {
-    uwt_orb_params op;
-    uwt_default_orb_params(&op);
-    op.n_features = n_features_;
-    op.n_levels = n_levels_;
-    op.edge_threshold = edge_threshold_;
-    op.fast_threshold = fast_threshold_;
-    op.upright = upright_ ? 1 : 0;
-    if (!orb_pattern_.empty() && orb_pattern_.size() != 1024) throw std::invalid_argument("RobustMatcher: orb_pattern_ holds 1024 entries");
-    if (orb_pattern_ != pattern_sent_) {   // (the context keeps a pattern until it is given another)
-      surf_check(uwt_orb_set_pattern(tracker_->ctx(), orb_pattern_.empty() ? nullptr : orb_pattern_.data()), "uwt_orb_set_pattern");
-      pattern_sent_ = orb_pattern_;
-    }
+  // A detector's two entries, P its parameter block and D an element of its descriptor rows:
+  //   uwt_surf_detect_describe_batch(ctx, n_frames, slots, &params, cap, kp_out, desc_out, counts_out), or ORB's of the same shape;
+  //   uwt_surf_describe_batch(ctx, n_frames, slots, &params, keypoints_in, n_in, cap, kp_out, desc_out), or ORB's.
+  template <typename P, typename D>
+  using DetectFn = int (*)(uwt_ctx*, int32_t, const int32_t*, const P*, int32_t, uwt_keypoint*, D*, int32_t*);
+  template <typename P, typename D>
+  using DescribeFn = int (*)(uwt_ctx*, int32_t, const int32_t*, const P*, const uwt_keypoint*, const int32_t*, int32_t, uwt_keypoint*, D*);
+
+  // :186-223 and on, either detector: the previous frame described at the records it kept (Frame::*kept) when usekeypoints is set and
+  // it has some (:192-195, :216-218), else detected; the current one detected; then the matcher over rows of `row` elements,
+  // ransacTest and the assignment
+  template <typename P, typename D>
+  std::vector<uwt_match> track(Frame* _previous_frame, Frame* _current_frame, int a, int b, bool usekeypoints, const P& params,
+                               DetectFn<P, D> detect_fn, const char* detect_name, DescribeFn<P, D> describe_fn, const char* describe_name,
+                               int row, std::vector<uwt_keypoint> Frame::*kept) {
     std::vector<uwt_keypoint> kp[2];
-    std::vector<uint8_t> desc[2];
-    if (usekeypoints && !_previous_frame->orb_keypoints_.empty()) {
-      const int32_t n = (int32_t)_previous_frame->orb_keypoints_.size();
+    std::vector<D> desc[2];
+    const std::vector<uwt_keypoint>& had = _previous_frame->*kept;
+    if (usekeypoints && !had.empty()) {
+      const int32_t n = (int32_t)had.size();
       kp[0].resize((size_t)n);
-      desc[0].resize((size_t)n * 32);
-      surf_check(uwt_orb_describe_batch(tracker_->ctx(), 1, &a, &op, _previous_frame->orb_keypoints_.data(), &n, n, kp[0].data(),
-                                        desc[0].data()), "uwt_orb_describe_batch");
+      desc[0].resize((size_t)n * (size_t)row);
+      status(describe_fn(tracker_->ctx(), 1, &a, &params, had.data(), &n, n, kp[0].data(), desc[0].data()), describe_name);
     } else {
-      orb_detect(a, op, kp[0], desc[0]);
+      detect(a, params, detect_fn, detect_name, row, kp[0], desc[0]);
     }
-    orb_detect(b, op, kp[1], desc[1]);
+    detect(b, params, detect_fn, detect_name, row, kp[1], desc[1]);
     std::array<std::vector<float>, 2> xy;
     for (int f = 0; f < 2; f++)
       for (const uwt_keypoint& k : kp[f]) xy[(size_t)f].insert(xy[(size_t)f].end(), {k.x, k.y});
     std::vector<uwt_match> good = DetectAndTrackFeatures(_previous_frame, _current_frame, desc[0].data(), (int)kp[0].size(), desc[1].data(),
-                                                         (int)kp[1].size(), 32, xy);
-    _previous_frame->orb_keypoints_.clear();
-    _current_frame->orb_keypoints_.clear();
+                                                         (int)kp[1].size(), row, xy);
+    (_previous_frame->*kept).clear();
+    (_current_frame->*kept).clear();
     for (const uwt_match& mt : good) {
-      _previous_frame->orb_keypoints_.push_back(kp[0][(size_t)mt.query_idx]);
-      _current_frame->orb_keypoints_.push_back(kp[1][(size_t)mt.train_idx]);
+      (_previous_frame->*kept).push_back(kp[0][(size_t)mt.query_idx]);
+      (_current_frame->*kept).push_back(kp[1][(size_t)mt.train_idx]);
     }
     return good;
   }
-  void orb_detect(int slot, const uwt_orb_params& op, std::vector<uwt_keypoint>& kp, std::vector<uint8_t>& desc) {
+  template <typename P, typename D>
+  void detect(int slot, const P& params, DetectFn<P, D> detect_fn, const char* detect_name, int row, std::vector<uwt_keypoint>& kp,
+              std::vector<D>& desc) {
     kp.resize((size_t)surf_cap_);
-    desc.resize((size_t)surf_cap_ * 32);
+    desc.resize((size_t)surf_cap_ * (size_t)row);
     int32_t count = 0;
-    surf_check(uwt_orb_detect_describe_batch(tracker_->ctx(), 1, &slot, &op, surf_cap_, kp.data(), desc.data(), &count),
-               "uwt_orb_detect_describe_batch");
+    status(detect_fn(tracker_->ctx(), 1, &slot, &params, surf_cap_, kp.data(), desc.data(), &count), detect_name);
     kp.resize((size_t)count);
-    desc.resize((size_t)count * 32);
+    desc.resize((size_t)count * (size_t)row);
   }
   std::vector<int8_t> pattern_sent_;
-  void surf_check(int st, const char* what) {
+  void status(int st, const char* what) {
     if (st != UWT_OK) throw std::runtime_error(std::string(what) + ": " + uwt_status_string(st) + " (" + uwt_last_error(tracker_->ctx()) + ")");
-  }
-  void surf_detect(int slot, const uwt_surf_params& sp, std::vector<uwt_keypoint>& kp, std::vector<float>& desc) {
-    kp.resize((size_t)surf_cap_);
-    desc.resize((size_t)surf_cap_ * 64);
-    int32_t count = 0;
-    surf_check(uwt_surf_detect_describe_batch(tracker_->ctx(), 1, &slot, &sp, surf_cap_, kp.data(), desc.data(), &count),
-               "uwt_surf_detect_describe_batch");
-    kp.resize((size_t)count);
-    desc.resize((size_t)count * 64);
   }
   std::vector<uwt_match> match(int norm, const void* a, int n, const void* b, int m, int dim, size_t elem) {
     if (n < 0 || m < 0 || dim < 1) throw std::invalid_argument("MatchDescriptors: negative count or dim < 1");

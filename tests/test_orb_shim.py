@@ -38,18 +38,23 @@ def test_cpp_mirror_calls_what_the_python_mirror_calls():
     py = open(os.path.join(ROOT, "uw-slam_amd", "tracker.py")).read()
     assert re.search(r"explicit RobustMatcher\(Tracker\* tracker, int detector = 0\)", hpp)
     assert re.search(r"def __init__\(self, ctx_or_tracker, .*detector=0\)", py)
-    cpp_orb = hpp[hpp.index("track_orb(Frame* _previous_frame"):hpp.index("std::vector<int8_t> pattern_sent_;")]
-    py_orb = py[py.index("def _track_orb"):py.index("def _track_descriptors")]
+    # both mirrors have one body for both detectors; what is ORB's own is its branch (C++) and its table entry (Python)
+    cpp_orb = hpp[hpp.index("if (detector_ == 1) {"):hpp.index("uwt_surf_params sp;")]
+    cpp_body = hpp[hpp.index("std::vector<uwt_match> track(Frame* _previous_frame"):hpp.index("std::vector<int8_t> pattern_sent_;")]
+    py_body = py[py.index("build, detect, describe, kept = self._DETECTORS[self.detector_]"):py.index("_DETECTORS = {")]
+    py_orb = py[py.index("        1: (lambda self: capi.default_orb_params("):py.index("def _track_descriptors")]
     # the same entries in the same order: the pattern, describe at the kept records or detect, detect the current frame
-    cpp_calls = re.findall(r"\b(uwt_orb_set_pattern|uwt_orb_describe_batch|orb_detect|uwt_orb_detect_describe_batch)\(", cpp_orb)
-    py_calls = re.findall(r"\.(orb_set_pattern|orb_describe_batch|orb_detect_describe_batch)\(", py_orb)
-    assert cpp_calls[:4] == ["uwt_orb_set_pattern", "uwt_orb_describe_batch", "orb_detect", "orb_detect"]
-    assert "uwt_orb_detect_describe_batch" in cpp_calls
-    assert py_calls == ["orb_set_pattern", "orb_describe_batch", "orb_detect_describe_batch", "orb_detect_describe_batch"]
+    cpp_calls = re.findall(r"\b(uwt_orb_set_pattern|uwt_orb_describe_batch|uwt_orb_detect_describe_batch)\b", cpp_orb)
+    assert cpp_calls == [n for n in ("uwt_orb_set_pattern", "uwt_orb_detect_describe_batch", "uwt_orb_describe_batch") for _ in "12"]   # (entry, its name)
+    assert re.findall(r"\b(describe_fn|detect|detect_fn)\(", cpp_body) == ["describe_fn", "detect", "detect", "detect", "detect_fn"]
+    py_calls = re.findall(r"(orb_set_pattern\(|getattr\(ctx, describe\)\(|getattr\(ctx, detect\)\()", py_body)
+    assert py_calls == ["orb_set_pattern(", "getattr(ctx, describe)(", "getattr(ctx, detect)(", "getattr(ctx, detect)("]
+    assert '"orb_detect_describe_batch", "orb_describe_batch", "orb_keypoints_"' in py_orb
     for field in ("n_features", "n_levels", "edge_threshold", "fast_threshold", "upright"):
         assert "op.%s = " % field in cpp_orb and "%s=" % field in py_orb, field
-    assert "orb_keypoints_" in cpp_orb and "orb_keypoints_" in py_orb and "surf_keypoints_" not in cpp_orb + py_orb
-    assert ", 32, xy)" in cpp_orb     # 32-byte rows: the uint8 overload, Hamming
+    assert "orb_keypoints_" in cpp_orb and "surf_keypoints_" not in cpp_orb + py_orb
+    assert '"uwt_orb_describe_batch", 32, &Frame::orb_keypoints_)' in cpp_orb     # 32-byte rows: the uint8 overload, Hamming
+    assert "track_orb" not in hpp + py   # one body each
 
 
 @pytest.mark.gpu

@@ -859,31 +859,23 @@ class Context:
                                                        C.c_void_p(d_info_ptr)))
         return kp_cap
 
-    def surf_detect_describe_batch(self, slots, params=None, cap=UWT_MATCH_MAX_ROWS, describe=True, out=None):
-        """SURF key points and descriptors of the frames resident in `slots` (uwt_surf_detect_describe_batch).  Returns one
-        (key points KEYPOINT [n], descriptors float32 [n, 64] or None) per frame.  out: (kp [F, cap] KEYPOINT, desc [F, cap, 64]
-        float32 or None, counts [F] int32) to be written in place — the rows past a frame's count stay as they are."""
+    # ---- SURF and ORB detection and description: one helper per form; fn: the library's entry, dtype / row: a descriptor row
+    def _detect_describe(self, fn, dtype, row, slots, params, cap, describe, out):
         slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
         F = slots.size
         if out is None:
-            out = (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, 64), np.float32) if describe else None, np.zeros(F, np.int32))
+            out = (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, row), dtype) if describe else None, np.zeros(F, np.int32))
         kp, desc, cnt = out
-        self._chk(lib().uwt_surf_detect_describe_batch(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None,
-                                                       cap, C.c_void_p(kp.ctypes.data),
-                                                       C.c_void_p(desc.ctypes.data) if desc is not None else None, _p(cnt, C.c_int32)))
+        self._chk(fn(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None, cap, C.c_void_p(kp.ctypes.data),
+                     C.c_void_p(desc.ctypes.data) if desc is not None else None, _p(cnt, C.c_int32)))
         return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy() if desc is not None else None) for i in range(F)]
 
-    def surf_detect_describe_batch_async(self, slots, d_kp_ptr, d_desc_ptr, d_counts_ptr, params=None, cap=UWT_MATCH_MAX_ROWS):
-        """The same enqueued on the context stream, results in device memory (d_kp_ptr: F x cap KEYPOINT, d_desc_ptr: F x cap x 64
-        float32 or None, d_counts_ptr: F int32); sync() to wait."""
+    def _detect_describe_async(self, fn, slots, d_kp_ptr, d_desc_ptr, d_counts_ptr, params, cap):
         slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        self._chk(lib().uwt_surf_detect_describe_batch_async(self._h, slots.size, _p(slots, C.c_int32),
-                                                             C.byref(params) if params is not None else None, cap, C.c_void_p(d_kp_ptr),
-                                                             C.c_void_p(d_desc_ptr) if d_desc_ptr else None, C.c_void_p(d_counts_ptr)))
+        self._chk(fn(self._h, slots.size, _p(slots, C.c_int32), C.byref(params) if params is not None else None, cap,
+                     C.c_void_p(d_kp_ptr), C.c_void_p(d_desc_ptr) if d_desc_ptr else None, C.c_void_p(d_counts_ptr)))
 
-    def surf_describe_batch(self, slots, keypoints_list, params=None, cap=None):
-        """Orientation and descriptors at the caller's key points (uwt_surf_describe_batch: useProvidedKeypoints): keypoints_list
-        holds one KEYPOINT array per frame (x, y, size are read).  Returns one (key points with directions, descriptors) per frame."""
+    def _describe(self, fn, dtype, row, slots, keypoints_list, params, cap, out):
         slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
         kin = [np.ascontiguousarray(k, KEYPOINT).reshape(-1) for k in keypoints_list]
         cap = max([cap or 1] + [len(k) for k in kin])
@@ -891,11 +883,26 @@ class Context:
         kp, n = np.zeros((F, cap), KEYPOINT), np.zeros(F, np.int32)
         for i, k in enumerate(kin):
             kp[i, :len(k)], n[i] = k, len(k)
-        out, desc = np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, 64), np.float32)
-        self._chk(lib().uwt_surf_describe_batch(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None,
-                                                C.c_void_p(kp.ctypes.data), _p(n, C.c_int32), cap, C.c_void_p(out.ctypes.data),
-                                                C.c_void_p(desc.ctypes.data)))
-        return [(out[i, :n[i]].copy(), desc[i, :n[i]].copy()) for i in range(F)]
+        res, desc = out if out is not None else (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, row), dtype))
+        self._chk(fn(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None, C.c_void_p(kp.ctypes.data),
+                     _p(n, C.c_int32), cap, C.c_void_p(res.ctypes.data), C.c_void_p(desc.ctypes.data)))
+        return [(res[i, :n[i]].copy(), desc[i, :n[i]].copy()) for i in range(F)]
+
+    def surf_detect_describe_batch(self, slots, params=None, cap=UWT_MATCH_MAX_ROWS, describe=True, out=None):
+        """SURF key points and descriptors of the frames resident in `slots` (uwt_surf_detect_describe_batch).  Returns one
+        (key points KEYPOINT [n], descriptors float32 [n, 64] or None) per frame.  out: (kp [F, cap] KEYPOINT, desc [F, cap, 64]
+        float32 or None, counts [F] int32) to be written in place — the rows past a frame's count stay as they are."""
+        return self._detect_describe(lib().uwt_surf_detect_describe_batch, np.float32, 64, slots, params, cap, describe, out)
+
+    def surf_detect_describe_batch_async(self, slots, d_kp_ptr, d_desc_ptr, d_counts_ptr, params=None, cap=UWT_MATCH_MAX_ROWS):
+        """The same enqueued on the context stream, results in device memory (d_kp_ptr: F x cap KEYPOINT, d_desc_ptr: F x cap x 64
+        float32 or None, d_counts_ptr: F int32); sync() to wait."""
+        self._detect_describe_async(lib().uwt_surf_detect_describe_batch_async, slots, d_kp_ptr, d_desc_ptr, d_counts_ptr, params, cap)
+
+    def surf_describe_batch(self, slots, keypoints_list, params=None, cap=None):
+        """Orientation and descriptors at the caller's key points (uwt_surf_describe_batch: useProvidedKeypoints): keypoints_list
+        holds one KEYPOINT array per frame (x, y, size are read).  Returns one (key points with directions, descriptors) per frame."""
+        return self._describe(lib().uwt_surf_describe_batch, np.float32, 64, slots, keypoints_list, params, cap, None)
 
     def orb_set_pattern(self, pattern=None):
         """Loads a sampling pattern (int8 [256, 4]; uwt_orb_set_pattern) for the ORB calls that follow; None restores the default."""
@@ -907,40 +914,18 @@ class Context:
         """ORB key points and descriptors of the frames resident in `slots` (uwt_orb_detect_describe_batch).  Returns one
         (key points KEYPOINT [n], descriptors uint8 [n, 32] or None) per frame.  out: (kp [F, cap] KEYPOINT, desc [F, cap, 32]
         uint8 or None, counts [F] int32) to be written in place — the rows past a frame's count stay as they are."""
-        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        F = slots.size
-        if out is None:
-            out = (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, 32), np.uint8) if describe else None, np.zeros(F, np.int32))
-        kp, desc, cnt = out
-        self._chk(lib().uwt_orb_detect_describe_batch(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None,
-                                                      cap, C.c_void_p(kp.ctypes.data),
-                                                      C.c_void_p(desc.ctypes.data) if desc is not None else None, _p(cnt, C.c_int32)))
-        return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy() if desc is not None else None) for i in range(F)]
+        return self._detect_describe(lib().uwt_orb_detect_describe_batch, np.uint8, 32, slots, params, cap, describe, out)
 
     def orb_detect_describe_batch_async(self, slots, d_kp_ptr, d_desc_ptr, d_counts_ptr, params=None, cap=UWT_MATCH_MAX_ROWS):
         """The same enqueued on the context stream, results in device memory (d_kp_ptr: F x cap KEYPOINT, d_desc_ptr: F x cap x 32
         bytes or None, d_counts_ptr: F int32); sync() to wait."""
-        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        self._chk(lib().uwt_orb_detect_describe_batch_async(self._h, slots.size, _p(slots, C.c_int32),
-                                                            C.byref(params) if params is not None else None, cap, C.c_void_p(d_kp_ptr),
-                                                            C.c_void_p(d_desc_ptr) if d_desc_ptr else None, C.c_void_p(d_counts_ptr)))
+        self._detect_describe_async(lib().uwt_orb_detect_describe_batch_async, slots, d_kp_ptr, d_desc_ptr, d_counts_ptr, params, cap)
 
     def orb_describe_batch(self, slots, keypoints_list, params=None, cap=None, out=None):
         """Direction and descriptors at the caller's key points (uwt_orb_describe_batch: useProvidedKeypoints): keypoints_list
         holds one KEYPOINT array per frame (x, y, octave are read).  Returns one (key points with directions, descriptors) per
         frame.  out: (kp [F, cap] KEYPOINT, desc [F, cap, 32] uint8) to be written in place."""
-        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        kin = [np.ascontiguousarray(k, KEYPOINT).reshape(-1) for k in keypoints_list]
-        cap = max([cap or 1] + [len(k) for k in kin])
-        F = slots.size
-        kp, n = np.zeros((F, cap), KEYPOINT), np.zeros(F, np.int32)
-        for i, k in enumerate(kin):
-            kp[i, :len(k)], n[i] = k, len(k)
-        res, desc = out if out is not None else (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, 32), np.uint8))
-        self._chk(lib().uwt_orb_describe_batch(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None,
-                                               C.c_void_p(kp.ctypes.data), _p(n, C.c_int32), cap, C.c_void_p(res.ctypes.data),
-                                               C.c_void_p(desc.ctypes.data)))
-        return [(res[i, :n[i]].copy(), desc[i, :n[i]].copy()) for i in range(F)]
+        return self._describe(lib().uwt_orb_describe_batch, np.uint8, 32, slots, keypoints_list, params, cap, out)
 
     def orb_layer(self, slot, level):
         """One layer of the ORB scale pyramid of a slot (uwt_orb_layer): uint8 [h_l, w_l]"""

@@ -1,6 +1,4 @@
 // uwt_capi_orb.hip — host side of libuwt_hip.so: ORB detection and description.
-#include <functional>
-
 #include "uwt_ctx.h"
 #include "uwt_orb.h"
 
@@ -85,46 +83,9 @@ int uwt_orb_set_pattern(uwt_ctx* c, const int8_t* pattern_or_null) {
   return UWT_OK;
 }
 
-static_assert(sizeof(OrbKeypoint) == sizeof(uwt_keypoint), "uwt_keypoint layout");
 static_assert(sizeof(uwt_orb_params) == 20, "uwt_orb_params layout");
 
 namespace {
-
-constexpr size_t kOrbChunkBytes = 256u << 20;   // scratch a chunk of frames may take
-constexpr int kOrbMaxChunk = 4096;              // frames of a chunk at most (a launch's grid)
-
-// the geometry of a call: the layers, the quotas and, when the call detects, the bounds of the candidate lists
-void orb_plan(const uwt_ctx* c, const uwt_orb_params& op, bool detect, OrbArgs* a) {
-  const LevelK& L = c->lv[0];
-  a->img = c->img[0];
-  a->frame_stride = (size_t)L.n;
-  a->pitch = L.pitch;
-  a->w = c->p.width;
-  a->h = c->p.height;
-  a->n_levels = op.n_levels;
-  a->edge = op.edge_threshold;
-  a->fast_threshold = op.fast_threshold;
-  a->upright = op.upright ? 1 : 0;
-  int32_t quota[kOrbMaxLevels] = {};
-  uwt_orb_level_quota(op.n_features, op.n_levels, quota);
-  size_t loff = 0, roff = 0;
-  long long kept = 0;
-  for (int l = 0; l < kOrbMaxLevels; l++) {
-    const bool on = l < op.n_levels;
-    a->lw[l] = on ? orb_layer_dim(a->w, l) : 0;
-    a->lh[l] = on ? orb_layer_dim(a->h, l) : 0;
-    a->loff[l] = loff;
-    if (l > 0) loff += (size_t)a->lw[l] * (size_t)a->lh[l];
-    a->quota[l] = on && detect ? quota[l] : 0;
-    kept += a->quota[l];
-    a->raw_cap[l] = on && detect ? (int)orb_raw_bound(a->lw[l], a->lh[l], a->edge) : 0;
-    a->raw_off[l] = roff;
-    roff += (size_t)a->raw_cap[l];
-  }
-  a->layer_stride = (loff + 15) & ~(size_t)15;
-  a->raw_stride = roff;
-  a->kept_stride = (int)kept;
-}
 
 // the scratch of a chunk of nf frames: [slots | raw counts | counts | layers | raw keys | raw H | kept | keep | key points | descriptors | extra]
 struct OrbLayout {
@@ -148,13 +109,6 @@ OrbLayout orb_layout(const OrbArgs& g, int nf, int cap, size_t extra) {
   return l;
 }
 
-// frames of a chunk: as many as kOrbChunkBytes hold, one at least
-int orb_chunk_frames(const OrbArgs& g, int n_frames, int cap) {
-  const size_t per = orb_layout(g, 1, cap, 0).total;
-  const size_t fit = std::max<size_t>(1, kOrbChunkBytes / per);
-  return (int)std::min<size_t>(fit, (size_t)std::min(n_frames, kOrbMaxChunk));
-}
-
 // the context's pattern on the device: the default one the first time, a new one behind uwt_orb_set_pattern
 int orb_pattern_ready(uwt_ctx* c) {
   if (c->orb_pattern_state == 0) {
@@ -170,42 +124,8 @@ int orb_pattern_ready(uwt_ctx* c) {
   return UWT_OK;
 }
 
-// Grows the scratch to a chunk of nf frames, sends the chunk's slot list and enqueues the layers.  g: the call's geometry; *a: the chunk.
-int orb_begin_chunk(uwt_ctx* c, const OrbArgs& g, const int32_t* slots, int nf, int cap, size_t extra, OrbArgs* a, unsigned char** extra_out) {
-  const OrbLayout l = orb_layout(g, nf, cap, extra);
-  int st = c->orb_buf.reserve(c, c->stream, l.total);
-  if (st) return st;
-  st = orb_pattern_ready(c);
-  if (st) return st;
-  unsigned char* b = (unsigned char*)c->orb_buf.p;
-  *a = g;
-  a->slots = (const int*)(b + l.slots);
-  a->n_frames = nf;
-  a->layers = b + l.layers;
-  a->raw_key = (unsigned long long*)(b + l.raw_key);
-  a->raw_h = (long long*)(b + l.raw_h);
-  a->raw_count = (int*)(b + l.raw_count);
-  a->kept = (OrbKept*)(b + l.kept);
-  a->keep = b + l.keep;
-  a->kp = (OrbKeypoint*)(b + l.kp);
-  a->desc = b + l.desc;
-  a->counts = (int*)(b + l.counts);
-  a->cap = cap;
-  a->pattern = (const signed char*)c->orb_pat.p;
-  if (extra_out) *extra_out = b + l.extra;
-  HIPCHK(c, hipMemcpyAsync((void*)a->slots, slots, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(a->raw_count, 0, sizeof(int) * (size_t)nf * kOrbMaxLevels, c->stream));
-  launch_orb_layers(c->stream, *a);
-  HIPCHK(c, hipGetLastError());
-  return UWT_OK;
-}
-
-// The checks of an ORB call; *op: the parameters in force.  Nothing is enqueued when a check fails.
-int orb_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_orb_params* params, uwt_orb_params* op) {
-  if (n_frames < 1 || cap < 1 || !slots) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_frames < 1, cap < 1 or a null list");
-  if (cap > UWT_MATCH_MAX_ROWS) return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS");
-  for (int f = 0; f < n_frames; f++)
-    if (!slot_range_ok(c, slots[f], 1)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": slot out of range");
+// the parameters in force (*op) and their checks
+int orb_params_check(uwt_ctx* c, const char* what, const uwt_orb_params* params, uwt_orb_params* op) {
   if (params) *op = *params;
   else uwt_default_orb_params(op);
   if (op->n_features < 1 || op->n_features > kOrbMaxFeatures || op->n_levels < 1 || op->n_levels > kOrbMaxLevels)
@@ -217,135 +137,123 @@ int orb_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, 
   return UWT_OK;
 }
 
-// Key points (detected, or the caller's host lists kp_in / n_in: n_frames x cap, described as they are), then directions and
-// descriptors, for n_frames frames in chunks.  The results of a chunk are in its scratch; `deliver` takes them (first frame of the
-// chunk, the chunk's arguments) before the next chunk runs.
-int orb_run(uwt_ctx* c, const uwt_orb_params& op, int n_frames, const int32_t* slots, int cap, const uwt_keypoint* kp_in, const int32_t* n_in,
-            bool want_desc, const std::function<int(int, const OrbArgs&)>& deliver) {
-  int st = compute_begin_pairs(c, n_frames, slots, slots);
-  if (st) return st;
-  OrbArgs g;
-  orb_plan(c, op, kp_in == nullptr, &g);
-  const int chunk = orb_chunk_frames(g, n_frames, cap);
-  for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-    const int nf = std::min(chunk, n_frames - f0);
-    OrbArgs a;
-    st = orb_begin_chunk(c, g, slots + f0, nf, cap, 0, &a, nullptr);
-    if (st) return st;
-    int rows = std::min(cap, std::max(g.kept_stride, 1));
-    if (kp_in) {
-      rows = 0;
-      for (int f = 0; f < nf; f++) rows = std::max(rows, n_in[f0 + f]);
-      HIPCHK(c, hipMemcpyAsync(a.counts, n_in + f0, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(a.kp, kp_in + (size_t)f0 * cap, sizeof(OrbKeypoint) * (size_t)cap * nf, hipMemcpyHostToDevice, c->stream));
-    } else {
-      launch_orb_detect(c->stream, a);
-    }
-    if (!want_desc) a.desc = nullptr;
-    launch_orb_describe(c->stream, a, rows);
-    HIPCHK(c, hipGetLastError());
-    st = deliver(f0, a);
-    if (st) return st;
-  }
-  return UWT_OK;
-}
-
-// the chunk's results to the caller's device arrays, every row of the chunk (d_desc is not written when the chunk has no descriptors)
-int orb_deliver_device(uwt_ctx* c, int f0, const OrbArgs& a, uwt_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts) {
-  const size_t recs = (size_t)a.n_frames * a.cap, g0 = (size_t)f0 * a.cap;
-  HIPCHK(c, hipMemcpyAsync(d_counts + f0, a.counts, sizeof(int) * (size_t)a.n_frames, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_kp + g0, a.kp, sizeof(OrbKeypoint) * recs, hipMemcpyDeviceToDevice, c->stream));
-  if (a.desc) HIPCHK(c, hipMemcpyAsync(d_desc + g0 * 32, a.desc, 32 * recs, hipMemcpyDeviceToDevice, c->stream));
-  return UWT_OK;
-}
-
-// the chunk's results to host memory: only the rows below each frame's count are written
-int orb_deliver_host(uwt_ctx* c, int f0, const OrbArgs& a, uwt_keypoint* kp_out, uint8_t* desc_out, int32_t* counts_out) {
-  std::vector<int32_t> cnt((size_t)a.n_frames);
-  HIPCHK(c, hipMemcpyAsync(cnt.data(), a.counts, sizeof(int) * (size_t)a.n_frames, hipMemcpyDeviceToHost, c->stream));
-  const size_t g0 = (size_t)f0 * a.cap;
-  int st = rows_to_host(c, a.cap, a.n_frames, {{a.kp, sizeof(OrbKeypoint), cnt.data(), kp_out + g0},
-                                                {a.desc, 32, cnt.data(), a.desc ? desc_out + g0 * 32 : nullptr}});
-  if (!st && counts_out)
-    for (int f = 0; f < a.n_frames; f++) counts_out[f0 + f] = std::min(std::max(cnt[(size_t)f], 0), a.cap);
-  return st;
-}
-
-// one frame's chunk for a per-stage entry: the checks, the stream order and the layers up to `level`
-int orb_stage_begin(uwt_ctx* c, const char* what, int32_t slot, int32_t level, bool detect, size_t extra, OrbArgs* a, unsigned char** x) {
-  if (level < 0 || level >= kOrbMaxLevels) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": level outside 0..7");
+// One ORB call: its parameters, its geometry (g), its chunk (a), and the driver's parts over them.
+struct OrbCall {
+  uwt_ctx* c;
+  int cap;
   uwt_orb_params op;
-  int st = orb_check(c, what, 1, &slot, 1, nullptr, &op);
-  if (st) return st;
-  st = compute_begin(c, slot, 1);
-  if (st) return st;
-  OrbArgs g;
-  orb_plan(c, op, detect, &g);
-  return orb_begin_chunk(c, g, &slot, 1, 1, extra, a, x);
-}
+  OrbArgs g, a;
+  Detector d;
+
+  OrbCall(uwt_ctx* c_, const uwt_orb_params* params, int cap_) : c(c_), cap(cap_) {
+    d.prepare = [this, params](const char* what, bool detect) {
+      const int st = orb_params_check(c, what, params, &op);
+      return st ? st : plan(detect);
+    };
+    d.kp_ok = [this](const uwt_keypoint& k) {
+      const int l = k.octave;
+      if (!(std::fabs(k.x) <= 1e6f && std::fabs(k.y) <= 1e6f && l >= 0 && l < op.n_levels)) return false;   // (a NaN fails)
+      const int gx = orb_layer_pos(k.x, l), gy = orb_layer_pos(k.y, l), e = op.edge_threshold;
+      return gx >= e && gx < orb_layer_dim(c->p.width, l) - e && gy >= e && gy < orb_layer_dim(c->p.height, l) - e;
+    };
+    d.kp_msg = ": a key point that is not finite, has an octave outside 0..n_levels-1 or lies closer than edge_threshold to a border of "
+               "its layer";
+    d.chunk = &a;
+    d.begin = [this](const int32_t* slots, int nf, size_t extra, unsigned char** x) { return begin(slots, nf, extra, x); };
+    d.detect = [this](int) { return launch_orb_detect(c->stream, a), (int)UWT_OK; };
+    d.describe = [this](int rows) { launch_orb_describe(c->stream, a, rows); };
+  }
+  // the geometry of a call: the layers, the quotas and, when the call detects, the bounds of the candidate lists
+  int plan(bool detect) {
+    detect_image(c, &g);
+    g.n_levels = op.n_levels;
+    g.edge = op.edge_threshold;
+    g.fast_threshold = op.fast_threshold;
+    g.upright = op.upright ? 1 : 0;
+    int32_t quota[kOrbMaxLevels] = {};
+    uwt_orb_level_quota(op.n_features, op.n_levels, quota);
+    size_t loff = 0, roff = 0;
+    long long kept = 0;
+    for (int l = 0; l < kOrbMaxLevels; l++) {
+      const bool on = l < op.n_levels;
+      g.lw[l] = on ? orb_layer_dim(g.w, l) : 0;
+      g.lh[l] = on ? orb_layer_dim(g.h, l) : 0;
+      g.loff[l] = loff;
+      if (l > 0) loff += (size_t)g.lw[l] * (size_t)g.lh[l];
+      g.quota[l] = on && detect ? quota[l] : 0;
+      kept += g.quota[l];
+      g.raw_cap[l] = on && detect ? (int)orb_raw_bound(g.lw[l], g.lh[l], g.edge) : 0;
+      g.raw_off[l] = roff;
+      roff += (size_t)g.raw_cap[l];
+    }
+    g.layer_stride = (loff + 15) & ~(size_t)15;
+    g.raw_stride = roff;
+    g.kept_stride = (int)kept;
+    d.frame_bytes = orb_layout(g, 1, cap, 0).total;
+    d.rows = std::min(cap, std::max(g.kept_stride, 1));
+    return UWT_OK;
+  }
+  // Grows the scratch to a chunk of nf frames, sends the chunk's slot list and the pattern, and enqueues the layers.
+  int begin(const int32_t* slots, int nf, size_t extra, unsigned char** extra_out) {
+    const OrbLayout l = orb_layout(g, nf, cap, extra);
+    int st = c->orb_buf.reserve(c, c->stream, l.total);
+    if (st) return st;
+    st = orb_pattern_ready(c);
+    if (st) return st;
+    unsigned char* b = (unsigned char*)c->orb_buf.p;
+    a = g;
+    a.slots = (const int*)(b + l.slots);
+    a.n_frames = nf;
+    a.layers = b + l.layers;
+    a.raw_key = (unsigned long long*)(b + l.raw_key);
+    a.raw_h = (long long*)(b + l.raw_h);
+    a.raw_count = (int*)(b + l.raw_count);
+    a.kept = (OrbKept*)(b + l.kept);
+    a.keep = b + l.keep;
+    a.kp = (OrbKeypoint*)(b + l.kp);
+    a.desc = b + l.desc;
+    a.desc_row = 32;
+    a.counts = (int*)(b + l.counts);
+    a.cap = cap;
+    a.pattern = (const signed char*)c->orb_pat.p;
+    if (extra_out) *extra_out = b + l.extra;
+    HIPCHK(c, hipMemcpyAsync((void*)a.slots, slots, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(a.raw_count, 0, sizeof(int) * (size_t)nf * kOrbMaxLevels, c->stream));
+    launch_orb_layers(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return UWT_OK;
+  }
+};
 
 }  // namespace
 
 int uwt_orb_detect_describe_batch(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params, int32_t cap,
                                   uwt_keypoint* kp_out, uint8_t* desc_out, int32_t* counts_out) {
-  if (c) (void)hipSetDevice(c->p.device);
-  const char* what = "uwt_orb_detect_describe_batch";
-  if (!c || !kp_out || !counts_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  uwt_orb_params op;
-  int st = orb_check(c, what, n_frames, slots, cap, params, &op);
-  if (st) return st;
-  return orb_run(c, op, n_frames, slots, cap, nullptr, nullptr, desc_out != nullptr,
-                 [&](int f0, const OrbArgs& a) { return orb_deliver_host(c, f0, a, kp_out, desc_out, counts_out); });
+  OrbCall o(c, params, cap);
+  return detect_entry(c, "uwt_orb_detect_describe_batch", o.d, DetectForm::host, n_frames, slots, cap, nullptr, nullptr, kp_out, desc_out, counts_out);
 }
 
 int uwt_orb_detect_describe_batch_async(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params, int32_t cap,
                                         uwt_keypoint* d_kp_out, uint8_t* d_desc_out, int32_t* d_counts_out) {
-  if (c) (void)hipSetDevice(c->p.device);
-  const char* what = "uwt_orb_detect_describe_batch_async";
-  if (!c || !d_kp_out || !d_counts_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  uwt_orb_params op;
-  int st = orb_check(c, what, n_frames, slots, cap, params, &op);
-  if (st) return st;
-  st = orb_run(c, op, n_frames, slots, cap, nullptr, nullptr, d_desc_out != nullptr,
-               [&](int f0, const OrbArgs& a) { return orb_deliver_device(c, f0, a, d_kp_out, d_desc_out, d_counts_out); });
-  if (st) return st;
-  return compute_end(c, c->dep_first, c->dep_n);
+  OrbCall o(c, params, cap);
+  return detect_entry(c, "uwt_orb_detect_describe_batch_async", o.d, DetectForm::device, n_frames, slots, cap, nullptr, nullptr, d_kp_out, d_desc_out,
+                      d_counts_out);
 }
 
 int uwt_orb_describe_batch(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params, const uwt_keypoint* keypoints_in,
                            const int32_t* n_in, int32_t cap, uwt_keypoint* kp_out, uint8_t* desc_out) {
-  if (c) (void)hipSetDevice(c->p.device);
-  const char* what = "uwt_orb_describe_batch";
-  if (!c || !keypoints_in || !n_in || !kp_out || !desc_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  uwt_orb_params op;
-  int st = orb_check(c, what, n_frames, slots, cap, params, &op);
-  if (st) return st;
-  for (int f = 0; f < n_frames; f++) {
-    if (n_in[f] < 0 || n_in[f] > cap) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key-point count outside 0..cap");
-    const uwt_keypoint* k = keypoints_in + (size_t)f * cap;
-    for (int i = 0; i < n_in[f]; i++) {
-      const int l = k[i].octave;
-      bool ok = std::fabs(k[i].x) <= 1e6f && std::fabs(k[i].y) <= 1e6f && l >= 0 && l < op.n_levels;   // (a NaN fails)
-      if (ok) {
-        const int gx = orb_layer_pos(k[i].x, l), gy = orb_layer_pos(k[i].y, l), e = op.edge_threshold;
-        ok = gx >= e && gx < orb_layer_dim(c->p.width, l) - e && gy >= e && gy < orb_layer_dim(c->p.height, l) - e;
-      }
-      if (!ok)
-        return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": a key point that is not finite, has an octave outside 0..n_levels-1 or "
-                                                                "lies closer than edge_threshold to a border of its layer");
-    }
-  }
-  // the device keeps every row of a chunk; only the rows below a frame's count come back
-  return orb_run(c, op, n_frames, slots, cap, keypoints_in, n_in, true,
-                 [&](int f0, const OrbArgs& a) { return orb_deliver_host(c, f0, a, kp_out, desc_out, nullptr); });
+  OrbCall o(c, params, cap);
+  return detect_entry(c, "uwt_orb_describe_batch", o.d, DetectForm::given, n_frames, slots, cap, keypoints_in, n_in, kp_out, desc_out, nullptr);
 }
 
 int uwt_orb_layer(uwt_ctx* c, int32_t slot, int32_t level, uint8_t* out, int32_t* lw, int32_t* lh) {
   if (c) (void)hipSetDevice(c->p.device);
   const char* what = "uwt_orb_layer";
   if (!c || !out || !lw || !lh) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  OrbArgs a;
-  int st = orb_stage_begin(c, what, slot, level, false, 0, &a, nullptr);
+  if (level < 0 || level >= kOrbMaxLevels) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": level outside 0..7");
+  OrbCall o(c, nullptr, 1);
+  const OrbArgs& a = o.a;
+  int st = stage_begin(c, what, o.d, slot, false, 0, nullptr);
   if (st) return st;
   const size_t w = (size_t)a.lw[level], h = (size_t)a.lh[level];
   if (w && h) {
@@ -366,9 +274,10 @@ int uwt_orb_fast_scores(uwt_ctx* c, int32_t slot, int32_t level, int32_t* out) {
   if (!c || !out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
   if (level < 0 || level >= kOrbMaxLevels) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": level outside 0..7");
   const size_t n = (size_t)orb_layer_dim(c->p.width, level) * (size_t)orb_layer_dim(c->p.height, level);
-  OrbArgs a;
+  OrbCall o(c, nullptr, 1);
+  OrbArgs& a = o.a;
   unsigned char* x = nullptr;
-  int st = orb_stage_begin(c, what, slot, level, true, sizeof(int) * n + 16, &a, &x);
+  int st = stage_begin(c, what, o.d, slot, true, sizeof(int) * n + 16, &x);
   if (st) return st;
   if (n) {
     HIPCHK(c, hipMemsetAsync(x, 0, sizeof(int) * n, c->stream));
@@ -390,11 +299,12 @@ int uwt_orb_harris(uwt_ctx* c, int32_t slot, int32_t level, const int32_t* xy, i
   for (int i = 0; i < n; i++)
     if (xy[2 * i] < 4 || xy[2 * i] >= lw - 4 || xy[2 * i + 1] < 4 || xy[2 * i + 1] >= lh - 4)
       return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": a pixel closer than 4 to a border of the layer");
-  OrbArgs a;
+  OrbCall o(c, nullptr, 1);
+  const OrbArgs& a = o.a;
   unsigned char* x = nullptr;
   Carve cv(16);
   const size_t at_xy = cv.take<int>(2 * (size_t)n), at_h = cv.take<long long>((size_t)n);
-  int st = orb_stage_begin(c, what, slot, level, false, cv.total(), &a, &x);
+  int st = stage_begin(c, what, o.d, slot, false, cv.total(), &x);
   if (st) return st;
   HIPCHK(c, hipMemcpyAsync(x + at_xy, xy, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
   launch_orb_harris(c->stream, a, level, (const int*)(x + at_xy), n, (long long*)(x + at_h));

@@ -1,6 +1,4 @@
 // uwt_capi_surf.hip — host side of libuwt_hip.so: SURF detection and description.
-#include <functional>
-
 #include "uwt_ctx.h"
 #include "uwt_surf.h"
 
@@ -22,13 +20,9 @@ double uwt_keypoint_angle_deg(float dir_x, float dir_y) {
   return a >= 360.0 ? 0.0 : a;
 }
 
-static_assert(sizeof(SurfKeypoint) == sizeof(uwt_keypoint) && sizeof(uwt_keypoint) == 32, "uwt_keypoint layout");
 static_assert(sizeof(uwt_surf_params) == 24, "uwt_surf_params layout");
 
 namespace {
-
-constexpr size_t kSurfChunkBytes = 256u << 20;   // scratch a chunk of frames may take
-constexpr int kSurfMaxChunk = 4096;              // frames of a chunk at most (a launch's grid)
 
 // the scratch of a chunk of nf frames: [slots | raw counts | counts | integral | raw | keys | keep | key points | descriptors | extra]
 struct SurfLayout {
@@ -52,183 +46,123 @@ SurfLayout surf_layout(const uwt_ctx* c, int nf, size_t raw_cap, int cap, size_t
   return l;
 }
 
-// frames of a chunk: as many as kSurfChunkBytes hold, one at least
-int surf_chunk_frames(const uwt_ctx* c, int n_frames, size_t raw_cap, int cap) {
-  const size_t per = surf_layout(c, 1, raw_cap, cap, 0).total;
-  const size_t fit = std::max<size_t>(1, kSurfChunkBytes / per);
-  return (int)std::min<size_t>(fit, (size_t)std::min(n_frames, kSurfMaxChunk));
-}
-
-// Grows the scratch to a chunk of nf frames, sends the chunk's slot list and enqueues the integral images.  *a describes the chunk.
-int surf_begin_chunk(uwt_ctx* c, const uwt_surf_params& sp, const int32_t* slots, int nf, size_t raw_cap, int cap, size_t extra,
-                     SurfArgs* a, unsigned char** extra_out) {
-  const SurfLayout l = surf_layout(c, nf, raw_cap, cap, extra);
-  int st = c->surf_buf.reserve(c, c->stream, l.total);
-  if (st) return st;
-  unsigned char* b = (unsigned char*)c->surf_buf.p;
-  const LevelK& L = c->lv[0];
-  a->img = c->img[0];
-  a->frame_stride = (size_t)L.n;
-  a->pitch = L.pitch;
-  a->w = c->p.width;
-  a->h = c->p.height;
-  a->slots = (const int*)(b + l.slots);
-  a->n_frames = nf;
-  a->integral = (uint32_t*)(b + l.integral);
-  a->threshold = sp.hessian_threshold;
-  a->n_octaves = sp.n_octaves;
-  a->layers = sp.n_octave_layers + 2;
-  a->upright = sp.upright ? 1 : 0;
-  a->raw = (SurfKeypoint*)(b + l.raw);
-  a->raw_key = (unsigned long long*)(b + l.key);
-  a->raw_count = (int*)(b + l.raw_count);
-  a->raw_cap = (int)raw_cap;
-  a->keep = b + l.keep;
-  a->kp = (SurfKeypoint*)(b + l.kp);
-  a->desc = (float*)(b + l.desc);
-  a->counts = (int*)(b + l.counts);
-  a->cap = cap;
-  if (extra_out) *extra_out = b + l.extra;
-  HIPCHK(c, hipMemcpyAsync((void*)a->slots, slots, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-  launch_surf_integral(c->stream, *a);
-  HIPCHK(c, hipGetLastError());
+// the parameters in force (*sp) and their checks
+int surf_params_check(uwt_ctx* c, const char* what, const uwt_surf_params* params, uwt_surf_params* sp) {
+  if (params) *sp = *params;
+  else uwt_default_surf_params(sp);
+  if (!std::isfinite(sp->hessian_threshold)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": threshold is not finite");
+  if (sp->n_octaves < 1 || sp->n_octaves > kSurfMaxOctaves || sp->n_octave_layers < 1 || sp->n_octave_layers > kSurfMaxLayers - 2)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_octaves or n_octave_layers outside 1..4");
+  if (((long long)c->p.width + 1) * ((long long)c->p.height + 1) >= (1ll << 31))
+    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": the integral image has 2^31 entries or more");
   return UWT_OK;
 }
 
-// where a run's key points come from: nothing set, every frame is detected; else one of the two groups (kp_in wins if both are set)
-struct SurfSource {
-  const uwt_keypoint* kp_in = nullptr;   // the caller's lists in host memory (n_frames x cap): described as they are, no detection
-  const int32_t* n_in = nullptr;         // their counts
-  // the tracking call (n_frames = 2 n_pairs), a path per previous frame decided on the device: surf_track_enqueue's arguments (uwt_ctx.h)
+// One SURF call: its parameters, its chunk, and the driver's parts over them.  With the device paths of the tracking call set
+// (n_frames = 2 n_pairs; surf_track_enqueue's arguments, uwt_ctx.h) a chunk's extra scratch holds the frames' modes: detection runs
+// under them (the blocks of a frame on another path return at once), k_surf_take_provided has put the provided records and counts
+// where detection would have, and describe, sized by cap, serves both.
+struct SurfCall {
+  uwt_ctx* c;
+  int cap;
+  uwt_surf_params sp;
+  size_t raw_cap = 0;
+  SurfArgs a;
   const int* d_path = nullptr;
   int n_pairs = 0;
   const uwt_keypoint* d_prev_kp = nullptr;
   const int32_t* d_n_prev = nullptr;
-};
+  int* mode = nullptr;   // the chunk's modes (a.mode) where d_path is set
+  Detector d;
 
-// Key points from `src`, then orientation and descriptors, for n_frames frames in chunks.  The results of a chunk are in its
-// scratch; `deliver` takes them (first frame of the chunk, the chunk's arguments) before the next chunk runs.  With device paths a
-// chunk's extra scratch holds the frames' modes: detection runs under them (the blocks of a frame on another path return at once),
-// k_surf_take_provided has put the provided records and counts where detection would have, and describe, sized by cap, serves both.
-int surf_run(uwt_ctx* c, const uwt_surf_params& sp, int n_frames, const int32_t* slots, int cap, const SurfSource& src, bool want_desc,
-             const std::function<int(int, const SurfArgs&)>& deliver) {
-  int st = compute_begin_pairs(c, n_frames, slots, slots);
-  if (st) return st;
-  const size_t raw_cap = src.kp_in ? 0 : surf_raw_bound(c->p.width, c->p.height, sp.n_octaves, sp.n_octave_layers + 2);
-  const int chunk = surf_chunk_frames(c, n_frames, raw_cap, cap);
-  for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-    const int nf = std::min(chunk, n_frames - f0);
-    SurfArgs a;
-    unsigned char* x = nullptr;
-    st = surf_begin_chunk(c, sp, slots + f0, nf, raw_cap, cap, src.d_path ? sizeof(int) * (size_t)nf : 0, &a, &x);
-    if (st) return st;
-    int rows = cap;
-    if (src.kp_in) {
-      rows = 0;
-      for (int f = 0; f < nf; f++) rows = std::max(rows, src.n_in[f0 + f]);
-      HIPCHK(c, hipMemcpyAsync(a.counts, src.n_in + f0, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(a.kp, src.kp_in + (size_t)f0 * cap, sizeof(SurfKeypoint) * (size_t)cap * nf, hipMemcpyHostToDevice, c->stream));
-    } else {
-      if (src.d_path) {
-        int* mode = reinterpret_cast<int*>(x);
-        a.mode = mode;
-        launch_surf_take_provided(c->stream, a, f0, src.n_pairs, src.d_path, reinterpret_cast<const SurfKeypoint*>(src.d_prev_kp),
-                                  src.d_n_prev, mode);
-      }
-      HIPCHK(c, hipMemsetAsync(a.raw_count, 0, sizeof(int) * (size_t)nf, c->stream));
+  SurfCall(uwt_ctx* c_, const uwt_surf_params* params, int cap_) : c(c_), cap(cap_) {
+    d.prepare = [this, params](const char* what, bool detect) {
+      const int st = surf_params_check(c, what, params, &sp);
+      return st ? st : plan(detect);
+    };
+    d.kp_ok = [](const uwt_keypoint& k) { return surf_keypoint_ok(k.x, k.y, k.size); };
+    d.kp_msg = ": key point outside |x|, |y| <= 1e6, 0 < size <= 4096";
+    d.chunk = &a;
+    d.begin = [this](const int32_t* slots, int nf, size_t extra, unsigned char** x) { return begin(slots, nf, extra, x); };
+    d.detect = [this](int f0) {
+      if (d_path)
+        launch_surf_take_provided(c->stream, a, f0, n_pairs, d_path, reinterpret_cast<const SurfKeypoint*>(d_prev_kp), d_n_prev, mode);
+      HIPCHK(c, hipMemsetAsync(a.raw_count, 0, sizeof(int) * (size_t)a.n_frames, c->stream));
       launch_surf_detect(c->stream, a);
-    }
-    if (!want_desc) a.desc = nullptr;
-    launch_surf_describe(c->stream, a, rows);
-    HIPCHK(c, hipGetLastError());
-    st = deliver(f0, a);
-    if (st) return st;
+      return (int)UWT_OK;
+    };
+    d.describe = [this](int rows) { launch_surf_describe(c->stream, a, rows); };
   }
-  return UWT_OK;
-}
-
-// the chunk's results to the caller's device arrays, every row of the chunk (d_desc is not written when the chunk has no descriptors)
-int surf_deliver_device(uwt_ctx* c, int f0, const SurfArgs& a, uwt_keypoint* d_kp, float* d_desc, int32_t* d_counts) {
-  const size_t recs = (size_t)a.n_frames * a.cap, g0 = (size_t)f0 * a.cap;
-  HIPCHK(c, hipMemcpyAsync(d_counts + f0, a.counts, sizeof(int) * (size_t)a.n_frames, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_kp + g0, a.kp, sizeof(SurfKeypoint) * recs, hipMemcpyDeviceToDevice, c->stream));
-  if (a.desc) HIPCHK(c, hipMemcpyAsync(d_desc + g0 * 64, a.desc, sizeof(float) * 64 * recs, hipMemcpyDeviceToDevice, c->stream));
-  return UWT_OK;
-}
-
-// the chunk's results to host memory: only the rows below each frame's count are written
-int surf_deliver_host(uwt_ctx* c, int f0, const SurfArgs& a, uwt_keypoint* kp_out, float* desc_out, int32_t* counts_out) {
-  std::vector<int32_t> cnt((size_t)a.n_frames);
-  HIPCHK(c, hipMemcpyAsync(cnt.data(), a.counts, sizeof(int) * (size_t)a.n_frames, hipMemcpyDeviceToHost, c->stream));
-  const size_t g0 = (size_t)f0 * a.cap;
-  int st = rows_to_host(c, a.cap, a.n_frames, {{a.kp, sizeof(SurfKeypoint), cnt.data(), kp_out + g0},
-                                                {a.desc, sizeof(float) * 64, cnt.data(), a.desc ? desc_out + g0 * 64 : nullptr}});
-  if (!st && counts_out)
-    for (int f = 0; f < a.n_frames; f++) counts_out[f0 + f] = std::min(std::max(cnt[(size_t)f], 0), a.cap);
-  return st;
-}
+  // the geometry under sp: the bound of the candidate lists when the call detects
+  int plan(bool detect) {
+    raw_cap = detect ? surf_raw_bound(c->p.width, c->p.height, sp.n_octaves, sp.n_octave_layers + 2) : 0;
+    d.frame_bytes = surf_layout(c, 1, raw_cap, cap, 0).total;
+    d.rows = cap;
+    return UWT_OK;
+  }
+  // Grows the scratch to a chunk of nf frames, sends the chunk's slot list and enqueues the integral images.
+  int begin(const int32_t* slots, int nf, size_t extra, unsigned char** extra_out) {
+    const size_t modes = d_path ? sizeof(int) * (size_t)nf : 0;   // (no call has both)
+    const SurfLayout l = surf_layout(c, nf, raw_cap, cap, extra + modes);
+    int st = c->surf_buf.reserve(c, c->stream, l.total);
+    if (st) return st;
+    unsigned char* b = (unsigned char*)c->surf_buf.p;
+    detect_image(c, &a);
+    a.slots = (const int*)(b + l.slots);
+    a.n_frames = nf;
+    a.integral = (uint32_t*)(b + l.integral);
+    a.threshold = sp.hessian_threshold;
+    a.n_octaves = sp.n_octaves;
+    a.layers = sp.n_octave_layers + 2;
+    a.upright = sp.upright ? 1 : 0;
+    a.raw = (SurfKeypoint*)(b + l.raw);
+    a.raw_key = (unsigned long long*)(b + l.key);
+    a.raw_count = (int*)(b + l.raw_count);
+    a.raw_cap = (int)raw_cap;
+    a.keep = b + l.keep;
+    a.kp = (SurfKeypoint*)(b + l.kp);
+    a.desc = b + l.desc;
+    a.desc_row = sizeof(float) * 64;
+    a.counts = (int*)(b + l.counts);
+    a.cap = cap;
+    a.mode = mode = modes ? (int*)(b + l.extra) : nullptr;
+    if (extra_out) *extra_out = b + l.extra;
+    HIPCHK(c, hipMemcpyAsync((void*)a.slots, slots, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+    launch_surf_integral(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return UWT_OK;
+  }
+};
 
 }  // namespace
 
 int uwt_surf_detect_describe_batch(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const uwt_surf_params* params, int32_t cap,
                                    uwt_keypoint* kp_out, float* desc_out, int32_t* counts_out) {
-  if (c) (void)hipSetDevice(c->p.device);
-  const char* what = "uwt_surf_detect_describe_batch";
-  if (!c || !kp_out || !counts_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  uwt_surf_params sp;
-  int st = surf_check(c, what, n_frames, slots, cap, params, &sp);
-  if (st) return st;
-  return surf_run(c, sp, n_frames, slots, cap, SurfSource(), desc_out != nullptr,
-                  [&](int f0, const SurfArgs& a) { return surf_deliver_host(c, f0, a, kp_out, desc_out, counts_out); });
+  SurfCall s(c, params, cap);
+  return detect_entry(c, "uwt_surf_detect_describe_batch", s.d, DetectForm::host, n_frames, slots, cap, nullptr, nullptr, kp_out, desc_out, counts_out);
 }
 
 int uwt_surf_detect_describe_batch_async(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const uwt_surf_params* params,
                                          int32_t cap, uwt_keypoint* d_kp_out, float* d_desc_out, int32_t* d_counts_out) {
-  if (c) (void)hipSetDevice(c->p.device);
-  const char* what = "uwt_surf_detect_describe_batch_async";
-  if (!c || !d_kp_out || !d_counts_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  uwt_surf_params sp;
-  int st = surf_check(c, what, n_frames, slots, cap, params, &sp);
-  if (st) return st;
-  st = surf_run(c, sp, n_frames, slots, cap, SurfSource(), d_desc_out != nullptr,
-                [&](int f0, const SurfArgs& a) { return surf_deliver_device(c, f0, a, d_kp_out, d_desc_out, d_counts_out); });
-  if (st) return st;
-  return compute_end(c, c->dep_first, c->dep_n);
+  SurfCall s(c, params, cap);
+  return detect_entry(c, "uwt_surf_detect_describe_batch_async", s.d, DetectForm::device, n_frames, slots, cap, nullptr, nullptr, d_kp_out, d_desc_out,
+                      d_counts_out);
 }
 
 int uwt_surf_describe_batch(uwt_ctx* c, int32_t n_frames, const int32_t* slots, const uwt_surf_params* params,
                             const uwt_keypoint* keypoints_in, const int32_t* n_in, int32_t cap, uwt_keypoint* kp_out, float* desc_out) {
-  if (c) (void)hipSetDevice(c->p.device);
-  const char* what = "uwt_surf_describe_batch";
-  if (!c || !keypoints_in || !n_in || !kp_out || !desc_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  uwt_surf_params sp;
-  int st = surf_check(c, what, n_frames, slots, cap, params, &sp);
-  if (st) return st;
-  for (int f = 0; f < n_frames; f++) {
-    if (n_in[f] < 0 || n_in[f] > cap) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key-point count outside 0..cap");
-    const uwt_keypoint* k = keypoints_in + (size_t)f * cap;
-    for (int i = 0; i < n_in[f]; i++)
-      if (!surf_keypoint_ok(k[i].x, k[i].y, k[i].size))
-        return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": key point outside |x|, |y| <= 1e6, 0 < size <= 4096");
-  }
-  // the device keeps every row of a chunk; only the rows below a frame's count come back
-  return surf_run(c, sp, n_frames, slots, cap, SurfSource{keypoints_in, n_in}, true,
-                  [&](int f0, const SurfArgs& a) { return surf_deliver_host(c, f0, a, kp_out, desc_out, nullptr); });
+  SurfCall s(c, params, cap);
+  return detect_entry(c, "uwt_surf_describe_batch", s.d, DetectForm::given, n_frames, slots, cap, keypoints_in, n_in, kp_out, desc_out, nullptr);
 }
 
 int uwt_surf_integral(uwt_ctx* c, int32_t slot, uint32_t* out) {
   if (c) (void)hipSetDevice(c->p.device);
   const char* what = "uwt_surf_integral";
   if (!c || !out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  uwt_surf_params sp;
-  int st = surf_check(c, what, 1, &slot, 1, nullptr, &sp);
+  SurfCall s(c, nullptr, 1);
+  int st = stage_begin(c, what, s.d, slot, false, 0, nullptr);
   if (st) return st;
-  st = compute_begin(c, slot, 1);
-  if (st) return st;
-  SurfArgs a;
-  st = surf_begin_chunk(c, sp, &slot, 1, 0, 1, 0, &a, nullptr);
-  if (st) return st;
-  HIPCHK(c, hipMemcpyAsync(out, a.integral, sizeof(uint32_t) * (size_t)(a.w + 1) * (size_t)(a.h + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, s.a.integral, sizeof(uint32_t) * (size_t)(s.a.w + 1) * (size_t)(s.a.h + 1), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return UWT_OK;
 }
@@ -239,18 +173,13 @@ int uwt_surf_response_layer(uwt_ctx* c, int32_t slot, int32_t octave, int32_t la
   if (!c || !out || !gw || !gh) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
   if (octave < 0 || octave >= kSurfMaxOctaves || layer < 0 || layer >= kSurfMaxLayers)
     return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": octave outside 0..3 or layer outside 0..5");
-  uwt_surf_params sp;
-  int st = surf_check(c, what, 1, &slot, 1, nullptr, &sp);
-  if (st) return st;
-  st = compute_begin(c, slot, 1);
-  if (st) return st;
   const int w = c->p.width >> octave, h = c->p.height >> octave;
   const size_t n = (size_t)w * (size_t)h;
-  SurfArgs a;
+  SurfCall s(c, nullptr, 1);
   unsigned char* x = nullptr;
-  st = surf_begin_chunk(c, sp, &slot, 1, 0, 1, sizeof(double) * n + 16, &a, &x);
+  int st = stage_begin(c, what, s.d, slot, false, sizeof(double) * n + 16, &x);
   if (st) return st;
-  launch_surf_response_layer(c->stream, a, octave, layer, (double*)x);
+  launch_surf_response_layer(c->stream, s.a, octave, layer, (double*)x);
   HIPCHK(c, hipGetLastError());
   if (n) HIPCHK(c, hipMemcpyAsync(out, x, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -265,23 +194,20 @@ int uwt_surf_response_layer(uwt_ctx* c, int32_t slot, int32_t octave, int32_t la
 // Nothing is enqueued when a check fails.
 int uwt::surf_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_surf_params* params,
                     uwt_surf_params* sp) {
-  if (n_frames < 1 || cap < 1 || !slots) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_frames < 1, cap < 1 or a null list");
-  if (cap > UWT_MATCH_MAX_ROWS) return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS");
-  for (int f = 0; f < n_frames; f++)
-    if (!slot_range_ok(c, slots[f], 1)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": slot out of range");
-  if (params) *sp = *params;
-  else uwt_default_surf_params(sp);
-  if (!std::isfinite(sp->hessian_threshold)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": threshold is not finite");
-  if (sp->n_octaves < 1 || sp->n_octaves > kSurfMaxOctaves || sp->n_octave_layers < 1 || sp->n_octave_layers > kSurfMaxLayers - 2)
-    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_octaves or n_octave_layers outside 1..4");
-  if (((long long)c->p.width + 1) * ((long long)c->p.height + 1) >= (1ll << 31))
-    return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": the integral image has 2^31 entries or more");
-  return UWT_OK;
+  int st = detect_check(c, what, n_frames, slots, cap);
+  return st ? st : surf_params_check(c, what, params, sp);
 }
 
 // The tracking call's SURF: the path of every previous frame decided on the device, delivered as the asynchronous call delivers.
 int uwt::surf_track_enqueue(uwt_ctx* c, const uwt_surf_params& sp, int n_pairs, const int32_t* slots, int cap, const int* d_path,
                             const uwt_keypoint* d_prev_kp, const int32_t* d_n_prev, uwt_keypoint* d_kp, float* d_desc, int* d_counts) {
-  return surf_run(c, sp, 2 * n_pairs, slots, cap, SurfSource{nullptr, nullptr, d_path, n_pairs, d_prev_kp, d_n_prev}, true,
-                  [&](int f0, const SurfArgs& a) { return surf_deliver_device(c, f0, a, d_kp, d_desc, d_counts); });
+  SurfCall s(c, nullptr, cap);
+  s.sp = sp;
+  s.d_path = d_path;
+  s.n_pairs = n_pairs;
+  s.d_prev_kp = d_prev_kp;
+  s.d_n_prev = d_n_prev;
+  s.plan(true);
+  return detect_run(c, s.d, 2 * n_pairs, slots, cap, nullptr, nullptr, true,
+                    [&](int f0, const DetectArgs& a) { return deliver_device(c, f0, a, d_kp, d_desc, d_counts); });
 }

@@ -3,11 +3,9 @@
 // alone.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
 
-#include "uwt_surf.h"   // the key-point record
+#include "uwt_detect.h"
 
 namespace uwt {
 
@@ -24,7 +22,7 @@ constexpr int kOrbRankBlock = 1024;
 constexpr int kOrbDescWaves = 4;       // key points of a describe block: one wave each
 constexpr double kOrbHarrisDen = 25.0 * 7140.0 * 7140.0 * 7140.0 * 7140.0;   // exact: 2^8 * 25 * 1785^4
 
-using OrbKeypoint = SurfKeypoint;
+using OrbKeypoint = Keypoint;
 struct OrbKept { unsigned long long key; long long H; };   // key: (layer << 40) | (gy << 20) | gx, the contract's order
 
 __host__ __device__ inline long long orb_pow(int base, int level) {
@@ -48,12 +46,7 @@ inline size_t orb_raw_bound(int lw, int lh, int edge) {
   return (size_t)((bw + 1) / 2) * (size_t)((bh + 1) / 2);
 }
 
-struct OrbArgs {
-  const uint8_t* img;        // the level-0 image plane of slot 0
-  size_t frame_stride;       // bytes from one slot's plane to the next
-  int pitch, w, h;
-  const int* slots;          // the chunk's slots (device)
-  int n_frames;
+struct OrbArgs : DetectArgs {   // (desc: n_frames x cap x 32 bytes)
   int n_levels, edge, fast_threshold, upright;
   int kept_stride;               // the sum of the quotas: entries of a frame in kept and keep
   int lw[kOrbMaxLevels], lh[kOrbMaxLevels];
@@ -69,10 +62,6 @@ struct OrbArgs {
   int* raw_count;                // n_frames x kOrbMaxLevels, zero before the score launches
   OrbKept* kept;                 // n_frames x kept_stride: the layers' quota survivors, layer after layer
   unsigned char* keep;           // n_frames x kept_stride: work area of the capacity cut
-  OrbKeypoint* kp;               // n_frames x cap: the key points in contract order
-  uint8_t* desc;                 // n_frames x cap x 32, or null
-  int* counts;                   // n_frames
-  int cap;
   const signed char* pattern;    // 256 x (x0, y0, x1, y1)
   int* score_out = nullptr;      // the per-stage entry: the dense score map of frame 0's layer, lw x lh, zero before the launch
 };

@@ -12,6 +12,7 @@
 #pragma once
 
 #include "uwt_orb.h"
+#include "uwt_select.h"
 
 namespace uwt {
 
@@ -165,8 +166,6 @@ __global__ __launch_bounds__(kOrbBlock) void k_orb_harris(OrbArgs a, int l, cons
 // grid (n_levels, n_frames), 1024 threads.  Layer l keeps its quota[l] first by (H descending, key ascending); candidate i's rank
 // there is its place among them, behind what the layers below keep.
 __global__ __launch_bounds__(kOrbRankBlock) void k_orb_rank(OrbArgs a) {
-  __shared__ unsigned long long t_key[kOrbRankBlock];
-  __shared__ long long t_h[kOrbRankBlock];
   const int l = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
   const int n = min(a.raw_count[f * kOrbMaxLevels + l], a.raw_cap[l]);
   int before = 0;
@@ -180,18 +179,7 @@ __global__ __launch_bounds__(kOrbRankBlock) void k_orb_rank(OrbArgs a) {
     const bool mine = i < n;
     const long long hi = mine ? H[i] : 0;
     const unsigned long long ki = mine ? key[i] : 0ull;
-    int rank = 0;
-    for (int j0 = 0; j0 < n; j0 += kOrbRankBlock) {
-      __syncthreads();
-      if (j0 + tid < n) {
-        t_key[tid] = key[j0 + tid];
-        t_h[tid] = H[j0 + tid];
-      }
-      __syncthreads();
-      const int m = min(kOrbRankBlock, n - j0);
-      if (mine)
-        for (int j = 0; j < m; j++) rank += (t_h[j] > hi || (t_h[j] == hi && t_key[j] < ki)) ? 1 : 0;
-    }
+    const int rank = select_rank<kOrbRankBlock>(n, mine, hi, ki, [&](int j) { return H[j]; }, [&](int j) { return key[j]; });
     if (mine && rank < q) {   // (before + rank < the sum of the quotas = n_features)
       out[rank].key = ((unsigned long long)l << 40) | ki;
       out[rank].H = hi;
@@ -202,69 +190,29 @@ __global__ __launch_bounds__(kOrbRankBlock) void k_orb_rank(OrbArgs a) {
 // grid n_frames, 1024 threads.  A frame whose layers keep more than cap in all keeps the cap first by (H descending, key
 // ascending); every kept candidate goes to the place its key has among the kept.
 __global__ __launch_bounds__(kOrbRankBlock) void k_orb_select(OrbArgs a) {
-  __shared__ unsigned long long t_key[kOrbRankBlock];
-  __shared__ long long t_h[kOrbRankBlock];
-  __shared__ unsigned char t_keep[kOrbRankBlock];
-  const int f = blockIdx.x, tid = threadIdx.x;
+  const int f = blockIdx.x;
   int n = 0;
   for (int k = 0; k < a.n_levels; k++) n += min(min(a.raw_count[f * kOrbMaxLevels + k], a.raw_cap[k]), a.quota[k]);
   const OrbKept* in = a.kept + (size_t)f * a.kept_stride;
-  unsigned char* keep = a.keep + (size_t)f * a.kept_stride;
-  const bool over = n > a.cap;
-  if (over) {
-    for (int i0 = 0; i0 < n; i0 += kOrbRankBlock) {
-      const int i = i0 + tid;
-      const bool mine = i < n;
-      const long long hi = mine ? in[i].H : 0;
-      const unsigned long long ki = mine ? in[i].key : 0ull;
-      int rank = 0;
-      for (int j0 = 0; j0 < n; j0 += kOrbRankBlock) {
-        __syncthreads();
-        if (j0 + tid < n) {
-          t_key[tid] = in[j0 + tid].key;
-          t_h[tid] = in[j0 + tid].H;
-        }
-        __syncthreads();
-        const int m = min(kOrbRankBlock, n - j0);
-        if (mine)
-          for (int j = 0; j < m; j++) rank += (t_h[j] > hi || (t_h[j] == hi && t_key[j] < ki)) ? 1 : 0;
-      }
-      if (mine) keep[i] = rank < a.cap ? 1 : 0;
-    }
-  }
-  for (int i0 = 0; i0 < n; i0 += kOrbRankBlock) {
-    const int i = i0 + tid;
-    const bool mine = i < n && (!over || keep[i]);   // (keep[i] is this thread's own write)
-    const unsigned long long ki = mine ? in[i].key : 0ull;
-    int pos = 0;
-    for (int j0 = 0; j0 < n; j0 += kOrbRankBlock) {
-      __syncthreads();   // (also: every thread's keep[] of the pass above has been written)
-      if (j0 + tid < n) {
-        t_key[tid] = in[j0 + tid].key;
-        t_keep[tid] = over ? keep[j0 + tid] : (unsigned char)1;
-      }
-      __syncthreads();
-      const int m = min(kOrbRankBlock, n - j0);
-      if (mine)
-        for (int j = 0; j < m; j++) pos += (t_keep[j] && t_key[j] < ki) ? 1 : 0;
-    }
-    if (mine && pos < a.cap) {
-      const int l = (int)(ki >> 40), gy = (int)((ki >> 20) & 0xFFFFFull), gx = (int)(ki & 0xFFFFFull);
-      const long long p6 = orb_pow(6, l);
-      const double p5 = (double)orb_pow(5, l);
-      OrbKeypoint k;
-      k.x = (float)((double)((long long)gx * p6) / p5);
-      k.y = (float)((double)((long long)gy * p6) / p5);
-      k.size = (float)((double)((long long)kOrbPatch * p6) / p5);
-      k.response = (float)((double)in[i].H / kOrbHarrisDen);
-      k.dir_x = 1.0f;
-      k.dir_y = 0.0f;
-      k.octave = l;
-      k.laplacian = 0;
-      a.kp[(size_t)f * a.cap + pos] = k;
-    }
-  }
-  if (tid == 0) a.counts[f] = over ? a.cap : n;
+  n = select_ordered<kOrbRankBlock>(
+      n, a.cap, a.keep + (size_t)f * a.kept_stride, [&](int j) { return in[j].H; }, [&](int j) { return in[j].key; },
+      [&](int i, int pos) {
+        const unsigned long long ki = in[i].key;
+        const int l = (int)(ki >> 40), gy = (int)((ki >> 20) & 0xFFFFFull), gx = (int)(ki & 0xFFFFFull);
+        const long long p6 = orb_pow(6, l);
+        const double p5 = (double)orb_pow(5, l);
+        OrbKeypoint k;
+        k.x = (float)((double)((long long)gx * p6) / p5);
+        k.y = (float)((double)((long long)gy * p6) / p5);
+        k.size = (float)((double)((long long)kOrbPatch * p6) / p5);
+        k.response = (float)((double)in[i].H / kOrbHarrisDen);
+        k.dir_x = 1.0f;
+        k.dir_y = 0.0f;
+        k.octave = l;
+        k.laplacian = 0;
+        a.kp[(size_t)f * a.cap + pos] = k;
+      });
+  if (threadIdx.x == 0) a.counts[f] = n;
 }
 
 // ---- direction and descriptor ------------------------------------------------------------------------------------------------------
@@ -276,7 +224,7 @@ __global__ __launch_bounds__(64 * kOrbDescWaves) void k_orb_describe(OrbArgs a) 
   if (k >= min(a.counts[f], a.cap)) return;   // (uniform over the wave)
   OrbKeypoint* kp = a.kp + (size_t)f * a.cap + k;
   const int l = kp->octave;
-  uint8_t* desc = a.desc ? a.desc + ((size_t)f * a.cap + k) * 32 : nullptr;
+  uint8_t* desc = a.desc ? static_cast<uint8_t*>(a.desc) + ((size_t)f * a.cap + k) * 32 : nullptr;
   // what the host checks of a caller's record (detection's own always pass) holds here too: no read leaves the layer
   bool ok = l >= 0 && l < a.n_levels && fabsf(kp->x) <= 1e6f && fabsf(kp->y) <= 1e6f;
   int gx = 0, gy = 0;

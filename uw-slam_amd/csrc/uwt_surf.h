@@ -3,8 +3,7 @@
 // alone.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "uwt_detect.h"
 
 namespace uwt {
 
@@ -16,7 +15,7 @@ constexpr int kSurfSelectBlock = 1024;
 constexpr int kSurfDescWaves = 4;      // key points of a describe block: one wave each
 constexpr int kSurfDetect = 0, kSurfProvided = 1, kSurfNone = 2;   // SurfArgs::mode: detection; the caller's key points; no key points
 
-struct SurfKeypoint { float x, y, size, response, dir_x, dir_y; int octave, laplacian; };
+using SurfKeypoint = Keypoint;
 
 // the range of a key point a caller provides (host lists: uwt_surf_describe_batch; device lists: k_track_predicate): |x|, |y| <= 1e6,
 // 0 < size <= 4096.  Comparisons only, so a NaN fails.
@@ -34,12 +33,7 @@ inline size_t surf_raw_bound(int w, int h, int n_octaves, int layers) {
   return n < 64 ? 64 : n;
 }
 
-struct SurfArgs {
-  const uint8_t* img;        // the level-0 image plane of slot 0
-  size_t frame_stride;       // bytes from one slot's plane to the next
-  int pitch, w, h;
-  const int* slots;          // the chunk's slots (device)
-  int n_frames;
+struct SurfArgs : DetectArgs {   // (desc: n_frames x cap x 64 floats)
   uint32_t* integral;        // n_frames x (h + 1) x (w + 1)
   double threshold;
   int n_octaves, layers, upright;
@@ -48,10 +42,6 @@ struct SurfArgs {
   int* raw_count;            // n_frames, zero before the response launches
   int raw_cap;               // surf_raw_bound: never exceeded
   unsigned char* keep;       // n_frames x raw_cap: work area of the selection
-  SurfKeypoint* kp;          // n_frames x cap: the key points in contract order
-  float* desc;               // n_frames x cap x 64, or null
-  int* counts;               // n_frames
-  int cap;
   const int* mode = nullptr; // n_frames, or null: every frame is detected.  Else the frame's path, decided on the device: only a
                              // frame with kSurfDetect runs detection (k_surf_response, k_surf_select return at once for the others)
 };

@@ -9,6 +9,7 @@
 //                                  summing in sample order), then 400 samples over the lanes and one descriptor element per lane
 #pragma once
 
+#include "uwt_select.h"
 #include "uwt_surf.h"
 
 namespace uwt {
@@ -226,57 +227,14 @@ __global__ __launch_bounds__(kSurfBlock) void k_surf_response(SurfArgs a, int oc
 // grid n_frames, 1024 threads.  A frame with more than cap candidates keeps the cap first by (response descending, key ascending);
 // every kept candidate goes to the place its key has among the kept.
 __global__ __launch_bounds__(kSurfSelectBlock) void k_surf_select(SurfArgs a) {
-  // the candidates every thread compares its own with pass through LDS in tiles of one per thread (all lanes read the same entry)
-  __shared__ unsigned long long t_key[kSurfSelectBlock];
-  __shared__ float t_resp[kSurfSelectBlock];
-  __shared__ unsigned char t_keep[kSurfSelectBlock];
-  const int f = blockIdx.x, tid = threadIdx.x;
+  const int f = blockIdx.x;
   if (a.mode && a.mode[f] != kSurfDetect) return;   // (uniform) the frame's count and key points come from elsewhere
-  const int n = min(a.raw_count[f], a.raw_cap);
   const SurfKeypoint* raw = a.raw + (size_t)f * a.raw_cap;
   const unsigned long long* key = a.raw_key + (size_t)f * a.raw_cap;
-  unsigned char* keep = a.keep + (size_t)f * a.raw_cap;
-  const bool over = n > a.cap;
-  if (over) {
-    for (int i0 = 0; i0 < n; i0 += kSurfSelectBlock) {
-      const int i = i0 + tid;
-      const bool mine = i < n;
-      const float ri = mine ? raw[i].response : 0.f;
-      const unsigned long long ki = mine ? key[i] : 0ull;
-      int rank = 0;
-      for (int j0 = 0; j0 < n; j0 += kSurfSelectBlock) {
-        __syncthreads();
-        if (j0 + tid < n) {
-          t_key[tid] = key[j0 + tid];
-          t_resp[tid] = raw[j0 + tid].response;
-        }
-        __syncthreads();
-        const int m = min(kSurfSelectBlock, n - j0);
-        if (mine)
-          for (int q = 0; q < m; q++) rank += (t_resp[q] > ri || (t_resp[q] == ri && t_key[q] < ki)) ? 1 : 0;
-      }
-      if (mine) keep[i] = rank < a.cap ? 1 : 0;
-    }
-  }
-  for (int i0 = 0; i0 < n; i0 += kSurfSelectBlock) {
-    const int i = i0 + tid;
-    const bool mine = i < n && (!over || keep[i]);   // (keep[i] is this thread's own write)
-    const unsigned long long ki = mine ? key[i] : 0ull;
-    int pos = 0;
-    for (int j0 = 0; j0 < n; j0 += kSurfSelectBlock) {
-      __syncthreads();   // (also: every thread's keep[] of the pass above has been written)
-      if (j0 + tid < n) {
-        t_key[tid] = key[j0 + tid];
-        t_keep[tid] = over ? keep[j0 + tid] : (unsigned char)1;
-      }
-      __syncthreads();
-      const int m = min(kSurfSelectBlock, n - j0);
-      if (mine)
-        for (int q = 0; q < m; q++) pos += (t_keep[q] && t_key[q] < ki) ? 1 : 0;
-    }
-    if (mine && pos < a.cap) a.kp[(size_t)f * a.cap + pos] = raw[i];
-  }
-  if (tid == 0) a.counts[f] = over ? a.cap : n;
+  const int n = select_ordered<kSurfSelectBlock>(
+      min(a.raw_count[f], a.raw_cap), a.cap, a.keep + (size_t)f * a.raw_cap, [&](int j) { return raw[j].response; },
+      [&](int j) { return key[j]; }, [&](int i, int pos) { a.kp[(size_t)f * a.cap + pos] = raw[i]; });
+  if (threadIdx.x == 0) a.counts[f] = n;
 }
 
 // ---- orientation and descriptor ---------------------------------------------------------------------------------------------------
@@ -383,7 +341,7 @@ __global__ __launch_bounds__(64 * kSurfDescWaves) void k_surf_describe(SurfArgs 
   float q = acc * acc;
   for (int m = 32; m > 0; m >>= 1) q = q + __shfl_xor(q, m, 64);
   const float n = sqrtf(q);
-  a.desc[((size_t)f * a.cap + k) * 64 + lane] = n == 0.f ? 0.f : acc / n;
+  static_cast<float*>(a.desc)[((size_t)f * a.cap + k) * 64 + lane] = n == 0.f ? 0.f : acc / n;
 }
 
 // ---- the caller's key points from device memory (the tracking call) --------------------------------------------------------------

@@ -303,37 +303,33 @@ class RobustMatcher:
         a, b = tracker._bind(_previous_frame), tracker._bind(_current_frame)
         if _previous_frame._slot != a:
             raise RuntimeError("DetectAndTrackFeatures: more frames than slots (max_frames)")
-        if self.detector_ == 1:
-            return self._track_orb(_previous_frame, _current_frame, a, b, usekeypoints)
-        params = capi.default_surf_params(hessian_threshold=self.hessian_threshold_, n_octaves=self.n_octaves_,
-                                          n_octave_layers=self.n_octave_layers_, upright=int(self.upright_))
-        if usekeypoints and len(_previous_frame.surf_keypoints_):
-            kp0, d0 = self._ctx.surf_describe_batch([a], [_previous_frame.surf_keypoints_], params=params)[0]
-            kp1, d1 = self._ctx.surf_detect_describe_batch([b], params=params)[0]
+        build, detect, describe, kept = self._DETECTORS[self.detector_]
+        params = build(self)
+        ctx = self._ctx
+        if self.detector_ == 1 and self.orb_pattern_ is not self._pattern_sent:   # (the context keeps a pattern until it is given another)
+            ctx.orb_set_pattern(self.orb_pattern_)
+            self._pattern_sent = self.orb_pattern_
+        if usekeypoints and len(getattr(_previous_frame, kept)):
+            kp0, d0 = getattr(ctx, describe)([a], [getattr(_previous_frame, kept)], params=params)[0]
+            kp1, d1 = getattr(ctx, detect)([b], params=params)[0]
         else:
-            (kp0, d0), (kp1, d1) = self._ctx.surf_detect_describe_batch([a, b], params=params)
+            (kp0, d0), (kp1, d1) = getattr(ctx, detect)([a, b], params=params)
         xy = (np.stack([kp0["x"], kp0["y"]], 1), np.stack([kp1["x"], kp1["y"]], 1))
-        good = self._track_descriptors(_previous_frame, _current_frame, d0, d1, xy)
-        _previous_frame.surf_keypoints_, _current_frame.surf_keypoints_ = kp0[good["query_idx"]], kp1[good["train_idx"]]
+        good = self._track_descriptors(_previous_frame, _current_frame, d0, d1, xy)   # (float32 rows: L2; uint8 rows: Hamming)
+        setattr(_previous_frame, kept, kp0[good["query_idx"]])
+        setattr(_current_frame, kept, kp1[good["train_idx"]])
         return good
 
-    def _track_orb(self, _previous_frame, _current_frame, a, b, usekeypoints):
-        """src/Tracker.cpp:210-223 and on: ORB on both frames (the previous one described at the records it kept when
-        usekeypoints is set and it has some, :216-218), then the matcher under Hamming, ransacTest and the assignment"""
-        params = capi.default_orb_params(n_features=self.n_features_, n_levels=self.n_levels_, edge_threshold=self.edge_threshold_,
-                                         fast_threshold=self.fast_threshold_, upright=int(self.upright_))
-        if self.orb_pattern_ is not self._pattern_sent:   # (the context keeps a pattern until it is given another)
-            self._ctx.orb_set_pattern(self.orb_pattern_)
-            self._pattern_sent = self.orb_pattern_
-        if usekeypoints and len(_previous_frame.orb_keypoints_):
-            kp0, d0 = self._ctx.orb_describe_batch([a], [_previous_frame.orb_keypoints_], params=params)[0]
-            kp1, d1 = self._ctx.orb_detect_describe_batch([b], params=params)[0]
-        else:
-            (kp0, d0), (kp1, d1) = self._ctx.orb_detect_describe_batch([a, b], params=params)
-        xy = (np.stack([kp0["x"], kp0["y"]], 1), np.stack([kp1["x"], kp1["y"]], 1))
-        good = self._track_descriptors(_previous_frame, _current_frame, d0, d1, xy)
-        _previous_frame.orb_keypoints_, _current_frame.orb_keypoints_ = kp0[good["query_idx"]], kp1[good["train_idx"]]
-        return good
+    # per detector (src/Tracker.cpp:186-206 SURF, :210-223 ORB): the params builder, the context's detect and describe-at-given
+    # methods, and the frame attribute that holds the records kept; the norm follows from the descriptors' dtype (MatchDescriptors)
+    _DETECTORS = {
+        0: (lambda self: capi.default_surf_params(hessian_threshold=self.hessian_threshold_, n_octaves=self.n_octaves_,
+                                                  n_octave_layers=self.n_octave_layers_, upright=int(self.upright_)),
+            "surf_detect_describe_batch", "surf_describe_batch", "surf_keypoints_"),
+        1: (lambda self: capi.default_orb_params(n_features=self.n_features_, n_levels=self.n_levels_, edge_threshold=self.edge_threshold_,
+                                                 fast_threshold=self.fast_threshold_, upright=int(self.upright_)),
+            "orb_detect_describe_batch", "orb_describe_batch", "orb_keypoints_"),
+    }
 
     def _track_descriptors(self, _previous_frame, _current_frame, desc_prev, desc_cur, keypoints):
         matches = self.MatchDescriptors(desc_prev, desc_cur)
