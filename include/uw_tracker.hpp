@@ -388,8 +388,9 @@ class Tracker {
     check(st, "uwt_estimate_pose_candidates_batch");
   }
   // System::Tracking() (src/System.cpp:193-223) for a list of (previous, current) pairs through the device-resident call
-  // (uwt_tracking_batch): SURF, the matcher, ransacTest, getGoodKeypoints and the live alignment run as one chain on the device,
-  // and keypoints_, surf_keypoints_, n_matches_ of both frames and previous->rigid_transformation_ end up exactly as the loop
+  // (uwt_tracking_batch; uwt_tracking_orb_batch for RobustMatcher(tracker, 1)): the detector, the matcher, ransacTest, getGoodKeypoints
+  // and the live alignment run as one chain on the device, and keypoints_, surf_keypoints_ (orb_keypoints_ with ORB), n_matches_ of
+  // both frames and previous->rigid_transformation_ end up exactly as the loop
   // { ApplyGradient; DetectAndTrackFeatures(previous, current, n_matches_ >= 110); ObtainPatchesPoints; EstimatePoseFeatures } over
   // the same list leaves them.  Pairs that share no frame go into one call; a pair that names a frame an earlier pair of the list
   // has written (the next pair of a sequence) waits for that pair's results, as it does in the loop.  A pair without a good match
@@ -638,6 +639,15 @@ class RobustMatcher {
                  uwt_surf_describe_batch, "uwt_surf_describe_batch", 64, &Frame::surf_keypoints_);
   }
 
+  // orb_pattern_ to the context when it is not the one sent last, for Tracker::TrackingBatch (as DetectAndTrackFeatures sends it)
+  void SendOrbPattern() {
+    if (!orb_pattern_.empty() && orb_pattern_.size() != 1024) throw std::invalid_argument("RobustMatcher: orb_pattern_ holds 1024 entries");
+    if (orb_pattern_ != pattern_sent_) {
+      status(uwt_orb_set_pattern(tracker_->ctx(), orb_pattern_.empty() ? nullptr : orb_pattern_.data()), "uwt_orb_set_pattern");
+      pattern_sent_ = orb_pattern_;
+    }
+  }
+
   float ratio_ = 0.65f;      // include/Tracker.h:80
   bool refineF_ = true;      // include/Tracker.h:81 — a no-op here: the refit's result is discarded by the reference (:124, :141-166)
   double distance_ = 3.0;    // include/Tracker.h:82
@@ -727,18 +737,30 @@ class RobustMatcher {
 };
 
 inline void Tracker::TrackingBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, RobustMatcher& rm, int32_t cap) {
+  // RobustMatcher(tracker, 1): uwt_tracking_orb_batch under the matcher's pattern, the records in orb_keypoints_
+  const bool orb = rm.detector_ == 1;
+  std::vector<uwt_keypoint> Frame::*kept = orb ? &Frame::orb_keypoints_ : &Frame::surf_keypoints_;
+  const char* entry = orb ? "uwt_tracking_orb_batch" : "uwt_tracking_batch";
   uwt_tracking_params tp;
+  uwt_tracking_orb_params top;
   uwt_default_tracking_params(&tp);
+  uwt_default_tracking_orb_params(&top);
   tp.surf.hessian_threshold = rm.hessian_threshold_;
   tp.surf.n_octaves = rm.n_octaves_;
   tp.surf.n_octave_layers = rm.n_octave_layers_;
-  tp.surf.upright = rm.upright_ ? 1 : 0;
+  tp.surf.upright = top.orb.upright = rm.upright_ ? 1 : 0;
+  top.orb.n_features = rm.n_features_;
+  top.orb.n_levels = rm.n_levels_;
+  top.orb.edge_threshold = rm.edge_threshold_;
+  top.orb.fast_threshold = rm.fast_threshold_;
   tp.ransac.distance = rm.distance_;
   tp.ransac.confidence = rm.confidence_;
   tp.ransac.max_hypotheses = rm.max_hypotheses_;
   tp.ransac.seed = rm.seed_;
-  tp.ratio = rm.ratio_;
-  tp.min_matches = 110;   // src/System.cpp:208
+  top.ransac = tp.ransac;
+  tp.ratio = top.ratio = rm.ratio_;
+  tp.min_matches = top.min_matches = 110;   // src/System.cpp:208
+  if (orb) rm.SendOrbPattern();
   if (cap < 1) throw std::invalid_argument("TrackingBatch: cap < 1");
   std::vector<uwt_stats> all;
   for (size_t i = 0; i < _pairs.size();) {
@@ -769,29 +791,32 @@ inline void Tracker::TrackingBatch(const std::vector<std::pair<Frame*, Frame*>>&
       Frame* f = run[k].first;
       if (!bound(f) || !bound(run[k].second) || !f->obtained_gradients_ || !run[k].second->obtained_gradients_)
         throw std::runtime_error("TrackingBatch: more frames than slots (max_frames)");
-      const size_t m = f->surf_keypoints_.size();
+      const std::vector<uwt_keypoint>& had = f->*kept;
+      const size_t m = had.size();
       n_prev[k] = (int32_t)m;
-      std::copy(f->surf_keypoints_.begin(), f->surf_keypoints_.begin() + (m < (size_t)cap ? m : (size_t)cap), prev.begin() + k * (size_t)cap);
+      std::copy(had.begin(), had.begin() + (m < (size_t)cap ? m : (size_t)cap), prev.begin() + k * (size_t)cap);
     }
     std::vector<float> poses(n * 7);
     std::vector<uwt_stats> stats(n, uwt_stats{});
     std::vector<uwt_tracking_info> info(n);
     std::vector<uwt_match> good(n * (size_t)cap);
     std::vector<uwt_keypoint> kept_prev(n * (size_t)cap), kept_cur(n * (size_t)cap);
-    const int st = uwt_tracking_batch(ctx(), (int32_t)n, a.data(), b.data(), &tp, cap, prev.data(), n_prev.data(), poses.data(), stats.data(),
-                                      info.data(), good.data(), kept_prev.data(), kept_cur.data());
-    if (st != UWT_OK && st != UWT_ERR_PAIR_FAILED) check(st, "uwt_tracking_batch");
+    const int st = orb ? uwt_tracking_orb_batch(ctx(), (int32_t)n, a.data(), b.data(), &top, cap, prev.data(), n_prev.data(), poses.data(),
+                                                stats.data(), info.data(), good.data(), kept_prev.data(), kept_cur.data())
+                       : uwt_tracking_batch(ctx(), (int32_t)n, a.data(), b.data(), &tp, cap, prev.data(), n_prev.data(), poses.data(),
+                                            stats.data(), info.data(), good.data(), kept_prev.data(), kept_cur.data());
+    if (st != UWT_OK && st != UWT_ERR_PAIR_FAILED) check(st, entry);
     for (size_t k = 0; k < n; k++) {
       Frame* p = run[k].first;
       Frame* c = run[k].second;
       const size_t m = (size_t)info[k].n_matches;
       p->n_matches_ = c->n_matches_ = (int)m;
-      p->surf_keypoints_.assign(kept_prev.begin() + k * (size_t)cap, kept_prev.begin() + k * (size_t)cap + m);
-      c->surf_keypoints_.assign(kept_cur.begin() + k * (size_t)cap, kept_cur.begin() + k * (size_t)cap + m);
+      (p->*kept).assign(kept_prev.begin() + k * (size_t)cap, kept_prev.begin() + k * (size_t)cap + m);
+      (c->*kept).assign(kept_cur.begin() + k * (size_t)cap, kept_cur.begin() + k * (size_t)cap + m);
       p->keypoints_.clear();
       c->keypoints_.clear();
-      for (const uwt_keypoint& q : p->surf_keypoints_) p->keypoints_.insert(p->keypoints_.end(), {q.x, q.y});
-      for (const uwt_keypoint& q : c->surf_keypoints_) c->keypoints_.insert(c->keypoints_.end(), {q.x, q.y});
+      for (const uwt_keypoint& q : p->*kept) p->keypoints_.insert(p->keypoints_.end(), {q.x, q.y});
+      for (const uwt_keypoint& q : c->*kept) c->keypoints_.insert(c->keypoints_.end(), {q.x, q.y});
       std::copy(poses.begin() + 7 * k, poses.begin() + 7 * (k + 1), p->rigid_transformation_.data());
     }
     all.insert(all.end(), stats.begin(), stats.end());

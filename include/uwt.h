@@ -704,9 +704,9 @@ int uwt_surf_response_layer(uwt_ctx* ctx, int32_t slot, int32_t octave, int32_t 
  * defaults those of cuda::ORB::create(): 500 features, scale 1.2, 8 levels, edge threshold 31, first level 0, WTA_K 2, Harris score,
  * patch 31, FAST threshold 20, no blur before description.  The sampling pattern is DATA of the context (uwt_orb_set_pattern): the
  * default is the recipe below, not OpenCV's table — the one distance from OpenCV a caller who has that table can close themselves.
- * Not built: masks, WTA_K 3 / 4, FAST-score ranking, blur before description, a scale other than 1.2, a first level other than 0,
- * and an ORB branch of uwt_tracking_batch (its params struct is pinned at 56 bytes and its contract is "bit for bit the staged
- * sequence": the chain is a follow-up to this staged path).
+ * Not built: masks, WTA_K 3 / 4, FAST-score ranking, blur before description, a scale other than 1.2, a first level other than 0.
+ * Built since round 18: an ORB branch of uwt_tracking_batch — uwt_tracking_orb_batch, in the section after this one (the SURF call's
+ * params struct is pinned at 56 bytes, so the branch has a record and entry points of its own).
  *
  * Scale pyramid.  Integer, every layer from the level-0 u8 plane of the slot (w x h) alone; independent of the context's tracking
  *   pyramid.  The scale of layer l = 0 .. n_levels - 1 is the exact rational 6^l / 5^l.  Layer width w_l = (w 5^l + 6^l / 2) / 6^l
@@ -886,6 +886,42 @@ int uwt_tracking_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, 
                        const uwt_keypoint* prev_kp_or_null, const int32_t* n_prev_or_null,
                        float* poses_out, uwt_stats* stats_out_or_null, uwt_tracking_info* info_out, uwt_match* good_out,
                        uwt_keypoint* kept_prev_out, uwt_keypoint* kept_cur_out);
+/* The same chain for RobustMatcher(1): ORB and the Hamming matcher (src/Tracker.cpp:210-223).  uwt_tracking_params is pinned and holds
+ * SURF's parameters, so this detector has a record of its own; uwt_tracking_io, uwt_tracking_info and the uwt_keypoint records are
+ * those above.  The contract is that of uwt_tracking_batch, steps 1-6, with these substitutions:
+ *   Q: use ? what uwt_orb_describe_batch gives at the provided records : what uwt_orb_detect_describe_batch gives on the previous
+ *      frame with capacity cap.  T: uwt_orb_detect_describe_batch on the current frame with capacity cap.  Both under the context's
+ *      pattern in force (uwt_orb_set_pattern) and params.orb.
+ *   symMatches = uwt_match_descriptors_batch(UWT_NORM_HAMMING, 32, Q, T, cap, ratio).
+ * No new arithmetic: every output of a pair is bit for bit what that staged sequence gives on the same context, and depends neither on
+ * the batch, nor on the pair's place there, nor on uwt_tuning, nor on scheduling.  Hand-over and aliasing: as above (d_kept_cur /
+ * d_n_matches of one call are valid d_prev_kp / d_n_prev of the next, no uwt_sync between them; the inputs and outputs of one call
+ * must not overlap).
+ * Host-side refusals, nothing enqueued and the outputs untouched: those of uwt_tracking_batch with the ranges of uwt_orb_params in
+ * place of SURF's; UWT_ERR_CAPACITY also for a frame wider or higher than 16384.
+ * What only the device can see is handled as above (UWT_ERR_INVALID_ARG in that pair's info.status and uwt_stats, n_matches 0, the
+ * identity pose, neither path run on its previous frame, its neighbours untouched, UWT_ERR_PAIR_FAILED from the synchronous call): a
+ * provided count outside 0..cap; one of the first 200 kept (x, y) outside level 0; and a USED provided record that
+ * uwt_orb_describe_batch would refuse on the host — x or y not finite or beyond 1e6 in magnitude, an octave outside 0 .. n_levels - 1,
+ * a layer position closer than edge_threshold (the parameter) to a border of its layer.
+ * A frame too small for layer 0's band is no front-end error: its counts are 0, info.status is UWT_OK and the pair's uwt_stats carry
+ * UWT_ERR_NO_VALID_POINTS. */
+typedef struct uwt_tracking_orb_params {
+  uwt_orb_params    orb;          /* uwt_default_orb_params                                          */
+  uwt_ransac_params ransac;       /* uwt_default_ransac_params                                       */
+  float             ratio;        /* 0.65f; finite                                                   */
+  int32_t           min_matches;  /* 110; >= 0                                                       */
+} uwt_tracking_orb_params;        /* 56 bytes (orb: 20, 4 of padding, ransac: 24) */
+
+/* {uwt_default_orb_params, uwt_default_ransac_params, 0.65f, 110} */
+int uwt_default_tracking_orb_params(uwt_tracking_orb_params* p);
+int uwt_tracking_orb_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                 const uwt_tracking_orb_params* params_or_null, int32_t cap, const uwt_tracking_io* io);
+int uwt_tracking_orb_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                           const uwt_tracking_orb_params* params_or_null, int32_t cap,
+                           const uwt_keypoint* prev_kp_or_null, const int32_t* n_prev_or_null,
+                           float* poses_out, uwt_stats* stats_out_or_null, uwt_tracking_info* info_out, uwt_match* good_out,
+                           uwt_keypoint* kept_prev_out, uwt_keypoint* kept_cur_out);
 /* uwt_match_descriptors_batch_async with both descriptor sets and their counts already in DEVICE memory (d_query / d_train: n_pairs x
  * cap x dim elements, d_n_query / d_n_train: n_pairs), read in place: nothing is uploaded.  The launch is bounded by cap instead of
  * the counts (blocks past a pair's counts return at once; the merge of the train parts is exact, so the different cut shows in no

@@ -8,6 +8,10 @@ which nothing leaves the device between the stages.
       of 16 and 256 pairs, each for both forms, profiler off; and the predicate's effect: a batch of 16 with every previous frame
       on the provided path against every one on detection.  --staged-only: the staged figures alone (a library without the chained
       call: the parent commit)
+  python tools/live_bench.py --orb --out profiles/r18/live_bench_orb.json
+      RobustMatcher(1): the staged ORB sequence against the ORB chain (uwt_tracking_orb_batch*), with the SURF chain alongside, host to
+      host on one resident pair and on resident batches of 16 and 256; the three forms take turns within every round, so a drift of
+      the clocks falls on all of them alike
   rocprofv3 --kernel-trace --stats -d <dir> --output-format csv -- python tools/live_bench.py --trace-run chained|staged
       a few one-pair calls of one form for the kernel trace, in a run of its own (no counters together with tracing)
 
@@ -127,6 +131,69 @@ def measure(out_path, staged_only):
     print(json.dumps(rec))
 
 
+def staged_orb(ctx, ref, tgt):
+    """staged() under RobustMatcher(1): ORB and the Hamming matcher (the rows' dtype chooses the norm)"""
+    P = len(ref)
+    res = ctx.orb_detect_describe_batch(list(ref) + list(tgt), cap=CAP)
+    xy = [np.stack([k["x"], k["y"]], 1) for k, _ in res]
+    sym = ctx.match_descriptors_batch([(res[i][1], res[P + i][1]) for i in range(P)], cap=CAP)
+    rs = ctx.ransac_inliers_batch([(sym[i], xy[i], xy[P + i]) for i in range(P)], cap=CAP, kp_cap=CAP)
+    kept = [xy[i][rs[i][1]["query_idx"]] for i in range(P)]
+    poses, _ = ctx.estimate_pose_features_batch(ref, tgt, [k[:200] for k in kept])
+    return poses, [len(k) for k in kept]
+
+
+def measure_orb(out_path):
+    import torch
+    capi, ctx = setup(256)
+    rec = dict(width=W, height=H, cap=CAP, source_id=capi.source_id(), forms=["orb_staged", "orb_chained", "surf_chained"], host_to_host={})
+    for P, warm, rounds in ((1, 5, 30), (16, 2, 8), (256, 1, 3)):
+        ref, tgt = pair_lists(P)
+        i32 = dict(dtype=torch.int32, device="cuda")
+        s = dict(poses=torch.zeros((P, 7), **i32), stats=torch.zeros((P, 4), **i32), info=torch.zeros((P, 8), **i32),
+                 good=torch.zeros((P, CAP, 3), **i32), kept_prev=torch.zeros((P, CAP, 8), **i32), kept_cur=torch.zeros((P, CAP, 8), **i32),
+                 n_matches=torch.zeros((P,), **i32))
+        torch.cuda.synchronize()
+        io = {k: v.data_ptr() for k, v in s.items()}
+        out = (np.zeros((P, 7), np.float32), np.zeros(P, capi.STATS), np.zeros(P, capi.TRACKING_INFO), np.zeros((P, CAP), capi.MATCH),
+               np.zeros((P, CAP), capi.KEYPOINT), np.zeros((P, CAP), capi.KEYPOINT))
+
+        def orb_chained():
+            if P == 1:   # one pair: the synchronous form, results on the host, as the staged sequence leaves them
+                return ctx.tracking_orb_batch(ref, tgt, cap=CAP, out=out)
+            ctx.tracking_orb_batch_async(ref, tgt, io, cap=CAP)
+            ctx.sync()
+
+        def surf_chained():
+            if P == 1:
+                return ctx.tracking_batch(ref, tgt, cap=CAP, out=out)
+            ctx.tracking_batch_async(ref, tgt, io, cap=CAP)
+            ctx.sync()
+
+        forms = dict(orb_staged=lambda: staged_orb(ctx, ref, tgt), orb_chained=orb_chained, surf_chained=surf_chained)
+        if P == 1:   # the forms agree before they are timed
+            poses, kept = staged_orb(ctx, ref, tgt)
+            r = ctx.tracking_orb_batch(ref, tgt, cap=CAP, out=out)
+            assert r["poses"].tobytes() == poses.tobytes() and int(r["info"]["n_matches"][0]) == kept[0]
+            rec["orb_matches_kept_pair0"] = kept[0]
+            rec["orb_keypoints_pair0"] = [int(r["info"]["n_kp_prev"][0]), int(r["info"]["n_kp_cur"][0])]
+        times = {k: [] for k in forms}
+        for k, fn in forms.items():
+            for _ in range(warm):
+                fn()
+        for _ in range(rounds):
+            for k, fn in forms.items():
+                t = time.perf_counter()
+                fn()
+                times[k].append(time.perf_counter() - t)
+        rec["host_to_host"][str(P)] = {k: dict(ms=summary([t * 1e3 for t in v]), pairs_per_s=summary([P / t for t in v])) for k, v in times.items()}
+    ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def trace_run(form):
     capi, ctx = setup(1)
     ref, tgt = pair_lists(1)
@@ -143,8 +210,11 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13", "live_bench.json"))
     ap.add_argument("--staged-only", action="store_true")
     ap.add_argument("--trace-run", choices=["chained", "staged"])
+    ap.add_argument("--orb", action="store_true")
     a = ap.parse_args()
     if a.trace_run:
         trace_run(a.trace_run)
+    elif a.orb:
+        measure_orb(a.out)
     else:
         measure(a.out, a.staged_only)

@@ -46,14 +46,16 @@ def track_live(w, h, intr, frames, depths, arith=0, detector=0):
     return np.array(poses, np.float32).reshape(-1, 7), stats, kept
 
 
-def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048):
-    """The same loop as successive one-pair uwt_tracking_batch_async calls: what a frame kept goes to the next call in device memory
-    (two sets of buffers, taken in turn), nothing is read back between the calls and the host waits once, at the end.  Same returns."""
+def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0):
+    """The same loop as successive one-pair uwt_tracking_batch_async calls (detector 1: uwt_tracking_orb_batch_async): what a frame kept
+    goes to the next call in device memory (two sets of buffers, taken in turn), nothing is read back between the calls and the host
+    waits once, at the end.  Same returns."""
     import torch
     capi = importlib.import_module("uw-slam_amd.capi")
     n = len(frames)
     ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=4, max_pairs=1, has_depth=int(bool(depths)), arith=arith))
     ctx.set_deferred(True)   # pyramids and gradients are enqueued only
+    enqueue = ctx.tracking_orb_batch_async if detector == 1 else ctx.tracking_batch_async
     i32 = dict(dtype=torch.int32, device="cuda")
     poses, stats, info = torch.zeros((n - 1, 7), **i32), torch.zeros((n - 1, 4), **i32), torch.zeros((n - 1, 8), **i32)
     sets = [dict(good=torch.zeros((cap, 3), **i32), kept_prev=torch.zeros((cap, 8), **i32), kept_cur=torch.zeros((cap, 8), **i32),
@@ -72,7 +74,7 @@ def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048):
         io.update(poses=poses[k].data_ptr(), stats=stats[k].data_ptr(), info=info[k].data_ptr())
         if k:
             io.update(prev_kp=sets[(k - 1) % 2]["kept_cur"].data_ptr(), n_prev=sets[(k - 1) % 2]["n_matches"].data_ptr())
-        ctx.tracking_batch_async([k % 4], [(k + 1) % 4], io, cap=cap)
+        enqueue([k % 4], [(k + 1) % 4], io, cap=cap)
     ctx.sync()
     st = stats.cpu().numpy().view(capi.STATS).reshape(-1)
     kept = info.cpu().numpy().view(capi.TRACKING_INFO).reshape(-1)["n_matches"]
@@ -101,9 +103,10 @@ def main():
     ap.add_argument("--live", action="store_true", help="the reference's live loop, System::Tracking (src/System.cpp:193-223): SURF key "
                     "points detected, described, matched and RANSAC-filtered on the device, then EstimatePoseFeatures on their patches")
     ap.add_argument("--detector", choices=["surf", "orb"], default="surf", help="with --live: the detector of RobustMatcher(int detector) "
-                    "(src/Tracker.cpp:38-46); orb runs the staged path only (no --chained)")
-    ap.add_argument("--chained", action="store_true", help="with --live: the loop as successive device-resident calls (uwt_tracking_batch_async) "
-                    "that hand their key points on in device memory, one wait at the end; the same trajectory")
+                    "(src/Tracker.cpp:38-46)")
+    ap.add_argument("--chained", action="store_true", help="with --live: the loop as successive device-resident calls (uwt_tracking_batch_async, "
+                    "uwt_tracking_orb_batch_async with --detector orb) that hand their key points on in device memory, one wait at the end; "
+                    "the same trajectory")
     ap.add_argument("--out", default="trajectory")
     a = ap.parse_args()
     S = importlib.import_module("uw-slam_amd.sequence")
@@ -136,12 +139,11 @@ def main():
         over.update(n_levels=4, first_level=3, last_level=0, max_iters=a.fixed_iters, early_exit=0)
     trk = S.SequenceTracker(a.width, a.height, fx, fy, cx - x0, cy - y0, depth=bool(depths), **over)
     t0 = time.perf_counter()
-    if a.detector == "orb" and (a.chained or not a.live):
-        ap.error("--detector orb goes with --live and without --chained: uwt_tracking_batch has no ORB branch")
-    if a.live and a.detector == "orb":
-        poses, stats, n_matches = track_live(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"], detector=1)
-    elif a.live:
-        poses, stats, n_matches = (track_live_chained if a.chained else track_live)(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"])
+    if a.detector == "orb" and not a.live:
+        ap.error("--detector orb goes with --live")
+    if a.live:
+        poses, stats, n_matches = (track_live_chained if a.chained else track_live)(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths,
+                                                                                    over["arith"], detector=int(a.detector == "orb"))
     else:
         poses, stats = trk.track(frames, depths)
     dt = time.perf_counter() - t0

@@ -74,6 +74,11 @@ class TrackingParams(C.Structure):
     _fields_ = [("surf", SurfParams), ("ransac", RansacParams), ("ratio", C.c_float), ("min_matches", C.c_int32)]
 
 
+class TrackingOrbParams(C.Structure):
+    """uwt_tracking_orb_params: the same record for RobustMatcher(1), with the ORB parameters in SURF's place (56 bytes)"""
+    _fields_ = [("orb", OrbParams), ("ransac", RansacParams), ("ratio", C.c_float), ("min_matches", C.c_int32)]
+
+
 class TrackingIO(C.Structure):
     """uwt_tracking_io: device pointers of one uwt_tracking_batch_async call"""
     _fields_ = [("d_prev_kp", C.c_void_p), ("d_n_prev", C.c_void_p), ("d_poses", C.c_void_p), ("d_stats", C.c_void_p),
@@ -120,6 +125,7 @@ SYMBOLS = [
     "uwt_orb_detect_describe_batch", "uwt_orb_detect_describe_batch_async", "uwt_orb_describe_batch", "uwt_orb_layer",
     "uwt_orb_fast_scores", "uwt_orb_harris",
     "uwt_default_tracking_params", "uwt_tracking_batch_async", "uwt_tracking_batch", "uwt_match_descriptors_device_async",
+    "uwt_default_tracking_orb_params", "uwt_tracking_orb_batch_async", "uwt_tracking_orb_batch",
 ]
 
 _lib = None
@@ -259,19 +265,29 @@ def orb_layer_size(w, h, level):
     return lw.value, lh.value
 
 
-def default_tracking_params(surf=None, ransac=None, **over):
-    """uwt_default_tracking_params: the SURF and RANSAC defaults, ratio 0.65, min_matches 110.  surf / ransac: dicts of fields of the
-    nested records to change; the other keywords are fields of the record itself."""
-    p = TrackingParams()
-    st = lib().uwt_default_tracking_params(C.byref(p))
+def _tracking_params(p, fn, name, detector, detector_over, ransac, over):
+    st = fn(C.byref(p))
     if st:
-        raise UwtError(st, "uwt_default_tracking_params")
-    for rec, d in ((p.surf, surf or {}), (p.ransac, ransac or {}), (p, over)):
+        raise UwtError(st, name)
+    for rec, d in ((getattr(p, detector), detector_over or {}), (p.ransac, ransac or {}), (p, over)):
         for k, v in d.items():
             if not hasattr(rec, k):
                 raise AttributeError(k)
             setattr(rec, k, v)
     return p
+
+
+def default_tracking_params(surf=None, ransac=None, **over):
+    """uwt_default_tracking_params: the SURF and RANSAC defaults, ratio 0.65, min_matches 110.  surf / ransac: dicts of fields of the
+    nested records to change; the other keywords are fields of the record itself."""
+    return _tracking_params(TrackingParams(), lib().uwt_default_tracking_params, "uwt_default_tracking_params", "surf", surf, ransac, over)
+
+
+def default_tracking_orb_params(orb=None, ransac=None, **over):
+    """uwt_default_tracking_orb_params: the ORB and RANSAC defaults, ratio 0.65, min_matches 110; orb / ransac / the other keywords as
+    in default_tracking_params."""
+    return _tracking_params(TrackingOrbParams(), lib().uwt_default_tracking_orb_params, "uwt_default_tracking_orb_params", "orb", orb,
+                            ransac, over)
 
 
 def keypoint_angle_deg(dir_x, dir_y):
@@ -949,7 +965,22 @@ class Context:
         return out
 
     def tracking_batch(self, ref_slots, tgt_slots, prev=None, params=None, cap=2048, out=None, raise_on_pair_failure=False):
-        """System::Tracking for many pairs in one device-resident call (uwt_tracking_batch), host in and out.  prev: None, or one
+        """System::Tracking for many pairs in one device-resident call with SURF and the L2 matcher (uwt_tracking_batch; params:
+        TrackingParams); arguments and result: _tracking_batch."""
+        return self._tracking_batch(lib().uwt_tracking_batch, ref_slots, tgt_slots, prev, params, cap, out, raise_on_pair_failure)
+
+    def tracking_orb_batch(self, ref_slots, tgt_slots, prev=None, params=None, cap=2048, out=None, raise_on_pair_failure=False):
+        """tracking_batch for RobustMatcher(1): ORB and the Hamming matcher (uwt_tracking_orb_batch; params: TrackingOrbParams), under
+        the context's pattern in force.  Arguments and result as there."""
+        return self._tracking_batch(lib().uwt_tracking_orb_batch, ref_slots, tgt_slots, prev, params, cap, out, raise_on_pair_failure)
+
+    def tracking_orb_batch_async(self, ref_slots, tgt_slots, io, params=None, cap=2048):
+        """tracking_batch_async for RobustMatcher(1) (uwt_tracking_orb_batch_async)."""
+        self._tracking_batch_async(lib().uwt_tracking_orb_batch_async, ref_slots, tgt_slots, io, params, cap)
+
+    def _tracking_batch(self, fn, ref_slots, tgt_slots, prev, params, cap, out, raise_on_pair_failure):
+        """System::Tracking for many pairs in one device-resident call (fn: uwt_tracking_batch or uwt_tracking_orb_batch), host in and
+        out.  prev: None, or one
         KEYPOINT array per pair (what the previous frame kept; an empty one for a pair that has none), or the packed form
         (kp [P, cap] KEYPOINT, n [P] int32).  out: (poses [P, 7] float32, stats [P] STATS, info [P] TRACKING_INFO, good [P, cap]
         MATCH, kept_prev [P, cap] KEYPOINT, kept_cur [P, cap] KEYPOINT) to be written in place — the rows past a pair's count stay
@@ -970,18 +1001,23 @@ class Context:
             out = (np.zeros((max(P, 1), 7), np.float32), np.zeros(max(P, 1), STATS), np.zeros(max(P, 1), TRACKING_INFO),
                    np.zeros((max(P, 1), c), MATCH), np.zeros((max(P, 1), c), KEYPOINT), np.zeros((max(P, 1), c), KEYPOINT))
         poses, stats, info, good, kept_prev, kept_cur = out
-        st = lib().uwt_tracking_batch(self._h, P, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.byref(params) if params is not None else None,
-                                      cap, C.c_void_p(kp.ctypes.data) if kp is not None else None,
-                                      _p(n, C.c_int32) if n is not None else None, _p(poses, C.c_float), C.c_void_p(stats.ctypes.data),
-                                      C.c_void_p(info.ctypes.data), C.c_void_p(good.ctypes.data), C.c_void_p(kept_prev.ctypes.data),
-                                      C.c_void_p(kept_cur.ctypes.data))
+        st = fn(self._h, P, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.byref(params) if params is not None else None,
+                cap, C.c_void_p(kp.ctypes.data) if kp is not None else None,
+                _p(n, C.c_int32) if n is not None else None, _p(poses, C.c_float), C.c_void_p(stats.ctypes.data),
+                C.c_void_p(info.ctypes.data), C.c_void_p(good.ctypes.data), C.c_void_p(kept_prev.ctypes.data),
+                C.c_void_p(kept_cur.ctypes.data))
         self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
         cnt = info["n_matches"]
         return dict(status=st, poses=poses[:P], stats=stats[:P], info=info[:P], good=[good[i, :cnt[i]].copy() for i in range(P)],
                     kept_prev=[kept_prev[i, :cnt[i]].copy() for i in range(P)], kept_cur=[kept_cur[i, :cnt[i]].copy() for i in range(P)])
 
     def tracking_batch_async(self, ref_slots, tgt_slots, io, params=None, cap=2048):
-        """The same enqueued on the context stream with every input and result in device memory (uwt_tracking_batch_async).  io: a
+        """tracking_batch without waiting, device in and out (uwt_tracking_batch_async); io: _tracking_batch_async."""
+        self._tracking_batch_async(lib().uwt_tracking_batch_async, ref_slots, tgt_slots, io, params, cap)
+
+    def _tracking_batch_async(self, fn, ref_slots, tgt_slots, io, params, cap):
+        """The same enqueued on the context stream with every input and result in device memory (fn: uwt_tracking_batch_async or
+        uwt_tracking_orb_batch_async).  io: a
         dict of device addresses — poses (P x 7 float32), info (P TRACKING_INFO), good (P x cap MATCH), kept_prev, kept_cur (P x cap
         KEYPOINT), n_matches (P int32), optionally stats (P STATS) and prev_kp / n_prev (P x cap KEYPOINT, P int32: kept_cur /
         n_matches of the call before, of ANOTHER set of buffers).  Never waits for the device; sync() to wait."""
@@ -989,8 +1025,8 @@ class Context:
         tgt = np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
         rec = TrackingIO(*[io.get(k) or None for k in ("prev_kp", "n_prev", "poses", "stats", "info", "good", "kept_prev", "kept_cur",
                                                         "n_matches")])
-        self._chk(lib().uwt_tracking_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
-                                                 C.byref(params) if params is not None else None, cap, C.byref(rec)))
+        self._chk(fn(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.byref(params) if params is not None else None, cap,
+                     C.byref(rec)))
 
     def match_descriptors_device_async(self, n_pairs, dim, cap, d_query_ptr, d_n_query_ptr, d_train_ptr, d_n_train_ptr, d_matches_ptr,
                                        d_counts_ptr, ratio=0.65, norm=NORM_L2):

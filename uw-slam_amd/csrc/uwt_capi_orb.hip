@@ -137,12 +137,20 @@ int orb_params_check(uwt_ctx* c, const char* what, const uwt_orb_params* params,
   return UWT_OK;
 }
 
-// One ORB call: its parameters, its geometry (g), its chunk (a), and the driver's parts over them.
+// One ORB call: its parameters, its geometry (g), its chunk (a), and the driver's parts over them.  With the device paths of the
+// tracking call set (n_frames = 2 n_pairs; orb_track_enqueue's arguments, uwt_ctx.h) a chunk's extra scratch holds the frames' modes:
+// detection runs under them (the blocks of a frame on another path return at once), k_orb_take_provided has put the provided records
+// and counts where detection would have, and describe, sized by cap, serves both.
 struct OrbCall {
   uwt_ctx* c;
   int cap;
   uwt_orb_params op;
   OrbArgs g, a;
+  const int* d_path = nullptr;
+  int n_pairs = 0;
+  const uwt_keypoint* d_prev_kp = nullptr;
+  const int32_t* d_n_prev = nullptr;
+  int* mode = nullptr;   // the chunk's modes (a.mode) where d_path is set
   Detector d;
 
   OrbCall(uwt_ctx* c_, const uwt_orb_params* params, int cap_) : c(c_), cap(cap_) {
@@ -151,16 +159,18 @@ struct OrbCall {
       return st ? st : plan(detect);
     };
     d.kp_ok = [this](const uwt_keypoint& k) {
-      const int l = k.octave;
-      if (!(std::fabs(k.x) <= 1e6f && std::fabs(k.y) <= 1e6f && l >= 0 && l < op.n_levels)) return false;   // (a NaN fails)
-      const int gx = orb_layer_pos(k.x, l), gy = orb_layer_pos(k.y, l), e = op.edge_threshold;
-      return gx >= e && gx < orb_layer_dim(c->p.width, l) - e && gy >= e && gy < orb_layer_dim(c->p.height, l) - e;
+      return orb_keypoint_ok(k.x, k.y, k.octave, op.n_levels, op.edge_threshold, c->p.width, c->p.height);
     };
     d.kp_msg = ": a key point that is not finite, has an octave outside 0..n_levels-1 or lies closer than edge_threshold to a border of "
                "its layer";
     d.chunk = &a;
     d.begin = [this](const int32_t* slots, int nf, size_t extra, unsigned char** x) { return begin(slots, nf, extra, x); };
-    d.detect = [this](int) { return launch_orb_detect(c->stream, a), (int)UWT_OK; };
+    d.detect = [this](int f0) {
+      if (d_path)
+        launch_orb_take_provided(c->stream, a, f0, n_pairs, d_path, reinterpret_cast<const OrbKeypoint*>(d_prev_kp), d_n_prev, mode);
+      launch_orb_detect(c->stream, a);
+      return (int)UWT_OK;
+    };
     d.describe = [this](int rows) { launch_orb_describe(c->stream, a, rows); };
   }
   // the geometry of a call: the layers, the quotas and, when the call detects, the bounds of the candidate lists
@@ -190,12 +200,13 @@ struct OrbCall {
     g.raw_stride = roff;
     g.kept_stride = (int)kept;
     d.frame_bytes = orb_layout(g, 1, cap, 0).total;
-    d.rows = std::min(cap, std::max(g.kept_stride, 1));
+    d.rows = d_path ? cap : std::min(cap, std::max(g.kept_stride, 1));   // (a provided list may hold cap records)
     return UWT_OK;
   }
   // Grows the scratch to a chunk of nf frames, sends the chunk's slot list and the pattern, and enqueues the layers.
   int begin(const int32_t* slots, int nf, size_t extra, unsigned char** extra_out) {
-    const OrbLayout l = orb_layout(g, nf, cap, extra);
+    const size_t modes = d_path ? sizeof(int) * (size_t)nf : 0;   // (no call has both)
+    const OrbLayout l = orb_layout(g, nf, cap, extra + modes);
     int st = c->orb_buf.reserve(c, c->stream, l.total);
     if (st) return st;
     st = orb_pattern_ready(c);
@@ -216,6 +227,7 @@ struct OrbCall {
     a.counts = (int*)(b + l.counts);
     a.cap = cap;
     a.pattern = (const signed char*)c->orb_pat.p;
+    a.mode = mode = modes ? (int*)(b + l.extra) : nullptr;
     if (extra_out) *extra_out = b + l.extra;
     HIPCHK(c, hipMemcpyAsync((void*)a.slots, slots, sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(a.raw_count, 0, sizeof(int) * (size_t)nf * kOrbMaxLevels, c->stream));
@@ -315,3 +327,25 @@ int uwt_orb_harris(uwt_ctx* c, int32_t slot, int32_t level, const int32_t* xy, i
 }
 
 }  // extern "C"
+
+// ---- what the chained tracking call uses of this unit (declared in uwt_ctx.h) -------------------------------------------------------
+// Nothing is enqueued when a check fails.
+int uwt::orb_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_orb_params* params,
+                   uwt_orb_params* op) {
+  int st = detect_check(c, what, n_frames, slots, cap);
+  return st ? st : orb_params_check(c, what, params, op);
+}
+
+// The tracking call's ORB: the path of every previous frame decided on the device, delivered as the asynchronous call delivers.
+int uwt::orb_track_enqueue(uwt_ctx* c, const uwt_orb_params& op, int n_pairs, const int32_t* slots, int cap, const int* d_path,
+                           const uwt_keypoint* d_prev_kp, const int32_t* d_n_prev, uwt_keypoint* d_kp, uint8_t* d_desc, int* d_counts) {
+  OrbCall o(c, nullptr, cap);
+  o.op = op;
+  o.d_path = d_path;
+  o.n_pairs = n_pairs;
+  o.d_prev_kp = d_prev_kp;
+  o.d_n_prev = d_n_prev;
+  o.plan(true);
+  return detect_run(c, o.d, 2 * n_pairs, slots, cap, nullptr, nullptr, true,
+                    [&](int f0, const DetectArgs& a) { return deliver_device(c, f0, a, d_kp, d_desc, d_counts); });
+}

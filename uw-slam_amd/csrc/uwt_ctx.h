@@ -157,7 +157,8 @@ struct uwt_ctx {
   DevBuf orb_buf, orb_pat;
   int8_t orb_pattern[1024] = {};
   int orb_pattern_state = 0;
-  // the chained tracking call (uwt_tracking_batch*): per pair and side the key points, descriptors and counts SURF leaves, the paths
+  // the chained tracking call (uwt_tracking_batch*, uwt_tracking_orb_batch*): per pair and side the key points, descriptors and counts
+  // the detector leaves, the paths
   // and flags of the previous frames, symMatches and the RANSAC records; behind them the synchronous form's inputs and results
   DevBuf track_buf;
   DevBuf stage[2];                      // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
@@ -232,11 +233,17 @@ int counted_rows_to_host(uwt_ctx* c, const float4* d_rows, size_t stride, const 
 // the checks of a SURF call (uwt_capi_surf.hip); *sp: the parameters in force
 int surf_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_surf_params* params,
                uwt_surf_params* sp);
-// SURF for the 2 x n_pairs frames of a tracking call, job j < n_pairs the previous frame of pair j under d_path[j] (kSurfDetect /
-// kSurfProvided at d_prev_kp, d_n_prev / kSurfNone), the others the current frames, detected: the chunk loop of every SURF call, each
+// SURF for the 2 x n_pairs frames of a tracking call, job j < n_pairs the previous frame of pair j under d_path[j] (kPathDetect /
+// kPathProvided at d_prev_kp, d_n_prev / kPathNone), the others the current frames, detected: the chunk loop of every SURF call, each
 // chunk's rows delivered to d_kp (2 n_pairs x cap records), d_desc (x 64 floats) and d_counts (2 n_pairs).  slots: the 2 n_pairs slots.
 int surf_track_enqueue(uwt_ctx* c, const uwt_surf_params& sp, int n_pairs, const int32_t* slots, int cap, const int* d_path,
                        const uwt_keypoint* d_prev_kp, const int32_t* d_n_prev, uwt_keypoint* d_kp, float* d_desc, int* d_counts);
+// the checks of an ORB call (uwt_capi_orb.hip); *op: the parameters in force
+int orb_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slots, int cap, const uwt_orb_params* params, uwt_orb_params* op);
+// ORB for the 2 x n_pairs frames of a tracking call, as surf_track_enqueue: the chunk loop of every ORB call under the context's
+// pattern in force, each chunk's rows delivered to d_kp, d_desc (2 n_pairs x cap x 32 bytes) and d_counts
+int orb_track_enqueue(uwt_ctx* c, const uwt_orb_params& op, int n_pairs, const int32_t* slots, int cap, const int* d_path,
+                      const uwt_keypoint* d_prev_kp, const int32_t* d_n_prev, uwt_keypoint* d_kp, uint8_t* d_desc, int* d_counts);
 // symMatches: a matching call's checks, k_knn2 both ways and k_match_filter.  MatchIn::device: the sets and counts are device memory,
 // read in place, a count outside 0..cap taken as 0 (uwt_match_descriptors_device_async); host: host memory (uwt_match_descriptors_batch*)
 enum class MatchIn { host, device };

@@ -30,6 +30,26 @@ struct DetectArgs {
   int desc_row;              // SURF: 64 floats, ORB: 32 bytes
 };
 
+// a frame's path in a tracking call (SurfArgs::mode, OrbArgs::mode), decided on the device: detection; the caller's key points; no
+// key points
+constexpr int kPathDetect = 0, kPathProvided = 1, kPathNone = 2;
+
+// The caller's key points from device memory (k_surf_take_provided, k_orb_take_provided), grid (ceil(cap / 256), n_frames), 256
+// threads.  The chunk's frames are jobs j0 .. of a tracking call over n_pairs pairs (job j < n_pairs: the previous frame of pair j, whose
+// path is path[j]; the others: current frames, always detected): writes the chunk's modes, and for a frame that is not detected its
+// count (the provided one, or 0) and the provided records into a.kp.  A provided count is in 0..cap (k_track_predicate refused the pair
+// otherwise).
+__device__ __forceinline__ void take_provided(const DetectArgs& a, int j0, int n_pairs, const int* __restrict__ path,
+                                              const Keypoint* __restrict__ prev_kp, const int* __restrict__ n_prev, int* __restrict__ mode) {
+  const int f = blockIdx.y, j = j0 + f, i = blockIdx.x * 256 + threadIdx.x;
+  const int m = j < n_pairs ? path[j] : kPathDetect;
+  if (i == 0) mode[f] = m;
+  if (m == kPathDetect) return;
+  const int n = m == kPathProvided ? min(max(n_prev[j], 0), a.cap) : 0;
+  if (i == 0) a.counts[f] = n;
+  if (i < n) a.kp[(size_t)f * a.cap + i] = prev_kp[(size_t)j * a.cap + i];
+}
+
 // ---- the pure host rules -----------------------------------------------------------------------------------------------------
 constexpr size_t kChunkBytes = 256u << 20;   // scratch a chunk of frames may take
 constexpr int kMaxChunk = 4096;              // frames of a chunk at most (a launch's grid)

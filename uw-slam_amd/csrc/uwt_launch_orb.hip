@@ -1,5 +1,5 @@
 // uwt_launch_orb.hip — the launches of ORB detection and description: k_orb_layers, k_orb_fast, k_orb_rank, k_orb_select,
-// k_orb_describe, k_orb_harris.
+// k_orb_describe, k_orb_harris, k_orb_take_provided.
 #include "uwt_orb_kernels.h"
 
 namespace uwt {
@@ -29,6 +29,12 @@ void launch_orb_describe(hipStream_t s, const OrbArgs& a, int rows) {
   if (rows < 1) return;
   hipLaunchKernelGGL(k_orb_describe, dim3((unsigned)((rows + kOrbDescWaves - 1) / kOrbDescWaves), (unsigned)a.n_frames),
                      dim3(64 * kOrbDescWaves), 0, s, a);
+}
+
+void launch_orb_take_provided(hipStream_t s, const OrbArgs& a, int j0, int n_pairs, const int* path, const OrbKeypoint* prev_kp,
+                              const int* n_prev, int* mode) {
+  hipLaunchKernelGGL(k_orb_take_provided, dim3((unsigned)((a.cap + 255) / 256), (unsigned)a.n_frames), dim3(256), 0, s, a, j0, n_pairs,
+                     path, prev_kp, n_prev, mode);
 }
 
 void launch_orb_harris(hipStream_t s, const OrbArgs& a, int level, const int* xy, int n, long long* out) {

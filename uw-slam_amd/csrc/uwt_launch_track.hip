@@ -4,9 +4,22 @@
 
 namespace uwt {
 
-void launch_track_predicate(hipStream_t s, int n_pairs, const SurfKeypoint* prev_kp, const int* n_prev, int cap, int min_matches,
-                            int* path, int* refused) {
-  hipLaunchKernelGGL(k_track_predicate, dim3((unsigned)n_pairs), dim3(256), 0, s, n_pairs, prev_kp, n_prev, cap, min_matches, path, refused);
+namespace {
+template <typename Rule>
+void track_predicate(hipStream_t s, int n_pairs, const Keypoint* prev_kp, const int* n_prev, int cap, int min_matches, const Rule& rule,
+                     int* path, int* refused) {
+  hipLaunchKernelGGL(k_track_predicate<Rule>, dim3((unsigned)n_pairs), dim3(256), 0, s, n_pairs, prev_kp, n_prev, cap, min_matches, rule,
+                     path, refused);
+}
+}  // namespace
+
+void launch_track_predicate(hipStream_t s, int n_pairs, const Keypoint* prev_kp, const int* n_prev, int cap, int min_matches,
+                            const SurfRecordRule& rule, int* path, int* refused) {
+  track_predicate(s, n_pairs, prev_kp, n_prev, cap, min_matches, rule, path, refused);
+}
+void launch_track_predicate(hipStream_t s, int n_pairs, const Keypoint* prev_kp, const int* n_prev, int cap, int min_matches,
+                            const OrbRecordRule& rule, int* path, int* refused) {
+  track_predicate(s, n_pairs, prev_kp, n_prev, cap, min_matches, rule, path, refused);
 }
 
 void launch_match_counts(hipStream_t s, int n_pairs, int cap, const int* n_query, const int* n_train, int* out_query, int* out_train) {

@@ -39,6 +39,14 @@ __host__ __device__ inline int orb_layer_dim(int n, int level) {
 __host__ __device__ inline int orb_layer_pos(float v, int level) {
   return (int)floor((double)v * (double)orb_pow(5, level) / (double)orb_pow(6, level) + 0.5);
 }
+// the range of a key point a caller provides (host lists: uwt_orb_describe_batch; device lists: k_track_predicate) on a w x h frame:
+// |x|, |y| <= 1e6, the octave in 0 .. n_levels - 1, the layer position at least `edge` from every border of its layer.  Comparisons
+// and orb_layer_pos only, so a NaN fails.
+__host__ __device__ inline bool orb_keypoint_ok(float x, float y, int octave, int n_levels, int edge, int w, int h) {
+  if (!(fabsf(x) <= 1e6f && fabsf(y) <= 1e6f && octave >= 0 && octave < n_levels)) return false;
+  const int gx = orb_layer_pos(x, octave), gy = orb_layer_pos(y, octave);
+  return gx >= edge && gx < orb_layer_dim(w, octave) - edge && gy >= edge && gy < orb_layer_dim(h, octave) - edge;
+}
 // candidates a layer's band holds at most: a strict maximum of its 3 x 3 has no candidate beside it
 inline size_t orb_raw_bound(int lw, int lh, int edge) {
   const long long bw = (long long)lw - 2 * edge, bh = (long long)lh - 2 * edge;
@@ -64,6 +72,9 @@ struct OrbArgs : DetectArgs {   // (desc: n_frames x cap x 32 bytes)
   unsigned char* keep;           // n_frames x kept_stride: work area of the capacity cut
   const signed char* pattern;    // 256 x (x0, y0, x1, y1)
   int* score_out = nullptr;      // the per-stage entry: the dense score map of frame 0's layer, lw x lh, zero before the launch
+  const int* mode = nullptr;     // n_frames, or null: every frame is detected.  Else the frame's path, decided on the device: only a
+                                 // frame with kPathDetect runs detection (k_orb_fast, k_orb_rank, k_orb_select return at once for the
+                                 // others, whose kp and counts come from k_orb_take_provided)
 };
 
 // layers 1 .. n_levels - 1 of every frame of the chunk, one launch
@@ -74,6 +85,10 @@ void launch_orb_fast(hipStream_t s, const OrbArgs& a, int level);
 void launch_orb_detect(hipStream_t s, const OrbArgs& a);
 // directions (unless a.upright) and descriptors of a.kp[f * cap .. + counts[f]); rows: the largest count the batch can hold
 void launch_orb_describe(hipStream_t s, const OrbArgs& a, int rows);
+// The chunk's frames are jobs j0 .. j0 + n_frames - 1 of a tracking call over n_pairs pairs (take_provided, uwt_detect.h): writes
+// a.mode, and for a frame that is not detected its count and the provided records into a.kp.  a.mode must be set.
+void launch_orb_take_provided(hipStream_t s, const OrbArgs& a, int j0, int n_pairs, const int* path, const OrbKeypoint* prev_kp,
+                              const int* n_prev, int* mode);
 // H at n pixels (x, y) of frame 0's layer: the per-stage entry
 void launch_orb_harris(hipStream_t s, const OrbArgs& a, int level, const int* xy, int n, long long* out);
 

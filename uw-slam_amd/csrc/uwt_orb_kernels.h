@@ -9,6 +9,7 @@
 //                    — the output is a function of the SET of candidates alone
 //   k_orb_describe   one wave per key point: the patch moments over the lanes, then 64 tests per pass balloted into a word
 //   k_orb_harris     the per-stage entry: a thread per given pixel
+//   k_orb_take_provided  the tracking call: the modes of a chunk's frames, and the provided records where detection would have put its own
 #pragma once
 
 #include "uwt_orb.h"
@@ -117,6 +118,7 @@ __global__ __launch_bounds__(kOrbBlock) void k_orb_fast(OrbArgs a, int l) {
   __shared__ uint8_t pix[P * P];
   __shared__ int sc[S * S];
   const int f = blockIdx.z, tid = threadIdx.x;
+  if (a.mode && a.mode[f] != kPathDetect) return;   // (uniform: ahead of every barrier)
   const int lw = a.lw[l], lh = a.lh[l], e = a.edge;
   int pitch;
   const uint8_t* img = orb_layer_ptr(a, f, l, &pitch);
@@ -167,6 +169,7 @@ __global__ __launch_bounds__(kOrbBlock) void k_orb_harris(OrbArgs a, int l, cons
 // there is its place among them, behind what the layers below keep.
 __global__ __launch_bounds__(kOrbRankBlock) void k_orb_rank(OrbArgs a) {
   const int l = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+  if (a.mode && a.mode[f] != kPathDetect) return;   // (uniform: ahead of every barrier)
   const int n = min(a.raw_count[f * kOrbMaxLevels + l], a.raw_cap[l]);
   int before = 0;
   for (int k = 0; k < l; k++) before += min(min(a.raw_count[f * kOrbMaxLevels + k], a.raw_cap[k]), a.quota[k]);
@@ -191,6 +194,7 @@ __global__ __launch_bounds__(kOrbRankBlock) void k_orb_rank(OrbArgs a) {
 // ascending); every kept candidate goes to the place its key has among the kept.
 __global__ __launch_bounds__(kOrbRankBlock) void k_orb_select(OrbArgs a) {
   const int f = blockIdx.x;
+  if (a.mode && a.mode[f] != kPathDetect) return;   // (uniform) the frame's count and key points come from elsewhere
   int n = 0;
   for (int k = 0; k < a.n_levels; k++) n += min(min(a.raw_count[f * kOrbMaxLevels + k], a.raw_cap[k]), a.quota[k]);
   const OrbKept* in = a.kept + (size_t)f * a.kept_stride;
@@ -213,6 +217,14 @@ __global__ __launch_bounds__(kOrbRankBlock) void k_orb_select(OrbArgs a) {
         a.kp[(size_t)f * a.cap + pos] = k;
       });
   if (threadIdx.x == 0) a.counts[f] = n;
+}
+
+// ---- the caller's key points from device memory (the tracking call) --------------------------------------------------------------
+// grid (ceil(cap / 256), n_frames): take_provided of uwt_detect.h
+__global__ __launch_bounds__(256) void k_orb_take_provided(OrbArgs a, int j0, int n_pairs, const int* __restrict__ path,
+                                                           const OrbKeypoint* __restrict__ prev_kp, const int* __restrict__ n_prev,
+                                                           int* __restrict__ mode) {
+  take_provided(a, j0, n_pairs, path, prev_kp, n_prev, mode);
 }
 
 // ---- direction and descriptor ------------------------------------------------------------------------------------------------------

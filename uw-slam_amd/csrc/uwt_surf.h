@@ -13,7 +13,6 @@ constexpr int kSurfTile = 32;          // grid points of a response tile along x
 constexpr int kSurfBlock = 256;
 constexpr int kSurfSelectBlock = 1024;
 constexpr int kSurfDescWaves = 4;      // key points of a describe block: one wave each
-constexpr int kSurfDetect = 0, kSurfProvided = 1, kSurfNone = 2;   // SurfArgs::mode: detection; the caller's key points; no key points
 
 using SurfKeypoint = Keypoint;
 
@@ -43,7 +42,7 @@ struct SurfArgs : DetectArgs {   // (desc: n_frames x cap x 64 floats)
   int raw_cap;               // surf_raw_bound: never exceeded
   unsigned char* keep;       // n_frames x raw_cap: work area of the selection
   const int* mode = nullptr; // n_frames, or null: every frame is detected.  Else the frame's path, decided on the device: only a
-                             // frame with kSurfDetect runs detection (k_surf_response, k_surf_select return at once for the others)
+                             // frame with kPathDetect runs detection (k_surf_response, k_surf_select return at once for the others)
 };
 
 // both passes of the integral image of every frame of the chunk

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kSurfBlock) void k_surf_response(SurfArgs a, int oc
   extern __shared__ double lds_r[];
   constexpr int T = kSurfTile + 2;
   const int f = blockIdx.z;
-  if (a.mode && a.mode[f] != kSurfDetect) return;   // (uniform: ahead of every barrier)
+  if (a.mode && a.mode[f] != kPathDetect) return;   // (uniform: ahead of every barrier)
   const uint32_t* I = a.integral + (size_t)f * (size_t)(a.h + 1) * (size_t)(a.w + 1);
   const int gx0 = blockIdx.x * kSurfTile - 1, gy0 = blockIdx.y * kSurfTile - 1;   // grid point of the tile's (0, 0), halo included
   const int L = a.layers;
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(kSurfBlock) void k_surf_response(SurfArgs a, int oc
 // every kept candidate goes to the place its key has among the kept.
 __global__ __launch_bounds__(kSurfSelectBlock) void k_surf_select(SurfArgs a) {
   const int f = blockIdx.x;
-  if (a.mode && a.mode[f] != kSurfDetect) return;   // (uniform) the frame's count and key points come from elsewhere
+  if (a.mode && a.mode[f] != kPathDetect) return;   // (uniform) the frame's count and key points come from elsewhere
   const SurfKeypoint* raw = a.raw + (size_t)f * a.raw_cap;
   const unsigned long long* key = a.raw_key + (size_t)f * a.raw_cap;
   const int n = select_ordered<kSurfSelectBlock>(
@@ -345,18 +345,11 @@ __global__ __launch_bounds__(64 * kSurfDescWaves) void k_surf_describe(SurfArgs 
 }
 
 // ---- the caller's key points from device memory (the tracking call) --------------------------------------------------------------
-// grid (ceil(cap / 256), n_frames).  path[] holds kSurfDetect / kSurfProvided / kSurfNone per pair; a provided count is in 0..cap
-// (k_track_predicate refused the pair otherwise).
+// grid (ceil(cap / 256), n_frames): take_provided of uwt_detect.h
 __global__ __launch_bounds__(256) void k_surf_take_provided(SurfArgs a, int j0, int n_pairs, const int* __restrict__ path,
                                                             const SurfKeypoint* __restrict__ prev_kp, const int* __restrict__ n_prev,
                                                             int* __restrict__ mode) {
-  const int f = blockIdx.y, j = j0 + f, i = blockIdx.x * 256 + threadIdx.x;
-  const int m = j < n_pairs ? path[j] : kSurfDetect;
-  if (i == 0) mode[f] = m;
-  if (m == kSurfDetect) return;
-  const int n = m == kSurfProvided ? min(max(n_prev[j], 0), a.cap) : 0;
-  if (i == 0) a.counts[f] = n;
-  if (i < n) a.kp[(size_t)f * a.cap + i] = prev_kp[(size_t)j * a.cap + i];
+  take_provided(a, j0, n_pairs, path, prev_kp, n_prev, mode);
 }
 
 }  // namespace uwt

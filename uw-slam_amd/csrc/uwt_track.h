@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "uwt_match.h"
+#include "uwt_orb.h"
 #include "uwt_ransac.h"
 #include "uwt_surf.h"
 
@@ -17,12 +18,23 @@ __host__ __device__ inline bool inside_level0(float x, float y, float w, float h
 
 struct TrackInfo { int status, used_provided, n_kp_prev, n_kp_cur, n_symmetric, n_matches, best_hypothesis, hypotheses_run; };
 
-// `usekeypoints` per pair, on the device: path[p] = kSurfProvided when the previous frame is described at its provided key points
-// (prev_kp != null, n_prev[p] >= 1 and >= min_matches), kSurfDetect when it is detected, kSurfNone — and refused[p] = 1 — when the
-// provided list is unusable: a count outside 0..cap, or a record of a used list that fails surf_keypoint_ok (the host checks of
-// uwt_surf_describe_batch).  One block per pair.
-void launch_track_predicate(hipStream_t s, int n_pairs, const SurfKeypoint* prev_kp, const int* n_prev, int cap, int min_matches,
-                            int* path, int* refused);
+// what a detector asks of a provided record: uwt_surf_describe_batch's host check, uwt_orb_describe_batch's (on a w x h frame under the
+// call's n_levels and edge_threshold)
+struct SurfRecordRule {
+  __host__ __device__ bool operator()(const Keypoint& k) const { return surf_keypoint_ok(k.x, k.y, k.size); }
+};
+struct OrbRecordRule {
+  int n_levels, edge, w, h;
+  __host__ __device__ bool operator()(const Keypoint& k) const { return orb_keypoint_ok(k.x, k.y, k.octave, n_levels, edge, w, h); }
+};
+
+// `usekeypoints` per pair, on the device: path[p] = kPathProvided when the previous frame is described at its provided key points
+// (prev_kp != null, n_prev[p] >= 1 and >= min_matches), kPathDetect when it is detected, kPathNone — and refused[p] = 1 — when the
+// provided list is unusable: a count outside 0..cap, or a record of a used list that fails the detector's rule.  One block per pair.
+void launch_track_predicate(hipStream_t s, int n_pairs, const Keypoint* prev_kp, const int* n_prev, int cap, int min_matches,
+                            const SurfRecordRule& rule, int* path, int* refused);
+void launch_track_predicate(hipStream_t s, int n_pairs, const Keypoint* prev_kp, const int* n_prev, int cap, int min_matches,
+                            const OrbRecordRule& rule, int* path, int* refused);
 // the counts of a device-input matching call as the kernels may use them: a count outside 0..cap is 0
 void launch_match_counts(hipStream_t s, int n_pairs, int cap, const int* n_query, const int* n_train, int* out_query, int* out_train);
 struct GoodKeypointsArgs {

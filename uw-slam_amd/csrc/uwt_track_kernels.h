@@ -1,6 +1,6 @@
 // uwt_track_kernels.h — the joints of the chained tracking call: small kernels that keep the data of System::Tracking's stages on the
 // device between them.  None of them does floating-point arithmetic: they compare, copy and count.
-//   k_track_predicate      usekeypoints per pair, with the checks of a provided list the host cannot make
+//   k_track_predicate      usekeypoints per pair, with the checks of a provided list the host cannot make (the record rule: SURF's or ORB's)
 //   k_match_counts         device counts of a matching call clamped to what the kernels may use
 //   k_good_keypoints       getGoodKeypoints on whole records, the live call's key points, the inside-level-0 check
 //   k_tracking_info        the per-pair record
@@ -10,20 +10,22 @@
 
 namespace uwt {
 
-static __global__ __launch_bounds__(256) void k_track_predicate(int n_pairs, const SurfKeypoint* __restrict__ prev_kp,
-                                                                const int* __restrict__ n_prev, int cap, int min_matches,
+// Rule: the detector's range check of a provided record (SurfRecordRule, OrbRecordRule), taken by value.
+template <typename Rule>
+static __global__ __launch_bounds__(256) void k_track_predicate(int n_pairs, const Keypoint* __restrict__ prev_kp,
+                                                                const int* __restrict__ n_prev, int cap, int min_matches, Rule ok,
                                                                 int* __restrict__ path, int* __restrict__ refused) {
   const int p = blockIdx.x, tid = threadIdx.x;
   const int n = prev_kp ? n_prev[p] : 0;
   int bad = (n < 0 || n > cap) ? 1 : 0;
   const bool use = !bad && prev_kp && n >= 1 && n >= min_matches;
   if (use) {
-    const SurfKeypoint* k = prev_kp + (size_t)p * cap;
-    for (int i = tid; i < n; i += 256) bad |= surf_keypoint_ok(k[i].x, k[i].y, k[i].size) ? 0 : 1;
+    const Keypoint* k = prev_kp + (size_t)p * cap;
+    for (int i = tid; i < n; i += 256) bad |= ok(k[i]) ? 0 : 1;
   }
   bad = __syncthreads_or(bad);
   if (tid == 0) {
-    path[p] = bad ? kSurfNone : (use ? kSurfProvided : kSurfDetect);
+    path[p] = bad ? kPathNone : (use ? kPathProvided : kPathDetect);
     refused[p] = bad ? 1 : 0;
   }
 }
@@ -73,7 +75,7 @@ static __global__ __launch_bounds__(256) void k_tracking_info(TrackInfoArgs a) {
   const RansacInfo* r = a.ransac + p;
   TrackInfo o;
   o.status = (a.refused[p] || a.outside[p]) ? a.invalid_status : r->status;
-  o.used_provided = a.path[p] == kSurfProvided ? 1 : 0;
+  o.used_provided = a.path[p] == kPathProvided ? 1 : 0;
   o.n_kp_prev = a.n_kp_prev[p];
   o.n_kp_cur = a.n_kp_cur[p];
   o.n_symmetric = a.n_symmetric[p];

@@ -383,18 +383,26 @@ def Tracking(tracker, robust_matcher, previous_frame, current_frame):
 
 def TrackingBatch(tracker, robust_matcher, pairs, cap=2048):
     """System::Tracking() for a list of (previous_frame, current_frame) pairs through the device-resident call
-    (uwt_tracking_batch): SURF, the matcher, ransacTest, getGoodKeypoints and the live alignment run as one chain on the device,
-    and keypoints_, surf_keypoints_, n_matches_ of both frames and previous_frame.rigid_transformation_ end up exactly as the
-    Tracking loop over the same list leaves them.  Pairs that share no frame go into one call; a pair that names a frame an earlier
+    (uwt_tracking_batch, or uwt_tracking_orb_batch for RobustMatcher(detector=1)): the detector, the matcher, ransacTest,
+    getGoodKeypoints and the live alignment run as one chain on the device, and keypoints_, surf_keypoints_ (orb_keypoints_ with ORB),
+    n_matches_ of both frames and previous_frame.rigid_transformation_ end up exactly as the Tracking loop over the same list with the
+    same matcher leaves them.  Pairs that share no frame go into one call; a pair that names a frame an earlier
     pair of the list has written (the next pair of a sequence) waits for that pair's results, as it does in the loop.  Returns
     the per-pair stats; a pair without a good match has ERR_NO_VALID_POINTS there and its frames' lists empty."""
     ctx = tracker._ctx
     rm = robust_matcher
-    params = capi.default_tracking_params(
-        surf=dict(hessian_threshold=rm.hessian_threshold_, n_octaves=rm.n_octaves_, n_octave_layers=rm.n_octave_layers_,
-                  upright=int(rm.upright_)),
-        ransac=dict(distance=rm.distance_, confidence=rm.confidence_, max_hypotheses=rm.max_hypotheses_, seed=rm.seed_),
-        ratio=rm.ratio_, min_matches=110)
+    build, _, _, kept = rm._DETECTORS[rm.detector_]
+    detector_params = build(rm)
+    common = dict(ransac=dict(distance=rm.distance_, confidence=rm.confidence_, max_hypotheses=rm.max_hypotheses_, seed=rm.seed_),
+                  ratio=rm.ratio_, min_matches=110)
+    fields = {k: getattr(detector_params, k) for k, _ in detector_params._fields_}
+    if rm.detector_ == 1:
+        params, call = capi.default_tracking_orb_params(orb=fields, **common), ctx.tracking_orb_batch
+        if rm.orb_pattern_ is not rm._pattern_sent:   # as DetectAndTrackFeatures: the context keeps a pattern until it is given another
+            ctx.orb_set_pattern(rm.orb_pattern_)
+            rm._pattern_sent = rm.orb_pattern_
+    else:
+        params, call = capi.default_tracking_params(surf=fields, **common), ctx.tracking_batch
     stats, i = [], 0
     while i < len(pairs):
         run, seen = [], set()
@@ -410,13 +418,13 @@ def TrackingBatch(tracker, robust_matcher, pairs, cap=2048):
         for (a, b), (sa, sb) in zip(run, slots):   # binding a later pair's frame may have taken an earlier frame's slot
             if a._slot != sa or b._slot != sb or not (a.obtained_gradients_ and b.obtained_gradients_):
                 raise RuntimeError("TrackingBatch: more frames than slots (max_frames)")
-        r = ctx.tracking_batch([s[0] for s in slots], [s[1] for s in slots], prev=[a.surf_keypoints_ for a, _ in run], params=params,
-                               cap=cap)
+        r = call([s[0] for s in slots], [s[1] for s in slots], prev=[getattr(a, kept) for a, _ in run], params=params, cap=cap)
         for k, (a, b) in enumerate(run):
             kp0, kp1 = r["kept_prev"][k], r["kept_cur"][k]
             a.n_matches_ = b.n_matches_ = len(kp0)
             a.keypoints_, b.keypoints_ = np.stack([kp0["x"], kp0["y"]], 1), np.stack([kp1["x"], kp1["y"]], 1)
-            a.surf_keypoints_, b.surf_keypoints_ = kp0, kp1
+            setattr(a, kept, kp0)
+            setattr(b, kept, kp1)
             a.rigid_transformation_ = r["poses"][k].copy()
             st = r["stats"][k]
             stats.append(dict(status=int(st["status"]), iterations=int(st["iterations"]), n_valid=int(st["n_valid"]), error=float(st["error"])))
