@@ -331,7 +331,13 @@ class Tracker {
   // tables are built and consumed on the device (previous->candidatePoints_ is left as it is); the reference's constants are
   // the call's own, so the tracker's params are not touched.  At most max_pairs pairs, whose frames must all be bound at once
   // (2 x pairs <= max_frames for distinct frames); per-pair stats in last_batch_stats().
-  void EstimatePoseFeaturesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs) {
+  // With options (uwt_table_options: robust weights and / or the bilinear sampler, the call's own): uwt_estimate_pose_features_batch_opt.
+  void EstimatePoseFeaturesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs) { features_batch(_pairs, nullptr); }
+  void EstimatePoseFeaturesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, const uwt_table_options& _options) {
+    features_batch(_pairs, &_options);
+  }
+ private:
+  void features_batch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, const uwt_table_options* opt) {
     const size_t n = _pairs.size();
     if (n == 0) return;
     std::vector<int32_t> a(n), b(n), counts(n);
@@ -352,19 +358,32 @@ class Tracker {
     }
     std::vector<float> poses(n * 7);
     last_batch_stats_.assign(n, uwt_stats{});
-    const int st = uwt_estimate_pose_features_batch(ctx(), (int32_t)n, a.data(), b.data(), kp.data(), counts.data(), poses.data(),
-                                                    last_batch_stats_.data());
+    const int st = opt ? uwt_estimate_pose_features_batch_opt(ctx(), (int32_t)n, a.data(), b.data(), kp.data(), counts.data(), opt,
+                                                              poses.data(), last_batch_stats_.data())
+                       : uwt_estimate_pose_features_batch(ctx(), (int32_t)n, a.data(), b.data(), kp.data(), counts.data(), poses.data(),
+                                                          last_batch_stats_.data());
     if (st == UWT_OK || st == UWT_ERR_PAIR_FAILED)
       for (size_t i = 0; i < n; i++) std::copy(poses.begin() + 7 * i, poses.begin() + 7 * (i + 1), _pairs[i].first->rigid_transformation_.data());
     if (st == UWT_OK) last_stats_ = last_batch_stats_.back();
-    check(st, "uwt_estimate_pose_features_batch");
+    check(st, opt ? "uwt_estimate_pose_features_batch_opt" : "uwt_estimate_pose_features_batch");
   }
+ public:
   // Semi-dense tracking for many pairs at once: ObtainCandidatePoints(previous) (src/Tracker.cpp:1314-1362) on the levels the
   // tracker iterates, then EstimatePose(previous, current) (:362-597) over those tables, under the tracker's params.  Each
   // previous frame's rigid_transformation_ comes out.  The candidate tables are built and consumed on the device
   // (previous->candidatePoints_ is left as it is).  At most max_pairs pairs, whose frames must all be bound at once (2 x pairs <=
   // max_frames for distinct frames); per-pair stats in last_batch_stats().
+  // With options (uwt_table_options: robust weights and / or the bilinear sampler, the call's own — the tracker's params keep theirs
+  // and are not looked at for them): uwt_estimate_pose_candidates_batch_opt.
   void EstimatePoseCandidatesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, double gradient_threshold = 20.0) {
+    candidates_batch(_pairs, gradient_threshold, nullptr);
+  }
+  void EstimatePoseCandidatesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, const uwt_table_options& _options,
+                                   double gradient_threshold = 20.0) {
+    candidates_batch(_pairs, gradient_threshold, &_options);
+  }
+ private:
+  void candidates_batch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, double gradient_threshold, const uwt_table_options* opt) {
     const size_t n = _pairs.size();
     if (n == 0) return;
     std::vector<int32_t> a(n), b(n);
@@ -380,13 +399,16 @@ class Tracker {
     }
     std::vector<float> poses(n * 7);
     last_batch_stats_.assign(n, uwt_stats{});
-    const int st = uwt_estimate_pose_candidates_batch(ctx(), (int32_t)n, a.data(), b.data(), gradient_threshold, poses.data(),
-                                                      last_batch_stats_.data());
+    const int st = opt ? uwt_estimate_pose_candidates_batch_opt(ctx(), (int32_t)n, a.data(), b.data(), gradient_threshold, opt,
+                                                                poses.data(), last_batch_stats_.data())
+                       : uwt_estimate_pose_candidates_batch(ctx(), (int32_t)n, a.data(), b.data(), gradient_threshold, poses.data(),
+                                                            last_batch_stats_.data());
     if (st == UWT_OK || st == UWT_ERR_PAIR_FAILED)
       for (size_t i = 0; i < n; i++) std::copy(poses.begin() + 7 * i, poses.begin() + 7 * (i + 1), _pairs[i].first->rigid_transformation_.data());
     if (st == UWT_OK) last_stats_ = last_batch_stats_.back();
-    check(st, "uwt_estimate_pose_candidates_batch");
+    check(st, opt ? "uwt_estimate_pose_candidates_batch_opt" : "uwt_estimate_pose_candidates_batch");
   }
+ public:
   // System::Tracking() (src/System.cpp:193-223) for a list of (previous, current) pairs through the device-resident call
   // (uwt_tracking_batch; uwt_tracking_orb_batch for RobustMatcher(tracker, 1)): the detector, the matcher, ransacTest, getGoodKeypoints
   // and the live alignment run as one chain on the device, and keypoints_, surf_keypoints_ (orb_keypoints_ with ORB), n_matches_ of

@@ -375,7 +375,8 @@ int uwt_obtain_patch_points_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t*
  * tgt_slots[i]; key points as in uwt_obtain_patch_points_batch.
  * Geometry, intrinsics, arith, has_depth and accumulate_f64 come from the context; its first_level, last_level, max_iters,
  * epsilon, gain, z_factor, angle_factor, initial_error, early_exit, weights and sampler are ignored and left as they are (no
- * uwt_update_params round trip).  1 <= n_pairs <= max_pairs, slots in range and every used key point inside level 0, or
+ * uwt_update_params round trip; the live call under robust weights or the bilinear sampler: uwt_track_features_batch_opt_async /
+ * uwt_estimate_pose_features_batch_opt below, which take them as options of the call).  1 <= n_pairs <= max_pairs, slots in range and every used key point inside level 0, or
  * UWT_ERR_INVALID_ARG with nothing enqueued.  A pair with no valid point (no key points, every key point on zero depth) gets
  * UWT_ERR_NO_VALID_POINTS in its own uwt_stats; the other pairs are unaffected.  The tables, their counts and the solver state
  * never leave the device: one producer launch, then one launch per Gauss-Newton evaluation with the update in its tail.
@@ -391,6 +392,36 @@ int uwt_estimate_pose_features_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_
                                      const float* keypoints_xy, const int32_t* n_keypoints,
                                      float* poses_out, uwt_stats* stats_out_or_null);
 
+/* ---- robust weights and the bilinear sampler in the batched table calls ---------------------------------------------- */
+
+/* The options of one batched table call.  They are the call's own: the context's weights and sampler are neither read nor changed. */
+typedef struct uwt_table_options {
+  int32_t weights;      /* as uwt_params::weights: 0 identity, 1 Tukey (the reference's TukeyFunctionWeights and medians), 2 Huber */
+  int32_t sampler;      /* as uwt_params::sampler: 0 round(), 1 bilinear */
+  int32_t reserved[6];  /* zero */
+} uwt_table_options;    /* 32 bytes */
+int uwt_default_table_options(uwt_table_options* o);   /* {0, 0} */
+
+/* uwt_track_features_batch_async / uwt_estimate_pose_features_batch under the call's own weights and sampler; everything else
+ * (the reference's constants of the live call, the arguments and their checks, ordering against uploads, asynchrony, failure per
+ * pair in the pair's own uwt_stats) as documented there.  opt_or_null null or {0, 0}: the code of the entries above, the same
+ * bytes.  weights outside 0..2, sampler outside 0..1 or a non-zero reserved word: UWT_ERR_INVALID_ARG with nothing enqueued.
+ * Otherwise, for every pair, pose and uwt_stats are what uwt_obtain_patch_points + uwt_estimate_pose_points give on a context whose
+ * params carry the live call's constants and these weights and sampler: per row the residual of either sampler, the weight from
+ * the pair's scale (median and MAD of the rounded residuals' 511 signed bins), w J, (r gain) w and the error numerator
+ * sum r (r w); f64 sums whatever accumulate_f64 says.  Weights and sampler combine freely here (Tukey over the bilinear sampler bins
+ * the rounded residual, as Huber does).  The tables never leave the device: with weights an evaluation is two launches (the
+ * scale pass, whose last block per pair derives the scale, then the weighted pass with the update in its tail), with the bilinear
+ * sampler alone one; the pairs' histograms are cleared once per call.  The rows are grouped by 1024 per block by the pair's own
+ * count and the blocks folded in slice order: a pair's bits depend neither on the batch it runs in, nor on its place there, nor
+ * on uwt_tuning. */
+int uwt_track_features_batch_opt_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                       const float* keypoints_xy, const int32_t* n_keypoints, const uwt_table_options* opt_or_null,
+                                       float* d_poses_out, uwt_stats* d_stats_out_or_null);
+int uwt_estimate_pose_features_batch_opt(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                         const float* keypoints_xy, const int32_t* n_keypoints, const uwt_table_options* opt_or_null,
+                                         float* poses_out, uwt_stats* stats_out_or_null);
+
 /* ---- semi-dense tracking for a batch of pairs (candidate tables built and consumed on the device) --------------------- */
 
 /* Tracker::ObtainCandidatePoints(previous) (src/Tracker.cpp:1314-1362) on levels last_level..first_level, then
@@ -402,7 +433,8 @@ int uwt_estimate_pose_features_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_
  * first_level, last_level, max_iters, epsilon, gain, z_factor, angle_factor, initial_error, early_exit, handoff_scale_t, arith and
  * accumulate_f64 — the constants uwt_estimate_pose_points honours — and reads the params without changing them.
  * weights != 0 or sampler != 0: UWT_ERR_INVALID_ARG with nothing enqueued (robust weights and the bilinear sampler over
- * candidate tables: uwt_obtain_candidate_points + uwt_estimate_pose_points).  So are 1 <= n_pairs <= max_pairs violated, a slot
+ * candidate tables: uwt_track_candidates_batch_opt_async / uwt_estimate_pose_candidates_batch_opt below, or the per-pair path,
+ * uwt_obtain_candidate_points + uwt_estimate_pose_points).  So are 1 <= n_pairs <= max_pairs violated, a slot
  * out of range, a null list and a non-finite threshold.
  * For every pair, pose and uwt_stats are the bits uwt_obtain_candidate_points per level followed by uwt_estimate_pose_points
  * give on the same context (f64 sums, accumulate_f64 = 1; the f32 sums of accumulate_f64 = 0 are grouped by 1024 rows here,
@@ -422,6 +454,20 @@ int uwt_track_candidates_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_
 /* The same, synchronous, results in host memory (UWT_ERR_PAIR_FAILED when a pair failed, its status in its uwt_stats). */
 int uwt_estimate_pose_candidates_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
                                        double threshold, float* poses_out, uwt_stats* stats_out_or_null);
+/* The same under the call's own weights and sampler (uwt_table_options, above): the context's weights and sampler are neither read
+ * nor changed, and the call does not refuse on them; the context's schedule and solver constants, the early-exit polls, the
+ * arguments and their checks, ordering against uploads, asynchrony and failure per pair are those of the entries above.
+ * opt_or_null null or {0, 0}: the code of the entries above, the same bytes.  A bad option: UWT_ERR_INVALID_ARG with nothing
+ * enqueued.  Otherwise, for every pair, pose and uwt_stats are what uwt_obtain_candidate_points per level followed by
+ * uwt_estimate_pose_points give on a context whose params carry these weights and sampler (f64 sums whatever accumulate_f64
+ * says, as there); launches per evaluation, grouping and the independence of batch, place and uwt_tuning as described at
+ * uwt_track_features_batch_opt_async. */
+int uwt_track_candidates_batch_opt_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                         double threshold, const uwt_table_options* opt_or_null, float* d_poses_out,
+                                         uwt_stats* d_stats_out_or_null);
+int uwt_estimate_pose_candidates_batch_opt(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                           double threshold, const uwt_table_options* opt_or_null, float* poses_out,
+                                           uwt_stats* stats_out_or_null);
 
 /* ---- descriptor matching for a batch of pairs: the matching half of RobustMatcher::DetectAndTrackFeatures -------------- */
 

@@ -86,6 +86,11 @@ class TrackingIO(C.Structure):
                 ("d_n_matches", C.c_void_p)]
 
 
+class TableOptions(C.Structure):
+    """uwt_table_options: the weights (0 identity, 1 Tukey, 2 Huber) and sampler (0 round(), 1 bilinear) of one batched table call"""
+    _fields_ = [("weights", C.c_int32), ("sampler", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 class Level(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
                 ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
@@ -119,6 +124,8 @@ SYMBOLS = [
     "uwt_default_ransac_params", "uwt_ransac_iterations", "uwt_ransac_inliers_batch", "uwt_ransac_inliers_batch_async",
     "uwt_obtain_patch_points_batch", "uwt_track_features_batch_async", "uwt_estimate_pose_features_batch",
     "uwt_track_candidates_batch_async", "uwt_estimate_pose_candidates_batch",
+    "uwt_default_table_options", "uwt_track_features_batch_opt_async", "uwt_estimate_pose_features_batch_opt",
+    "uwt_track_candidates_batch_opt_async", "uwt_estimate_pose_candidates_batch_opt",
     "uwt_default_surf_params", "uwt_keypoint_angle_deg", "uwt_surf_detect_describe_batch", "uwt_surf_detect_describe_batch_async",
     "uwt_surf_describe_batch", "uwt_surf_integral", "uwt_surf_response_layer",
     "uwt_default_orb_params", "uwt_orb_level_quota", "uwt_orb_default_pattern", "uwt_orb_layer_size", "uwt_orb_set_pattern",
@@ -197,6 +204,19 @@ def default_params(width, height, fx, fy, cx, cy, **over):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def table_options(weights=None, sampler=None):
+    """uwt_default_table_options ({0, 0}) with the given fields set"""
+    o = TableOptions()
+    st = lib().uwt_default_table_options(C.byref(o))
+    if st:
+        raise UwtError(st, "uwt_default_table_options")
+    if weights is not None:
+        o.weights = weights
+    if sampler is not None:
+        o.sampler = sampler
+    return o
 
 
 def default_ransac_params(**over):
@@ -733,48 +753,77 @@ class Context:
                                                       _p(pts, C.c_float), cap, _p(cnt, C.c_int32)))
         return [pts[f, :min(int(cnt[f]), cap)].copy() for f in range(sl.size)], cnt[:sl.size]
 
-    def estimate_pose_features_batch(self, ref_slots, tgt_slots, keypoints_list, raise_on_pair_failure=False):
+    def estimate_pose_features_batch(self, ref_slots, tgt_slots, keypoints_list, raise_on_pair_failure=False, weights=None,
+                                     sampler=None):
         """System::Tracking's live call for many pairs: keypoints_list[i] are the key points of the frame in ref_slots[i].
+        weights / sampler (either given): the call's own robust weights and sampler, uwt_estimate_pose_features_batch_opt.
         Returns (poses [P, 7], per-pair stats)."""
         ref = np.ascontiguousarray(ref_slots, np.int32)
         tgt = np.ascontiguousarray(tgt_slots, np.int32)
         kp, n = self._keypoint_block(keypoints_list)
         poses = np.empty((ref.size, 7), np.float32)
         stats = (Stats * max(ref.size, 1))()
-        st = lib().uwt_estimate_pose_features_batch(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
-                                                    _p(n, C.c_int32), _p(poses, C.c_float), stats)
+        if weights is None and sampler is None:
+            st = lib().uwt_estimate_pose_features_batch(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
+                                                        _p(n, C.c_int32), _p(poses, C.c_float), stats)
+        else:
+            opt = table_options(weights, sampler)
+            st = lib().uwt_estimate_pose_features_batch_opt(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
+                                                            _p(n, C.c_int32), C.byref(opt), _p(poses, C.c_float), stats)
         self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
         return poses, [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
 
-    def track_features_batch_async(self, ref_slots, tgt_slots, keypoints_list, d_poses_ptr, d_stats_ptr=None):
+    def track_features_batch_async(self, ref_slots, tgt_slots, keypoints_list, d_poses_ptr, d_stats_ptr=None, weights=None,
+                                   sampler=None):
         """The same enqueued on the context stream, results in device memory (d_poses_ptr: P x 7 float32, d_stats_ptr: P x 4
         int32-sized uwt_stats or None); sync() to wait."""
         ref = np.ascontiguousarray(ref_slots, np.int32)
         tgt = np.ascontiguousarray(tgt_slots, np.int32)
         kp, n = self._keypoint_block(keypoints_list)
-        self._chk(lib().uwt_track_features_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
-                                                       _p(n, C.c_int32), C.c_void_p(d_poses_ptr),
-                                                       C.c_void_p(d_stats_ptr) if d_stats_ptr else None))
+        d_stats = C.c_void_p(d_stats_ptr) if d_stats_ptr else None
+        if weights is None and sampler is None:
+            self._chk(lib().uwt_track_features_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
+                                                           _p(n, C.c_int32), C.c_void_p(d_poses_ptr), d_stats))
+        else:
+            opt = table_options(weights, sampler)
+            self._chk(lib().uwt_track_features_batch_opt_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
+                                                               _p(kp, C.c_float), _p(n, C.c_int32), C.byref(opt),
+                                                               C.c_void_p(d_poses_ptr), d_stats))
 
-    def estimate_pose_candidates_batch(self, ref_slots, tgt_slots, threshold=20.0, raise_on_pair_failure=False):
+    def estimate_pose_candidates_batch(self, ref_slots, tgt_slots, threshold=20.0, raise_on_pair_failure=False, weights=None,
+                                       sampler=None):
         """Semi-dense tracking for many pairs: Tracker::ObtainCandidatePoints(previous) on every iterated level, then EstimatePose
-        (previous, current) over those tables, under the context's params.  Returns (poses [P, 7], per-pair stats)."""
+        (previous, current) over those tables, under the context's params.  weights / sampler (either given): the call's own robust
+        weights and sampler, uwt_estimate_pose_candidates_batch_opt (the context's are then not looked at).
+        Returns (poses [P, 7], per-pair stats)."""
         ref = np.ascontiguousarray(ref_slots, np.int32)
         tgt = np.ascontiguousarray(tgt_slots, np.int32)
         poses = np.empty((max(ref.size, 1), 7), np.float32)
         stats = (Stats * max(ref.size, 1))()
-        st = lib().uwt_estimate_pose_candidates_batch(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.c_double(threshold),
-                                                      _p(poses, C.c_float), stats)
+        if weights is None and sampler is None:
+            st = lib().uwt_estimate_pose_candidates_batch(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.c_double(threshold),
+                                                          _p(poses, C.c_float), stats)
+        else:
+            opt = table_options(weights, sampler)
+            st = lib().uwt_estimate_pose_candidates_batch_opt(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
+                                                              C.c_double(threshold), C.byref(opt), _p(poses, C.c_float), stats)
         self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
         return poses[:ref.size], [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
 
-    def track_candidates_batch_async(self, ref_slots, tgt_slots, d_poses_ptr, d_stats_ptr=None, threshold=20.0):
+    def track_candidates_batch_async(self, ref_slots, tgt_slots, d_poses_ptr, d_stats_ptr=None, threshold=20.0, weights=None,
+                                     sampler=None):
         """The same enqueued on the context stream, results in device memory (d_poses_ptr: P x 7 float32, d_stats_ptr: P x 4
         int32-sized uwt_stats or None); sync() to wait."""
         ref = np.ascontiguousarray(ref_slots, np.int32)
         tgt = np.ascontiguousarray(tgt_slots, np.int32)
-        self._chk(lib().uwt_track_candidates_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.c_double(threshold),
-                                                         C.c_void_p(d_poses_ptr), C.c_void_p(d_stats_ptr) if d_stats_ptr else None))
+        d_stats = C.c_void_p(d_stats_ptr) if d_stats_ptr else None
+        if weights is None and sampler is None:
+            self._chk(lib().uwt_track_candidates_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
+                                                             C.c_double(threshold), C.c_void_p(d_poses_ptr), d_stats))
+        else:
+            opt = table_options(weights, sampler)
+            self._chk(lib().uwt_track_candidates_batch_opt_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
+                                                                 C.c_double(threshold), C.byref(opt), C.c_void_p(d_poses_ptr), d_stats))
 
     @staticmethod
     def _descriptor_block(pairs, packed, cap):

@@ -728,6 +728,20 @@ UpdateArgs update_args(uwt_ctx* c, int lvl) {
   return ua;
 }
 
+// the general path's per-pair histograms and scales, for a context created without robust weights (uwt_update_params, the table
+// batch's options); each piece is retried on its own after a failed allocation
+int ensure_general_buffers(uwt_ctx* c) {
+  if (c->hist && c->scale) return UWT_OK;
+  const size_t mp = (size_t)c->p.max_pairs;
+  if (!c->hist) HIPCHK(c, hipMalloc((void**)&c->hist, sizeof(unsigned int) * kHistBins * mp));
+  if (!c->scale) {
+    HIPCHK(c, hipMalloc((void**)&c->scale, sizeof(PairScale) * mp));
+    HIPCHK(c, hipMemset(c->scale, 0, sizeof(PairScale) * mp));
+    HIPCHK(c, hipStreamSynchronize(nullptr));   // (the NULL stream's memset against the context's non-blocking streams: see uwt_create)
+  }
+  return UWT_OK;
+}
+
 // the update of the evaluation `ra` launches, in that launch's tail (tail_update_wave) instead of k_gn_update(ua)
 void arm_tail(uwt_ctx* c, ResidualArgs& ra, const UpdateArgs& ua) {
   ra.tail.on = 1;
@@ -1130,11 +1144,9 @@ int uwt_update_params(uwt_ctx* c, const uwt_params* p) {
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_update_params: bad solver constants");
   (void)hipSetDevice(o.device);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if ((p->sampler || p->weights) && !c->hist) {
-    HIPCHK(c, hipMalloc((void**)&c->hist, sizeof(unsigned int) * kHistBins * o.max_pairs));
-    HIPCHK(c, hipMalloc((void**)&c->scale, sizeof(PairScale) * o.max_pairs));
-    HIPCHK(c, hipMemset(c->scale, 0, sizeof(PairScale) * o.max_pairs));
-    HIPCHK(c, hipStreamSynchronize(nullptr));   // (the NULL stream's memset against the context's non-blocking streams: see uwt_create)
+  if (p->sampler || p->weights) {
+    const int st = ensure_general_buffers(c);
+    if (st) return st;
   }
   c->p = *p;
   c->spec_budget = c->spec_calm = 0;   // a new schedule: the speculative budget starts over

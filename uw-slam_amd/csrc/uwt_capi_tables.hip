@@ -321,6 +321,19 @@ int enqueue_patch_tables(uwt_ctx* c, int n, const int* d_slots, const float* kp,
   return enqueue_patch_producer(c, n, d_slots);
 }
 
+// the options of a batched table call: null = {0, 0}; weights in 0..2, sampler in 0..1, reserved words zero
+int table_options(uwt_ctx* c, const char* what, const uwt_table_options* opt, uwt_table_options* out) {
+  std::memset(out, 0, sizeof(*out));
+  if (!opt) return UWT_OK;
+  if (opt->weights < 0 || opt->weights > 2 || opt->sampler < 0 || opt->sampler > 1)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": uwt_table_options: weights outside 0..2 or sampler outside 0..1");
+  for (int32_t r : opt->reserved)
+    if (r) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": uwt_table_options: reserved word not zero");
+  *out = *opt;
+  return UWT_OK;
+}
+constexpr uwt_table_options kIdentityTables = {};
+
 // One level of device-resident tables: pair i's rows at ta.tables + i * ta.stride, its count at ta.counts[i]; slices: the grid's
 // bound on a table's slices, which every pair's count obeys (the counts stay on the device), and the record stride
 struct TableLevel {
@@ -335,9 +348,19 @@ struct TableLevel {
 // once.  polls: the host reads the early exits back on the dense batch's schedule (enqueue_estimate) — the count
 // of pairs still on the level after evaluation first_poll - 1, then after twice as many, ..., each read one evaluation late; no
 // launch once none is left.  Without, nothing here waits for the device.
+// opt (checked by table_options): robust weights and / or the bilinear sampler — an evaluation is then k_table_hist (weights only)
+// + k_table_general, records of the general kind; the pairs' histogram rows are cleared here once, every scale pass leaves them so.
+// q.weights and q.sampler are not looked at.
 int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const TableLevel* lv, uint32_t* recs, bool polls,
-                           float* d_poses, StatsOut* d_stats) {
+                           const uwt_table_options& opt, float* d_poses, StatsOut* d_stats) {
   const int tb = 128, blocks = (n_pairs + tb - 1) / tb;
+  const bool general = opt.weights || opt.sampler;
+  if (opt.weights) {
+    int st = ensure_general_buffers(c);
+    if (st) return st;
+    HIPCHK(c, hipMemsetAsync(c->hist, 0, sizeof(unsigned int) * kHistBins * (size_t)n_pairs, c->stream));
+  }
+  const GeneralArgs ga = {opt.sampler, opt.weights, q.gain, c->hist, c->scale};
   hipLaunchKernelGGL(k_init_state, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, q.initial_error);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
@@ -355,13 +378,15 @@ int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const T
     ua.early_exit = q.early_exit;
     ua.epsilon = q.epsilon;
     ua.gain = q.gain;
+    if (general) ua.general = 1;
     LatePoll late(c->tn.first_poll);
     for (int k = 0; k < q.max_iters; k++) {
       ua.k = k;
       int st = late.arm(c, c->stream, polls, k, q.max_iters, &ua.active);
       if (st) return st;
       arm_tail(c, ra, ua);
-      uwt::launch_table_eval(c->stream, launch_sel(c), ra, lv[lvl].ta, n_pairs);
+      if (general) uwt::launch_table_general(c->stream, launch_sel(c), ra, lv[lvl].ta, ga, n_pairs);
+      else uwt::launch_table_eval(c->stream, launch_sel(c), ra, lv[lvl].ta, n_pairs);
       HIPCHK(c, hipGetLastError());
       bool none_left = false;
       st = late.look(c, c->stream, &none_left);
@@ -377,10 +402,14 @@ int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const T
 }
 
 // System::Tracking's live call for n_pairs pairs, enqueued on the context stream: the producer over the reference frames, then
-// enqueue_table_estimate under feature_params, which the host never polls.  No read-back, no wait for the device.
+// enqueue_table_estimate under feature_params and the call's options (null: identity weights, round()), which the host never
+// polls.  No read-back, no wait for the device.
 int features_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, const float* kp,
-                     const int32_t* n_kp, float* d_poses, StatsOut* d_stats) {
-  int st = check_features_args(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp);
+                     const int32_t* n_kp, const uwt_table_options* opt_or_null, float* d_poses, StatsOut* d_stats) {
+  uwt_table_options opt;
+  int st = table_options(c, what, opt_or_null, &opt);
+  if (st) return st;
+  st = check_features_args(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp);
   if (st) return st;
   st = ensure_features(c);
   if (st) return st;
@@ -394,7 +423,7 @@ int features_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* r
   int rows = 0;
   for (int i = 0; i < n_pairs; i++) rows = std::max(rows, std::min(n_kp[i], kPatchMaxKeypoints) * kPatchMaxRows);
   const TableLevel lv0 = {{c->feat_tab, c->feat_cnt, kFeatTableRows}, table_slices(rows)};
-  return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, d_poses, d_stats);
+  return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, opt, d_poses, d_stats);
 }
 
 }  // namespace
@@ -416,24 +445,54 @@ int uwt_obtain_patch_points_batch(uwt_ctx* c, int32_t n_frames, const int32_t* s
   return counted_rows_to_host(c, c->feat_tab, kFeatTableRows, c->feat_cnt, n_frames, cap, pts_out, counts_out);
 }
 
-int uwt_track_features_batch_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
-                                   const float* kp, const int32_t* n_kp, float* d_poses_out, uwt_stats* d_stats_out) {
+namespace {
+
+int features_async(uwt_ctx* c, const char* what, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, const float* kp,
+                   const int32_t* n_kp, const uwt_table_options* opt, float* d_poses_out, uwt_stats* d_stats_out) {
   if (c) (void)hipSetDevice(c->p.device);
-  if (!c || !d_poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_track_features_batch_async: null argument");
-  int st = features_enqueue(c, "uwt_track_features_batch_async", n_pairs, ref_slots, tgt_slots, kp, n_kp, d_poses_out,
-                            reinterpret_cast<StatsOut*>(d_stats_out));
+  if (!c || !d_poses_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  int st = features_enqueue(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out));
   if (st) return st;
   return compute_end(c, c->dep_first, c->dep_n);
 }
 
-int uwt_estimate_pose_features_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
-                                     const float* kp, const int32_t* n_kp, float* poses_out, uwt_stats* stats_out) {
+int features_sync(uwt_ctx* c, const char* what, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, const float* kp,
+                  const int32_t* n_kp, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out) {
   if (c) (void)hipSetDevice(c->p.device);
-  if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_features_batch: null argument");
-  const char* what = "uwt_estimate_pose_features_batch";
-  int st = features_enqueue(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp, c->d_poses, c->d_stats);
+  if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  int st = features_enqueue(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, c->d_poses, c->d_stats);
   if (st) return st;
   return read_back_pairs(c, what, n_pairs, poses_out, stats_out);
+}
+
+}  // namespace
+
+int uwt_default_table_options(uwt_table_options* o) {
+  if (!o) return UWT_ERR_INVALID_ARG;
+  std::memset(o, 0, sizeof(*o));
+  return UWT_OK;
+}
+
+int uwt_track_features_batch_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                   const float* kp, const int32_t* n_kp, float* d_poses_out, uwt_stats* d_stats_out) {
+  return features_async(c, "uwt_track_features_batch_async", n_pairs, ref_slots, tgt_slots, kp, n_kp, nullptr, d_poses_out, d_stats_out);
+}
+
+int uwt_estimate_pose_features_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                     const float* kp, const int32_t* n_kp, float* poses_out, uwt_stats* stats_out) {
+  return features_sync(c, "uwt_estimate_pose_features_batch", n_pairs, ref_slots, tgt_slots, kp, n_kp, nullptr, poses_out, stats_out);
+}
+
+int uwt_track_features_batch_opt_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                       const float* kp, const int32_t* n_kp, const uwt_table_options* opt, float* d_poses_out,
+                                       uwt_stats* d_stats_out) {
+  return features_async(c, "uwt_track_features_batch_opt_async", n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, d_poses_out, d_stats_out);
+}
+
+int uwt_estimate_pose_features_batch_opt(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                         const float* kp, const int32_t* n_kp, const uwt_table_options* opt, float* poses_out,
+                                         uwt_stats* stats_out) {
+  return features_sync(c, "uwt_estimate_pose_features_batch_opt", n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, poses_out, stats_out);
 }
 
 // ---- semi-dense tracking for a batch of pairs: candidate tables built and evaluated on the device ------------------------
@@ -443,16 +502,21 @@ namespace {
 // Tracker::ObtainCandidatePoints(previous) on levels last_level..first_level, then Tracker::EstimatePose(previous, current) over
 // those tables, for n_pairs pairs, enqueued on the context stream: per level the slot-list producer (pair i's table at cand_tab +
 // level offset + i * gw * gh, its count at cand_cnt[lvl * n_pairs + i]), then enqueue_table_estimate under the context's params,
-// polled under early_exit.  The only waits are the early-exit polls.
+// polled under early_exit.  The only waits are the early-exit polls.  with_options: an _opt entry — weights and sampler are the
+// call's (opt_or_null, null: identity and round()), the context's are not looked at; else the context's must be identity and round().
 int candidates_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
-                       float* d_poses, StatsOut* d_stats) {
+                       bool with_options, const uwt_table_options* opt_or_null, float* d_poses, StatsOut* d_stats) {
   const uwt_params& p = c->p;
-  int st = check_pair_lists(c, what, n_pairs, ref_slots, tgt_slots);
+  uwt_table_options opt;
+  int st = table_options(c, what, opt_or_null, &opt);
+  if (st) return st;
+  st = check_pair_lists(c, what, n_pairs, ref_slots, tgt_slots);
   if (st) return st;
   if (!std::isfinite(threshold)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": threshold is not finite");
-  if (p.weights || p.sampler)
+  if (!with_options && (p.weights || p.sampler))
     return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": identity weights and the nearest sampler only; robust weights or the "
-                                                            "bilinear sampler over candidate tables: uwt_estimate_pose_points");
+                                                            "bilinear sampler over candidate tables: uwt_estimate_pose_points, or "
+                                                            "uwt_track_candidates_batch_opt_async / uwt_estimate_pose_candidates_batch_opt");
   size_t rows = 0, work = 0, tab_off[UWT_MAX_LEVELS] = {};
   int smax = 1;
   for (int l = p.last_level; l <= p.first_level; l++) {
@@ -482,29 +546,56 @@ int candidates_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t*
     const int cells = c->lv[l].gw * c->lv[l].gh;   // the bound every pair's count obeys
     lv[l] = {{tab, cnt, cells}, table_slices(cells)};
   }
-  return enqueue_table_estimate(c, n_pairs, p, lv, (uint32_t*)c->cand_recs.p, p.early_exit != 0, d_poses, d_stats);
+  return enqueue_table_estimate(c, n_pairs, p, lv, (uint32_t*)c->cand_recs.p, p.early_exit != 0, opt, d_poses, d_stats);
+}
+
+}  // namespace
+
+namespace {
+
+int candidates_async(uwt_ctx* c, const char* what, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
+                     bool with_options, const uwt_table_options* opt, float* d_poses_out, uwt_stats* d_stats_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !d_poses_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  int st = candidates_enqueue(c, what, n_pairs, ref_slots, tgt_slots, threshold, with_options, opt, d_poses_out,
+                              reinterpret_cast<StatsOut*>(d_stats_out));
+  if (st) return st;
+  return compute_end(c, c->dep_first, c->dep_n);
+}
+
+int candidates_sync(uwt_ctx* c, const char* what, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
+                    bool with_options, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out) {
+  if (c) (void)hipSetDevice(c->p.device);
+  if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  int st = candidates_enqueue(c, what, n_pairs, ref_slots, tgt_slots, threshold, with_options, opt, c->d_poses, c->d_stats);
+  if (st) return st;
+  return read_back_pairs(c, what, n_pairs, poses_out, stats_out);
 }
 
 }  // namespace
 
 int uwt_track_candidates_batch_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
                                      float* d_poses_out, uwt_stats* d_stats_out) {
-  if (c) (void)hipSetDevice(c->p.device);
-  if (!c || !d_poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_track_candidates_batch_async: null argument");
-  int st = candidates_enqueue(c, "uwt_track_candidates_batch_async", n_pairs, ref_slots, tgt_slots, threshold, d_poses_out,
-                              reinterpret_cast<StatsOut*>(d_stats_out));
-  if (st) return st;
-  return compute_end(c, c->dep_first, c->dep_n);
+  return candidates_async(c, "uwt_track_candidates_batch_async", n_pairs, ref_slots, tgt_slots, threshold, false, nullptr, d_poses_out,
+                          d_stats_out);
 }
 
 int uwt_estimate_pose_candidates_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
                                        float* poses_out, uwt_stats* stats_out) {
-  if (c) (void)hipSetDevice(c->p.device);
-  if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_candidates_batch: null argument");
-  const char* what = "uwt_estimate_pose_candidates_batch";
-  int st = candidates_enqueue(c, what, n_pairs, ref_slots, tgt_slots, threshold, c->d_poses, c->d_stats);
-  if (st) return st;
-  return read_back_pairs(c, what, n_pairs, poses_out, stats_out);
+  return candidates_sync(c, "uwt_estimate_pose_candidates_batch", n_pairs, ref_slots, tgt_slots, threshold, false, nullptr, poses_out,
+                         stats_out);
+}
+
+int uwt_track_candidates_batch_opt_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
+                                         const uwt_table_options* opt, float* d_poses_out, uwt_stats* d_stats_out) {
+  return candidates_async(c, "uwt_track_candidates_batch_opt_async", n_pairs, ref_slots, tgt_slots, threshold, true, opt, d_poses_out,
+                          d_stats_out);
+}
+
+int uwt_estimate_pose_candidates_batch_opt(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                           double threshold, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out) {
+  return candidates_sync(c, "uwt_estimate_pose_candidates_batch_opt", n_pairs, ref_slots, tgt_slots, threshold, true, opt, poses_out,
+                         stats_out);
 }
 
 }  // extern "C"
@@ -523,5 +614,6 @@ int uwt::features_device_enqueue(uwt_ctx* c, int n_pairs, float* d_poses, uwt_st
   int st = enqueue_patch_producer(c, n_pairs, c->d_ref);
   if (st) return st;
   const TableLevel lv0 = {{c->feat_tab, c->feat_cnt, kFeatTableRows}, table_slices(kFeatTableRows)};
-  return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, d_poses, reinterpret_cast<StatsOut*>(d_stats));
+  return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, kIdentityTables, d_poses,
+                                reinterpret_cast<StatsOut*>(d_stats));
 }

@@ -107,7 +107,7 @@ struct uwt_ctx {
   size_t partial_records = 0;
   float* d_poses = nullptr;
   StatsOut* d_stats = nullptr;
-  unsigned int* hist = nullptr;         // general path: [pair][2][kHistBins]
+  unsigned int* hist = nullptr;         // general path: [pair][kHistBins], all-zero between evaluations
   PairScale* scale = nullptr;           // general path: [pair]
   int* d_active = nullptr;              // early-exit polling counters
   unsigned int* d_tickets = nullptr;    // tail update: one counter per pair, zero between launches
@@ -215,6 +215,7 @@ int launch_residual(uwt_ctx* c, hipStream_t s, const ResidualArgs& a, int n_pair
 int launch_general(uwt_ctx* c, hipStream_t s, const ResidualArgs& ra, int n_pairs, bool dump);
 ResidualArgs residual_args(uwt_ctx* c, int lvl);
 UpdateArgs update_args(uwt_ctx* c, int lvl);
+int ensure_general_buffers(uwt_ctx* c);
 void arm_tail(uwt_ctx* c, ResidualArgs& ra, const UpdateArgs& ua);
 int poll_arm(uwt_ctx* c);
 int poll_any_left(uwt_ctx* c, bool* left);

@@ -19,6 +19,8 @@
 //                  the evaluation's tail
 //   k_grad_mag_slots + k_candidates_slots + k_scan_counts, then k_table_eval per level   semi-dense tracking for a batch of pairs
 //                  (the producers of these two calls also serve the per-stage entries, over a slot list of their own)
+//   k_table_hist + k_table_general   the same two calls under uwt_table_options (robust weights / bilinear sampler): the scale pass
+//                  with the scale in its tail, then the weighted pass with the update in its tail
 //   k_ls_sequential   the LS mirror (src/LeastSquares.cpp): every accumulator's f32 chain in the reference's order
 //   k_add_patch_points, k_remap_crop, k_trajectory*   the rows next to the path
 //   masked_sums_*  a pixel's 28 f64 sums under an EXEC mask of the valid lanes (no select anywhere in the loop)
@@ -2297,12 +2299,52 @@ __device__ __forceinline__ void hist_groups(const LevelK& L, const WarpK& K, con
   }
 }
 
+// The tail of a scale pass's block: the block's LDS histogram h (bin b at h[b * REP], REP replicas summed) goes to the pair's
+// global bins gh, then a ticket is drawn; of the `expected` blocks that draw one for this pair and evaluation, the last reads and
+// clears the bins, derives the scale into *scale_out and clears the ticket word.  hist_block expects the launch's slices, the
+// table form (k_table_hist) the pair's own slice count.  Every thread of the block calls it, behind a barrier after its last count.
+template <int REP>
+__device__ __forceinline__ void hist_flush_scale(unsigned int* __restrict__ h, unsigned int* __restrict__ gh, const unsigned int expected,
+                                                 PairScale* __restrict__ scale_out, int weights) {
+  __shared__ int s_last;
+  // This block's counts must be performed (at the device's coherence point, where atomics execute) before its ticket is
+  // drawn.  No fence: a release fence writes back the XCD's whole L2 (and 256 threads issuing one each took the scale
+  // pass from 41 to 265 us per launch) — instead the adds RETURN their old values, which come from the coherence point, so
+  // a thread that holds them has its adds performed; the barrier collects all threads.
+  unsigned int seen = 0;
+  for (int i = threadIdx.x; i < kHistBins - 1; i += kBlock) {
+    unsigned int t;
+    if constexpr (REP == 8) {
+      const uint4 lo = *reinterpret_cast<const uint4*>(&h[i * REP]), hi = *reinterpret_cast<const uint4*>(&h[i * REP + 4]);
+      t = lo.x + lo.y + lo.z + lo.w + hi.x + hi.y + hi.z + hi.w;
+    } else {
+      static_assert(REP == 1, "eight replicas or one");
+      t = h[i];
+    }
+    if (t) seen |= atomicAdd(&gh[i], t);
+  }
+  if (seen == 0xffffffffu) s_last = 0;   // (never true: a use the compiler cannot drop, so the returns are waited for)
+  __syncthreads();
+  if (threadIdx.x == 0) s_last = atomicAdd(&gh[kHistTicketWord], 1u) == expected - 1u ? 1 : 0;
+  __syncthreads();
+  if (!s_last || threadIdx.x >= 64) return;
+  const int lane = threadIdx.x;
+  unsigned int mine[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int b = lane * 8 + k;
+    mine[k] = b < 511 ? atomicExch(&gh[b], 0u) : 0u;   // read at the coherence point, leave the bin cleared
+  }
+  if (lane == 0) atomicExch(&gh[kHistTicketWord], 0u);
+  const PairScale sc = wave_scale(mine, h, weights == kWeightsTukeyRef, lane);   // (h: every wave of the block is past its flush)
+  if (lane == 0) *scale_out = sc;
+}
+
 // the scale pass of one block: slice blockIdx.x of `pair` at `pose` (the body of k_resid_hist_v and of k_hist_iterate)
 template <int AR, int VEC, bool DEPTH, int SAMPLER, bool RAGGED>
 __device__ __forceinline__ void hist_block(const ResidualArgs& a, const int pair, const Pose& pose, const int ref_slot, const int tgt_slot,
                                            unsigned int* __restrict__ hist, PairScale* __restrict__ scale_out, int weights) {
   __shared__ unsigned int h[kHistBins * kHistRep];
-  __shared__ int s_last;
   for (int i = threadIdx.x; i < kHistRep * kHistBins; i += kBlock) h[i] = 0;
   __syncthreads();
   WarpK K;
@@ -2319,32 +2361,7 @@ __device__ __forceinline__ void hist_block(const ResidualArgs& a, const int pair
   hist_groups<AR, VEC, DEPTH, SAMPLER, RAGGED>(L, K, I1, I2, DP, myh, g_begin, g_end, n_groups);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the masked ds_add_u32 above are the asm's own: the compiler does not count them
   __syncthreads();
-  unsigned int* gh = hist + (size_t)pair * kHistBins;
-  // This block's counts must be performed (at the device's coherence point, where atomics execute) before its ticket is
-  // drawn.  No fence: a release fence writes back the XCD's whole L2 (and 256 threads issuing one each took the scale
-  // pass from 41 to 265 us per launch) — instead the adds RETURN their old values, which come from the coherence point, so
-  // a thread that holds them has its adds performed; the barrier collects all threads.
-  unsigned int seen = 0;
-  for (int i = threadIdx.x; i < kHistBins - 1; i += kBlock) {
-    const uint4 lo = *reinterpret_cast<const uint4*>(&h[i * kHistRep]), hi = *reinterpret_cast<const uint4*>(&h[i * kHistRep + 4]);
-    const unsigned int t = lo.x + lo.y + lo.z + lo.w + hi.x + hi.y + hi.z + hi.w;
-    if (t) seen |= atomicAdd(&gh[i], t);
-  }
-  if (seen == 0xffffffffu) s_last = 0;   // (never true: a use the compiler cannot drop, so the returns are waited for)
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(&gh[kHistTicketWord], 1u) == gridDim.x - 1 ? 1 : 0;
-  __syncthreads();
-  if (!s_last || threadIdx.x >= 64) return;
-  const int lane = threadIdx.x;
-  unsigned int mine[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const int b = lane * 8 + k;
-    mine[k] = b < 511 ? atomicExch(&gh[b], 0u) : 0u;   // read at the coherence point, leave the bin cleared
-  }
-  if (lane == 0) atomicExch(&gh[kHistTicketWord], 0u);
-  const PairScale sc = wave_scale(mine, h, weights == kWeightsTukeyRef, lane);   // (h: every wave of the block is past its flush)
-  if (lane == 0) scale_out[pair] = sc;
+  hist_flush_scale<kHistRep>(h, hist + (size_t)pair * kHistBins, gridDim.x, scale_out + pair, weights);
 }
 
 template <int AR, int VEC, bool DEPTH, int SAMPLER, bool RAGGED = false>
@@ -3297,6 +3314,104 @@ __global__ __launch_bounds__(kBlock) void k_table_eval(const ResidualArgs a, con
   uint32_t* rec = a.partials + ((size_t)pair * a.slices + blockIdx.x) * kRecWords;
   if constexpr (MASKED) block_reduce_store<AccT, false, double>(acc, r2d, n_valid, rec, (AccT)0, true);
   else block_reduce_store<AccT>(acc, sum_r2, n_valid, rec, (AccT)0, true);
+  if (threadIdx.x < 64) tail_fold_wave(a, pair, a.slices, slices);   // wave 0 wrote the block's record
+}
+
+// The batched tables on the general path (uwt_table_options: robust weights and / or the bilinear sampler), k_table_eval's grid,
+// slicing and early returns.  Per evaluation with weights: k_table_hist, then k_table_general; without: k_table_general alone.
+// Per row the terms of k_points_hist / k_points_general, so a pair's pose is what uwt_estimate_pose_points gives under
+// uwt_params::weights / ::sampler; the sums are f64 whatever accumulate_f64 says, as there.
+//
+// k_table_hist — the scale pass: a block counts rint(rf) of its up to kFeatPtsPerBlock rows in one 512-word LDS histogram
+// (k_points_hist's), then hist_flush_scale with the pair's own slice count: the pair's last block leaves the scale in
+// ga.scale[pair] and the pair's row of ga.hist all-zero again.  No clearing per evaluation, no launch for the scale.
+template <int AR>
+__global__ __launch_bounds__(kBlock) void k_table_hist(const ResidualArgs a, const TableArgs ta, const GeneralArgs ga) {
+  const int pair = (int)blockIdx.y + a.pair_base;
+  const int count = min(ta.counts[pair], ta.stride);
+  const int slices = min(table_slices(count), a.slices);
+  if ((int)blockIdx.x >= slices) return;
+  const PairState st = a.state[pair];
+  if (st.level_done || st.status) return;
+  __shared__ unsigned int h[kHistBins];
+  for (int i = threadIdx.x; i < kHistBins; i += kBlock) h[i] = 0;
+  __syncthreads();
+  float T[12];
+  pose_to_T12(st.pose, T);
+  const LevelK L = a.L;
+  const uint8_t* __restrict__ I1 = a.img + (size_t)a.ref_slots[pair] * L.n;
+  const uint8_t* __restrict__ I2 = a.img + (size_t)a.tgt_slots[pair] * L.n;
+  const float4* __restrict__ tab = ta.tables + (size_t)pair * ta.stride;
+#pragma unroll
+  for (int r = 0; r < kFeatPtsPerBlock / kBlock; r++) {
+    const int q = (int)blockIdx.x * kFeatPtsPerBlock + r * kBlock + (int)threadIdx.x;
+    if (q >= count) continue;
+    float x2, y2, iz, rf;
+    uint32_t i1x;
+    if (!general_point<AR>(L, T, ga.sampler, I1, I2, tab[q], x2, y2, iz, rf, i1x)) continue;
+    atomicAdd(&h[(int)rintf(rf) + 255], 1u);   // |rf| <= 255 on a valid row: bins 0..510
+  }
+  __syncthreads();
+  hist_flush_scale<1>(h, ga.hist + (size_t)pair * kHistBins, (unsigned int)slices, ga.scale + pair, ga.weights);
+}
+
+// k_table_general — the weighted / bilinear pass: four rows per thread, the 27 f64 sums and the error numerator under an EXEC
+// mask of the valid lanes (masked_sums_*), integer sum of rint(rf)^2, the record of the `general` kind through
+// block_reduce_store(.., err, coherent), the update in the launch's tail (tail_fold_wave; the host arms tail.general = 1).
+template <int AR, bool UNIT_FACTORS>
+__global__ __launch_bounds__(kBlock) void k_table_general(const ResidualArgs a, const TableArgs ta, const GeneralArgs ga) {
+  const int pair = (int)blockIdx.y + a.pair_base;
+  const int count = min(ta.counts[pair], ta.stride);
+  const int slices = min(table_slices(count), a.slices);
+  if ((int)blockIdx.x >= slices) return;
+  const PairState st = a.state[pair];
+  if (st.level_done || st.status) return;
+  float T[12];
+  pose_to_T12(st.pose, T);
+  const LevelK L = a.L;
+  const size_t ref_off = (size_t)a.ref_slots[pair] * L.n;
+  const uint8_t* __restrict__ I1 = a.img + ref_off;
+  const uint8_t* __restrict__ I2 = a.img + (size_t)a.tgt_slots[pair] * L.n;
+  const int16_t* __restrict__ GX = a.gx + ref_off;
+  const int16_t* __restrict__ GY = a.gy + ref_off;
+  const float4* __restrict__ tab = ta.tables + (size_t)pair * ta.stride;
+  const float inv_mad = ga.weights ? ga.scale[pair].inv_mad : 1.f;   // (the scale pass of this evaluation: the launch before)
+  double acc[kAccFloats];
+#pragma unroll
+  for (int i = 0; i < kAccFloats; i++) acc[i] = 0.0;
+  double err = 0.0;
+  uint32_t sum_r2 = 0, n_valid = 0;
+#pragma unroll
+  for (int r = 0; r < kFeatPtsPerBlock / kBlock; r++) {
+    const int q = (int)blockIdx.x * kFeatPtsPerBlock + r * kBlock + (int)threadIdx.x;
+    float x2 = 0.f, y2 = 0.f, iz = 0.f, rf = 0.f;
+    uint32_t i1x = 0;
+    bool ok = q < count;
+    if (ok) ok = general_point<AR>(L, T, ga.sampler, I1, I2, tab[q], x2, y2, iz, rf, i1x);
+    float g0 = 0.f, g1 = 0.f;
+    if (ok) {
+      g0 = (float)GX[i1x];
+      g1 = (float)GY[i1x];
+    }
+    float J[6];
+    pixel_jacobian<AR, UNIT_FACTORS, false, true>(L, a.zf, a.af, x2, y2, iz, g0, g1, J);
+    const float w = robust_weight(ga.weights, rf, inv_mad);
+    const double e = (double)rf * (double)(rf * w);   // Residuals.mul(W) for the error (src/Tracker.cpp:500)
+    const float rw = (rf * ga.gain) * w;              // :559, :561
+    double Jd[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) Jd[k] = (double)(w * J[k]);   // :556
+    const unsigned long long m = __ballot(ok);
+    masked_sums_lo(acc, Jd, m);
+    masked_sums_hi<1>(acc, err, Jd, (double)rw, e, m);
+    if (ok) {
+      const int qr = (int)rintf(rf);
+      sum_r2 += (uint32_t)(qr * qr);
+      n_valid += 1u;
+    }
+  }
+  uint32_t* rec = a.partials + ((size_t)pair * a.slices + blockIdx.x) * kRecWords;
+  block_reduce_store<double, true>(acc, sum_r2, n_valid, rec, err, true);
   if (threadIdx.x < 64) tail_fold_wave(a, pair, a.slices, slices);   // wave 0 wrote the block's record
 }
 

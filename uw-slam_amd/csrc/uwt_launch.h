@@ -40,6 +40,10 @@ void launch_patch_points_batch(hipStream_t s, int n_frames, const float2* kp, co
                                const uint16_t* depth0, size_t slot_elems, int pitch, int w, int h, float4* out, int stride,
                                int* counts);
 void launch_table_eval(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, int n_pairs);
+// the same on the general path (uwt_table_options): k_table_hist (weights != 0; the pairs' bins are all-zero before and after), then
+// k_table_general with the update in its tail
+void launch_table_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, const GeneralArgs& ga,
+                          int n_pairs);
 // gradient_ of one level for a batch of frames (k_grad_mag_slots): frame f's plane at mag + f * L.n, its sum added to sums[f]
 // (cleared by the caller)
 void launch_grad_mag(hipStream_t s, const LevelK& L, int n_frames, const int* slots, const int16_t* gx, const int16_t* gy, uint8_t* mag,

@@ -1,6 +1,6 @@
 // uwt_launch_points.hip — dispatch of the sparse point producers over a slot list, for the batched calls and the per-stage entries:
 // the patch producer (k_patch_points_batch), gradient_ (k_grad_mag_slots) and the candidate producer (k_candidates_slots,
-// k_scan_counts); and of the batched table evaluation (k_table_eval).
+// k_scan_counts); and of the batched table evaluation (k_table_eval; k_table_hist + k_table_general).
 #include "uwt_launch.h"
 
 namespace uwt {
@@ -37,6 +37,16 @@ void launch_table_eval(hipStream_t s, const LaunchSel& sel, const ResidualArgs& 
     else if (unit) hipLaunchKernelGGL((k_table_eval<AR, true, float>), grid, blk, 0, s, a, ta);
     else if (sel.acc64) hipLaunchKernelGGL((k_table_eval<AR, false, double>), grid, blk, 0, s, a, ta);
     else hipLaunchKernelGGL((k_table_eval<AR, false, float>), grid, blk, 0, s, a, ta));
+}
+
+void launch_table_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, const GeneralArgs& ga,
+                          int n_pairs) {
+  const bool unit = (a.zf == 1.0f && a.af == 1.0f);
+  const dim3 grid(a.slices, n_pairs), blk(kBlock);
+  if (ga.weights) UWT_WITH_AR(sel.arith, hipLaunchKernelGGL((k_table_hist<AR>), grid, blk, 0, s, a, ta, ga));
+  UWT_WITH_AR(sel.arith,
+    if (unit) hipLaunchKernelGGL((k_table_general<AR, true>), grid, blk, 0, s, a, ta, ga);
+    else hipLaunchKernelGGL((k_table_general<AR, false>), grid, blk, 0, s, a, ta, ga));
 }
 
 }  // namespace uwt

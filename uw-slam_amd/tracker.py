@@ -179,11 +179,12 @@ class Tracker:
         _previous_frame.rigid_transformation_ = pose
         return st
 
-    def EstimatePoseFeaturesBatch(self, _pairs):
+    def EstimatePoseFeaturesBatch(self, _pairs, weights=None, sampler=None):
         """System::Tracking's live call (src/System.cpp:214-219) for a list of (previous, current) frame pairs in one call
         (uwt_estimate_pose_features_batch, as uw::Tracker::EstimatePoseFeaturesBatch): each previous frame's keypoints_ go in,
         its rigid_transformation_ comes out.  The reference's constants are the call's own; the tracker's params are not touched.
-        Returns the per-pair stats."""
+        weights (0 identity, 1 Tukey, 2 Huber) / sampler (0 round(), 1 bilinear), either given: the call's own options
+        (uwt_estimate_pose_features_batch_opt).  Returns the per-pair stats."""
         slots = [(self._bind(a), self._bind(b)) for a, b in _pairs]
         for (a, b), (sa, sb) in zip(_pairs, slots):   # binding a later pair's frame may have taken an earlier frame's slot
             if a._slot != sa or b._slot != sb:
@@ -191,7 +192,24 @@ class Tracker:
             if not a.obtained_gradients_:
                 raise RuntimeError("ApplyGradient(previous_frame) must run before EstimatePoseFeaturesBatch (or its slot was reused since)")
         poses, stats = self._ctx.estimate_pose_features_batch([s[0] for s in slots], [s[1] for s in slots],
-                                                              [a.keypoints_ for a, _ in _pairs])
+                                                              [a.keypoints_ for a, _ in _pairs], weights=weights, sampler=sampler)
+        for (a, _), pose in zip(_pairs, poses):
+            a.rigid_transformation_ = pose.copy()
+        return stats
+
+    def EstimatePoseCandidatesBatch(self, _pairs, gradient_threshold=20.0, weights=None, sampler=None):
+        """Semi-dense tracking for a list of (previous, current) frame pairs in one call (uwt_estimate_pose_candidates_batch, as
+        uw::Tracker::EstimatePoseCandidatesBatch): ObtainCandidatePoints(previous) on the iterated levels, then EstimatePose over
+        those tables under the tracker's params; each previous frame's rigid_transformation_ comes out.  weights / sampler, either
+        given: the call's own options (uwt_estimate_pose_candidates_batch_opt).  Returns the per-pair stats."""
+        slots = [(self._bind(a), self._bind(b)) for a, b in _pairs]
+        for (a, b), (sa, sb) in zip(_pairs, slots):   # binding a later pair's frame may have taken an earlier frame's slot
+            if a._slot != sa or b._slot != sb:
+                raise RuntimeError("EstimatePoseCandidatesBatch: more frames than slots (max_frames)")
+            if not a.obtained_gradients_:
+                raise RuntimeError("ApplyGradient(previous_frame) must run before EstimatePoseCandidatesBatch (or its slot was reused since)")
+        poses, stats = self._ctx.estimate_pose_candidates_batch([s[0] for s in slots], [s[1] for s in slots], gradient_threshold,
+                                                                weights=weights, sampler=sampler)
         for (a, _), pose in zip(_pairs, poses):
             a.rigid_transformation_ = pose.copy()
         return stats
