@@ -326,7 +326,14 @@ int uwt_solve_delta(uwt_ctx* ctx, const float A[36], const float b[6], float del
  * With the EstimatePoseFeatures constants (first = last = 0, max_iters 10, gain 1, z_factor 0.002, handoff_scale_t 1;
  * src/Tracker.cpp:634-640, 834, 856) this is the reference's live tracking call.  uwt_params::weights and ::sampler apply as in
  * the dense call.  A row whose reference position ((int)y, (int)x) lies outside the level is dropped (the reference's
- * Mat::at would read outside the image, :474-477). */
+ * Mat::at would read outside the image, :474-477).
+ * The call is a batch of one pair over the kernels of the batched table calls below: the tables are copied to the device, their
+ * rows grouped by 1024 per block and the blocks folded in slice order, the update in each evaluation's tail; with early_exit = 1
+ * the early exits are polled as uwt_track_candidates_batch_async polls them.  Pose and uwt_stats are the same bits as theirs for
+ * the same tables under either accumulate_f64.  (This call used to group its rows by 8192: under accumulate_f64 = 0 on the
+ * identity path, whose f32 sums follow the grouping, the last bits of a pose may differ from what it gave then.  The default's
+ * f64 sums and every pose under weights or the bilinear sampler have not moved.)  Like the batched calls, it is ordered behind
+ * uwt_upload_frames_async into its two slots. */
 int uwt_estimate_pose_points(uwt_ctx* ctx, int32_t ref_slot, int32_t tgt_slot, const float* const* tables,
                              const int32_t* n_points, float pose_out[7], uwt_stats* stats_out_or_null);
 /* Tracker::MedianMat (src/Tracker.cpp:1571-1594), MedianAbsoluteDeviation (:1607-1619), IdentityWeights (:1621-1624) and
@@ -437,10 +444,10 @@ int uwt_estimate_pose_features_batch_opt(uwt_ctx* ctx, int32_t n_pairs, const in
  * uwt_obtain_candidate_points + uwt_estimate_pose_points).  So are 1 <= n_pairs <= max_pairs violated, a slot
  * out of range, a null list and a non-finite threshold.
  * For every pair, pose and uwt_stats are the bits uwt_obtain_candidate_points per level followed by uwt_estimate_pose_points
- * give on the same context (f64 sums, accumulate_f64 = 1; the f32 sums of accumulate_f64 = 0 are grouped by 1024 rows here,
- * by 8192 there).  A pair's pose depends neither on the batch it runs in, nor on its place there, nor on uwt_tuning.  A pair
- * with no valid point on a level (a flat reference frame, every candidate on a zero depth byte) gets its status in its own
- * uwt_stats, as uwt_estimate_pose_points reports it; the other pairs are unaffected.
+ * give on the same context, under either accumulate_f64 (one grouping, 1024 rows per block, serves both calls).  A pair's pose
+ * depends neither on the batch it runs in, nor on its place there, nor on uwt_tuning.  A pair with no valid point on a level (a
+ * flat reference frame, every candidate on a zero depth byte) gets its status in its own uwt_stats, as
+ * uwt_estimate_pose_points reports it; the other pairs are unaffected.
  * The tables, their counts and the solver state never leave the device: per level a producer pass (gradient_ and its mean,
  * per-column counts, an exclusive scan, the ordered write), then per level one launch per Gauss-Newton evaluation with the
  * update in its tail, k_level_end between levels.  The caller may reuse the pair lists once the call returns.

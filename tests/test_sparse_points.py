@@ -161,8 +161,8 @@ def test_gpu_point_table_alignment_matches_dense_and_oracle(capi, O, synth):
 @pytest.mark.gpu
 @pytest.mark.parametrize("weights,sampler", [(1, 0), (2, 0), (0, 1), (2, 1)])
 def test_gpu_point_tables_on_the_general_path(capi, O, synth, weights, sampler):
-    """uwt_params::weights / ::sampler apply to explicit tables as to the dense call (k_points_hist, k_scale_stage,
-    k_points_general): candidate tables on three levels and a 20 000-row table of arbitrary rows, poses bit-identical."""
+    """uwt_params::weights / ::sampler apply to explicit tables as to the dense call (k_table_hist, k_table_general, the call a
+    batch of one pair): candidate tables on three levels and a 20 000-row table of arbitrary rows, poses bit-identical."""
     w, h = 160, 96
     over = dict(n_levels=4, first_level=2, last_level=0, max_iters=6, early_exit=0, weights=weights, sampler=sampler)
     ctx, ref, tgt, _ = _ctx_pair(capi, synth, w, h, 65, **over)
@@ -204,6 +204,82 @@ def test_gpu_point_table_rows_outside_the_level_are_dropped(capi, O, synth):
     assert np.array_equal(a, b) and np.array_equal(b, pose_cpu) and sb["n_valid"] == tr[-1]["n_valid"]
     only_out, s_out = ctx.estimate_pose_points(0, 1, {0: outside})
     assert s_out["status"] == capi.ERR_NO_VALID_POINTS and O.align_pair_points(p, ref, tgt, {0: outside})[0] == s_out["status"]
+
+
+def _rows_inside(rng, n, w, h):
+    rows = np.ones((n, 4), np.float32)
+    rows[:, 0] = rng.uniform(0, w - 0.01, n)
+    rows[:, 1] = rng.uniform(0, h - 0.01, n)
+    return rows
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [{}, dict(weights=2), dict(sampler=1)], ids=["identity", "huber", "bilinear"])
+def test_gpu_point_table_slice_boundaries(capi, O, synth, mode):
+    """Row counts around the 1024 rows of a block of k_table_eval / k_table_hist / k_table_general: none, one, a partial block,
+    exactly one block, one row into the next, across 8192, and more slices than the context's own record pool holds (20 000
+    rows, max_pairs = 1).  Status as the oracle's; pose, evaluations and valid rows bit for bit where it succeeds."""
+    w, h = 160, 96
+    over = dict(n_levels=4, first_level=0, last_level=0, max_iters=5, early_exit=0, **mode)
+    ref, tgt, _, _, _ = synth.render_pair(w, h, *MID, seed=67)
+    ctx = capi.Context(capi.default_params(w, h, *MID, max_frames=2, max_pairs=1, **over))
+    ctx.upload_frames(0, np.stack([ref, tgt]))
+    ctx.build_pyramids(0, 2)
+    ctx.apply_gradient(0, 2)
+    p = O.default_params(w, h, *MID, **over)
+    rng = np.random.default_rng(13)
+    for n in (0, 1, 6, 255, 1023, 1024, 1025, 2048, 8192, 8193, 20000):
+        rows = _rows_inside(rng, n, w, h)
+        pose, st = ctx.estimate_pose_points(0, 1, {0: rows})
+        so, pose_cpu, tr = O.align_pair_points(p, ref, tgt, {0: rows}, want_trace=True)
+        assert st["status"] == so, (n, st, so)
+        if so == 0:
+            assert np.array_equal(pose, pose_cpu), (n, pose, pose_cpu)
+            assert st["iterations"] == len(tr) and st["n_valid"] == tr[-1]["n_valid"], (n, st, tr[-1])
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_point_table_call_leaves_shared_state_clean(capi, O, synth):
+    """The histogram rows and the tail tickets are zero again behind a table call: the dense batch that follows it gives what it
+    gives on a context that never ran one."""
+    w, h = 160, 96
+    over = dict(n_levels=4, first_level=2, last_level=0, max_iters=6, early_exit=0, weights=2)
+    frames = []
+    for seed in (68, 69):
+        ref, tgt, _, _, _ = synth.render_pair(w, h, *MID, seed=seed, z=1.1)
+        frames += [ref, tgt]
+    rng = np.random.default_rng(14)
+    tables = {0: _rows_inside(rng, 20000, w, h), 1: _rows_inside(rng, 3000, w // 2, h // 2), 2: _rows_inside(rng, 700, w // 4, h // 4)}
+    results = []
+    for table_call in (True, False):
+        ctx = capi.Context(capi.default_params(w, h, *MID, max_frames=4, max_pairs=2, **over))
+        ctx.upload_frames(0, np.stack(frames))
+        ctx.build_pyramids(0, 4)
+        ctx.apply_gradient(0, 4)
+        if table_call:
+            assert ctx.estimate_pose_points(0, 1, tables)[1]["status"] == 0
+        results.append(ctx.estimate_pose_batch([0, 2], [1, 3], raise_on_pair_failure=True))
+        ctx.close()
+    (poses_a, stats_a), (poses_b, stats_b) = results
+    assert np.array_equal(poses_a, poses_b)
+    assert [dict(s) for s in stats_a] == [dict(s) for s in stats_b]
+
+
+@pytest.mark.gpu
+def test_gpu_point_tables_of_different_sizes_per_level(capi, O, synth):
+    """Two slices, then one, then an empty table, in the iteration order 2 -> 1 -> 0, out of a scratch sized by the largest: the
+    empty level ends the call with the oracle's status."""
+    w, h = 160, 96
+    over = dict(n_levels=4, first_level=2, last_level=0, max_iters=5, early_exit=0)
+    ctx, ref, tgt, _ = _ctx_pair(capi, synth, w, h, 67, **over)
+    p = O.default_params(w, h, *MID, **over)
+    rng = np.random.default_rng(15)
+    tables = {2: _rows_inside(rng, 1500, w // 4, h // 4), 1: _rows_inside(rng, 1024, w // 2, h // 2), 0: np.zeros((0, 4), np.float32)}
+    _, st = ctx.estimate_pose_points(0, 1, tables)
+    so = O.align_pair_points(p, ref, tgt, tables)[0]
+    assert st["status"] == capi.ERR_NO_VALID_POINTS and st["status"] == so
+    ctx.close()
 
 
 @pytest.mark.gpu

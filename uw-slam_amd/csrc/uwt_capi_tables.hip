@@ -1,87 +1,9 @@
-// uwt_capi_tables.hip — host side of libuwt_hip.so: alignment over point tables — the caller's tables, the candidate and patch
-// producers, and the batch calls that build the tables on the device and evaluate them there.
+// uwt_capi_tables.hip — host side of libuwt_hip.so: alignment over point tables — the candidate and patch producers, the batch
+// calls that build the tables on the device and evaluate them there, and the caller's own tables as a batch of one pair.
 #include "uwt_ctx.h"
 #include "uwt_track.h"
 
 extern "C" {
-
-int uwt_estimate_pose_points(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, const float* const* tables,
-                             const int32_t* n_points, float pose_out[7], uwt_stats* stats_out) {
-  if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
-  if (!c || !tables || !n_points || !pose_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_points: null argument");
-  const uwt_params& p = c->p;
-  size_t total = 0;
-  for (int l = p.last_level; l <= p.first_level; l++) {
-    // one partial record per 8192 points; the context owns max_slices x max_pairs records
-    if (n_points[l] < 0 || (size_t)n_points[l] > c->partial_records * (size_t)(kBlock * 32) || (n_points[l] > 0 && !tables[l]))
-      return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_points: bad table (null, negative or too many points)");
-    total += (size_t)n_points[l];
-  }
-  int st = upload_pairs(c, 1, &ref_slot, &tgt_slot);
-  if (st) return st;
-  st = c->scratch.reserve(c, c->stream, std::max<size_t>(16, total * 16));
-  if (st) return st;
-  float4* d_tab[UWT_MAX_LEVELS] = {};
-  size_t off = 0;
-  for (int l = p.last_level; l <= p.first_level; l++) {
-    d_tab[l] = (float4*)c->scratch.p + off;
-    if (n_points[l]) HIPCHK(c, hipMemcpyAsync(d_tab[l], tables[l], (size_t)n_points[l] * 16, hipMemcpyHostToDevice, c->stream));
-    off += (size_t)n_points[l];
-  }
-  const int tb = 64;
-  hipLaunchKernelGGL(k_init_state, dim3(1), dim3(tb), 0, c->stream, c->state, 1, p.initial_error);
-  HIPCHK(c, hipGetLastError());
-  const int per_block = kBlock * 32;
-  for (int lvl = p.first_level; lvl >= p.last_level; lvl--) {
-    ResidualArgs ra = residual_args(c, lvl);
-    PointsArgs pa;
-    pa.pts = d_tab[lvl];
-    pa.n_pts = n_points[lvl];
-    pa.pts_per_block = per_block;
-    ra.slices = std::max(1, (pa.n_pts + per_block - 1) / per_block);
-    UpdateArgs ua = update_args(c, lvl);
-    ua.slices = ra.slices;
-    const bool general = p.sampler || p.weights;   // robust weights / bilinear sampler: the per-stage form over the table
-    if (general) ua.general = 1;
-    const GeneralArgs ga = {p.sampler, p.weights, p.gain, c->hist, c->scale};
-    int next_poll = 2;
-    for (int k = 0; k < p.max_iters; k++) {
-      if (general) {
-        if (p.weights) HIPCHK(c, hipMemsetAsync(c->hist + (size_t)ra.pair_base * kHistBins, 0, sizeof(unsigned int) * kHistBins, c->stream));
-        uwt::launch_points_general(c->stream, launch_sel(c), ra, pa, ga);
-      } else {
-        uwt::launch_points(c->stream, launch_sel(c), ra, pa);
-      }
-      HIPCHK(c, hipGetLastError());
-      ua.k = k;
-      const bool poll = p.early_exit && (k + 1 == next_poll) && (k + 1 < p.max_iters);
-      ua.active = poll ? c->d_active : nullptr;
-      st = poll ? poll_arm(c) : UWT_OK;
-      if (st) return st;
-      hipLaunchKernelGGL(k_gn_update, dim3(1), dim3(kUpdateBlock), 0, c->stream, ua);
-      HIPCHK(c, hipGetLastError());
-      if (poll) {
-        bool left = true;
-        st = poll_any_left(c, &left);
-        if (st) return st;
-        if (!left) break;
-        next_poll *= 2;
-      }
-    }
-    hipLaunchKernelGGL(k_level_end, dim3(1), dim3(tb), 0, c->stream, c->state, 1, lvl, p.handoff_scale_t, p.initial_error);
-    HIPCHK(c, hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_write_out, dim3(1), dim3(tb), 0, c->stream, c->state, 1, c->d_poses, c->d_stats);
-  HIPCHK(c, hipGetLastError());
-  uwt_stats tmp;
-  HIPCHK(c, hipMemcpyAsync(pose_out, c->d_poses, sizeof(float) * 7, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&tmp, c->d_stats, sizeof(tmp), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (stats_out) *stats_out = tmp;
-  if (tmp.status != UWT_OK)
-    return fail(c, UWT_ERR_PAIR_FAILED, std::string("uwt_estimate_pose_points: ") + uwt_status_string(tmp.status));
-  return UWT_OK;
-}
 
 // ---- the sparse point producers: per-stage entries over a slot list in the scratch ------------------------------------
 namespace {
@@ -596,6 +518,55 @@ int uwt_estimate_pose_candidates_batch_opt(uwt_ctx* c, int32_t n_pairs, const in
                                            double threshold, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out) {
   return candidates_sync(c, "uwt_estimate_pose_candidates_batch_opt", n_pairs, ref_slots, tgt_slots, threshold, true, opt, poses_out,
                          stats_out);
+}
+
+// ---- the caller's own tables: a batch of one pair whose tables arrive from the host -----------------------------------------
+int uwt_estimate_pose_points(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, const float* const* tables,
+                             const int32_t* n_points, float pose_out[7], uwt_stats* stats_out) {
+  if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
+  if (!c || !tables || !n_points || !pose_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_points: null argument");
+  const uwt_params& p = c->p;
+  size_t total = 0;
+  int rows = 0;
+  for (int l = p.last_level; l <= p.first_level; l++) {
+    // the bound this entry has always refused beyond, kept so that what it accepts does not move; it limits nothing here (the
+    // records come from the scratch)
+    if (n_points[l] < 0 || (size_t)n_points[l] > c->partial_records * (size_t)(kBlock * 32) || (n_points[l] > 0 && !tables[l]))
+      return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_points: bad table (null, negative or too many points)");
+    total += (size_t)n_points[l];
+    rows = std::max(rows, n_points[l]);
+  }
+  int st = upload_pairs(c, 1, &ref_slot, &tgt_slot);
+  if (st) return st;
+  // scratch: [a count per level | the evaluations' records | the tables]
+  Carve cv(256);
+  const size_t o_cnt = cv.take<int>(UWT_MAX_LEVELS), o_recs = cv.take<uint32_t>((size_t)table_slices(rows) * kRecWords),
+               o_tab = cv.take<float4>(total);
+  st = c->scratch.reserve(c, c->stream, cv.tight());
+  if (st) return st;
+  st = compute_begin_pairs(c, 1, &ref_slot, &tgt_slot);
+  if (st) return st;
+  int* d_cnt = Carve::at<int>(c->scratch.p, o_cnt);
+  float4* d_tab = Carve::at<float4>(c->scratch.p, o_tab);
+  TableLevel lv[UWT_MAX_LEVELS];
+  for (int l = p.last_level; l <= p.first_level; l++) {
+    if (n_points[l]) HIPCHK(c, hipMemcpyAsync(d_tab, tables[l], (size_t)n_points[l] * 16, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(d_cnt + l), n_points[l], 1, c->stream));
+    lv[l] = {{d_tab, d_cnt + l, n_points[l]}, table_slices(n_points[l])};
+    d_tab += n_points[l];
+  }
+  st = enqueue_table_estimate(c, 1, p, lv, Carve::at<uint32_t>(c->scratch.p, o_recs), p.early_exit != 0, {p.weights, p.sampler},
+                              c->d_poses, c->d_stats);
+  if (!st) st = compute_end(c, c->dep_first, c->dep_n);
+  if (st) return st;
+  uwt_stats tmp;
+  HIPCHK(c, hipMemcpyAsync(pose_out, c->d_poses, sizeof(float) * 7, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&tmp, c->d_stats, sizeof(tmp), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (stats_out) *stats_out = tmp;
+  if (tmp.status != UWT_OK)
+    return fail(c, UWT_ERR_PAIR_FAILED, std::string("uwt_estimate_pose_points: ") + uwt_status_string(tmp.status));
+  return UWT_OK;
 }
 
 }  // extern "C"

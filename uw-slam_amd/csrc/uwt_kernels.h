@@ -14,12 +14,13 @@
 //                  one block per pair
 //   k_resid_hist_v (scale pass with the scale stage in its tail) + k_residual<.., WEIGHTS>   robust weights in the alignment loop;
 //                  k_residual<.., SAMPLER = 1>: bilinear sampler; k_residual<.., DUMP = true, ..>: the per-stage dump forms
-//   k_residual_points, k_points_hist + k_scale_stage, k_points_general   explicit point tables (identity / general path)
-//   k_patch_points_batch + k_table_eval   the live call for a batch of pairs: tables built and evaluated on the device, the update in
-//                  the evaluation's tail
+//   k_table_eval   explicit point tables, a batch of pairs per launch, the update in the evaluation's tail; uwt_estimate_pose_points
+//                  stages the caller's tables as a batch of one pair
+//   k_patch_points_batch + k_table_eval   the live call for a batch of pairs: tables built and evaluated on the device
 //   k_grad_mag_slots + k_candidates_slots + k_scan_counts, then k_table_eval per level   semi-dense tracking for a batch of pairs
 //                  (the producers of these two calls also serve the per-stage entries, over a slot list of their own)
-//   k_table_hist + k_table_general   the same two calls under uwt_table_options (robust weights / bilinear sampler): the scale pass
+//   k_table_hist + k_table_general   the same calls under robust weights / the bilinear sampler (uwt_table_options; for the
+//                  caller's tables uwt_params::weights, ::sampler): the scale pass
 //                  with the scale in its tail, then the weighted pass with the update in its tail
 //   k_ls_sequential   the LS mirror (src/LeastSquares.cpp): every accumulator's f32 chain in the reference's order
 //   k_add_patch_points, k_remap_crop, k_trajectory*   the rows next to the path
@@ -2025,8 +2026,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 
 // ------------------------------------------------------------------------------------------------------------
 // General residual path: robust weights (src/Tracker.cpp:495-496, 1571-1654) and the bilinear sampler extension.
-// The scale from a pair's signed residual histogram (wave_scale): in the tail of the dense scale pass (k_resid_hist_v, below),
-// or as a launch of its own behind the point tables' scale pass (k_scale_stage).
+// The scale from a pair's signed residual histogram (wave_scale): in the tail of the scale pass (hist_flush_scale, below), dense
+// (k_resid_hist_v) or over point tables (k_table_hist).
 // ------------------------------------------------------------------------------------------------------------
 struct GeneralArgs {
   int sampler;            // 0 nearest, 1 bilinear
@@ -2041,7 +2042,7 @@ struct GeneralArgs {
 //   (float)(n / 2)); the reference Tukey saturates negatives to 0 first (:1572-1573), Huber keeps the sign;
 //   the deviation histogram |q - med| follows from the same bins (clamped at 255 like the u8 conversion of
 //   MedianAbsoluteDeviation's input, :1613, or at 510 for Huber); MAD = 1.4826 * its median (:1607-1619), 0 => 1 (:1634-1637).
-// One wave per pair (four pairs per block).  Both medians are "the first bin whose cumulative count exceeds (float)(n / 2)"
+// One wave per pair.  Both medians are "the first bin whose cumulative count exceeds (float)(n / 2)"
 // of a histogram that is a function of the pair's 511 signed bins, so each is one pass: every lane owns 8 consecutive bins,
 // the lane totals are scanned across the wave, and the lane that holds the crossing reports the smallest index.
 __device__ __forceinline__ int first_crossing(const unsigned int v[8], float m, int lane) {
@@ -2131,25 +2132,6 @@ __device__ __forceinline__ PairScale wave_scale(const unsigned int mine[8], unsi
   if (!n || mad == 0.f) mad = 1.f;
   sc.inv_mad = (float)(1.0 / (double)mad);
   return sc;
-}
-
-static __global__ __launch_bounds__(256) void k_scale_stage(const GeneralArgs ga, const PairState* state, int n_pairs, int pair_base) {
-  __shared__ unsigned int sh[4][kHistBins];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + wave;
-  if (i >= n_pairs) return;
-  const int pair = i + pair_base;
-  const PairState st = state[pair];
-  if (st.level_done || st.status) return;
-  const unsigned int* gh = ga.hist + (size_t)pair * kHistBins;
-  unsigned int mine[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const int b = lane * 8 + k;
-    mine[k] = b < 511 ? gh[b] : 0u;
-  }
-  const PairScale sc = wave_scale(mine, sh[wave], ga.weights == kWeightsTukeyRef, lane);
-  if (lane == 0) ga.scale[pair] = sc;
 }
 
 // Vector form used by the alignment loop: same group walk as residual_block (VEC pixels per step), and kHistRep
@@ -3074,12 +3056,6 @@ __global__ __launch_bounds__(128) void k_ls_sequential(const float* __restrict__
 // iterate over when a sparse producer filled them (src/Tracker.cpp:401, 669).  Same per-point terms and the same
 // deterministic reduction as the dense kernel; reference values are gathered at ((int)y1, (int)x1) (:471-477).
 // ------------------------------------------------------------------------------------------------------------
-struct PointsArgs {
-  const float4* pts;        // table of this launch's single pair
-  int n_pts;
-  int pts_per_block;
-};
-
 // One row of a table: WarpFunction with the table's own w (src/Tracker.cpp:1439-1467) and the validity tests; i1x: the index
 // of the reference value, iz clamped at 0 (:452-453).  False: the row is not valid (x2, y2, iz, i1x are then of no use).
 template <int AR>
@@ -3108,48 +3084,7 @@ __device__ __forceinline__ int table_gather_index(const LevelK& L, float x2, flo
   return iy2 * L.pitch + ix2;
 }
 
-template <int AR, bool UNIT_FACTORS, typename AccT>
-__global__ __launch_bounds__(kBlock) void k_residual_points(const ResidualArgs a, const PointsArgs pa) {
-  const int pair = a.pair_base;
-  Pose pose;
-  if (a.state) {
-    const PairState st = a.state[pair];
-    if (st.level_done || st.status) return;
-    pose = st.pose;
-  } else {
-    pose = a.pose;
-  }
-  WarpK K;
-  pose_to_T12(pose, K.T);
-  const LevelK L = a.L;
-  const size_t ref_off = (size_t)a.ref_slots[pair] * L.n, tgt_off = (size_t)a.tgt_slots[pair] * L.n;
-  const uint8_t* __restrict__ I1 = a.img + ref_off;
-  const uint8_t* __restrict__ I2 = a.img + tgt_off;
-  const int16_t* __restrict__ GX = a.gx + ref_off;
-  const int16_t* __restrict__ GY = a.gy + ref_off;
-  AccT acc[kAccFloats];
-#pragma unroll
-  for (int i = 0; i < kAccFloats; i++) acc[i] = (AccT)0;
-  uint32_t sum_r2 = 0, n_valid = 0;
-  const int p_begin = blockIdx.x * pa.pts_per_block;
-  const int p_end = min(p_begin + pa.pts_per_block, pa.n_pts);
-  for (int q = p_begin + (int)threadIdx.x; q < p_end; q += kBlock) {
-    float x2, y2, iz;
-    uint32_t i1x;
-    if (!table_row<AR>(L, K.T, pa.pts[q], x2, y2, iz, i1x)) continue;
-    const int ri = (int)I2[table_gather_index(L, x2, y2)] - (int)I1[i1x];
-    float J[6];
-    pixel_jacobian<AR, UNIT_FACTORS>(L, a.zf, a.af, x2, y2, iz, (float)GX[i1x], (float)GY[i1x], J);
-    accumulate(acc, J, ri);
-    sum_r2 += (uint32_t)(ri * ri);
-    n_valid += 1;
-  }
-  block_reduce_store<AccT>(acc, sum_r2, n_valid, a.partials + ((size_t)pair * a.slices + blockIdx.x) * kRecWords);
-}
-
-// The same tables on the general path (robust weights and / or the bilinear sampler: uwt_params::weights, ::sampler): the
-// per-stage form of the dense path — k_points_hist, k_scale_stage, k_points_general per evaluation — over table rows.
-// One row: table_row, then the residual of either sampler.
+// One row on the general path (robust weights and / or the bilinear sampler): table_row, then the residual of either sampler.
 template <int AR>
 __device__ __forceinline__ bool general_point(const LevelK& L, const float* T, int sampler, const uint8_t* __restrict__ I1,
                                               const uint8_t* __restrict__ I2, const float4 P, float& x2, float& y2, float& iz, float& rf,
@@ -3162,88 +3097,14 @@ __device__ __forceinline__ bool general_point(const LevelK& L, const float* T, i
   return true;
 }
 
-// the scale pass: every valid row's rounded residual into the pair's signed bins
-template <int AR>
-__global__ __launch_bounds__(kBlock) void k_points_hist(const ResidualArgs a, const PointsArgs pa, const GeneralArgs ga) {
-  const int pair = a.pair_base;
-  const PairState st = a.state[pair];
-  if (st.level_done || st.status) return;
-  __shared__ unsigned int h[kHistBins];
-  for (int i = threadIdx.x; i < kHistBins; i += kBlock) h[i] = 0;
-  __syncthreads();
-  float T[12];
-  pose_to_T12(st.pose, T);
-  const LevelK L = a.L;
-  const uint8_t* __restrict__ I1 = a.img + (size_t)a.ref_slots[pair] * L.n;
-  const uint8_t* __restrict__ I2 = a.img + (size_t)a.tgt_slots[pair] * L.n;
-  const int p_begin = blockIdx.x * pa.pts_per_block, p_end = min(p_begin + pa.pts_per_block, pa.n_pts);
-  for (int q = p_begin + (int)threadIdx.x; q < p_end; q += kBlock) {
-    float x2, y2, iz, rf;
-    uint32_t i1x;
-    if (!general_point<AR>(L, T, ga.sampler, I1, I2, pa.pts[q], x2, y2, iz, rf, i1x)) continue;
-    atomicAdd(&h[(int)rintf(rf) + 255], 1u);
-  }
-  __syncthreads();
-  unsigned int* gh = ga.hist + (size_t)pair * kHistBins;
-  for (int i = threadIdx.x; i < kHistBins; i += kBlock)
-    if (h[i]) atomicAdd(&gh[i], h[i]);
-}
-
-// the weighted / bilinear accumulation over a table (records of the `general` kind)
-template <int AR, bool UNIT_FACTORS>
-__global__ __launch_bounds__(kBlock) void k_points_general(const ResidualArgs a, const PointsArgs pa, const GeneralArgs ga) {
-  const int pair = a.pair_base;
-  const PairState st = a.state[pair];
-  if (st.level_done || st.status) return;
-  float T[12];
-  pose_to_T12(st.pose, T);
-  const LevelK L = a.L;
-  const size_t ref_off = (size_t)a.ref_slots[pair] * L.n;
-  const uint8_t* __restrict__ I1 = a.img + ref_off;
-  const uint8_t* __restrict__ I2 = a.img + (size_t)a.tgt_slots[pair] * L.n;
-  const int16_t* __restrict__ GX = a.gx + ref_off;
-  const int16_t* __restrict__ GY = a.gy + ref_off;
-  const float inv_mad = ga.weights ? ga.scale[pair].inv_mad : 1.f;
-  double acc[kAccFloats];
-#pragma unroll
-  for (int i = 0; i < kAccFloats; i++) acc[i] = 0.0;
-  double err = 0.0;
-  uint32_t sum_r2 = 0, n_valid = 0;
-  const int p_begin = blockIdx.x * pa.pts_per_block, p_end = min(p_begin + pa.pts_per_block, pa.n_pts);
-  for (int q = p_begin + (int)threadIdx.x; q < p_end; q += kBlock) {
-    float x2, y2, iz, rf;
-    uint32_t i1x;
-    if (!general_point<AR>(L, T, ga.sampler, I1, I2, pa.pts[q], x2, y2, iz, rf, i1x)) continue;
-    float J[6];
-    pixel_jacobian<AR, UNIT_FACTORS, false, true>(L, a.zf, a.af, x2, y2, iz, (float)GX[i1x], (float)GY[i1x], J);
-    const float w = robust_weight(ga.weights, rf, inv_mad);
-    err += (double)rf * (double)(rf * w);         // Residuals.mul(W) for the error (src/Tracker.cpp:500)
-    const float rw = (rf * ga.gain) * w;           // :559, :561
-    double Jd[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) Jd[k] = (double)(w * J[k]);   // :556
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-      for (int j = i; j < 6; j++, s++) acc[s] = __builtin_fma(Jd[i], Jd[j], acc[s]);
-#pragma unroll
-    for (int i = 0; i < 6; i++) acc[21 + i] = __builtin_fma(Jd[i], (double)rw, acc[21 + i]);
-    const int qr = (int)rintf(rf);
-    sum_r2 += (uint32_t)(qr * qr);
-    n_valid += 1;
-  }
-  block_reduce_store<double, true>(acc, sum_r2, n_valid, a.partials + ((size_t)pair * a.slices + blockIdx.x) * kRecWords, err);
-}
-
 // k_table_eval: one launch = one Gauss-Newton evaluation of device-resident tables for a batch of pairs, the update in the
 // launch's tail (the live call, uwt_track_features_batch_async).  grid = (slices, pairs): a.slices is the batch's bound (and the
 // pairs' record stride), pair p's own slice count S_p = max(1, ceil(count_p / kFeatPtsPerBlock)) comes from its producer's count
 // on the device.  Blocks beyond S_p and blocks of a pair that has left the level return at once, without a ticket; the pair's
 // last block folds exactly S_p records (tail_fold_wave) and solves.  The slicing therefore depends on kFeatPtsPerBlock and the
 // pair's own count only, never on the batch it runs in: a pair's pose is the same bits alone or in any batch.
-// Per row: table_row, the nearest sample at table_gather_index and pixel_jacobian — k_residual_points' terms; f64 sums under an
-// EXEC mask of the valid lanes (masked_sums_*), the record through block_reduce_store(.., coherent).
+// Per row: table_row, the nearest sample at table_gather_index and pixel_jacobian; f64 sums under an EXEC mask of the valid
+// lanes (masked_sums_*), the record through block_reduce_store(.., coherent).
 constexpr int kPatchMaxKeypoints = 200;   // min(num_max_keypoints, 200), src/Tracker.cpp:1192
 constexpr int kPatchMaxRows = 144;        // table rows one key point can add at most (11 x 11 cells, 12 x 12 bound for the float loop)
 struct TableArgs {
@@ -3319,11 +3180,10 @@ __global__ __launch_bounds__(kBlock) void k_table_eval(const ResidualArgs a, con
 
 // The batched tables on the general path (uwt_table_options: robust weights and / or the bilinear sampler), k_table_eval's grid,
 // slicing and early returns.  Per evaluation with weights: k_table_hist, then k_table_general; without: k_table_general alone.
-// Per row the terms of k_points_hist / k_points_general, so a pair's pose is what uwt_estimate_pose_points gives under
-// uwt_params::weights / ::sampler; the sums are f64 whatever accumulate_f64 says, as there.
+// Per row general_point, pixel_jacobian and robust_weight; the sums are f64 whatever accumulate_f64 says.
 //
-// k_table_hist — the scale pass: a block counts rint(rf) of its up to kFeatPtsPerBlock rows in one 512-word LDS histogram
-// (k_points_hist's), then hist_flush_scale with the pair's own slice count: the pair's last block leaves the scale in
+// k_table_hist — the scale pass: a block counts rint(rf) of its up to kFeatPtsPerBlock rows in one 512-word LDS histogram,
+// then hist_flush_scale with the pair's own slice count: the pair's last block leaves the scale in
 // ga.scale[pair] and the pair's row of ga.hist all-zero again.  No clearing per evaluation, no launch for the scale.
 template <int AR>
 __global__ __launch_bounds__(kBlock) void k_table_hist(const ResidualArgs a, const TableArgs ta, const GeneralArgs ga) {

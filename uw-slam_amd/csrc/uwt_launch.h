@@ -27,10 +27,6 @@ void launch_residual(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a,
 // form)
 void launch_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, int n_pairs, int sampler, int weights,
                     unsigned int* hist, PairScale* scale, bool dump);
-// explicit point tables (k_residual_points)
-void launch_points(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const PointsArgs& pa);
-// the same on the general path: k_points_hist + k_scale_stage (weights != 0; the caller cleared the pair's bins), k_points_general
-void launch_points_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const PointsArgs& pa, const GeneralArgs& ga);
 
 // The sparse point producers and device-resident tables (uwt_launch_points.hip); the only launches of the producers, for the
 // batched calls and the per-stage entries alike.  Frame f of a producer is slot slots[f] (a device list).

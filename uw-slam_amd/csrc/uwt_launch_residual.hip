@@ -1,5 +1,5 @@
-// uwt_launch_residual.hip — dispatch of k_residual on the identity-weights / nearest-sampler path (the dominant kernel), its
-// per-stage dump form, and k_residual_points.
+// uwt_launch_residual.hip — dispatch of k_residual on the identity-weights / nearest-sampler path (the dominant kernel) and its
+// per-stage dump form.
 #include "uwt_launch.h"
 
 namespace uwt {
@@ -91,16 +91,6 @@ void launch_residual(hipStream_t s, const LaunchSel& sel, const ResidualArgs& ar
   UWT_WITH_AR(sel.arith,
     if (sel.depth) launch_residual_vd<AR, true>(s, a, n_pairs, unit, dump, sel.acc64, co);
     else launch_residual_vd<AR, false>(s, a, n_pairs, unit, dump, sel.acc64, co));
-}
-
-void launch_points(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const PointsArgs& pa) {
-  const bool unit = (a.zf == 1.0f && a.af == 1.0f);
-  const dim3 grid(a.slices), blk(kBlock);
-  UWT_WITH_AR(sel.arith,
-    if (unit && sel.acc64) hipLaunchKernelGGL((k_residual_points<AR, true, double>), grid, blk, 0, s, a, pa);
-    else if (unit) hipLaunchKernelGGL((k_residual_points<AR, true, float>), grid, blk, 0, s, a, pa);
-    else if (sel.acc64) hipLaunchKernelGGL((k_residual_points<AR, false, double>), grid, blk, 0, s, a, pa);
-    else hipLaunchKernelGGL((k_residual_points<AR, false, float>), grid, blk, 0, s, a, pa));
 }
 
 }  // namespace uwt
