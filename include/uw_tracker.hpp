@@ -23,6 +23,7 @@
 #include <array>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -279,6 +280,65 @@ class Tracker {
   void GetFrameLevel(Frame* _frame, int _lvl, int _plane, void* _host_out) {
     check(uwt_get_plane(ctx(), bind(_frame), _lvl, _plane, _host_out), "uwt_get_plane");
   }
+  // include/Tracker.h:188 (src/Tracker.cpp:1473-1525): _outputImage[round(warped)] = _originalImage[(int)point] for every row in
+  // order, the last row on a pixel winning; _outputImage (tight rows of the level's image) is written in place — pixels no row lands
+  // on keep their content — and validPixel returned.  _originalImage is the plane of a bound frame: (frame, level), or a view of
+  // level-0 pixels — those of a bound frame (by address), else uploaded as a frame of the tracker's own, which takes the
+  // least-recently-used slot.  (Levels 1.. exist on the device only: name them by frame and level.)
+  std::vector<uint8_t> ObtainImageTransformed(Frame* _originalFrame, int _lvl, const std::vector<float>& _candidatePoints,
+                                              const std::vector<float>& _warpedPoints, std::vector<uint8_t>& _outputImage) {
+    const int slot = bind(_originalFrame);
+    const uwt_level L = level(_lvl);
+    if (_candidatePoints.size() != _warpedPoints.size() || _outputImage.size() != (size_t)L.img_w * L.img_h)
+      throw std::runtime_error("ObtainImageTransformed: the tables differ in size, or the output is not the level's image");
+    std::vector<uint8_t> validPixel(_outputImage.size());
+    check(uwt_obtain_image_transformed(ctx(), slot, _lvl, _candidatePoints.data(), _warpedPoints.data(), (int32_t)(_warpedPoints.size() / 4),
+                                       _outputImage.data(), validPixel.data()), "uwt_obtain_image_transformed");
+    return validPixel;
+  }
+  std::vector<uint8_t> ObtainImageTransformed(const ImageView& _originalImage, const std::vector<float>& _candidatePoints,
+                                              const std::vector<float>& _warpedPoints, std::vector<uint8_t>& _outputImage) {
+    return ObtainImageTransformed(frame_of(_originalImage), 0, _candidatePoints, _warpedPoints, _outputImage);
+  }
+  // include/Tracker.h:257 (src/Tracker.cpp:1694-1737): [image1 | image2] over [blend(warped, image2) | blend(image1, image2)], 2 img_w
+  // x 2 img_h u8, returned instead of shown (imshow / waitKey and the window's resize loop are the caller's).  _image1 / _image2: the
+  // planes of two bound frames at _lvl; _imageWarped: tight rows of that level's image.
+  std::vector<uint8_t> DebugShowWarpedPerspective(Frame* _image1, Frame* _image2, const std::vector<uint8_t>& _imageWarped, int _lvl) {
+    const int32_t a = bind(_image1), b = bind(_image2);
+    const uwt_level L = level(_lvl);
+    if (!bound(_image1) || _imageWarped.size() != (size_t)L.img_w * L.img_h)
+      throw std::runtime_error("DebugShowWarpedPerspective: more frames than slots, or the warped image is not the level's image");
+    std::vector<uint8_t> mosaic(4 * _imageWarped.size());
+    check(uwt_warp_mosaic(ctx(), a, b, _lvl, _imageWarped.data(), mosaic.data()), "uwt_warp_mosaic");
+    return mosaic;
+  }
+  // ObtainAllPoints -> WarpFunction -> ObtainImageTransformed for a list of (previous, current) pairs under `poses` in one call
+  // (uwt_warp_image_batch): warped and valid are pairs x img_w x img_h u8, quality one record per pair.
+  struct WarpedImages {
+    std::vector<uint8_t> warped, valid;
+    std::vector<uwt_warp_quality> quality;
+  };
+  WarpedImages WarpedImageBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, const std::vector<SE3>& _poses, int _lvl = 0) {
+    const size_t n = _pairs.size();
+    if (_poses.size() != n) throw std::runtime_error("WarpedImageBatch: one pose per pair");
+    std::vector<int32_t> a(n), b(n);
+    for (size_t i = 0; i < n; i++) {
+      a[i] = bind(_pairs[i].first);
+      b[i] = bind(_pairs[i].second);
+    }
+    for (size_t i = 0; i < n; i++)   // binding a later pair's frame may have taken an earlier frame's slot
+      if (!bound(_pairs[i].first) || !bound(_pairs[i].second) || _pairs[i].first->slot_ != a[i] || _pairs[i].second->slot_ != b[i])
+        throw std::runtime_error("WarpedImageBatch: more frames than slots (max_frames)");
+    const uwt_level L = level(_lvl);
+    WarpedImages r;
+    r.warped.resize(n * (size_t)L.img_w * L.img_h);
+    r.valid.resize(r.warped.size());
+    r.quality.resize(n);
+    const int st = uwt_warp_image_batch(ctx(), (int32_t)n, a.data(), b.data(), _lvl, n ? _poses[0].data() : nullptr, r.warped.data(),
+                                        r.valid.data(), nullptr, r.quality.data());
+    if (st != UWT_ERR_PAIR_FAILED) check(st, "uwt_warp_image_batch");   // a failed pair has its status in its record
+    return r;
+  }
   // include/Tracker.h:145 — gradient_ > mean + GRADIENT_THRESHOLD (src/Options.cpp:27) on every level, x-major order
   void ObtainCandidatePoints(Frame* _frame, double gradient_threshold = 20.0) {
     const int slot = bind(_frame);
@@ -520,6 +580,17 @@ class Tracker {
     check(uwt_build_pyramids(ctx(), slot, 1), "uwt_build_pyramids");
     return slot;
   }
+  // the bound frame whose level-0 pixels a view shows (by address); else the view's pixels as a frame of the tracker's own
+  Frame* frame_of(const ImageView& v) {
+    for (Frame* f : owner_)
+      if (f && bound(f) && f->images_[0].data == v.data) return f;
+    if (!v.data || v.cols != params_.width || v.rows != params_.height)
+      throw std::runtime_error("ObtainImageTransformed: the view is neither a bound frame's level 0 nor an image of level 0's size");
+    scratch_frame_.reset(new Frame());
+    scratch_frame_->images_[0] = v;
+    return scratch_frame_.get();
+  }
+  std::unique_ptr<Frame> scratch_frame_;
   bool depth_available_;
   int patch_size_ = 5;                 // src/Tracker.cpp:274
   int max_frames_, device_;

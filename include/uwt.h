@@ -984,6 +984,75 @@ int uwt_match_descriptors_device_async(uwt_ctx* ctx, int32_t n_pairs, int32_t no
                                        const int32_t* d_n_query, const void* d_train, const int32_t* d_n_train, int32_t cap, float ratio,
                                        uwt_match* d_matches_out, int32_t* d_counts_out);
 
+/* ---- did the alignment work: Tracker::ObtainImageTransformed and DebugShowWarpedPerspective ---------------------------------- */
+
+/* Tracker::ObtainImageTransformed(original, candidatePoints N x 4, warpedPoints N x 4, output) (src/Tracker.cpp:1473-1525; live code
+ * inside FastEstimatePose, :930) carries a frame into another frame's view and returns the mask of the pixels it covered.  The contract:
+ * for rows i = 0..N-1 IN ORDER, x1 = (int)pts[i][0], y1 = (int)pts[i][1] (truncation toward zero), x2 = (int)round(warped[i][0]),
+ * y2 = (int)round(warped[i][1]) (C round: halves away from zero).
+ *   - A row LANDS iff y2 > 0 && y2 < rows && x2 > 0 && x2 < cols (:1483, the reference's own test: row 0 and column 0 are never
+ *     written).  rows x cols: the level's image, img_h x img_w.
+ *   - On landing output[y2, x2] = original[y1, x1] and valid[y2, x2] = 1.
+ *   - Pixels no row lands on keep what `output` held; their valid is 0.
+ *   - Ordering rule: among the rows that land on one pixel the one with the largest i wins (the reference is a sequential scatter).
+ * The device form is two passes over an int32 winner plane per pair that starts at -1: every landed row does atomicMax(winner[y2, x2], i),
+ * then one pass reads original[y1, x1] of each pixel's winner.  An integer maximum does not depend on the order of its operands, so the
+ * result is the same bits on every run and depends neither on the batch, nor on the pair's place in it, nor on uwt_tuning, nor on
+ * scheduling.
+ * Deviations (in the style of SURVEY C-3):
+ *   - A row whose (x1, y1) lies outside the level's image (or is not a number) is skipped: the reference would read out of bounds there.
+ *   - A row whose warped u or v is not finite, or has magnitude >= 2^31 - 128, is skipped: the conversion to int is undefined there.
+ * Tracker::DebugShowWarpedPerspective(image1, image2, imageWarped, lvl) (src/Tracker.cpp:1694-1737) builds the four-panel image
+ *   [ image1 | image2 ] over [ blend(imageWarped, image2) | blend(image1, image2) ],  2 img_w x 2 img_h u8,
+ * blend(a, b) = addWeighted(a, 0.5, b, 0.5, 1.0) = saturate_u8(cvRound(0.5 a + 0.5 b + 1)), cvRound to the even neighbour of a half: with
+ * s = a + b, s / 2 + 1 for an even s, the even one of (s - 1) / 2 + 1 and (s - 1) / 2 + 2 for an odd s, capped at 255.  The reference's
+ * "resize x2 while _lvl > 1" (:1729-1732) scales the window for the display and is not built; imshow / waitKey are the caller's. */
+typedef struct uwt_warp_quality {   /* per pair, 48 bytes, all integers: exact and order-independent */
+  int32_t status;          /* uwt_status_code of this pair */
+  int32_t n_points;        /* rows considered (dense: w*h of the level's grid) */
+  int32_t n_landed;        /* rows that passed the landing test */
+  int32_t n_covered;       /* pixels with valid = 1 (<= n_landed; the difference is the rows that lost) */
+  int64_t sum_abs;         /* over covered pixels: |warped - image2| */
+  int64_t sum_sq;          /* over covered pixels: (warped - image2)^2 */
+  int64_t sum_abs_unaligned; /* over the SAME covered pixels: |image1 - image2| (the "noalign" panel's content) */
+  int64_t reserved;
+} uwt_warp_quality;
+
+typedef struct uwt_warp_image_io {   /* every pointer is DEVICE memory, 4-byte aligned; planes are n_pairs x pitch x img_h u8 */
+  uint8_t*          d_warped;        /* out, may be null: image1 in image2's view; 0 where no row landed */
+  uint8_t*          d_valid;         /* out, may be null: 1 where a row landed */
+  uint8_t*          d_absdiff;       /* out, may be null: |warped - image2| where a row landed, else 0 */
+  uwt_warp_quality* d_quality;       /* out, required: n_pairs records */
+} uwt_warp_image_io;
+
+/* The reference's signature on host arrays for one frame: original = the image plane of `slot` at `lvl` (resident, pyramids built),
+ * pts / warped: n x 4 floats, image_inout / valid_out: img_w x img_h u8, tight.  image_inout is honoured as input (pixels not landed on
+ * keep its content).  n = 0 is UWT_OK: the image is untouched and the mask all zero.  Synchronous. */
+int uwt_obtain_image_transformed(uwt_ctx* ctx, int32_t slot, int32_t lvl, const float* pts, const float* warped, int32_t n,
+                                 uint8_t* image_inout, uint8_t* valid_out);
+/* The dense form for a batch of pairs, ObtainAllPoints -> WarpFunction -> ObtainImageTransformed in one call: the rows are the level's
+ * w x h point grid in ObtainAllPoints' order (i = y * w + x; z = depth * depth_scale / 2^lvl of the reference slot's depth plane, a point
+ * whose depth read as int16 is <= 0 becomes [0 0 1 0], z = 1 without a depth plane; src/Tracker.cpp:1266-1302), warped by uwt_warp's
+ * arithmetic under the pair's pose d_poses[p] (n_pairs x 7, DEVICE memory: uwt_tracking_io::d_poses and the pose buffers of the _async
+ * table calls are valid inputs with no uwt_sync between the calls, the stream orders them); original = ref_slots[p]'s image plane at lvl,
+ * image2 = tgt_slots[p]'s.  Pixels no row lands on are 0 in d_warped and d_absdiff.  Every output of a pair is bit for bit what
+ * uwt_obtain_image_transformed gives on that table and uwt_warp's rows.
+ * 1 <= n_pairs <= max_pairs; the frames must be resident with pyramids built (gradients are not needed).  Enqueued on the context's
+ * stream, ordered against uwt_upload_frames_async as the other batch calls are; uwt_sync() to wait.
+ * UWT_ERR_INVALID_ARG with nothing enqueued and the outputs untouched: a null list, a null d_poses, io or d_quality, n_pairs outside
+ * 1..max_pairs, a slot or level out of range.  A pose with a non-finite entry puts UWT_ERR_INVALID_ARG into that pair's status with all
+ * counts 0 and its planes zero; its neighbours are untouched. */
+int uwt_warp_image_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, int32_t lvl,
+                               const float* d_poses, const uwt_warp_image_io* io);
+/* The same, synchronous, HOST in and out: poses n_pairs x 7; warped_out / valid_out / absdiff_out n_pairs x img_w x img_h u8, tight,
+ * each may be null; quality_out n_pairs, required.  UWT_ERR_PAIR_FAILED when a pair failed, its status in its record. */
+int uwt_warp_image_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, int32_t lvl,
+                         const float* poses, uint8_t* warped_out, uint8_t* valid_out, uint8_t* absdiff_out,
+                         uwt_warp_quality* quality_out);
+/* The image of DebugShowWarpedPerspective for one pair: image1 = ref_slot's image plane at lvl, image2 = tgt_slot's, warped: img_w x
+ * img_h u8 (host), mosaic_out: 2 img_w x 2 img_h u8 (host).  Synchronous. */
+int uwt_warp_mosaic(uwt_ctx* ctx, int32_t ref_slot, int32_t tgt_slot, int32_t lvl, const uint8_t* warped, uint8_t* mosaic_out);
+
 /* ---- next to the path: frame ingest---------------------------------------------------------------- */
 
 typedef struct uwt_ingest uwt_ingest;

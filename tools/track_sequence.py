@@ -46,10 +46,33 @@ def track_live(w, h, intr, frames, depths, arith=0, detector=0):
     return np.array(poses, np.float32).reshape(-1, 7), stats, kept
 
 
-def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0):
+def quality_columns(records, w, h):
+    """The three per-pair columns of --quality from uwt_warp_quality records at level 0: the share of the frame the previous frame
+    covers after alignment, and the mean |difference| to the current frame over those pixels with and without the alignment"""
+    cov = np.maximum(records["n_covered"].astype(np.float64), 1.0)
+    return dict(coverage=[float(v) for v in records["n_covered"] / float(w * h)], mean_abs=[float(v) for v in records["sum_abs"] / cov],
+                mean_abs_unaligned=[float(v) for v in records["sum_abs_unaligned"] / cov])
+
+
+def sequence_quality(w, h, intr, frames, depths, poses, arith=0):
+    """uwt_warp_quality of every consecutive pair under its pose at level 0 (uwt_warp_image_batch), for the modes whose poses are on
+    the host"""
+    capi = importlib.import_module("uw-slam_amd.capi")
+    ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=2, max_pairs=1, has_depth=int(bool(depths)), arith=arith))
+    out = np.zeros(len(poses), capi.WARP_QUALITY)
+    for k in range(len(poses)):
+        ctx.upload_frames(0, np.stack(frames[k:k + 2]), np.stack(depths[k:k + 2]) if depths else None)
+        ctx.build_pyramids(0, 2)
+        out[k] = ctx.warp_image_batch([0], [1], poses[k:k + 1], lvl=0, absdiff=False)["quality"][0]
+    ctx.close()
+    return out
+
+
+def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0, quality=False):
     """The same loop as successive one-pair uwt_tracking_batch_async calls (detector 1: uwt_tracking_orb_batch_async): what a frame kept
     goes to the next call in device memory (two sets of buffers, taken in turn), nothing is read back between the calls and the host
-    waits once, at the end.  Same returns."""
+    waits once, at the end.  Same returns; quality: behind every call uwt_warp_image_batch_async on its device pose, inside the same
+    single wait — the records come back as a fourth result."""
     import torch
     capi = importlib.import_module("uw-slam_amd.capi")
     n = len(frames)
@@ -60,6 +83,7 @@ def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0
     poses, stats, info = torch.zeros((n - 1, 7), **i32), torch.zeros((n - 1, 4), **i32), torch.zeros((n - 1, 8), **i32)
     sets = [dict(good=torch.zeros((cap, 3), **i32), kept_prev=torch.zeros((cap, 8), **i32), kept_cur=torch.zeros((cap, 8), **i32),
                  n_matches=torch.zeros((1,), **i32)) for _ in range(2)]
+    records = torch.zeros((n - 1, 48), dtype=torch.uint8, device="cuda") if quality else None
     torch.cuda.synchronize()   # torch's fills run on torch's stream
 
     def load(i):
@@ -75,13 +99,17 @@ def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0
         if k:
             io.update(prev_kp=sets[(k - 1) % 2]["kept_cur"].data_ptr(), n_prev=sets[(k - 1) % 2]["n_matches"].data_ptr())
         enqueue([k % 4], [(k + 1) % 4], io, cap=cap)
+        if quality:
+            ctx.warp_image_batch_async([k % 4], [(k + 1) % 4], poses[k].data_ptr(), dict(quality=records[k].data_ptr()), lvl=0)
     ctx.sync()
     st = stats.cpu().numpy().view(capi.STATS).reshape(-1)
     kept = info.cpu().numpy().view(capi.TRACKING_INFO).reshape(-1)["n_matches"]
     out = poses.cpu().numpy().view(np.float32).reshape(-1, 7).copy()
+    rec = records.cpu().numpy().reshape(-1).view(capi.WARP_QUALITY) if quality else None
     ctx.close()
-    return out, [dict(status=int(s["status"]), iterations=int(s["iterations"]), n_valid=int(s["n_valid"]), error=float(s["error"])) for s in st], \
-        [int(v) for v in kept]
+    res = (out, [dict(status=int(s["status"]), iterations=int(s["iterations"]), n_valid=int(s["n_valid"]), error=float(s["error"])) for s in st],
+           [int(v) for v in kept])
+    return res + (rec,) if quality else res
 
 
 def main():
@@ -107,6 +135,9 @@ def main():
     ap.add_argument("--chained", action="store_true", help="with --live: the loop as successive device-resident calls (uwt_tracking_batch_async, "
                     "uwt_tracking_orb_batch_async with --detector orb) that hand their key points on in device memory, one wait at the end; "
                     "the same trajectory")
+    ap.add_argument("--quality", action="store_true", help="per pair, at level 0: the share of the frame the previous frame covers "
+                    "under the estimated pose and the mean |difference| over it with and without the alignment "
+                    "(Tracker::ObtainImageTransformed on the device; with --chained from the device poses, inside the same single wait)")
     ap.add_argument("--out", default="trajectory")
     a = ap.parse_args()
     S = importlib.import_module("uw-slam_amd.sequence")
@@ -141,11 +172,17 @@ def main():
     t0 = time.perf_counter()
     if a.detector == "orb" and not a.live:
         ap.error("--detector orb goes with --live")
-    if a.live:
+    records = None
+    if a.live and a.chained and a.quality:
+        poses, stats, n_matches, records = track_live_chained(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
+                                                              detector=int(a.detector == "orb"), quality=True)
+    elif a.live:
         poses, stats, n_matches = (track_live_chained if a.chained else track_live)(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths,
                                                                                     over["arith"], detector=int(a.detector == "orb"))
     else:
         poses, stats = trk.track(frames, depths)
+    if a.quality and records is None:
+        records = sequence_quality(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, np.asarray(poses, np.float32), over["arith"])
     dt = time.perf_counter() - t0
     traj = trk.trajectory(poses)
     ref = trk.trajectory(poses, reference_visualiser=True)
@@ -155,6 +192,11 @@ def main():
                    iterations=[int(s["iterations"]) for s in stats])
     if a.live:
         metrics["n_matches"] = n_matches
+    if a.quality:
+        metrics["quality"] = quality_columns(records, a.width, a.height)
+        q = metrics["quality"]
+        print("coverage %.3f, mean |difference| %.2f aligned against %.2f unaligned (means over %d pairs)"
+              % (np.mean(q["coverage"]), np.mean(q["mean_abs"]), np.mean(q["mean_abs_unaligned"]), len(poses)))
     if a.groundtruth:
         ts, gtp = (T.read_groundtruth_euroc if a.euroc else T.read_groundtruth_tum)(a.groundtruth)
         idx_all = np.clip(T.ground_truth_indices(len(gtp), len(names), a.start, euroc=a.euroc), 0, len(gtp) - 1)

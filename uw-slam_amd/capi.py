@@ -27,6 +27,8 @@ KEYPOINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("response", "
 STATS = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("n_valid", "<i4"), ("error", "<f4")])   # uwt_stats
 TRACKING_INFO = np.dtype([("status", "<i4"), ("used_provided", "<i4"), ("n_kp_prev", "<i4"), ("n_kp_cur", "<i4"), ("n_symmetric", "<i4"),
                           ("n_matches", "<i4"), ("best_hypothesis", "<i4"), ("hypotheses_run", "<i4")])   # uwt_tracking_info
+WARP_QUALITY = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("n_landed", "<i4"), ("n_covered", "<i4"), ("sum_abs", "<i8"),
+                         ("sum_sq", "<i8"), ("sum_abs_unaligned", "<i8"), ("reserved", "<i8")])   # uwt_warp_quality
 
 
 class Params(C.Structure):
@@ -86,6 +88,11 @@ class TrackingIO(C.Structure):
                 ("d_n_matches", C.c_void_p)]
 
 
+class WarpImageIO(C.Structure):
+    """uwt_warp_image_io: device pointers of one uwt_warp_image_batch_async call"""
+    _fields_ = [("d_warped", C.c_void_p), ("d_valid", C.c_void_p), ("d_absdiff", C.c_void_p), ("d_quality", C.c_void_p)]
+
+
 class TableOptions(C.Structure):
     """uwt_table_options: the weights (0 identity, 1 Tukey, 2 Huber) and sampler (0 round(), 1 bilinear) of one batched table call"""
     _fields_ = [("weights", C.c_int32), ("sampler", C.c_int32), ("reserved", C.c_int32 * 6)]
@@ -133,6 +140,7 @@ SYMBOLS = [
     "uwt_orb_fast_scores", "uwt_orb_harris",
     "uwt_default_tracking_params", "uwt_tracking_batch_async", "uwt_tracking_batch", "uwt_match_descriptors_device_async",
     "uwt_default_tracking_orb_params", "uwt_tracking_orb_batch_async", "uwt_tracking_orb_batch",
+    "uwt_obtain_image_transformed", "uwt_warp_image_batch_async", "uwt_warp_image_batch", "uwt_warp_mosaic",
 ]
 
 _lib = None
@@ -1129,6 +1137,62 @@ class Context:
                 s += 1
         return dict(A=A, jtr=np.array(acc.jtr), sum_r2=int(acc.sum_r2), n_valid=int(acc.n_valid), J=J, r=r, valid=v, w=w,
                     err_num=err.value, inv_mad=inv_mad.value)
+
+    # -- did the alignment work: ObtainImageTransformed / DebugShowWarpedPerspective
+    def obtain_image_transformed(self, slot, lvl, pts, warped, image=None):
+        """Tracker::ObtainImageTransformed (src/Tracker.cpp:1473-1525) for one explicit table: original = the image plane of `slot` at
+        `lvl`, pts / warped: N x 4, image: the output image as it is before the call (img_h x img_w u8; None: zeros).  Returns (the
+        output image, validPixel)."""
+        L = self.level_info(lvl)
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        warped = np.ascontiguousarray(warped, np.float32).reshape(-1, 4)
+        assert pts.shape == warped.shape
+        out = np.zeros((L.img_h, L.img_w), np.uint8) if image is None else np.array(image, np.uint8, order="C")
+        assert out.shape == (L.img_h, L.img_w)
+        valid = np.empty((L.img_h, L.img_w), np.uint8)
+        self._chk(lib().uwt_obtain_image_transformed(self._h, slot, lvl, _p(pts, C.c_float), _p(warped, C.c_float), pts.shape[0],
+                                                     _p(out, C.c_uint8), _p(valid, C.c_uint8)))
+        return out, valid
+
+    def warp_image_batch(self, ref_slots, tgt_slots, poses, lvl=0, absdiff=True, raise_on_pair_failure=False):
+        """The dense form for many pairs, host in and out (uwt_warp_image_batch): poses [P, 7].  Returns a dict: status (OK or
+        ERR_PAIR_FAILED), warped, valid, absdiff ([P, img_h, img_w] u8; absdiff None when not asked for) and quality ([P] WARP_QUALITY)."""
+        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
+        P = ref.size
+        assert tgt.size == P and poses.shape[0] == P
+        L = self.level_info(lvl)
+        warped = np.zeros((max(P, 1), L.img_h, L.img_w), np.uint8)
+        valid = np.zeros_like(warped)
+        diff = np.zeros_like(warped) if absdiff else None
+        quality = np.zeros(max(P, 1), WARP_QUALITY)
+        st = lib().uwt_warp_image_batch(self._h, P, _p(ref, C.c_int32), _p(tgt, C.c_int32), lvl, _p(poses, C.c_float),
+                                        _p(warped, C.c_uint8), _p(valid, C.c_uint8), _p(diff, C.c_uint8) if absdiff else None,
+                                        C.c_void_p(quality.ctypes.data))
+        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+        return dict(status=st, warped=warped[:P], valid=valid[:P], absdiff=diff[:P] if absdiff else None, quality=quality[:P])
+
+    def warp_image_batch_async(self, ref_slots, tgt_slots, d_poses_ptr, io, lvl=0):
+        """The same enqueued on the context stream with the poses and every result in device memory (uwt_warp_image_batch_async).
+        d_poses_ptr: P x 7 float32, e.g. the pose buffer of a tracking call enqueued before, with no sync() in between; io: a dict of
+        device addresses — quality (P WARP_QUALITY) and optionally warped, valid, absdiff (P x pitch x img_h u8 each).  Never waits
+        for the device; sync() to wait."""
+        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
+        rec = WarpImageIO(*[io.get(k) or None for k in ("warped", "valid", "absdiff", "quality")])
+        self._chk(lib().uwt_warp_image_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), lvl,
+                                                   C.c_void_p(d_poses_ptr), C.byref(rec)))
+
+    def warp_mosaic(self, ref_slot, tgt_slot, lvl, warped):
+        """The image of Tracker::DebugShowWarpedPerspective (src/Tracker.cpp:1694-1737) for one pair: [image1 | image2] over
+        [blend(warped, image2) | blend(image1, image2)], 2 img_h x 2 img_w u8 (uwt_warp_mosaic)."""
+        L = self.level_info(lvl)
+        warped = np.ascontiguousarray(warped, np.uint8)
+        assert warped.shape == (L.img_h, L.img_w)
+        out = np.empty((2 * L.img_h, 2 * L.img_w), np.uint8)
+        self._chk(lib().uwt_warp_mosaic(self._h, ref_slot, tgt_slot, lvl, _p(warped, C.c_uint8), _p(out, C.c_uint8)))
+        return out
 
 
 class Ingest:

@@ -1074,7 +1074,8 @@ int uwt_destroy(uwt_ctx* c) {
   for (int i = 1; i < uwt_ctx::kMaxParts; i++)
     if (c->part_stream[i]) (void)hipStreamSynchronize(c->part_stream[i]);
   for (DevBuf* b : {&c->scratch, &c->stage[0], &c->stage[1], &c->cand_tab, &c->cand_cnt, &c->cand_work, &c->cand_recs, &c->match_desc,
-                    &c->match_cnt, &c->match_part, &c->match_out, &c->ransac_buf, &c->surf_buf, &c->orb_buf, &c->orb_pat, &c->track_buf})
+                    &c->match_cnt, &c->match_part, &c->match_out, &c->ransac_buf, &c->surf_buf, &c->orb_buf, &c->orb_pat, &c->track_buf,
+                    &c->warp_buf})
     (void)b->release();
   // the fixed-size allocations of uwt_create, uwt_update_params, ensure_features and ransac_need_rows (null: nothing to free)
   for (int l = 0; l < UWT_MAX_LEVELS; l++)

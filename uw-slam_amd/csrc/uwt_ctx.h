@@ -161,6 +161,9 @@ struct uwt_ctx {
   // the detector leaves, the paths
   // and flags of the previous frames, symMatches and the RANSAC records; behind them the synchronous form's inputs and results
   DevBuf track_buf;
+  // the image warp (uwt_obtain_image_transformed, uwt_warp_image_batch*, uwt_warp_mosaic): the winner planes of every pair and, for
+  // the host forms, their inputs and results — grown on use
+  DevBuf warp_buf;
   DevBuf stage[2];                      // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
   bool profiling = false;
   int spec_budget = 0;                  // speculative launching: evaluations a level gets (0: first_poll + 1); doubled when an alignment

@@ -237,6 +237,61 @@ class Tracker:
     def GetFrameData(self, _frame, lvl, plane):
         return self._ctx.get_plane(self._bind(_frame), lvl, plane)
 
+    def _find_plane(self, _image):
+        """(slot, level) of an image the device holds: a Frame (its level 0), a (Frame, lvl) pair, or pixels — the level is the one of
+        that size, the slot the resident frame whose plane at that level (GetFrameData) has these pixels.  Pixels of level 0's size
+        that no resident frame has are uploaded as a frame of their own (it takes the least-recently-used slot); pixels of a coarser
+        level's size that are nowhere on the device cannot be placed: the device builds levels 1.. from level 0."""
+        if isinstance(_image, Frame):
+            return self._bind(_image), 0
+        if isinstance(_image, tuple):
+            return self._bind(_image[0]), int(_image[1])
+        img = np.ascontiguousarray(_image, np.uint8)
+        n = self._ctx.params.n_levels
+        sizes = [(L.img_h, L.img_w) for L in (self._ctx.level_info(l) for l in range(n))]
+        if img.shape not in sizes:
+            raise ValueError("the image has the size of no pyramid level")
+        lvl = sizes.index(img.shape)
+        for slot, f in enumerate(self._owner):
+            if f is None:
+                continue
+            plane = f.images_[0] if lvl == 0 else self._ctx.get_plane(slot, lvl, capi.PLANE_IMAGE)
+            if plane is img or np.array_equal(plane, img):
+                return self._bind(f), lvl
+        if lvl != 0:
+            raise ValueError("an image of a coarser level's size that is no resident plane cannot be placed on the device")
+        self._scratch_frame = Frame(img)
+        return self._bind(self._scratch_frame), 0
+
+    def ObtainImageTransformed(self, _originalImage, _candidatePoints, _warpedPoints, _outputImage):
+        """include/Tracker.h:188, src/Tracker.cpp:1473-1525: _outputImage[round(warped)] = _originalImage[(int)point] for every row
+        in order, the last row on a pixel winning; _outputImage is written in place (pixels no row lands on keep their content) and
+        validPixel returned.  _originalImage: see _find_plane."""
+        slot, lvl = self._find_plane(_originalImage)
+        out, valid = self._ctx.obtain_image_transformed(slot, lvl, _candidatePoints, _warpedPoints, _outputImage)
+        _outputImage[...] = out
+        return valid
+
+    def DebugShowWarpedPerspective(self, _image1, _image2, _imageWarped, _lvl):
+        """include/Tracker.h:257, src/Tracker.cpp:1694-1737: the four-panel image [image1 | image2] over [blend(warped, image2) |
+        blend(image1, image2)], returned instead of shown (imshow / waitKey and the window's resize loop are the caller's).  _lvl is
+        the reference's argument; the level is the one of the images' size.  _image1, _image2: see _find_plane."""
+        a, la = self._find_plane(_image1)
+        b, lb = self._find_plane(_image2)
+        if la != lb or self._owner[a] is None or self._owner[a]._slot != a:
+            raise RuntimeError("DebugShowWarpedPerspective: images of two levels, or more frames than slots (max_frames)")
+        return self._ctx.warp_mosaic(a, b, la, _imageWarped)
+
+    def WarpedImageBatch(self, pairs, poses, lvl=0):
+        """ObtainAllPoints -> WarpFunction -> ObtainImageTransformed for a list of (previous, current) frame pairs under `poses`
+        ([P, 7]) in one call (uwt_warp_image_batch): returns (warped [P, h, w], valid [P, h, w], quality [P] capi.WARP_QUALITY)."""
+        slots = [(self._bind(a), self._bind(b)) for a, b in pairs]
+        for (a, b), (sa, sb) in zip(pairs, slots):   # binding a later pair's frame may have taken an earlier frame's slot
+            if a._slot != sa or b._slot != sb:
+                raise RuntimeError("WarpedImageBatch: more frames than slots (max_frames)")
+        r = self._ctx.warp_image_batch([s[0] for s in slots], [s[1] for s in slots], poses, lvl=lvl, absdiff=False)
+        return r["warped"], r["valid"], r["quality"]
+
 
 class RobustMatcher:
     """include/Tracker.h:65-88 — the matching half of RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258): knnMatch in
