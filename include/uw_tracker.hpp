@@ -339,6 +339,53 @@ class Tracker {
     if (st != UWT_ERR_PAIR_FAILED) check(st, "uwt_warp_image_batch");   // a failed pair has its status in its record
     return r;
   }
+  // Visualizer::AddPointCloudFromRGBD (src/Visualizer.cpp:421-446) for a list of frames under the accumulated poses `_traj` in one call
+  // (uwt_point_cloud_batch; the contract: include/uwt.h): the records in frame order and, inside a frame, in row order; info holds
+  // one record per frame, then the call's.  _params null: the reference's call (the dense level-0 table, every 100th row).
+  struct PointCloud {
+    std::vector<uwt_cloud_point> points;
+    std::vector<uwt_cloud_info> info;
+  };
+  PointCloud PointCloudBatch(const std::vector<Frame*>& _frames, const std::vector<SE3>& _traj, const uwt_cloud_params* _params = nullptr) {
+    const size_t n = _frames.size();
+    if (_traj.size() != n || !n) throw std::runtime_error("PointCloudBatch: one pose per frame, one frame at least");
+    uwt_cloud_params cp;
+    if (_params) cp = *_params;
+    else check(uwt_default_cloud_params(&cp), "uwt_default_cloud_params");
+    if (cp.stride < 1) throw std::runtime_error("PointCloudBatch: stride < 1");
+    std::vector<int32_t> slots(n);
+    for (size_t i = 0; i < n; i++) {
+      slots[i] = bind(_frames[i]);
+      if (cp.source == 1 && !_frames[i]->obtained_gradients_)
+        throw std::runtime_error("PointCloudBatch: the candidate source needs ApplyGradient (or the frame's slot was reused since)");
+    }
+    for (size_t i = 0; i < n; i++)   // binding a later frame may have taken an earlier frame's slot
+      if (!bound(_frames[i]) || _frames[i]->slot_ != slots[i]) throw std::runtime_error("PointCloudBatch: more frames than slots (max_frames)");
+    const uwt_level L = level(0);
+    PointCloud r;
+    r.points.resize(n * (((size_t)L.w * L.h - 1) / (size_t)cp.stride + 1));
+    r.info.resize(n + 1);
+    const int st = uwt_point_cloud_batch(ctx(), (int32_t)n, slots.data(), _traj[0].data(), &cp, r.points.data(), (int64_t)r.points.size(),
+                                         r.info.data());
+    if (st != UWT_ERR_PAIR_FAILED) check(st, "uwt_point_cloud_batch");   // a failed frame has its status in its record
+    r.points.resize((size_t)r.info[n].written);
+    return r;
+  }
+  // the same on one explicit N x 4 table of any producer (uwt_point_cloud_points); _frame serves the intensities
+  std::vector<uwt_cloud_point> PointCloudPoints(Frame* _frame, const std::vector<float>& _points, const SE3& _pose,
+                                                const uwt_cloud_params* _params = nullptr) {
+    uwt_cloud_params cp;
+    if (_params) cp = *_params;
+    else check(uwt_default_cloud_params(&cp), "uwt_default_cloud_params");
+    if (cp.stride < 1) throw std::runtime_error("PointCloudPoints: stride < 1");
+    const int32_t n = (int32_t)(_points.size() / 4);
+    std::vector<uwt_cloud_point> out(n ? ((size_t)n - 1) / (size_t)cp.stride + 1 : 0);
+    int64_t count = 0;
+    check(uwt_point_cloud_points(ctx(), bind(_frame), _points.data(), n, _pose.data(), &cp, out.data(), (int64_t)out.size(), &count),
+          "uwt_point_cloud_points");
+    out.resize((size_t)count);
+    return out;
+  }
   // include/Tracker.h:145 — gradient_ > mean + GRADIENT_THRESHOLD (src/Options.cpp:27) on every level, x-major order
   void ObtainCandidatePoints(Frame* _frame, double gradient_threshold = 20.0) {
     const int slot = bind(_frame);
@@ -606,6 +653,46 @@ class Tracker {
 inline Frame::~Frame() {
   if (tracker_) tracker_->forget(this);
 }
+
+// include/Map.h — Map::AddPointCloudFromRGBD (src/Map.cpp:33-45): recent_cloud_points_ is the x y z columns of the frame's level-0
+// candidatePoints_ (N x 3, row-major).  A frame whose points were never materialised (the dense ObtainAllPoints keeps no table) has
+// none to keep: std::runtime_error.
+class Map {
+ public:
+  std::vector<float> recent_cloud_points_;
+  void AddPointCloudFromRGBD(Frame* frame) {
+    const std::vector<float>& t = frame->candidatePoints_[0];
+    if (t.empty()) throw std::runtime_error("Map::AddPointCloudFromRGBD: the frame has no level-0 candidatePoints_");
+    const size_t num_cloud_points = t.size() / 4;
+    recent_cloud_points_.resize(num_cloud_points * 3);
+    for (size_t i = 0; i < num_cloud_points; i++)
+      for (int k = 0; k < 3; k++) recent_cloud_points_[3 * i + k] = t[4 * i + k];
+  }
+};
+
+// The map-building part of include/Visualizer.h — Visualizer::AddPointCloudFromRGBD (src/Visualizer.cpp:421-446) on the device:
+// every 100th row of the frame's level-0 table (its candidatePoints_[0] when a sparse producer ran, else ObtainAllPoints' dense table of
+// the bound frame), unprojected and offset by previous_pose's translation, appended to point_cloud_.  previous_pose is the
+// accumulation UpdateMessages keeps (uwt_accumulate_trajectory with t_scale 40, reference_axes 0); the tags count the calls.
+class Visualizer {
+ public:
+  explicit Visualizer(Tracker* tracker) : tracker_(tracker) {}
+  std::vector<uwt_cloud_point> point_cloud_;
+  SE3 previous_pose_;
+  void AddPointCloudFromRGBD(Frame* frame, const SE3& previous_pose) {
+    previous_pose_ = previous_pose;
+    std::vector<uwt_cloud_point> rec = frame->candidatePoints_[0].empty()
+                                           ? tracker_->PointCloudBatch({frame}, {previous_pose}).points
+                                           : tracker_->PointCloudPoints(frame, frame->candidatePoints_[0], previous_pose);
+    for (uwt_cloud_point& p : rec) p.tag = (p.tag & 255u) | ((uint32_t)n_calls_ << 8);
+    n_calls_++;
+    point_cloud_.insert(point_cloud_.end(), rec.begin(), rec.end());
+  }
+
+ private:
+  Tracker* tracker_;
+  int n_calls_ = 0;
+};
 
 // include/Tracker.h:65-88 — RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258) from the matcher on: knnMatch in both
 // directions, ratioTest twice and symmetryTest on the GPU (uwt_match_descriptors_batch), ransacTest as the inlier selection of

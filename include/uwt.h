@@ -1053,6 +1053,86 @@ int uwt_warp_image_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots
  * img_h u8 (host), mosaic_out: 2 img_w x 2 img_h u8 (host).  Synchronous. */
 int uwt_warp_mosaic(uwt_ctx* ctx, int32_t ref_slot, int32_t tgt_slot, int32_t lvl, const uint8_t* warped, uint8_t* mosaic_out);
 
+/* ---- the map: Visualizer::AddPointCloudFromRGBD and Map::AddPointCloudFromRGBD ------------------------------------------------- */
+
+/* Visualizer::AddPointCloudFromRGBD(Frame*) (src/Visualizer.cpp:421-446) unprojects the frame's level-0 candidatePoints_ table, takes
+ * every 100th row, offsets it by the accumulated pose's translation and appends it to point_cloud_; Map::AddPointCloudFromRGBD(Frame*)
+ * (src/Map.cpp:33-45) keeps the x y z columns of that table as recent_cloud_points_.  The contract of the device form:
+ * A cloud is a sequence of 16-byte records uwt_cloud_point { x, y, z, tag }, tag = intensity | (frame_index_in_call << 8), intensity =
+ * image[(int)y][(int)x] (truncation toward zero: -0.5 reads column 0) at level 0 of the frame's slot, 0 where that pixel lies outside the
+ * image or the coordinate is not a number.  The geometry never reads the image.
+ * Frame f of a call has a level-0 table of N rows [x, y, z, w] and a pose traj[f] = qx qy qz qw tx ty tz.
+ *   - Selection: rows i = 0, stride, 2 stride, ... < N IN THAT ORDER (the loop "for (i = 0; i < rows; i += 100)", :437); stride >= 1, the
+ *     reference's is 100.  skip_invalid = 0 (the reference): every selected row is emitted, the [0 0 1 0] rows of zero depth included —
+ *     the reference emits them, a quirk reproduced.  skip_invalid = 1 (extension): a selected row with w == 0 is dropped, the others keep
+ *     their order.
+ *   - Unprojection: X = ((x - cx) invfx) z, Y = ((y - cy) invfy) z with level 0's intrinsics, exactly uwt_warp's under the context's
+ *     arith: the MatExpr-folded x * invfx + (float)(-(double)cx * invfx) in the OpenCV set, as written in the legacy set, then * z, all
+ *     in f32.  Z = z.
+ *   - mode 0, the reference's visualiser (:440-442): point = (-X - tx, -Z - tz, -Y - ty), each one f32 subtraction, t = traj[f]'s
+ *     translation UNPERMUTED: the reference reads previous_pose_.translation(), not the published position, so the caller passes the
+ *     accumulation made with reference_axes = 0.
+ *   - mode 1, world (extension, no counterpart in the reference): point = the first three rows of T(traj[f]) [X Y Z w], T =
+ *     uwt_se3_matrix's matrix, each row (float)(T0 X + ((T1 Y + T2 Z) + T3 w)) formed in f64.  This one definition holds in BOTH
+ *     arithmetic sets (the legacy set's f32 chain is not used here).
+ *   - Order: the cloud of a call is frame 0's points, then frame 1's, ..., each in row order — what successive push_backs give.
+ *   - Independence: the bytes of a frame's points depend neither on the batch, nor on the frame's place in it (the tag's frame index
+ *     apart), nor on uwt_tuning, nor on the run: where a record goes follows from counts and a scan, never from an atomic cursor.
+ * Deviations (in the style of SURVEY C-3): a frame whose pose has a non-finite entry contributes no points; its record carries
+ * UWT_ERR_INVALID_ARG with n_rows, n_selected and n_points 0; its neighbours are untouched. */
+typedef struct uwt_cloud_point {   /* 16 bytes */
+  float x, y, z;
+  uint32_t tag;              /* intensity | (frame_index_in_call << 8) */
+} uwt_cloud_point;
+
+typedef struct uwt_cloud_params {   /* 32 bytes */
+  int32_t mode;              /* 0: the reference's visualiser; 1: world */
+  int32_t stride;            /* >= 1; the reference: 100 */
+  int32_t skip_invalid;      /* 0: the reference; 1: drop selected rows with w == 0 */
+  int32_t source;            /* 0: ObtainAllPoints' dense level-0 table; 1: ObtainCandidatePoints' under `threshold` */
+  double  threshold;         /* source 1 only; finite */
+  int32_t reserved[2];       /* must be zero */
+} uwt_cloud_params;
+
+typedef struct uwt_cloud_info {   /* 32 bytes; n_frames records for the frames, then ONE for the call */
+  int32_t status;            /* a frame: UWT_OK or UWT_ERR_INVALID_ARG (its pose); the call: UWT_OK or UWT_ERR_CAPACITY */
+  int32_t n_rows;            /* a frame: N; the call: n_frames */
+  int32_t n_selected;        /* a frame: rows selected, ceil(N / stride); the call: 0 */
+  int32_t n_points;          /* a frame: records it emits (skip_invalid 0: n_selected); the call: 0 */
+  int64_t offset;            /* a frame: its first record in the cloud; the call: the total number of points, the FULL count */
+  int64_t written;           /* records actually written: a frame's inside cap; the call: min(total, cap) */
+} uwt_cloud_info;
+
+/* {0, 100, 0, 0, 20.0, {0, 0}}: the reference's call */
+int uwt_default_cloud_params(uwt_cloud_params* params);
+/* The cloud of n_frames resident frames, every pointer DEVICE memory: d_traj n_frames x 7 (the output of
+ * uwt_accumulate_trajectory_device_async goes straight in), d_points_out `cap` records, d_info_out n_frames + 1 records.
+ *   source 0: frame f's table is ObtainAllPoints' dense level-0 table of slots[f] (src/Tracker.cpp:1259-1310), rows i = y w + x, z and the
+ *     invalid rule exactly as uwt_warp_image_batch documents them; it is never materialised (2 bytes of depth and 1 of the image are
+ *     read per selected pixel, 16 written).  With skip_invalid 0 every offset is closed-form and the call is one launch.
+ *   source 1: ObtainCandidatePoints' level-0 table of slots[f] under `threshold`: bit for bit the rows of
+ *     uwt_obtain_candidate_points(slots[f], 0, threshold).  The frames need gradients (uwt_apply_gradient).
+ * Points beyond cap are not written — the records beyond it stay as they were — and UWT_ERR_CAPACITY goes into the call's record, which
+ * still holds the full count, as uwt_obtain_candidate_points writes min(count, cap) rows and returns the full count.
+ * Enqueued on the context's stream, ordered against uwt_upload_frames_async as the other batch calls are; it never waits for the device
+ * (uwt_sync() to wait).  1 <= n_frames <= max_frames (and <= 65535).
+ * UWT_ERR_INVALID_ARG with nothing enqueued and the outputs untouched: a null argument (d_points_out may be null with cap 0), cap < 0, n_frames
+ * out of range, a slot out of range, a mode or source outside 0..1, skip_invalid outside 0..1, stride < 1, a non-zero reserved word, a
+ * non-finite threshold. */
+int uwt_point_cloud_batch_async(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const float* d_traj, const uwt_cloud_params* params,
+                                uwt_cloud_point* d_points_out, int64_t cap, uwt_cloud_info* d_info_out);
+/* The same, synchronous, HOST arrays: traj n_frames x 7, points_out cap records (those below the call's `written` are delivered),
+ * info_out n_frames + 1.  UWT_ERR_PAIR_FAILED when a frame failed (its status in its record), else UWT_ERR_CAPACITY when cap was too
+ * small; the records are valid in both cases. */
+int uwt_point_cloud_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const float* traj, const uwt_cloud_params* params,
+                          uwt_cloud_point* points_out, int64_t cap, uwt_cloud_info* info_out);
+/* The reference's call on ONE explicit host table: pts n x 4 floats of any producer, `slot` serves the intensities only, traj_pose 7
+ * floats; params->source and threshold are ignored.  The tag's frame index is 0.  *count_out: the full count; min(count, cap) records are
+ * written.  n = 0 is UWT_OK with count 0.  UWT_ERR_CAPACITY when count > cap, UWT_ERR_INVALID_ARG for a non-finite pose (count 0).
+ * The batch form over the same rows gives the same bytes.  Synchronous. */
+int uwt_point_cloud_points(uwt_ctx* ctx, int32_t slot, const float* pts, int32_t n, const float traj_pose[7],
+                           const uwt_cloud_params* params, uwt_cloud_point* points_out, int64_t cap, int64_t* count_out);
+
 /* ---- next to the path: frame ingest---------------------------------------------------------------- */
 
 typedef struct uwt_ingest uwt_ingest;
@@ -1088,6 +1168,19 @@ int uwt_accumulate_trajectory(uwt_ctx* ctx, const float* poses, int32_t n, const
  * (t_scale 40, reference_axes 1) that has to reproduce src/Visualizer.cpp:304-325 exactly stays sequential. */
 int uwt_accumulate_trajectory_scan(uwt_ctx* ctx, const float* poses, int32_t n, const float start_pose[7], float t_scale,
                                    int32_t reference_axes, float* traj_out);
+/* uwt_accumulate_trajectory with d_poses and d_traj_out (n x 7 each) in DEVICE memory: the same sequential kernel launched on them on the
+ * context's stream, no copy and no wait, the results bit for bit the same.  d_poses may be uwt_tracking_io::d_poses of a call enqueued
+ * before and d_traj_out the d_traj of uwt_point_cloud_batch_async enqueued behind: tracking -> trajectory -> cloud with one uwt_sync()
+ * at the end.  n = 0: nothing is enqueued.  start_pose: host.  d_poses and d_traj_out must not overlap (the kernel reads and writes
+ * through restrict pointers; accumulating in place is refused): UWT_ERR_INVALID_ARG with nothing enqueued. */
+int uwt_accumulate_trajectory_device_async(uwt_ctx* ctx, const float* d_poses, int32_t n, const float start_pose[7], float t_scale,
+                                           int32_t reference_axes, float* d_traj_out);
+/* The same behind a previous pose that is in DEVICE memory: d_start_pose, 7 floats as an accumulation with reference_axes = 0 stores
+ * them (a row of an earlier call's d_traj_out).  A live loop accumulates one pose per frame with it — row k from row k - 1 — at a
+ * constant cost per frame and still without a wait; the rows are bit for bit those of one call over all poses.  d_traj_out must
+ * overlap neither d_poses nor d_start_pose: UWT_ERR_INVALID_ARG with nothing enqueued. */
+int uwt_accumulate_trajectory_device_from_async(uwt_ctx* ctx, const float* d_poses, int32_t n, const float* d_start_pose, float t_scale,
+                                                int32_t reference_axes, float* d_traj_out);
 
 #ifdef __cplusplus
 }

@@ -68,11 +68,40 @@ def sequence_quality(w, h, intr, frames, depths, poses, arith=0):
     return out
 
 
-def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0, quality=False):
+CLOUD_MODES = {"reference": 0, "world": 1}
+
+
+def cloud_accumulation(mode):
+    """(t_scale, reference_axes) of the accumulation a cloud mode takes its poses from: the reference's visualiser reads
+    previous_pose_ (t_scale 40, unpermuted: src/Visualizer.cpp:307-313, :425); world: the plain SE(3) prefix product"""
+    return (40.0, False) if mode == 0 else (1.0, False)
+
+
+def sequence_cloud(w, h, intr, frames, depths, poses, stride=100, mode=0, arith=0):
+    """Visualizer::AddPointCloudFromRGBD over a tracked sequence, for the modes whose poses are on the host: pair k's previous frame
+    under the pose accumulated up to pair k (uwt_accumulate_trajectory, uwt_point_cloud_batch).  Returns capi.CLOUD_POINT records."""
+    capi = importlib.import_module("uw-slam_amd.capi")
+    ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=1, max_pairs=1, has_depth=int(bool(depths)), arith=arith))
+    t_scale, axes = cloud_accumulation(mode)
+    traj = ctx.accumulate_trajectory(np.asarray(poses, np.float32), t_scale=t_scale, reference_axes=axes)
+    p = capi.default_cloud_params(mode=mode, stride=stride)
+    parts = []
+    for k in range(len(traj)):
+        ctx.upload_frames(0, frames[k][None], depths[k][None] if depths else None)
+        rec = ctx.point_cloud_batch([0], traj[k:k + 1], p)["points"].copy()
+        rec["tag"] = (rec["tag"] & 255) | np.uint32(k << 8)
+        parts.append(rec)
+    ctx.close()
+    return np.concatenate(parts) if parts else np.zeros(0, capi.CLOUD_POINT)
+
+
+def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0, quality=False, cloud=None):
     """The same loop as successive one-pair uwt_tracking_batch_async calls (detector 1: uwt_tracking_orb_batch_async): what a frame kept
     goes to the next call in device memory (two sets of buffers, taken in turn), nothing is read back between the calls and the host
     waits once, at the end.  Same returns; quality: behind every call uwt_warp_image_batch_async on its device pose, inside the same
-    single wait — the records come back as a fourth result."""
+    single wait — the records come back as a fourth result.  cloud = (stride, mode): behind every call the trajectory is
+    accumulated from the device poses, one pose per call (uwt_accumulate_trajectory_device_from_async), and, frame by frame while it is resident, the cloud
+    enqueued (uwt_point_cloud_batch_async), still inside the single wait — the records come back as the last result."""
     import torch
     capi = importlib.import_module("uw-slam_amd.capi")
     n = len(frames)
@@ -84,6 +113,16 @@ def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0
     sets = [dict(good=torch.zeros((cap, 3), **i32), kept_prev=torch.zeros((cap, 8), **i32), kept_cur=torch.zeros((cap, 8), **i32),
                  n_matches=torch.zeros((1,), **i32)) for _ in range(2)]
     records = torch.zeros((n - 1, 48), dtype=torch.uint8, device="cuda") if quality else None
+    if cloud:
+        # A frame leaves its slot three calls later, and pair k's accumulated pose exists once pair k's call is enqueued: behind every
+        # call ONE pose is accumulated, row k from row k - 1 in device memory, and frame k's points follow it.
+        stride, mode = cloud
+        per = -(-(w * h) // stride)
+        cp = capi.default_cloud_params(mode=mode, stride=stride)
+        t_scale, axes = cloud_accumulation(mode)
+        traj = torch.zeros((n - 1, 7), dtype=torch.float32, device="cuda")
+        cpts = torch.zeros((n - 1, per, 16), dtype=torch.uint8, device="cuda")
+        cinfo = torch.zeros((n - 1, 2, 32), dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()   # torch's fills run on torch's stream
 
     def load(i):
@@ -101,18 +140,33 @@ def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0
         enqueue([k % 4], [(k + 1) % 4], io, cap=cap)
         if quality:
             ctx.warp_image_batch_async([k % 4], [(k + 1) % 4], poses[k].data_ptr(), dict(quality=records[k].data_ptr()), lvl=0)
+        if cloud:
+            if k:
+                ctx.accumulate_trajectory_device_from_async(poses[k].data_ptr(), 1, traj[k - 1].data_ptr(), traj[k].data_ptr(),
+                                                            t_scale=t_scale, reference_axes=axes)
+            else:
+                ctx.accumulate_trajectory_device_async(poses[0].data_ptr(), 1, traj[0].data_ptr(), t_scale=t_scale, reference_axes=axes)
+            ctx.point_cloud_batch_async([k % 4], traj[k].data_ptr(), cpts[k].data_ptr(), per, cinfo[k].data_ptr(), cp)
     ctx.sync()
     st = stats.cpu().numpy().view(capi.STATS).reshape(-1)
     kept = info.cpu().numpy().view(capi.TRACKING_INFO).reshape(-1)["n_matches"]
     out = poses.cpu().numpy().view(np.float32).reshape(-1, 7).copy()
     rec = records.cpu().numpy().reshape(-1).view(capi.WARP_QUALITY) if quality else None
+    if cloud:
+        cl = cpts.cpu().numpy().reshape(n - 1, per * 16).view(capi.CLOUD_POINT).copy()
+        written = cinfo.cpu().numpy().reshape(n - 1, 2, 32).view(capi.CLOUD_INFO)[:, 1, 0]["written"]
+        for k in range(n - 1):
+            cl[k]["tag"] = (cl[k]["tag"] & 255) | np.uint32(k << 8)
+        cl = np.concatenate([cl[k, :int(written[k])] for k in range(n - 1)]) if n > 1 else np.zeros(0, capi.CLOUD_POINT)
     ctx.close()
     res = (out, [dict(status=int(s["status"]), iterations=int(s["iterations"]), n_valid=int(s["n_valid"]), error=float(s["error"])) for s in st],
            [int(v) for v in kept])
-    return res + (rec,) if quality else res
+    if quality:
+        res = res + (rec,)
+    return res + (cl,) if cloud else res
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", required=True)
     ap.add_argument("--depth")
@@ -138,7 +192,18 @@ def main():
     ap.add_argument("--quality", action="store_true", help="per pair, at level 0: the share of the frame the previous frame covers "
                     "under the estimated pose and the mean |difference| over it with and without the alignment "
                     "(Tracker::ObtainImageTransformed on the device; with --chained from the device poses, inside the same single wait)")
+    ap.add_argument("--cloud", metavar="OUT.ply", help="write the point-cloud map (Visualizer::AddPointCloudFromRGBD on the device: every "
+                    "--cloud-stride-th row of each pair's previous frame under the accumulated pose) as a binary PLY; with --live --chained "
+                    "the trajectory and the cloud are enqueued behind the tracking calls, inside the same single wait")
+    ap.add_argument("--cloud-stride", type=int, default=100, help="the reference takes every 100th row (src/Visualizer.cpp:437)")
+    ap.add_argument("--cloud-mode", choices=sorted(CLOUD_MODES), default="reference", help="reference: the visualiser's axes and offset "
+                    "(:440-442); world: the camera points under the plain SE(3) prefix product of the pair poses")
     ap.add_argument("--out", default="trajectory")
+    return ap
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
     S = importlib.import_module("uw-slam_amd.sequence")
     T = importlib.import_module("uw-slam_amd.trajectory")
@@ -172,10 +237,16 @@ def main():
     t0 = time.perf_counter()
     if a.detector == "orb" and not a.live:
         ap.error("--detector orb goes with --live")
-    records = None
-    if a.live and a.chained and a.quality:
-        poses, stats, n_matches, records = track_live_chained(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
-                                                              detector=int(a.detector == "orb"), quality=True)
+    if a.cloud and a.cloud_stride < 1:
+        ap.error("--cloud-stride must be at least 1")
+    records = cloud = None
+    cloud_args = (a.cloud_stride, CLOUD_MODES[a.cloud_mode]) if a.cloud else None
+    if a.live and a.chained and (a.quality or a.cloud):
+        res = track_live_chained(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
+                                 detector=int(a.detector == "orb"), quality=a.quality, cloud=cloud_args)
+        poses, stats, n_matches = res[:3]
+        records = res[3] if a.quality else None
+        cloud = res[-1] if a.cloud else None
     elif a.live:
         poses, stats, n_matches = (track_live_chained if a.chained else track_live)(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths,
                                                                                     over["arith"], detector=int(a.detector == "orb"))
@@ -183,6 +254,8 @@ def main():
         poses, stats = trk.track(frames, depths)
     if a.quality and records is None:
         records = sequence_quality(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, np.asarray(poses, np.float32), over["arith"])
+    if a.cloud and cloud is None:
+        cloud = sequence_cloud(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, poses, *cloud_args, arith=over["arith"])
     dt = time.perf_counter() - t0
     traj = trk.trajectory(poses)
     ref = trk.trajectory(poses, reference_visualiser=True)
@@ -197,6 +270,10 @@ def main():
         q = metrics["quality"]
         print("coverage %.3f, mean |difference| %.2f aligned against %.2f unaligned (means over %d pairs)"
               % (np.mean(q["coverage"]), np.mean(q["mean_abs"]), np.mean(q["mean_abs_unaligned"]), len(poses)))
+    if a.cloud:
+        metrics["cloud_points"] = int(cloud.size)
+        T.write_ply(a.cloud, cloud)
+        print("%d cloud points (every %d-th row, %s) in %s" % (cloud.size, a.cloud_stride, a.cloud_mode, a.cloud))
     if a.groundtruth:
         ts, gtp = (T.read_groundtruth_euroc if a.euroc else T.read_groundtruth_tum)(a.groundtruth)
         idx_all = np.clip(T.ground_truth_indices(len(gtp), len(names), a.start, euroc=a.euroc), 0, len(gtp) - 1)

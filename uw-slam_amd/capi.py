@@ -29,6 +29,9 @@ TRACKING_INFO = np.dtype([("status", "<i4"), ("used_provided", "<i4"), ("n_kp_pr
                           ("n_matches", "<i4"), ("best_hypothesis", "<i4"), ("hypotheses_run", "<i4")])   # uwt_tracking_info
 WARP_QUALITY = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("n_landed", "<i4"), ("n_covered", "<i4"), ("sum_abs", "<i8"),
                          ("sum_sq", "<i8"), ("sum_abs_unaligned", "<i8"), ("reserved", "<i8")])   # uwt_warp_quality
+CLOUD_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("tag", "<u4")])   # uwt_cloud_point
+CLOUD_INFO = np.dtype([("status", "<i4"), ("n_rows", "<i4"), ("n_selected", "<i4"), ("n_points", "<i4"), ("offset", "<i8"),
+                       ("written", "<i8")])   # uwt_cloud_info
 
 
 class Params(C.Structure):
@@ -93,6 +96,25 @@ class WarpImageIO(C.Structure):
     _fields_ = [("d_warped", C.c_void_p), ("d_valid", C.c_void_p), ("d_absdiff", C.c_void_p), ("d_quality", C.c_void_p)]
 
 
+class CloudParams(C.Structure):
+    """uwt_cloud_params: mode (0 the reference's visualiser, 1 world), stride, skip_invalid, source (0 dense, 1 candidates), threshold"""
+    _fields_ = [("mode", C.c_int32), ("stride", C.c_int32), ("skip_invalid", C.c_int32), ("source", C.c_int32), ("threshold", C.c_double),
+                ("reserved", C.c_int32 * 2)]
+
+
+def default_cloud_params(**over):
+    """uwt_default_cloud_params: {0, 100, 0, 0, 20.0}, the reference's call; keyword arguments override fields"""
+    p = CloudParams()
+    st = lib().uwt_default_cloud_params(C.byref(p))
+    if st:
+        raise UwtError(st, "uwt_default_cloud_params")
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 class TableOptions(C.Structure):
     """uwt_table_options: the weights (0 identity, 1 Tukey, 2 Huber) and sampler (0 round(), 1 bilinear) of one batched table call"""
     _fields_ = [("weights", C.c_int32), ("sampler", C.c_int32), ("reserved", C.c_int32 * 6)]
@@ -141,6 +163,8 @@ SYMBOLS = [
     "uwt_default_tracking_params", "uwt_tracking_batch_async", "uwt_tracking_batch", "uwt_match_descriptors_device_async",
     "uwt_default_tracking_orb_params", "uwt_tracking_orb_batch_async", "uwt_tracking_orb_batch",
     "uwt_obtain_image_transformed", "uwt_warp_image_batch_async", "uwt_warp_image_batch", "uwt_warp_mosaic",
+    "uwt_default_cloud_params", "uwt_point_cloud_batch_async", "uwt_point_cloud_batch", "uwt_point_cloud_points",
+    "uwt_accumulate_trajectory_device_async", "uwt_accumulate_trajectory_device_from_async",
 ]
 
 _lib = None
@@ -1193,6 +1217,63 @@ class Context:
         out = np.empty((2 * L.img_h, 2 * L.img_w), np.uint8)
         self._chk(lib().uwt_warp_mosaic(self._h, ref_slot, tgt_slot, lvl, _p(warped, C.c_uint8), _p(out, C.c_uint8)))
         return out
+
+
+    # -- the map: Visualizer::AddPointCloudFromRGBD
+    def point_cloud_batch(self, slots, traj, params=None, cap=None, raise_on_failure=False):
+        """The cloud of resident frames, host in and out (uwt_point_cloud_batch): traj [F, 7], the accumulation with reference_axes = 0.
+        cap None: room for every selected row.  Returns a dict: status (OK, ERR_PAIR_FAILED or ERR_CAPACITY), points ([written]
+        CLOUD_POINT), info ([F] CLOUD_INFO) and call (the call's CLOUD_INFO record: offset = the full count)."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        traj = np.ascontiguousarray(traj, np.float32).reshape(-1, 7)
+        F = slots.size
+        assert traj.shape[0] == F
+        params = default_cloud_params() if params is None else params
+        if cap is None:
+            L = self.level_info(0)
+            cap = F * (-(-(L.w * L.h) // max(int(params.stride), 1)))
+        pts = np.zeros(max(cap, 1), CLOUD_POINT)
+        info = np.zeros(F + 1, CLOUD_INFO)
+        st = lib().uwt_point_cloud_batch(self._h, F, _p(slots, C.c_int32), _p(traj, C.c_float), C.byref(params),
+                                         C.c_void_p(pts.ctypes.data), C.c_int64(cap), C.c_void_p(info.ctypes.data))
+        self._chk(st, allow=() if raise_on_failure else (ERR_PAIR_FAILED, ERR_CAPACITY))
+        return dict(status=st, points=pts[:int(info[F]["written"])], info=info[:F], call=info[F])
+
+    def point_cloud_batch_async(self, slots, d_traj_ptr, d_points_ptr, cap, d_info_ptr, params=None):
+        """The same enqueued on the context stream with the poses and every result in device memory (uwt_point_cloud_batch_async):
+        d_traj_ptr F x 7 float32 (e.g. what accumulate_trajectory_device_async left, with no sync() in between), d_points_ptr cap
+        CLOUD_POINT records, d_info_ptr F + 1 CLOUD_INFO records.  Never waits for the device; sync() to wait."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        params = default_cloud_params() if params is None else params
+        self._chk(lib().uwt_point_cloud_batch_async(self._h, slots.size, _p(slots, C.c_int32), C.c_void_p(d_traj_ptr), C.byref(params),
+                                                    C.c_void_p(d_points_ptr), C.c_int64(cap), C.c_void_p(d_info_ptr)))
+
+    def point_cloud_points(self, slot, pts, traj_pose, params=None, cap=None):
+        """Visualizer::AddPointCloudFromRGBD (src/Visualizer.cpp:421-446) on one explicit N x 4 table (uwt_point_cloud_points); `slot`
+        serves the intensities.  Returns (points [min(count, cap)] CLOUD_POINT, the full count, status OK or ERR_CAPACITY)."""
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        pose = np.ascontiguousarray(traj_pose, np.float32).reshape(7)
+        params = default_cloud_params() if params is None else params
+        n = pts.shape[0]
+        cap = -(-n // max(int(params.stride), 1)) if cap is None else cap
+        out = np.zeros(max(cap, 1), CLOUD_POINT)
+        cnt = C.c_int64()
+        st = lib().uwt_point_cloud_points(self._h, slot, _p(pts, C.c_float), n, _p(pose, C.c_float), C.byref(params),
+                                          C.c_void_p(out.ctypes.data), C.c_int64(cap), C.byref(cnt))
+        self._chk(st, allow=(ERR_CAPACITY,))
+        return out[:min(cnt.value, cap)], cnt.value, st
+
+    def accumulate_trajectory_device_async(self, d_poses_ptr, n, d_traj_ptr, start=None, t_scale=1.0, reference_axes=False):
+        """uwt_accumulate_trajectory on device pointers (n x 7 float32 each), enqueued on the context stream: no copy, no wait."""
+        start = np.array([0, 0, 0, 1, 0, 0, 0], np.float32) if start is None else np.ascontiguousarray(start, np.float32)
+        self._chk(lib().uwt_accumulate_trajectory_device_async(self._h, C.c_void_p(d_poses_ptr), int(n), _p(start, C.c_float),
+                                                               C.c_float(t_scale), int(bool(reference_axes)), C.c_void_p(d_traj_ptr)))
+
+    def accumulate_trajectory_device_from_async(self, d_poses_ptr, n, d_start_ptr, d_traj_ptr, t_scale=1.0, reference_axes=False):
+        """The same behind a previous pose in device memory (uwt_accumulate_trajectory_device_from_async): d_start_ptr 7 float32, a row of
+        an earlier accumulation made with reference_axes False."""
+        self._chk(lib().uwt_accumulate_trajectory_device_from_async(self._h, C.c_void_p(d_poses_ptr), int(n), C.c_void_p(d_start_ptr),
+                                                                    C.c_float(t_scale), int(bool(reference_axes)), C.c_void_p(d_traj_ptr)))
 
 
 class Ingest:

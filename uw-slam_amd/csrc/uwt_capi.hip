@@ -1075,7 +1075,7 @@ int uwt_destroy(uwt_ctx* c) {
     if (c->part_stream[i]) (void)hipStreamSynchronize(c->part_stream[i]);
   for (DevBuf* b : {&c->scratch, &c->stage[0], &c->stage[1], &c->cand_tab, &c->cand_cnt, &c->cand_work, &c->cand_recs, &c->match_desc,
                     &c->match_cnt, &c->match_part, &c->match_out, &c->ransac_buf, &c->surf_buf, &c->orb_buf, &c->orb_pat, &c->track_buf,
-                    &c->warp_buf})
+                    &c->warp_buf, &c->cloud_buf})
     (void)b->release();
   // the fixed-size allocations of uwt_create, uwt_update_params, ensure_features and ransac_need_rows (null: nothing to free)
   for (int l = 0; l < UWT_MAX_LEVELS; l++)
@@ -1085,13 +1085,14 @@ int uwt_destroy(uwt_ctx* c) {
                   (void*)c->feat_tab, (void*)c->feat_cnt, (void*)c->feat_kp, (void*)c->feat_nkp, (void*)c->feat_recs,
                   (void*)c->ransac_need})
     (void)hipFree(p);
-  for (void* p : {(void*)c->h_small, (void*)c->h_active, (void*)c->h_pairs, (void*)c->h_feat}) (void)hipHostFree(p);
+  for (void* p : {(void*)c->h_small, (void*)c->h_active, (void*)c->h_pairs, (void*)c->h_feat, (void*)c->h_cloud}) (void)hipHostFree(p);
   auto drop = [](hipEvent_t e) { if (e) (void)hipEventDestroy(e); };
   for (hipEvent_t e : c->ev_poll) drop(e);
   for (hipEvent_t e : c->ev_feat) drop(e);
   for (hipEvent_t e : c->ev_pool) drop(e);
   for (hipEvent_t e : c->ev_join) drop(e);
   for (hipEvent_t e : c->ev_pairs) drop(e);
+  for (hipEvent_t e : c->ev_cloud) drop(e);
   for (hipEvent_t e : c->ev_level) drop(e);
   for (hipEvent_t e : {c->ev_fork, c->ev_pyramids, c->ev_side_done}) drop(e);
   for (int i = 0; i < uwt_ctx::kDeps; i++) { drop(c->busy[i].ev); drop(c->fresh[i].ev); }

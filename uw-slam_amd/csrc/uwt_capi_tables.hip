@@ -588,3 +588,19 @@ int uwt::features_device_enqueue(uwt_ctx* c, int n_pairs, float* d_poses, uwt_st
   return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, kIdentityTables, d_poses,
                                 reinterpret_cast<StatsOut*>(d_stats));
 }
+
+int uwt::candidates_level0_enqueue(uwt_ctx* c, int n, const int* d_slots, double threshold, const float4** tab, size_t* stride,
+                                   const int** counts) {
+  const LevelK& L = c->lv[0];
+  const size_t rows = (size_t)L.gw * L.gh;
+  Carve cv(kCandidatesAlign);
+  candidates_work_layout(cv, L, n);
+  int st = c->cand_tab.reserve(c, c->stream, rows * n * sizeof(float4));
+  if (!st) st = c->cand_cnt.reserve(c, c->stream, sizeof(int) * UWT_MAX_LEVELS * (size_t)n);
+  if (!st) st = c->cand_work.reserve(c, c->stream, cv.total());
+  if (st) return st;
+  *tab = (const float4*)c->cand_tab.p;
+  *stride = rows;
+  *counts = (const int*)c->cand_cnt.p;
+  return enqueue_candidates(c, 0, n, d_slots, threshold, c->cand_work.p, (float4*)c->cand_tab.p, (int*)c->cand_cnt.p);
+}

@@ -164,6 +164,14 @@ struct uwt_ctx {
   // the image warp (uwt_obtain_image_transformed, uwt_warp_image_batch*, uwt_warp_mosaic): the winner planes of every pair and, for
   // the host forms, their inputs and results — grown on use
   DevBuf warp_buf;
+  // the point-cloud map (uwt_point_cloud_batch*, uwt_point_cloud_points): the slot list, the per-block counts and their scan and, for
+  // the host forms, their inputs and results — grown on use
+  DevBuf cloud_buf;
+  // pinned staging of its slot list, a ring of kPairStages blocks of max_frames slots (as h_pairs), made on first use: the caller's
+  // list is copied before the call returns and the copy to the device never makes the host wait for the stream
+  int* h_cloud = nullptr;
+  hipEvent_t ev_cloud[kPairStages] = {};
+  int cloud_stage = 0;
   DevBuf stage[2];                      // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
   bool profiling = false;
   int spec_budget = 0;                  // speculative launching: evaluations a level gets (0: first_poll + 1); doubled when an alignment
@@ -267,6 +275,11 @@ int ransac_device_enqueue(uwt_ctx* c, int n_pairs, int cap, const uwt_ransac_par
 // runs the patch producer and the alignment from them
 int features_device_begin(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots);
 int features_device_enqueue(uwt_ctx* c, int n_pairs, float* d_poses, uwt_stats* d_stats);
+// Tracker::ObtainCandidatePoints on level 0 for the n frames of the device slot list d_slots (uwt_capi_tables.hip: the producer of the
+// batched semi-dense calls over cand_tab / cand_cnt / cand_work, grown to what the call needs), enqueued on the context stream: frame
+// f's table at *tab + f * *stride, its full count at (*counts)[f]
+int candidates_level0_enqueue(uwt_ctx* c, int n, const int* d_slots, double threshold, const float4** tab, size_t* stride,
+                              const int** counts);
 // UWT_ERR_PAIR_FAILED with the first failed pair's status in the message, or UWT_OK
 int first_failure(uwt_ctx* c, const char* what, const uwt_stats* stats, int n);
 

@@ -3496,9 +3496,8 @@ static __global__ __launch_bounds__(kBlock) void k_remap_crop(const uint8_t* __r
 // Visualizer::UpdateMessages pose accumulation (src/Visualizer.cpp:304-325): final_i = final_{i-1} * SE3(q_i, s·t_i).
 // Strictly sequential (float SE(3) products are not associative to the last bit), one lane; n is a trajectory
 // length, not a pixel count.
-static __global__ void k_trajectory(const float* __restrict__ poses, int n, Pose prev, float t_scale, int reference_axes,
-                             float* __restrict__ out) {
-  if (threadIdx.x || blockIdx.x) return;
+__device__ __forceinline__ void trajectory_walk(const float* __restrict__ poses, int n, Pose prev, float t_scale, int reference_axes,
+                                                float* __restrict__ out) {
   for (int i = 0; i < n; i++) {
     const float* p = poses + 7 * (size_t)i;
     Pose cur, fin;
@@ -3512,6 +3511,20 @@ static __global__ void k_trajectory(const float* __restrict__ poses, int n, Pose
     if (reference_axes) { o[4] = -fin.t[2]; o[5] = -fin.t[0]; o[6] = -fin.t[1]; }
     else { o[4] = fin.t[0]; o[5] = fin.t[1]; o[6] = fin.t[2]; }
   }
+}
+static __global__ void k_trajectory(const float* __restrict__ poses, int n, Pose prev, float t_scale, int reference_axes,
+                             float* __restrict__ out) {
+  if (threadIdx.x || blockIdx.x) return;
+  trajectory_walk(poses, n, prev, t_scale, reference_axes, out);
+}
+// the same behind a previous pose that is in device memory (7 floats as the accumulation stores them with reference_axes = 0)
+static __global__ void k_trajectory_from(const float* __restrict__ poses, int n, const float* __restrict__ prev7, float t_scale,
+                                  int reference_axes, float* __restrict__ out) {
+  if (threadIdx.x || blockIdx.x) return;
+  Pose prev;
+  for (int k = 0; k < 4; k++) prev.q[k] = prev7[k];
+  for (int k = 0; k < 3; k++) prev.t[k] = prev7[4 + k];
+  trajectory_walk(poses, n, prev, t_scale, reference_axes, out);
 }
 
 // The same accumulation as a prefix product (SE(3) composition is associative; in floats the grouping shows in the last

@@ -1,6 +1,6 @@
 // uwt_launch.h — internal: the launch dispatchers of the heavy kernel templates, one translation unit per family so that the
 // library builds in parallel (uwt_launch_residual.hip, uwt_launch_general.hip, uwt_launch_flow.hip, uwt_launch_points.hip; the image
-// warp's are in uwt_warpimg.h / uwt_launch_warpimg.hip).
+// warp's are in uwt_warpimg.h / uwt_launch_warpimg.hip, the point cloud's in uwt_cloud.h / uwt_launch_cloud.hip).
 // A dispatcher picks the instantiation from run-time facts (arithmetic set, depth plane, level width, intrinsics, factors) and
 // enqueues it; it reports nothing — the caller checks hipGetLastError().
 #pragma once

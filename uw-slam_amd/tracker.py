@@ -292,6 +292,61 @@ class Tracker:
         r = self._ctx.warp_image_batch([s[0] for s in slots], [s[1] for s in slots], poses, lvl=lvl, absdiff=False)
         return r["warped"], r["valid"], r["quality"]
 
+    def PointCloudBatch(self, frames, traj, params=None):
+        """Visualizer::AddPointCloudFromRGBD for a list of frames under the accumulated poses `traj` ([F, 7]) in one call
+        (uwt_point_cloud_batch): returns (points capi.CLOUD_POINT in frame order and, inside a frame, in row order; info [F]
+        capi.CLOUD_INFO; the call's record).  params None: the reference's call (the dense level-0 table, every 100th row)."""
+        params = capi.default_cloud_params() if params is None else params
+        slots = [self._bind(f) for f in frames]
+        for f, s in zip(frames, slots):   # binding a later frame may have taken an earlier frame's slot
+            if f._slot != s:
+                raise RuntimeError("PointCloudBatch: more frames than slots (max_frames)")
+            if params.source == 1 and not f.obtained_gradients_:
+                raise RuntimeError("PointCloudBatch: the candidate source needs ApplyGradient (or the frame's slot was reused since)")
+        r = self._ctx.point_cloud_batch(slots, traj, params)
+        return r["points"], r["info"], r["call"]
+
+
+class Map:
+    """include/Map.h — Map::AddPointCloudFromRGBD (src/Map.cpp:33-45): recent_cloud_points_ is the x y z columns of the frame's
+    level-0 candidatePoints_; PointCloudBatch: the tracker's batch call."""
+
+    def __init__(self, tracker=None):
+        self._tracker = tracker
+        self.recent_cloud_points_ = np.zeros((0, 3), np.float32)
+
+    def AddPointCloudFromRGBD(self, frame):
+        if 0 not in frame.candidatePoints_:   # the dense ObtainAllPoints keeps no table
+            raise RuntimeError("Map.AddPointCloudFromRGBD: the frame has no level-0 candidatePoints_")
+        self.recent_cloud_points_ = np.asarray(frame.candidatePoints_[0], np.float32).reshape(-1, 4)[:, :3]   # a view, N x 3
+
+    def PointCloudBatch(self, frames, traj, params=None):
+        return self._tracker.PointCloudBatch(frames, traj, params)
+
+
+class Visualizer:
+    """The map-building part of include/Visualizer.h — Visualizer::AddPointCloudFromRGBD (src/Visualizer.cpp:421-446) on the device:
+    every 100th row of the frame's level-0 table (its candidatePoints_[0] when a sparse producer ran, else ObtainAllPoints' dense
+    table of the bound frame), unprojected and offset by previous_pose's translation, appended to point_cloud_.  previous_pose is
+    the accumulation UpdateMessages keeps (accumulate_trajectory with t_scale 40, reference_axes False); the tags count the calls."""
+
+    def __init__(self, tracker):
+        self._tracker = tracker
+        self.point_cloud_ = np.zeros(0, capi.CLOUD_POINT)
+        self.previous_pose_ = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)
+        self._n_calls = 0
+
+    def AddPointCloudFromRGBD(self, frame, previous_pose):
+        self.previous_pose_ = np.array(previous_pose, np.float32).reshape(7)
+        if 0 in frame.candidatePoints_:
+            rec = self._tracker._ctx.point_cloud_points(self._tracker._bind(frame), frame.candidatePoints_[0], self.previous_pose_)[0]
+        else:
+            rec = self._tracker.PointCloudBatch([frame], self.previous_pose_[None])[0]
+        rec = rec.copy()
+        rec["tag"] = (rec["tag"] & 255) | np.uint32(self._n_calls << 8)
+        self._n_calls += 1
+        self.point_cloud_ = np.concatenate([self.point_cloud_, rec])
+
 
 class RobustMatcher:
     """include/Tracker.h:65-88 — the matching half of RobustMatcher::DetectAndTrackFeatures (src/Tracker.cpp:171-258): knnMatch in

@@ -1,6 +1,6 @@
 """Trajectory I/O next to the tracking path: the reference visualiser's 14-column CSV
 (src/Visualizer.cpp:386-400), TUM-format trajectory files, and the two ground-truth readers
-(ReadGroundTruthTUM / ReadGroundTruthEUROC, src/Visualizer.cpp:449-505).  The pose accumulation itself
+(ReadGroundTruthTUM / ReadGroundTruthEUROC, src/Visualizer.cpp:449-505), and PLY files of the point-cloud map.  The pose accumulation itself
 (Visualizer::UpdateMessages, :304-325) runs in the library: Context.accumulate_trajectory / uwt_accumulate_trajectory.
 """
 import numpy as np
@@ -30,6 +30,50 @@ def write_tum(path, timestamps, traj):
     with open(path, "w") as f:
         for t, p in zip(timestamps, traj):
             f.write("%.6f %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n" % (t, p[4], p[5], p[6], p[0], p[1], p[2], p[3]))
+
+
+PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "u1")])
+
+
+def write_ply(path, points, binary=True):
+    """A point cloud as a PLY file with x y z (float) and a grey `intensity` (uchar) per vertex, binary little-endian or ASCII.
+    points: uwt_cloud_point records (capi.CLOUD_POINT: the intensity is the low byte of the tag) or an n x 3 / n x 4 array (x y z
+    [intensity])."""
+    points = np.asarray(points)
+    v = np.zeros(points.shape[0], PLY_VERTEX)
+    if points.dtype.names:
+        v["x"], v["y"], v["z"] = points["x"], points["y"], points["z"]
+        v["intensity"] = (points["tag"] & 255).astype(np.uint8)
+    else:
+        pts = points.reshape(-1, points.shape[-1])
+        v["x"], v["y"], v["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+        if pts.shape[1] > 3:
+            v["intensity"] = pts[:, 3].astype(np.uint8)
+    header = ("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar intensity\nend_header\n" % ("binary_little_endian" if binary else "ascii", v.size))
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        if binary:
+            f.write(v.tobytes())
+        else:
+            for r in v:   # %.9g: a float32 survives the round trip
+                f.write(("%.9g %.9g %.9g %d\n" % (r["x"], r["y"], r["z"], r["intensity"])).encode("ascii"))
+
+
+def read_ply(path):
+    """Reads what write_ply wrote: a PLY_VERTEX array"""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii").split("\n")
+    n = int([l for l in head if l.startswith("element vertex")][0].split()[2])
+    if any(l.startswith("format binary_little_endian") for l in head):
+        return np.frombuffer(data[end:end + n * PLY_VERTEX.itemsize], PLY_VERTEX).copy()
+    v = np.zeros(n, PLY_VERTEX)
+    for i, line in enumerate(data[end:].decode("ascii").split("\n")[:n]):
+        x, y, z, g = line.split()
+        v[i] = (np.float32(x), np.float32(y), np.float32(z), int(g))
+    return v
 
 
 def read_groundtruth_tum(path):
