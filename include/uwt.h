@@ -222,6 +222,15 @@ int uwt_apply_gradient(uwt_ctx* ctx, int32_t first_slot, int32_t n);
 int uwt_estimate_pose_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
                             float* poses_out, uwt_stats* stats_out_or_null);
 
+/* Alignment of device pointers.  Every pointer to DEVICE memory an entry point takes must be aligned to the widest access a kernel
+ * makes through it, stated at the entry ("alignment:"), and needs no more than that: a buffer may start anywhere such a multiple falls,
+ * e.g. inside a larger allocation of the caller's.  In short: 4 bytes for poses (rows of 7 floats), uwt_stats, uwt_keypoint, uwt_match,
+ * uwt_tracking_info, counts and the u8 planes of uwt_warp_image_io (written four pixels at a time); 1 byte for the RANSAC mask; 8 bytes
+ * for the records that hold 64-bit fields (uwt_ransac_info, uwt_warp_quality, uwt_cloud_info); 16 bytes for uwt_cloud_point (one
+ * 16-byte store per point) and for the descriptor sets uwt_match_descriptors_device_async reads (16-byte loads).  No entry point
+ * writes or reads outside the extents it documents: not a row past the last pair's cap, not a pose past n_pairs, not a record past a
+ * cloud's cap; and no result depends on bytes outside those extents or on the rows past a count (tests/test_gpu_guard_bands.py). */
+
 /* Whole per-frame path for a resident batch: pyramids of slots [first_slot, first_slot+n_frames), gradients of
  * the same slots, then EstimatePose for the pairs — enqueued on the context stream, results written to DEVICE
  * memory (d_poses_out: n_pairs x 7 floats, d_stats_out_or_null: n_pairs uwt_stats).  uwt_sync() to wait.
@@ -235,7 +244,8 @@ int uwt_estimate_pose_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_sl
  * look taken while the next evaluation already runs — and stops launching for a level every pair has left; smaller levels
  * decide on the device), so it returns only once the last level's first iterations are queued.
  * Ordering against uwt_upload_frames_async covers every slot the call touches: the prepared range AND every slot the pair
- * lists name (they may lie outside the range). */
+ * lists name (they may lie outside the range).
+ * alignment: d_poses_out 4 bytes, d_stats_out_or_null 4 bytes. */
 int uwt_track_batch_async(uwt_ctx* ctx, int32_t first_slot, int32_t n_frames, int32_t grad_refs_only,
                           int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
                           float* d_poses_out, uwt_stats* d_stats_out_or_null);
@@ -389,7 +399,8 @@ int uwt_obtain_patch_points_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t*
  * never leave the device: one producer launch, then one launch per Gauss-Newton evaluation with the update in its tail.
  * A pair's pose does not depend on the batch it runs in.  The caller may reuse every host array once the call returns.
  * Results go to DEVICE memory, as in uwt_track_batch_async (d_poses_out: n_pairs x 7 floats, d_stats_out_or_null: n_pairs
- * uwt_stats), ordered against uwt_upload_frames_async like it.  The call never waits for the device; uwt_sync() to wait. */
+ * uwt_stats), ordered against uwt_upload_frames_async like it.  The call never waits for the device; uwt_sync() to wait.
+ * alignment: d_poses_out 4 bytes, d_stats_out_or_null 4 bytes (the same in the _opt form). */
 int uwt_track_features_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
                                    const float* keypoints_xy, const int32_t* n_keypoints,
                                    float* d_poses_out, uwt_stats* d_stats_out_or_null);
@@ -455,7 +466,8 @@ int uwt_estimate_pose_features_batch_opt(uwt_ctx* ctx, int32_t n_pairs, const in
  * uwt_stats), ordered against uwt_upload_frames_async like it.  With early_exit = 0 the call never waits for the device.  With
  * early_exit = 1 it waits at the early-exit polls as uwt_track_batch_async does (after evaluations first_poll, then twice as
  * many, ..., of each level, each look taken while the next evaluation runs; no launch for a level once every pair has left
- * it).  uwt_sync() to wait for the results. */
+ * it).  uwt_sync() to wait for the results.
+ * alignment: d_poses_out 4 bytes, d_stats_out_or_null 4 bytes (the same in the _opt form). */
 int uwt_track_candidates_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
                                      double threshold, float* d_poses_out, uwt_stats* d_stats_out_or_null);
 /* The same, synchronous, results in host memory (UWT_ERR_PAIR_FAILED when a pair failed, its status in its uwt_stats). */
@@ -534,7 +546,8 @@ int uwt_match_descriptors_batch(uwt_ctx* ctx, int32_t n_pairs, int32_t norm, int
 /* The same without waiting: results in DEVICE memory (d_matches_out: n_pairs x cap uwt_match, d_counts_out: n_pairs), on the
  * context's stream; uwt_sync() to wait.  Host arrays from uwt_host_alloc are read when the copy runs and must stay untouched until
  * then; any other host array may be reused once the call returns (the runtime has staged it).  The context's scratch is reused by
- * the next matching call, which the stream orders behind this one. */
+ * the next matching call, which the stream orders behind this one.
+ * alignment: d_matches_out 4 bytes, d_counts_out 4 bytes. */
 int uwt_match_descriptors_batch_async(uwt_ctx* ctx, int32_t n_pairs, int32_t norm, int32_t dim, const void* query,
                                       const int32_t* n_query, const void* train, const int32_t* n_train, int32_t cap, float ratio,
                                       uwt_match* d_matches_out, int32_t* d_counts_out);
@@ -614,7 +627,8 @@ int uwt_ransac_inliers_batch(uwt_ctx* ctx, int32_t n_pairs, const uwt_match* mat
  * host arrays, staged as in uwt_match_descriptors_batch_async.  The match indices cannot be checked on the host: the kernel checks
  * them, and a pair with an index outside its key-point count (or a match count outside 0..cap) gets UWT_ERR_INVALID_ARG in its
  * own info.status and no inliers; the other pairs are unaffected.  need(k) is not known per pair on the host here: the context
- * builds it for every N up to cap the first time these parameters are used (cap * cap / 2 logarithms, once). */
+ * builds it for every N up to cap the first time these parameters are used (cap * cap / 2 logarithms, once).
+ * alignment: d_matches 4 bytes, d_n_matches 4, d_mask_out 1 (byte stores), d_good_out 4, d_counts_out 4, d_info_out 8 (it holds doubles). */
 int uwt_ransac_inliers_batch_async(uwt_ctx* ctx, int32_t n_pairs, const uwt_match* d_matches, const int32_t* d_n_matches,
                                    int32_t cap, const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur,
                                    const int32_t* n_kp_cur, int32_t kp_cap, const uwt_ransac_params* params, uint8_t* d_mask_out,
@@ -729,7 +743,10 @@ double uwt_keypoint_angle_deg(float dir_x, float dir_y);
 int uwt_surf_detect_describe_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_surf_params* params_or_null,
                                    int32_t cap, uwt_keypoint* kp_out, float* desc_out_or_null, int32_t* counts_out);
 /* The same without waiting: results in DEVICE memory (d_kp_out: n_frames x cap, d_desc_out_or_null: n_frames x cap x 64,
- * d_counts_out: n_frames) on the context's stream, ordered against uwt_upload_frames_async; uwt_sync() to wait. */
+ * d_counts_out: n_frames) on the context's stream, ordered against uwt_upload_frames_async; uwt_sync() to wait.  As in the host form, the
+ * rows past a frame's count are not written: they keep what they held.
+ * alignment: d_kp_out 4 bytes, d_desc_out_or_null 4 bytes (a set that goes on to uwt_match_descriptors_device_async needs its 16),
+ * d_counts_out 4 bytes. */
 int uwt_surf_detect_describe_batch_async(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_surf_params* params_or_null,
                                          int32_t cap, uwt_keypoint* d_kp_out, float* d_desc_out_or_null, int32_t* d_counts_out);
 /* useProvidedKeypoints (src/Tracker.cpp:192-195): orientation and descriptors at the caller's key points.  keypoints_in: n_frames x
@@ -843,7 +860,10 @@ int uwt_orb_set_pattern(uwt_ctx* ctx, const int8_t* pattern_1024_or_null);
 int uwt_orb_detect_describe_batch(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params_or_null,
                                   int32_t cap, uwt_keypoint* kp_out, uint8_t* desc_out_or_null, int32_t* counts_out);
 /* The same without waiting: results in DEVICE memory (d_kp_out: n_frames x cap, d_desc_out_or_null: n_frames x cap x 32,
- * d_counts_out: n_frames) on the context's stream, ordered against uwt_upload_frames_async; uwt_sync() to wait. */
+ * d_counts_out: n_frames) on the context's stream, ordered against uwt_upload_frames_async; uwt_sync() to wait.  As in the host form, the
+ * rows past a frame's count are not written: they keep what they held.
+ * alignment: d_kp_out 4 bytes, d_desc_out_or_null 4 bytes (a set that goes on to uwt_match_descriptors_device_async needs its 16),
+ * d_counts_out 4 bytes. */
 int uwt_orb_detect_describe_batch_async(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const uwt_orb_params* params_or_null,
                                         int32_t cap, uwt_keypoint* d_kp_out, uint8_t* d_desc_out_or_null, int32_t* d_counts_out);
 /* useProvidedKeypoints: direction and descriptors at the caller's key points.  keypoints_in: n_frames x cap records, frame f's
@@ -914,7 +934,7 @@ typedef struct uwt_tracking_info {   /* per pair, 32 bytes */
   int32_t best_hypothesis, hypotheses_run;   /* of uwt_ransac_info */
 } uwt_tracking_info;
 
-typedef struct uwt_tracking_io {     /* every pointer is DEVICE memory */
+typedef struct uwt_tracking_io {     /* every pointer is DEVICE memory, 4-byte aligned (no record here holds a wider field) */
   const uwt_keypoint* d_prev_kp;     /* in, may be null: n_pairs x cap, what the previous frame kept */
   const int32_t*      d_n_prev;      /* in, null iff d_prev_kp is: n_pairs counts */
   float*              d_poses;       /* out: n_pairs x 7 */
@@ -979,7 +999,9 @@ int uwt_tracking_orb_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slo
  * cap x dim elements, d_n_query / d_n_train: n_pairs), read in place: nothing is uploaded.  The launch is bounded by cap instead of
  * the counts (blocks past a pair's counts return at once; the merge of the train parts is exact, so the different cut shows in no
  * bit): the results are those of uwt_match_descriptors_batch.  A device count outside 0..cap is taken as 0: that pair has count 0.
- * Host-side errors as there (the counts cannot be checked on the host). */
+ * Host-side errors as there (the counts cannot be checked on the host).
+ * alignment: d_query and d_train 16 bytes (rows that are a multiple of 16 bytes long — every L2 row, Hamming rows of 16, 32, ... bytes —
+ * are read with 16-byte loads; other rows a 32-bit word at a time); d_n_query, d_n_train, d_matches_out and d_counts_out 4 bytes. */
 int uwt_match_descriptors_device_async(uwt_ctx* ctx, int32_t n_pairs, int32_t norm, int32_t dim, const void* d_query,
                                        const int32_t* d_n_query, const void* d_train, const int32_t* d_n_train, int32_t cap, float ratio,
                                        uwt_match* d_matches_out, int32_t* d_counts_out);
@@ -1022,7 +1044,7 @@ typedef struct uwt_warp_image_io {   /* every pointer is DEVICE memory, 4-byte a
   uint8_t*          d_warped;        /* out, may be null: image1 in image2's view; 0 where no row landed */
   uint8_t*          d_valid;         /* out, may be null: 1 where a row landed */
   uint8_t*          d_absdiff;       /* out, may be null: |warped - image2| where a row landed, else 0 */
-  uwt_warp_quality* d_quality;       /* out, required: n_pairs records */
+  uwt_warp_quality* d_quality;       /* out, required: n_pairs records; 8-byte aligned (64-bit sums) */
 } uwt_warp_image_io;
 
 /* The reference's signature on host arrays for one frame: original = the image plane of `slot` at `lvl` (resident, pyramids built),
@@ -1041,7 +1063,8 @@ int uwt_obtain_image_transformed(uwt_ctx* ctx, int32_t slot, int32_t lvl, const 
  * stream, ordered against uwt_upload_frames_async as the other batch calls are; uwt_sync() to wait.
  * UWT_ERR_INVALID_ARG with nothing enqueued and the outputs untouched: a null list, a null d_poses, io or d_quality, n_pairs outside
  * 1..max_pairs, a slot or level out of range.  A pose with a non-finite entry puts UWT_ERR_INVALID_ARG into that pair's status with all
- * counts 0 and its planes zero; its neighbours are untouched. */
+ * counts 0 and its planes zero; its neighbours are untouched.
+ * alignment: d_poses 4 bytes; io: at uwt_warp_image_io (planes 4 bytes, d_quality 8). */
 int uwt_warp_image_batch_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, int32_t lvl,
                                const float* d_poses, const uwt_warp_image_io* io);
 /* The same, synchronous, HOST in and out: poses n_pairs x 7; warped_out / valid_out / absdiff_out n_pairs x img_w x img_h u8, tight,
@@ -1118,7 +1141,8 @@ int uwt_default_cloud_params(uwt_cloud_params* params);
  * (uwt_sync() to wait).  1 <= n_frames <= max_frames (and <= 65535).
  * UWT_ERR_INVALID_ARG with nothing enqueued and the outputs untouched: a null argument (d_points_out may be null with cap 0), cap < 0, n_frames
  * out of range, a slot out of range, a mode or source outside 0..1, skip_invalid outside 0..1, stride < 1, a non-zero reserved word, a
- * non-finite threshold. */
+ * non-finite threshold.
+ * alignment: d_traj 4 bytes, d_points_out 16 bytes (one 16-byte store per point), d_info_out 8 bytes (64-bit fields). */
 int uwt_point_cloud_batch_async(uwt_ctx* ctx, int32_t n_frames, const int32_t* slots, const float* d_traj, const uwt_cloud_params* params,
                                 uwt_cloud_point* d_points_out, int64_t cap, uwt_cloud_info* d_info_out);
 /* The same, synchronous, HOST arrays: traj n_frames x 7, points_out cap records (those below the call's `written` are delivered),
@@ -1172,7 +1196,8 @@ int uwt_accumulate_trajectory_scan(uwt_ctx* ctx, const float* poses, int32_t n, 
  * context's stream, no copy and no wait, the results bit for bit the same.  d_poses may be uwt_tracking_io::d_poses of a call enqueued
  * before and d_traj_out the d_traj of uwt_point_cloud_batch_async enqueued behind: tracking -> trajectory -> cloud with one uwt_sync()
  * at the end.  n = 0: nothing is enqueued.  start_pose: host.  d_poses and d_traj_out must not overlap (the kernel reads and writes
- * through restrict pointers; accumulating in place is refused): UWT_ERR_INVALID_ARG with nothing enqueued. */
+ * through restrict pointers; accumulating in place is refused): UWT_ERR_INVALID_ARG with nothing enqueued.
+ * alignment: d_poses and d_traj_out 4 bytes (and d_start_pose of the form below). */
 int uwt_accumulate_trajectory_device_async(uwt_ctx* ctx, const float* d_poses, int32_t n, const float start_pose[7], float t_scale,
                                            int32_t reference_axes, float* d_traj_out);
 /* The same behind a previous pose that is in DEVICE memory: d_start_pose, 7 floats as an accumulation with reference_axes = 0 stores
@@ -1181,6 +1206,27 @@ int uwt_accumulate_trajectory_device_async(uwt_ctx* ctx, const float* d_poses, i
  * overlap neither d_poses nor d_start_pose: UWT_ERR_INVALID_ARG with nothing enqueued. */
 int uwt_accumulate_trajectory_device_from_async(uwt_ctx* ctx, const float* d_poses, int32_t n, const float* d_start_pose, float t_scale,
                                                 int32_t reference_axes, float* d_traj_out);
+
+/* ---- test instrumentation: guards inside the context's own scratch ------------------------------------------------------------ */
+
+/* Not part of the tracker: these two serve tests/test_gpu_guard_bands.py, which uses them to see whether a kernel writes outside an
+ * array of the context's growable scratch (the staging of every synchronous entry point and the work areas of the asynchronous ones:
+ * one block per stage, cut into arrays).  No reference counterpart.
+ * uwt_debug_guards(ctx, guard_bytes): waits for everything the context has enqueued, releases every growable block (each is made again
+ * on its next use, like any growth) and, for guard_bytes > 0, makes every such block from then on with a gap of guard_bytes (rounded
+ * up to the array alignment of the stage) behind EVERY array, one in front of the first and one behind the last; each use of a block
+ * fills its gaps with a byte pattern on the context's stream.  0 (the default of a new context) turns the guards off again: offsets,
+ * sizes and launches are then exactly those of a context that never had them.  Results do not depend on the setting.  guard_bytes
+ * outside 0..2^24: UWT_ERR_INVALID_ARG.
+ *   - Only the gaps carry the pattern; the arrays are never filled.  A pattern in scratch that a latent error reads as an index or a
+ *     count could turn a silent error into a wild access; the gaps are read by no correct code, so what they hold cannot matter.
+ *   - The allocations uwt_create makes once (planes, pair state, histograms, the live call's tables) are outside this.
+ * uwt_debug_check_guards(ctx, damaged_bytes_out): waits for the context's streams, compares every gap recorded by the last use of
+ * every block, and returns UWT_OK with *damaged_bytes_out = the number of damaged bytes (0: none).  On damage uwt_last_error names the
+ * stage's block, the index of the array in front of the first damaged gap (-1: the gap in front of the first array) and the first
+ * damaged byte's offset in that gap. */
+int uwt_debug_guards(uwt_ctx* ctx, int64_t guard_bytes);
+int uwt_debug_check_guards(uwt_ctx* ctx, int64_t* damaged_bytes_out);
 
 #ifdef __cplusplus
 }

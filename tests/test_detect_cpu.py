@@ -25,6 +25,13 @@ int main(int argc, char** argv) {
   uwt::Carve cv(16);
   const size_t a = cv.take<int>(3), b = cv.take<uint8_t>(17), c = cv.take<double>(0), d = cv.take<unsigned long long>(2);
   std::printf("%zu %zu %zu %zu %zu %zu\n", a, b, c, d, cv.tight(), cv.total());
+  uwt::Carve g(16, 100);   // the same with guards (uwt_debug_guards): a gap of 100 bytes, rounded up to the alignment, behind every array
+  const size_t ga = g.take<int>(3), gb = g.take<uint8_t>(17);
+  g.align = 64;
+  const size_t gc = g.take<double>(2);
+  std::printf("%zu %zu %zu %zu %zu", ga, gb, gc, g.tight(), g.total());
+  for (const uwt::GuardGap& q : g.gaps) std::printf(" %lld %zu %d", q.at, q.bytes, q.array);
+  std::printf("\n");
   return 0;
 }
 '''
@@ -42,6 +49,7 @@ def ask(tmp_path_factory):
         out = subprocess.run([str(exe)] + [str(v) for c in cases for v in c], check=True, capture_output=True, text=True).stdout.split("\n")
         budget, grid = (int(v) for v in out[0].split())
         n = len(cases)
+        run.guarded = [int(v) for v in out[3 + n].split()]
         return budget, grid, [int(v) for v in out[1:1 + n]], [int(v) for v in out[1 + n].split()], [int(v) for v in out[2 + n].split()]
     return run
 
@@ -66,3 +74,12 @@ def test_rows_rule_and_carving(ask):
     a, b, c, d, tight, total = carve
     assert (a, b, c, d) == (0, 16, 48, 48)     # each array on the next multiple of 16 behind the one before; an empty one takes none
     assert tight == 64 and total == 64
+
+
+def test_carving_with_guards(ask):
+    """a gap behind every array, from the array's last byte to the next array (the pad in front of it included), each at least the
+    guard rounded up to the alignment in force; the arrays keep their alignment; the last gap ends the block"""
+    ask([])
+    a, b, c, tight, total, *gaps = ask.guarded
+    assert (a, b, c) == (0, 128, 320) and tight == total == 512
+    assert gaps == [12, 116, 0, 145, 175, 1, 336, 176, 2]   # (offset, bytes, the array in front) x 3

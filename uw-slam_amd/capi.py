@@ -165,6 +165,7 @@ SYMBOLS = [
     "uwt_obtain_image_transformed", "uwt_warp_image_batch_async", "uwt_warp_image_batch", "uwt_warp_mosaic",
     "uwt_default_cloud_params", "uwt_point_cloud_batch_async", "uwt_point_cloud_batch", "uwt_point_cloud_points",
     "uwt_accumulate_trajectory_device_async", "uwt_accumulate_trajectory_device_from_async",
+    "uwt_debug_guards", "uwt_debug_check_guards",
 ]
 
 _lib = None
@@ -435,6 +436,18 @@ class Context:
         if st and st not in allow:
             raise UwtError(st, lib().uwt_last_error(self._h).decode())
         return st
+
+    def debug_guards(self, guard_bytes):
+        """Test instrumentation (uwt_debug_guards): guard gaps of guard_bytes around and inside every growable scratch block of the
+        context from now on; 0 turns them off.  Waits for the context's work and releases the blocks."""
+        self._chk(lib().uwt_debug_guards(self._h, C.c_int64(int(guard_bytes))))
+
+    def debug_check_guards(self):
+        """(damaged bytes, the library's description of the first damaged gap or "") over the gaps of every block's last use
+        (uwt_debug_check_guards)"""
+        n = C.c_int64(-1)
+        self._chk(lib().uwt_debug_check_guards(self._h, C.byref(n)))
+        return int(n.value), (lib().uwt_last_error(self._h).decode() if n.value else "")
 
     def update_params(self, **over):
         """Change solver constants of the live context (uwt_update_params)."""

@@ -615,17 +615,50 @@ int first_failure(uwt_ctx* c, const char* what, const uwt_stats* stats, int n) {
 
 
 hipError_t DevBuf::release() {
-  const hipError_t e = p ? hipFree(p) : hipSuccess;
-  p = nullptr, bytes = 0;
+  const hipError_t e = block ? hipFree(block) : hipSuccess;
+  p = block = nullptr, bytes = 0;
+  gaps.clear();
   return e;
 }
 
-int DevBuf::reserve(uwt_ctx* c, hipStream_t stream, size_t want) {
-  if (want <= bytes) return UWT_OK;
-  if (p) HIPCHK(c, hipStreamSynchronize(stream));
-  HIPCHK(c, release());
-  HIPCHK(c, hipMalloc(&p, want));
-  bytes = want;
+// With guards (uwt_ctx::guard_bytes): [lead | want bytes, the carve's gaps inside | tail], p behind the lead — a multiple of 256, so p
+// is aligned as hipMalloc's blocks are; a carve's last gap is its tail.  The gaps are those of THIS use, filled on every use.  A block
+// serves carved and plain uses in turn (the shared scratch), so EVERY block is allocated with room for a tail behind `bytes`: a later
+// plain use of up to `bytes` finds its tail gap inside the allocation whatever made the block.
+int DevBuf::reserve(uwt_ctx* c, hipStream_t stream, size_t want, const Carve* cv) {
+  const size_t g = c->guard_bytes, lead = (g + 255) & ~(size_t)255, tail = g && !(cv && cv->guard) ? g : 0;
+  if (want > bytes || (g && !block)) {
+    if (block) HIPCHK(c, hipStreamSynchronize(stream));
+    HIPCHK(c, release());
+    HIPCHK(c, hipMalloc(&block, lead + want + g));
+    p = static_cast<unsigned char*>(block) + lead;
+    bytes = want;
+  }
+  if (!g) return UWT_OK;
+  gaps.clear();
+  gaps.push_back({-(long long)lead, lead, -1});
+  if (cv && cv->guard) gaps.insert(gaps.end(), cv->gaps.begin(), cv->gaps.end());
+  else gaps.push_back({(long long)want, tail, 0});
+  for (const GuardGap& gap : gaps) {
+    if (gap.at + (long long)gap.bytes > (long long)(bytes + g)) return fail(c, UWT_ERR_INVALID_ARG, "DevBuf::reserve: a guard gap outside its block");
+    if (gap.bytes) HIPCHK(c, hipMemsetAsync(static_cast<unsigned char*>(p) + gap.at, kGuardPattern, gap.bytes, stream));
+  }
+  return UWT_OK;
+}
+
+int DevBuf::reserve(uwt_ctx* c, hipStream_t stream, const Carve& cv) { return reserve(c, stream, cv.total(), &cv); }
+int DevBuf::reserve(uwt_ctx* c, hipStream_t stream, const Carve& cv, size_t want) { return reserve(c, stream, want, &cv); }
+
+int DevBuf::adopt(uwt_ctx* c, hipStream_t stream, const Carve& inner, const void* base) {
+  const long long shift = static_cast<const unsigned char*>(base) - static_cast<const unsigned char*>(p);
+  for (GuardGap gap : inner.gaps) {
+    gap.at += shift;
+    gap.array += 1000;   // (told apart from the block's own arrays in a report)
+    if (gap.at < 0 || gap.at + (long long)gap.bytes > (long long)(bytes + c->guard_bytes))
+      return fail(c, UWT_ERR_INVALID_ARG, "DevBuf::adopt: a guard gap outside its block");
+    gaps.push_back(gap);
+    if (gap.bytes) HIPCHK(c, hipMemsetAsync(static_cast<unsigned char*>(p) + gap.at, kGuardPattern, gap.bytes, stream));
+  }
   return UWT_OK;
 }
 
@@ -1065,18 +1098,69 @@ int uwt_create(const uwt_params* p, uwt_ctx** out) {
   return UWT_OK;
 }
 
-int uwt_destroy(uwt_ctx* c) {
-  if (!c) return UWT_ERR_INVALID_ARG;
-  (void)hipSetDevice(c->p.device);
+extern "C++" {
+// every buffer of the context that grows on use, by the name uwt_debug_check_guards reports
+struct NamedBuf { const char* name; DevBuf* b; };
+static std::vector<NamedBuf> growable(uwt_ctx* c) {
+  return {{"scratch", &c->scratch}, {"stage[0]", &c->stage[0]}, {"stage[1]", &c->stage[1]}, {"cand_tab", &c->cand_tab},
+          {"cand_cnt", &c->cand_cnt}, {"cand_work", &c->cand_work}, {"cand_recs", &c->cand_recs}, {"match_desc", &c->match_desc},
+          {"match_cnt", &c->match_cnt}, {"match_part", &c->match_part}, {"match_out", &c->match_out}, {"ransac_buf", &c->ransac_buf},
+          {"surf_buf", &c->surf_buf}, {"orb_buf", &c->orb_buf}, {"orb_pat", &c->orb_pat}, {"track_buf", &c->track_buf},
+          {"warp_buf", &c->warp_buf}, {"cloud_buf", &c->cloud_buf}};
+}
+
+static void drain_streams(uwt_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->side) (void)hipStreamSynchronize(c->side);  // an aborted uwt_track_batch_async may have left work there
   if (c->copy) (void)hipStreamSynchronize(c->copy);
   for (int i = 1; i < uwt_ctx::kMaxParts; i++)
     if (c->part_stream[i]) (void)hipStreamSynchronize(c->part_stream[i]);
-  for (DevBuf* b : {&c->scratch, &c->stage[0], &c->stage[1], &c->cand_tab, &c->cand_cnt, &c->cand_work, &c->cand_recs, &c->match_desc,
-                    &c->match_cnt, &c->match_part, &c->match_out, &c->ransac_buf, &c->surf_buf, &c->orb_buf, &c->orb_pat, &c->track_buf,
-                    &c->warp_buf, &c->cloud_buf})
-    (void)b->release();
+}
+
+}  // extern "C++"
+
+int uwt_debug_guards(uwt_ctx* c, int64_t guard_bytes) {
+  if (!c) return UWT_ERR_INVALID_ARG;
+  if (guard_bytes < 0 || guard_bytes > (1ll << 24)) return fail(c, UWT_ERR_INVALID_ARG, "uwt_debug_guards: guard_bytes outside 0..2^24");
+  (void)hipSetDevice(c->p.device);
+  drain_streams(c);
+  for (const NamedBuf& nb : growable(c)) HIPCHK(c, nb.b->release());
+  if (c->orb_pattern_state == 2) c->orb_pattern_state = 1;   // the device copy of the pattern went with orb_pat: the next ORB call sends it
+  c->guard_bytes = (size_t)guard_bytes;
+  return UWT_OK;
+}
+
+int uwt_debug_check_guards(uwt_ctx* c, int64_t* damaged_bytes_out) {
+  if (!c || !damaged_bytes_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_debug_check_guards: null argument");
+  (void)hipSetDevice(c->p.device);
+  drain_streams(c);
+  long long damaged = 0;
+  std::string first;
+  std::vector<unsigned char> host;
+  for (const NamedBuf& nb : growable(c))
+    for (const GuardGap& gap : nb.b->gaps) {
+      if (!gap.bytes) continue;
+      host.resize(gap.bytes);
+      HIPCHK(c, hipMemcpy(host.data(), static_cast<unsigned char*>(nb.b->p) + gap.at, gap.bytes, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < gap.bytes; i++)
+        if (host[i] != kGuardPattern) {
+          if (!damaged)
+            first = std::string("uwt_debug_check_guards: ") + nb.name + ": the gap behind array " + std::to_string(gap.array) +
+                    " is damaged from its byte " + std::to_string(i) + " on (the gap: " + std::to_string(gap.bytes) + " bytes at offset " +
+                    std::to_string(gap.at) + ")";
+          damaged++;
+        }
+    }
+  *damaged_bytes_out = damaged;
+  if (damaged) c->last_error = first;
+  return UWT_OK;
+}
+
+int uwt_destroy(uwt_ctx* c) {
+  if (!c) return UWT_ERR_INVALID_ARG;
+  (void)hipSetDevice(c->p.device);
+  drain_streams(c);
+  for (const NamedBuf& nb : growable(c)) (void)nb.b->release();
   // the fixed-size allocations of uwt_create, uwt_update_params, ensure_features and ransac_need_rows (null: nothing to free)
   for (int l = 0; l < UWT_MAX_LEVELS; l++)
     for (void* p : {(void*)c->img[l], (void*)c->depth[l], (void*)c->gx[l], (void*)c->gy[l]}) (void)hipFree(p);

@@ -138,9 +138,9 @@ int uwt_point_cloud_batch_async(uwt_ctx* c, int32_t n_frames, const int32_t* slo
   if (!d_traj || !d_info_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_point_cloud_batch_async: null argument");
   int st = cloud_batch_check(c, "uwt_point_cloud_batch_async", n_frames, slots, params, d_points_out, cap);
   if (st) return st;
-  Carve cv(256);
+  Carve cv(256, c->guard_bytes);
   const CloudWork w = cloud_work_layout(cv, c->lv[0].gw * c->lv[0].gh, params->stride, n_frames);
-  st = c->cloud_buf.reserve(c, c->stream, cv.total());
+  st = c->cloud_buf.reserve(c, c->stream, cv);
   if (st) return st;
   return cloud_batch_enqueue(c, n_frames, slots, d_traj, *params, w, d_points_out, cap, d_info_out);
 }
@@ -154,11 +154,11 @@ int uwt_point_cloud_batch(uwt_ctx* c, int32_t n_frames, const int32_t* slots, co
   if (st) return st;
   const int rows = c->lv[0].gw * c->lv[0].gh;
   const int64_t room = std::min<int64_t>(cap, (int64_t)n_frames * ((rows - 1) / params->stride + 1));   // records the call can write at most
-  Carve cv(256);   // [the work area | poses | records | the cloud]
+  Carve cv(256, c->guard_bytes);   // [the work area | poses | records | the cloud]
   const CloudWork w = cloud_work_layout(cv, rows, params->stride, n_frames);
   const size_t o_traj = cv.take<float>(7 * (size_t)n_frames), o_info = cv.take<uwt_cloud_info>((size_t)n_frames + 1),
                o_pts = cv.take<uwt_cloud_point>((size_t)room);
-  st = c->cloud_buf.reserve(c, c->stream, cv.total());
+  st = c->cloud_buf.reserve(c, c->stream, cv);
   if (st) return st;
   void* b = c->cloud_buf.p;
   float* d_traj = Carve::at<float>(b, o_traj);
@@ -195,11 +195,11 @@ int uwt_point_cloud_points(uwt_ctx* c, int32_t slot, const float* pts, int32_t n
     if (!std::isfinite(traj_pose[k])) return fail(c, UWT_ERR_INVALID_ARG, "uwt_point_cloud_points: the pose has a non-finite entry");
   if (n == 0) return UWT_OK;
   const int64_t room = std::min<int64_t>(cap, (n - 1) / params->stride + 1);   // records the call can write at most
-  Carve cv(256);   // [the work area | the pose | records | the table | the cloud]
+  Carve cv(256, c->guard_bytes);   // [the work area | the pose | records | the table | the cloud]
   const CloudWork w = cloud_work_layout(cv, n, params->stride, 1);
   const size_t o_traj = cv.take<float>(7), o_info = cv.take<uwt_cloud_info>(2), o_tab = cv.take<float4>((size_t)n),
                o_pts = cv.take<uwt_cloud_point>((size_t)room);
-  st = c->cloud_buf.reserve(c, c->stream, cv.total());
+  st = c->cloud_buf.reserve(c, c->stream, cv);
   if (st) return st;
   st = compute_begin(c, slot, 1);
   if (st) return st;

@@ -51,12 +51,26 @@ int detect_run(uwt_ctx* c, const Detector& d, int n_frames, const int32_t* slots
   return UWT_OK;
 }
 
+// Grid (blocks, n_frames): the rows below frame f's count (confined to 0..cap) of a fixed-stride table of `words` 32-bit words a row,
+// from the chunk's scratch to the caller's table.  The rows past the count are neither read nor written.
+static __global__ __launch_bounds__(256) void k_deliver_rows(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
+                                                             const int* __restrict__ counts, int cap, int words) {
+  const int f = blockIdx.y;
+  const size_t n = (size_t)min(max(counts[f], 0), cap) * words, base = (size_t)f * cap * words;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[base + i] = src[base + i];
+}
+
 int deliver_device(uwt_ctx* c, int f0, const DetectArgs& a, uwt_keypoint* d_kp, void* d_desc, int32_t* d_counts) {
-  const size_t recs = (size_t)a.n_frames * a.cap, g0 = (size_t)f0 * a.cap;
+  const size_t g0 = (size_t)f0 * a.cap;
   HIPCHK(c, hipMemcpyAsync(d_counts + f0, a.counts, sizeof(int) * (size_t)a.n_frames, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_kp + g0, a.kp, sizeof(Keypoint) * recs, hipMemcpyDeviceToDevice, c->stream));
-  if (a.desc)
-    HIPCHK(c, hipMemcpyAsync((unsigned char*)d_desc + g0 * a.desc_row, a.desc, (size_t)a.desc_row * recs, hipMemcpyDeviceToDevice, c->stream));
+  auto rows = [&](const void* src, void* dst, int words) {
+    const int blocks = (int)std::min<size_t>(((size_t)a.cap * words + 255) / 256, 64);
+    hipLaunchKernelGGL(k_deliver_rows, dim3(blocks, a.n_frames), dim3(256), 0, c->stream, (const uint32_t*)src, (uint32_t*)dst, a.counts,
+                       a.cap, words);
+  };
+  rows(a.kp, d_kp + g0, (int)(sizeof(Keypoint) / 4));
+  if (a.desc) rows(a.desc, (unsigned char*)d_desc + g0 * a.desc_row, a.desc_row / 4);
+  HIPCHK(c, hipGetLastError());
   return UWT_OK;
 }
 

@@ -137,9 +137,9 @@ int uwt_match_descriptors_batch(uwt_ctx* c, int32_t n_pairs, int32_t norm, int32
   // (the checks of match_enqueue that the size of the result area depends on)
   if (n_pairs < 1 || cap < 1) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": n_pairs < 1 or cap < 1");
   if (cap > kMatchMaxRows) return fail(c, UWT_ERR_CAPACITY, std::string(what) + ": cap above UWT_MATCH_MAX_ROWS");
-  Carve cv(16);   // [matches | counts]
+  Carve cv(16, c->guard_bytes);   // [matches | counts]
   const size_t o_matches = cv.take<MatchOut>((size_t)n_pairs * cap), o_counts = cv.take<int>((size_t)n_pairs);
-  int st = c->match_out.reserve(c, c->stream, cv.tight());
+  int st = c->match_out.reserve(c, c->stream, cv, cv.tight());
   if (st) return st;
   uwt_match* d_matches = Carve::at<uwt_match>(c->match_out.p, o_matches);
   int* d_counts = Carve::at<int>(c->match_out.p, o_counts);
@@ -249,13 +249,13 @@ RansacArgs ransac_args(const uwt_ctx* c, const uwt_ransac_params& rp, int n_pair
   return a;
 }
 
-// The staged forms: grows the scratch to `bytes` (ransac_carve at `o` and what the caller carved behind it), fills the rows of need(k)
+// The staged forms: grows the scratch to the carve `cv` (ransac_carve at `o` and what the caller carved behind it), fills the rows of need(k)
 // for `ns`, the values of N the call can meet, and uploads the (x, y) tables and their counts.  The caller adds the matches and the
 // results, which are in device memory, and launches.
 int ransac_enqueue(uwt_ctx* c, int n_pairs, int cap, const float* kp_prev, const int32_t* n_kp_prev, const float* kp_cur,
                    const int32_t* n_kp_cur, int kp_cap, const uwt_ransac_params& rp, const std::vector<int>& ns, const RansacScratch& o,
-                   size_t bytes, RansacArgs* a) {
-  int st = c->ransac_buf.reserve(c, c->stream, bytes);
+                   const Carve& cv, RansacArgs* a) {
+  int st = c->ransac_buf.reserve(c, c->stream, cv);
   if (!st) st = ransac_need_rows(c, rp, ns);
   if (st) return st;
   void* b = c->ransac_buf.p;
@@ -288,9 +288,9 @@ int uwt_ransac_inliers_batch_async(uwt_ctx* c, int32_t n_pairs, const uwt_match*
   int st = ransac_check(c, what, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, params, &rp);
   if (st) return st;
   RansacArgs a;
-  Carve cv(16);
+  Carve cv(16, c->guard_bytes);
   const RansacScratch o = ransac_carve(cv, n_pairs, cap, kp_cap);
-  st = ransac_enqueue(c, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, rp, ransac_all_rows(cap), o, cv.total(), &a);
+  st = ransac_enqueue(c, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, rp, ransac_all_rows(cap), o, cv, &a);
   if (st) return st;
   a.matches = reinterpret_cast<const MatchOut*>(d_matches);
   a.n_matches = d_n_matches;
@@ -330,11 +330,11 @@ int uwt_ransac_inliers_batch(uwt_ctx* c, int32_t n_pairs, const uwt_match* match
   ns.erase(std::unique(ns.begin(), ns.end()), ns.end());
   const size_t recs = (size_t)n_pairs * cap;
   RansacArgs a;
-  Carve cv(16);   // behind the call's own: [matches | good | info | match counts | inlier counts | mask]
+  Carve cv(16, c->guard_bytes);   // behind the call's own: [matches | good | info | match counts | inlier counts | mask]
   const RansacScratch o = ransac_carve(cv, n_pairs, cap, kp_cap);
   const size_t o_matches = cv.take<MatchOut>(recs), o_good = cv.take<MatchOut>(recs), o_info = cv.take<RansacInfo>((size_t)n_pairs),
                o_n_matches = cv.take<int>((size_t)n_pairs), o_counts = cv.take<int>((size_t)n_pairs), o_mask = cv.take<uint8_t>(recs);
-  st = ransac_enqueue(c, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, rp, ns, o, cv.total(), &a);
+  st = ransac_enqueue(c, n_pairs, cap, kp_prev, n_kp_prev, kp_cur, n_kp_cur, kp_cap, rp, ns, o, cv, &a);
   if (st) return st;
   void* b = c->ransac_buf.p;
   a.matches = Carve::at<MatchOut>(b, o_matches);
@@ -380,9 +380,9 @@ int uwt::ransac_device_enqueue(uwt_ctx* c, int n_pairs, int cap, const uwt_ransa
                                const int32_t* d_n_matches, const uwt_keypoint* d_kp_prev, const int32_t* d_n_kp_prev,
                                const uwt_keypoint* d_kp_cur, const int32_t* d_n_kp_cur, uwt_match* d_good, int32_t* d_counts,
                                uwt_ransac_info* d_info) {
-  Carve cv(16);
+  Carve cv(16, c->guard_bytes);
   const size_t o_quads = cv.take<float4>((size_t)cap * n_pairs), o_mask = cv.take<uint8_t>((size_t)cap * n_pairs);
-  int st = c->ransac_buf.reserve(c, c->stream, cv.total());
+  int st = c->ransac_buf.reserve(c, c->stream, cv);
   if (!st) st = ransac_need_rows(c, rp, ransac_all_rows(cap));
   if (st) return st;
   RansacArgs a = ransac_args(c, rp, n_pairs, cap, cap);

@@ -91,9 +91,8 @@ namespace {
 struct OrbLayout {
   size_t slots, raw_count, counts, layers, raw_key, raw_h, kept, keep, kp, desc, extra, total;
 };
-OrbLayout orb_layout(const OrbArgs& g, int nf, int cap, size_t extra) {
+OrbLayout orb_layout(Carve& cv, const OrbArgs& g, int nf, int cap, size_t extra) {
   OrbLayout l;
-  Carve cv(16);
   l.slots = cv.take<int>((size_t)nf);
   l.raw_count = cv.take<int>((size_t)nf * kOrbMaxLevels);
   l.counts = cv.take<int>((size_t)nf);
@@ -199,15 +198,17 @@ struct OrbCall {
     g.layer_stride = (loff + 15) & ~(size_t)15;
     g.raw_stride = roff;
     g.kept_stride = (int)kept;
-    d.frame_bytes = orb_layout(g, 1, cap, 0).total;
+    Carve cv(16, c->guard_bytes);
+    d.frame_bytes = orb_layout(cv, g, 1, cap, 0).total;
     d.rows = d_path ? cap : std::min(cap, std::max(g.kept_stride, 1));   // (a provided list may hold cap records)
     return UWT_OK;
   }
   // Grows the scratch to a chunk of nf frames, sends the chunk's slot list and the pattern, and enqueues the layers.
   int begin(const int32_t* slots, int nf, size_t extra, unsigned char** extra_out) {
     const size_t modes = d_path ? sizeof(int) * (size_t)nf : 0;   // (no call has both)
-    const OrbLayout l = orb_layout(g, nf, cap, extra + modes);
-    int st = c->orb_buf.reserve(c, c->stream, l.total);
+    Carve cv(16, c->guard_bytes);
+    const OrbLayout l = orb_layout(cv, g, nf, cap, extra + modes);
+    int st = c->orb_buf.reserve(c, c->stream, cv);
     if (st) return st;
     st = orb_pattern_ready(c);
     if (st) return st;
@@ -314,9 +315,10 @@ int uwt_orb_harris(uwt_ctx* c, int32_t slot, int32_t level, const int32_t* xy, i
   OrbCall o(c, nullptr, 1);
   const OrbArgs& a = o.a;
   unsigned char* x = nullptr;
-  Carve cv(16);
+  Carve cv(16, c->guard_bytes);
   const size_t at_xy = cv.take<int>(2 * (size_t)n), at_h = cv.take<long long>((size_t)n);
   int st = stage_begin(c, what, o.d, slot, false, cv.total(), &x);
+  if (!st) st = c->orb_buf.adopt(c, c->stream, cv, x);
   if (st) return st;
   HIPCHK(c, hipMemcpyAsync(x + at_xy, xy, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
   launch_orb_harris(c->stream, a, level, (const int*)(x + at_xy), n, (long long*)(x + at_h));

@@ -12,10 +12,10 @@ int resize_half_host(uwt_ctx* c, const char* what, bool even_only, const T* src,
   const int dw = uwt_half_size(sw), dh = uwt_half_size(sh);
   if (!c || !src || !dst || sw < 1 || sh < 1 || dw < 1 || dh < 1 || (even_only && ((sw | sh) & 1))) return fail(c, UWT_ERR_INVALID_ARG, what);
   const size_t sp = ((size_t)sw + 3) & ~(size_t)3, dp = ((size_t)dw + 3) & ~(size_t)3, es = sizeof(T);
-  Carve cv(256);   // [source plane | result plane]
+  Carve cv(256, c->guard_bytes);   // [source plane | result plane]
   cv.take<T>(sp * sh);
   const size_t off = cv.take<T>(dp * dh);
-  int st = c->scratch.reserve(c, c->stream, cv.tight() + 64);
+  int st = c->scratch.reserve(c, c->stream, cv, cv.tight() + 64);
   if (st) return st;
   unsigned char* d = (unsigned char*)c->scratch.p;
   HIPCHK(c, hipMemcpy2DAsync(d, sp * es, src, (size_t)sw * es, (size_t)sw * es, sh, hipMemcpyHostToDevice, c->stream));
@@ -28,9 +28,9 @@ int resize_half_host(uwt_ctx* c, const char* what, bool even_only, const T* src,
 
 int run_se3_op(uwt_ctx* c, int op, const float* a, int na, const float* b, int nb, float* out, int nout, int* flag) {
   if (!c) return UWT_ERR_INVALID_ARG;
-  Carve cv(256);   // floats [0,64) a, [64,128) b, [128,256) out, [256] flag
+  Carve cv(256, c->guard_bytes);   // floats [0,64) a, [64,128) b, [128,256) out, [256] flag
   const size_t o_a = cv.take<float>(64), o_b = cv.take<float>(64), o_out = cv.take<float>(128), o_flag = cv.take<int>(1);
-  int st = c->scratch.reserve(c, c->stream, 4096);   // (a page: the carving needs less)
+  int st = c->scratch.reserve(c, c->stream, cv, std::max<size_t>(4096, cv.total()));   // (a page: the carving needs less without guards)
   if (st) return st;
   float *da = Carve::at<float>(c->scratch.p, o_a), *db = Carve::at<float>(c->scratch.p, o_b), *dout = Carve::at<float>(c->scratch.p, o_out);
   int* dflag = Carve::at<int>(c->scratch.p, o_flag);
@@ -64,10 +64,10 @@ int uwt_scharr3(uwt_ctx* c, const uint8_t* src, int32_t w, int32_t h, int16_t* g
   if (!c || !src || !gx || !gy || w < 1 || h < 1) return fail(c, UWT_ERR_INVALID_ARG, "uwt_scharr3");
   const size_t pitch = ((size_t)w + 3) & ~(size_t)3;   // rows padded to whole groups of four, as the context's level planes are
   const size_t n = pitch * h;
-  Carve cv(256);   // [image | gx, gy]
+  Carve cv(256, c->guard_bytes);   // [image | gx, gy]
   cv.take<uint8_t>(n);
   const size_t off = cv.take<int16_t>(2 * n);
-  int st = c->scratch.reserve(c, c->stream, cv.tight());
+  int st = c->scratch.reserve(c, c->stream, cv, cv.tight());
   if (st) return st;
   uint8_t* d = (uint8_t*)c->scratch.p;
   int16_t* dgx = (int16_t*)(d + off);

@@ -28,10 +28,9 @@ namespace {
 struct SurfLayout {
   size_t slots, raw_count, counts, integral, raw, key, keep, kp, desc, extra, total;
 };
-SurfLayout surf_layout(const uwt_ctx* c, int nf, size_t raw_cap, int cap, size_t extra) {
+SurfLayout surf_layout(const uwt_ctx* c, Carve& cv, int nf, size_t raw_cap, int cap, size_t extra) {
   SurfLayout l;
   const size_t px = (size_t)(c->p.width + 1) * (size_t)(c->p.height + 1);
-  Carve cv(16);
   l.slots = cv.take<int>((size_t)nf);
   l.raw_count = cv.take<int>((size_t)nf);
   l.counts = cv.take<int>((size_t)nf);
@@ -96,15 +95,17 @@ struct SurfCall {
   // the geometry under sp: the bound of the candidate lists when the call detects
   int plan(bool detect) {
     raw_cap = detect ? surf_raw_bound(c->p.width, c->p.height, sp.n_octaves, sp.n_octave_layers + 2) : 0;
-    d.frame_bytes = surf_layout(c, 1, raw_cap, cap, 0).total;
+    Carve cv(16, c->guard_bytes);
+    d.frame_bytes = surf_layout(c, cv, 1, raw_cap, cap, 0).total;
     d.rows = cap;
     return UWT_OK;
   }
   // Grows the scratch to a chunk of nf frames, sends the chunk's slot list and enqueues the integral images.
   int begin(const int32_t* slots, int nf, size_t extra, unsigned char** extra_out) {
     const size_t modes = d_path ? sizeof(int) * (size_t)nf : 0;   // (no call has both)
-    const SurfLayout l = surf_layout(c, nf, raw_cap, cap, extra + modes);
-    int st = c->surf_buf.reserve(c, c->stream, l.total);
+    Carve cv(16, c->guard_bytes);
+    const SurfLayout l = surf_layout(c, cv, nf, raw_cap, cap, extra + modes);
+    int st = c->surf_buf.reserve(c, c->stream, cv);
     if (st) return st;
     unsigned char* b = (unsigned char*)c->surf_buf.p;
     detect_image(c, &a);

@@ -46,7 +46,7 @@ int stage_slots(uwt_ctx* c, int* d, int first, int n) {
 // the work area at `work` (candidates_work_layout), frame f's table at out + f * gw * gh, its full count at counts[f]
 int enqueue_candidates(uwt_ctx* c, int lvl, int n, const int* d_slots, double threshold, void* work, float4* out, int* counts) {
   const LevelK& L = c->lv[lvl];
-  Carve cv(kCandidatesAlign);
+  Carve cv(kCandidatesAlign, c->guard_bytes);
   const CandidatesLayout o = candidates_work_layout(cv, L, n);
   uwt::CandidatesWork w;
   w.sums = Carve::at<unsigned long long>(work, o.o_sums);
@@ -69,11 +69,11 @@ int uwt_gradient_magnitude(uwt_ctx* c, int32_t slot, int32_t lvl, uint8_t* mag_o
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_gradient_magnitude");
   const LevelK& L = c->lv[lvl];   // gradient_[lvl]: the level's image, img_w x img_h
   // scratch: [sum (not read) | slot list at 64 | the plane at 256]
-  Carve cv(64);
+  Carve cv(64, c->guard_bytes);
   const size_t o_sum = cv.take<unsigned long long>(1), o_slot = cv.take<int>(1);
   cv.align = 256;
   const size_t o_mag = cv.take<uint8_t>((size_t)L.n);
-  int st = c->scratch.reserve(c, c->stream, cv.tight());
+  int st = c->scratch.reserve(c, c->stream, cv, cv.tight());
   if (st) return st;
   st = compute_begin(c, slot, 1);
   if (st) return st;
@@ -98,11 +98,11 @@ int uwt_obtain_candidate_points_batch(uwt_ctx* c, int32_t first_slot, int32_t n_
   const LevelK& L = c->lv[lvl];
   const size_t rows = (size_t)L.gw * L.gh;   // a frame's table: a row for every cell of the point grid (the bound is never reached)
   // scratch: [the producer's work area | slot list | counts | tables]
-  Carve cv(kCandidatesAlign);
+  Carve cv(kCandidatesAlign, c->guard_bytes);
   candidates_work_layout(cv, L, n_frames);   // (at the base, where enqueue_candidates carves it again)
   const size_t o_slots = cv.take<int>((size_t)n_frames), o_cnt = cv.take<int>((size_t)n_frames),
                o_tab = cv.take<float4>((size_t)n_frames * rows);
-  int st = c->scratch.reserve(c, c->stream, cv.tight());
+  int st = c->scratch.reserve(c, c->stream, cv, cv.tight());
   if (st) return st;
   st = compute_begin(c, first_slot, n_frames);
   if (st) return st;
@@ -130,12 +130,12 @@ int uwt_obtain_patch_points(uwt_ctx* c, int32_t slot, const float* kp, int32_t n
   if (st) return st;
   const int stride = std::min(cap, kPatchMaxKeypoints * kPatchMaxRows);   // rows written at most
   // scratch: [key point count | slot list | row count | key points at 64 | table at 4096]; the count, the slot and the key points
-  // go down in one copy
-  Carve cv(64);
-  const size_t o_hdr = cv.take<int>(3), o_kp = cv.take<float2>(kPatchMaxKeypoints);
+  // go down in one copy, so they are ONE array of the carve (nothing may come between them)
+  Carve cv(64, c->guard_bytes);
+  const size_t o_hdr = cv.take<uint8_t>(64 + sizeof(float2) * kPatchMaxKeypoints), o_kp = o_hdr + 64;
   cv.align = 4096;
   const size_t o_tab = cv.take<float4>((size_t)stride);
-  st = c->scratch.reserve(c, c->stream, cv.tight());
+  st = c->scratch.reserve(c, c->stream, cv, cv.tight());
   if (st) return st;
   st = compute_begin(c, slot, 1);
   if (st) return st;
@@ -445,7 +445,7 @@ int candidates_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t*
     const LevelK& L = c->lv[l];
     tab_off[l] = rows;
     rows += (size_t)L.gw * L.gh * n_pairs;
-    Carve cv(kCandidatesAlign);
+    Carve cv(kCandidatesAlign, c->guard_bytes);
     candidates_work_layout(cv, L, n_pairs);
     work = std::max(work, cv.total());
     smax = std::max(smax, table_slices(L.gw * L.gh));
@@ -539,10 +539,10 @@ int uwt_estimate_pose_points(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, con
   int st = upload_pairs(c, 1, &ref_slot, &tgt_slot);
   if (st) return st;
   // scratch: [a count per level | the evaluations' records | the tables]
-  Carve cv(256);
+  Carve cv(256, c->guard_bytes);
   const size_t o_cnt = cv.take<int>(UWT_MAX_LEVELS), o_recs = cv.take<uint32_t>((size_t)table_slices(rows) * kRecWords),
                o_tab = cv.take<float4>(total);
-  st = c->scratch.reserve(c, c->stream, cv.tight());
+  st = c->scratch.reserve(c, c->stream, cv, cv.tight());
   if (st) return st;
   st = compute_begin_pairs(c, 1, &ref_slot, &tgt_slot);
   if (st) return st;
@@ -593,11 +593,11 @@ int uwt::candidates_level0_enqueue(uwt_ctx* c, int n, const int* d_slots, double
                                    const int** counts) {
   const LevelK& L = c->lv[0];
   const size_t rows = (size_t)L.gw * L.gh;
-  Carve cv(kCandidatesAlign);
+  Carve cv(kCandidatesAlign, c->guard_bytes);
   candidates_work_layout(cv, L, n);
   int st = c->cand_tab.reserve(c, c->stream, rows * n * sizeof(float4));
   if (!st) st = c->cand_cnt.reserve(c, c->stream, sizeof(int) * UWT_MAX_LEVELS * (size_t)n);
-  if (!st) st = c->cand_work.reserve(c, c->stream, cv.total());
+  if (!st) st = c->cand_work.reserve(c, c->stream, cv);
   if (st) return st;
   *tab = (const float4*)c->cand_tab.p;
   *stride = rows;

@@ -202,9 +202,9 @@ int tracking_async(uwt_ctx* c, const char* what, const TrackDetector& d, int n_p
   if (st) return st;
   if (io->d_prev_kp && (io->d_prev_kp == io->d_kept_prev || io->d_prev_kp == io->d_kept_cur || io->d_n_prev == io->d_n_matches))
     return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": the provided key points or counts are also an output of this call");
-  Carve cv(256);
+  Carve cv(256, c->guard_bytes);
   const TrackLayout l = track_carve(cv, n_pairs, cap, d.desc_row);
-  st = c->track_buf.reserve(c, c->stream, cv.total());
+  st = c->track_buf.reserve(c, c->stream, cv);
   if (st) return st;
   return tracking_enqueue(c, what, d, n_pairs, ref_slots, tgt_slots, cap, l, *io);
 }
@@ -217,10 +217,10 @@ int tracking_sync(uwt_ctx* c, const char* what, const TrackDetector& d, int n_pa
     return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
   int st = tracking_check(c, what, d, n_pairs, ref_slots, tgt_slots, prev_kp != nullptr, n_prev != nullptr);
   if (st) return st;
-  Carve cv(256);
+  Carve cv(256, c->guard_bytes);
   const TrackLayout l = track_carve(cv, n_pairs, cap, d.desc_row);
   const TrackIoLayout o = track_io_carve(cv, n_pairs, cap);
-  st = c->track_buf.reserve(c, c->stream, cv.total());
+  st = c->track_buf.reserve(c, c->stream, cv);
   if (st) return st;
   void* b = c->track_buf.p;
   const size_t recs = (size_t)n_pairs * cap;

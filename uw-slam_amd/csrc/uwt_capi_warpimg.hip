@@ -66,10 +66,10 @@ int uwt_obtain_image_transformed(uwt_ctx* c, int32_t slot, int32_t lvl, const fl
       !slot_range_ok(c, slot, 1))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_obtain_image_transformed: null argument, n < 0, or a slot or level out of range");
   const LevelK& L = c->lv[lvl];
-  Carve cv(256);   // [winner | image | valid | the slot | table | warped rows]
+  Carve cv(256, c->guard_bytes);   // [winner | image | valid | the slot | table | warped rows]
   const size_t o_win = cv.take<int>(L.n), o_img = cv.take<uint8_t>(L.n), o_val = cv.take<uint8_t>(L.n), o_slot = cv.take<int>(1),
                o_pts = cv.take<float4>(n), o_wp = cv.take<float4>(n);
-  int st = c->warp_buf.reserve(c, c->stream, cv.total());
+  int st = c->warp_buf.reserve(c, c->stream, cv);
   if (st) return st;
   st = compute_begin(c, slot, 1);
   if (st) return st;
@@ -124,12 +124,12 @@ int uwt_warp_image_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, 
   if (st) return st;
   const LevelK& L = c->lv[lvl];
   const size_t planes = (size_t)L.n * n_pairs;
-  Carve cv(256);   // [winner planes | poses | records | warped | valid | absdiff]
+  Carve cv(256, c->guard_bytes);   // [winner planes | poses | records | warped | valid | absdiff]
   cv.take<int>(planes);
   const size_t o_pose = cv.take<float>(7 * (size_t)n_pairs), o_q = cv.take<uwt_warp_quality>(n_pairs),
                o_w = cv.take<uint8_t>(warped_out ? planes : 0), o_v = cv.take<uint8_t>(valid_out ? planes : 0),
                o_d = cv.take<uint8_t>(absdiff_out ? planes : 0);
-  st = c->warp_buf.reserve(c, c->stream, cv.total());
+  st = c->warp_buf.reserve(c, c->stream, cv);
   if (st) return st;
   void* b = c->warp_buf.p;
   uwt_warp_image_io io;
@@ -159,9 +159,9 @@ int uwt_warp_mosaic(uwt_ctx* c, int32_t ref_slot, int32_t tgt_slot, int32_t lvl,
       !slot_range_ok(c, tgt_slot, 1))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_warp_mosaic: null argument, or a slot or level out of range");
   const LevelK& L = c->lv[lvl];
-  Carve cv(256);   // [warped | mosaic]
+  Carve cv(256, c->guard_bytes);   // [warped | mosaic]
   const size_t o_w = cv.take<uint8_t>(L.n), o_m = cv.take<uint8_t>(4 * (size_t)L.iw * L.ih);
-  int st = c->warp_buf.reserve(c, c->stream, cv.total());
+  int st = c->warp_buf.reserve(c, c->stream, cv);
   if (st) return st;
   st = compute_begin_pairs(c, 1, &ref_slot, &tgt_slot);
   if (st) return st;

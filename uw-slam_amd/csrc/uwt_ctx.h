@@ -24,23 +24,45 @@ namespace uwt {
 // A device buffer that grows on use (its contents are not kept).  reserve: nothing when it holds `bytes` already; else `stream` is
 // drained first — work enqueued before, an asynchronous call's included, may still read the old block — then the block is freed
 // and a new one allocated.  One buffer per stage: a stage's asynchronous call is never disturbed by another stage's growth.
+//
+// Test instrumentation (uwt_debug_guards; off unless a test turns it on, and then nothing below changes an offset, a size or a launch):
+// with uwt_ctx::guard_bytes set, the block gets a guard before its first byte and one behind its last, and a carved block one behind
+// every array (Carve).  reserve then remembers where the gaps are and fills them with kGuardPattern on `stream` on EVERY use, and
+// uwt_debug_check_guards compares them.  The arrays themselves are never filled: only bytes no correct code reads carry the pattern.
+struct GuardGap { long long at; size_t bytes; int array; };   // offset from DevBuf::p; the array in front of the gap (-1: the lead)
+constexpr unsigned char kGuardPattern = 0xC7;
+struct Carve;
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
-  int reserve(uwt_ctx* c, hipStream_t stream, size_t want);
+  void* block = nullptr;          // what hipMalloc returned: p, or p minus the lead guard
+  std::vector<GuardGap> gaps;     // of the last use (empty with guards off)
+  int reserve(uwt_ctx* c, hipStream_t stream, size_t want, const Carve* cv = nullptr);
+  int reserve(uwt_ctx* c, hipStream_t stream, const Carve& cv);                // cv.total() bytes
+  int reserve(uwt_ctx* c, hipStream_t stream, const Carve& cv, size_t want);   // a site that reserves another size than total()
+  // the gaps of a carve that lies INSIDE one of the block's arrays, at `base` (a per-stage entry's area behind a detector's chunk)
+  int adopt(uwt_ctx* c, hipStream_t stream, const Carve& inner, const void* base);
   hipError_t release();   // the only hipFree of a buffer that can grow
 };
 
 // Carves one allocation into arrays: take<T>(n) is the offset of n elements of T, each array starting on the next multiple of
 // `align` behind the one before (align may be changed between two takes); total() the bytes to reserve, the last array padded
-// like the others, tight() the same without that pad; at<T>(base, offset) the array's address.
+// like the others, tight() the same without that pad; at<T>(base, offset) the array's address.  guard: uwt_ctx::guard_bytes — not 0:
+// every array is followed by a gap of `guard` bytes rounded up to align (recorded in `gaps`, which DevBuf::reserve takes over).
 struct Carve {
-  size_t align, end = 0;
-  explicit Carve(size_t a) : align(a) {}
+  size_t align, guard, end = 0;
+  std::vector<GuardGap> gaps;
+  explicit Carve(size_t a, size_t guard_bytes = 0) : align(a), guard(guard_bytes) {}
   size_t up(size_t b) const { return (b + align - 1) & ~(align - 1); }
   template <typename T> size_t take(size_t n) {
     const size_t at = up(end);
     end = at + sizeof(T) * n;
+    if (guard) {
+      if (!gaps.empty()) gaps.back().bytes = at - (size_t)gaps.back().at;   // (the pad in front of this array belongs to the gap before)
+      const size_t stop = up(end) + up(guard);
+      gaps.push_back({(long long)end, stop - end, (int)gaps.size()});
+      end = stop;
+    }
     return at;
   }
   size_t total() const { return up(end); }
@@ -118,6 +140,7 @@ struct uwt_ctx {
   // launch the batch-dependent slicing aims at; 0: 1024 for a batch that runs as two halves (one block per slot of the chip),
   // else 4096
   int* h_active = nullptr;              // pinned
+  size_t guard_bytes = 0;               // uwt_debug_guards: guards around and inside every DevBuf (0: none, the default)
   DevBuf scratch;                       // per-stage entry points
   // the live call for a batch of pairs (uwt_track_features_batch_async, uwt_obtain_patch_points_batch), allocated on first use:
   // max_pairs tables of kPatchMaxKeypoints x kPatchMaxRows rows and their counts, the key points as the device reads them, the

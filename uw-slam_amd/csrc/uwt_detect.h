@@ -93,7 +93,8 @@ int detect_check(uwt_ctx* c, const char* what, int n_frames, const int32_t* slot
 // chunk, the chunk's arguments) before the next chunk runs.  d is prepared.
 int detect_run(uwt_ctx* c, const Detector& d, int n_frames, const int32_t* slots, int cap, const uwt_keypoint* kp_in, const int32_t* n_in,
                bool want_desc, const Deliver& deliver);
-// the chunk's results to the caller's device arrays, every row of the chunk (d_desc is not written when the chunk has no descriptors)
+// the chunk's results to the caller's device arrays: the counts, and the rows below each frame's count, in 32-bit words (d_desc is not
+// written when the chunk has no descriptors); the rows past a count keep what they held, as the header says
 int deliver_device(uwt_ctx* c, int f0, const DetectArgs& a, uwt_keypoint* d_kp, void* d_desc, int32_t* d_counts);
 // the chunk's results to host memory: only the rows below each frame's count are written
 int deliver_host(uwt_ctx* c, int f0, const DetectArgs& a, uwt_keypoint* kp_out, void* desc_out, int32_t* counts_out);
