@@ -329,6 +329,37 @@ int uwt_se3_handoff(uwt_ctx* ctx, float pose_inout[7], int32_t scale_t);
 int uwt_solve_delta(uwt_ctx* ctx, const float A[36], const float b[6], float delta_out[6], float* Ainv_out_or_null,
                     int32_t* nonsingular_out_or_null);
 
+/* The state of one pair inside an alignment, as the update kernels keep it: pose (quaternion x y z w, translation), the error of the
+ * last accepted step and of this evaluation, level_done / status (uwt_stats::status), evaluations so far, valid points of the last one. */
+typedef struct uwt_pair_state {
+  float pose[7];
+  float last_error, error;
+  int32_t level_done, status, iters, n_valid;
+} uwt_pair_state;   /* 52 bytes */
+
+/* Test surface: the tail of one Gauss-Newton iteration (src/Tracker.cpp:495-574: fold of the evaluation's block records, error, exit
+ * test, b, A.inv() * b, pose <- pose * exp(delta)) on records the CALLER wrote, through either of the library's two fold forms.  No
+ * alignment call uses this entry.
+ *   form 0   the block form (k_gn_update as the alignments launch it: 256 threads per pair); needs stride == count.  A pair that arrives
+ *            with level_done or status set is returned unchanged.
+ *   form 1   the tail form: `count` one-wave blocks per pair draw the pair's ticket, the last one folds and updates, as in the tail of a
+ *            residual or table launch.  Those launches draw no ticket for a finished pair; here every pair is updated.
+ * Every array is indexed by the absolute pair: pairs pair_base .. pair_base + n_pairs - 1 are updated, rows below pair_base travel to
+ * the device and back untouched.  With rows = pair_base + n_pairs:
+ *   records      rows x stride x 64 words, a pair's first `count` records folded (1 <= count <= stride, count <= 160, stride <= 256).
+ *                A record: 27 f64 sums (21 of A's upper triangle, row-major, 6 of J^T r) in words 0-53 | valid points, u32, word 54 |
+ *                sum of r^2, u64, words 56-57 | the error numerator, f64, words 58-59 (general != 0) | the rest not part of any sum.
+ *   states_in, states_out   rows records each.
+ *   k, max_iters, early_exit, epsilon, gain, general   as an alignment passes them (general != 0: records of the weighted / bilinear
+ *                kind: gain already applied, error from the error numerator).  The solve is the context's arithmetic set's.
+ *   active_out   the number of pairs that took a step.
+ *   tickets_out_or_null   rows words: the ticket words after the call (form 0: zeros; form 1: zero again after a correct run).
+ * rows > 1024 or any other argument out of range: UWT_ERR_INVALID_ARG, the outputs untouched. */
+int uwt_gn_update_records(uwt_ctx* ctx, int32_t form, int32_t n_pairs, int32_t pair_base, int32_t stride, int32_t count,
+                          const uint32_t* records, const uwt_pair_state* states_in, int32_t k, int32_t max_iters, int32_t early_exit,
+                          float epsilon, float gain, int32_t general, uwt_pair_state* states_out, int32_t* active_out,
+                          uint32_t* tickets_out_or_null);
+
 /* ---- sparse point tables (Frame::candidatePoints_[lvl]) -------------------------------------------- */
 
 /* Tracker::EstimatePose / EstimatePoseFeatures over explicit per-level point tables (src/Tracker.cpp:401, 669): tables[l]

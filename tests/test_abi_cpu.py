@@ -61,6 +61,7 @@ def test_struct_layouts_match_header(capi):
     assert C.sizeof(capi.Stats) == 16
     assert C.sizeof(capi.Accum) == 21 * 8 + 6 * 8 + 8 + 8
     assert C.sizeof(capi.Tuning) == 2 * 4 + 2 * 8 + 12 * 4 + 4 * 4
+    assert C.sizeof(capi.PairState) == 13 * 4 == capi.PAIR_STATE_DTYPE.itemsize   # uwt_pair_state: pose[7], 2 floats, 4 ints
 
 
 def test_library_reads_no_environment_and_carries_no_experiment_switches():

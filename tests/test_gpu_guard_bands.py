@@ -448,6 +448,22 @@ def jacobian_case(ctx, pose):
     return dict(A=r["A"], jtr=r["jtr"], sum_r2=r["sum_r2"], n_valid=r["n_valid"], valid=r["valid"], J=r["J"][v], r=r["r"][v])
 
 
+def gn_update_case(ctx):
+    """uwt_gn_update_records in both forms: 3 pairs behind a pair_base of 2, 17 records of a stride of 20"""
+    import gn_update_cases as GC
+    import gn_update_ref as GR
+    recs = np.zeros((5, 20, GR.REC_WORDS), np.uint32)
+    for p in range(5):
+        recs[p, :17] = GC.fold_records(17, seed=p)
+    states = np.array([GR.state(iters=p) for p in range(5)], GR.STATE_DTYPE)
+    out = []
+    for form in (0, 1):
+        r = recs[:, :17] if form == 0 else recs
+        st, active, tickets = ctx.gn_update_records(form, r, states, 17, pair_base=2, early_exit=0)
+        out += [st.view(np.uint8), active, tickets]
+    return out
+
+
 def scratch_cases(capi, synth, ctx, gt):
     """name -> a call of one stage that owns a growable block (or carves the shared scratch), on the 165 x 99 frames"""
     w, h = 165, 99
@@ -514,6 +530,7 @@ def scratch_cases(capi, synth, ctx, gt):
         "stage_ls": lambda: (ctx.ls_accumulate(J, r, wt), ctx.ls_accumulate_sse(J, r, wt)),
         "stage_robust_weights": lambda: ctx.robust_weights(np.linspace(-60, 60, 1000).astype(np.float32)),
         "stage_trajectory": lambda: (ctx.accumulate_trajectory(poses, t_scale=40.0), ctx.accumulate_trajectory(poses, scan=True)),
+        "stage_gn_update": lambda: gn_update_case(ctx),
         "stage_gradient_and_candidates": lambda: (ctx.gradient_magnitude(2, 1), ctx.obtain_candidate_points(2, 1, 5.0),
                                                   ctx.obtain_candidate_points_batch(0, 3, 0, 5.0)),
         "stage_patches": lambda: (ctx.obtain_patch_points(0, kps[2]), ctx.obtain_patch_points_batch([0, 2, 3], kps),
@@ -540,7 +557,7 @@ SCRATCH_CASES = ["candidates_batch", "candidates_batch_huber_bilinear", "feature
                  "match_host_hamming", "match_device_l2", "ransac", "surf", "surf_describe", "surf_stages", "orb", "orb_stages",
                  "tracking_surf", "tracking_orb", "warp_explicit", "warp_batch", "warp_batch_level_2", "warp_mosaic", "cloud_batch",
                  "cloud_batch_cut", "cloud_batch_async", "cloud_points", "stage_resize", "stage_scharr", "stage_se3", "stage_warp", "stage_jacobian", "stage_ls",
-                 "stage_robust_weights", "stage_trajectory", "stage_gradient_and_candidates", "stage_patches", "stage_pose_points"]
+                 "stage_robust_weights", "stage_trajectory", "stage_gn_update", "stage_gradient_and_candidates", "stage_patches", "stage_pose_points"]
 
 
 @pytest.mark.gpu

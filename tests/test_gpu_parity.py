@@ -225,6 +225,12 @@ def test_se3_ops_match_oracle_and_golden(capi, O, golden):
     rng = np.random.default_rng(77)
     for xi in rng.normal(0, 0.3, (50, 6)).astype(np.float32):
         assert np.array_equal(ctx.se3_exp(xi), O.se3_exp(xi))
+    # the thetas at which a branch of exp or of its sines changes, and beyond pi (tests/gn_update_cases.py)
+    import gn_update_cases as GC
+    for name, xi, prior in GC.exp_cases():
+        e = O.se3_exp(xi)
+        assert ctx.se3_exp(xi).tobytes() == e.tobytes(), name
+        assert ctx.se3_mul(prior, e).tobytes() == O.se3_mul(prior, e).tobytes(), name
 
 
 def test_solve_delta_matches_oracle_and_golden(capi, O, golden):
@@ -237,6 +243,14 @@ def test_solve_delta_matches_oracle_and_golden(capi, O, golden):
     # singular ⇒ zero inverse ⇒ δ = 0, no error raised (cv::Mat::inv semantics)
     dd, Ai, good = ctx.solve_delta(np.zeros((6, 6), np.float32), np.ones(6, np.float32))
     assert not good and not Ai.any() and not dd.any()
+    # rank-deficient at every pivot, pivot ties, a swap at every column, a pivot on either side of the threshold, J'J-like scaling
+    import gn_update_cases as GC
+    for name, (A, jtr, singular_at) in GC.solve_cases().items():
+        b = (-50.0 * jtr.astype(np.float64)).astype(np.float32)
+        dd, Ai, good = ctx.solve_delta(A, b)
+        X, ok = O.inv6(A)
+        assert good == ok == (singular_at is None), name
+        assert Ai.tobytes() == X.tobytes() and dd.tobytes() == O.solve_delta(A, b).tobytes(), name
 
 
 # ------------------------------------------------------------------ warp + per-pixel terms

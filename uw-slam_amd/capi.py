@@ -135,6 +135,17 @@ class Accum(C.Structure):
                 ("n_valid", C.c_int32), ("pad", C.c_int32)]
 
 
+class PairState(C.Structure):
+    """uwt_pair_state: a pair's state inside an alignment (uwt_gn_update_records)"""
+    _fields_ = [("pose", C.c_float * 7), ("last_error", C.c_float), ("error", C.c_float), ("level_done", C.c_int32),
+                ("status", C.c_int32), ("iters", C.c_int32), ("n_valid", C.c_int32)]
+
+
+# the same record as a numpy dtype: arrays of states go in and out of Context.gn_update_records
+PAIR_STATE_DTYPE = np.dtype([("pose", "<f4", (7,)), ("last_error", "<f4"), ("error", "<f4"), ("level_done", "<i4"), ("status", "<i4"),
+                             ("iters", "<i4"), ("n_valid", "<i4")])
+
+
 # every symbol include/uwt.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "uwt_abi_version", "uwt_source_id", "uwt_status_string", "uwt_last_error", "uwt_default_params", "uwt_create", "uwt_destroy",
@@ -143,7 +154,7 @@ SYMBOLS = [
     "uwt_stream", "uwt_profile_enable", "uwt_profile_read", "uwt_profile_read_levels", "uwt_profile_clock", "uwt_halve_u8", "uwt_halve_u16", "uwt_scharr3",
     "uwt_half_size", "uwt_resize_half_u8", "uwt_resize_half_u16",
     "uwt_warp", "uwt_residual_jacobian", "uwt_ls_accumulate", "uwt_se3_exp", "uwt_se3_mul", "uwt_se3_matrix",
-    "uwt_se3_handoff", "uwt_solve_delta", "uwt_accumulate_trajectory", "uwt_accumulate_trajectory_scan",
+    "uwt_se3_handoff", "uwt_solve_delta", "uwt_gn_update_records", "uwt_accumulate_trajectory", "uwt_accumulate_trajectory_scan",
     "uwt_residual_jacobian_weighted", "uwt_estimate_pose_points", "uwt_gradient_magnitude",
     "uwt_obtain_candidate_points", "uwt_obtain_candidate_points_batch", "uwt_obtain_patch_points", "uwt_add_patch_points",
     "uwt_ingest_create", "uwt_ingest_destroy", "uwt_ingest_maps", "uwt_ingest_undistort", "uwt_ingest_calculate_roi",
@@ -704,6 +715,25 @@ class Context:
         self._chk(lib().uwt_solve_delta(self._h, _p(A, C.c_float), _p(b, C.c_float), _p(d, C.c_float), _p(Ai, C.c_float),
                                         C.byref(ok)))
         return d, Ai.reshape(6, 6), bool(ok.value)
+
+    def gn_update_records(self, form, records, states, count, pair_base=0, k=0, max_iters=50, early_exit=1, epsilon=1e-3, gain=50.0,
+                          general=0):
+        """uwt_gn_update_records (test surface): one update of pairs pair_base.. from explicit records.  records: rows x stride x 64
+        uint32 words, states: rows records of PAIR_STATE_DTYPE (rows = pair_base + the pairs to update); form 0 the block form, 1 the
+        tail form.  Returns (states_out, active, tickets)."""
+        records = np.ascontiguousarray(records, np.uint32)
+        states = np.ascontiguousarray(states, PAIR_STATE_DTYPE).reshape(-1)
+        if records.ndim != 3 or records.shape[2] != 64 or records.shape[0] != states.size:
+            raise ValueError("records: rows x stride x 64 words, one row per state")
+        rows, stride = records.shape[0], records.shape[1]
+        out = np.full(rows, 0, PAIR_STATE_DTYPE)
+        tickets = np.full(rows, 0xffffffff, np.uint32)
+        active = C.c_int32(-1)
+        self._chk(lib().uwt_gn_update_records(self._h, int(form), rows - int(pair_base), int(pair_base), stride, int(count),
+                                              _p(records, C.c_uint32), states.ctypes.data_as(C.POINTER(PairState)), int(k), int(max_iters),
+                                              int(early_exit), C.c_float(epsilon), C.c_float(gain), int(general),
+                                              out.ctypes.data_as(C.POINTER(PairState)), C.byref(active), _p(tickets, C.c_uint32)))
+        return out, active.value, tickets
 
     def accumulate_trajectory(self, poses, start=None, t_scale=1.0, reference_axes=False, scan=False):
         """scan=True: the parallel prefix product (equal to the sequential form to float rounding, not bit for bit)."""

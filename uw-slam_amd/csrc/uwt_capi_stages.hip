@@ -279,6 +279,70 @@ int uwt_solve_delta(uwt_ctx* c, const float A[36], const float b[6], float delta
   return UWT_OK;
 }
 
+static_assert(sizeof(uwt_pair_state) == sizeof(PairState) && offsetof(uwt_pair_state, last_error) == offsetof(PairState, last_error) &&
+              offsetof(uwt_pair_state, n_valid) == offsetof(PairState, n_valid), "uwt_pair_state layout");
+
+// Test surface: one update of pairs [pair_base, pair_base + n_pairs) from the caller's records, by k_gn_update (form 0) or by the tail
+// form under k_tail_fold_stage (form 1).  Every device array is indexed by the absolute pair, like an alignment's.
+int uwt_gn_update_records(uwt_ctx* c, int32_t form, int32_t n_pairs, int32_t pair_base, int32_t stride, int32_t count,
+                          const uint32_t* records, const uwt_pair_state* states_in, int32_t k, int32_t max_iters, int32_t early_exit,
+                          float epsilon, float gain, int32_t general, uwt_pair_state* states_out, int32_t* active_out,
+                          uint32_t* tickets_out) {
+  if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
+  constexpr int kMaxRows = 1024, kMaxStride = 256;
+  if (!c || !records || !states_in || !states_out || !active_out || (form != 0 && form != 1) || n_pairs < 1 || pair_base < 0 ||
+      pair_base > kMaxRows || n_pairs > kMaxRows - pair_base || count < 1 || count > kMaxSlices || stride < count || stride > kMaxStride ||
+      (form == 0 && stride != count))
+    return fail(c, UWT_ERR_INVALID_ARG, "uwt_gn_update_records: a null array, form not 0 / 1, pairs outside 1..1024 rows, count outside 1..160, "
+                                        "stride < count or > 256, or form 0 with stride != count");
+  const size_t rows = (size_t)pair_base + n_pairs;
+  Carve cv(256, c->guard_bytes);   // [records | states | active | tickets]
+  const size_t o_rec = cv.take<uint32_t>(rows * stride * kRecWords), o_st = cv.take<PairState>(rows), o_act = cv.take<int>(1),
+               o_tk = cv.take<unsigned int>(rows);
+  int st = c->scratch.reserve(c, c->stream, cv);
+  if (st) return st;
+  uint32_t* d_rec = Carve::at<uint32_t>(c->scratch.p, o_rec);
+  PairState* d_st = Carve::at<PairState>(c->scratch.p, o_st);
+  int* d_act = Carve::at<int>(c->scratch.p, o_act);
+  unsigned int* d_tk = Carve::at<unsigned int>(c->scratch.p, o_tk);
+  HIPCHK(c, hipMemcpyAsync(d_rec, records, sizeof(uint32_t) * rows * stride * kRecWords, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_st, states_in, sizeof(PairState) * rows, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_act, 0, sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(d_tk, 0, sizeof(unsigned int) * rows, c->stream));
+  const int legacy = c->p.arith == UWT_ARITH_LEGACY ? 1 : 0;
+  if (form == 0) {
+    UpdateArgs u{};
+    u.partials = d_rec;
+    u.state = d_st;
+    u.slices = count;
+    u.k = k; u.max_iters = max_iters; u.early_exit = early_exit; u.epsilon = epsilon; u.gain = gain;
+    u.pair_base = pair_base;
+    u.general = general ? 1 : 0;
+    u.active = d_act;
+    u.legacy_solve = legacy;
+    hipLaunchKernelGGL(k_gn_update, dim3(n_pairs), dim3(kUpdateBlock), 0, c->stream, u);
+  } else {
+    ResidualArgs a{};
+    a.partials = d_rec;
+    a.pair_base = pair_base;
+    a.slices = stride;
+    a.tail.tickets = d_tk;
+    a.tail.state = d_st;
+    a.tail.active = d_act;
+    a.tail.on = 1;
+    a.tail.k = k; a.tail.max_iters = max_iters; a.tail.early_exit = early_exit; a.tail.epsilon = epsilon; a.tail.gain = gain;
+    a.tail.general = general ? 1 : 0;
+    a.tail.legacy_solve = legacy;
+    hipLaunchKernelGGL(k_tail_fold_stage, dim3(count, n_pairs), dim3(64), 0, c->stream, a, (int)stride, (int)count);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(states_out, d_st, sizeof(PairState) * rows, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(active_out, d_act, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (tickets_out) HIPCHK(c, hipMemcpyAsync(tickets_out, d_tk, sizeof(unsigned int) * rows, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return UWT_OK;
+}
+
 int uwt_robust_weights(uwt_ctx* c, const float* residuals, int32_t n, int32_t kind, float* weights_out, float* median_out,
                        float* mad_out) {
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device

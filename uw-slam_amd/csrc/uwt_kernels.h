@@ -3607,4 +3607,11 @@ static __global__ void k_se3_ops(int op, const float* in_a, const float* in_b, f
   }
 }
 
+// Test surface (uwt_gn_update_records): the tail form of the update on records the caller wrote.  grid = (count, pairs), one wave per
+// block: every block draws its pair's ticket as the blocks of a residual / table launch do behind their record, the last one folds the
+// pair's first `count` records of `stride` and updates the pair's state (tail_fold_wave).  Reads a.partials, a.pair_base and a.tail only.
+static __global__ __launch_bounds__(64) void k_tail_fold_stage(const ResidualArgs a, int stride, int count) {
+  tail_fold_wave(a, (int)blockIdx.y + a.pair_base, stride, count);
+}
+
 }  // namespace uwt
