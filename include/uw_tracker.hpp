@@ -258,6 +258,33 @@ class Tracker {
     check(uwt_estimate_pose_batch(ctx(), 1, &a, &b, _previous_frame->rigid_transformation_.data(), &last_stats_),
           "uwt_estimate_pose_batch");
   }
+  // EstimatePose from a start pose (uwt_estimate_pose_batch_seeded; no reference counterpart: the reference always starts at the
+  // identity, src/Tracker.cpp:385): _seed is the pose in front of the first evaluation, used as given — a keyframe's prediction
+  // (PredictSeeds), the previous pair's pose, another stage's result.  handoff 0: the reference's level hand-off; 1: the pose crosses
+  // the levels unchanged (uwt_seed_options).
+  void EstimatePoseSeeded(Frame* _previous_frame, Frame* _current_frame, const SE3& _seed, int32_t handoff = 0) {
+    const int32_t a = bind(_previous_frame), b = bind(_current_frame);
+    if (!_previous_frame->obtained_gradients_)
+      throw std::runtime_error("EstimatePoseSeeded: ApplyGradient(previous) not called (or its slot was reused since)");
+    const SE3 seed = _seed;   // (the seed may be the previous frame's own rigid_transformation_, which the call writes)
+    const uwt_seed_options so = seed_options(handoff);
+    check(uwt_estimate_pose_batch_seeded(ctx(), 1, &a, &b, _previous_frame->rigid_transformation_.data(), &last_stats_, seed.data(), &so),
+          "uwt_estimate_pose_batch_seeded");
+  }
+  // The constant-velocity motion model in keyframe coordinates (uwt_predict_seeds): _prev = the poses keyframe -> frame p - 1, _cur =
+  // keyframe -> frame p, n x 7 floats each; returns the seeds (cur * prev^-1) * cur for keyframe -> frame p + 1.
+  std::vector<float> PredictSeeds(const std::vector<float>& _prev, const std::vector<float>& _cur) {
+    if (_prev.size() != _cur.size() || _prev.size() % 7) throw std::invalid_argument("PredictSeeds: n x 7 floats each");
+    std::vector<float> out(_cur.size());
+    check(uwt_predict_seeds(ctx(), (int32_t)(_cur.size() / 7), _prev.data(), _cur.data(), out.data()), "uwt_predict_seeds");
+    return out;
+  }
+  static uwt_seed_options seed_options(int32_t handoff) {
+    uwt_seed_options so;
+    uwt_default_seed_options(&so);
+    so.handoff = handoff;
+    return so;
+  }
   // include/Tracker.h:124 — the vectorised prototype's schedule: levels PYRAMID_LEVELS-1 .. 0, <= 50 iterations, gain 50,
   // epsilon 1e-3, no z / angle factor applied (src/Tracker.cpp:877-885, 1082).  The reference BODY is not reproduced: its
   // residual ignores the warp (:933-944) and column 0 of Jw1 is zeroed by a typo (:986); this runs the same per-point
@@ -443,8 +470,16 @@ class Tracker {
   void EstimatePoseFeaturesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, const uwt_table_options& _options) {
     features_batch(_pairs, &_options);
   }
+  // From start poses (_seeds: pairs x 7 floats, one seed per pair; handoff as EstimatePoseSeeded): uwt_estimate_pose_features_batch_seeded.
+  void EstimatePoseFeaturesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, const std::vector<float>& _seeds, int32_t handoff = 0,
+                                 const uwt_table_options* _options_or_null = nullptr) {
+    if (_seeds.size() != 7 * _pairs.size()) throw std::invalid_argument("EstimatePoseFeaturesBatch: 7 floats of seed per pair");
+    const uwt_seed_options so = seed_options(handoff);
+    features_batch(_pairs, _options_or_null, _seeds.data(), &so);
+  }
  private:
-  void features_batch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, const uwt_table_options* opt) {
+  void features_batch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, const uwt_table_options* opt, const float* seeds = nullptr,
+                      const uwt_seed_options* sopt = nullptr) {
     const size_t n = _pairs.size();
     if (n == 0) return;
     std::vector<int32_t> a(n), b(n), counts(n);
@@ -465,14 +500,16 @@ class Tracker {
     }
     std::vector<float> poses(n * 7);
     last_batch_stats_.assign(n, uwt_stats{});
-    const int st = opt ? uwt_estimate_pose_features_batch_opt(ctx(), (int32_t)n, a.data(), b.data(), kp.data(), counts.data(), opt,
+    const int st = sopt ? uwt_estimate_pose_features_batch_seeded(ctx(), (int32_t)n, a.data(), b.data(), kp.data(), counts.data(), opt,
+                                                                  poses.data(), last_batch_stats_.data(), seeds, sopt)
+                   : opt ? uwt_estimate_pose_features_batch_opt(ctx(), (int32_t)n, a.data(), b.data(), kp.data(), counts.data(), opt,
                                                               poses.data(), last_batch_stats_.data())
                        : uwt_estimate_pose_features_batch(ctx(), (int32_t)n, a.data(), b.data(), kp.data(), counts.data(), poses.data(),
                                                           last_batch_stats_.data());
     if (st == UWT_OK || st == UWT_ERR_PAIR_FAILED)
       for (size_t i = 0; i < n; i++) std::copy(poses.begin() + 7 * i, poses.begin() + 7 * (i + 1), _pairs[i].first->rigid_transformation_.data());
     if (st == UWT_OK) last_stats_ = last_batch_stats_.back();
-    check(st, opt ? "uwt_estimate_pose_features_batch_opt" : "uwt_estimate_pose_features_batch");
+    check(st, sopt ? "uwt_estimate_pose_features_batch_seeded" : opt ? "uwt_estimate_pose_features_batch_opt" : "uwt_estimate_pose_features_batch");
   }
  public:
   // Semi-dense tracking for many pairs at once: ObtainCandidatePoints(previous) (src/Tracker.cpp:1314-1362) on the levels the
@@ -489,8 +526,17 @@ class Tracker {
                                    double gradient_threshold = 20.0) {
     candidates_batch(_pairs, gradient_threshold, &_options);
   }
+  // From start poses (_seeds: pairs x 7 floats; handoff as EstimatePoseSeeded): uwt_estimate_pose_candidates_batch_seeded — the weights
+  // and the sampler are then the call's (null options: identity weights and round()), as in the options overload.
+  void EstimatePoseCandidatesBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, const std::vector<float>& _seeds, int32_t handoff = 0,
+                                   const uwt_table_options* _options_or_null = nullptr, double gradient_threshold = 20.0) {
+    if (_seeds.size() != 7 * _pairs.size()) throw std::invalid_argument("EstimatePoseCandidatesBatch: 7 floats of seed per pair");
+    const uwt_seed_options so = seed_options(handoff);
+    candidates_batch(_pairs, gradient_threshold, _options_or_null, _seeds.data(), &so);
+  }
  private:
-  void candidates_batch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, double gradient_threshold, const uwt_table_options* opt) {
+  void candidates_batch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, double gradient_threshold, const uwt_table_options* opt,
+                        const float* seeds = nullptr, const uwt_seed_options* sopt = nullptr) {
     const size_t n = _pairs.size();
     if (n == 0) return;
     std::vector<int32_t> a(n), b(n);
@@ -506,14 +552,16 @@ class Tracker {
     }
     std::vector<float> poses(n * 7);
     last_batch_stats_.assign(n, uwt_stats{});
-    const int st = opt ? uwt_estimate_pose_candidates_batch_opt(ctx(), (int32_t)n, a.data(), b.data(), gradient_threshold, opt,
+    const int st = sopt ? uwt_estimate_pose_candidates_batch_seeded(ctx(), (int32_t)n, a.data(), b.data(), gradient_threshold, opt,
+                                                                    poses.data(), last_batch_stats_.data(), seeds, sopt)
+                   : opt ? uwt_estimate_pose_candidates_batch_opt(ctx(), (int32_t)n, a.data(), b.data(), gradient_threshold, opt,
                                                                 poses.data(), last_batch_stats_.data())
                        : uwt_estimate_pose_candidates_batch(ctx(), (int32_t)n, a.data(), b.data(), gradient_threshold, poses.data(),
                                                             last_batch_stats_.data());
     if (st == UWT_OK || st == UWT_ERR_PAIR_FAILED)
       for (size_t i = 0; i < n; i++) std::copy(poses.begin() + 7 * i, poses.begin() + 7 * (i + 1), _pairs[i].first->rigid_transformation_.data());
     if (st == UWT_OK) last_stats_ = last_batch_stats_.back();
-    check(st, opt ? "uwt_estimate_pose_candidates_batch_opt" : "uwt_estimate_pose_candidates_batch");
+    check(st, sopt ? "uwt_estimate_pose_candidates_batch_seeded" : opt ? "uwt_estimate_pose_candidates_batch_opt" : "uwt_estimate_pose_candidates_batch");
   }
  public:
   // System::Tracking() (src/System.cpp:193-223) for a list of (previous, current) pairs through the device-resident call
@@ -525,7 +573,19 @@ class Tracker {
   // has written (the next pair of a sequence) waits for that pair's results, as it does in the loop.  A pair without a good match
   // has UWT_ERR_NO_VALID_POINTS in its stats and leaves its frames' lists empty; that does not throw.  Per-pair stats in
   // last_batch_stats().  (Defined behind RobustMatcher, whose parameters it reads.)
-  void TrackingBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, RobustMatcher& _robust_matcher, int32_t cap = 2048);
+  void TrackingBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, RobustMatcher& _robust_matcher, int32_t cap = 2048) {
+    tracking_batch(_pairs, _robust_matcher, cap, nullptr);
+  }
+  // From start poses for the live alignment (_seeds: pairs x 7 floats; uwt_tracking_batch_seeded / uwt_tracking_orb_batch_seeded): the
+  // front end is untouched, and a pair it fails keeps the identity.
+  void TrackingBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, RobustMatcher& _robust_matcher, const std::vector<float>& _seeds,
+                     int32_t cap = 2048) {
+    if (_seeds.size() != 7 * _pairs.size()) throw std::invalid_argument("TrackingBatch: 7 floats of seed per pair");
+    tracking_batch(_pairs, _robust_matcher, cap, _seeds.data());
+  }
+ private:
+  void tracking_batch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, RobustMatcher& _robust_matcher, int32_t cap, const float* seeds);
+ public:
   const std::vector<uwt_stats>& last_batch_stats() const { return last_batch_stats_; }
   // EstimatePose over the sparse tables a producer left in previous->candidatePoints_[lvl] (src/Tracker.cpp:401)
   void EstimatePoseOverCandidatePoints(Frame* _previous_frame, Frame* _current_frame) {
@@ -916,11 +976,11 @@ class RobustMatcher {
   Tracker* tracker_;
 };
 
-inline void Tracker::TrackingBatch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, RobustMatcher& rm, int32_t cap) {
+inline void Tracker::tracking_batch(const std::vector<std::pair<Frame*, Frame*>>& _pairs, RobustMatcher& rm, int32_t cap, const float* seeds) {
   // RobustMatcher(tracker, 1): uwt_tracking_orb_batch under the matcher's pattern, the records in orb_keypoints_
   const bool orb = rm.detector_ == 1;
   std::vector<uwt_keypoint> Frame::*kept = orb ? &Frame::orb_keypoints_ : &Frame::surf_keypoints_;
-  const char* entry = orb ? "uwt_tracking_orb_batch" : "uwt_tracking_batch";
+  const char* entry = orb ? (seeds ? "uwt_tracking_orb_batch_seeded" : "uwt_tracking_orb_batch") : (seeds ? "uwt_tracking_batch_seeded" : "uwt_tracking_batch");
   uwt_tracking_params tp;
   uwt_tracking_orb_params top;
   uwt_default_tracking_params(&tp);
@@ -981,10 +1041,19 @@ inline void Tracker::TrackingBatch(const std::vector<std::pair<Frame*, Frame*>>&
     std::vector<uwt_tracking_info> info(n);
     std::vector<uwt_match> good(n * (size_t)cap);
     std::vector<uwt_keypoint> kept_prev(n * (size_t)cap), kept_cur(n * (size_t)cap);
-    const int st = orb ? uwt_tracking_orb_batch(ctx(), (int32_t)n, a.data(), b.data(), &top, cap, prev.data(), n_prev.data(), poses.data(),
-                                                stats.data(), info.data(), good.data(), kept_prev.data(), kept_cur.data())
-                       : uwt_tracking_batch(ctx(), (int32_t)n, a.data(), b.data(), &tp, cap, prev.data(), n_prev.data(), poses.data(),
-                                            stats.data(), info.data(), good.data(), kept_prev.data(), kept_cur.data());
+    int st;
+    if (seeds) {
+      const float* run_seeds = seeds + 7 * (i - n);
+      st = orb ? uwt_tracking_orb_batch_seeded(ctx(), (int32_t)n, a.data(), b.data(), &top, cap, prev.data(), n_prev.data(), poses.data(),
+                                               stats.data(), info.data(), good.data(), kept_prev.data(), kept_cur.data(), run_seeds, nullptr)
+               : uwt_tracking_batch_seeded(ctx(), (int32_t)n, a.data(), b.data(), &tp, cap, prev.data(), n_prev.data(), poses.data(),
+                                           stats.data(), info.data(), good.data(), kept_prev.data(), kept_cur.data(), run_seeds, nullptr);
+    } else {
+      st = orb ? uwt_tracking_orb_batch(ctx(), (int32_t)n, a.data(), b.data(), &top, cap, prev.data(), n_prev.data(), poses.data(),
+                                        stats.data(), info.data(), good.data(), kept_prev.data(), kept_cur.data())
+               : uwt_tracking_batch(ctx(), (int32_t)n, a.data(), b.data(), &tp, cap, prev.data(), n_prev.data(), poses.data(),
+                                    stats.data(), info.data(), good.data(), kept_prev.data(), kept_cur.data());
+    }
     if (st != UWT_OK && st != UWT_ERR_PAIR_FAILED) check(st, entry);
     for (size_t k = 0; k < n; k++) {
       Frame* p = run[k].first;

@@ -1238,6 +1238,111 @@ int uwt_accumulate_trajectory_device_async(uwt_ctx* ctx, const float* d_poses, i
 int uwt_accumulate_trajectory_device_from_async(uwt_ctx* ctx, const float* d_poses, int32_t n, const float* d_start_pose, float t_scale,
                                                 int32_t reference_axes, float* d_traj_out);
 
+/* ---- seeded calls: an alignment that starts from a given pose (keyframe tracking, a motion-model prediction, a refinement) ------- */
+
+/* Every alignment above starts at the identity, as Tracker::EstimatePose* does (src/Tracker.cpp:385, :647).  The entries below are
+ * their counterparts with a start pose per pair, a SEED: 7 floats qx qy qz qw tx ty tz that stand where that identity stood — the pose
+ * in front of the first evaluation of the first iterated level, used exactly as given: nothing normalises, scales or pre-compensates
+ * it (the intended sources are this library's own poses).  Everything behind it is the existing loop under the existing constants.  No
+ * reference counterpart: the reference's System carries current_keyframe_ / keyframes_ / AddKeyFrame (src/System.cpp:264-278) and
+ * never tracks against them.
+ * The reference's level hand-off doubles q.xyz behind every level that is not level 0 (:580-590), so a rotation carried in by a seed
+ * is multiplied too (twice doubled over three levels); hence the option of the seeded calls:
+ *   handoff 0  the reference's hand-off (uwt_se3_handoff under uwt_params::handoff_scale_t; the live call's :856) — the default;
+ *   handoff 1  keep: the pose crosses every level boundary unchanged, the last one included; last_error is re-armed as before.
+ * Rules, the same in every seeded entry (each takes the arguments and the checks of its unseeded counterpart, then the tail
+ * seeds_or_null, sopt_or_null):
+ *   - seeds_or_null null: every pair starts at the identity; with handoff 0 the results are the unseeded entry's byte for byte.
+ *     sopt_or_null null: {0}.  handoff outside 0..1 or a non-zero reserved word: UWT_ERR_INVALID_ARG with nothing enqueued.
+ *   - per-pair failure: a seed with a non-finite entry gives that pair alone uwt_stats {UWT_ERR_INVALID_ARG, iterations 0, n_valid 0,
+ *     error 0} and the identity as its pose (a non-finite value is never echoed); the pair runs no evaluation, the other pairs' bits
+ *     are what they are without it, and the synchronous forms return UWT_ERR_PAIR_FAILED.  The test is made on the device (device
+ *     seeds are invisible to the host), in the synchronous forms too.  Every other failure is reported as in the unseeded entry.
+ *   - synchronous forms: seeds are n_pairs x 7 HOST floats, copied into the context before anything is enqueued; a rerun of the
+ *     speculative one- or two-pair call starts from that copy again.
+ *   - _async forms: seeds are n_pairs x 7 floats in DEVICE memory, alignment 4 bytes, not a byte outside that extent is read.  They are
+ *     read on the context's stream: the pose buffer of a call enqueued before on the same context may go in without a wait; it must
+ *     stay untouched until this call has completed.  The seed range must overlap no output of the same call (d_poses_out,
+ *     d_stats_out): UWT_ERR_INVALID_ARG with nothing enqueued — an alignment may be evaluated by launches that run after results
+ *     were written, and each must find the seed.
+ *   - a pair's bits depend neither on the batch, nor on its place in it, nor on uwt_tuning. */
+typedef struct uwt_seed_options {
+  int32_t handoff;      /* 0: the reference's hand-off (default); 1: keep */
+  int32_t reserved[7];  /* zero */
+} uwt_seed_options;     /* 32 bytes */
+int uwt_default_seed_options(uwt_seed_options* o);   /* {0} */
+
+/* uwt_estimate_pose_batch from seeds (host seeds, host results; every launch form of the unseeded call). */
+int uwt_estimate_pose_batch_seeded(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                   float* poses_out, uwt_stats* stats_out_or_null, const float* seeds_or_null,
+                                   const uwt_seed_options* sopt_or_null);
+/* uwt_track_batch_async from seeds in device memory, ordered against uploads exactly as the unseeded call.
+ * alignment: d_poses_out, d_stats_out_or_null and d_seeds_or_null 4 bytes. */
+int uwt_track_batch_seeded_async(uwt_ctx* ctx, int32_t first_slot, int32_t n_frames, int32_t grad_refs_only, int32_t n_pairs,
+                                 const int32_t* ref_slots, const int32_t* tgt_slots, float* d_poses_out, uwt_stats* d_stats_out_or_null,
+                                 const float* d_seeds_or_null, const uwt_seed_options* sopt_or_null);
+/* The live call (uwt_track_features_batch_opt_async / uwt_estimate_pose_features_batch_opt) from seeds: level 0 only, so a seed is
+ * what lets it follow a motion its ten iterations cannot absorb from the identity.  The hand-off is the live call's (:856).
+ * alignment: as uwt_track_features_batch_async, d_seeds_or_null 4 bytes. */
+int uwt_track_features_batch_seeded_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                          const float* keypoints_xy, const int32_t* n_keypoints, const uwt_table_options* opt_or_null,
+                                          float* d_poses_out, uwt_stats* d_stats_out_or_null, const float* d_seeds_or_null,
+                                          const uwt_seed_options* sopt_or_null);
+int uwt_estimate_pose_features_batch_seeded(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                            const float* keypoints_xy, const int32_t* n_keypoints, const uwt_table_options* opt_or_null,
+                                            float* poses_out, uwt_stats* stats_out_or_null, const float* seeds_or_null,
+                                            const uwt_seed_options* sopt_or_null);
+/* Semi-dense tracking (uwt_track_candidates_batch_opt_async / uwt_estimate_pose_candidates_batch_opt) from seeds.
+ * alignment: as uwt_track_candidates_batch_async, d_seeds_or_null 4 bytes. */
+int uwt_track_candidates_batch_seeded_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                            double threshold, const uwt_table_options* opt_or_null, float* d_poses_out,
+                                            uwt_stats* d_stats_out_or_null, const float* d_seeds_or_null,
+                                            const uwt_seed_options* sopt_or_null);
+int uwt_estimate_pose_candidates_batch_seeded(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                              double threshold, const uwt_table_options* opt_or_null, float* poses_out,
+                                              uwt_stats* stats_out_or_null, const float* seeds_or_null,
+                                              const uwt_seed_options* sopt_or_null);
+
+/* The chained tracking calls (uwt_tracking_batch_async / uwt_tracking_orb_batch_async) from seeds in device memory: uwt_tracking_io
+ * stays as it is, the seeds are arguments — a live loop passes the previous call's io.d_poses.  The front end is untouched: info, good
+ * and the kept lists are the unseeded chain's.  A pair that reaches the live call without a key point — every pair the front end fails —
+ * starts at the identity whatever its seed row holds, and keeps the unseeded call's record and the identity pose.  The seeds must
+ * overlap no output of io (d_poses, d_stats, d_info, d_good, d_kept_prev, d_kept_cur, d_n_matches, each in its full n_pairs [x cap]
+ * extent): UWT_ERR_INVALID_ARG with nothing enqueued.  alignment: as the unseeded chains, d_seeds_or_null 4 bytes. */
+int uwt_tracking_batch_seeded_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                    const uwt_tracking_params* params_or_null, int32_t cap, const uwt_tracking_io* io,
+                                    const float* d_seeds_or_null, const uwt_seed_options* sopt_or_null);
+int uwt_tracking_orb_batch_seeded_async(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                        const uwt_tracking_orb_params* params_or_null, int32_t cap, const uwt_tracking_io* io,
+                                        const float* d_seeds_or_null, const uwt_seed_options* sopt_or_null);
+
+/* The synchronous chains (uwt_tracking_batch / uwt_tracking_orb_batch) from HOST seeds, everything else as there: what the language
+ * mirrors' TrackingBatch(..., seeds) calls. */
+int uwt_tracking_batch_seeded(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                              const uwt_tracking_params* params_or_null, int32_t cap, const uwt_keypoint* prev_kp_or_null,
+                              const int32_t* n_prev_or_null, float* poses_out, uwt_stats* stats_out_or_null, uwt_tracking_info* info_out,
+                              uwt_match* good_out, uwt_keypoint* kept_prev_out, uwt_keypoint* kept_cur_out, const float* seeds_or_null,
+                              const uwt_seed_options* sopt_or_null);
+int uwt_tracking_orb_batch_seeded(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                  const uwt_tracking_orb_params* params_or_null, int32_t cap, const uwt_keypoint* prev_kp_or_null,
+                                  const int32_t* n_prev_or_null, float* poses_out, uwt_stats* stats_out_or_null,
+                                  uwt_tracking_info* info_out, uwt_match* good_out, uwt_keypoint* kept_prev_out,
+                                  uwt_keypoint* kept_cur_out, const float* seeds_or_null, const uwt_seed_options* sopt_or_null);
+
+/* The constant-velocity motion model in keyframe coordinates, on the device: seed_i = (cur_i * prev_i^-1) * cur_i with prev = the pose
+ * keyframe -> frame p - 1, cur = keyframe -> frame p, the seed for keyframe -> frame p + 1.  (Frame-to-frame tracking needs no kernel:
+ * its constant-velocity seed IS the previous call's pose buffer.)  The library's own contract, the same in both arithmetic sets:
+ *   inverse of prev = (q, t):  qi = (-qx, -qy, -qz, qw), the conjugate;  R = the rotation uwt_se3_matrix gives for qi (f32, as there);
+ *     ti[k] = (float)(-(((double)R[3k] * t[0] + (double)R[3k+1] * t[1]) + (double)R[3k+2] * t[2])) — each row in f64, products exact,
+ *     added in this order, negated, rounded once (contraction cannot change it);
+ *   rel = uwt_se3_mul(cur, (qi, ti));  seed = uwt_se3_mul(rel, cur) — the bits of uwt_se3_mul.
+ * A row with a non-finite entry in prev or cur gives an all-NaN seed row, which a seeded call then refuses for that pair.
+ * d_prev, d_cur, d_seed_out: n x 7 floats in device memory, alignment 4 bytes; d_seed_out must overlap neither input:
+ * UWT_ERR_INVALID_ARG with nothing enqueued.  Enqueued on the context's stream, no wait; n = 0: nothing is enqueued. */
+int uwt_predict_seeds_device_async(uwt_ctx* ctx, int32_t n, const float* d_prev, const float* d_cur, float* d_seed_out);
+/* The same kernel on host arrays (n x 7 floats each), staged through the context's scratch; synchronous; the same bits. */
+int uwt_predict_seeds(uwt_ctx* ctx, int32_t n, const float* prev, const float* cur, float* seed_out);
+
 /* ---- test instrumentation: guards inside the context's own scratch ------------------------------------------------------------ */
 
 /* Not part of the tracker: these two serve tests/test_gpu_guard_bands.py, which uses them to see whether a kernel writes outside an

@@ -95,19 +95,22 @@ def sequence_cloud(w, h, intr, frames, depths, poses, stride=100, mode=0, arith=
     return np.concatenate(parts) if parts else np.zeros(0, capi.CLOUD_POINT)
 
 
-def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0, quality=False, cloud=None):
+def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0, quality=False, cloud=None, motion_model="identity"):
     """The same loop as successive one-pair uwt_tracking_batch_async calls (detector 1: uwt_tracking_orb_batch_async): what a frame kept
     goes to the next call in device memory (two sets of buffers, taken in turn), nothing is read back between the calls and the host
     waits once, at the end.  Same returns; quality: behind every call uwt_warp_image_batch_async on its device pose, inside the same
     single wait — the records come back as a fourth result.  cloud = (stride, mode): behind every call the trajectory is
     accumulated from the device poses, one pose per call (uwt_accumulate_trajectory_device_from_async), and, frame by frame while it is resident, the cloud
-    enqueued (uwt_point_cloud_batch_async), still inside the single wait — the records come back as the last result."""
+    enqueued (uwt_point_cloud_batch_async), still inside the single wait — the records come back as the last result.
+    motion_model "constant": pair k's live alignment starts from pair k - 1's pose, taken from device memory inside the single wait
+    (uwt_tracking_batch_seeded_async / uwt_tracking_orb_batch_seeded_async)."""
     import torch
     capi = importlib.import_module("uw-slam_amd.capi")
     n = len(frames)
     ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=4, max_pairs=1, has_depth=int(bool(depths)), arith=arith))
     ctx.set_deferred(True)   # pyramids and gradients are enqueued only
     enqueue = ctx.tracking_orb_batch_async if detector == 1 else ctx.tracking_batch_async
+    enqueue_seeded = ctx.tracking_orb_batch_seeded_async if detector == 1 else ctx.tracking_batch_seeded_async
     i32 = dict(dtype=torch.int32, device="cuda")
     poses, stats, info = torch.zeros((n - 1, 7), **i32), torch.zeros((n - 1, 4), **i32), torch.zeros((n - 1, 8), **i32)
     sets = [dict(good=torch.zeros((cap, 3), **i32), kept_prev=torch.zeros((cap, 8), **i32), kept_cur=torch.zeros((cap, 8), **i32),
@@ -137,7 +140,10 @@ def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0
         io.update(poses=poses[k].data_ptr(), stats=stats[k].data_ptr(), info=info[k].data_ptr())
         if k:
             io.update(prev_kp=sets[(k - 1) % 2]["kept_cur"].data_ptr(), n_prev=sets[(k - 1) % 2]["n_matches"].data_ptr())
-        enqueue([k % 4], [(k + 1) % 4], io, cap=cap)
+        if motion_model == "constant" and k:
+            enqueue_seeded([k % 4], [(k + 1) % 4], io, cap=cap, d_seeds_ptr=poses[k - 1].data_ptr())
+        else:
+            enqueue([k % 4], [(k + 1) % 4], io, cap=cap)
         if quality:
             ctx.warp_image_batch_async([k % 4], [(k + 1) % 4], poses[k].data_ptr(), dict(quality=records[k].data_ptr()), lvl=0)
         if cloud:
@@ -164,6 +170,58 @@ def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0
     if quality:
         res = res + (rec,)
     return res + (cl,) if cloud else res
+
+
+def keyframe_of(i, interval):
+    """the frame that frame i >= 1 is tracked against: N * floor((i - 1) / N) — a fixed policy, nothing in it depends on the data"""
+    return interval * ((i - 1) // interval)
+
+
+def track_keyframes(w, h, intr, frames, depths, over, interval=1, motion_model="identity", handoff="reference"):
+    """Dense tracking of frame i against its keyframe (keyframe_of) through uwt_track_batch_seeded_async, one pair per call, seeds,
+    poses and the trajectory in device memory and one wait at the end (plus the early-exit looks of the calls themselves).
+    motion_model "constant": the pair's seed is the constant-velocity prediction in keyframe coordinates
+    (uwt_predict_seeds_device_async from the two poses before; the first frame behind a new keyframe starts at the identity, the second
+    from prev = identity); with interval 1 — frame-to-frame tracking — the prediction IS the previous pair's pose buffer.
+    The world pose of frame i is its keyframe's trajectory row times its pose (uwt_accumulate_trajectory_device_from_async).
+    Returns (poses [n - 1, 7] keyframe -> frame, stats, trajectory [n - 1, 7], keyframe index per pair)."""
+    import torch
+    capi = importlib.import_module("uw-slam_amd.capi")
+    n = len(frames)
+    ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=3, max_pairs=1, has_depth=int(bool(depths)), **over))
+    f32 = dict(dtype=torch.float32, device="cuda")
+    poses, seeds, traj = torch.zeros((n - 1, 7), **f32), torch.zeros((n - 1, 7), **f32), torch.zeros((n - 1, 7), **f32)
+    stats = torch.zeros((n - 1, 4), dtype=torch.int32, device="cuda")
+    ident = torch.tensor([0, 0, 0, 1, 0, 0, 0], **f32)
+    torch.cuda.synchronize()   # torch's fills run on torch's stream
+    keys = []
+    for i in range(1, n):
+        p, kf = i - 1, keyframe_of(i, interval)
+        keys.append(kf)
+        if kf == i - 1:   # the previous frame becomes the keyframe: slot 0
+            ctx.set_frame(0, frames[kf], depths[kf] if depths else None)
+            ctx.build_pyramids(0, 1)
+        cur = 1 + (i % 2)
+        ctx.set_frame(cur, frames[i], depths[i] if depths else None)
+        seed = None
+        if motion_model == "constant" and p >= 1:
+            if interval == 1:
+                seed = poses[p - 1].data_ptr()
+            elif kf != i - 1:
+                before = ident if kf == i - 2 else poses[p - 2]
+                ctx.predict_seeds_device_async(1, before.data_ptr(), poses[p - 1].data_ptr(), seeds[p].data_ptr())
+                seed = seeds[p].data_ptr()
+        ctx.track_batch_seeded_async(cur, 1, [0], [cur], poses[p].data_ptr(), stats[p].data_ptr(), d_seeds_ptr=seed, handoff=handoff)
+        if kf == 0:
+            ctx.accumulate_trajectory_device_async(poses[p].data_ptr(), 1, traj[p].data_ptr())
+        else:
+            ctx.accumulate_trajectory_device_from_async(poses[p].data_ptr(), 1, traj[kf - 1].data_ptr(), traj[p].data_ptr())
+    ctx.sync()
+    st = stats.cpu().numpy().view(capi.STATS).reshape(-1)
+    out = (poses.cpu().numpy().copy(), [dict(status=int(s["status"]), iterations=int(s["iterations"]), n_valid=int(s["n_valid"]),
+                                              error=float(s["error"])) for s in st], traj.cpu().numpy().copy(), keys)
+    ctx.close()
+    return out
 
 
 def build_parser():
@@ -202,8 +260,23 @@ def build_parser():
     return ap
 
 
+def add_seed_arguments(ap):
+    """where an alignment starts and what it is tracked against (the seeded calls, include/uwt.h): main's parser is build_parser's
+    plus these"""
+    ap.add_argument("--motion-model", choices=["identity", "constant"], default="identity", help="where an alignment starts: identity, "
+                    "as the reference (src/Tracker.cpp:385), or constant velocity — pair k starts from pair k - 1's pose (with --live "
+                    "--chained from device memory, inside the single wait), a frame tracked against a keyframe from "
+                    "uwt_predict_seeds_device_async")
+    ap.add_argument("--keyframe-interval", type=int, default=0, metavar="N", help="dense tracking against keyframes: frame i against frame "
+                    "N * floor((i - 1) / N), its world pose from the keyframe's trajectory row; a new keyframe starts at the identity "
+                    "(0: consecutive frames through the batch path)")
+    ap.add_argument("--handoff", choices=["reference", "keep"], default="reference", help="how a seeded pose crosses the pyramid levels "
+                    "(uwt_seed_options): the reference's hand-off doubles q.xyz at every level, keep leaves the pose as it is")
+    return ap
+
+
 def main():
-    ap = build_parser()
+    ap = add_seed_arguments(build_parser())
     a = ap.parse_args()
     S = importlib.import_module("uw-slam_amd.sequence")
     T = importlib.import_module("uw-slam_amd.trajectory")
@@ -239,17 +312,31 @@ def main():
         ap.error("--detector orb goes with --live")
     if a.cloud and a.cloud_stride < 1:
         ap.error("--cloud-stride must be at least 1")
-    records = cloud = None
+    if a.keyframe_interval < 0:
+        ap.error("--keyframe-interval must be at least 1 (0: off)")
+    seeded = a.keyframe_interval > 0 or (a.motion_model == "constant" and not a.live)
+    if seeded and (a.live or a.quality or a.cloud):
+        ap.error("--keyframe-interval (and --motion-model constant without --live) is the dense tracker alone: no --live, --quality or --cloud")
+    if a.motion_model == "constant" and a.live and not a.chained:
+        ap.error("--motion-model constant with --live goes with --chained")
+    records = cloud = device_traj = None
     cloud_args = (a.cloud_stride, CLOUD_MODES[a.cloud_mode]) if a.cloud else None
-    if a.live and a.chained and (a.quality or a.cloud):
+    if seeded:
+        poses, stats, device_traj, keyframes = track_keyframes(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over,
+                                                               max(1, a.keyframe_interval), a.motion_model, a.handoff)
+    elif a.live and a.chained and (a.quality or a.cloud):
         res = track_live_chained(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
-                                 detector=int(a.detector == "orb"), quality=a.quality, cloud=cloud_args)
+                                 detector=int(a.detector == "orb"), quality=a.quality, cloud=cloud_args, motion_model=a.motion_model)
         poses, stats, n_matches = res[:3]
         records = res[3] if a.quality else None
         cloud = res[-1] if a.cloud else None
     elif a.live:
-        poses, stats, n_matches = (track_live_chained if a.chained else track_live)(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths,
-                                                                                    over["arith"], detector=int(a.detector == "orb"))
+        if a.chained:
+            poses, stats, n_matches = track_live_chained(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
+                                                         detector=int(a.detector == "orb"), motion_model=a.motion_model)
+        else:
+            poses, stats, n_matches = track_live(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
+                                                 detector=int(a.detector == "orb"))
     else:
         poses, stats = trk.track(frames, depths)
     if a.quality and records is None:
@@ -257,8 +344,18 @@ def main():
     if a.cloud and cloud is None:
         cloud = sequence_cloud(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, poses, *cloud_args, arith=over["arith"])
     dt = time.perf_counter() - t0
-    traj = trk.trajectory(poses)
-    ref = trk.trajectory(poses, reference_visualiser=True)
+    if device_traj is not None and a.keyframe_interval > 1:
+        # keyframe-relative poses: the trajectory is the one accumulated on the device through the keyframes' rows; the visualiser's
+        # scaled accumulation (src/Visualizer.cpp:304-325) is defined over consecutive pairs and has no keyframe form
+        traj = ref = device_traj
+        if a.groundtruth:
+            ap.error("--groundtruth compares per-pair poses of consecutive frames: not with --keyframe-interval above 1")
+        np.save(a.out + "_keyframes.npy", np.asarray(keyframes, np.int32))
+    else:
+        traj = trk.trajectory(poses)
+        ref = trk.trajectory(poses, reference_visualiser=True)
+    if device_traj is not None:
+        np.save(a.out + "_trajectory.npy", device_traj)
     gt = None
     bad = sum(s["status"] != 0 for s in stats)
     metrics = dict(pairs=int(len(poses)), failed=int(bad), seconds=dt, crop_offset=[int(x0), int(y0)],

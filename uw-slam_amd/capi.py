@@ -120,6 +120,14 @@ class TableOptions(C.Structure):
     _fields_ = [("weights", C.c_int32), ("sampler", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
+class SeedOptions(C.Structure):
+    """uwt_seed_options: how a seeded call's pose crosses the level boundaries (handoff 0 the reference's hand-off, 1 keep)"""
+    _fields_ = [("handoff", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+HANDOFF_REFERENCE, HANDOFF_KEEP = 0, 1
+
+
 class Level(C.Structure):
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
                 ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
@@ -176,6 +184,11 @@ SYMBOLS = [
     "uwt_obtain_image_transformed", "uwt_warp_image_batch_async", "uwt_warp_image_batch", "uwt_warp_mosaic",
     "uwt_default_cloud_params", "uwt_point_cloud_batch_async", "uwt_point_cloud_batch", "uwt_point_cloud_points",
     "uwt_accumulate_trajectory_device_async", "uwt_accumulate_trajectory_device_from_async",
+    "uwt_default_seed_options", "uwt_estimate_pose_batch_seeded", "uwt_track_batch_seeded_async",
+    "uwt_track_features_batch_seeded_async", "uwt_estimate_pose_features_batch_seeded",
+    "uwt_track_candidates_batch_seeded_async", "uwt_estimate_pose_candidates_batch_seeded",
+    "uwt_tracking_batch_seeded_async", "uwt_tracking_orb_batch_seeded_async", "uwt_predict_seeds_device_async",
+    "uwt_tracking_batch_seeded", "uwt_tracking_orb_batch_seeded", "uwt_predict_seeds",
     "uwt_debug_guards", "uwt_debug_check_guards",
 ]
 
@@ -261,6 +274,33 @@ def table_options(weights=None, sampler=None):
     if sampler is not None:
         o.sampler = sampler
     return o
+
+
+def seed_options(handoff=None):
+    """uwt_default_seed_options ({0}) with the hand-off set (HANDOFF_REFERENCE / HANDOFF_KEEP, or "reference" / "keep")"""
+    o = SeedOptions()
+    st = lib().uwt_default_seed_options(C.byref(o))
+    if st:
+        raise UwtError(st, "uwt_default_seed_options")
+    if handoff is not None:
+        o.handoff = {"reference": HANDOFF_REFERENCE, "keep": HANDOFF_KEEP}.get(handoff, handoff)
+    return o
+
+
+def _host_seeds(seeds, n):
+    """Host seeds as the synchronous seeded calls take them: None, or n x 7 float32"""
+    if seeds is None:
+        return None, None
+    a = np.ascontiguousarray(seeds, np.float32).reshape(-1, 7)
+    if a.shape[0] != n:
+        raise ValueError("seeds: %d rows for %d pairs" % (a.shape[0], n))
+    return a, _p(a, C.c_float)
+
+
+def _sopt(handoff):
+    if isinstance(handoff, SeedOptions):
+        return C.byref(handoff)
+    return None if handoff is None else C.byref(seed_options(handoff))
 
 
 def default_ransac_params(**over):
@@ -541,6 +581,46 @@ class Context:
         self._chk(lib().uwt_track_batch_async(self._h, first_slot, n_frames, int(grad_refs_only), ref.size, _p(ref, C.c_int32),
                                               _p(tgt, C.c_int32), C.c_void_p(d_poses_ptr),
                                               C.c_void_p(d_stats_ptr) if d_stats_ptr else None))
+
+    def estimate_pose_batch_seeded(self, ref_slots, tgt_slots, seeds=None, handoff=None, raise_on_pair_failure=False):
+        """estimate_pose_batch from start poses (uwt_estimate_pose_batch_seeded): seeds None (the identity) or [P, 7] float32 host
+        poses; handoff: None / 0 / "reference", 1 / "keep", or a SeedOptions."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        n = ref.size
+        poses = np.empty((n, 7), np.float32)
+        stats = (Stats * n)()
+        keep, sp = _host_seeds(seeds, n)
+        st = lib().uwt_estimate_pose_batch_seeded(self._h, n, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(poses, C.c_float), stats, sp,
+                                                  _sopt(handoff))
+        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+        return poses, [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats]
+
+    def track_batch_seeded_async(self, first_slot, n_frames, ref_slots, tgt_slots, d_poses_ptr, d_stats_ptr=None, grad_refs_only=True,
+                                 d_seeds_ptr=None, handoff=None):
+        """track_batch_async from seeds in device memory (uwt_track_batch_seeded_async): d_seeds_ptr None or P x 7 float32, e.g. the
+        pose buffer of a call enqueued before, no wait between; it may overlap no output of this call."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        self._chk(lib().uwt_track_batch_seeded_async(self._h, first_slot, n_frames, int(grad_refs_only), ref.size, _p(ref, C.c_int32),
+                                                     _p(tgt, C.c_int32), C.c_void_p(d_poses_ptr),
+                                                     C.c_void_p(d_stats_ptr) if d_stats_ptr else None,
+                                                     C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+
+    def predict_seeds_device_async(self, n, d_prev_ptr, d_cur_ptr, d_seed_ptr):
+        """uwt_predict_seeds_device_async: seed = (cur * prev^-1) * cur per row, n x 7 float32 each in device memory, no wait."""
+        self._chk(lib().uwt_predict_seeds_device_async(self._h, int(n), C.c_void_p(d_prev_ptr), C.c_void_p(d_cur_ptr),
+                                                       C.c_void_p(d_seed_ptr)))
+
+    def predict_seeds(self, prev, cur):
+        """uwt_predict_seeds: the constant-velocity seeds (cur * prev^-1) * cur of host poses [n, 7], computed on the device"""
+        a = np.ascontiguousarray(prev, np.float32).reshape(-1, 7)
+        b = np.ascontiguousarray(cur, np.float32).reshape(-1, 7)
+        if a.shape != b.shape:
+            raise ValueError("predict_seeds: prev and cur differ in shape")
+        out = np.empty_like(a)
+        self._chk(lib().uwt_predict_seeds(self._h, a.shape[0], _p(a, C.c_float), _p(b, C.c_float), _p(out, C.c_float)))
+        return out
 
     def track_batch_host_async(self, first_slot, n_frames, ref_slots, tgt_slots, h_poses, h_stats=None, grad_refs_only=True):
         """h_poses: pinned float32 [n, 7]; h_stats: pinned int32 [n, 4] or None.  Returns the ticket for wait_ticket()."""
@@ -865,6 +945,62 @@ class Context:
                                                                _p(kp, C.c_float), _p(n, C.c_int32), C.byref(opt),
                                                                C.c_void_p(d_poses_ptr), d_stats))
 
+    def estimate_pose_features_batch_seeded(self, ref_slots, tgt_slots, keypoints_list, seeds=None, handoff=None, weights=None,
+                                            sampler=None, raise_on_pair_failure=False):
+        """estimate_pose_features_batch from start poses (uwt_estimate_pose_features_batch_seeded; seeds, handoff: as
+        estimate_pose_batch_seeded)."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        kp, n = self._keypoint_block(keypoints_list)
+        poses = np.empty((max(ref.size, 1), 7), np.float32)
+        stats = (Stats * max(ref.size, 1))()
+        opt = table_options(weights, sampler)
+        keep, sp = _host_seeds(seeds, ref.size)
+        st = lib().uwt_estimate_pose_features_batch_seeded(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
+                                                           _p(n, C.c_int32), C.byref(opt), _p(poses, C.c_float), stats, sp,
+                                                           _sopt(handoff))
+        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+        return poses[:ref.size], [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
+
+    def track_features_batch_seeded_async(self, ref_slots, tgt_slots, keypoints_list, d_poses_ptr, d_stats_ptr=None, d_seeds_ptr=None,
+                                          handoff=None, weights=None, sampler=None):
+        """track_features_batch_async from seeds in device memory (uwt_track_features_batch_seeded_async)."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        kp, n = self._keypoint_block(keypoints_list)
+        opt = table_options(weights, sampler)
+        self._chk(lib().uwt_track_features_batch_seeded_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
+                                                              _p(n, C.c_int32), C.byref(opt), C.c_void_p(d_poses_ptr),
+                                                              C.c_void_p(d_stats_ptr) if d_stats_ptr else None,
+                                                              C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+
+    def estimate_pose_candidates_batch_seeded(self, ref_slots, tgt_slots, seeds=None, handoff=None, threshold=20.0, weights=None,
+                                              sampler=None, raise_on_pair_failure=False):
+        """estimate_pose_candidates_batch from start poses (uwt_estimate_pose_candidates_batch_seeded); the weights and the sampler
+        are the call's, as in the _opt entry."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        poses = np.empty((max(ref.size, 1), 7), np.float32)
+        stats = (Stats * max(ref.size, 1))()
+        opt = table_options(weights, sampler)
+        keep, sp = _host_seeds(seeds, ref.size)
+        st = lib().uwt_estimate_pose_candidates_batch_seeded(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
+                                                             C.c_double(threshold), C.byref(opt), _p(poses, C.c_float), stats, sp,
+                                                             _sopt(handoff))
+        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+        return poses[:ref.size], [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
+
+    def track_candidates_batch_seeded_async(self, ref_slots, tgt_slots, d_poses_ptr, d_stats_ptr=None, d_seeds_ptr=None, handoff=None,
+                                            threshold=20.0, weights=None, sampler=None):
+        """track_candidates_batch_async from seeds in device memory (uwt_track_candidates_batch_seeded_async)."""
+        ref = np.ascontiguousarray(ref_slots, np.int32)
+        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        opt = table_options(weights, sampler)
+        self._chk(lib().uwt_track_candidates_batch_seeded_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
+                                                                C.c_double(threshold), C.byref(opt), C.c_void_p(d_poses_ptr),
+                                                                C.c_void_p(d_stats_ptr) if d_stats_ptr else None,
+                                                                C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+
     def estimate_pose_candidates_batch(self, ref_slots, tgt_slots, threshold=20.0, raise_on_pair_failure=False, weights=None,
                                        sampler=None):
         """Semi-dense tracking for many pairs: Tracker::ObtainCandidatePoints(previous) on every iterated level, then EstimatePose
@@ -1102,7 +1238,19 @@ class Context:
         """tracking_batch_async for RobustMatcher(1) (uwt_tracking_orb_batch_async)."""
         self._tracking_batch_async(lib().uwt_tracking_orb_batch_async, ref_slots, tgt_slots, io, params, cap)
 
-    def _tracking_batch(self, fn, ref_slots, tgt_slots, prev, params, cap, out, raise_on_pair_failure):
+    def tracking_batch_seeded(self, ref_slots, tgt_slots, prev=None, params=None, cap=2048, out=None, raise_on_pair_failure=False,
+                              seeds=None, handoff=None):
+        """tracking_batch from host seeds [P, 7] (uwt_tracking_batch_seeded)."""
+        return self._tracking_batch(lib().uwt_tracking_batch_seeded, ref_slots, tgt_slots, prev, params, cap, out, raise_on_pair_failure,
+                                    (seeds, handoff))
+
+    def tracking_orb_batch_seeded(self, ref_slots, tgt_slots, prev=None, params=None, cap=2048, out=None, raise_on_pair_failure=False,
+                                  seeds=None, handoff=None):
+        """tracking_orb_batch from host seeds [P, 7] (uwt_tracking_orb_batch_seeded)."""
+        return self._tracking_batch(lib().uwt_tracking_orb_batch_seeded, ref_slots, tgt_slots, prev, params, cap, out,
+                                    raise_on_pair_failure, (seeds, handoff))
+
+    def _tracking_batch(self, fn, ref_slots, tgt_slots, prev, params, cap, out, raise_on_pair_failure, seeded=None):
         """System::Tracking for many pairs in one device-resident call (fn: uwt_tracking_batch or uwt_tracking_orb_batch), host in and
         out.  prev: None, or one
         KEYPOINT array per pair (what the previous frame kept; an empty one for a pair that has none), or the packed form
@@ -1125,11 +1273,15 @@ class Context:
             out = (np.zeros((max(P, 1), 7), np.float32), np.zeros(max(P, 1), STATS), np.zeros(max(P, 1), TRACKING_INFO),
                    np.zeros((max(P, 1), c), MATCH), np.zeros((max(P, 1), c), KEYPOINT), np.zeros((max(P, 1), c), KEYPOINT))
         poses, stats, info, good, kept_prev, kept_cur = out
+        tail = ()
+        if seeded is not None:
+            keep, sp = _host_seeds(seeded[0], P)
+            tail = (sp, _sopt(seeded[1]))
         st = fn(self._h, P, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.byref(params) if params is not None else None,
                 cap, C.c_void_p(kp.ctypes.data) if kp is not None else None,
                 _p(n, C.c_int32) if n is not None else None, _p(poses, C.c_float), C.c_void_p(stats.ctypes.data),
                 C.c_void_p(info.ctypes.data), C.c_void_p(good.ctypes.data), C.c_void_p(kept_prev.ctypes.data),
-                C.c_void_p(kept_cur.ctypes.data))
+                C.c_void_p(kept_cur.ctypes.data), *tail)
         self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
         cnt = info["n_matches"]
         return dict(status=st, poses=poses[:P], stats=stats[:P], info=info[:P], good=[good[i, :cnt[i]].copy() for i in range(P)],
@@ -1139,7 +1291,18 @@ class Context:
         """tracking_batch without waiting, device in and out (uwt_tracking_batch_async); io: _tracking_batch_async."""
         self._tracking_batch_async(lib().uwt_tracking_batch_async, ref_slots, tgt_slots, io, params, cap)
 
-    def _tracking_batch_async(self, fn, ref_slots, tgt_slots, io, params, cap):
+    def tracking_batch_seeded_async(self, ref_slots, tgt_slots, io, params=None, cap=2048, d_seeds_ptr=None, handoff=None):
+        """tracking_batch_async from seeds in device memory (uwt_tracking_batch_seeded_async): d_seeds_ptr None or P x 7 float32 —
+        a live loop passes the poses buffer of the call before (another buffer than io's)."""
+        self._tracking_batch_async(lib().uwt_tracking_batch_seeded_async, ref_slots, tgt_slots, io, params, cap,
+                                   (C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+
+    def tracking_orb_batch_seeded_async(self, ref_slots, tgt_slots, io, params=None, cap=2048, d_seeds_ptr=None, handoff=None):
+        """tracking_batch_seeded_async for RobustMatcher(1) (uwt_tracking_orb_batch_seeded_async)."""
+        self._tracking_batch_async(lib().uwt_tracking_orb_batch_seeded_async, ref_slots, tgt_slots, io, params, cap,
+                                   (C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+
+    def _tracking_batch_async(self, fn, ref_slots, tgt_slots, io, params, cap, tail=()):
         """The same enqueued on the context stream with every input and result in device memory (fn: uwt_tracking_batch_async or
         uwt_tracking_orb_batch_async).  io: a
         dict of device addresses — poses (P x 7 float32), info (P TRACKING_INFO), good (P x cap MATCH), kept_prev, kept_cur (P x cap
@@ -1150,7 +1313,7 @@ class Context:
         rec = TrackingIO(*[io.get(k) or None for k in ("prev_kp", "n_prev", "poses", "stats", "info", "good", "kept_prev", "kept_cur",
                                                         "n_matches")])
         self._chk(fn(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.byref(params) if params is not None else None, cap,
-                     C.byref(rec)))
+                     C.byref(rec), *tail))
 
     def match_descriptors_device_async(self, n_pairs, dim, cap, d_query_ptr, d_n_query_ptr, d_train_ptr, d_n_train_ptr, d_matches_ptr,
                                        d_counts_ptr, ratio=0.65, norm=NORM_L2):

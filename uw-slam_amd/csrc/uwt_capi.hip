@@ -254,7 +254,7 @@ struct CallOpts {
 // (k_hist_iterate), the weighted sums behind it.  640 x 480, one pair, 4 x 10: 91 launches -> 61.  Same device functions as
 // the launches it replaces: the same poses bit for bit.
 int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_poses, StatsOut* d_stats,
-                             const hipEvent_t* level_ready, const CallOpts& opt) {
+                             const hipEvent_t* level_ready, const CallOpts& opt, const Start& start) {
   const uwt_params& p = c->p;
   uint32_t* recs[2] = {c->partials, c->partials2};
   PairState* states[2] = {c->state, c->state2};
@@ -267,7 +267,8 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
   ia.u.gain = p.gain;
   ia.u.general = robust ? 1 : 0;
   ia.u.legacy_solve = p.arith == UWT_ARITH_LEGACY ? 1 : 0;
-  ia.scale_t = p.handoff_scale_t;
+  ia.scale_t = start.scale_t(p);
+  ia.seeds = start.d_seeds;       // read by the first launch alone (mode 0, or k_coarse / k_coarse_weighted without resume)
   ia.initial_error = p.initial_error;
   // Speculative launching (identity weights, early-exit schedules, the synchronous one- or two-pair call): every read-back of
   // "who is still iterating" costs a host round trip of about two evaluations; instead each level gets the evaluations levels
@@ -291,6 +292,7 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
   ca.u = ia.u;
   ca.state_out = states[sp ^ 1];     // where the first chained launch looks for its state
   ca.scale_t = ia.scale_t;
+  ca.seeds = ia.seeds;
   ca.initial_error = ia.initial_error;
   ca.inline_pairs = ia.inline_pairs;
   for (int i = 0; i < 4; i++) ca.pair_slots[i] = ia.pair_slots[i];
@@ -403,11 +405,11 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
 
 // Tracker::EstimatePose for a batch, enqueued on the context's stream (src/Tracker.cpp:362-597)
 int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats, const hipEvent_t* level_ready = nullptr,
-                     const CallOpts& opt = CallOpts()) {
+                     const CallOpts& opt = CallOpts(), const Start& start = Start()) {
   const uwt_params& p = c->p;
   const Chained form = chained_form(c, n_pairs);
   if (form != Chained::none)
-    return enqueue_estimate_chained(c, form == Chained::robust, n_pairs, d_poses, d_stats, level_ready, opt);
+    return enqueue_estimate_chained(c, form == Chained::robust, n_pairs, d_poses, d_stats, level_ready, opt, start);
   const int tb = 128;
   const bool general = p.sampler != 0 || p.weights != 0;
   // A batch is cut into parts that run the same schedule on streams of their own (fixed schedules; 16 pairs and the pixels of
@@ -459,7 +461,8 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
     u.pair_base = base;
     ca.u = u;
     ca.state_out = c->state;
-    ca.scale_t = p.handoff_scale_t;
+    ca.scale_t = start.scale_t(p);
+    ca.seeds = start.d_seeds;   // (read without resume only; the kernel indexes by the pair's place in the call)
     ca.initial_error = p.initial_error;
     ca.resume = resume ? 1 : 0;
     size_t ev = 0;
@@ -501,7 +504,8 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
     q.s = i ? c->part_stream[i] : c->stream;
     if (i) HIPCHK(c, hipStreamWaitEvent(q.s, c->ev_fork, 0));
     if (!coarse_lvl[p.first_level]) {
-      hipLaunchKernelGGL(k_init_state, dim3((q.cnt + tb - 1) / tb), dim3(tb), 0, q.s, c->state + q.base, q.cnt, p.initial_error);
+      hipLaunchKernelGGL(k_init_state, dim3((q.cnt + tb - 1) / tb), dim3(tb), 0, q.s, c->state + q.base, q.cnt, p.initial_error,
+                         start.d_seeds ? start.d_seeds + 7 * (size_t)q.base : nullptr, nullptr);
       HIPCHK(c, hipGetLastError());
     }
   }
@@ -572,7 +576,7 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
       }
     for (int i = 0; i < parts; i++) {
       hipLaunchKernelGGL(k_level_end, dim3((pt[i].cnt + tb - 1) / tb), dim3(tb), 0, pt[i].s, c->state + pt[i].base, pt[i].cnt, lvl,
-                         p.handoff_scale_t, p.initial_error);
+                         start.scale_t(p), p.initial_error);
       HIPCHK(c, hipGetLastError());
     }
   }
@@ -610,6 +614,49 @@ int first_failure(uwt_ctx* c, const char* what, const uwt_stats* stats, int n) {
     if (stats[i].status != UWT_OK)
       return fail(c, UWT_ERR_PAIR_FAILED, std::string(what) + ": at least one pair failed, first status: " +
                                               uwt_status_string(stats[i].status));
+  return UWT_OK;
+}
+
+// ---- the seeded calls (uwt.h "seeded calls") --------------------------------------------------------------------------------
+// the options of a seeded call: null = {0}; handoff in 0..1, reserved words zero
+int seed_options(uwt_ctx* c, const char* what, const uwt_seed_options* sopt, Start* out) {
+  *out = Start();
+  if (!sopt) return UWT_OK;
+  if (sopt->handoff < 0 || sopt->handoff > 1)
+    return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": uwt_seed_options: handoff outside 0..1");
+  for (int32_t r : sopt->reserved)
+    if (r) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": uwt_seed_options: reserved word not zero");
+  out->keep = sopt->handoff;
+  return UWT_OK;
+}
+
+// Device seeds may share no byte with an output of the same call: an alignment may be evaluated again by launches that run after
+// results were written (the speculative rerun; any later launch form that revisits a pair), and each must find the seed.
+int seeds_clear_of_range(uwt_ctx* c, const char* what, const float* d_seeds, int n_pairs, const void* out, size_t bytes) {
+  if (!d_seeds || n_pairs < 1 || !out || !bytes) return UWT_OK;
+  const uintptr_t s0 = (uintptr_t)d_seeds, s1 = s0 + sizeof(float) * 7 * (size_t)n_pairs, o0 = (uintptr_t)out, o1 = o0 + bytes;
+  if (s0 < o1 && o0 < s1) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": the seeds overlap an output of the call");
+  return UWT_OK;
+}
+
+int seeds_clear_of(uwt_ctx* c, const char* what, const float* d_seeds, int n_pairs, const void* d_poses_out, const void* d_stats_out) {
+  if (n_pairs < 1) return UWT_OK;
+  int st = seeds_clear_of_range(c, what, d_seeds, n_pairs, d_poses_out, sizeof(float) * 7 * (size_t)n_pairs);
+  if (!st) st = seeds_clear_of_range(c, what, d_seeds, n_pairs, d_stats_out, sizeof(uwt_stats) * (size_t)n_pairs);
+  return st;
+}
+
+// The synchronous forms: the caller's seeds into the context's page-locked block, which the kernels read in place (the calls are
+// synchronous: the block is free again when they return).  Null seeds: the identity, nothing staged.  n_pairs in 1..max_pairs.
+int stage_host_seeds(uwt_ctx* c, const float* seeds, int n_pairs, Start* start) {
+  start->d_seeds = nullptr;
+  if (!seeds) return UWT_OK;
+  if (!c->h_seeds) {
+    HIPCHK(c, hipHostMalloc((void**)&c->h_seeds, sizeof(float) * 7 * (size_t)c->p.max_pairs));
+    HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_seeds, c->h_seeds, 0));
+  }
+  std::memcpy(c->h_seeds, seeds, sizeof(float) * 7 * (size_t)n_pairs);
+  start->d_seeds = c->d_seeds;
   return UWT_OK;
 }
 
@@ -1169,7 +1216,7 @@ int uwt_destroy(uwt_ctx* c) {
                   (void*)c->feat_tab, (void*)c->feat_cnt, (void*)c->feat_kp, (void*)c->feat_nkp, (void*)c->feat_recs,
                   (void*)c->ransac_need})
     (void)hipFree(p);
-  for (void* p : {(void*)c->h_small, (void*)c->h_active, (void*)c->h_pairs, (void*)c->h_feat, (void*)c->h_cloud}) (void)hipHostFree(p);
+  for (void* p : {(void*)c->h_small, (void*)c->h_active, (void*)c->h_pairs, (void*)c->h_feat, (void*)c->h_cloud, (void*)c->h_seeds}) (void)hipHostFree(p);
   auto drop = [](hipEvent_t e) { if (e) (void)hipEventDestroy(e); };
   for (hipEvent_t e : c->ev_poll) drop(e);
   for (hipEvent_t e : c->ev_feat) drop(e);
@@ -1432,13 +1479,18 @@ static int prepare_frames(uwt_ctx* c, const char* bad_range, bool gradients, int
 int uwt_build_pyramids(uwt_ctx* c, int32_t first_slot, int32_t n) { return prepare_frames(c, "uwt_build_pyramids: bad range", false, first_slot, n); }
 int uwt_apply_gradient(uwt_ctx* c, int32_t first_slot, int32_t n) { return prepare_frames(c, "uwt_apply_gradient: bad range", true, first_slot, n); }
 
-int uwt_estimate_pose_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
-                            float* poses_out, uwt_stats* stats_out) {
+// uwt_estimate_pose_batch and its seeded form (seeds null, sopt null: the unseeded call)
+static int estimate_pose_batch(uwt_ctx* c, const char* what, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                               float* poses_out, uwt_stats* stats_out, const float* seeds, const uwt_seed_options* sopt) {
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
-  if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_estimate_pose_batch: null argument");
+  if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
   if (!ref_slots || !tgt_slots || n_pairs < 1) return fail(c, UWT_ERR_INVALID_ARG, "null pair lists or n_pairs < 1");
   if (n_pairs > c->p.max_pairs) return fail(c, UWT_ERR_CAPACITY, "n_pairs exceeds max_pairs");
-  int st;
+  Start start;
+  int st = seed_options(c, what, sopt, &start);
+  if (st) return st;
+  st = stage_host_seeds(c, seeds, n_pairs, &start);
+  if (st) return st;
   const bool chained = chained_form(c, n_pairs) == Chained::identity;
   CallOpts opt;
   opt.inline_pairs = n_pairs <= 2 && chained;
@@ -1465,7 +1517,8 @@ int uwt_estimate_pose_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slot
   // comes down again after kSpecCalm calls that were not cut), and the careful way — read-backs — if that is cut short too.
   opt.speculate = n_pairs <= 2 && c->p.early_exit && !c->profiling && chained && c->tn.speculation;
   for (int attempt = 0; attempt < 3; attempt++) {
-    st = enqueue_estimate(c, n_pairs, small ? c->d_small->poses : c->d_poses, small ? c->d_small->stats : c->d_stats, nullptr, opt);
+    st = enqueue_estimate(c, n_pairs, small ? c->d_small->poses : c->d_poses, small ? c->d_small->stats : c->d_stats, nullptr, opt,
+                          start);   // (a rerun starts from the staged seeds again)
     if (st) return st;
     if (!small) {
       HIPCHK(c, hipMemcpyAsync(poses_out, c->d_poses, sizeof(float) * 7 * n_pairs, hipMemcpyDeviceToHost, c->stream));
@@ -1491,15 +1544,34 @@ int uwt_estimate_pose_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slot
     if (st) return st;
   }
   if (stats_out) std::copy(tmp.begin(), tmp.end(), stats_out);
-  return first_failure(c, "uwt_estimate_pose_batch", tmp.data(), n_pairs);
+  return first_failure(c, what, tmp.data(), n_pairs);
+}
+
+int uwt_estimate_pose_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                            float* poses_out, uwt_stats* stats_out) {
+  return estimate_pose_batch(c, "uwt_estimate_pose_batch", n_pairs, ref_slots, tgt_slots, poses_out, stats_out, nullptr, nullptr);
+}
+
+int uwt_default_seed_options(uwt_seed_options* o) {
+  if (!o) return UWT_ERR_INVALID_ARG;
+  std::memset(o, 0, sizeof(*o));
+  return UWT_OK;
+}
+
+int uwt_estimate_pose_batch_seeded(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                   float* poses_out, uwt_stats* stats_out, const float* seeds, const uwt_seed_options* sopt) {
+  return estimate_pose_batch(c, "uwt_estimate_pose_batch_seeded", n_pairs, ref_slots, tgt_slots, poses_out, stats_out, seeds, sopt);
 }
 
 static int track_batch_enqueue(uwt_ctx* c, int32_t first_slot, int32_t n_frames, int32_t grad_refs_only, int32_t n_pairs,
-                               const int32_t* ref_slots, const int32_t* tgt_slots, float* d_poses_out, uwt_stats* d_stats_out) {
+                               const int32_t* ref_slots, const int32_t* tgt_slots, float* d_poses_out, uwt_stats* d_stats_out,
+                               const Start& start = Start()) {
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
   if (!c || !d_poses_out || !slot_range_ok(c, first_slot, n_frames))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_track_batch_async: bad argument");
-  int st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
+  int st = seeds_clear_of(c, "uwt_track_batch_seeded_async", start.d_seeds, n_pairs, d_poses_out, d_stats_out);
+  if (st) return st;
+  st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
   if (st) return st;
   // The alignment reads every slot the pair lists name, and with grad_refs_only the reference slots lie "wherever they
   // lie" (uwt.h): the dependency range of the call is the union of the prepared range and the pairs' slots, so that an
@@ -1526,7 +1598,7 @@ static int track_batch_enqueue(uwt_ctx* c, int32_t first_slot, int32_t n_frames,
   if (!c->tn.overlap_gradients || c->profiling || n_pairs < 768) {
     st = enqueue_gradients(c, g_first, g_n, g_slots);
     if (st) return st;
-    return enqueue_estimate(c, n_pairs, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out));
+    return enqueue_estimate(c, n_pairs, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out), nullptr, CallOpts(), start);
   }
   // The alignment starts at the coarsest iterated level and only then needs the finer gradients: the first level's are
   // computed here, the others on the side stream, each level's event gating the iterations that read it.
@@ -1544,7 +1616,7 @@ static int track_batch_enqueue(uwt_ctx* c, int32_t first_slot, int32_t n_frames,
     if (st) return st;
   }
   HIPCHK(c, hipEventRecord(c->ev_side_done, c->side));
-  st = enqueue_estimate(c, n_pairs, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out), c->ev_level);
+  st = enqueue_estimate(c, n_pairs, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out), c->ev_level, CallOpts(), start);
   // whatever follows on the context stream (the next call's pyramids, a plane read-back) is ordered after the side work
   const hipError_t e = hipStreamWaitEvent(c->stream, c->ev_side_done, 0);
   if (st) return st;
@@ -1555,6 +1627,18 @@ static int track_batch_enqueue(uwt_ctx* c, int32_t first_slot, int32_t n_frames,
 int uwt_track_batch_async(uwt_ctx* c, int32_t first_slot, int32_t n_frames, int32_t grad_refs_only, int32_t n_pairs,
                           const int32_t* ref_slots, const int32_t* tgt_slots, float* d_poses_out, uwt_stats* d_stats_out) {
   int st = track_batch_enqueue(c, first_slot, n_frames, grad_refs_only, n_pairs, ref_slots, tgt_slots, d_poses_out, d_stats_out);
+  if (st) return st;
+  return compute_end(c, c->dep_first, c->dep_n);
+}
+
+int uwt_track_batch_seeded_async(uwt_ctx* c, int32_t first_slot, int32_t n_frames, int32_t grad_refs_only, int32_t n_pairs,
+                                 const int32_t* ref_slots, const int32_t* tgt_slots, float* d_poses_out, uwt_stats* d_stats_out,
+                                 const float* d_seeds, const uwt_seed_options* sopt) {
+  Start start;
+  int st = seed_options(c, "uwt_track_batch_seeded_async", sopt, &start);
+  if (st) return st;
+  start.d_seeds = d_seeds;
+  st = track_batch_enqueue(c, first_slot, n_frames, grad_refs_only, n_pairs, ref_slots, tgt_slots, d_poses_out, d_stats_out, start);
   if (st) return st;
   return compute_end(c, c->dep_first, c->dep_n);
 }

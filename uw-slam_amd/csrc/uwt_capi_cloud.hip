@@ -265,4 +265,37 @@ int uwt_accumulate_trajectory_device_from_async(uwt_ctx* c, const float* d_poses
   return UWT_OK;
 }
 
+int uwt_predict_seeds_device_async(uwt_ctx* c, int32_t n, const float* d_prev, const float* d_cur, float* d_seed_out) {
+  if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
+  if (!c || !d_prev || !d_cur || !d_seed_out || n < 0) return fail(c, UWT_ERR_INVALID_ARG, "uwt_predict_seeds_device_async");
+  if (ranges_overlap(d_prev, d_seed_out, n) || ranges_overlap(d_cur, d_seed_out, n))
+    return fail(c, UWT_ERR_INVALID_ARG, "uwt_predict_seeds_device_async: d_seed_out overlaps an input");
+  if (n == 0) return UWT_OK;
+  const int tb = 64;
+  hipLaunchKernelGGL(k_predict_seeds, dim3((n + tb - 1) / tb), dim3(tb), 0, c->stream, d_prev, d_cur, n, d_seed_out);
+  HIPCHK(c, hipGetLastError());
+  return UWT_OK;
+}
+
+int uwt_predict_seeds(uwt_ctx* c, int32_t n, const float* prev, const float* cur, float* seed_out) {
+  if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
+  if (!c || !prev || !cur || !seed_out || n < 0) return fail(c, UWT_ERR_INVALID_ARG, "uwt_predict_seeds");
+  if (n == 0) return UWT_OK;
+  // scratch: [prev | cur | seeds]
+  Carve cv(256, c->guard_bytes);
+  const size_t rows = 7 * (size_t)n, o_prev = cv.take<float>(rows), o_cur = cv.take<float>(rows), o_out = cv.take<float>(rows);
+  int st = c->scratch.reserve(c, c->stream, cv);
+  if (st) return st;
+  float* d_prev = Carve::at<float>(c->scratch.p, o_prev);
+  float* d_cur = Carve::at<float>(c->scratch.p, o_cur);
+  float* d_out = Carve::at<float>(c->scratch.p, o_out);
+  HIPCHK(c, hipMemcpyAsync(d_prev, prev, sizeof(float) * rows, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_cur, cur, sizeof(float) * rows, hipMemcpyHostToDevice, c->stream));
+  st = uwt_predict_seeds_device_async(c, n, d_prev, d_cur, d_out);
+  if (st) return st;
+  HIPCHK(c, hipMemcpyAsync(seed_out, d_out, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return UWT_OK;
+}
+
 }  // extern "C"

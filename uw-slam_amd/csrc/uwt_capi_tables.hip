@@ -273,8 +273,9 @@ struct TableLevel {
 // opt (checked by table_options): robust weights and / or the bilinear sampler — an evaluation is then k_table_hist (weights only)
 // + k_table_general, records of the general kind; the pairs' histogram rows are cleared here once, every scale pass leaves them so.
 // q.weights and q.sampler are not looked at.
+// start: where the alignments start and how they cross the levels (the seeded entries; the default: identity, q's hand-off).
 int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const TableLevel* lv, uint32_t* recs, bool polls,
-                           const uwt_table_options& opt, float* d_poses, StatsOut* d_stats) {
+                           const uwt_table_options& opt, float* d_poses, StatsOut* d_stats, const Start& start = Start()) {
   const int tb = 128, blocks = (n_pairs + tb - 1) / tb;
   const bool general = opt.weights || opt.sampler;
   if (opt.weights) {
@@ -283,7 +284,8 @@ int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const T
     HIPCHK(c, hipMemsetAsync(c->hist, 0, sizeof(unsigned int) * kHistBins * (size_t)n_pairs, c->stream));
   }
   const GeneralArgs ga = {opt.sampler, opt.weights, q.gain, c->hist, c->scale};
-  hipLaunchKernelGGL(k_init_state, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, q.initial_error);
+  hipLaunchKernelGGL(k_init_state, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, q.initial_error, start.d_seeds,
+                     start.d_gate);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
   for (int lvl = q.first_level; lvl >= q.last_level; lvl--) {
@@ -315,7 +317,7 @@ int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const T
       if (st) return st;
       if (none_left) break;
     }
-    hipLaunchKernelGGL(k_level_end, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, lvl, q.handoff_scale_t, q.initial_error);
+    hipLaunchKernelGGL(k_level_end, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, lvl, start.scale_t(q), q.initial_error);
     HIPCHK(c, hipGetLastError());
   }
   hipLaunchKernelGGL(k_write_out, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, d_poses, d_stats);
@@ -327,7 +329,8 @@ int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const T
 // enqueue_table_estimate under feature_params and the call's options (null: identity weights, round()), which the host never
 // polls.  No read-back, no wait for the device.
 int features_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, const float* kp,
-                     const int32_t* n_kp, const uwt_table_options* opt_or_null, float* d_poses, StatsOut* d_stats) {
+                     const int32_t* n_kp, const uwt_table_options* opt_or_null, float* d_poses, StatsOut* d_stats,
+                     const Start& start = Start()) {
   uwt_table_options opt;
   int st = table_options(c, what, opt_or_null, &opt);
   if (st) return st;
@@ -345,7 +348,7 @@ int features_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* r
   int rows = 0;
   for (int i = 0; i < n_pairs; i++) rows = std::max(rows, std::min(n_kp[i], kPatchMaxKeypoints) * kPatchMaxRows);
   const TableLevel lv0 = {{c->feat_tab, c->feat_cnt, kFeatTableRows}, table_slices(rows)};
-  return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, opt, d_poses, d_stats);
+  return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, opt, d_poses, d_stats, start);
 }
 
 }  // namespace
@@ -370,19 +373,33 @@ int uwt_obtain_patch_points_batch(uwt_ctx* c, int32_t n_frames, const int32_t* s
 namespace {
 
 int features_async(uwt_ctx* c, const char* what, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, const float* kp,
-                   const int32_t* n_kp, const uwt_table_options* opt, float* d_poses_out, uwt_stats* d_stats_out) {
+                   const int32_t* n_kp, const uwt_table_options* opt, float* d_poses_out, uwt_stats* d_stats_out,
+                   const float* d_seeds = nullptr, const uwt_seed_options* sopt = nullptr) {
   if (c) (void)hipSetDevice(c->p.device);
   if (!c || !d_poses_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  int st = features_enqueue(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out));
+  Start start;
+  int st = seed_options(c, what, sopt, &start);
+  if (st) return st;
+  start.d_seeds = d_seeds;
+  st = seeds_clear_of(c, what, d_seeds, n_pairs, d_poses_out, d_stats_out);
+  if (st) return st;
+  st = features_enqueue(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out), start);
   if (st) return st;
   return compute_end(c, c->dep_first, c->dep_n);
 }
 
 int features_sync(uwt_ctx* c, const char* what, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, const float* kp,
-                  const int32_t* n_kp, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out) {
+                  const int32_t* n_kp, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out,
+                  const float* seeds = nullptr, const uwt_seed_options* sopt = nullptr) {
   if (c) (void)hipSetDevice(c->p.device);
   if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  int st = features_enqueue(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, c->d_poses, c->d_stats);
+  Start start;
+  int st = seed_options(c, what, sopt, &start);
+  if (st) return st;
+  if (seeds && (n_pairs < 1 || n_pairs > c->p.max_pairs)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": count outside 1..max_pairs");
+  st = stage_host_seeds(c, seeds, n_pairs, &start);
+  if (st) return st;
+  st = features_enqueue(c, what, n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, c->d_poses, c->d_stats, start);
   if (st) return st;
   return read_back_pairs(c, what, n_pairs, poses_out, stats_out);
 }
@@ -417,6 +434,20 @@ int uwt_estimate_pose_features_batch_opt(uwt_ctx* c, int32_t n_pairs, const int3
   return features_sync(c, "uwt_estimate_pose_features_batch_opt", n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, poses_out, stats_out);
 }
 
+int uwt_track_features_batch_seeded_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                          const float* kp, const int32_t* n_kp, const uwt_table_options* opt, float* d_poses_out,
+                                          uwt_stats* d_stats_out, const float* d_seeds, const uwt_seed_options* sopt) {
+  return features_async(c, "uwt_track_features_batch_seeded_async", n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, d_poses_out, d_stats_out,
+                        d_seeds, sopt);
+}
+
+int uwt_estimate_pose_features_batch_seeded(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                            const float* kp, const int32_t* n_kp, const uwt_table_options* opt, float* poses_out,
+                                            uwt_stats* stats_out, const float* seeds, const uwt_seed_options* sopt) {
+  return features_sync(c, "uwt_estimate_pose_features_batch_seeded", n_pairs, ref_slots, tgt_slots, kp, n_kp, opt, poses_out, stats_out,
+                       seeds, sopt);
+}
+
 // ---- semi-dense tracking for a batch of pairs: candidate tables built and evaluated on the device ------------------------
 namespace {
 
@@ -427,7 +458,8 @@ namespace {
 // polled under early_exit.  The only waits are the early-exit polls.  with_options: an _opt entry — weights and sampler are the
 // call's (opt_or_null, null: identity and round()), the context's are not looked at; else the context's must be identity and round().
 int candidates_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
-                       bool with_options, const uwt_table_options* opt_or_null, float* d_poses, StatsOut* d_stats) {
+                       bool with_options, const uwt_table_options* opt_or_null, float* d_poses, StatsOut* d_stats,
+                       const Start& start = Start()) {
   const uwt_params& p = c->p;
   uwt_table_options opt;
   int st = table_options(c, what, opt_or_null, &opt);
@@ -468,7 +500,7 @@ int candidates_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t*
     const int cells = c->lv[l].gw * c->lv[l].gh;   // the bound every pair's count obeys
     lv[l] = {{tab, cnt, cells}, table_slices(cells)};
   }
-  return enqueue_table_estimate(c, n_pairs, p, lv, (uint32_t*)c->cand_recs.p, p.early_exit != 0, opt, d_poses, d_stats);
+  return enqueue_table_estimate(c, n_pairs, p, lv, (uint32_t*)c->cand_recs.p, p.early_exit != 0, opt, d_poses, d_stats, start);
 }
 
 }  // namespace
@@ -476,20 +508,34 @@ int candidates_enqueue(uwt_ctx* c, const char* what, int n_pairs, const int32_t*
 namespace {
 
 int candidates_async(uwt_ctx* c, const char* what, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
-                     bool with_options, const uwt_table_options* opt, float* d_poses_out, uwt_stats* d_stats_out) {
+                     bool with_options, const uwt_table_options* opt, float* d_poses_out, uwt_stats* d_stats_out,
+                     const float* d_seeds = nullptr, const uwt_seed_options* sopt = nullptr) {
   if (c) (void)hipSetDevice(c->p.device);
   if (!c || !d_poses_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  int st = candidates_enqueue(c, what, n_pairs, ref_slots, tgt_slots, threshold, with_options, opt, d_poses_out,
-                              reinterpret_cast<StatsOut*>(d_stats_out));
+  Start start;
+  int st = seed_options(c, what, sopt, &start);
+  if (st) return st;
+  start.d_seeds = d_seeds;
+  st = seeds_clear_of(c, what, d_seeds, n_pairs, d_poses_out, d_stats_out);
+  if (st) return st;
+  st = candidates_enqueue(c, what, n_pairs, ref_slots, tgt_slots, threshold, with_options, opt, d_poses_out,
+                          reinterpret_cast<StatsOut*>(d_stats_out), start);
   if (st) return st;
   return compute_end(c, c->dep_first, c->dep_n);
 }
 
 int candidates_sync(uwt_ctx* c, const char* what, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, double threshold,
-                    bool with_options, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out) {
+                    bool with_options, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out,
+                    const float* seeds = nullptr, const uwt_seed_options* sopt = nullptr) {
   if (c) (void)hipSetDevice(c->p.device);
   if (!c || !poses_out) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  int st = candidates_enqueue(c, what, n_pairs, ref_slots, tgt_slots, threshold, with_options, opt, c->d_poses, c->d_stats);
+  Start start;
+  int st = seed_options(c, what, sopt, &start);
+  if (st) return st;
+  if (seeds && (n_pairs < 1 || n_pairs > c->p.max_pairs)) return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": count outside 1..max_pairs");
+  st = stage_host_seeds(c, seeds, n_pairs, &start);
+  if (st) return st;
+  st = candidates_enqueue(c, what, n_pairs, ref_slots, tgt_slots, threshold, with_options, opt, c->d_poses, c->d_stats, start);
   if (st) return st;
   return read_back_pairs(c, what, n_pairs, poses_out, stats_out);
 }
@@ -518,6 +564,20 @@ int uwt_estimate_pose_candidates_batch_opt(uwt_ctx* c, int32_t n_pairs, const in
                                            double threshold, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out) {
   return candidates_sync(c, "uwt_estimate_pose_candidates_batch_opt", n_pairs, ref_slots, tgt_slots, threshold, true, opt, poses_out,
                          stats_out);
+}
+
+int uwt_track_candidates_batch_seeded_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                            double threshold, const uwt_table_options* opt, float* d_poses_out, uwt_stats* d_stats_out,
+                                            const float* d_seeds, const uwt_seed_options* sopt) {
+  return candidates_async(c, "uwt_track_candidates_batch_seeded_async", n_pairs, ref_slots, tgt_slots, threshold, true, opt, d_poses_out,
+                          d_stats_out, d_seeds, sopt);
+}
+
+int uwt_estimate_pose_candidates_batch_seeded(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                              double threshold, const uwt_table_options* opt, float* poses_out, uwt_stats* stats_out,
+                                              const float* seeds, const uwt_seed_options* sopt) {
+  return candidates_sync(c, "uwt_estimate_pose_candidates_batch_seeded", n_pairs, ref_slots, tgt_slots, threshold, true, opt, poses_out,
+                         stats_out, seeds, sopt);
 }
 
 // ---- the caller's own tables: a batch of one pair whose tables arrive from the host -----------------------------------------
@@ -581,12 +641,14 @@ int uwt::features_device_begin(uwt_ctx* c, const char* what, int n_pairs, const 
 
 // features_enqueue behind its staging: the key points and their counts are on the device already, so the grid's slices are the
 // bound of any table (a pair's own slice count comes from its producer's count: the bound shows in no bit)
-int uwt::features_device_enqueue(uwt_ctx* c, int n_pairs, float* d_poses, uwt_stats* d_stats) {
+int uwt::features_device_enqueue(uwt_ctx* c, int n_pairs, float* d_poses, uwt_stats* d_stats, const Start& start) {
   int st = enqueue_patch_producer(c, n_pairs, c->d_ref);
   if (st) return st;
+  Start gated = start;
+  gated.d_gate = c->feat_nkp;
   const TableLevel lv0 = {{c->feat_tab, c->feat_cnt, kFeatTableRows}, table_slices(kFeatTableRows)};
   return enqueue_table_estimate(c, n_pairs, feature_params(c), &lv0, c->feat_recs, false, kIdentityTables, d_poses,
-                                reinterpret_cast<StatsOut*>(d_stats));
+                                reinterpret_cast<StatsOut*>(d_stats), gated);
 }
 
 int uwt::candidates_level0_enqueue(uwt_ctx* c, int n, const int* d_slots, double threshold, const float4** tab, size_t* stride,

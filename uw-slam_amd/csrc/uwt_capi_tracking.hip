@@ -128,7 +128,7 @@ int tracking_check(uwt_ctx* c, const char* what, const TrackDetector& d, int n_p
 
 // The chain, enqueued on the context stream (the arguments have passed tracking_check; the scratch holds `l` at its base).
 int tracking_enqueue(uwt_ctx* c, const char* what, const TrackDetector& d, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
-                     int cap, const TrackLayout& l, const uwt_tracking_io& io) {
+                     int cap, const TrackLayout& l, const uwt_tracking_io& io, const Start& start = Start()) {
   void* b = c->track_buf.p;
   int* d_path = Carve::at<int>(b, l.path);
   int* d_refused = Carve::at<int>(b, l.refused);
@@ -176,7 +176,7 @@ int tracking_enqueue(uwt_ctx* c, const char* what, const TrackDetector& d, int n
   launch_good_keypoints(c->stream, ga);
   HIPCHK(c, hipGetLastError());
   // 6. ObtainPatchesPoints + EstimatePoseFeatures
-  st = features_device_enqueue(c, n_pairs, io.d_poses, io.d_stats);
+  st = features_device_enqueue(c, n_pairs, io.d_poses, io.d_stats, start);
   if (st) return st;
   TrackInfoArgs ia;
   ia.refused = d_refused; ia.outside = d_outside; ia.path = d_path;
@@ -195,10 +195,26 @@ int tracking_enqueue(uwt_ctx* c, const char* what, const TrackDetector& d, int n
 
 // The asynchronous form of either detector (`what`: the entry's name).
 int tracking_async(uwt_ctx* c, const char* what, const TrackDetector& d, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
-                   int cap, const uwt_tracking_io* io) {
+                   int cap, const uwt_tracking_io* io, const float* d_seeds = nullptr, const uwt_seed_options* sopt = nullptr) {
   if (!c || !io || !io->d_poses || !io->d_info || !io->d_good || !io->d_kept_prev || !io->d_kept_cur || !io->d_n_matches)
     return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  int st = tracking_check(c, what, d, n_pairs, ref_slots, tgt_slots, io->d_prev_kp != nullptr, io->d_n_prev != nullptr);
+  Start start;
+  int st = seed_options(c, what, sopt, &start);
+  if (st) return st;
+  start.d_seeds = d_seeds;
+  st = seeds_clear_of(c, what, d_seeds, n_pairs, io->d_poses, io->d_stats);
+  if (st) return st;
+  if (d_seeds && n_pairs >= 1 && cap >= 1) {   // every output of the chain: the front end writes its own before the seeds are read
+    const size_t P = (size_t)n_pairs, rows = P * (size_t)cap;
+    const struct { const void* p; size_t bytes; } outs[] = {{io->d_info, sizeof(uwt_tracking_info) * P}, {io->d_good, sizeof(uwt_match) * rows},
+                                                            {io->d_kept_prev, sizeof(uwt_keypoint) * rows},
+                                                            {io->d_kept_cur, sizeof(uwt_keypoint) * rows}, {io->d_n_matches, sizeof(int32_t) * P}};
+    for (const auto& o : outs) {
+      st = seeds_clear_of_range(c, what, d_seeds, n_pairs, o.p, o.bytes);
+      if (st) return st;
+    }
+  }
+  st = tracking_check(c, what, d, n_pairs, ref_slots, tgt_slots, io->d_prev_kp != nullptr, io->d_n_prev != nullptr);
   if (st) return st;
   if (io->d_prev_kp && (io->d_prev_kp == io->d_kept_prev || io->d_prev_kp == io->d_kept_cur || io->d_n_prev == io->d_n_matches))
     return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": the provided key points or counts are also an output of this call");
@@ -206,16 +222,22 @@ int tracking_async(uwt_ctx* c, const char* what, const TrackDetector& d, int n_p
   const TrackLayout l = track_carve(cv, n_pairs, cap, d.desc_row);
   st = c->track_buf.reserve(c, c->stream, cv);
   if (st) return st;
-  return tracking_enqueue(c, what, d, n_pairs, ref_slots, tgt_slots, cap, l, *io);
+  return tracking_enqueue(c, what, d, n_pairs, ref_slots, tgt_slots, cap, l, *io, start);
 }
 
 // The synchronous form of either detector, host in and out.
 int tracking_sync(uwt_ctx* c, const char* what, const TrackDetector& d, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, int cap,
                   const uwt_keypoint* prev_kp, const int32_t* n_prev, float* poses_out, uwt_stats* stats_out, uwt_tracking_info* info_out,
-                  uwt_match* good_out, uwt_keypoint* kept_prev_out, uwt_keypoint* kept_cur_out) {
+                  uwt_match* good_out, uwt_keypoint* kept_prev_out, uwt_keypoint* kept_cur_out, const float* seeds = nullptr,
+                  const uwt_seed_options* sopt = nullptr) {
   if (!c || !poses_out || !info_out || !good_out || !kept_prev_out || !kept_cur_out)
     return fail(c, UWT_ERR_INVALID_ARG, std::string(what) + ": null argument");
-  int st = tracking_check(c, what, d, n_pairs, ref_slots, tgt_slots, prev_kp != nullptr, n_prev != nullptr);
+  Start start;
+  int st = seed_options(c, what, sopt, &start);
+  if (st) return st;
+  st = tracking_check(c, what, d, n_pairs, ref_slots, tgt_slots, prev_kp != nullptr, n_prev != nullptr);
+  if (st) return st;
+  st = stage_host_seeds(c, seeds, n_pairs, &start);
   if (st) return st;
   Carve cv(256, c->guard_bytes);
   const TrackLayout l = track_carve(cv, n_pairs, cap, d.desc_row);
@@ -238,7 +260,7 @@ int tracking_sync(uwt_ctx* c, const char* what, const TrackDetector& d, int n_pa
     HIPCHK(c, hipMemcpyAsync((void*)io.d_prev_kp, prev_kp, sizeof(uwt_keypoint) * recs, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync((void*)io.d_n_prev, n_prev, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, c->stream));
   }
-  st = tracking_enqueue(c, what, d, n_pairs, ref_slots, tgt_slots, cap, l, io);
+  st = tracking_enqueue(c, what, d, n_pairs, ref_slots, tgt_slots, cap, l, io, start);
   if (st) return st;
   std::vector<uwt_stats> stats((size_t)n_pairs);
   std::vector<int32_t> counts((size_t)n_pairs);
@@ -299,6 +321,45 @@ int uwt_tracking_orb_batch_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref
   if (!c) return UWT_ERR_INVALID_ARG;
   (void)hipSetDevice(c->p.device);
   return tracking_async(c, "uwt_tracking_orb_batch_async", orb_detector(c, params, cap), n_pairs, ref_slots, tgt_slots, cap, io);
+}
+
+int uwt_tracking_batch_seeded(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                              const uwt_tracking_params* params, int32_t cap, const uwt_keypoint* prev_kp, const int32_t* n_prev,
+                              float* poses_out, uwt_stats* stats_out, uwt_tracking_info* info_out, uwt_match* good_out,
+                              uwt_keypoint* kept_prev_out, uwt_keypoint* kept_cur_out, const float* seeds, const uwt_seed_options* sopt) {
+  if (!c) return UWT_ERR_INVALID_ARG;
+  (void)hipSetDevice(c->p.device);
+  return tracking_sync(c, "uwt_tracking_batch_seeded", surf_detector(c, params, cap), n_pairs, ref_slots, tgt_slots, cap, prev_kp, n_prev,
+                       poses_out, stats_out, info_out, good_out, kept_prev_out, kept_cur_out, seeds, sopt);
+}
+
+int uwt_tracking_orb_batch_seeded(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                  const uwt_tracking_orb_params* params, int32_t cap, const uwt_keypoint* prev_kp, const int32_t* n_prev,
+                                  float* poses_out, uwt_stats* stats_out, uwt_tracking_info* info_out, uwt_match* good_out,
+                                  uwt_keypoint* kept_prev_out, uwt_keypoint* kept_cur_out, const float* seeds,
+                                  const uwt_seed_options* sopt) {
+  if (!c) return UWT_ERR_INVALID_ARG;
+  (void)hipSetDevice(c->p.device);
+  return tracking_sync(c, "uwt_tracking_orb_batch_seeded", orb_detector(c, params, cap), n_pairs, ref_slots, tgt_slots, cap, prev_kp,
+                       n_prev, poses_out, stats_out, info_out, good_out, kept_prev_out, kept_cur_out, seeds, sopt);
+}
+
+int uwt_tracking_batch_seeded_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                    const uwt_tracking_params* params, int32_t cap, const uwt_tracking_io* io, const float* d_seeds,
+                                    const uwt_seed_options* sopt) {
+  if (!c) return UWT_ERR_INVALID_ARG;
+  (void)hipSetDevice(c->p.device);
+  return tracking_async(c, "uwt_tracking_batch_seeded_async", surf_detector(c, params, cap), n_pairs, ref_slots, tgt_slots, cap, io,
+                        d_seeds, sopt);
+}
+
+int uwt_tracking_orb_batch_seeded_async(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,
+                                        const uwt_tracking_orb_params* params, int32_t cap, const uwt_tracking_io* io,
+                                        const float* d_seeds, const uwt_seed_options* sopt) {
+  if (!c) return UWT_ERR_INVALID_ARG;
+  (void)hipSetDevice(c->p.device);
+  return tracking_async(c, "uwt_tracking_orb_batch_seeded_async", orb_detector(c, params, cap), n_pairs, ref_slots, tgt_slots, cap, io,
+                        d_seeds, sopt);
 }
 
 int uwt_tracking_orb_batch(uwt_ctx* c, int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,

@@ -207,6 +207,10 @@ struct uwt_ctx {
   struct SmallResults { float poses[kSmallBatch * 7]; StatsOut stats[kSmallBatch]; int cut; };
   SmallResults* h_small = nullptr;      // pinned, device-visible
   SmallResults* d_small = nullptr;      // its device address
+  // the seeded synchronous calls: the caller's host seeds (max_pairs x 7 floats) are copied here before anything is enqueued and
+  // the kernels read them in place (page-locked, device-visible: no copy, no launch); a rerun of the speculative call reads them again
+  float* h_seeds = nullptr;             // pinned, made on first use
+  float* d_seeds = nullptr;             // its device address
   bool deferred = false;                // uwt_set_deferred: stage calls return once enqueued
   unsigned poll_seq = 0;                // batch path: read-backs alternate between two counters / events (taken one evaluation late)
   hipEvent_t ev_poll[2] = {};
@@ -237,7 +241,22 @@ inline int fail(uwt_ctx* c, int code, const std::string& msg) {
       return fail(ctx, UWT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                     \
   } while (0)
 
+// Where a seeded call's alignments start and how their poses cross the level boundaries (uwt.h "seeded calls"): d_seeds null = the
+// identity; keep = uwt_seed_options::handoff 1.  The default is every unseeded entry's.
+struct Start {
+  const float* d_seeds = nullptr;   // n_pairs x 7 floats in memory the device reads, or null
+  int keep = 0;
+  const int* d_gate = nullptr;      // table calls: per-pair counts, a pair whose count is 0 starts at the identity (k_init_state), or null
+  // (handoff_scale_t is any int, non-zero = on, as the kernels always read it: only `keep` can give kHandoffKeep)
+  int scale_t(const uwt_params& q) const { return keep ? kHandoffKeep : (q.handoff_scale_t != 0 ? 1 : 0); }
+};
+
 // ---- helpers of uwt_capi.hip that the other host units call (described at their definitions) ------------------------------
+int seed_options(uwt_ctx* c, const char* what, const uwt_seed_options* sopt_or_null, Start* out);
+int seeds_clear_of(uwt_ctx* c, const char* what, const float* d_seeds, int n_pairs, const void* d_poses_out, const void* d_stats_out);
+// the same against any output of a call: `bytes` bytes at `out` (null: no such output)
+int seeds_clear_of_range(uwt_ctx* c, const char* what, const float* d_seeds, int n_pairs, const void* out, size_t bytes);
+int stage_host_seeds(uwt_ctx* c, const float* seeds_or_null, int n_pairs, Start* start);
 inline bool slot_range_ok(const uwt_ctx* c, int first, int n) { return first >= 0 && n >= 0 && (long long)first + n <= c->p.max_frames; }
 template <typename T>
 int launch_resize(uwt_ctx* c, const T* src, T* dst, int sw, int sh, int src_pitch, int dw, int dh, int dst_pitch, size_t sfs,
@@ -295,9 +314,9 @@ int ransac_device_enqueue(uwt_ctx* c, int n_pairs, int cap, const uwt_ransac_par
                           uwt_ransac_info* d_info);
 // the live call from key points that are in device memory: features_device_begin checks the pair lists, makes the context's feat_kp
 // (max_pairs x 200 float2) / feat_nkp exist and sends the lists; once the caller's kernels have filled both, features_device_enqueue
-// runs the patch producer and the alignment from them
+// runs the patch producer and the alignment from them (start: a seeded chain's; a pair without a key point starts at the identity)
 int features_device_begin(uwt_ctx* c, const char* what, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots);
-int features_device_enqueue(uwt_ctx* c, int n_pairs, float* d_poses, uwt_stats* d_stats);
+int features_device_enqueue(uwt_ctx* c, int n_pairs, float* d_poses, uwt_stats* d_stats, const Start& start = Start());
 // Tracker::ObtainCandidatePoints on level 0 for the n frames of the device slot list d_slots (uwt_capi_tables.hip: the producer of the
 // batched semi-dense calls over cand_tab / cand_cnt / cand_work, grown to what the call needs), enqueued on the context stream: frame
 // f's table at *tab + f * *stride, its full count at (*counts)[f]

@@ -2572,6 +2572,52 @@ static __global__ __launch_bounds__(kUpdateBlock) void k_gn_update(const UpdateA
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Where an alignment starts and how its pose crosses a level boundary (the seeded entries, uwt.h "seeded calls").
+// first_state: the state in front of the first evaluation of the first iterated level.  seeds null: the identity of
+// src/Tracker.cpp:385.  Else pair's row of seeds (7 floats qx qy qz qw tx ty tz, read as they are: nothing normalises or
+// scales them); a row with a non-finite entry starts nothing: the pair carries UWT_ERR_INVALID_ARG and the identity from
+// here on, and every launch returns at once for it (status != 0), as for any failed pair.
+// level_handoff: scale_t 0 / 1 = the reference's hand-off (se3_handoff under uwt_params::handoff_scale_t), kHandoffKeep =
+// uwt_seed_options::handoff 1: the pose crosses unchanged.  Both sit in the block-uniform preamble and the update tail.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int kHandoffKeep = 2;
+constexpr int kStatusBadSeed = 1;   // UWT_ERR_INVALID_ARG
+
+__device__ __forceinline__ PairState first_state(const float* __restrict__ seeds, int pair, float initial_error) {
+  PairState st;
+  pose_identity(st.pose);  // src/Tracker.cpp:385
+  st.last_error = initial_error;
+  st.error = 0.f;
+  st.level_done = 0;
+  st.status = 0;
+  st.iters = 0;
+  st.n_valid = 0;
+  if (seeds) {
+    float v[7];
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+      v[k] = seeds[7 * (size_t)pair + k];
+      finite = finite && (__float_as_uint(v[k]) & 0x7f800000u) != 0x7f800000u;
+    }
+    if (finite) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) st.pose.q[k] = v[k];
+#pragma unroll
+      for (int k = 0; k < 3; k++) st.pose.t[k] = v[4 + k];
+    } else {
+      st.status = kStatusBadSeed;
+    }
+  }
+  return st;
+}
+
+__device__ __forceinline__ bool level_handoff(Pose& p, int scale_t) {
+  if (scale_t == kHandoffKeep) return true;
+  return se3_handoff(p, scale_t != 0);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // k_iterate: one launch = one Gauss-Newton iteration of one pyramid level for a whole batch, on the dense
 // nearest-neighbour / identity-weights path.  Every block first brings its pair's state up to date — the update that
 // belongs to the PREVIOUS evaluation (records of the other parity), and the level hand-off when this launch opens a new
@@ -2587,7 +2633,8 @@ struct IterArgs {
   int mode;                   // 0: first evaluation of the alignment (fresh state); 1: update, evaluate; 2: update, hand-off, evaluate;
                               // 3: evaluate from state_in as it is (the launch behind k_coarse)
   int prev_lvl;               // level the pending update / hand-off belongs to (mode 2)
-  int scale_t;
+  int scale_t;                // level_handoff's: 0 / 1 the reference's hand-off, kHandoffKeep
+  const float* seeds;         // mode 0: the pairs' start poses (first_state), null = the identity
   float initial_error;
   int* cut_short;             // optional (speculative launching, early-exit schedules): set when a level's launches ran out
                               // before the pair's exit test fired, i.e. the host stopped launching too early (may be host memory)
@@ -2597,16 +2644,7 @@ struct IterArgs {
 
 __device__ __forceinline__ PairState iterate_state(const IterArgs& ia, int pair, unsigned char* lds, bool count_active) {
   PairState st;
-  if (ia.mode == 0) {
-    pose_identity(st.pose);  // src/Tracker.cpp:385
-    st.last_error = ia.initial_error;
-    st.error = 0.f;
-    st.level_done = 0;
-    st.status = 0;
-    st.iters = 0;
-    st.n_valid = 0;
-    return st;
-  }
+  if (ia.mode == 0) return first_state(ia.seeds, pair, ia.initial_error);
   if (ia.mode == 3) return ia.state_in[pair];   // behind k_coarse: the state is current, nothing is pending
   st = update_compute(ia.u, ia.u.partials + (size_t)pair * ia.u.slices * kRecWords, &ia.state_in[pair], lds, count_active);
   if (ia.mode == 2) {   // end of a pyramid level: hand-off (src/Tracker.cpp:580-590) and re-arm for the next level (:392-393)
@@ -2614,7 +2652,7 @@ __device__ __forceinline__ PairState iterate_state(const IterArgs& ia, int pair,
     if (ia.cut_short && ia.u.early_exit && !st.level_done && st.status == 0 && count_active && threadIdx.x == 0)
       __hip_atomic_store(ia.cut_short, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if (st.status == 0 && ia.prev_lvl != 0) {
-      if (!se3_handoff(st.pose, ia.scale_t != 0)) st.status = 1;  // SOPHUS_ENSURE would abort
+      if (!level_handoff(st.pose, ia.scale_t)) st.status = 1;  // SOPHUS_ENSURE would abort
     }
     st.level_done = 0;
     st.last_error = ia.initial_error;
@@ -2691,7 +2729,8 @@ struct CoarseArgs {
   int n_levels;
   UpdateArgs u;                        // max_iters, early_exit, epsilon, gain
   PairState* state_out;
-  int scale_t;
+  int scale_t;                         // see IterArgs
+  const float* seeds;                  // !resume: the pairs' start poses (first_state), null = the identity
   float initial_error;
   int inline_pairs;                    // see IterArgs
   int pair_slots[4];
@@ -2737,13 +2776,7 @@ __device__ __forceinline__ void coarse_body(const CoarseArgs& ca) {
   if (ca.resume) {
     st = ca.state_out[pair];   // a level of a batch behind the coarser one's launch: re-armed by that launch's tail
   } else {
-    pose_identity(st.pose);  // src/Tracker.cpp:385
-    st.last_error = ca.initial_error;
-    st.error = 0.f;
-    st.level_done = 0;
-    st.status = 0;
-    st.iters = 0;
-    st.n_valid = 0;
+    st = first_state(ca.seeds, pair, ca.initial_error);
   }
 #pragma unroll
   for (int li = 0; li < NLEV; li++) {
@@ -2776,7 +2809,7 @@ __device__ __forceinline__ void coarse_body(const CoarseArgs& ca) {
     }
     // end of a pyramid level: hand-off (src/Tracker.cpp:580-590) and re-arm for the next level (:392-393)
     if (st.status == 0 && ca.level_id[li] != 0) {
-      if (!se3_handoff(st.pose, ca.scale_t != 0)) st.status = 1;  // SOPHUS_ENSURE would abort
+      if (!level_handoff(st.pose, ca.scale_t)) st.status = 1;  // SOPHUS_ENSURE would abort
     }
     st.level_done = 0;
     st.last_error = ca.initial_error;
@@ -2808,13 +2841,7 @@ __global__ __launch_bounds__(kBlock) void k_coarse_weighted(const CoarseArgs ca)
   if (ca.resume) {
     st = ca.state_out[pair];
   } else {
-    pose_identity(st.pose);  // src/Tracker.cpp:385
-    st.last_error = ca.initial_error;
-    st.error = 0.f;
-    st.level_done = 0;
-    st.status = 0;
-    st.iters = 0;
-    st.n_valid = 0;
+    st = first_state(ca.seeds, pair, ca.initial_error);
   }
 #pragma unroll
   for (int li = 0; li < NLEV; li++) {
@@ -2872,7 +2899,7 @@ __global__ __launch_bounds__(kBlock) void k_coarse_weighted(const CoarseArgs ca)
     }
     // end of a pyramid level: hand-off (src/Tracker.cpp:580-590) and re-arm for the next level (:392-393)
     if (st.status == 0 && ca.level_id[li] != 0) {
-      if (!se3_handoff(st.pose, ca.scale_t != 0)) st.status = 1;  // SOPHUS_ENSURE would abort
+      if (!level_handoff(st.pose, ca.scale_t)) st.status = 1;  // SOPHUS_ENSURE would abort
     }
     st.level_done = 0;
     st.last_error = ca.initial_error;
@@ -2911,18 +2938,15 @@ static __global__ void k_set_pose(PairState* state, Pose pose, float initial_err
   state[0] = st;
 }
 
-static __global__ void k_init_state(PairState* state, int n, float initial_error) {
+// `state`, `seeds` (null: the identity) and `gate` point at the first pair of the launch.  gate (the chained tracking call, else
+// null): a pair whose count is 0 — no key point reached the live call: every pair the front end failed — starts at the identity
+// whatever its seed row holds, so that its record is the unseeded call's.
+static __global__ void k_init_state(PairState* state, int n, float initial_error, const float* __restrict__ seeds,
+                                    const int* __restrict__ gate) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  PairState st;
-  pose_identity(st.pose);  // src/Tracker.cpp:385
-  st.last_error = initial_error;
-  st.error = 0.f;
-  st.level_done = 0;
-  st.status = 0;
-  st.iters = 0;
-  st.n_valid = 0;
-  state[i] = st;
+  const bool seeded = seeds && !(gate && gate[i] == 0);
+  state[i] = first_state(seeded ? seeds : nullptr, i, initial_error);
 }
 
 // end of a pyramid level: hand-off (src/Tracker.cpp:580-590) and re-arm for the next level (:392-393)
@@ -2931,7 +2955,7 @@ static __global__ void k_level_end(PairState* state, int n, int lvl, int scale_t
   if (i >= n) return;
   PairState st = state[i];
   if (st.status == 0 && lvl != 0) {
-    if (!se3_handoff(st.pose, scale_t != 0)) st.status = 1;  // SOPHUS_ENSURE would abort
+    if (!level_handoff(st.pose, scale_t)) st.status = 1;  // SOPHUS_ENSURE would abort
   }
   st.level_done = 0;
   st.last_error = initial_error;
@@ -3525,6 +3549,48 @@ static __global__ void k_trajectory_from(const float* __restrict__ poses, int n,
   for (int k = 0; k < 4; k++) prev.q[k] = prev7[k];
   for (int k = 0; k < 3; k++) prev.t[k] = prev7[4 + k];
   trajectory_walk(poses, n, prev, t_scale, reference_axes, out);
+}
+
+// The constant-velocity motion model in keyframe coordinates (uwt_predict_seeds_device_async): seed = (cur * prev^-1) * cur, one
+// thread per row.  The inverse as uwt.h states it operation by operation — the conjugate, its rotation matrix in f32 (quat_to_rot),
+// each translation row in f64 (the products of two floats are exact there, so contraction changes nothing), rounded once — and the
+// products se3_mul's.  A non-finite input row gives an all-NaN seed row.
+static __global__ void k_predict_seeds(const float* __restrict__ prev, const float* __restrict__ cur, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float a[7], b[7];
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    a[k] = prev[7 * (size_t)i + k];
+    b[k] = cur[7 * (size_t)i + k];
+    finite = finite && (__float_as_uint(a[k]) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(b[k]) & 0x7f800000u) != 0x7f800000u;
+  }
+  float* o = out + 7 * (size_t)i;
+  if (!finite) {
+#pragma unroll
+    for (int k = 0; k < 7; k++) o[k] = __uint_as_float(0x7fc00000u);
+    return;
+  }
+  Pose inv, c, rel, seed;
+  inv.q[0] = -a[0]; inv.q[1] = -a[1]; inv.q[2] = -a[2]; inv.q[3] = a[3];
+  float R[9];
+  quat_to_rot(inv.q, R);
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double s = ((double)R[3 * k] * (double)a[4] + (double)R[3 * k + 1] * (double)a[5]) + (double)R[3 * k + 2] * (double)a[6];
+    inv.t[k] = (float)(-s);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) c.q[k] = b[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) c.t[k] = b[4 + k];
+  se3_mul(c, inv, rel);
+  se3_mul(rel, c, seed);
+#pragma unroll
+  for (int k = 0; k < 4; k++) o[k] = seed.q[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) o[4 + k] = seed.t[k];
 }
 
 // The same accumulation as a prefix product (SE(3) composition is associative; in floats the grouping shows in the last

@@ -120,6 +120,23 @@ class Tracker:
         _previous_frame.rigid_transformation_ = poses[0]
         return stats[0]
 
+    def EstimatePoseSeeded(self, _previous_frame, _current_frame, seed, handoff=0):
+        """EstimatePose from a start pose (uwt_estimate_pose_batch_seeded): seed = qx qy qz qw tx ty tz, the pose in front of the first
+        evaluation, used as given — a keyframe's prediction (PredictSeeds), the previous pair's pose, another stage's result.
+        handoff: 0 / "reference" the reference's level hand-off, 1 / "keep" the pose crosses the levels unchanged."""
+        a, b = self._bind(_previous_frame), self._bind(_current_frame)
+        if not _previous_frame.obtained_gradients_:
+            raise RuntimeError("ApplyGradient(previous_frame) must run before EstimatePoseSeeded (or its slot was reused since)")
+        poses, stats = self._ctx.estimate_pose_batch_seeded([a], [b], np.asarray(seed, np.float32).reshape(1, 7), handoff,
+                                                            raise_on_pair_failure=True)
+        _previous_frame.rigid_transformation_ = poses[0]
+        return stats[0]
+
+    def PredictSeeds(self, prev, cur):
+        """The constant-velocity motion model in keyframe coordinates (uwt_predict_seeds): prev = the poses keyframe -> frame p - 1,
+        cur = keyframe -> frame p, [n, 7] each; returns the seeds (cur * prev^-1) * cur for keyframe -> frame p + 1."""
+        return self._ctx.predict_seeds(prev, cur)
+
     def FastEstimatePose(self, _previous_frame, _current_frame):
         """include/Tracker.h:124 — the vectorised prototype's schedule (levels PYRAMID_LEVELS-1 .. 0, <= 50 iterations,
         gain 50; src/Tracker.cpp:877-885, 1082) over EstimatePose's per-point terms.  The reference body is broken
@@ -179,37 +196,49 @@ class Tracker:
         _previous_frame.rigid_transformation_ = pose
         return st
 
-    def EstimatePoseFeaturesBatch(self, _pairs, weights=None, sampler=None):
+    def EstimatePoseFeaturesBatch(self, _pairs, weights=None, sampler=None, seeds=None, handoff=None):
         """System::Tracking's live call (src/System.cpp:214-219) for a list of (previous, current) frame pairs in one call
         (uwt_estimate_pose_features_batch, as uw::Tracker::EstimatePoseFeaturesBatch): each previous frame's keypoints_ go in,
         its rigid_transformation_ comes out.  The reference's constants are the call's own; the tracker's params are not touched.
         weights (0 identity, 1 Tukey, 2 Huber) / sampler (0 round(), 1 bilinear), either given: the call's own options
-        (uwt_estimate_pose_features_batch_opt).  Returns the per-pair stats."""
+        (uwt_estimate_pose_features_batch_opt).  seeds ([P, 7]) / handoff, either given: the pairs' start poses
+        (uwt_estimate_pose_features_batch_seeded).  Returns the per-pair stats."""
         slots = [(self._bind(a), self._bind(b)) for a, b in _pairs]
         for (a, b), (sa, sb) in zip(_pairs, slots):   # binding a later pair's frame may have taken an earlier frame's slot
             if a._slot != sa or b._slot != sb:
                 raise RuntimeError("EstimatePoseFeaturesBatch: more frames than slots (max_frames)")
             if not a.obtained_gradients_:
                 raise RuntimeError("ApplyGradient(previous_frame) must run before EstimatePoseFeaturesBatch (or its slot was reused since)")
-        poses, stats = self._ctx.estimate_pose_features_batch([s[0] for s in slots], [s[1] for s in slots],
-                                                              [a.keypoints_ for a, _ in _pairs], weights=weights, sampler=sampler)
+        if seeds is None and handoff is None:
+            poses, stats = self._ctx.estimate_pose_features_batch([s[0] for s in slots], [s[1] for s in slots],
+                                                                  [a.keypoints_ for a, _ in _pairs], weights=weights, sampler=sampler)
+        else:
+            poses, stats = self._ctx.estimate_pose_features_batch_seeded([s[0] for s in slots], [s[1] for s in slots],
+                                                                         [a.keypoints_ for a, _ in _pairs], seeds, handoff,
+                                                                         weights=weights, sampler=sampler)
         for (a, _), pose in zip(_pairs, poses):
             a.rigid_transformation_ = pose.copy()
         return stats
 
-    def EstimatePoseCandidatesBatch(self, _pairs, gradient_threshold=20.0, weights=None, sampler=None):
+    def EstimatePoseCandidatesBatch(self, _pairs, gradient_threshold=20.0, weights=None, sampler=None, seeds=None, handoff=None):
         """Semi-dense tracking for a list of (previous, current) frame pairs in one call (uwt_estimate_pose_candidates_batch, as
         uw::Tracker::EstimatePoseCandidatesBatch): ObtainCandidatePoints(previous) on the iterated levels, then EstimatePose over
         those tables under the tracker's params; each previous frame's rigid_transformation_ comes out.  weights / sampler, either
-        given: the call's own options (uwt_estimate_pose_candidates_batch_opt).  Returns the per-pair stats."""
+        given: the call's own options (uwt_estimate_pose_candidates_batch_opt).  seeds ([P, 7]) / handoff, either given: the pairs'
+        start poses (uwt_estimate_pose_candidates_batch_seeded; the weights and the sampler are then the call's, identity and round()
+        unless given).  Returns the per-pair stats."""
         slots = [(self._bind(a), self._bind(b)) for a, b in _pairs]
         for (a, b), (sa, sb) in zip(_pairs, slots):   # binding a later pair's frame may have taken an earlier frame's slot
             if a._slot != sa or b._slot != sb:
                 raise RuntimeError("EstimatePoseCandidatesBatch: more frames than slots (max_frames)")
             if not a.obtained_gradients_:
                 raise RuntimeError("ApplyGradient(previous_frame) must run before EstimatePoseCandidatesBatch (or its slot was reused since)")
-        poses, stats = self._ctx.estimate_pose_candidates_batch([s[0] for s in slots], [s[1] for s in slots], gradient_threshold,
-                                                                weights=weights, sampler=sampler)
+        if seeds is None and handoff is None:
+            poses, stats = self._ctx.estimate_pose_candidates_batch([s[0] for s in slots], [s[1] for s in slots], gradient_threshold,
+                                                                    weights=weights, sampler=sampler)
+        else:
+            poses, stats = self._ctx.estimate_pose_candidates_batch_seeded([s[0] for s in slots], [s[1] for s in slots], seeds, handoff,
+                                                                           gradient_threshold, weights=weights, sampler=sampler)
         for (a, _), pose in zip(_pairs, poses):
             a.rigid_transformation_ = pose.copy()
         return stats
@@ -509,14 +538,16 @@ def Tracking(tracker, robust_matcher, previous_frame, current_frame):
     return tracker.EstimatePoseFeatures(previous_frame, current_frame)
 
 
-def TrackingBatch(tracker, robust_matcher, pairs, cap=2048):
+def TrackingBatch(tracker, robust_matcher, pairs, cap=2048, seeds=None):
     """System::Tracking() for a list of (previous_frame, current_frame) pairs through the device-resident call
     (uwt_tracking_batch, or uwt_tracking_orb_batch for RobustMatcher(detector=1)): the detector, the matcher, ransacTest,
     getGoodKeypoints and the live alignment run as one chain on the device, and keypoints_, surf_keypoints_ (orb_keypoints_ with ORB),
     n_matches_ of both frames and previous_frame.rigid_transformation_ end up exactly as the Tracking loop over the same list with the
     same matcher leaves them.  Pairs that share no frame go into one call; a pair that names a frame an earlier
     pair of the list has written (the next pair of a sequence) waits for that pair's results, as it does in the loop.  Returns
-    the per-pair stats; a pair without a good match has ERR_NO_VALID_POINTS there and its frames' lists empty."""
+    the per-pair stats; a pair without a good match has ERR_NO_VALID_POINTS there and its frames' lists empty.
+    seeds ([len(pairs), 7]): the pairs' start poses for the live alignment (uwt_tracking_batch_seeded / uwt_tracking_orb_batch_seeded);
+    the front end is untouched, and a pair it fails keeps the identity."""
     ctx = tracker._ctx
     rm = robust_matcher
     build, _, _, kept = rm._DETECTORS[rm.detector_]
@@ -526,11 +557,15 @@ def TrackingBatch(tracker, robust_matcher, pairs, cap=2048):
     fields = {k: getattr(detector_params, k) for k, _ in detector_params._fields_}
     if rm.detector_ == 1:
         params, call = capi.default_tracking_orb_params(orb=fields, **common), ctx.tracking_orb_batch
+        seeded_call = ctx.tracking_orb_batch_seeded
         if rm.orb_pattern_ is not rm._pattern_sent:   # as DetectAndTrackFeatures: the context keeps a pattern until it is given another
             ctx.orb_set_pattern(rm.orb_pattern_)
             rm._pattern_sent = rm.orb_pattern_
     else:
         params, call = capi.default_tracking_params(surf=fields, **common), ctx.tracking_batch
+        seeded_call = ctx.tracking_batch_seeded
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, np.float32).reshape(len(pairs), 7)
     stats, i = [], 0
     while i < len(pairs):
         run, seen = [], set()
@@ -546,7 +581,11 @@ def TrackingBatch(tracker, robust_matcher, pairs, cap=2048):
         for (a, b), (sa, sb) in zip(run, slots):   # binding a later pair's frame may have taken an earlier frame's slot
             if a._slot != sa or b._slot != sb or not (a.obtained_gradients_ and b.obtained_gradients_):
                 raise RuntimeError("TrackingBatch: more frames than slots (max_frames)")
-        r = call([s[0] for s in slots], [s[1] for s in slots], prev=[getattr(a, kept) for a, _ in run], params=params, cap=cap)
+        if seeds is None:
+            r = call([s[0] for s in slots], [s[1] for s in slots], prev=[getattr(a, kept) for a, _ in run], params=params, cap=cap)
+        else:
+            r = seeded_call([s[0] for s in slots], [s[1] for s in slots], prev=[getattr(a, kept) for a, _ in run], params=params, cap=cap,
+                            seeds=seeds[i - len(run):i])
         for k, (a, b) in enumerate(run):
             kp0, kp1 = r["kept_prev"][k], r["kept_cur"][k]
             a.n_matches_ = b.n_matches_ = len(kp0)
