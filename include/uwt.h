@@ -131,8 +131,10 @@ typedef struct uwt_tuning {
   int32_t coarse_batch_px;   /* batches: levels of up to this many pixels run one block per pair, one launch per level;
                                 0: never [6144]                                                                             */
   int32_t coarse_weighted;   /* the same for robust weights over the nearest sampler (k_coarse_weighted) [1]                */
-  int32_t overlap_gradients; /* uwt_track_batch_async: finer levels' gradients on a side stream beside the first, coarse
-                                iterations [1]                                                                              */
+  int32_t overlap_gradients; /* uwt_track_batch_async, from 768 pairs on: finer levels' gradients on a side stream beside the
+                                first, coarse iterations, and the call's pyramids and gradients of the levels >= 1 under the
+                                level 0 of the batch call enqueued before it (early preparation).  0: neither, 1: both,
+                                2: the side stream without the early preparation, 3: both at any batch size [1]            */
   int32_t first_poll;        /* early-exit schedules: evaluations of a level before the host first looks [3]                */
   int32_t chained;           /* -1: update chained into the next evaluation's launch for a few pairs; 1 / 0: always / never
                                 [-1]                                                                                        */
@@ -161,7 +163,7 @@ int uwt_get_params(const uwt_ctx* ctx, uwt_params* out);
 /* the context's launch-shape switches (uwt_tuning); uwt_set_tuning waits for the context's work in flight and applies to every
  * later call.  A value outside its range (split 1..4, split_min >= 1, split_min_px >= 1, stream_bytes >= 0, tail_update 0..2,
  * target_blocks 0..2^20, coarse_batch_px 0..2^24, first_poll 1..2^20, chained -1..1) returns UWT_ERR_INVALID_ARG and changes
- * nothing; the on / off switches take any non-zero value as 1. */
+ * nothing; the on / off switches take any non-zero value as 1, overlap_gradients a value outside 0..3 as 1. */
 int uwt_get_tuning(const uwt_ctx* ctx, uwt_tuning* out);
 int uwt_set_tuning(uwt_ctx* ctx, const uwt_tuning* t);
 /* Tracker::~Tracker (src/Tracker.cpp:280-293) */
@@ -245,6 +247,12 @@ int uwt_estimate_pose_batch(uwt_ctx* ctx, int32_t n_pairs, const int32_t* ref_sl
  * decide on the device), so it returns only once the last level's first iterations are queued.
  * Ordering against uwt_upload_frames_async covers every slot the call touches: the prepared range AND every slot the pair
  * lists name (they may lie outside the range).
+ * Early preparation (uwt_tuning::overlap_gradients): when the entry before this one on the context was a dense batch call of a fixed
+ * schedule that ends on level 0 (identity weights, first_level >= 1, no profiling), this call's pyramids and its gradients of the
+ * levels >= 1 may run before that call has ended — past its level 1 it reads level-0 planes alone, whatever slots the two calls
+ * name.  Any other entry between the two, uwt_plane_device_ptr and uwt_stream included, is ordered as it always was: the call after
+ * it is enqueued in one piece behind it.  Results never depend on it.  Level-0 frames a producer writes in place must be complete
+ * (the producer waited for) before the call that reads them is made; work merely enqueued on uwt_stream does not order them.
  * alignment: d_poses_out 4 bytes, d_stats_out_or_null 4 bytes. */
 int uwt_track_batch_async(uwt_ctx* ctx, int32_t first_slot, int32_t n_frames, int32_t grad_refs_only,
                           int32_t n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots,

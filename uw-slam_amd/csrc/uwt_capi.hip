@@ -149,7 +149,7 @@ static int copy_strided_frame_in(uwt_ctx* c, void* plane0, const void* host, siz
 constexpr int kFewFrames = 8;   // up to here a frame set takes the one-launch forms (k_pyramid_all, k_scharr3_levels)
 
 template <typename T>
-void launch_pyramid_all(uwt_ctx* c, T* const* planes_in, T* const* planes, int n, const int* d_slots, int first_slot) {
+void launch_pyramid_all(uwt_ctx* c, T* const* planes_in, T* const* planes, int n, const int* d_slots, int first_slot, hipStream_t on) {
   PyramidArgs<T> a;
   std::memset(&a, 0, sizeof(a));
   a.src = planes_in[0];
@@ -164,7 +164,7 @@ void launch_pyramid_all(uwt_ctx* c, T* const* planes_in, T* const* planes, int n
   a.slots = d_slots;
   a.first_slot = first_slot;
   const int tiles = ((a.w + 63) / 64) * ((a.h + 63) / 64);
-  hipLaunchKernelGGL(k_pyramid_all<T>, dim3(tiles, n), dim3(kBlock), 0, c->stream, a);
+  hipLaunchKernelGGL(k_pyramid_all<T>, dim3(tiles, n), dim3(kBlock), 0, on, a);
 }
 
 int prof_begin(uwt_ctx* c, size_t* idx, int lvl = 0, int evaluations = 1) {
@@ -242,6 +242,8 @@ struct CallOpts {
                                        // end, redo conservatively if cut short
   bool inline_pairs = false;           // the (at most two) pairs' slots travel in the kernel arguments: no pair list upload
   int pair_slots[4] = {0, 0, 0, 0};    // ref 0, tgt 0, ref 1, tgt 1
+  bool window = false;                 // uwt_track_batch_async: record the window events of the early preparation (uwt_ctx::ev_window)
+                                       // where the schedule has a window
 };
 
 // The chained form of Tracker::EstimatePose for a few pairs (dense points, any level size): one launch step per evaluation —
@@ -487,6 +489,11 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
   if (tickets) HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
   struct Part { int base, cnt; hipStream_t s; ResidualArgs ra; UpdateArgs ua; };
   Part pt[uwt_ctx::kMaxParts];
+  // The window of the early preparation (uwt_ctx::ev_window): once a part has finished level 1 of a schedule that ends on level 0,
+  // what is left of it reads the level-0 planes alone.  Identity weights, fixed schedules, any number of parts; no window for a
+  // schedule that ends above level 0 or has level 0 alone, nor in a profiled call (its kernels are timed with nothing beside them).
+  const bool window = opt.window && !general && !p.early_exit && p.last_level == 0 && p.first_level >= 1 && !c->profiling &&
+                      !c->compute_only;
   // every early return below (a failed launch or event call) leaves part streams forked and not joined: drain them before
   // the error reaches the caller, so that uwt_sync / uwt_destroy on the context stream really mean "nothing is running"
   struct JoinGuard {
@@ -516,6 +523,7 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
       if (coarse_lvl[lvl]) {
         int st = run_coarse(q.base, q.cnt, q.s, lvl, lvl != p.first_level);
         if (st) return st;
+        if (window && lvl == 1) HIPCHK(c, hipEventRecord(c->ev_window[i], q.s));
         continue;
       }
       q.ra = residual_args(c, lvl);
@@ -578,18 +586,21 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
       hipLaunchKernelGGL(k_level_end, dim3((pt[i].cnt + tb - 1) / tb), dim3(tb), 0, pt[i].s, c->state + pt[i].base, pt[i].cnt, lvl,
                          start.scale_t(p), p.initial_error);
       HIPCHK(c, hipGetLastError());
+      if (window && lvl == 1) HIPCHK(c, hipEventRecord(c->ev_window[i], pt[i].s));
     }
   }
   for (int i = 0; i < parts; i++) {
     hipLaunchKernelGGL(k_write_out, dim3((pt[i].cnt + tb - 1) / tb), dim3(tb), 0, pt[i].s, c->state + pt[i].base, pt[i].cnt,
                        d_poses + 7 * (size_t)pt[i].base, d_stats ? d_stats + pt[i].base : nullptr);
     HIPCHK(c, hipGetLastError());
+    if (window && parts > 1 && i == 0) HIPCHK(c, hipEventRecord(c->ev_first_end, pt[0].s));   // (where the next call's preparation starts)
     if (i) {
       HIPCHK(c, hipEventRecord(c->ev_join[i], pt[i].s));
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[i], 0));
     }
   }
   guard.joined = true;
+  if (window) c->win_parts = parts;
   return UWT_OK;
 }
 
@@ -674,6 +685,7 @@ hipError_t DevBuf::release() {
 // plain use of up to `bytes` finds its tail gap inside the allocation whatever made the block.
 int DevBuf::reserve(uwt_ctx* c, hipStream_t stream, size_t want, const Carve* cv) {
   const size_t g = c->guard_bytes, lead = (g + 255) & ~(size_t)255, tail = g && !(cv && cv->guard) ? g : 0;
+  if (stream != c->copy) close_window(c);   // an entry's work area (an asynchronous upload's staging is ordered by the slot rings)
   if (want > bytes || (g && !block)) {
     if (block) HIPCHK(c, hipStreamSynchronize(stream));
     HIPCHK(c, release());
@@ -698,6 +710,7 @@ int DevBuf::reserve(uwt_ctx* c, hipStream_t stream, const Carve& cv, size_t want
 
 int DevBuf::adopt(uwt_ctx* c, hipStream_t stream, const Carve& inner, const void* base) {
   const long long shift = static_cast<const unsigned char*>(base) - static_cast<const unsigned char*>(p);
+  if (stream != c->copy) close_window(c);
   for (GuardGap gap : inner.gaps) {
     gap.at += shift;
     gap.array += 1000;   // (told apart from the block's own arrays in a report)
@@ -714,22 +727,23 @@ int DevBuf::adopt(uwt_ctx* c, hipStream_t stream, const Carve& inner, const void
 // Whole cells in tight rows of whole groups of four: k_halve; every other size: k_resize_half.
 template <typename T>
 int launch_resize(uwt_ctx* c, const T* src, T* dst, int sw, int sh, int src_pitch, int dw, int dh, int dst_pitch, size_t sfs,
-                  size_t dfs, int n_frames, const int* d_slots, int first_slot) {
+                  size_t dfs, int n_frames, const int* d_slots, int first_slot, hipStream_t on) {
   if (n_frames == 0) return UWT_OK;
+  hipStream_t stream = on ? on : c->stream;
   if (sw == 2 * dw && sh == 2 * dh && dw % 4 == 0) {
     const int groups = (dw / 4) * dh;
-    hipLaunchKernelGGL((k_halve<T, 4>), dim3((groups + kBlock - 1) / kBlock, n_frames), dim3(kBlock), 0, c->stream, src,
+    hipLaunchKernelGGL((k_halve<T, 4>), dim3((groups + kBlock - 1) / kBlock, n_frames), dim3(kBlock), 0, stream, src,
                        dst, dw, dh, src_pitch, dst_pitch, sfs, dfs, d_slots, first_slot);
   } else {
     const int groups = (dst_pitch / 4) * dh;
-    hipLaunchKernelGGL((k_resize_half<T>), dim3((groups + kBlock - 1) / kBlock, n_frames), dim3(kBlock), 0, c->stream, src,
+    hipLaunchKernelGGL((k_resize_half<T>), dim3((groups + kBlock - 1) / kBlock, n_frames), dim3(kBlock), 0, stream, src,
                        dst, sw, sh, src_pitch, dw, dh, dst_pitch, sfs, dfs, d_slots, first_slot);
   }
   HIPCHK(c, hipGetLastError());
   return UWT_OK;
 }
-template int launch_resize<uint8_t>(uwt_ctx*, const uint8_t*, uint8_t*, int, int, int, int, int, int, size_t, size_t, int, const int*, int);
-template int launch_resize<uint16_t>(uwt_ctx*, const uint16_t*, uint16_t*, int, int, int, int, int, int, size_t, size_t, int, const int*, int);
+template int launch_resize<uint8_t>(uwt_ctx*, const uint8_t*, uint8_t*, int, int, int, int, int, int, size_t, size_t, int, const int*, int, hipStream_t);
+template int launch_resize<uint16_t>(uwt_ctx*, const uint16_t*, uint16_t*, int, int, int, int, int, int, size_t, size_t, int, const int*, int, hipStream_t);
 
 // src/gx/gy point at slot 0 of the level planes; the frames processed are slots[0..n) if given, else first_slot..+n
 int launch_scharr(uwt_ctx* c, const uint8_t* src, int16_t* gx, int16_t* gy, int w, int h, int pitch, size_t fs, int n_frames,
@@ -889,7 +903,11 @@ int dep_wait(uwt_ctx* c, const uwt_ctx::SlotDep* ring, int next, bool dropped, h
   return UWT_OK;
 }
 // a compute call on slots [first, first + n): ordered behind the uploads into them ...
-int compute_begin(uwt_ctx* c, int first, int n) { return dep_wait(c, c->fresh, c->fresh_next, c->fresh_dropped, c->stream, first, n); }
+// (and behind the whole of a batch call before it: the window that call left for the next one's early preparation closes)
+int compute_begin(uwt_ctx* c, int first, int n) {
+  close_window(c);
+  return dep_wait(c, c->fresh, c->fresh_next, c->fresh_dropped, c->stream, first, n);
+}
 // ... and remembered, so that a later upload into them waits for it
 int compute_end(uwt_ctx* c, int first, int n) {
   c->busy_seq[c->busy_next] = ++c->ticket_seq;
@@ -909,38 +927,68 @@ int compute_begin_pairs(uwt_ctx* c, int n, const int32_t* slots_a, const int32_t
   return compute_begin(c, c->dep_first, c->dep_n);
 }
 
-// The caller's lists are copied before this returns (they may be temporaries): into a pinned staging buffer, then
-// asynchronously to the device.  Unchanged lists (the steady state of a resident batch) are not re-sent.
-int upload_pairs(uwt_ctx* c, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots) {
+// the range checks of a call's pair lists
+static int check_pair_lists_range(uwt_ctx* c, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots) {
   if (!ref_slots || !tgt_slots || n_pairs < 1) return fail(c, UWT_ERR_INVALID_ARG, "null pair lists or n_pairs < 1");
   if (n_pairs > c->p.max_pairs) return fail(c, UWT_ERR_CAPACITY, "n_pairs exceeds max_pairs");
   for (int i = 0; i < n_pairs; i++)
     if (ref_slots[i] < 0 || ref_slots[i] >= c->p.max_frames || tgt_slots[i] < 0 || tgt_slots[i] >= c->p.max_frames)
       return fail(c, UWT_ERR_INVALID_ARG, "pair slot out of range");
+  return UWT_OK;
+}
+
+// The caller's lists are copied before this returns (they may be temporaries): into a pinned staging buffer, then
+// asynchronously to the device.  Unchanged lists (the steady state of a resident batch) are not re-sent.
+// early false: every entry's form — the lists go to the current device set on the context stream, behind whatever read it.
+// early (an open window, track_batch_enqueue): the previous call's launches still read the current set, so new lists go to the
+// idle one on the side stream — the caller has made that stream wait for the window events, which lie behind the entry of the
+// previous call and so behind the end of every call that read the idle set — and the idle set becomes the current one; lists the
+// idle set holds already (a caller that alternates two lists) make it current without a copy.
+static int send_pairs(uwt_ctx* c, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots, bool early) {
   const size_t block = 2 * (size_t)c->p.max_pairs;
-  {
-    const int* h_ref = c->h_pairs + c->pair_stage * block;
+  auto holds = [&](int set) {
+    const int* h_ref = c->h_pairs + c->pair_stage[set] * block;
     const int* h_tgt = h_ref + c->p.max_pairs;
-    if (n_pairs == c->n_pairs_cached && !std::memcmp(h_ref, ref_slots, sizeof(int) * n_pairs) &&
-        !std::memcmp(h_tgt, tgt_slots, sizeof(int) * n_pairs))
-      return UWT_OK;
+    return n_pairs == c->n_pairs_cached[set] && !std::memcmp(h_ref, ref_slots, sizeof(int) * n_pairs) &&
+           !std::memcmp(h_tgt, tgt_slots, sizeof(int) * n_pairs);
+  };
+  auto make_current = [&](int set) {
+    c->pair_set = set;
+    c->d_ref = c->d_pair_set[set];
+    c->d_tgt = c->d_ref + c->p.max_pairs;
+  };
+  if (holds(c->pair_set)) return UWT_OK;
+  const int set = early ? c->pair_set ^ 1 : c->pair_set;
+  if (early && holds(set)) {
+    make_current(set);
+    return UWT_OK;
   }
-  const int stage = (c->pair_stage + 1) % uwt_ctx::kPairStages;
-  HIPCHK(c, hipEventSynchronize(c->ev_pairs[stage]));  // the copy that last read this block (kPairStages lists ago)
+  int stage = (c->pair_stage_last + 1) % uwt_ctx::kPairStages;
+  while (stage == c->pair_stage[0] || stage == c->pair_stage[1]) stage = (stage + 1) % uwt_ctx::kPairStages;
+  HIPCHK(c, hipEventSynchronize(c->ev_pairs[stage]));  // the copy that last read this block (at least two lists ago)
   int* h_ref = c->h_pairs + stage * block;
   int* h_tgt = h_ref + c->p.max_pairs;
   std::memcpy(h_ref, ref_slots, sizeof(int) * n_pairs);
   std::memcpy(h_tgt, tgt_slots, sizeof(int) * n_pairs);
-  c->pair_stage = stage;
-  c->n_pairs_cached = n_pairs;
-  HIPCHK(c, hipMemcpyAsync(c->d_ref, h_ref, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_tgt, h_tgt, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev_pairs[stage], c->stream));
+  c->pair_stage[set] = c->pair_stage_last = stage;
+  c->n_pairs_cached[set] = n_pairs;
+  make_current(set);
+  hipStream_t s = early ? c->side : c->stream;
+  HIPCHK(c, hipMemcpyAsync(c->d_ref, h_ref, sizeof(int) * n_pairs, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_tgt, h_tgt, sizeof(int) * n_pairs, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(c->ev_pairs[stage], s));
   return UWT_OK;
+}
+
+int upload_pairs(uwt_ctx* c, int n_pairs, const int32_t* ref_slots, const int32_t* tgt_slots) {
+  close_window(c);
+  int st = check_pair_lists_range(c, n_pairs, ref_slots, tgt_slots);
+  return st ? st : send_pairs(c, n_pairs, ref_slots, tgt_slots, false);
 }
 
 // the synchronous form of a batch call enqueued with the context's d_poses / d_stats: both copied back, the stream drained
 int read_back_pairs(uwt_ctx* c, const char* what, int n, float* poses_out, uwt_stats* stats_out) {
+  close_window(c);
   std::vector<uwt_stats> tmp((size_t)n);
   HIPCHK(c, hipMemcpyAsync(poses_out, c->d_poses, sizeof(float) * 7 * n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_stats, sizeof(uwt_stats) * n, hipMemcpyDeviceToHost, c->stream));
@@ -954,6 +1002,7 @@ int read_back_pairs(uwt_ctx* c, const char* what, int n, float* poses_out, uwt_s
 // holds, ONE wait for all of them, the rows picked out on the host.  counts may be the target of a copy enqueued before: it is
 // read after the wait.
 int rows_to_host(uwt_ctx* c, int cap, int n_items, std::initializer_list<RowSet> sets) {
+  close_window(c);
   std::vector<std::vector<unsigned char>> tmp;
   for (const RowSet& s : sets) {
     tmp.emplace_back(s.d_rows ? s.elem_bytes * (size_t)cap * n_items : 0);
@@ -974,6 +1023,7 @@ int rows_to_host(uwt_ctx* c, int cap, int n_items, std::initializer_list<RowSet>
 // counts are read first, then one copy per frame of its min(count, cap) rows, packed at f * cap in pts_out
 int counted_rows_to_host(uwt_ctx* c, const float4* d_rows, size_t stride, const int* d_counts, int n_items, int cap, float* pts_out,
                          int32_t* counts_out) {
+  close_window(c);
   HIPCHK(c, hipMemcpyAsync(counts_out, d_counts, sizeof(int) * n_items, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int f = 0; f < n_items; f++) {
@@ -1100,6 +1150,9 @@ int uwt_create(const uwt_params* p, uwt_ctx** out) {
   for (int i = 0; i < uwt_ctx::kPairStages; i++) CREATE_CHK(hipEventCreateWithFlags(&c->ev_pairs[i], hipEventDisableTiming));
   CREATE_CHK(hipEventCreateWithFlags(&c->ev_pyramids, hipEventDisableTiming));
   CREATE_CHK(hipEventCreateWithFlags(&c->ev_side_done, hipEventDisableTiming));
+  CREATE_CHK(hipEventCreateWithFlags(&c->ev_entry, hipEventDisableTiming));
+  CREATE_CHK(hipEventCreateWithFlags(&c->ev_first_end, hipEventDisableTiming));
+  for (int i = 0; i < uwt_ctx::kMaxParts; i++) CREATE_CHK(hipEventCreateWithFlags(&c->ev_window[i], hipEventDisableTiming));
   for (int l = 0; l < UWT_MAX_LEVELS; l++) CREATE_CHK(hipEventCreateWithFlags(&c->ev_level[l], hipEventDisableTiming));
   for (int l = 0; l < p->n_levels; l++) {
     const size_t n = (size_t)c->lv[l].n * p->max_frames;
@@ -1115,8 +1168,9 @@ int uwt_create(const uwt_params* p, uwt_ctx** out) {
     }
   }
   CREATE_CHK(hipMalloc((void**)&c->state, sizeof(PairState) * p->max_pairs));
-  CREATE_CHK(hipMalloc((void**)&c->d_ref, sizeof(int) * p->max_pairs));
-  CREATE_CHK(hipMalloc((void**)&c->d_tgt, sizeof(int) * p->max_pairs));
+  for (int i = 0; i < 2; i++) CREATE_CHK(hipMalloc((void**)&c->d_pair_set[i], sizeof(int) * 2 * (size_t)p->max_pairs));
+  c->d_ref = c->d_pair_set[0];
+  c->d_tgt = c->d_ref + p->max_pairs;
   CREATE_CHK(hipMalloc((void**)&c->partials, c->partial_records * kRecWords * sizeof(uint32_t)));
   CREATE_CHK(hipMalloc((void**)&c->partials2, c->partial_records * kRecWords * sizeof(uint32_t)));
   CREATE_CHK(hipMalloc((void**)&c->state2, sizeof(PairState) * p->max_pairs));
@@ -1170,6 +1224,7 @@ int uwt_debug_guards(uwt_ctx* c, int64_t guard_bytes) {
   if (!c) return UWT_ERR_INVALID_ARG;
   if (guard_bytes < 0 || guard_bytes > (1ll << 24)) return fail(c, UWT_ERR_INVALID_ARG, "uwt_debug_guards: guard_bytes outside 0..2^24");
   (void)hipSetDevice(c->p.device);
+  close_window(c);
   drain_streams(c);
   for (const NamedBuf& nb : growable(c)) HIPCHK(c, nb.b->release());
   if (c->orb_pattern_state == 2) c->orb_pattern_state = 1;   // the device copy of the pattern went with orb_pat: the next ORB call sends it
@@ -1211,7 +1266,7 @@ int uwt_destroy(uwt_ctx* c) {
   // the fixed-size allocations of uwt_create, uwt_update_params, ensure_features and ransac_need_rows (null: nothing to free)
   for (int l = 0; l < UWT_MAX_LEVELS; l++)
     for (void* p : {(void*)c->img[l], (void*)c->depth[l], (void*)c->gx[l], (void*)c->gy[l]}) (void)hipFree(p);
-  for (void* p : {(void*)c->state, (void*)c->d_ref, (void*)c->d_tgt, (void*)c->partials, (void*)c->partials2, (void*)c->state2,
+  for (void* p : {(void*)c->state, (void*)c->d_pair_set[0], (void*)c->d_pair_set[1], (void*)c->partials, (void*)c->partials2, (void*)c->state2,
                   (void*)c->d_poses, (void*)c->d_stats, (void*)c->d_active, (void*)c->d_tickets, (void*)c->hist, (void*)c->scale,
                   (void*)c->feat_tab, (void*)c->feat_cnt, (void*)c->feat_kp, (void*)c->feat_nkp, (void*)c->feat_recs,
                   (void*)c->ransac_need})
@@ -1225,7 +1280,8 @@ int uwt_destroy(uwt_ctx* c) {
   for (hipEvent_t e : c->ev_pairs) drop(e);
   for (hipEvent_t e : c->ev_cloud) drop(e);
   for (hipEvent_t e : c->ev_level) drop(e);
-  for (hipEvent_t e : {c->ev_fork, c->ev_pyramids, c->ev_side_done}) drop(e);
+  for (hipEvent_t e : c->ev_window) drop(e);
+  for (hipEvent_t e : {c->ev_fork, c->ev_pyramids, c->ev_side_done, c->ev_entry, c->ev_first_end}) drop(e);
   for (int i = 0; i < uwt_ctx::kDeps; i++) { drop(c->busy[i].ev); drop(c->fresh[i].ev); }
   for (hipStream_t s : c->part_stream)
     if (s) (void)hipStreamDestroy(s);
@@ -1254,12 +1310,14 @@ int uwt_set_tuning(uwt_ctx* c, const uwt_tuning* t) {
       t->coarse_batch_px > (1 << 24) || t->first_poll < 1 || t->first_poll > (1 << 20) || t->chained < -1 || t->chained > 1)
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_set_tuning: value out of range");   // (first_poll is doubled and incremented by the schedulers: bounded well inside int)
   (void)hipSetDevice(c->p.device);
+  close_window(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->side));   // (joined into the context stream by every call that ended well; an early preparation runs there)
   c->tn = *t;
   c->spec_budget = c->spec_calm = 0;
-  for (int32_t* b : {&c->tn.coarse, &c->tn.coarse_weighted, &c->tn.overlap_gradients, &c->tn.speculation, &c->tn.fused_stages,
-                     &c->tn.pyramid_batch, &c->tn.typed_loads})
+  for (int32_t* b : {&c->tn.coarse, &c->tn.coarse_weighted, &c->tn.speculation, &c->tn.fused_stages, &c->tn.pyramid_batch, &c->tn.typed_loads})
     *b = *b != 0;
+  if (c->tn.overlap_gradients < 0 || c->tn.overlap_gradients > 3) c->tn.overlap_gradients = 1;   // (an on / off switch until the early preparation)
   std::memset(c->tn.reserved, 0, sizeof(c->tn.reserved));
   return UWT_OK;
 }
@@ -1276,6 +1334,7 @@ int uwt_update_params(uwt_ctx* c, const uwt_params* p) {
       (p->arith != UWT_ARITH_OPENCV && p->arith != UWT_ARITH_LEGACY))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_update_params: bad solver constants");
   (void)hipSetDevice(o.device);
+  close_window(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (p->sampler || p->weights) {
     const int st = ensure_general_buffers(c);
@@ -1362,6 +1421,7 @@ static int plane_ptr(uwt_ctx* c, int slot, int lvl, int plane, void** out, size_
 int uwt_plane_device_ptr(uwt_ctx* c, int32_t slot, int32_t lvl, int32_t plane, void** out) {
   size_t elem;
   int st = plane_ptr(c, slot, lvl, plane, out, &elem);
+  if (c) close_window(c);   // (a caller about to read or write planes itself)
   return st ? fail(c, st, "uwt_plane_device_ptr: bad slot/level/plane") : UWT_OK;
 }
 
@@ -1371,6 +1431,7 @@ int uwt_get_plane(uwt_ctx* c, int32_t slot, int32_t lvl, int32_t plane, void* ho
   size_t elem;
   int st = plane_ptr(c, slot, lvl, plane, &d, &elem);
   if (st || !host_out) return fail(c, UWT_ERR_INVALID_ARG, "uwt_get_plane: bad slot/level/plane");
+  close_window(c);   // the plane is read behind the call before: the next call's preparation may not overtake the copy
   const LevelK& L = c->lv[lvl];   // the level's image, img_w x img_h, without the pad columns of its rows
   HIPCHK(c, hipMemcpy2DAsync(host_out, (size_t)L.iw * elem, d, (size_t)L.pitch * elem, (size_t)L.iw * elem, L.ih, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1379,15 +1440,16 @@ int uwt_get_plane(uwt_ctx* c, int32_t slot, int32_t lvl, int32_t plane, void* ho
 
 // System::AddFrame's pyramid loop for slots first_slot..+n.  depth_slots (device list of n_depth slots), when given,
 // restricts the depth pyramids to those slots: only a pair's reference frame is ever read through its depth
-// (src/Tracker.cpp:1266-1272).
-static int enqueue_pyramids(uwt_ctx* c, int first_slot, int n, const int* depth_slots = nullptr, int n_depth = 0) {
+// (src/Tracker.cpp:1266-1272).  on: the stream (null: the context's).
+static int enqueue_pyramids(uwt_ctx* c, int first_slot, int n, const int* depth_slots = nullptr, int n_depth = 0, hipStream_t on = nullptr) {
+  hipStream_t stream = on ? on : c->stream;
   const bool fused = n <= kFewFrames && c->p.n_levels >= 3 && c->p.n_levels <= kPyrMaxLevels && c->whole && c->lv[0].iw % 4 == 0 &&
                      c->lv[0].ih % 4 == 0 && c->tn.fused_stages;
   if (fused) {   // the whole pyramid of each plane in one launch
-    if (n) launch_pyramid_all<uint8_t>(c, c->img, c->img, n, nullptr, first_slot);
+    if (n) launch_pyramid_all<uint8_t>(c, c->img, c->img, n, nullptr, first_slot, stream);
     if (c->p.has_depth) {
-      if (depth_slots) { if (n_depth) launch_pyramid_all<uint16_t>(c, c->depth, c->depth, n_depth, depth_slots, 0); }
-      else if (n) launch_pyramid_all<uint16_t>(c, c->depth, c->depth, n, nullptr, first_slot);
+      if (depth_slots) { if (n_depth) launch_pyramid_all<uint16_t>(c, c->depth, c->depth, n_depth, depth_slots, 0, stream); }
+      else if (n) launch_pyramid_all<uint16_t>(c, c->depth, c->depth, n, nullptr, first_slot, stream);
     }
     HIPCHK(c, hipGetLastError());
     return UWT_OK;
@@ -1401,7 +1463,7 @@ static int enqueue_pyramids(uwt_ctx* c, int first_slot, int n, const int* depth_
       a.src = c->img[0];
       for (int l = 0; l < 4; l++) { a.stride[l] = c->lv[l].n; a.pitch[l] = c->lv[l].pitch; if (l) a.dst[l - 1] = c->img[l]; }
       a.w = c->lv[0].iw; a.h = c->lv[0].ih; a.slots = nullptr; a.first_slot = first_slot;
-      hipLaunchKernelGGL(k_pyramid_batch<uint8_t>, dim3(tiles, n), dim3(kBlock), 0, c->stream, a);
+      hipLaunchKernelGGL(k_pyramid_batch<uint8_t>, dim3(tiles, n), dim3(kBlock), 0, stream, a);
     }
     const int nd16 = !c->p.has_depth ? 0 : (depth_slots ? n_depth : n);
     if (nd16) {
@@ -1409,7 +1471,7 @@ static int enqueue_pyramids(uwt_ctx* c, int first_slot, int n, const int* depth_
       a.src = c->depth[0];
       for (int l = 0; l < 4; l++) { a.stride[l] = c->lv[l].n; a.pitch[l] = c->lv[l].pitch; if (l) a.dst[l - 1] = c->depth[l]; }
       a.w = c->lv[0].iw; a.h = c->lv[0].ih; a.slots = depth_slots; a.first_slot = depth_slots ? 0 : first_slot;
-      hipLaunchKernelGGL(k_pyramid_batch<uint16_t>, dim3(tiles, nd16), dim3(kBlock), 0, c->stream, a);
+      hipLaunchKernelGGL(k_pyramid_batch<uint16_t>, dim3(tiles, nd16), dim3(kBlock), 0, stream, a);
     }
     HIPCHK(c, hipGetLastError());
     l0 = 4;
@@ -1417,11 +1479,11 @@ static int enqueue_pyramids(uwt_ctx* c, int first_slot, int n, const int* depth_
   for (int l = l0; l < c->p.n_levels; l++) {
     const LevelK& S = c->lv[l - 1];
     const LevelK& D = c->lv[l];
-    int st = launch_resize<uint8_t>(c, c->img[l - 1], c->img[l], S.iw, S.ih, S.pitch, D.iw, D.ih, D.pitch, S.n, D.n, n, nullptr, first_slot);
+    int st = launch_resize<uint8_t>(c, c->img[l - 1], c->img[l], S.iw, S.ih, S.pitch, D.iw, D.ih, D.pitch, S.n, D.n, n, nullptr, first_slot, stream);
     if (st) return st;
     if (c->p.has_depth) {
-      st = depth_slots ? launch_resize<uint16_t>(c, c->depth[l - 1], c->depth[l], S.iw, S.ih, S.pitch, D.iw, D.ih, D.pitch, S.n, D.n, n_depth, depth_slots)
-                       : launch_resize<uint16_t>(c, c->depth[l - 1], c->depth[l], S.iw, S.ih, S.pitch, D.iw, D.ih, D.pitch, S.n, D.n, n, nullptr, first_slot);
+      st = depth_slots ? launch_resize<uint16_t>(c, c->depth[l - 1], c->depth[l], S.iw, S.ih, S.pitch, D.iw, D.ih, D.pitch, S.n, D.n, n_depth, depth_slots, 0, stream)
+                       : launch_resize<uint16_t>(c, c->depth[l - 1], c->depth[l], S.iw, S.ih, S.pitch, D.iw, D.ih, D.pitch, S.n, D.n, n, nullptr, first_slot, stream);
       if (st) return st;
     }
   }
@@ -1567,11 +1629,43 @@ static int track_batch_enqueue(uwt_ctx* c, int32_t first_slot, int32_t n_frames,
                                const int32_t* ref_slots, const int32_t* tgt_slots, float* d_poses_out, uwt_stats* d_stats_out,
                                const Start& start = Start()) {
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
-  if (!c || !d_poses_out || !slot_range_ok(c, first_slot, n_frames))
+  if (!c) return fail(c, UWT_ERR_INVALID_ARG, "uwt_track_batch_async: bad argument");
+  // the window the previous call left (uwt_ctx::win_open) is taken here whatever becomes of this call: one that fails leaves none
+  const bool had_window = c->win_open;
+  const int win_parts = c->win_parts;
+  close_window(c);
+  c->win_parts = 0;
+  if (!d_poses_out || !slot_range_ok(c, first_slot, n_frames))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_track_batch_async: bad argument");
   int st = seeds_clear_of(c, "uwt_track_batch_seeded_async", start.d_seeds, n_pairs, d_poses_out, d_stats_out);
   if (st) return st;
-  st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);
+  // The side stream pays from ~768 pairs on (+1.7 % at 1024); below, its events cost more than the overlap returns
+  // (one pair: +14 % latency).  A profiled call times its kernels alone: nothing runs beside them.  overlap_gradients 3 forces
+  // it at any batch size; 2 keeps the side stream and turns the early preparation off.
+  const int og = c->tn.overlap_gradients;
+  const bool overlap = og != 0 && !c->profiling && (n_pairs >= 768 || og == 3);
+  // Early preparation: the previous entry on this context was a batch call that left a window (uwt_ctx::win_open) — this call's
+  // pyramids and its gradients of the levels >= 1 go on the side stream behind that call's level 1, under its level 0.
+  const bool early = had_window && overlap && og != 2;
+  st = check_pair_lists_range(c, n_pairs, ref_slots, tgt_slots);
+  if (st) return st;
+  // once anything is on the side stream, an error may not leave it running (uwt_sync, uwt_destroy and the next entry look at
+  // the context stream, which a call that ends well makes wait for it)
+  struct SideGuard {
+    uwt_ctx* c; bool armed = false;
+    ~SideGuard() { if (armed) (void)hipStreamSynchronize(c->side); }
+  } side_guard{c};
+  if (early) {
+    HIPCHK(c, hipEventRecord(c->ev_entry, c->stream));   // the previous call's end
+    side_guard.armed = true;
+    for (int i = 0; i < win_parts; i++) HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_window[i], 0));
+    // Where in the window: a batch that runs as parts ends staggered — the first part is through about half a millisecond
+    // before the last (1024 pairs of 640 x 480), and while the last runs alone half of the chip's block slots stand empty.  The
+    // preparation goes there, behind the first part's end: measured +2.5 % on the default batch, against +0.7 % right behind
+    // level 1, where its 2 GB of traffic slow both parts' level-0 launches by nearly what it takes alone (profiles/r24).
+    if (win_parts > 1) HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_first_end, 0));
+  }
+  st = send_pairs(c, n_pairs, ref_slots, tgt_slots, early);
   if (st) return st;
   // The alignment reads every slot the pair lists name, and with grad_refs_only the reference slots lie "wherever they
   // lie" (uwt.h): the dependency range of the call is the union of the prepared range and the pairs' slots, so that an
@@ -1583,7 +1677,9 @@ static int track_batch_enqueue(uwt_ctx* c, int32_t first_slot, int32_t n_frames,
   }
   c->dep_first = lo;
   c->dep_n = hi - lo;
-  st = compute_begin(c, c->dep_first, c->dep_n);   // behind the asynchronous uploads into these slots
+  // behind the asynchronous uploads into these slots (an early preparation reads them on the side stream)
+  st = dep_wait(c, c->fresh, c->fresh_next, c->fresh_dropped, c->stream, c->dep_first, c->dep_n);
+  if (!st && early) st = dep_wait(c, c->fresh, c->fresh_next, c->fresh_dropped, c->side, c->dep_first, c->dep_n);
   if (st) return st;
   // The tracker reads gradients and depth of the previous (reference) frame only (src/Tracker.cpp:407-408, 1266-1272).
   // grad_refs_only computes those planes — gradients of every level, depth levels 1.. — for the pairs' reference slots
@@ -1591,36 +1687,57 @@ static int track_batch_enqueue(uwt_ctx* c, int32_t first_slot, int32_t n_frames,
   // (src/System.cpp:246-251, 197-213).
   const int* g_slots = grad_refs_only ? c->d_ref : nullptr;   // gradient frames: a slot list or the range
   const int g_first = g_slots ? 0 : first_slot, g_n = g_slots ? n_pairs : n_frames;
-  st = grad_refs_only ? enqueue_pyramids(c, first_slot, n_frames, c->d_ref, n_pairs) : enqueue_pyramids(c, first_slot, n_frames);
+  hipStream_t prep = early ? c->side : c->stream;
+  st = grad_refs_only ? enqueue_pyramids(c, first_slot, n_frames, c->d_ref, n_pairs, prep) : enqueue_pyramids(c, first_slot, n_frames, nullptr, 0, prep);
   if (st) return st;
-  // The side stream pays from ~768 pairs on (+1.7 % at 1024); below, its events cost more than the overlap returns
-  // (one pair: +14 % latency).  A profiled call times its kernels alone: nothing runs beside them.
-  if (!c->tn.overlap_gradients || c->profiling || n_pairs < 768) {
+  CallOpts opt;
+  opt.window = overlap && og != 2;   // (the next call decides for itself; without the switch nothing is recorded)
+  if (!overlap) {
     st = enqueue_gradients(c, g_first, g_n, g_slots);
     if (st) return st;
-    return enqueue_estimate(c, n_pairs, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out), nullptr, CallOpts(), start);
+    return enqueue_estimate(c, n_pairs, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out), nullptr, opt, start);
   }
-  // The alignment starts at the coarsest iterated level and only then needs the finer gradients: the first level's are
-  // computed here, the others on the side stream, each level's event gating the iterations that read it.
-  HIPCHK(c, hipEventRecord(c->ev_pyramids, c->stream));
-  st = enqueue_gradient_level(c, c->p.first_level, g_first, g_n, g_slots);
-  if (st) return st;
-  HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_pyramids, 0));
-  for (int l = c->p.first_level - 1; l >= 0; l--) {
-    st = enqueue_gradient_level(c, l, g_first, g_n, g_slots, c->side);
+  HIPCHK(c, hipEventRecord(c->ev_pyramids, prep));
+  if (early) {
+    // every level >= 1 now, each level's event gating the iterations that read it; level 0 behind the previous call's end (its
+    // launches read gx[0] / gy[0] to their last), under this call's coarse levels as without the window.  The context stream
+    // waits for the pyramids and the first level's gradients; the part streams fork from it.
+    for (int l = c->p.n_levels - 1; l >= 1; l--) {
+      st = enqueue_gradient_level(c, l, g_first, g_n, g_slots, c->side);
+      if (st) return st;
+      HIPCHK(c, hipEventRecord(c->ev_level[l], c->side));
+    }
+    HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_entry, 0));
+    st = enqueue_gradient_level(c, 0, g_first, g_n, g_slots, c->side);
     if (st) return st;
-    HIPCHK(c, hipEventRecord(c->ev_level[l], c->side));
-  }
-  for (int l = c->p.first_level + 1; l < c->p.n_levels; l++) {  // levels the solver never iterates: ApplyGradient still fills them
-    st = enqueue_gradient_level(c, l, g_first, g_n, g_slots, c->side);
+    HIPCHK(c, hipEventRecord(c->ev_level[0], c->side));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_pyramids, 0));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_level[c->p.first_level], 0));
+  } else {
+    // The alignment starts at the coarsest iterated level and only then needs the finer gradients: the first level's are
+    // computed here, the others on the side stream, each level's event gating the iterations that read it.
+    st = enqueue_gradient_level(c, c->p.first_level, g_first, g_n, g_slots);
     if (st) return st;
+    side_guard.armed = true;
+    HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_pyramids, 0));
+    for (int l = c->p.first_level - 1; l >= 0; l--) {
+      st = enqueue_gradient_level(c, l, g_first, g_n, g_slots, c->side);
+      if (st) return st;
+      HIPCHK(c, hipEventRecord(c->ev_level[l], c->side));
+    }
+    for (int l = c->p.first_level + 1; l < c->p.n_levels; l++) {  // levels the solver never iterates: ApplyGradient still fills them
+      st = enqueue_gradient_level(c, l, g_first, g_n, g_slots, c->side);
+      if (st) return st;
+    }
   }
   HIPCHK(c, hipEventRecord(c->ev_side_done, c->side));
-  st = enqueue_estimate(c, n_pairs, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out), c->ev_level, CallOpts(), start);
+  st = enqueue_estimate(c, n_pairs, d_poses_out, reinterpret_cast<StatsOut*>(d_stats_out), c->ev_level, opt, start);
   // whatever follows on the context stream (the next call's pyramids, a plane read-back) is ordered after the side work
   const hipError_t e = hipStreamWaitEvent(c->stream, c->ev_side_done, 0);
   if (st) return st;
   if (e != hipSuccess) return fail(c, UWT_ERR_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e));
+  side_guard.armed = false;
+  c->win_open = c->win_parts > 0;
   return UWT_OK;
 }
 
@@ -1680,6 +1797,7 @@ int uwt_sync(uwt_ctx* c) {
   (void)hipSetDevice(c->p.device);
   HIPCHK(c, hipStreamSynchronize(c->copy));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->side));   // (every call that ended well has joined it into the context stream: nothing left as a rule)
   if (c->profiling) {
     int st = prof_collect(c);
     if (st) return st;
@@ -1689,6 +1807,7 @@ int uwt_sync(uwt_ctx* c) {
 
 int uwt_stream(uwt_ctx* c, void** out) {
   if (!c || !out) return UWT_ERR_INVALID_ARG;
+  close_window(c);
   *out = (void*)c->stream;
   return UWT_OK;
 }
@@ -1696,6 +1815,7 @@ int uwt_stream(uwt_ctx* c, void** out) {
 int uwt_profile_enable(uwt_ctx* c, int32_t on) {
   if (c) (void)hipSetDevice(c->p.device);  // one context = one device; callers may have switched the thread's device
   if (!c) return UWT_ERR_INVALID_ARG;
+  close_window(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->ev_used = 0;
   c->profiling = (on & 1) != 0;

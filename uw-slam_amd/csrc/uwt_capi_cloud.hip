@@ -242,6 +242,7 @@ int uwt_accumulate_trajectory_device_async(uwt_ctx* c, const float* d_poses, int
   if (ranges_overlap(d_poses, d_traj_out, n))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_accumulate_trajectory_device_async: d_poses and d_traj_out overlap");
   if (n == 0) return UWT_OK;
+  close_window(c);   // (device work on the context stream that passes through no helper)
   Pose P;
   for (int k = 0; k < 4; k++) P.q[k] = start_pose[k];
   for (int k = 0; k < 3; k++) P.t[k] = start_pose[4 + k];
@@ -260,6 +261,7 @@ int uwt_accumulate_trajectory_device_from_async(uwt_ctx* c, const float* d_poses
   if (ranges_overlap(d_poses, d_traj_out, n) || (n > 0 && s0 < o0 + one * (size_t)n && o0 < s0 + one))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_accumulate_trajectory_device_from_async: d_traj_out overlaps an input");
   if (n == 0) return UWT_OK;
+  close_window(c);   // (device work on the context stream that passes through no helper)
   hipLaunchKernelGGL(k_trajectory_from, dim3(1), dim3(64), 0, c->stream, d_poses, n, d_start_pose, t_scale, reference_axes, d_traj_out);
   HIPCHK(c, hipGetLastError());
   return UWT_OK;
@@ -271,6 +273,7 @@ int uwt_predict_seeds_device_async(uwt_ctx* c, int32_t n, const float* d_prev, c
   if (ranges_overlap(d_prev, d_seed_out, n) || ranges_overlap(d_cur, d_seed_out, n))
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_predict_seeds_device_async: d_seed_out overlaps an input");
   if (n == 0) return UWT_OK;
+  close_window(c);   // (device work on the context stream that passes through no helper)
   const int tb = 64;
   hipLaunchKernelGGL(k_predict_seeds, dim3((n + tb - 1) / tb), dim3(tb), 0, c->stream, d_prev, d_cur, n, d_seed_out);
   HIPCHK(c, hipGetLastError());

@@ -97,20 +97,37 @@ struct uwt_ctx {
   // (the host enqueues twice as many)
   uwt_tuning tn;
   hipEvent_t ev_pyramids = nullptr, ev_side_done = nullptr, ev_level[UWT_MAX_LEVELS] = {};
+  // Early preparation (uwt_tuning::overlap_gradients 1 / 3): past its level 1 a dense batch call reads no plane of a
+  // level >= 1, and the next call's preparation — pyramids, gradients of the levels >= 1 — writes nothing else.  A call that ends on
+  // level 0 records ev_window[part] behind level 1 on each part's stream; win_open: the previous device-work entry on this context
+  // was such a call and nothing has touched the context since (close_window), so the next uwt_track_batch_async may put its
+  // preparation on `side` behind these events, under the previous call's level 0.  win_parts: events the call in hand recorded.
+  // ev_entry: the context stream at a call's entry, i.e. the previous call's end — the level-0 gradients wait for it.
+  // ev_first_end: the end of part 0 of a call that ran as parts — inside the window, and where the preparation is placed then.
+  hipEvent_t ev_window[kMaxParts] = {}, ev_entry = nullptr, ev_first_end = nullptr;
+  bool win_open = false;
+  int win_parts = 0;
   uint8_t* img[UWT_MAX_LEVELS] = {};
   uint16_t* depth[UWT_MAX_LEVELS] = {};
   int16_t* gx[UWT_MAX_LEVELS] = {};
   int16_t* gy[UWT_MAX_LEVELS] = {};
   PairState* state = nullptr;
+  // the pair lists the launches read: those of set pair_set.  Two device sets [ref(max_pairs) | tgt(max_pairs)]: an early
+  // preparation reads its call's reference list while the previous call's launches still read theirs, so a call with new lists that
+  // prepares early sends them to the idle set (on `side`) and makes that set the current one; every other call writes the current
+  // set on the context stream, behind everything that read it.
   int* d_ref = nullptr;
   int* d_tgt = nullptr;
+  int* d_pair_set[2] = {};
+  int pair_set = 0;
   // pinned staging of the pair lists, a ring of kPairStages [ref(max_pairs) | tgt(max_pairs)] blocks: a new list is
-  // written to the next block while the asynchronous copy of the previous one may still be reading its own
+  // written to a block neither device set was filled from while the asynchronous copy of an earlier one may still be reading its own
   static constexpr int kPairStages = 4;
   int* h_pairs = nullptr;
   hipEvent_t ev_pairs[kPairStages] = {};
-  int pair_stage = 0;                   // block holding the lists that are on the device
-  int n_pairs_cached = 0;
+  int pair_stage[2] = {0, 1};           // per device set: the block holding the lists that are in it ...
+  int n_pairs_cached[2] = {0, 0};       // ... and how many pairs they have (0: none yet)
+  int pair_stage_last = 1;              // the block written last
   // Copy stream + slot-range dependencies (uwt_upload_frames_async): `busy` = compute work enqueued on `stream` that
   // reads or writes a slot range, `fresh` = uploads enqueued on `copy` into a slot range.  An upload waits for the busy
   // entries it overlaps, a compute call for the fresh ones; both rings are in stream order, so once an entry has been
@@ -260,7 +277,7 @@ int stage_host_seeds(uwt_ctx* c, const float* seeds_or_null, int n_pairs, Start*
 inline bool slot_range_ok(const uwt_ctx* c, int first, int n) { return first >= 0 && n >= 0 && (long long)first + n <= c->p.max_frames; }
 template <typename T>
 int launch_resize(uwt_ctx* c, const T* src, T* dst, int sw, int sh, int src_pitch, int dw, int dh, int dst_pitch, size_t sfs,
-                  size_t dfs, int n_frames, const int* d_slots = nullptr, int first_slot = 0);   // T: uint8_t, uint16_t
+                  size_t dfs, int n_frames, const int* d_slots = nullptr, int first_slot = 0, hipStream_t on = nullptr);   // T: uint8_t, uint16_t
 int launch_scharr(uwt_ctx* c, const uint8_t* src, int16_t* gx, int16_t* gy, int w, int h, int pitch, size_t fs, int n_frames,
                   const int* d_slots = nullptr, int first_slot = 0, hipStream_t on = nullptr);
 LaunchSel launch_sel(const uwt_ctx* c);
@@ -273,6 +290,11 @@ void arm_tail(uwt_ctx* c, ResidualArgs& ra, const UpdateArgs& ua);
 int poll_arm(uwt_ctx* c);
 int poll_any_left(uwt_ctx* c, bool* left);
 int dep_wait(uwt_ctx* c, const uwt_ctx::SlotDep* ring, int next, bool dropped, hipStream_t waiter, int first, int n);
+// Early preparation: whatever enqueues device work on the context, reads planes back or changes its settings between two batch calls
+// closes the window the first one left (uwt_ctx::win_open) — the next call is then enqueued in one piece behind it.  Called by the
+// helpers such entries pass through: compute_begin / compute_begin_pairs, upload_pairs, DevBuf::reserve / adopt on any stream but
+// the copy stream, the read-back helpers, and by the entries that pass through none of them.
+inline void close_window(uwt_ctx* c) { c->win_open = false; }
 int compute_begin(uwt_ctx* c, int first, int n);
 int compute_end(uwt_ctx* c, int first, int n);
 int compute_begin_pairs(uwt_ctx* c, int n, const int32_t* slots_a, const int32_t* slots_b);
