@@ -184,6 +184,18 @@ int prof_begin(uwt_ctx* c, size_t* idx, int lvl = 0, int evaluations = 1) {
   return UWT_OK;
 }
 
+// closes prof_begin's bracket behind the launch on stream s, which evaluated `pixels` pixels `evaluations` times
+hipError_t prof_end(uwt_ctx* c, size_t idx, hipStream_t s, long long pixels, int evaluations = 1) {
+  c->prof_launches += evaluations;
+  c->prof_pixels += pixels * evaluations;
+  return hipEventRecord(c->ev_pool[idx + 1], s);
+}
+
+// stream s waits for level lvl's gradients, unless it is the first level
+hipError_t wait_level(const uwt_ctx* c, hipStream_t s, const hipEvent_t* level_ready, int lvl) {
+  return level_ready && lvl != c->p.first_level ? hipStreamWaitEvent(s, level_ready[lvl], 0) : hipSuccess;
+}
+
 int prof_collect(uwt_ctx* c) {  // after a stream sync
   for (size_t i = 0; i + 1 < c->ev_used; i += 2) {
     float ms = 0.f;
@@ -240,11 +252,28 @@ Chained chained_form(const uwt_ctx* c, int n_pairs) {
 struct CallOpts {
   bool speculate = false;              // launch a level's usual number of evaluations without reading back, check once at the
                                        // end, redo conservatively if cut short
-  bool inline_pairs = false;           // the (at most two) pairs' slots travel in the kernel arguments: no pair list upload
-  int pair_slots[4] = {0, 0, 0, 0};    // ref 0, tgt 0, ref 1, tgt 1
+  InlinePairs pairs = {};              // on: the (at most two) pairs' slots travel in the kernel arguments: no pair list upload
   bool window = false;                 // uwt_track_batch_async: record the window events of the early preparation (uwt_ctx::ev_window)
                                        // where the schedule has a window
 };
+
+// The arguments of a k_coarse / k_coarse_w4 / k_coarse_weighted launch but for what differs from site to site: the levels
+// (coarse_level, n_levels), resume, u.pair_base and where the pairs' states are kept (state_out).
+CoarseArgs coarse_args(const UpdateRule& rule, const StartRec& start, const InlinePairs& pairs) {
+  CoarseArgs ca;
+  std::memset(&ca, 0, sizeof(ca));
+  ca.u.rule = rule;
+  ca.start = start;
+  ca.pairs = pairs;
+  return ca;
+}
+
+// level lvl as the i-th of the launch
+void coarse_level(uwt_ctx* c, CoarseArgs& ca, int i, int lvl) {
+  ca.lv[i] = residual_args(c, lvl);
+  ca.lv[i].state = nullptr;
+  ca.level_id[i] = lvl;
+}
 
 // The chained form of Tracker::EstimatePose for a few pairs (dense points, any level size): one launch step per evaluation —
 // each block first applies the update of the previous evaluation (and the level hand-off when a level begins), then
@@ -263,15 +292,8 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
   int rp = 0, sp = 0;            // parity of the records / states the NEXT evaluation writes
   IterArgs ia;
   std::memset(&ia, 0, sizeof(ia));
-  ia.u.max_iters = p.max_iters;
-  ia.u.early_exit = p.early_exit;
-  ia.u.epsilon = p.epsilon;
-  ia.u.gain = p.gain;
-  ia.u.general = robust ? 1 : 0;
-  ia.u.legacy_solve = p.arith == UWT_ARITH_LEGACY ? 1 : 0;
-  ia.scale_t = start.scale_t(p);
-  ia.seeds = start.d_seeds;       // read by the first launch alone (mode 0, or k_coarse / k_coarse_weighted without resume)
-  ia.initial_error = p.initial_error;
+  ia.u.rule = update_rule(p, robust);
+  ia.start = start.rec(p);        // seeds: read by the first launch alone (mode 0, or k_coarse / k_coarse_weighted without resume)
   // Speculative launching (identity weights, early-exit schedules, the synchronous one- or two-pair call): every read-back of
   // "who is still iterating" costs a host round trip of about two evaluations; instead each level gets the evaluations levels
   // usually take plus one, nothing is read back, and the level switch notes on the device whether a pair was cut short — the
@@ -280,8 +302,7 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
   const int evals = speculate ? std::min(p.max_iters, std::max(c->spec_budget, c->tn.first_poll + 1)) : p.max_iters;
   ia.cut_short = speculate ? &c->d_small->cut : nullptr;
   if (speculate) c->h_small->cut = 0;   // host store into page-locked memory, ahead of the launches that may set it
-  ia.inline_pairs = opt.inline_pairs ? 1 : 0;
-  for (int i = 0; i < 4; i++) ia.pair_slots[i] = opt.pair_slots[i];
+  ia.pairs = opt.pairs;
   // robust weights: the per-pair residual histograms (and the ticket word of each) start an alignment all-zero; every scale
   // pass leaves them so
   if (robust) HIPCHK(c, hipMemsetAsync(c->hist, 0, sizeof(unsigned int) * kHistBins * n_pairs, c->stream));
@@ -289,25 +310,15 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
   // the chained launches.
   int start_lvl = p.first_level;
   bool after_coarse = false;
-  CoarseArgs ca;
-  std::memset(&ca, 0, sizeof(ca));
-  ca.u = ia.u;
+  CoarseArgs ca = coarse_args(ia.u.rule, ia.start, ia.pairs);
   ca.state_out = states[sp ^ 1];     // where the first chained launch looks for its state
-  ca.scale_t = ia.scale_t;
-  ca.seeds = ia.seeds;
-  ca.initial_error = ia.initial_error;
-  ca.inline_pairs = ia.inline_pairs;
-  for (int i = 0; i < 4; i++) ca.pair_slots[i] = ia.pair_slots[i];
   if (!robust) {   // identity weights: up to kCoarseMaxLevels levels in one k_coarse launch
     int nc = 0;
     while (nc < kCoarseMaxLevels && start_lvl - nc > p.last_level && c->lv[start_lvl - nc].ng <= kCoarseMaxPixels) nc++;
     if (nc > 0 && c->tn.coarse && !c->profiling && !c->compute_only) {
       for (int i = 0; i < nc; i++) {
-        const int lvl = p.first_level - i;
-        if (level_ready && lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(c->stream, level_ready[lvl], 0));  // its gradients
-        ca.lv[i] = residual_args(c, lvl);
-        ca.lv[i].state = nullptr;
-        ca.level_id[i] = lvl;
+        HIPCHK(c, wait_level(c, c->stream, level_ready, p.first_level - i));
+        coarse_level(c, ca, i, p.first_level - i);
       }
       ca.n_levels = nc;
       uwt::launch_coarse_chain(c->stream, launch_sel(c), ca, n_pairs);
@@ -317,10 +328,8 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
     }
   } else {   // robust weights over the nearest sampler: one k_coarse_weighted launch per level
     while (c->tn.coarse_weighted && p.sampler == 0 && start_lvl > p.last_level && c->lv[start_lvl].ng <= kCoarseMaxPixels) {
-      if (level_ready && start_lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(c->stream, level_ready[start_lvl], 0));  // its gradients
-      ca.lv[0] = residual_args(c, start_lvl);
-      ca.lv[0].state = nullptr;
-      ca.level_id[0] = start_lvl;
+      HIPCHK(c, wait_level(c, c->stream, level_ready, start_lvl));
+      coarse_level(c, ca, 0, start_lvl);
       ca.n_levels = 1;
       ca.resume = after_coarse ? 1 : 0;
       uwt::launch_coarse_level(c->stream, launch_sel(c), ca, n_pairs, p.weights);
@@ -332,7 +341,7 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
   bool first = true;
   int prev_slices = 0, prev_k = 0, prev_lvl = p.first_level;
   for (int lvl = start_lvl; lvl >= p.last_level; lvl--) {
-    if (level_ready && lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(c->stream, level_ready[lvl], 0));  // its gradients
+    HIPCHK(c, wait_level(c, c->stream, level_ready, lvl));
     ResidualArgs ra = residual_args(c, lvl);
     ra.state = nullptr;
     level_slicing(c, lvl, n_pairs, c->tn.target_blocks ? c->tn.target_blocks : 4096, false, ra.groups_per_block, ra.slices);
@@ -369,11 +378,7 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
         uwt::launch_iterate(c->stream, launch_sel(c), ra, ia, n_pairs);
       }
       HIPCHK(c, hipGetLastError());
-      if (c->profiling) {
-        HIPCHK(c, hipEventRecord(c->ev_pool[ev + 1], c->stream));
-        c->prof_launches += 1;
-        c->prof_pixels += (long long)n_pairs * c->lv[lvl].gw * c->lv[lvl].gh;
-      }
+      if (c->profiling) HIPCHK(c, prof_end(c, ev, c->stream, (long long)n_pairs * c->lv[lvl].gw * c->lv[lvl].gh));
       first = false;
       prev_slices = ra.slices;
       prev_k = k;
@@ -453,19 +458,12 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
       coarse_lvl[lvl] = c->lv[lvl].ng <= c->tn.coarse_batch_px;
   // one coarse level of pairs [base, base + cnt) on stream s; resume: the pairs' states exist (a level ran before this one)
   auto run_coarse = [&](int base, int cnt, hipStream_t s, int lvl, bool resume) -> int {
-    CoarseArgs ca;
-    std::memset(&ca, 0, sizeof(ca));
-    ca.lv[0] = residual_args(c, lvl);
-    ca.lv[0].state = nullptr;
-    ca.level_id[0] = lvl;
+    // (the seeds are read without resume only; the kernel indexes them by the pair's place in the call)
+    CoarseArgs ca = coarse_args(update_rule(p, general), start.rec(p), InlinePairs{});
+    coarse_level(c, ca, 0, lvl);
     ca.n_levels = 1;
-    UpdateArgs u = update_args(c, lvl);
-    u.pair_base = base;
-    ca.u = u;
+    ca.u.pair_base = base;
     ca.state_out = c->state;
-    ca.scale_t = start.scale_t(p);
-    ca.seeds = start.d_seeds;   // (read without resume only; the kernel indexes by the pair's place in the call)
-    ca.initial_error = p.initial_error;
     ca.resume = resume ? 1 : 0;
     size_t ev = 0;
     if (c->profiling) {
@@ -474,11 +472,8 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
     }
     uwt::launch_coarse_level(s, launch_sel(c), ca, cnt, general ? p.weights : 0);
     HIPCHK(c, hipGetLastError());
-    if (c->profiling) {   // (fixed schedules only: the level runs max_iters evaluations; the launch stands for that many)
-      HIPCHK(c, hipEventRecord(c->ev_pool[ev + 1], s));
-      c->prof_launches += p.max_iters;
-      c->prof_pixels += (long long)cnt * c->lv[lvl].gw * c->lv[lvl].gh * p.max_iters;
-    }
+    // (fixed schedules only: the level runs max_iters evaluations; the launch stands for that many)
+    if (c->profiling) HIPCHK(c, prof_end(c, ev, s, (long long)cnt * c->lv[lvl].gw * c->lv[lvl].gh, p.max_iters));
     return UWT_OK;
   };
   // tn.tail_update: the update in the tail of the evaluation's launch where the batch runs as parts, on one stream only when
@@ -511,15 +506,15 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
     q.s = i ? c->part_stream[i] : c->stream;
     if (i) HIPCHK(c, hipStreamWaitEvent(q.s, c->ev_fork, 0));
     if (!coarse_lvl[p.first_level]) {
-      hipLaunchKernelGGL(k_init_state, dim3((q.cnt + tb - 1) / tb), dim3(tb), 0, q.s, c->state + q.base, q.cnt, p.initial_error,
-                         start.d_seeds ? start.d_seeds + 7 * (size_t)q.base : nullptr, nullptr);
+      hipLaunchKernelGGL(k_init_state, dim3((q.cnt + tb - 1) / tb), dim3(tb), 0, q.s, c->state + q.base, q.cnt, start.rec(p, q.base),
+                         nullptr);
       HIPCHK(c, hipGetLastError());
     }
   }
   for (int lvl = p.first_level; lvl >= p.last_level; lvl--) {
     for (int i = 0; i < parts; i++) {
       Part& q = pt[i];
-      if (level_ready && lvl != p.first_level) HIPCHK(c, hipStreamWaitEvent(q.s, level_ready[lvl], 0));  // its gradients
+      HIPCHK(c, wait_level(c, q.s, level_ready, lvl));
       if (coarse_lvl[lvl]) {
         int st = run_coarse(q.base, q.cnt, q.s, lvl, lvl != p.first_level);
         if (st) return st;
@@ -527,7 +522,7 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
         continue;
       }
       q.ra = residual_args(c, lvl);
-      q.ua = update_args(c, lvl);
+      q.ua = update_args(c, lvl, general);
       q.ra.pair_base = q.ua.pair_base = q.base;
       q.ra.stream_planes = streams(lvl);
       level_slicing(c, lvl, n_pairs, target_blocks, !p.early_exit, q.ra.groups_per_block, q.ra.slices);
@@ -538,7 +533,6 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
       const size_t shift = (size_t)q.base * (size_t)(smax - q.ra.slices) * kRecWords;
       q.ra.partials = c->partials + shift;
       q.ua.partials = c->partials + shift;
-      if (general) q.ua.general = 1;
     }
     if (coarse_lvl[lvl]) continue;
     // Early exit (one part): the host reads back how many pairs are still iterating after the update of evaluation
@@ -569,11 +563,7 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
         if (tail) arm_tail(c, q.ra, q.ua);
         st = general ? launch_general(c, q.s, q.ra, q.cnt, false) : launch_residual(c, q.s, q.ra, q.cnt, false);
         if (st) return st;
-        if (c->profiling) {
-          HIPCHK(c, hipEventRecord(c->ev_pool[ev + 1], q.s));
-          c->prof_launches += 1;
-          c->prof_pixels += (long long)q.cnt * c->lv[lvl].gw * c->lv[lvl].gh;
-        }
+        if (c->profiling) HIPCHK(c, prof_end(c, ev, q.s, (long long)q.cnt * c->lv[lvl].gw * c->lv[lvl].gh));
         if (!tail) {
           hipLaunchKernelGGL(k_gn_update, dim3(q.cnt), dim3(kUpdateBlock), 0, q.s, q.ua);
           HIPCHK(c, hipGetLastError());
@@ -584,7 +574,7 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
       }
     for (int i = 0; i < parts; i++) {
       hipLaunchKernelGGL(k_level_end, dim3((pt[i].cnt + tb - 1) / tb), dim3(tb), 0, pt[i].s, c->state + pt[i].base, pt[i].cnt, lvl,
-                         start.scale_t(p), p.initial_error);
+                         start.rec(p));
       HIPCHK(c, hipGetLastError());
       if (window && lvl == 1) HIPCHK(c, hipEventRecord(c->ev_window[i], pt[i].s));
     }
@@ -778,7 +768,7 @@ int launch_residual(uwt_ctx* c, hipStream_t s, const ResidualArgs& a, int n_pair
   return UWT_OK;
 }
 
-ResidualArgs residual_args(uwt_ctx* c, int lvl) {
+ResidualArgs residual_args(uwt_ctx* c, int lvl, const uwt_params& q) {
   ResidualArgs a;
   std::memset(&a, 0, sizeof(a));
   a.img = c->img[lvl];
@@ -789,13 +779,13 @@ ResidualArgs residual_args(uwt_ctx* c, int lvl) {
   a.tgt_slots = c->d_tgt;
   a.state = c->state;
   a.L = c->lv[lvl];
-  a.zf = c->p.z_factor;
-  a.af = c->p.angle_factor;
+  a.zf = q.z_factor;
+  a.af = q.angle_factor;
   a.groups_per_block = c->groups_per_block[lvl];
   a.slices = c->slices[lvl];
   a.partials = c->partials;
   a.scale = c->scale;
-  a.gain = c->p.gain;
+  a.gain = q.gain;
   a.typed_loads = c->tn.typed_loads;
   return a;
 }
@@ -808,17 +798,18 @@ int launch_general(uwt_ctx* c, hipStream_t s, const ResidualArgs& ra, int n_pair
   return UWT_OK;
 }
 
-UpdateArgs update_args(uwt_ctx* c, int lvl) {
+// the update's rule under the constants q; general: the records are the general path's
+UpdateRule update_rule(const uwt_params& q, bool general) {
+  return {q.max_iters, q.early_exit, q.epsilon, q.gain, general ? 1 : 0, q.arith == UWT_ARITH_LEGACY ? 1 : 0};
+}
+
+UpdateArgs update_args(uwt_ctx* c, int lvl, const uwt_params& q, bool general) {
   UpdateArgs ua;
   std::memset(&ua, 0, sizeof(ua));
   ua.partials = c->partials;
   ua.state = c->state;
   ua.slices = c->slices[lvl];
-  ua.max_iters = c->p.max_iters;
-  ua.early_exit = c->p.early_exit;
-  ua.epsilon = c->p.epsilon;
-  ua.gain = c->p.gain;
-  ua.legacy_solve = c->p.arith == UWT_ARITH_LEGACY ? 1 : 0;
+  ua.rule = update_rule(q, general);
   return ua;
 }
 
@@ -843,12 +834,7 @@ void arm_tail(uwt_ctx* c, ResidualArgs& ra, const UpdateArgs& ua) {
   ra.tail.state = ua.state;
   ra.tail.active = ua.active;
   ra.tail.k = ua.k;
-  ra.tail.max_iters = ua.max_iters;
-  ra.tail.early_exit = ua.early_exit;
-  ra.tail.general = ua.general;
-  ra.tail.legacy_solve = ua.legacy_solve;
-  ra.tail.epsilon = ua.epsilon;
-  ra.tail.gain = ua.gain;
+  ra.tail.rule = ua.rule;
 }
 
 // Reference-mode early exit, read back synchronously: the launch handed c->d_active counts the pairs still iterating on its
@@ -1555,13 +1541,13 @@ static int estimate_pose_batch(uwt_ctx* c, const char* what, int32_t n_pairs, co
   if (st) return st;
   const bool chained = chained_form(c, n_pairs) == Chained::identity;
   CallOpts opt;
-  opt.inline_pairs = n_pairs <= 2 && chained;
-  if (opt.inline_pairs) {   // the slots travel in the kernel arguments
+  opt.pairs.on = n_pairs <= 2 && chained;
+  if (opt.pairs.on) {   // the slots travel in the kernel arguments
     for (int i = 0; i < n_pairs; i++) {
       if (ref_slots[i] < 0 || ref_slots[i] >= c->p.max_frames || tgt_slots[i] < 0 || tgt_slots[i] >= c->p.max_frames)
         return fail(c, UWT_ERR_INVALID_ARG, "pair slot out of range");
-      opt.pair_slots[2 * i] = ref_slots[i];
-      opt.pair_slots[2 * i + 1] = tgt_slots[i];
+      opt.pairs.slots[2 * i] = ref_slots[i];
+      opt.pairs.slots[2 * i + 1] = tgt_slots[i];
     }
   } else {
     st = upload_pairs(c, n_pairs, ref_slots, tgt_slots);

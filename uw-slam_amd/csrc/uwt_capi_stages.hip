@@ -309,17 +309,16 @@ int uwt_gn_update_records(uwt_ctx* c, int32_t form, int32_t n_pairs, int32_t pai
   HIPCHK(c, hipMemcpyAsync(d_st, states_in, sizeof(PairState) * rows, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(d_act, 0, sizeof(int), c->stream));
   HIPCHK(c, hipMemsetAsync(d_tk, 0, sizeof(unsigned int) * rows, c->stream));
-  const int legacy = c->p.arith == UWT_ARITH_LEGACY ? 1 : 0;
+  const UpdateRule rule = {max_iters, early_exit, epsilon, gain, general ? 1 : 0, c->p.arith == UWT_ARITH_LEGACY ? 1 : 0};
   if (form == 0) {
     UpdateArgs u{};
     u.partials = d_rec;
     u.state = d_st;
     u.slices = count;
-    u.k = k; u.max_iters = max_iters; u.early_exit = early_exit; u.epsilon = epsilon; u.gain = gain;
+    u.k = k;
+    u.rule = rule;
     u.pair_base = pair_base;
-    u.general = general ? 1 : 0;
     u.active = d_act;
-    u.legacy_solve = legacy;
     hipLaunchKernelGGL(k_gn_update, dim3(n_pairs), dim3(kUpdateBlock), 0, c->stream, u);
   } else {
     ResidualArgs a{};
@@ -330,9 +329,8 @@ int uwt_gn_update_records(uwt_ctx* c, int32_t form, int32_t n_pairs, int32_t pai
     a.tail.state = d_st;
     a.tail.active = d_act;
     a.tail.on = 1;
-    a.tail.k = k; a.tail.max_iters = max_iters; a.tail.early_exit = early_exit; a.tail.epsilon = epsilon; a.tail.gain = gain;
-    a.tail.general = general ? 1 : 0;
-    a.tail.legacy_solve = legacy;
+    a.tail.k = k;
+    a.tail.rule = rule;
     hipLaunchKernelGGL(k_tail_fold_stage, dim3(count, n_pairs), dim3(64), 0, c->stream, a, (int)stride, (int)count);
   }
   HIPCHK(c, hipGetLastError());

@@ -284,25 +284,16 @@ int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const T
     HIPCHK(c, hipMemsetAsync(c->hist, 0, sizeof(unsigned int) * kHistBins * (size_t)n_pairs, c->stream));
   }
   const GeneralArgs ga = {opt.sampler, opt.weights, q.gain, c->hist, c->scale};
-  hipLaunchKernelGGL(k_init_state, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, q.initial_error, start.d_seeds,
-                     start.d_gate);
+  hipLaunchKernelGGL(k_init_state, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, start.rec(q), start.d_gate);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemsetAsync(c->d_tickets, 0, sizeof(unsigned int) * (size_t)n_pairs, c->stream));
   for (int lvl = q.first_level; lvl >= q.last_level; lvl--) {
-    ResidualArgs ra = residual_args(c, lvl);
-    ra.zf = q.z_factor;
-    ra.af = q.angle_factor;
-    ra.gain = q.gain;
+    ResidualArgs ra = residual_args(c, lvl, q);
     ra.slices = lv[lvl].slices;
     ra.partials = recs;
-    UpdateArgs ua = update_args(c, lvl);
+    UpdateArgs ua = update_args(c, lvl, q, general);
     ua.partials = recs;
     ua.slices = ra.slices;
-    ua.max_iters = q.max_iters;
-    ua.early_exit = q.early_exit;
-    ua.epsilon = q.epsilon;
-    ua.gain = q.gain;
-    if (general) ua.general = 1;
     LatePoll late(c->tn.first_poll);
     for (int k = 0; k < q.max_iters; k++) {
       ua.k = k;
@@ -317,7 +308,7 @@ int enqueue_table_estimate(uwt_ctx* c, int n_pairs, const uwt_params& q, const T
       if (st) return st;
       if (none_left) break;
     }
-    hipLaunchKernelGGL(k_level_end, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, lvl, start.scale_t(q), q.initial_error);
+    hipLaunchKernelGGL(k_level_end, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, lvl, start.rec(q));
     HIPCHK(c, hipGetLastError());
   }
   hipLaunchKernelGGL(k_write_out, dim3(blocks), dim3(tb), 0, c->stream, c->state, n_pairs, d_poses, d_stats);

@@ -266,6 +266,10 @@ struct Start {
   const int* d_gate = nullptr;      // table calls: per-pair counts, a pair whose count is 0 starts at the identity (k_init_state), or null
   // (handoff_scale_t is any int, non-zero = on, as the kernels always read it: only `keep` can give kHandoffKeep)
   int scale_t(const uwt_params& q) const { return keep ? kHandoffKeep : (q.handoff_scale_t != 0 ? 1 : 0); }
+  // what the kernels read of it under the constants q; base: the first pair of the launch where its kernel counts from there (k_init_state)
+  StartRec rec(const uwt_params& q, int base = 0) const {
+    return {scale_t(q), d_seeds ? d_seeds + 7 * (size_t)base : nullptr, q.initial_error};
+  }
 };
 
 // ---- helpers of uwt_capi.hip that the other host units call (described at their definitions) ------------------------------
@@ -283,8 +287,12 @@ int launch_scharr(uwt_ctx* c, const uint8_t* src, int16_t* gx, int16_t* gy, int 
 LaunchSel launch_sel(const uwt_ctx* c);
 int launch_residual(uwt_ctx* c, hipStream_t s, const ResidualArgs& a, int n_pairs, bool dump);
 int launch_general(uwt_ctx* c, hipStream_t s, const ResidualArgs& ra, int n_pairs, bool dump);
-ResidualArgs residual_args(uwt_ctx* c, int lvl);
-UpdateArgs update_args(uwt_ctx* c, int lvl);
+// (q: the constants the launches run under; the table calls have their own)
+UpdateRule update_rule(const uwt_params& q, bool general);
+ResidualArgs residual_args(uwt_ctx* c, int lvl, const uwt_params& q);
+inline ResidualArgs residual_args(uwt_ctx* c, int lvl) { return residual_args(c, lvl, c->p); }
+UpdateArgs update_args(uwt_ctx* c, int lvl, const uwt_params& q, bool general);
+inline UpdateArgs update_args(uwt_ctx* c, int lvl, bool general) { return update_args(c, lvl, c->p, general); }
 int ensure_general_buffers(uwt_ctx* c);
 void arm_tail(uwt_ctx* c, ResidualArgs& ra, const UpdateArgs& ua);
 int poll_arm(uwt_ctx* c);

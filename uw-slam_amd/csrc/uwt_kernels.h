@@ -1261,14 +1261,27 @@ static __global__ __launch_bounds__(1024) void k_robust_weights(const float* __r
 // reference level (implicit dense point table), gathers the target level, accumulates in registers and writes
 // one partial record.  Reference planes are read with one VEC-wide load per plane per group.
 // ------------------------------------------------------------------------------------------------------------
+// The rule of the Gauss-Newton update (update_solve_wave): the constants of the solver an alignment runs under, the same for every
+// launch of it.  The iteration index `k` and the poll counter `active` belong to the launch and sit beside it (UpdateArgs, TailUpdate).
+// (The order of the fields here, in UpdateArgs and in StartRec is part of the kernels' register budget: the coarse kernels sit at
+// the scalar-register limit, and which argument words share a load decides how many of them are spilled.)
+struct UpdateRule {
+  int max_iters;
+  int early_exit;
+  float epsilon;
+  float gain;
+  int general;       // 1: records of the general path (gain already applied, error numerator in slot 29)
+  int legacy_solve;  // uwt_params::arith == UWT_ARITH_LEGACY: A.inv() formed, then multiplied (else cv::solve's LU on b)
+};
+
 // The update of an evaluation in the tail of the evaluation's own launch (tail_update_wave) instead of a k_gn_update launch.
 struct TailUpdate {
   unsigned int* tickets;    // one word per pair (indexed like `state`), zero between launches
   PairState* state;         // the pairs' states, writable
   int* active;              // see UpdateArgs
   int on;                   // 0: the launch leaves its records to k_gn_update
-  int k, max_iters, early_exit, general, legacy_solve;
-  float epsilon, gain;
+  int k;                    // iteration index at this level
+  UpdateRule rule;
 };
 
 struct ResidualArgs {
@@ -2367,14 +2380,9 @@ struct UpdateArgs {
   PairState* state;
   int slices;
   int k;             // iteration index at this level
-  int max_iters;
-  int early_exit;
-  float epsilon;
-  float gain;
-  int pair_base;
-  int general;       // 1: records of the general path (gain already applied, error numerator in slot 29)
+  UpdateRule rule;
   int* active;       // optional: counts the pairs still iterating after this update (early-exit polling)
-  int legacy_solve;  // uwt_params::arith == UWT_ARITH_LEGACY: A.inv() formed, then multiplied (else cv::solve's LU on b)
+  int pair_base;
 };
 
 constexpr int kUpdateBlock = 256;   // threads of an updating block: all fold the records, wave 0 solves
@@ -2384,8 +2392,9 @@ constexpr int kUpdateLdsBytes = 2 * 8 * 32 * 8 + 512;   // part sums (two readin
 
 // One wave, uniform values: from the evaluation's folded sums (sums[0..26]: JtJ upper triangle and Jtr, sums[27]: the
 // weighted error numerator; isums: valid pixels, integer sum of r^2) to the pair's next state.
-__device__ __forceinline__ void update_solve_wave(const UpdateArgs& a, PairState& st, const double* __restrict__ sums,
-                                                  const long long* __restrict__ isums, bool count_active, int lane) {
+// active: null, or the counter of the pairs still iterating after this update (the caller passes it where this wave is to count).
+__device__ __forceinline__ void update_solve_wave(const UpdateRule& a, int k, int* active, PairState& st, const double* __restrict__ sums,
+                                                  const long long* __restrict__ isums, int lane) {
   const int n = (int)isums[0];
   const long long sr2 = isums[1];
   st.iters += 1;
@@ -2401,7 +2410,7 @@ __device__ __forceinline__ void update_solve_wave(const UpdateArgs& a, PairState
                                   : (float)((double)inv_n * (double)sr2);       // :501, scaled-gemm form (exact integer Σr²)
     st.error = error;
     if (a.early_exit &&
-        (error >= st.last_error || a.k == a.max_iters - 1 || fabsf(error - st.last_error) < a.epsilon)) {  // :508
+        (error >= st.last_error || k == a.max_iters - 1 || fabsf(error - st.last_error) < a.epsilon)) {  // :508
       st.level_done = 1;
       update = false;
     } else {
@@ -2418,7 +2427,7 @@ __device__ __forceinline__ void update_solve_wave(const UpdateArgs& a, PairState
     se3_exp_wave(delta, d);                                                         // :574
     se3_mul(st.pose, d, np);
     st.pose = np;
-    if (count_active && a.active && lane == 0) atomicAdd(a.active, 1);
+    if (active && lane == 0) atomicAdd(active, 1);
   }
 }
 
@@ -2479,20 +2488,11 @@ __device__ __forceinline__ void tail_fold_wave(const ResidualArgs& a, int pair, 
     if (lane < kAccFloats) t_sums[lane] = fs;
     else if (lane == 27) t_isums[0] = (long long)(uint32_t)ls;
     else if (lane == 28) t_isums[1] = ls;
-    else if (lane == 29) t_sums[kAccFloats] = a.tail.general ? fs : 0.0;
+    else if (lane == 29) t_sums[kAccFloats] = a.tail.rule.general ? fs : 0.0;
   }
   __builtin_amdgcn_wave_barrier();
-  UpdateArgs u;
-  u.k = a.tail.k;
-  u.max_iters = a.tail.max_iters;
-  u.early_exit = a.tail.early_exit;
-  u.epsilon = a.tail.epsilon;
-  u.gain = a.tail.gain;
-  u.general = a.tail.general;
-  u.legacy_solve = a.tail.legacy_solve;
-  u.active = a.tail.active;
   PairState st = a.tail.state[pair];   // as every block of the pair read it at the start: nobody has written it since
-  update_solve_wave(u, st, t_sums, t_isums, true, lane);
+  update_solve_wave(a.tail.rule, a.tail.k, a.tail.active, st, t_sums, t_isums, lane);
   if (lane == 0) a.tail.state[pair] = st;
 }
 
@@ -2552,12 +2552,12 @@ __device__ __forceinline__ PairState update_compute(const UpdateArgs& a, const u
       if (tid < kAccFloats) sums[tid] = fs;
       else if (tid == 27) isums[0] = (long long)(uint32_t)ls;
       else if (tid == 28) isums[1] = ls;
-      else if (tid == 29) sums[kAccFloats] = a.general ? fs : 0.0;
+      else if (tid == 29) sums[kAccFloats] = a.rule.general ? fs : 0.0;
     }
   }
   __builtin_amdgcn_wave_barrier();   // the sums were written by lanes of wave 0, which alone reads them
   if (tid < 64) {   // wave 0 runs the tail together on the same (uniform) values
-    if (live) update_solve_wave(a, st, sums, isums, count_active, lane);
+    if (live) update_solve_wave(a.rule, a.k, count_active ? a.active : nullptr, st, sums, isums, lane);
     if (lane == 0) *s_state = st;
   }
   __syncthreads();
@@ -2579,25 +2579,43 @@ static __global__ __launch_bounds__(kUpdateBlock) void k_gn_update(const UpdateA
 // here on, and every launch returns at once for it (status != 0), as for any failed pair.
 // level_handoff: scale_t 0 / 1 = the reference's hand-off (se3_handoff under uwt_params::handoff_scale_t), kHandoffKeep =
 // uwt_seed_options::handoff 1: the pose crosses unchanged.  Both sit in the block-uniform preamble and the update tail.
+// level_end: the one body of the level-end rule, for every launch form that ends a level.
+// StartRec is what the three read, built on the host by Start::rec (uwt_ctx.h); the device functions take it by reference to
+// where it already is (the kernel-argument segment).
 // ------------------------------------------------------------------------------------------------------------
 constexpr int kHandoffKeep = 2;
 constexpr int kStatusBadSeed = 1;   // UWT_ERR_INVALID_ARG
 
-__device__ __forceinline__ PairState first_state(const float* __restrict__ seeds, int pair, float initial_error) {
+struct StartRec {
+  int scale_t;           // level_handoff's: 0 / 1 the reference's hand-off, kHandoffKeep
+  const float* seeds;    // the pairs' start poses, read by the alignment's first launch alone; null = the identity
+  float initial_error;   // last_error in front of every level (src/Tracker.cpp:392-393)
+};
+
+// the state in front of an alignment's first evaluation at `pose`
+__device__ __forceinline__ PairState fresh_state(const Pose& pose, float initial_error) {
   PairState st;
-  pose_identity(st.pose);  // src/Tracker.cpp:385
+  st.pose = pose;
   st.last_error = initial_error;
   st.error = 0.f;
   st.level_done = 0;
   st.status = 0;
   st.iters = 0;
   st.n_valid = 0;
-  if (seeds) {
+  return st;
+}
+
+// seeded false: the pair starts at the identity whatever its seed row holds (k_init_state's gate)
+__device__ __forceinline__ PairState first_state(const StartRec& s, int pair, bool seeded = true) {
+  Pose id;
+  pose_identity(id);  // src/Tracker.cpp:385
+  PairState st = fresh_state(id, s.initial_error);
+  if (s.seeds && seeded) {
     float v[7];
     bool finite = true;
 #pragma unroll
     for (int k = 0; k < 7; k++) {
-      v[k] = seeds[7 * (size_t)pair + k];
+      v[k] = s.seeds[7 * (size_t)pair + k];
       finite = finite && (__float_as_uint(v[k]) & 0x7f800000u) != 0x7f800000u;
     }
     if (finite) {
@@ -2617,6 +2635,29 @@ __device__ __forceinline__ bool level_handoff(Pose& p, int scale_t) {
   return se3_handoff(p, scale_t != 0);
 }
 
+// end of pyramid level `lvl`: hand-off (src/Tracker.cpp:580-590) and re-arm for the next level (:392-393)
+__device__ __forceinline__ void level_end(PairState& st, int lvl, const StartRec& s) {
+  if (st.status == 0 && lvl != 0) {
+    if (!level_handoff(st.pose, s.scale_t)) st.status = 1;  // SOPHUS_ENSURE would abort
+  }
+  st.level_done = 0;
+  st.last_error = s.initial_error;
+}
+
+// The (at most two) pairs of a small call in the kernel arguments: no pair list in memory, nothing uploaded.
+struct InlinePairs {
+  int on;         // 0: the pair lists in memory
+  int slots[4];   // ref 0, tgt 0, ref 1, tgt 1
+};
+
+// the slots of pair `pair`, the lp-th of its launch; `ip` is the kernel argument itself
+// (selects, not an indexed read: indexing the by-value argument would send it through scratch memory)
+__device__ __forceinline__ void pair_slots(const InlinePairs& ip, int lp, int pair, const int* __restrict__ ref_slots,
+                                           const int* __restrict__ tgt_slots, int& ref_slot, int& tgt_slot) {
+  ref_slot = ip.on ? (lp == 0 ? ip.slots[0] : ip.slots[2]) : ref_slots[pair];
+  tgt_slot = ip.on ? (lp == 0 ? ip.slots[1] : ip.slots[3]) : tgt_slots[pair];
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // k_iterate: one launch = one Gauss-Newton iteration of one pyramid level for a whole batch, on the dense
 // nearest-neighbour / identity-weights path.  Every block first brings its pair's state up to date — the update that
@@ -2633,29 +2674,22 @@ struct IterArgs {
   int mode;                   // 0: first evaluation of the alignment (fresh state); 1: update, evaluate; 2: update, hand-off, evaluate;
                               // 3: evaluate from state_in as it is (the launch behind k_coarse)
   int prev_lvl;               // level the pending update / hand-off belongs to (mode 2)
-  int scale_t;                // level_handoff's: 0 / 1 the reference's hand-off, kHandoffKeep
-  const float* seeds;         // mode 0: the pairs' start poses (first_state), null = the identity
-  float initial_error;
+  StartRec start;             // seeds: mode 0 (first_state)
   int* cut_short;             // optional (speculative launching, early-exit schedules): set when a level's launches ran out
                               // before the pair's exit test fired, i.e. the host stopped launching too early (may be host memory)
-  int inline_pairs;           // 1: the (at most two) pairs' slots travel in the kernel arguments, no pair list in memory
-  int pair_slots[4];          // ref 0, tgt 0, ref 1, tgt 1
+  InlinePairs pairs;
 };
 
 __device__ __forceinline__ PairState iterate_state(const IterArgs& ia, int pair, unsigned char* lds, bool count_active) {
   PairState st;
-  if (ia.mode == 0) return first_state(ia.seeds, pair, ia.initial_error);
+  if (ia.mode == 0) return first_state(ia.start, pair);
   if (ia.mode == 3) return ia.state_in[pair];   // behind k_coarse: the state is current, nothing is pending
   st = update_compute(ia.u, ia.u.partials + (size_t)pair * ia.u.slices * kRecWords, &ia.state_in[pair], lds, count_active);
-  if (ia.mode == 2) {   // end of a pyramid level: hand-off (src/Tracker.cpp:580-590) and re-arm for the next level (:392-393)
+  if (ia.mode == 2) {   // end of a pyramid level
     // with early exit a level ends only through its exit test (which fires at the last iteration at the latest)
-    if (ia.cut_short && ia.u.early_exit && !st.level_done && st.status == 0 && count_active && threadIdx.x == 0)
+    if (ia.cut_short && ia.u.rule.early_exit && !st.level_done && st.status == 0 && count_active && threadIdx.x == 0)
       __hip_atomic_store(ia.cut_short, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (st.status == 0 && ia.prev_lvl != 0) {
-      if (!level_handoff(st.pose, ia.scale_t)) st.status = 1;  // SOPHUS_ENSURE would abort
-    }
-    st.level_done = 0;
-    st.last_error = ia.initial_error;
+    level_end(st, ia.prev_lvl, ia.start);
   }
   return st;
 }
@@ -2675,10 +2709,8 @@ __global__ __launch_bounds__(kBlock) void k_iterate(const ResidualArgs a, const 
   const int pair = (int)blockIdx.y + a.pair_base, slice = (int)blockIdx.x;
   // the first group's reference planes do not depend on the pose: their (cold) loads travel while the update runs
   RefGroup<VEC> first;
-  const int lp = (int)blockIdx.y;
-  // (selects, not an indexed read: indexing the by-value argument would send it through scratch memory)
-  const int ref_slot = ia.inline_pairs ? (lp == 0 ? ia.pair_slots[0] : ia.pair_slots[2]) : a.ref_slots[pair];
-  const int tgt_slot = ia.inline_pairs ? (lp == 0 ? ia.pair_slots[1] : ia.pair_slots[3]) : a.tgt_slots[pair];
+  int ref_slot, tgt_slot;
+  pair_slots(ia.pairs, (int)blockIdx.y, pair, a.ref_slots, a.tgt_slots, ref_slot, tgt_slot);
   load_first_group<VEC, DEPTH, COMPUTE_ONLY>(first, a, ref_slot, slice);
   PairState st = iterate_state(ia, pair, lds, slice == 0);
   if (slice == 0 && threadIdx.x == 0) ia.state_out[pair] = st;
@@ -2703,9 +2735,8 @@ __global__ __launch_bounds__(kBlock) void k_hist_iterate(const ResidualArgs a, c
                                                          PairScale* __restrict__ scale_out, int weights) {
   __shared__ __attribute__((aligned(16))) unsigned char ulds[kUpdateLdsBytes];
   const int pair = (int)blockIdx.y + a.pair_base, slice = (int)blockIdx.x;
-  const int lp = (int)blockIdx.y;
-  const int ref_slot = ia.inline_pairs ? (lp == 0 ? ia.pair_slots[0] : ia.pair_slots[2]) : a.ref_slots[pair];
-  const int tgt_slot = ia.inline_pairs ? (lp == 0 ? ia.pair_slots[1] : ia.pair_slots[3]) : a.tgt_slots[pair];
+  int ref_slot, tgt_slot;
+  pair_slots(ia.pairs, (int)blockIdx.y, pair, a.ref_slots, a.tgt_slots, ref_slot, tgt_slot);
   const PairState st = iterate_state(ia, pair, ulds, slice == 0);
   if (slice == 0 && threadIdx.x == 0) ia.state_out[pair] = st;
   if (st.level_done || st.status) return;   // (every block of the pair alike: nobody draws a ticket)
@@ -2727,13 +2758,10 @@ struct CoarseArgs {
   ResidualArgs lv[kCoarseMaxLevels];   // coarsest first; partials / slices / groups_per_block are set by the kernel
   int level_id[kCoarseMaxLevels];      // pyramid level of lv[i] (the hand-off is skipped behind level 0)
   int n_levels;
-  UpdateArgs u;                        // max_iters, early_exit, epsilon, gain
+  UpdateArgs u;                        // the rule and pair_base
   PairState* state_out;
-  int scale_t;                         // see IterArgs
-  const float* seeds;                  // !resume: the pairs' start poses (first_state), null = the identity
-  float initial_error;
-  int inline_pairs;                    // see IterArgs
-  int pair_slots[4];
+  StartRec start;                      // seeds: !resume (first_state)
+  InlinePairs pairs;
   int resume;                          // 1: continue from state_out[pair] instead of starting the alignment
 };
 
@@ -2770,13 +2798,13 @@ __device__ __forceinline__ void coarse_body(const CoarseArgs& ca) {
   uint32_t* rec = reinterpret_cast<uint32_t*>(lds + kLds);                     // the evaluation's record
   PairState* cur = reinterpret_cast<PairState*>(lds + kLds + kRecWords * 4);   // the state update_compute reads
   const int lp = (int)blockIdx.x, pair = lp + ca.u.pair_base;
-  const int ref_slot = ca.inline_pairs ? (lp == 0 ? ca.pair_slots[0] : ca.pair_slots[2]) : ca.lv[0].ref_slots[pair];
-  const int tgt_slot = ca.inline_pairs ? (lp == 0 ? ca.pair_slots[1] : ca.pair_slots[3]) : ca.lv[0].tgt_slots[pair];
+  int ref_slot, tgt_slot;
+  pair_slots(ca.pairs, lp, pair, ca.lv[0].ref_slots, ca.lv[0].tgt_slots, ref_slot, tgt_slot);
   PairState st;
   if (ca.resume) {
     st = ca.state_out[pair];   // a level of a batch behind the coarser one's launch: re-armed by that launch's tail
   } else {
-    st = first_state(ca.seeds, pair, ca.initial_error);
+    st = first_state(ca.start, pair);
   }
 #pragma unroll
   for (int li = 0; li < NLEV; li++) {
@@ -2790,7 +2818,7 @@ __device__ __forceinline__ void coarse_body(const CoarseArgs& ca) {
     u.slices = 1;
     u.active = nullptr;
     if (st.status == 0) {
-      for (int k = 0; k < u.max_iters; k++) {
+      for (int k = 0; k < u.rule.max_iters; k++) {
         __syncthreads();   // every thread has taken the state out of the update's LDS bytes: they become the reduction's
         if (threadIdx.x == 0) *cur = st;
         if constexpr (VECSEL == 4) {
@@ -2807,12 +2835,7 @@ __device__ __forceinline__ void coarse_body(const CoarseArgs& ca) {
         if (st.level_done || st.status) break;          // block-uniform (the exit test, src/Tracker.cpp:508)
       }
     }
-    // end of a pyramid level: hand-off (src/Tracker.cpp:580-590) and re-arm for the next level (:392-393)
-    if (st.status == 0 && ca.level_id[li] != 0) {
-      if (!level_handoff(st.pose, ca.scale_t)) st.status = 1;  // SOPHUS_ENSURE would abort
-    }
-    st.level_done = 0;
-    st.last_error = ca.initial_error;
+    level_end(st, ca.level_id[li], ca.start);
   }
   if (threadIdx.x == 0) ca.state_out[pair] = st;
 }
@@ -2835,13 +2858,13 @@ __global__ __launch_bounds__(kBlock) void k_coarse_weighted(const CoarseArgs ca)
   __shared__ PairState cur;                                                         // the state update_compute reads
   __shared__ PairScale s_scale;
   const int lp = (int)blockIdx.x, pair = lp + ca.u.pair_base;
-  const int ref_slot = ca.inline_pairs ? (lp == 0 ? ca.pair_slots[0] : ca.pair_slots[2]) : ca.lv[0].ref_slots[pair];
-  const int tgt_slot = ca.inline_pairs ? (lp == 0 ? ca.pair_slots[1] : ca.pair_slots[3]) : ca.lv[0].tgt_slots[pair];
+  int ref_slot, tgt_slot;
+  pair_slots(ca.pairs, lp, pair, ca.lv[0].ref_slots, ca.lv[0].tgt_slots, ref_slot, tgt_slot);
   PairState st;
   if (ca.resume) {
     st = ca.state_out[pair];
   } else {
-    st = first_state(ca.seeds, pair, ca.initial_error);
+    st = first_state(ca.start, pair);
   }
 #pragma unroll
   for (int li = 0; li < NLEV; li++) {
@@ -2856,10 +2879,10 @@ __global__ __launch_bounds__(kBlock) void k_coarse_weighted(const CoarseArgs ca)
     UpdateArgs u = ca.u;
     u.slices = 1;
     u.active = nullptr;
-    u.general = 1;
+    u.rule.general = 1;
     const size_t ref_off = (size_t)ref_slot * L.n, tgt_off = (size_t)tgt_slot * L.n;
     if (st.status == 0) {
-      for (int k = 0; k < u.max_iters; k++) {
+      for (int k = 0; k < u.rule.max_iters; k++) {
         // the scale pass (MedianMat / MedianAbsoluteDeviation, src/Tracker.cpp:1571-1619) at this evaluation's pose
         for (int i = threadIdx.x; i < kHistRep * kHistBins; i += kBlock) h[i] = 0;
         __syncthreads();   // (also: every thread has taken the last state out of the update's bytes)
@@ -2897,25 +2920,15 @@ __global__ __launch_bounds__(kBlock) void k_coarse_weighted(const CoarseArgs ca)
         if (st.level_done || st.status) break;            // block-uniform (the exit test, src/Tracker.cpp:508)
       }
     }
-    // end of a pyramid level: hand-off (src/Tracker.cpp:580-590) and re-arm for the next level (:392-393)
-    if (st.status == 0 && ca.level_id[li] != 0) {
-      if (!level_handoff(st.pose, ca.scale_t)) st.status = 1;  // SOPHUS_ENSURE would abort
-    }
-    st.level_done = 0;
-    st.last_error = ca.initial_error;
+    level_end(st, ca.level_id[li], ca.start);
   }
   if (threadIdx.x == 0) ca.state_out[pair] = st;
 }
 
 struct StatsOut { int status, iterations, n_valid; float error; };
 
-// After the last evaluation: its update, the last level's hand-off, and the results (one block per pair).
-static __global__ __launch_bounds__(kUpdateBlock) void k_finish(const IterArgs ia, float* __restrict__ poses, StatsOut* __restrict__ stats) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kUpdateLdsBytes];
-  const int pair = (int)blockIdx.x + ia.u.pair_base;
-  const PairState st = iterate_state(ia, pair, lds, true);
-  if (threadIdx.x) return;
-  ia.state_out[pair] = st;
+// a pair's results: its row of `poses` (7 floats) and, where asked for, of `stats`
+__device__ __forceinline__ void write_result(const PairState& st, int pair, float* __restrict__ poses, StatsOut* __restrict__ stats) {
   for (int k = 0; k < 4; k++) poses[7 * pair + k] = st.pose.q[k];
   for (int k = 0; k < 3; k++) poses[7 * pair + 4 + k] = st.pose.t[k];
   if (stats) {
@@ -2925,40 +2938,36 @@ static __global__ __launch_bounds__(kUpdateBlock) void k_finish(const IterArgs i
   }
 }
 
+// After the last evaluation: its update, the last level's hand-off, and the results (one block per pair).
+static __global__ __launch_bounds__(kUpdateBlock) void k_finish(const IterArgs ia, float* __restrict__ poses, StatsOut* __restrict__ stats) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kUpdateLdsBytes];
+  const int pair = (int)blockIdx.x + ia.u.pair_base;
+  const PairState st = iterate_state(ia, pair, lds, true);
+  if (threadIdx.x) return;
+  ia.state_out[pair] = st;
+  write_result(st, pair, poses, stats);
+}
+
 static __global__ void k_set_pose(PairState* state, Pose pose, float initial_error) {
   if (threadIdx.x || blockIdx.x) return;
-  PairState st;
-  st.pose = pose;
-  st.last_error = initial_error;
-  st.error = 0.f;
-  st.level_done = 0;
-  st.status = 0;
-  st.iters = 0;
-  st.n_valid = 0;
-  state[0] = st;
+  state[0] = fresh_state(pose, initial_error);
 }
 
-// `state`, `seeds` (null: the identity) and `gate` point at the first pair of the launch.  gate (the chained tracking call, else
+// `state`, `start.seeds` (null: the identity) and `gate` point at the first pair of the launch.  gate (the chained tracking call, else
 // null): a pair whose count is 0 — no key point reached the live call: every pair the front end failed — starts at the identity
 // whatever its seed row holds, so that its record is the unseeded call's.
-static __global__ void k_init_state(PairState* state, int n, float initial_error, const float* __restrict__ seeds,
-                                    const int* __restrict__ gate) {
+static __global__ void k_init_state(PairState* state, int n, const StartRec start, const int* __restrict__ gate) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const bool seeded = seeds && !(gate && gate[i] == 0);
-  state[i] = first_state(seeded ? seeds : nullptr, i, initial_error);
+  state[i] = first_state(start, i, !(gate && gate[i] == 0));
 }
 
-// end of a pyramid level: hand-off (src/Tracker.cpp:580-590) and re-arm for the next level (:392-393)
-static __global__ void k_level_end(PairState* state, int n, int lvl, int scale_t, float initial_error) {
+// level_end as a launch of its own (the batch and the table loops)
+static __global__ void k_level_end(PairState* state, int n, int lvl, const StartRec start) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;  // `state` points at the first pair of the launch
   if (i >= n) return;
   PairState st = state[i];
-  if (st.status == 0 && lvl != 0) {
-    if (!level_handoff(st.pose, scale_t)) st.status = 1;  // SOPHUS_ENSURE would abort
-  }
-  st.level_done = 0;
-  st.last_error = initial_error;
+  level_end(st, lvl, start);
   state[i] = st;
 }
 
@@ -2966,13 +2975,7 @@ static __global__ void k_write_out(const PairState* state, int n, float* poses, 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const PairState st = state[i];
-  for (int k = 0; k < 4; k++) poses[7 * i + k] = st.pose.q[k];
-  for (int k = 0; k < 3; k++) poses[7 * i + 4 + k] = st.pose.t[k];
-  if (stats) {
-    StatsOut o;
-    o.status = st.status; o.iterations = st.iters; o.n_valid = st.n_valid; o.error = st.error;
-    stats[i] = o;
-  }
+  write_result(st, i, poses, stats);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -3241,7 +3244,7 @@ __global__ __launch_bounds__(kBlock) void k_table_hist(const ResidualArgs a, con
 
 // k_table_general — the weighted / bilinear pass: four rows per thread, the 27 f64 sums and the error numerator under an EXEC
 // mask of the valid lanes (masked_sums_*), integer sum of rint(rf)^2, the record of the `general` kind through
-// block_reduce_store(.., err, coherent), the update in the launch's tail (tail_fold_wave; the host arms tail.general = 1).
+// block_reduce_store(.., err, coherent), the update in the launch's tail (tail_fold_wave; the host arms tail.rule.general = 1).
 template <int AR, bool UNIT_FACTORS>
 __global__ __launch_bounds__(kBlock) void k_table_general(const ResidualArgs a, const TableArgs ta, const GeneralArgs ga) {
   const int pair = (int)blockIdx.y + a.pair_base;
