@@ -451,6 +451,9 @@ class Tracker {
     uwt_params f = saved;
     f.first_level = 0; f.last_level = 0; f.max_iters = 10; f.gain = 1.0f; f.z_factor = 0.002f; f.angle_factor = 1.0f;
     f.handoff_scale_t = 1; f.early_exit = 1;
+    int32_t jac = UWT_JACOBIAN_REFERENCE;   // (0.002 compensates the pixel coordinate in the reference's column 2: 1 under the metric Jacobian)
+    check(uwt_get_jacobian(ctx(), &jac), "uwt_get_jacobian");
+    if (jac == UWT_JACOBIAN_METRIC) f.z_factor = 1.0f;
     check(uwt_update_params(ctx(), &f), "uwt_update_params");
     const float* tables[UWT_MAX_LEVELS] = {};
     int32_t counts[UWT_MAX_LEVELS] = {};
@@ -635,6 +638,9 @@ class Tracker {
     p.weights = weights;
     check(uwt_update_params(ctx(), &p), "uwt_update_params");
   }
+  // uwt_set_jacobian: UWT_JACOBIAN_REFERENCE (the default) or UWT_JACOBIAN_METRIC — every Estimate* call from here on; metric is
+  // meant to run with the seeded calls' handoff 1 (keep)
+  void SetJacobian(int mode) { check(uwt_set_jacobian(ctx(), mode), "uwt_set_jacobian"); }
   const uwt_stats& last_stats() const { return last_stats_; }
   uwt_level level(int lvl) {  // w_/h_/fx_/fy_/cx_/cy_/invfx_/invfy_[lvl], include/Tracker.h:516-526
     uwt_level L;

@@ -1351,6 +1351,39 @@ int uwt_predict_seeds_device_async(uwt_ctx* ctx, int32_t n, const float* d_prev,
 /* The same kernel on host arrays (n x 7 floats each), staged through the context's scratch; synchronous; the same bits. */
 int uwt_predict_seeds(uwt_ctx* ctx, int32_t n, const float* prev, const float* cur, float* seed_out);
 
+/* ---- the metric Jacobian (EXTENSION; no reference counterpart) ------------------------------------------------------------------ */
+
+/* The reference forms Jw (src/Tracker.cpp:455-467) with the warped PIXEL coordinates x2, y2 where the warped 3-D point's X, Y belong,
+ * so columns 2..5 of every Jacobian row are off by factors of 10^2 to 10^5 and the tracker estimates little but an image-plane shift.
+ * UWT_JACOBIAN_REFERENCE (the default of a new context) reproduces that bit for bit.  UWT_JACOBIAN_METRIC puts X = xn * z2, Y = yn * z2
+ * in, written in normalised coordinates; signs and column order are the reference's.
+ *
+ * The contract.  Inputs: the values the reference-mode Jw reads — x2, y2, iz behind the validity test and iz <- max(1 / z2, 0); the
+ * level's fx, fy, cx, cy, invfx, invfy (uwt_level); the factors zf = z_factor, af = angle_factor.  Everything f32, every operation
+ * rounded once, in the written order, no contraction; the same in both arithmetic sets:
+ *   xn = (x2 - cx) * invfx                                 yn = (y2 - cy) * invfy
+ *   row 0:  a0 = fx * iz      0      a2 = -(((fx * xn) * iz) * zf)   a3 = -(((fx * xn) * yn) * af)
+ *           a4 = (fx * (1 + xn * xn)) * af                            a5 = -((fx * yn) * af)
+ *   row 1:  0      b1 = fy * iz      b2 = -(((fy * yn) * iz) * zf)   b3 = -((fy * (1 + yn * yn)) * af)
+ *           b4 = ((fy * xn) * yn) * af                                b5 = (fy * xn) * af
+ * Everything else keeps the bits it has under the context's arith, accumulate_f64, weights and sampler: Jacobian_row = Jl * Jw in the
+ * arithmetic set's own form, validity and the residual, the robust scale and weights, the 28 sums and their fold, the exit test, the
+ * solve, exp and the composition.  Which kernel forms serve the mode (uwt_tuning, the level's shape) never shows in a result.
+ *
+ * The mode is state of the context (uwt_params and UWT_ABI_VERSION are unchanged).  uwt_set_jacobian, like uwt_set_tuning, waits for
+ * the context's work in flight and applies to every later call that forms a Jacobian: the dense calls in every launch form and all
+ * their seeded forms, uwt_estimate_pose_points, the batched table calls (features and candidates; plain, _opt, _seeded), both tracking
+ * chains, and the per-stage uwt_residual_jacobian / uwt_residual_jacobian_weighted.  Any other value: UWT_ERR_INVALID_ARG and nothing
+ * changes.  uwt_update_params neither reads nor resets the mode.
+ * One exception to "the call's own constants": the live call's z_factor = 0.002 (src/Tracker.cpp:640) is the reference's compensation
+ * for the pixel coordinate in column 2; in metric mode the live call, and the chains through it, run with z_factor = 1.  Its other
+ * constants stay.
+ * Metric mode is meant to run with handoff = 1 (keep) of the seeded entries (a null seed starts at the identity): with rotations that
+ * are real, the reference's q.xyz *= 2 hand-off overshoots and diverges on some pairs. */
+enum uwt_jacobian { UWT_JACOBIAN_REFERENCE = 0, UWT_JACOBIAN_METRIC = 1 };
+int uwt_set_jacobian(uwt_ctx* ctx, int32_t mode);
+int uwt_get_jacobian(const uwt_ctx* ctx, int32_t* out);
+
 /* ---- test instrumentation: guards inside the context's own scratch ------------------------------------------------------------ */
 
 /* Not part of the tracker: these two serve tests/test_gpu_guard_bands.py, which uses them to see whether a kernel writes outside an

@@ -61,7 +61,7 @@ def main():
     if a.output:
         with open(a.output, "w") as f:
             f.write("# Kernel resource usage (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)\n\n"
-                    "Template arguments of `k_residual`: `<ARITH (0 OpenCV, 1 legacy), VEC, DEPTH, UNIT_FACTORS, DUMP, AccT, SQUARE, "
+                    "Template arguments of `k_residual`: `<ARITH (0 OpenCV, 1 legacy; + 2: the metric Jacobian mode), VEC, DEPTH, UNIT_FACTORS, DUMP, AccT, SQUARE, "
                     "SAMPLER, WEIGHTS, COMPUTE_ONLY, LOADS (bit 0: non-temporal plane loads, bit 1: typed plane loads)>`; of `k_iterate`: "
                     "`<ARITH, VEC, DEPTH, PLAIN, COMPUTE_ONLY, PASS>`; of `k_coarse` / `k_coarse_w4`: `<ARITH, DEPTH, PLAIN, ...>`.\n\n" + txt)
     else:

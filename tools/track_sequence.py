@@ -25,13 +25,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def track_live(w, h, intr, frames, depths, arith=0, detector=0):
+def track_live(w, h, intr, frames, depths, arith=0, detector=0, jacobian="reference"):
     """System::Tracking over consecutive frames through the Python mirror: (poses [n - 1, 7], stats, matches kept per pair).
-    detector: 0 SURF, 1 ORB (RobustMatcher(int detector), src/Tracker.cpp:38-46)"""
+    detector: 0 SURF, 1 ORB (RobustMatcher(int detector), src/Tracker.cpp:38-46); jacobian: Tracker.SetJacobian"""
     M = importlib.import_module("uw-slam_amd.tracker")
     fx, fy, cx, cy = intr
     tracker = M.Tracker(bool(depths), max_frames=4, arith=arith)
     tracker.InitializePyramid(w, h, np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32))
+    tracker.SetJacobian(jacobian)
     rm = M.RobustMatcher(tracker, detector=detector)
     mk = lambda i: M.Frame(frames[i], depths[i] if depths else None, i)
     poses, stats, kept = [], [], []
@@ -95,7 +96,8 @@ def sequence_cloud(w, h, intr, frames, depths, poses, stride=100, mode=0, arith=
     return np.concatenate(parts) if parts else np.zeros(0, capi.CLOUD_POINT)
 
 
-def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0, quality=False, cloud=None, motion_model="identity"):
+def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0, quality=False, cloud=None, motion_model="identity",
+                       jacobian="reference"):
     """The same loop as successive one-pair uwt_tracking_batch_async calls (detector 1: uwt_tracking_orb_batch_async): what a frame kept
     goes to the next call in device memory (two sets of buffers, taken in turn), nothing is read back between the calls and the host
     waits once, at the end.  Same returns; quality: behind every call uwt_warp_image_batch_async on its device pose, inside the same
@@ -103,11 +105,13 @@ def track_live_chained(w, h, intr, frames, depths, arith=0, cap=2048, detector=0
     accumulated from the device poses, one pose per call (uwt_accumulate_trajectory_device_from_async), and, frame by frame while it is resident, the cloud
     enqueued (uwt_point_cloud_batch_async), still inside the single wait — the records come back as the last result.
     motion_model "constant": pair k's live alignment starts from pair k - 1's pose, taken from device memory inside the single wait
-    (uwt_tracking_batch_seeded_async / uwt_tracking_orb_batch_seeded_async)."""
+    (uwt_tracking_batch_seeded_async / uwt_tracking_orb_batch_seeded_async).
+    jacobian "metric": uwt_set_jacobian — the live alignment then runs with z_factor 1 (include/uwt.h "the metric Jacobian")."""
     import torch
     capi = importlib.import_module("uw-slam_amd.capi")
     n = len(frames)
     ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=4, max_pairs=1, has_depth=int(bool(depths)), arith=arith))
+    ctx.set_jacobian(jacobian)
     ctx.set_deferred(True)   # pyramids and gradients are enqueued only
     enqueue = ctx.tracking_orb_batch_async if detector == 1 else ctx.tracking_batch_async
     enqueue_seeded = ctx.tracking_orb_batch_seeded_async if detector == 1 else ctx.tracking_batch_seeded_async
@@ -177,18 +181,20 @@ def keyframe_of(i, interval):
     return interval * ((i - 1) // interval)
 
 
-def track_keyframes(w, h, intr, frames, depths, over, interval=1, motion_model="identity", handoff="reference"):
+def track_keyframes(w, h, intr, frames, depths, over, interval=1, motion_model="identity", handoff="reference", jacobian="reference"):
     """Dense tracking of frame i against its keyframe (keyframe_of) through uwt_track_batch_seeded_async, one pair per call, seeds,
     poses and the trajectory in device memory and one wait at the end (plus the early-exit looks of the calls themselves).
     motion_model "constant": the pair's seed is the constant-velocity prediction in keyframe coordinates
     (uwt_predict_seeds_device_async from the two poses before; the first frame behind a new keyframe starts at the identity, the second
     from prev = identity); with interval 1 — frame-to-frame tracking — the prediction IS the previous pair's pose buffer.
     The world pose of frame i is its keyframe's trajectory row times its pose (uwt_accumulate_trajectory_device_from_async).
+    jacobian "metric": uwt_set_jacobian on the context (meant to go with handoff "keep").
     Returns (poses [n - 1, 7] keyframe -> frame, stats, trajectory [n - 1, 7], keyframe index per pair)."""
     import torch
     capi = importlib.import_module("uw-slam_amd.capi")
     n = len(frames)
     ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=3, max_pairs=1, has_depth=int(bool(depths)), **over))
+    ctx.set_jacobian(jacobian)
     f32 = dict(dtype=torch.float32, device="cuda")
     poses, seeds, traj = torch.zeros((n - 1, 7), **f32), torch.zeros((n - 1, 7), **f32), torch.zeros((n - 1, 7), **f32)
     stats = torch.zeros((n - 1, 4), dtype=torch.int32, device="cuda")
@@ -270,8 +276,14 @@ def add_seed_arguments(ap):
     ap.add_argument("--keyframe-interval", type=int, default=0, metavar="N", help="dense tracking against keyframes: frame i against frame "
                     "N * floor((i - 1) / N), its world pose from the keyframe's trajectory row; a new keyframe starts at the identity "
                     "(0: consecutive frames through the batch path)")
-    ap.add_argument("--handoff", choices=["reference", "keep"], default="reference", help="how a seeded pose crosses the pyramid levels "
-                    "(uwt_seed_options): the reference's hand-off doubles q.xyz at every level, keep leaves the pose as it is")
+    ap.add_argument("--handoff", choices=["reference", "keep"], default=None, help="how a seeded pose crosses the pyramid levels "
+                    "(uwt_seed_options): the reference's hand-off doubles q.xyz at every level, keep leaves the pose as it is "
+                    "(default: reference; keep with --jacobian metric)")
+    ap.add_argument("--jacobian", choices=["reference", "metric"], default="reference", help="uwt_set_jacobian: reference, the reference's "
+                    "Jw with the warped pixel coordinates in columns 2..5, bit for bit; metric, the 3-D point's coordinates there "
+                    "(the correct Jacobian, an extension).  Dense tracking in metric mode goes through the seeded entry (frame to "
+                    "frame from the identity unless --keyframe-interval / --motion-model say otherwise) under --handoff keep unless "
+                    "another is named; with --live the alignment runs with z_factor 1")
     return ap
 
 
@@ -314,7 +326,10 @@ def main():
         ap.error("--cloud-stride must be at least 1")
     if a.keyframe_interval < 0:
         ap.error("--keyframe-interval must be at least 1 (0: off)")
-    seeded = a.keyframe_interval > 0 or (a.motion_model == "constant" and not a.live)
+    if a.handoff is None:
+        a.handoff = "keep" if a.jacobian == "metric" else "reference"
+    # (the unseeded dense entry has the reference's hand-off alone: metric mode takes the seeded one, with null seeds where no model is on)
+    seeded = a.keyframe_interval > 0 or ((a.motion_model == "constant" or a.jacobian == "metric") and not a.live)
     if seeded and (a.live or a.quality or a.cloud):
         ap.error("--keyframe-interval (and --motion-model constant without --live) is the dense tracker alone: no --live, --quality or --cloud")
     if a.motion_model == "constant" and a.live and not a.chained:
@@ -323,20 +338,21 @@ def main():
     cloud_args = (a.cloud_stride, CLOUD_MODES[a.cloud_mode]) if a.cloud else None
     if seeded:
         poses, stats, device_traj, keyframes = track_keyframes(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over,
-                                                               max(1, a.keyframe_interval), a.motion_model, a.handoff)
+                                                               max(1, a.keyframe_interval), a.motion_model, a.handoff, a.jacobian)
     elif a.live and a.chained and (a.quality or a.cloud):
         res = track_live_chained(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
-                                 detector=int(a.detector == "orb"), quality=a.quality, cloud=cloud_args, motion_model=a.motion_model)
+                                 detector=int(a.detector == "orb"), quality=a.quality, cloud=cloud_args, motion_model=a.motion_model,
+                                 jacobian=a.jacobian)
         poses, stats, n_matches = res[:3]
         records = res[3] if a.quality else None
         cloud = res[-1] if a.cloud else None
     elif a.live:
         if a.chained:
             poses, stats, n_matches = track_live_chained(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
-                                                         detector=int(a.detector == "orb"), motion_model=a.motion_model)
+                                                         detector=int(a.detector == "orb"), motion_model=a.motion_model, jacobian=a.jacobian)
         else:
             poses, stats, n_matches = track_live(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
-                                                 detector=int(a.detector == "orb"))
+                                                 detector=int(a.detector == "orb"), jacobian=a.jacobian)
     else:
         poses, stats = trk.track(frames, depths)
     if a.quality and records is None:

@@ -4,6 +4,13 @@
 //   make -C tools            (g++ against include/uwt.h and uw-slam_amd/libuwt_hip.so; see tools/Makefile)
 //   tools/uwt_bench [--pairs 1024] [--unique 32] [--steps 10] [--warmup 3] [--width 640] [--height 480] [--levels 4]
 //                   [--iters 10] [--no-depth] [--reference-schedule] [--legacy-arith] [--gpus N] [--rccl]
+//                   [--jacobian reference|metric] [--handoff reference|keep] [--untyped] [--angle-factor F]
+//
+// --jacobian metric: uwt_set_jacobian(UWT_JACOBIAN_METRIC); the steps then go through uwt_track_batch_seeded_async with null seeds and
+// handoff keep, the hand-off the mode is meant for (--handoff names another, and gives reference mode the seeded entry too).
+// --untyped: uwt_tuning::typed_loads = 0 — reference mode on untyped plane loads, the loads every metric kernel has.
+// --angle-factor F: uwt_params::angle_factor (default 1); any other value sends reference mode through the general Jacobian form —
+// with --untyped the very instantiation of k_residual, but for the mode, that the metric mode runs.
 //
 // --gpus N: the batched multi-GPU mode from a native host — one thread and one context per device, --pairs per device,
 // global pair i on device i mod N, one ncclAllGather (RCCL over xGMI) of the solved poses per step enqueued on each
@@ -37,6 +44,11 @@ namespace {
 int arg_int(int argc, char** argv, const char* name, int def) {
   for (int i = 1; i + 1 < argc; i++)
     if (!std::strcmp(argv[i], name)) return std::atoi(argv[i + 1]);
+  return def;
+}
+const char* arg_str(int argc, char** argv, const char* name, const char* def) {
+  for (int i = 1; i + 1 < argc; i++)
+    if (!std::strcmp(argv[i], name)) return argv[i + 1];
   return def;
 }
 bool arg_flag(int argc, char** argv, const char* name) {
@@ -79,6 +91,9 @@ struct Barrier {   // std::barrier is C++20
 struct Shared {
   int P, U, steps, warmup, w, h, levels, iters, n_dev;
   bool depth, ref_sched, rccl, legacy;
+  bool metric = false, untyped = false;
+  float angle_factor = 1.0f;
+  int handoff = -1;   // -1: the unseeded entry; 0 / 1: the seeded entry with null seeds under that hand-off
   Barrier* bar;
   ncclComm_t* comms;
   double t_start = 0, t_end = 0;
@@ -104,11 +119,22 @@ int run_device(Shared& S, int dev) {
     p.n_levels = S.levels; p.first_level = S.levels - 1; p.last_level = 0; p.max_iters = S.iters; p.early_exit = 0;
   }
   p.has_depth = S.depth ? 1 : 0;
+  p.angle_factor = S.angle_factor;
   p.arith = S.legacy ? UWT_ARITH_LEGACY : UWT_ARITH_OPENCV;   // (the default: OpenCV's generic code paths, include/uwt.h)
   p.max_frames = 2 * P;
   p.max_pairs = P;
   p.device = dev;
   CHK(uwt_create(&p, &ctx));
+  if (S.metric) CHK(uwt_set_jacobian(ctx, UWT_JACOBIAN_METRIC));
+  if (S.untyped) {
+    uwt_tuning tn;
+    CHK(uwt_get_tuning(ctx, &tn));
+    tn.typed_loads = 0;
+    CHK(uwt_set_tuning(ctx, &tn));
+  }
+  uwt_seed_options sopt;
+  uwt_default_seed_options(&sopt);
+  sopt.handoff = S.handoff > 0 ? 1 : 0;
 
   // U distinct pairs of this device's shard, tiled over its P resident pairs (slot 2i = reference, 2i+1 = target)
   const int U = S.U;
@@ -132,7 +158,8 @@ int run_device(Shared& S, int dev) {
   CHK(uwt_stream(ctx, &stream));
 
   auto step = [&]() -> int {
-    CHK(uwt_track_batch_async(ctx, 0, 2 * P, 1, P, ref_slots.data(), tgt_slots.data(), d_poses, nullptr));
+    if (S.handoff < 0) CHK(uwt_track_batch_async(ctx, 0, 2 * P, 1, P, ref_slots.data(), tgt_slots.data(), d_poses, nullptr));
+    else CHK(uwt_track_batch_seeded_async(ctx, 0, 2 * P, 1, P, ref_slots.data(), tgt_slots.data(), d_poses, nullptr, nullptr, &sopt));
     // the gather follows the alignment on the context's stream: no host synchronisation per step
     if (S.rccl && ncclAllGather(d_poses, d_all, (size_t)7 * P, ncclFloat, S.comms[dev], (hipStream_t)stream) != ncclSuccess) return 1;
     return 0;
@@ -179,6 +206,15 @@ int main(int argc, char** argv) {
   S.depth = !arg_flag(argc, argv, "--no-depth");
   S.ref_sched = arg_flag(argc, argv, "--reference-schedule");
   S.legacy = arg_flag(argc, argv, "--legacy-arith");
+  const std::string jac = arg_str(argc, argv, "--jacobian", "reference"), ho = arg_str(argc, argv, "--handoff", "");
+  if ((jac != "reference" && jac != "metric") || (ho != "" && ho != "reference" && ho != "keep")) {
+    std::fprintf(stderr, "uwt_bench: --jacobian reference|metric, --handoff reference|keep\n");
+    return 2;
+  }
+  S.metric = jac == "metric";
+  S.handoff = ho == "" ? (S.metric ? 1 : -1) : (ho == "keep" ? 1 : 0);
+  S.untyped = arg_flag(argc, argv, "--untyped");
+  S.angle_factor = (float)std::atof(arg_str(argc, argv, "--angle-factor", "1"));
   S.n_dev = arg_int(argc, argv, "--gpus", 1);
   S.rccl = S.n_dev > 1 || arg_flag(argc, argv, "--rccl");
   if (S.ref_sched) S.levels = 5;
@@ -242,12 +278,14 @@ int main(int argc, char** argv) {
   }
   std::printf("{\"metric\": \"frame-pair alignments/sec (%dx%d, %d pyr lvls)\", \"value\": %.2f, \"unit\": \"alignments/s\", "
               "\"n_gpus\": %d, \"steps\": %d, \"warmup\": %d, \"ms_per_step\": %.4f, \"scaling\": \"weak\", \"host\": \"C++ over the C ABI%s\", "
-              "\"config\": {\"workload\": \"%s, %d pairs resident per GPU (%d distinct)%s\", \"arithmetic\": \"%s\"}, "
+              "\"config\": {\"workload\": \"%s, %d pairs resident per GPU (%d distinct)%s\", \"arithmetic\": \"%s\", "
+              "\"jacobian\": \"%s\", \"handoff\": \"%s\", \"typed_loads\": %s, \"angle_factor\": %g}, "
               "\"poses_finite\": %s, \"tiled_pairs_identical\": %s, \"gathered_blocks_match\": %s, \"max_translation_m\": %.6f}\n",
               S.w, S.h, S.levels, (double)P * N * S.steps / sec, N, S.steps, S.warmup, sec * 1e3 / S.steps,
               S.rccl ? " + RCCL all-gather" : "",
               S.ref_sched ? "reference schedule (levels 4..1, <= 50 iterations, early exit)" : "fixed iterations, no early exit", P, U,
-              S.depth ? ", u16 depth plane" : "", S.legacy ? "legacy" : "opencv", finite ? "true" : "false", tiled_equal ? "true" : "false",
+              S.depth ? ", u16 depth plane" : "", S.legacy ? "legacy" : "opencv", S.metric ? "metric" : "reference",
+              S.handoff < 0 ? "reference (unseeded entry)" : (S.handoff ? "keep" : "reference"), S.untyped ? "false" : "true", (double)S.angle_factor, finite ? "true" : "false", tiled_equal ? "true" : "false",
               !S.rccl ? "null" : (gather_ok ? "true" : "false"), tmax);
   return (finite && tiled_equal && gather_ok) ? 0 : 1;
 }

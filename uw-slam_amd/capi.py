@@ -155,6 +155,8 @@ PAIR_STATE_DTYPE = np.dtype([("pose", "<f4", (7,)), ("last_error", "<f4"), ("err
 
 
 # every symbol include/uwt.h declares (tests check the library exports all of them)
+JACOBIAN_REFERENCE, JACOBIAN_METRIC = 0, 1   # enum uwt_jacobian
+
 SYMBOLS = [
     "uwt_abi_version", "uwt_source_id", "uwt_status_string", "uwt_last_error", "uwt_default_params", "uwt_create", "uwt_destroy",
     "uwt_level_info", "uwt_set_frame", "uwt_upload_frames", "uwt_upload_frames_async", "uwt_host_alloc", "uwt_host_free", "uwt_plane_device_ptr", "uwt_get_plane",
@@ -167,7 +169,7 @@ SYMBOLS = [
     "uwt_obtain_candidate_points", "uwt_obtain_candidate_points_batch", "uwt_obtain_patch_points", "uwt_add_patch_points",
     "uwt_ingest_create", "uwt_ingest_destroy", "uwt_ingest_maps", "uwt_ingest_undistort", "uwt_ingest_calculate_roi",
     "uwt_ingest_frame", "uwt_update_params", "uwt_get_params", "uwt_ls_accumulate_sse", "uwt_robust_weights",
-    "uwt_get_tuning", "uwt_set_tuning",
+    "uwt_get_tuning", "uwt_set_tuning", "uwt_get_jacobian", "uwt_set_jacobian",
     "uwt_knn_match_batch", "uwt_match_descriptors_batch", "uwt_match_descriptors_batch_async",
     "uwt_default_ransac_params", "uwt_ransac_iterations", "uwt_ransac_inliers_batch", "uwt_ransac_inliers_batch_async",
     "uwt_obtain_patch_points_batch", "uwt_track_features_batch_async", "uwt_estimate_pose_features_batch",
@@ -471,6 +473,18 @@ class Context:
                 raise AttributeError(k)
             setattr(t, k, int(v))
         self._chk(lib().uwt_set_tuning(self._h, C.byref(t)))
+
+    def get_jacobian(self):
+        """The context's Jacobian mode (uwt_get_jacobian): JACOBIAN_REFERENCE or JACOBIAN_METRIC."""
+        out = C.c_int32(0)
+        self._chk(lib().uwt_get_jacobian(self._h, C.byref(out)))
+        return out.value
+
+    def set_jacobian(self, mode):
+        """uwt_set_jacobian: 0 / "reference" the reference's Jw (pixel coordinates in columns 2..5; the default), 1 / "metric" the
+        3-D point's coordinates.  Applies to every later call that forms a Jacobian; metric is meant to run with handoff "keep"."""
+        mode = {"reference": JACOBIAN_REFERENCE, "metric": JACOBIAN_METRIC}.get(mode, mode)
+        self._chk(lib().uwt_set_jacobian(self._h, C.c_int32(int(mode))))
 
     def close(self):
         if self._h:

@@ -268,6 +268,11 @@ CoarseArgs coarse_args(const UpdateRule& rule, const StartRec& start, const Inli
   return ca;
 }
 
+// Robust weights over the nearest sampler: a coarse level runs in one k_coarse_weighted launch (uwt_tuning::coarse_weighted).  Not in
+// the metric Jacobian mode: that kernel keeps 20 bytes of scratch per lane in every form and a metric kernel may have none, so the
+// level stays on the per-evaluation launches — the same device functions, the same bits.
+bool coarse_weighted_on(const uwt_ctx* c) { return c->tn.coarse_weighted != 0 && c->jacobian != UWT_JACOBIAN_METRIC; }
+
 // level lvl as the i-th of the launch
 void coarse_level(uwt_ctx* c, CoarseArgs& ca, int i, int lvl) {
   ca.lv[i] = residual_args(c, lvl);
@@ -327,7 +332,7 @@ int enqueue_estimate_chained(uwt_ctx* c, bool robust, int n_pairs, float* d_pose
       after_coarse = true;
     }
   } else {   // robust weights over the nearest sampler: one k_coarse_weighted launch per level
-    while (c->tn.coarse_weighted && p.sampler == 0 && start_lvl > p.last_level && c->lv[start_lvl].ng <= kCoarseMaxPixels) {
+    while (coarse_weighted_on(c) && p.sampler == 0 && start_lvl > p.last_level && c->lv[start_lvl].ng <= kCoarseMaxPixels) {
       HIPCHK(c, wait_level(c, c->stream, level_ready, start_lvl));
       coarse_level(c, ca, 0, start_lvl);
       ca.n_levels = 1;
@@ -452,7 +457,7 @@ int enqueue_estimate(uwt_ctx* c, int n_pairs, float* d_poses, StatsOut* d_stats,
   // robust weights over the nearest sampler: k_coarse_weighted (histogram, scale, weighted sums and update of a whole level in
   // one block); the bilinear sampler stays on the launches.  Square pixels with unit factors or not: the kernels' PLAIN switch.
   bool coarse_lvl[UWT_MAX_LEVELS] = {};
-  if (p.accumulate_f64 != 0 && (!general || (p.sampler == 0 && p.weights != 0 && c->tn.coarse_weighted)) && c->tn.coarse_batch_px > 0 &&
+  if (p.accumulate_f64 != 0 && (!general || (p.sampler == 0 && p.weights != 0 && coarse_weighted_on(c))) && c->tn.coarse_batch_px > 0 &&
       !c->compute_only && !(c->profiling && p.early_exit))
     for (int lvl = p.first_level; lvl >= p.last_level; lvl--)
       coarse_lvl[lvl] = c->lv[lvl].ng <= c->tn.coarse_batch_px;
@@ -759,6 +764,7 @@ LaunchSel launch_sel(const uwt_ctx* c) {
   sel.depth = c->p.has_depth != 0;
   sel.acc64 = c->p.accumulate_f64 != 0;
   sel.compute_only = c->compute_only;
+  sel.metric = c->jacobian == UWT_JACOBIAN_METRIC;
   return sel;
 }
 
@@ -1305,6 +1311,25 @@ int uwt_set_tuning(uwt_ctx* c, const uwt_tuning* t) {
     *b = *b != 0;
   if (c->tn.overlap_gradients < 0 || c->tn.overlap_gradients > 3) c->tn.overlap_gradients = 1;   // (an on / off switch until the early preparation)
   std::memset(c->tn.reserved, 0, sizeof(c->tn.reserved));
+  return UWT_OK;
+}
+
+int uwt_get_jacobian(const uwt_ctx* c, int32_t* out) {
+  if (!c || !out) return UWT_ERR_INVALID_ARG;
+  *out = c->jacobian;
+  return UWT_OK;
+}
+
+int uwt_set_jacobian(uwt_ctx* c, int32_t mode) {
+  if (!c) return UWT_ERR_INVALID_ARG;
+  if (mode != UWT_JACOBIAN_REFERENCE && mode != UWT_JACOBIAN_METRIC)
+    return fail(c, UWT_ERR_INVALID_ARG, "uwt_set_jacobian: mode is neither UWT_JACOBIAN_REFERENCE nor UWT_JACOBIAN_METRIC");
+  (void)hipSetDevice(c->p.device);
+  close_window(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->side));   // (as uwt_set_tuning)
+  c->jacobian = mode;
+  c->spec_budget = c->spec_calm = 0;   // another solver: the speculative budget starts over
   return UWT_OK;
 }
 

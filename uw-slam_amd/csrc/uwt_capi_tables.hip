@@ -161,14 +161,15 @@ constexpr int kFeatKpFloats = 2 * kPatchMaxKeypoints;                 // one fra
 
 // the context's params with Tracker::EstimatePoseFeatures' locals (src/Tracker.cpp:633-640, 661, 834, 856): level 0 only, 10
 // iterations, epsilon 1e-3, last_error 50000, z_factor 0.002, no angle factor, gain 1 (Residuals.mul(1)), the early exit of :782,
-// the hand-off of :856; identity weights (:769), round() (:746)
+// the hand-off of :856; identity weights (:769), round() (:746).  Metric Jacobian mode: z_factor 1 — the 0.002 compensates the pixel
+// coordinate in the reference's column 2 (uwt.h "the metric Jacobian")
 uwt_params feature_params(const uwt_ctx* c) {
   uwt_params q = c->p;
   q.first_level = q.last_level = 0;
   q.max_iters = 10;
   q.epsilon = 0.001f;
   q.initial_error = 50000.0f;
-  q.z_factor = 0.002f;
+  q.z_factor = c->jacobian == UWT_JACOBIAN_METRIC ? 1.0f : 0.002f;
   q.angle_factor = 1.0f;
   q.gain = 1.0f;
   q.early_exit = 1;

@@ -96,6 +96,7 @@ struct uwt_ctx {
   // non-temporally; split_min_px: level-0 pixels of the batch at least — below, a launch is too short for a second stream to pay
   // (the host enqueues twice as many)
   uwt_tuning tn;
+  int32_t jacobian = UWT_JACOBIAN_REFERENCE;   // uwt_set_jacobian: every launch that forms Jw reads it through launch_sel
   hipEvent_t ev_pyramids = nullptr, ev_side_done = nullptr, ev_level[UWT_MAX_LEVELS] = {};
   // Early preparation (uwt_tuning::overlap_gradients 1 / 3): past its level 1 a dense batch call reads no plane of a
   // level >= 1, and the next call's preparation — pyramids, gradients of the levels >= 1 — writes nothing else.  A call that ends on

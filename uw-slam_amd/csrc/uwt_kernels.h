@@ -57,6 +57,13 @@ constexpr int kMaxSlices = 160;  // slices per pair and level at most (a 1280x96
 //   kArithLegacy  rounds 1-3: the small products as k-sequential f32 FMA chains, the unprojection as written, the inverse
 //                 formed and multiplied.  Cheaper, and not what OpenCV computes; kept selectable.
 constexpr int kArithOpenCV = 0, kArithLegacy = 1;
+// The Jacobian mode (uwt.h: uwt_jacobian) rides on the arithmetic argument of the kernels that form Jw — k_residual, k_residual_w4,
+// k_iterate, k_coarse, k_coarse_w4, k_coarse_weighted, k_table_eval, k_table_general: bit 1 of their first template argument (ARJ).
+// Reference mode is the bare arithmetic set, so a reference-mode instantiation is the kernel it was before the mode existed, name
+// and code.  Below those kernels every function takes the arithmetic set alone (AR) and the mode as a flag of its own (METRIC).
+constexpr int kJacMetric = 2;
+constexpr int arith_of(int arj) { return arj & 1; }
+constexpr bool metric_of(int arj) { return (arj & kJacMetric) != 0; }
 
 // One pyramid level.  Three sizes (equal whenever the level-0 size is divisible by 2^lvl and the row is whole groups of four):
 //   image   iw x ih   images_[lvl].cols / rows: the cv::resize(.., 0.5, 0.5) chain of src/System.cpp:246-251 (cvRound per level).
@@ -761,9 +768,28 @@ __device__ __forceinline__ void pixel_warp(const LevelK& L, const WarpK& K, F xf
 // and reduce to the f32 product (the exact product rounded once).  A zero row entry is +0 there (the sum starts from +0);
 // SIGNED_ZEROS reproduces that for the per-stage dumps, the sums cannot see it.
 // the non-zero entries of Jw (src/Tracker.cpp:455-467): row 0 = (a0, 0, a2, a3, a4, a5), row 1 = (0, b1, b2, b3, b4, b5)
-template <bool UNIT_FACTORS, bool SQUARE, typename F>
+// METRIC (uwt.h "the metric Jacobian"): the 3-D point's X = xn * z2, Y = yn * z2 where the reference has the pixel coordinates x2, y2,
+// written in normalised coordinates xn = (x2 - cx) * invfx, yn = (y2 - cy) * invfy — every operation as the header writes it, the
+// factors always multiplied in (the general form: no UNIT_FACTORS or SQUARE twin).
+template <bool UNIT_FACTORS, bool SQUARE, typename F, bool METRIC = false>
 __device__ __forceinline__ void jw_terms(const LevelK& L, float zf_, float af_, F x2, F y2, F iz, F& a0, F& b1, F a[4], F b[4]) {
   const F fx = bc<F>(L.fx), fy = bc<F>(L.fy), one = bc<F>(1.0f);
+  if constexpr (METRIC) {
+    static_assert(!UNIT_FACTORS && !SQUARE, "the metric Jacobian has the general form only");
+    const F zf = bc<F>(zf_), af = bc<F>(af_);
+    const F xn = (x2 - bc<F>(L.cx)) * bc<F>(L.invfx), yn = (y2 - bc<F>(L.cy)) * bc<F>(L.invfy);
+    a0 = fx * iz;
+    b1 = fy * iz;
+    a[0] = -(((fx * xn) * iz) * zf);
+    a[1] = -(((fx * xn) * yn) * af);
+    a[2] = (fx * (one + xn * xn)) * af;
+    a[3] = -((fx * yn) * af);
+    b[0] = -(((fy * yn) * iz) * zf);
+    b[1] = -((fy * (one + yn * yn)) * af);
+    b[2] = ((fy * xn) * yn) * af;
+    b[3] = (fy * xn) * af;
+    return;
+  }
   F a2, a3, a5, b2, b4, b5;
   if constexpr (SQUARE) {
     const F fx2 = fx * x2, fy2 = fx * y2;
@@ -797,11 +823,11 @@ __device__ __forceinline__ void jw_terms(const LevelK& L, float zf_, float af_, 
   b[0] = b2; b[1] = b3; b[2] = b4; b[3] = b5;
 }
 
-template <int AR, bool UNIT_FACTORS, bool SQUARE = false, bool SIGNED_ZEROS = false, typename F = float>
+template <int AR, bool UNIT_FACTORS, bool SQUARE = false, bool SIGNED_ZEROS = false, typename F = float, bool METRIC = false>
 __device__ __forceinline__ void pixel_jacobian(const LevelK& L, float zf_, float af_, F x2, F y2, F iz, F g0, F g1, F J[6]) {
   const F zero = bc<F>(0.0f);
   F a0, b1, av[4], bv[4];
-  jw_terms<UNIT_FACTORS, SQUARE, F>(L, zf_, af_, x2, y2, iz, a0, b1, av, bv);
+  jw_terms<UNIT_FACTORS, SQUARE, F, METRIC>(L, zf_, af_, x2, y2, iz, a0, b1, av, bv);
   const F a2 = av[0], a3 = av[1], a4 = av[2], a5 = av[3], b2 = bv[0], b3 = bv[1], b4 = bv[2], b5 = bv[3];
   if constexpr (AR == kArithOpenCV) {
     if constexpr (SIGNED_ZEROS) {   // (0 + p0) + p1 in double: a zero result is +0
@@ -1455,8 +1481,8 @@ __device__ __forceinline__ void fill_ray_tables(float* __restrict__ tab, const L
 // COMPUTE_ONLY (diagnostic, uwt_profile_enable(ctx, 2)): the same instruction stream with every load of the loop replaced
 // by register arithmetic — results are meaningless, its duration is the kernel's own instruction-issue floor.
 // residual_core evaluates one slice of one pair at `pose`; `lds` (optional) is the caller's buffer for the block reduction.
-template <int AR, int VEC, bool DEPTH, bool UNIT_FACTORS, bool DUMP, typename AccT, bool SQUARE = false, int SAMPLER = 0, int WEIGHTS = 0,
-          bool COMPUTE_ONLY = false, int EXT_LDS = 0, int STREAM = 0, bool RAGGED = false>   // EXT_LDS: 0 = own LDS, else rows per reduction pass in the caller's; STREAM: load_group; RAGGED: the level's grid rows are not whole groups of four (colm)
+template <int ARJ, int VEC, bool DEPTH, bool UNIT_FACTORS, bool DUMP, typename AccT, bool SQUARE = false, int SAMPLER = 0, int WEIGHTS = 0,
+          bool COMPUTE_ONLY = false, int EXT_LDS = 0, int STREAM = 0, bool RAGGED = false>   // ARJ: arithmetic set | Jacobian mode (kJacMetric); EXT_LDS: 0 = own LDS, else rows per reduction pass in the caller's; STREAM: load_group; RAGGED: the level's grid rows are not whole groups of four (colm)
 __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int pair, const int slice, const Pose& pose,
                                               unsigned char* lds, const RefGroup<VEC>* first = nullptr, int ref_slot = -1,
                                               int tgt_slot = -1, const CoreOverride* ov = nullptr);
@@ -1488,11 +1514,13 @@ __device__ __forceinline__ bool residual_block(const ResidualArgs& a, const int 
   return true;
 }
 
-template <int AR, int VEC, bool DEPTH, bool UNIT_FACTORS, bool DUMP, typename AccT, bool SQUARE, int SAMPLER, int WEIGHTS, bool COMPUTE_ONLY,
+template <int ARJ, int VEC, bool DEPTH, bool UNIT_FACTORS, bool DUMP, typename AccT, bool SQUARE, int SAMPLER, int WEIGHTS, bool COMPUTE_ONLY,
           int EXT_LDS, int STREAM, bool RAGGED>
 __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int pair, const int slice, const Pose& pose,
                                               unsigned char* lds, const RefGroup<VEC>* first, int ref_slot, int tgt_slot,
                                               const CoreOverride* ov) {
+  constexpr int AR = arith_of(ARJ);
+  constexpr bool METRIC = metric_of(ARJ);   // decides jw_terms' form and nothing else
   const int a_groups_per_block = ov ? ov->groups_per_block : a.groups_per_block;
   const bool a_probe = ov ? false : a.probe != 0;
   // MASKED: f64 sums added under an EXEC mask of the valid lanes (masked_sums_*), nothing of an invalid pixel sanitised
@@ -1785,7 +1813,7 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
 #pragma unroll
       for (int u = 0; u < NU; u++) {
         F a0, b1, av[4], bv[4];
-        jw_terms<UNIT_FACTORS, SQUARE, F>(L, a.zf, a.af, x2[u], y2[u], iz[u], a0, b1, av, bv);
+        jw_terms<UNIT_FACTORS, SQUARE, F, METRIC>(L, a.zf, a.af, x2[u], y2[u], iz[u], a0, b1, av, bv);
         const F j0 = g0[u] * a0, j1 = g1[u] * b1;
 #pragma unroll
         for (int c = 0; c < N; c++) {
@@ -1816,11 +1844,11 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
         }
         F a0, b1, av[4], bv[4], j0, j1, Ju[6];
         if constexpr (AR == kArithOpenCV) {
-          jw_terms<UNIT_FACTORS, SQUARE, F>(L, a.zf, a.af, x2[u], y2[u], iz[u], a0, b1, av, bv);
+          jw_terms<UNIT_FACTORS, SQUARE, F, METRIC>(L, a.zf, a.af, x2[u], y2[u], iz[u], a0, b1, av, bv);
           j0 = g0[u] * a0;
           j1 = g1[u] * b1;
         } else {
-          pixel_jacobian<AR, UNIT_FACTORS, SQUARE, false, F>(L, a.zf, a.af, x2[u], y2[u], iz[u], g0[u], g1[u], Ju);
+          pixel_jacobian<AR, UNIT_FACTORS, SQUARE, false, F, METRIC>(L, a.zf, a.af, x2[u], y2[u], iz[u], g0[u], g1[u], Ju);
         }
 #pragma unroll
         for (int c = 0; c < N; c++) {
@@ -1850,7 +1878,7 @@ __device__ __forceinline__ void residual_core(const ResidualArgs& a, const int p
     F J[NU][6];
 #pragma unroll
     for (int u = 0; u < NU; u++)
-      pixel_jacobian<AR, UNIT_FACTORS, SQUARE, DUMP, F>(L, a.zf, a.af, x2[u], y2[u], iz[u], g0[u], g1[u], J[u]);
+      pixel_jacobian<AR, UNIT_FACTORS, SQUARE, DUMP, F, METRIC>(L, a.zf, a.af, x2[u], y2[u], iz[u], g0[u], g1[u], J[u]);
     __builtin_amdgcn_sched_barrier(0);
     gathers_landed();
     // phase 4: residuals and accumulation
@@ -2848,8 +2876,9 @@ __device__ __forceinline__ void coarse_body(const CoarseArgs& ca) {
 // launch, the weighted launch and the update (three dependent launches of a few blocks each, ~20 us for a lone pair) by ~8 us
 // of one resident block.  Same device functions as the launches it replaces: same bits.
 // ------------------------------------------------------------------------------------------------------------
-template <int AR, bool DEPTH, int WEIGHTS, bool PLAIN, int NLEV = kCoarseMaxLevels, bool RAGGED = false>
+template <int ARJ, bool DEPTH, int WEIGHTS, bool PLAIN, int NLEV = kCoarseMaxLevels, bool RAGGED = false>
 __global__ __launch_bounds__(kBlock) void k_coarse_weighted(const CoarseArgs ca) {
+  constexpr int AR = arith_of(ARJ);   // the scale pass forms no Jacobian: the arithmetic set alone
   constexpr int VEC = 4;
   __shared__ unsigned int h[kHistBins * kHistRep];                                  // the residual histogram, kHistRep replicas per bin
   __shared__ unsigned int h_scratch[kHistBins];                                     // wave_scale's working copy
@@ -2913,7 +2942,7 @@ __global__ __launch_bounds__(kBlock) void k_coarse_weighted(const CoarseArgs ca)
         }
         __syncthreads();
         // the weighted sums (src/Tracker.cpp:554-561) through the weight table; the record lands in LDS
-        residual_core<AR, VEC, DEPTH, PLAIN, false, double, PLAIN, 0, WEIGHTS, false, 0, 0, RAGGED>(a, pair, 0, st.pose, nullptr, nullptr, ref_slot, tgt_slot, &ov);
+        residual_core<ARJ, VEC, DEPTH, PLAIN, false, double, PLAIN, 0, WEIGHTS, false, 0, 0, RAGGED>(a, pair, 0, st.pose, nullptr, nullptr, ref_slot, tgt_slot, &ov);
         __syncthreads();
         u.k = k;
         st = update_compute(u, rec, &cur, ulds, false);   // ends with a barrier: every thread has the new state
@@ -3147,8 +3176,9 @@ constexpr int kFeatMaxSlices = (kPatchMaxKeypoints * kPatchMaxRows + kFeatPtsPer
 static_assert(kFeatPtsPerBlock % kBlock == 0, "whole rows per thread");
 __host__ __device__ __forceinline__ int table_slices(int rows) { return rows > kFeatPtsPerBlock ? (rows + kFeatPtsPerBlock - 1) / kFeatPtsPerBlock : 1; }
 
-template <int AR, bool UNIT_FACTORS, typename AccT>
+template <int ARJ, bool UNIT_FACTORS, typename AccT>
 __global__ __launch_bounds__(kBlock) void k_table_eval(const ResidualArgs a, const TableArgs ta) {
+  constexpr int AR = arith_of(ARJ);
   constexpr bool MASKED = std::is_same<AccT, double>::value;
   const int pair = (int)blockIdx.y + a.pair_base;
   const int count = min(ta.counts[pair], ta.stride);
@@ -3185,7 +3215,7 @@ __global__ __launch_bounds__(kBlock) void k_table_eval(const ResidualArgs a, con
       g1 = (float)GY[i1x];
     }
     float J[6];
-    pixel_jacobian<AR, UNIT_FACTORS>(L, a.zf, a.af, x2, y2, iz, g0, g1, J);
+    pixel_jacobian<AR, UNIT_FACTORS, false, false, float, metric_of(ARJ)>(L, a.zf, a.af, x2, y2, iz, g0, g1, J);
     if constexpr (MASKED) {
       const unsigned long long m = __ballot(ok);
       double Jd[6];
@@ -3245,8 +3275,9 @@ __global__ __launch_bounds__(kBlock) void k_table_hist(const ResidualArgs a, con
 // k_table_general — the weighted / bilinear pass: four rows per thread, the 27 f64 sums and the error numerator under an EXEC
 // mask of the valid lanes (masked_sums_*), integer sum of rint(rf)^2, the record of the `general` kind through
 // block_reduce_store(.., err, coherent), the update in the launch's tail (tail_fold_wave; the host arms tail.rule.general = 1).
-template <int AR, bool UNIT_FACTORS>
+template <int ARJ, bool UNIT_FACTORS>
 __global__ __launch_bounds__(kBlock) void k_table_general(const ResidualArgs a, const TableArgs ta, const GeneralArgs ga) {
+  constexpr int AR = arith_of(ARJ);
   const int pair = (int)blockIdx.y + a.pair_base;
   const int count = min(ta.counts[pair], ta.stride);
   const int slices = min(table_slices(count), a.slices);
@@ -3281,7 +3312,7 @@ __global__ __launch_bounds__(kBlock) void k_table_general(const ResidualArgs a, 
       g1 = (float)GY[i1x];
     }
     float J[6];
-    pixel_jacobian<AR, UNIT_FACTORS, false, true>(L, a.zf, a.af, x2, y2, iz, g0, g1, J);
+    pixel_jacobian<AR, UNIT_FACTORS, false, true, float, metric_of(ARJ)>(L, a.zf, a.af, x2, y2, iz, g0, g1, J);
     const float w = robust_weight(ga.weights, rf, inv_mad);
     const double e = (double)rf * (double)(rf * w);   // Residuals.mul(W) for the error (src/Tracker.cpp:500)
     const float rw = (rf * ga.gain) * w;              // :559, :561

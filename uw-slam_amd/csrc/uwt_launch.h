@@ -1,6 +1,8 @@
 // uwt_launch.h — internal: the launch dispatchers of the heavy kernel templates, one translation unit per family so that the
 // library builds in parallel (uwt_launch_residual.hip, uwt_launch_general.hip, uwt_launch_flow.hip, uwt_launch_points.hip; the image
-// warp's are in uwt_warpimg.h / uwt_launch_warpimg.hip, the point cloud's in uwt_cloud.h / uwt_launch_cloud.hip).
+// warp's are in uwt_warpimg.h / uwt_launch_warpimg.hip, the point cloud's in uwt_cloud.h / uwt_launch_cloud.hip).  The metric Jacobian
+// mode's instantiations of all four families are in uwt_launch_metric.hip: each dispatcher hands a call with LaunchSel::metric set to
+// its twin there before it looks at anything else, so that no reference-mode unit holds a metric kernel.
 // A dispatcher picks the instantiation from run-time facts (arithmetic set, depth plane, level width, intrinsics, factors) and
 // enqueues it; it reports nothing — the caller checks hipGetLastError().
 #pragma once
@@ -14,6 +16,7 @@ struct LaunchSel {
   bool depth;          // the context has a depth plane
   bool acc64;          // f64 normal-equation sums (uwt_params::accumulate_f64)
   bool compute_only;   // the diagnostic twin (uwt_profile_enable bit 2)
+  bool metric;         // uwt_set_jacobian(UWT_JACOBIAN_METRIC): the kernels' ARJ = arith | kJacMetric
 };
 
 // A level's rows are pitched to whole groups of four pixels and walked in such groups.  level_ragged: the grid's rows are not
@@ -70,11 +73,31 @@ void launch_weighted(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a,
 // one coarse level of a batch, one block per pair: k_coarse_w4 (identity weights) / k_coarse_weighted
 void launch_coarse_level(hipStream_t s, const LaunchSel& sel, const CoarseArgs& ca, int cnt, int weights);
 
+// The metric mode's twins of the dispatchers above that launch a kernel which forms Jw (uwt_launch_metric.hip).  Every one takes the
+// general Jacobian form — factors multiplied in, no square-pixel sharing, untyped plane loads — whatever the intrinsics, the factors and
+// the plane-load switches of the tuning are: what they choose in reference mode never shows in a result, and the metric Jw has no
+// coinciding products to share.  compute_only is ignored (the diagnostic twin is the production kernel's).
+namespace metric {
+void launch_residual(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, int n_pairs, bool dump);
+void launch_weighted(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, int n_pairs, int sampler, int weights, bool dump);
+void launch_iterate(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const IterArgs& ia, int n_pairs);
+void launch_coarse_chain(hipStream_t s, const LaunchSel& sel, const CoarseArgs& ca, int n_pairs);
+void launch_coarse_level(hipStream_t s, const LaunchSel& sel, const CoarseArgs& ca, int cnt, int weights);
+void launch_table_eval(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, int n_pairs);
+void launch_table_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, const GeneralArgs& ga, int n_pairs);
+}  // namespace metric
+
 // runs the statements with AR a compile-time constant
 #define UWT_WITH_AR(arith, ...)                                              \
   do {                                                                       \
     if ((arith) == kArithLegacy) { constexpr int AR = kArithLegacy; __VA_ARGS__; }  \
     else { constexpr int AR = kArithOpenCV; __VA_ARGS__; }                   \
+  } while (0)
+// the same with ARJ = the arithmetic set | kJacMetric
+#define UWT_WITH_ARJ_METRIC(arith, ...)                                      \
+  do {                                                                       \
+    if ((arith) == kArithLegacy) { constexpr int ARJ = kArithLegacy | kJacMetric; __VA_ARGS__; }  \
+    else { constexpr int ARJ = kArithOpenCV | kJacMetric; __VA_ARGS__; }     \
   } while (0)
 
 }  // namespace uwt

@@ -46,6 +46,7 @@ void launch_coarse_level_t(hipStream_t s, const CoarseArgs& ca, int cnt, int wei
 }  // namespace
 
 void launch_iterate(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const IterArgs& ia, int n_pairs) {
+  if (sel.metric) return metric::launch_iterate(s, sel, a, ia, n_pairs);
   UWT_WITH_AR(sel.arith,
     if (sel.depth) launch_iterate_t<AR, true>(s, a, ia, n_pairs, sel.compute_only);
     else launch_iterate_t<AR, false>(s, a, ia, n_pairs, sel.compute_only));
@@ -54,6 +55,7 @@ void launch_iterate(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, 
 // up to kCoarseMaxLevels coarsest levels of a few pairs, to their end, in one launch; when one of them has ragged grid rows
 // (not whole groups of four) the launch takes the general form with the masking decided per level
 void launch_coarse_chain(hipStream_t s, const LaunchSel& sel, const CoarseArgs& ca, int n_pairs) {
+  if (sel.metric) return metric::launch_coarse_chain(s, sel, ca, n_pairs);
   const dim3 grid(n_pairs), blk(kBlock);
   bool all4 = true;
   for (int i = 0; i < ca.n_levels; i++) all4 = all4 && !level_ragged(ca.lv[i].L);
@@ -77,6 +79,7 @@ void launch_finish(hipStream_t s, const IterArgs& ia, int n_pairs, float* d_pose
 // one coarse level (up to kCoarseMaxPixels) of a batch, one block per pair, the level's iterations in one
 // launch: identity weights k_coarse_w4, robust weights over the nearest sampler k_coarse_weighted
 void launch_coarse_level(hipStream_t s, const LaunchSel& sel, const CoarseArgs& ca, int cnt, int weights) {
+  if (sel.metric) return metric::launch_coarse_level(s, sel, ca, cnt, weights);
   UWT_WITH_AR(sel.arith,
     if (sel.depth) launch_coarse_level_t<AR, true>(s, ca, cnt, weights);
     else launch_coarse_level_t<AR, false>(s, ca, cnt, weights));

@@ -88,6 +88,7 @@ void launch_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, 
     launch_weighted(s, sel, a, n_pairs, sampler, weights);
     return;
   }
+  if (sel.metric) return metric::launch_weighted(s, sel, a, n_pairs, sampler, weights, true);
   const bool unit = (a.zf == 1.0f && a.af == 1.0f);
   UWT_WITH_AR(sel.arith,
     if (sel.depth && unit) launch_dump_t<AR, true, true>(s, a, n_pairs, sampler, weights);
@@ -98,6 +99,7 @@ void launch_general(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, 
 
 // the weighted / bilinear sums of one evaluation (the scale, where weights are on, is in place)
 void launch_weighted(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, int n_pairs, int sampler, int weights) {
+  if (sel.metric) return metric::launch_weighted(s, sel, a, n_pairs, sampler, weights, false);
   const bool unit = (a.zf == 1.0f && a.af == 1.0f);
   const bool ragged = level_ragged(a.L);
   const int key = (ragged ? 0 : 4) | (sel.depth ? 2 : 0) | (unit ? 1 : 0);

@@ -30,6 +30,7 @@ void launch_candidates_slots(hipStream_t s, const LevelK& L, int n_frames, const
 }
 
 void launch_table_eval(hipStream_t s, const LaunchSel& sel, const ResidualArgs& a, const TableArgs& ta, int n_pairs) {
+  if (sel.metric) return metric::launch_table_eval(s, sel, a, ta, n_pairs);
   const bool unit = (a.zf == 1.0f && a.af == 1.0f);
   const dim3 grid(a.slices, n_pairs), blk(kBlock);
   UWT_WITH_AR(sel.arith,
@@ -44,6 +45,7 @@ void launch_table_general(hipStream_t s, const LaunchSel& sel, const ResidualArg
   const bool unit = (a.zf == 1.0f && a.af == 1.0f);
   const dim3 grid(a.slices, n_pairs), blk(kBlock);
   if (ga.weights) UWT_WITH_AR(sel.arith, hipLaunchKernelGGL((k_table_hist<AR>), grid, blk, 0, s, a, ta, ga));
+  if (sel.metric) return metric::launch_table_general(s, sel, a, ta, ga, n_pairs);   // (behind the scale pass, which forms no Jacobian)
   UWT_WITH_AR(sel.arith,
     if (unit) hipLaunchKernelGGL((k_table_general<AR, true>), grid, blk, 0, s, a, ta, ga);
     else hipLaunchKernelGGL((k_table_general<AR, false>), grid, blk, 0, s, a, ta, ga));

@@ -82,6 +82,7 @@ void launch_residual_vd(hipStream_t s, const ResidualArgs& a, int n_pairs, bool 
 }  // namespace
 
 void launch_residual(hipStream_t s, const LaunchSel& sel, const ResidualArgs& args, int n_pairs, bool dump) {
+  if (sel.metric) return metric::launch_residual(s, sel, args, n_pairs, dump);
   // the typed forms read pixel rays from block tables: a level whose pitch and rows exceed the table space (no supported size)
   // takes the plain forms
   ResidualArgs a = args;

@@ -132,6 +132,11 @@ class Tracker:
         _previous_frame.rigid_transformation_ = poses[0]
         return stats[0]
 
+    def SetJacobian(self, mode):
+        """uw::Tracker::SetJacobian (uwt_set_jacobian): 0 / "reference" the reference's Jw, 1 / "metric" the 3-D point's coordinates in
+        columns 2..5 — every Estimate* call from here on.  Metric is meant to run with handoff "keep" of the seeded calls."""
+        self._ctx.set_jacobian(mode)
+
     def PredictSeeds(self, prev, cur):
         """The constant-velocity motion model in keyframe coordinates (uwt_predict_seeds): prev = the poses keyframe -> frame p - 1,
         cur = keyframe -> frame p, [n, 7] each; returns the seeds (cur * prev^-1) * cur for keyframe -> frame p + 1."""
@@ -187,7 +192,9 @@ class Tracker:
             raise RuntimeError("ApplyGradient(previous_frame) must run before EstimatePoseFeatures (or its slot was reused since)")
         saved = {k: getattr(self._ctx.params, k) for k in ("first_level", "last_level", "max_iters", "gain", "z_factor",
                                                             "angle_factor", "handoff_scale_t", "early_exit")}
-        self._ctx.update_params(first_level=0, last_level=0, max_iters=10, gain=1.0, z_factor=0.002, angle_factor=1.0,
+        # (z_factor 0.002 compensates the pixel coordinate in the reference's column 2: 1 under the metric Jacobian, as in the batched call)
+        zf = 1.0 if self._ctx.get_jacobian() == capi.JACOBIAN_METRIC else 0.002
+        self._ctx.update_params(first_level=0, last_level=0, max_iters=10, gain=1.0, z_factor=zf, angle_factor=1.0,
                                 handoff_scale_t=1, early_exit=1)
         try:
             pose, st = self._ctx.estimate_pose_points(a, b, {0: _previous_frame.candidatePoints_[0]})
