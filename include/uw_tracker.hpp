@@ -398,6 +398,46 @@ class Tracker {
     r.points.resize((size_t)r.info[n].written);
     return r;
   }
+  // EXTENSION (no reference counterpart): the keyframe's depth codes from the 1..4 frames `_views` tracked against it and their poses
+  // (X_view = T X_keyframe, what the tracking calls return), one job of uwt_sweep_depth_batch (the contract: include/uwt.h).  _codes: the
+  // u16 hypotheses (uwt_sweep_hypotheses).  depth, cost: img_w x img_h u16 of the level, outcome: u8 (uwt_sweep_outcome), info the
+  // job's record.  _params null: the defaults with n_views and n_hyp taken from the arguments.
+  struct SweptDepth {
+    std::vector<uint16_t> depth, cost;
+    std::vector<uint8_t> outcome;
+    uwt_sweep_info info;
+  };
+  SweptDepth SweepDepth(Frame* _keyframe, const std::vector<Frame*>& _views, const std::vector<SE3>& _poses,
+                        const std::vector<uint16_t>& _codes, const uwt_sweep_params* _params = nullptr) {
+    const size_t n = _views.size();
+    if (_poses.size() != n || !n) throw std::runtime_error("SweepDepth: one pose per view, one view at least");
+    uwt_sweep_params sp;
+    if (_params) sp = *_params;
+    else {
+      check(uwt_default_sweep_params(&sp), "uwt_default_sweep_params");
+      sp.n_views = (int32_t)n;
+      sp.n_hyp = (int32_t)_codes.size();
+    }
+    if (sp.n_views != (int32_t)n || sp.n_hyp != (int32_t)_codes.size()) throw std::runtime_error("SweepDepth: n_views or n_hyp of the params");
+    const int32_t ref = bind(_keyframe);
+    if (sp.source == 1 && !_keyframe->obtained_gradients_)
+      throw std::runtime_error("SweepDepth: the candidate source needs ApplyGradient on the keyframe (or its slot was reused since)");
+    std::vector<int32_t> slots(n);
+    for (size_t i = 0; i < n; i++) slots[i] = bind(_views[i]);
+    if (!bound(_keyframe) || _keyframe->slot_ != ref) throw std::runtime_error("SweepDepth: more frames than slots (max_frames)");
+    for (size_t i = 0; i < n; i++)   // binding a later frame may have taken an earlier frame's slot
+      if (!bound(_views[i]) || _views[i]->slot_ != slots[i]) throw std::runtime_error("SweepDepth: more frames than slots (max_frames)");
+    if (sp.lvl < 0 || sp.lvl >= params_.n_levels) throw std::runtime_error("SweepDepth: level out of range");
+    const uwt_level L = level(sp.lvl);
+    SweptDepth r;
+    r.depth.resize((size_t)L.img_w * L.img_h);
+    r.cost.resize(r.depth.size());
+    r.outcome.resize(r.depth.size());
+    const int st = uwt_sweep_depth_batch(ctx(), 1, &ref, slots.data(), _poses[0].data(), _codes.data(), &sp, r.depth.data(), r.cost.data(),
+                                         r.outcome.data(), &r.info);
+    if (st != UWT_ERR_PAIR_FAILED) check(st, "uwt_sweep_depth_batch");   // a failed job has its status in its record
+    return r;
+  }
   // the same on one explicit N x 4 table of any producer (uwt_point_cloud_points); _frame serves the intensities
   std::vector<uwt_cloud_point> PointCloudPoints(Frame* _frame, const std::vector<float>& _points, const SE3& _pose,
                                                 const uwt_cloud_params* _params = nullptr) {

@@ -1384,6 +1384,115 @@ enum uwt_jacobian { UWT_JACOBIAN_REFERENCE = 0, UWT_JACOBIAN_METRIC = 1 };
 int uwt_set_jacobian(uwt_ctx* ctx, int32_t mode);
 int uwt_get_jacobian(const uwt_ctx* ctx, int32_t* out);
 
+/* ---- EXTENSION: depth from tracked motion, a plane sweep over resident frames -------------------------------------------------- */
+
+/* No reference counterpart: the reference has depth only where a sensor delivers it (src/Tracker.cpp:1266-1302).  Given a reference
+ * slot, 1..4 view slots and the poses a tracking call left (X_view = T * X_ref, the tracker's own convention: the pose buffers of
+ * uwt_track_batch_async, uwt_track_batch_seeded_async and uwt_tracking_io::d_poses go straight in), the sweep tries n_hyp depth CODES
+ * on every considered pixel of the reference slot and writes the code under which the views agree best.  A code d is what a depth
+ * plane holds: at level lvl it means the table row [x, y, z(d), 1] ObtainAllPoints makes for a pixel whose depth plane holds d,
+ * z(d) = (float)d * (float)(depth_scale / 2^lvl) as ObtainAllPoints computes it (src/Tracker.cpp:1266) (lvl = 0 is the intended
+ * level; lvl >= 1 reproduces the reference's / 2^lvl quirk and nothing more).  The row is warped by uwt_warp's arithmetic in the
+ * context's arithmetic set, the matching costs are integers, the only other floating point is the f64 refinement of step 10: the
+ * result is the same bytes on every run, in any batch, and the depth written is exactly the depth under which the tracker,
+ * uwt_warp_image_batch and uwt_point_cloud_batch compute the same landing pixels.
+ *
+ * A JOB is one reference slot and n_views view slots, 1 <= n_views <= 4 (the same for every job of a call), view v of job j under the
+ * pose d_poses[j * n_views + v].  The hypotheses are n_hyp codes d_0 < d_1 < ... < d_{n_hyp-1}, 3 <= n_hyp <= 64, each in 1..32767
+ * (what the tracker's (int16)depth > 0 accepts); they are host data of the call.
+ * Pixels considered: source = 0 the level's w x h point grid; source = 1 the pixels (x, y) of the rows
+ * uwt_obtain_candidate_points(slot, lvl, threshold) returns on a context without a depth plane: gradient_ > mean + threshold over the
+ * point grid (gradients must have been applied to the reference slot).  The sweep never reads a depth plane, so the zero-depth test
+ * ObtainCandidatePoints makes on a context WITH a depth plane is not part of the selection.
+ * For a considered pixel (x, y), patch radius r in {1, 2}, img_w x img_h the level's image:
+ *    1. BORDER unless r <= x <= img_w-1-r and r <= y <= img_h-1-r.
+ *    2. Landing, for hypothesis k and view v: [u, v', Z', .] = uwt_warp(lvl, [x, y, z(d_k), 1], T_v); x2 = (int)round(u), y2 =
+ *       (int)round(v') (C round); u or v' not finite or of magnitude >= 2^31 - 128 does not land (the image warp's rule).  It LANDS iff
+ *       Z' > 0 and r <= x2 <= img_w-1-r and r <= y2 <= img_h-1-r.  k is VALID iff it lands in every view.
+ *    3. FEW: fewer than 3 valid hypotheses.
+ *    4. cost[k] = sum over views and dy, dx in [-r, r] of | view_v[y2+dy, x2+dx] - ref[y+dy, x+dx] | on the u8 image planes: the
+ *       reference patch translated, not warped per pixel.  At most 25 * 255 * 4.
+ *    5. dist(a, b) = max over views of max(|x2_a - x2_b|, |y2_a - y2_b|).  LOW_PARALLAX when dist(first valid, last valid) <
+ *       min_parallax: the motion does not separate the hypotheses.
+ *    6. The winner is the valid k of least cost, the smallest such k on equal cost.
+ *    7. EDGE when the winner is 0 or n_hyp-1 or a neighbour k-1, k+1 is not valid.
+ *    8. POOR when cost[k] > max_mean_abs * (2r+1)^2 * n_views.
+ *    9. c2 = the least cost over valid j with dist(j, k) >= 2.  AMBIGUOUS when there is no such j, or unless
+ *       uniq_den * cost[k] < uniq_num * c2 (strict, 64-bit integers).
+ *   10. ESTIMATED.  With refine = 0, or den = c- - 2 c0 + c+ equal to 0 (c-, c0, c+ the costs of k-1, k, k+1), the code is d_k.  Else,
+ *       in f64, every operation rounded once, no contraction: a = (double)|c- - c+| / (double)(2 den); n = k+1 when c- > c+, else k-1;
+ *       rho_j = 1.0 / (double)d_j; rho = rho_k + a * (rho_n - rho_k); code = (int)rint(1.0 / rho) (ties to even), clamped to 1..32767.
+ * Outputs, job j's plane j * pitch * img_h elements behind job 0's, laid out like a slot's plane (pitch x img_h; columns >= img_w
+ * are never written): d_depth (u16) the code where ESTIMATED and 0 at every other pixel of the image; d_cost (u16) the winner's cost
+ * where ESTIMATED, else 0; d_outcome (u8) the values of uwt_sweep_outcome; d_info one record per job.  A job's bytes depend neither
+ * on the batch, nor on the job's place in it, nor on uwt_tuning, nor on the run: minima and sums of integers, no cursor, no float
+ * atomic.  The sweep never reads a depth plane: for a ONE-job call uwt_plane_device_ptr(ctx, ref_slot, lvl, UWT_PLANE_DEPTH) is a
+ * valid d_depth, which is how a keyframe gets its depth in place.
+ * What consumes a semi-dense level-0 plane (zeros where nothing was estimated) as it is: the live call
+ * (uwt_estimate_pose_features_batch: a key point on a zero is dropped), uwt_point_cloud_batch with skip_invalid = 1,
+ * uwt_warp_image_batch at level 0, and alignments that iterate level 0 alone (zero-depth points are [0 0 1 0] rows, never valid).
+ * uwt_build_pyramids averages the zeros in, as the reference's resize does: the coarser levels of such a plane are the
+ * caller's business. */
+enum uwt_sweep_outcome { UWT_SWEEP_NOT_SELECTED = 0, UWT_SWEEP_ESTIMATED = 1, UWT_SWEEP_BORDER = 2, UWT_SWEEP_FEW = 3,
+                         UWT_SWEEP_LOW_PARALLAX = 4, UWT_SWEEP_EDGE = 5, UWT_SWEEP_POOR = 6, UWT_SWEEP_AMBIGUOUS = 7 };
+
+typedef struct uwt_sweep_params {   /* 64 bytes */
+  int32_t lvl;            /* the level swept */
+  int32_t source;         /* 0: the point grid, 1: the candidate pixels */
+  double  threshold;      /* source 1: GRADIENT_THRESHOLD; finite */
+  int32_t n_views;        /* 1..4 */
+  int32_t n_hyp;          /* 3..64 */
+  int32_t radius;         /* 1 or 2 */
+  int32_t max_mean_abs;   /* >= 1: step 8 */
+  int32_t uniq_num;       /* >= 1: step 9 */
+  int32_t uniq_den;       /* >= 1 */
+  int32_t min_parallax;   /* >= 2: step 5 */
+  int32_t refine;         /* 0 or 1: step 10 */
+  int32_t reserved[4];    /* must be zero */
+} uwt_sweep_params;
+
+typedef struct uwt_sweep_info {   /* per job, 64 bytes, all integers: exact and order-independent */
+  int32_t status;          /* uwt_status_code of this job */
+  int32_t n_selected;      /* pixels considered = the sum of n_outcome[1..7] */
+  int32_t n_outcome[8];    /* by uwt_sweep_outcome; [0] is 0 */
+  int64_t sum_cost;        /* over the estimated pixels: the winner's cost */
+  int64_t sum_code;        /* over the estimated pixels: the code written */
+  int64_t reserved;
+} uwt_sweep_info;
+
+typedef struct uwt_sweep_io {   /* every pointer is DEVICE memory; planes are n_jobs x pitch x img_h elements */
+  uint16_t*       d_depth;      /* out, required; 2-byte aligned */
+  uint16_t*       d_cost;       /* out, may be null; 2-byte aligned */
+  uint8_t*        d_outcome;    /* out, may be null */
+  uwt_sweep_info* d_info;       /* out, required: n_jobs records; 8-byte aligned (64-bit sums) */
+} uwt_sweep_io;
+
+/* {0, 1, 20.0, 1, 32, 2, 12, 3, 4, 4, 1, {0}} */
+int uwt_default_sweep_params(uwt_sweep_params* out);
+/* HOST helper, no context: n codes uniform in inverse depth from z_near to z_far, in f64: rho_k = 1/z_near + k (1/z_far - 1/z_near) /
+ * (n - 1), d_k = rint(1 / (rho_k * depth_scale)).  UWT_ERR_INVALID_ARG: a null pointer, n outside 3..64, z_near, z_far or depth_scale
+ * not finite or not > 0, z_near >= z_far, or codes that are not strictly increasing or leave 1..32767 (codes_out is then untouched). */
+int uwt_sweep_hypotheses(double z_near, double z_far, double depth_scale, int32_t n, uint16_t* codes_out);
+/* The sweep for a batch of jobs.  ref_slots: n_jobs; view_slots: n_jobs x n_views; d_poses: DEVICE memory, n_jobs x n_views x 7
+ * floats; codes: n_hyp host values (copied before the call returns).  The frames must be resident with pyramids built, source = 1
+ * needs the reference slots' gradients.  Enqueued on the context's stream, ordered against uwt_upload_frames_async on every slot
+ * named as the other batch calls are; it never waits for the device; uwt_sync() to wait.
+ * UWT_ERR_INVALID_ARG with nothing enqueued and every output untouched: a null list, d_poses, codes, params, io, d_depth or d_info;
+ * n_jobs outside 1..max_pairs; a slot or level out of range; source outside 0..1, n_views outside 1..4, n_hyp outside 3..64, radius
+ * outside 1..2, refine outside 0..1; uniq_num, uniq_den or max_mean_abs < 1; min_parallax < 2; a non-zero reserved word; a threshold
+ * that is not finite; codes that are not strictly increasing or leave 1..32767.
+ * A pose with a non-finite entry puts UWT_ERR_INVALID_ARG into that job's status with all counts 0 and its planes zero; its
+ * neighbours are untouched.
+ * alignment: d_poses 4 bytes; io: at uwt_sweep_io. */
+int uwt_sweep_depth_batch_async(uwt_ctx* ctx, int32_t n_jobs, const int32_t* ref_slots, const int32_t* view_slots, const float* d_poses,
+                                const uint16_t* codes, const uwt_sweep_params* params, const uwt_sweep_io* io);
+/* The same, synchronous, HOST in and out: poses n_jobs x n_views x 7; depth_out (required) / cost_out n_jobs x img_w x img_h u16,
+ * outcome_out n_jobs x img_w x img_h u8, tight, the latter two may be null; info_out n_jobs, required.  UWT_ERR_PAIR_FAILED when a job
+ * failed, its status in its record. */
+int uwt_sweep_depth_batch(uwt_ctx* ctx, int32_t n_jobs, const int32_t* ref_slots, const int32_t* view_slots, const float* poses,
+                          const uint16_t* codes, const uwt_sweep_params* params, uint16_t* depth_out, uint16_t* cost_out,
+                          uint8_t* outcome_out, uwt_sweep_info* info_out);
+
 /* ---- test instrumentation: guards inside the context's own scratch ------------------------------------------------------------ */
 
 /* Not part of the tracker: these two serve tests/test_gpu_guard_bands.py, which uses them to see whether a kernel writes outside an

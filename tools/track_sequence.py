@@ -230,6 +230,40 @@ def track_keyframes(w, h, intr, frames, depths, over, interval=1, motion_model="
     return out
 
 
+def sweep_keyframes(w, h, intr, frames, poses, keyframes, n_views, codes, arith=0, source=1):
+    """Depth for every keyframe of a keyframe-tracked sequence (track_keyframes) from the first n_views frames tracked against it and
+    their poses (keyframe -> frame, the tracker's convention): uwt_sweep_depth_batch_async writes the depth codes straight into the
+    keyframe's level-0 depth plane (uwt_plane_device_ptr), which is then read back.  Returns (depth [K, h, w] u16, a list of per-keyframe
+    dicts: keyframe, views, coverage = estimated pixels / (w h), n_selected and the counts by uwt_sweep_outcome)."""
+    import torch
+    capi = importlib.import_module("uw-slam_amd.capi")
+    # (the sweep reads level 0 alone: two levels, the least a pyramid has)
+    ctx = capi.Context(capi.default_params(w, h, *intr, max_frames=1 + n_views, max_pairs=1, has_depth=1, arith=arith, n_levels=2,
+                                           first_level=1, last_level=0))
+    planes, report = [], []
+    for kf in sorted(set(keyframes)):
+        pairs = [p for p, k in enumerate(keyframes) if k == kf][:n_views]   # pair p tracks frame p + 1 against keyframes[p]
+        if len(pairs) < n_views:
+            continue   # the last keyframe of the sequence may have fewer frames behind it
+        batch = np.stack([frames[kf]] + [frames[p + 1] for p in pairs])
+        ctx.upload_frames(0, batch, np.zeros(batch.shape, np.uint16))
+        ctx.build_pyramids(0, 1 + n_views)
+        ctx.apply_gradient(0, 1)
+        d_poses = torch.tensor(np.asarray(poses, np.float32)[pairs], dtype=torch.float32, device="cuda")
+        d_info = torch.zeros(64, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()   # torch's copies run on torch's stream
+        params = capi.default_sweep_params(n_views=n_views, n_hyp=len(codes), source=source)
+        ctx.sweep_depth_async([0], list(range(1, 1 + n_views)), d_poses.data_ptr(), codes,
+                              dict(depth=ctx.plane_device_ptr(0, 0, capi.PLANE_DEPTH), info=d_info.data_ptr()), params)
+        ctx.sync()
+        planes.append(ctx.get_plane(0, 0, capi.PLANE_DEPTH))   # the keyframe's depth plane, as any consumer reads it
+        info = d_info.cpu().numpy().view(capi.SWEEP_INFO)[0]
+        report.append(dict(keyframe=int(kf), views=[int(p + 1) for p in pairs], coverage=float(info["n_outcome"][1]) / float(w * h),
+                           n_selected=int(info["n_selected"]), outcomes=[int(v) for v in info["n_outcome"]]))
+    ctx.close()
+    return (np.stack(planes) if planes else np.zeros((0, h, w), np.uint16)), report
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", required=True)
@@ -284,6 +318,14 @@ def add_seed_arguments(ap):
                     "(the correct Jacobian, an extension).  Dense tracking in metric mode goes through the seeded entry (frame to "
                     "frame from the identity unless --keyframe-interval / --motion-model say otherwise) under --handoff keep unless "
                     "another is named; with --live the alignment runs with z_factor 1")
+    ap.add_argument("--sweep-depth", type=int, default=0, metavar="N", help="with --keyframe-interval: estimate every keyframe's depth from "
+                    "the first N (1..4) frames tracked against it and their poses (uwt_sweep_depth_batch_async, an extension), written "
+                    "into the keyframe's level-0 depth plane; reports coverage and the outcome counts per keyframe and saves the planes "
+                    "as <out>_sweep_depth.npy.  The tool makes no accuracy claim on depth-less data: poses tracked on z = 1 carry that "
+                    "assumption, and the depth swept under them inherits it")
+    ap.add_argument("--sweep-range", default="0.5,2.5", metavar="ZNEAR,ZFAR", help="the depth range the hypotheses cover, uniform in "
+                    "inverse depth (uwt_sweep_hypotheses)")
+    ap.add_argument("--sweep-hyp", type=int, default=32, help="depth hypotheses, 3..64")
     return ap
 
 
@@ -334,11 +376,20 @@ def main():
         ap.error("--keyframe-interval (and --motion-model constant without --live) is the dense tracker alone: no --live, --quality or --cloud")
     if a.motion_model == "constant" and a.live and not a.chained:
         ap.error("--motion-model constant with --live goes with --chained")
-    records = cloud = device_traj = None
+    if a.sweep_depth and (a.keyframe_interval < 1 or not 1 <= a.sweep_depth <= min(4, a.keyframe_interval)):
+        ap.error("--sweep-depth N goes with --keyframe-interval K, 1 <= N <= min(4, K)")
+    records = cloud = device_traj = sweep_report = None
     cloud_args = (a.cloud_stride, CLOUD_MODES[a.cloud_mode]) if a.cloud else None
     if seeded:
         poses, stats, device_traj, keyframes = track_keyframes(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over,
                                                                max(1, a.keyframe_interval), a.motion_model, a.handoff, a.jacobian)
+        if a.sweep_depth:
+            capi = importlib.import_module("uw-slam_amd.capi")
+            z_near, z_far = [float(v) for v in a.sweep_range.split(",")]
+            codes = capi.sweep_hypotheses(z_near, z_far, 0.0002, a.sweep_hyp)
+            sweep_planes, sweep_report = sweep_keyframes(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, poses, keyframes,
+                                                         a.sweep_depth, codes, over["arith"])
+            np.save(a.out + "_sweep_depth.npy", sweep_planes)
     elif a.live and a.chained and (a.quality or a.cloud):
         res = track_live_chained(a.width, a.height, (fx, fy, cx - x0, cy - y0), frames, depths, over["arith"],
                                  detector=int(a.detector == "orb"), quality=a.quality, cloud=cloud_args, motion_model=a.motion_model,
@@ -383,6 +434,11 @@ def main():
         q = metrics["quality"]
         print("coverage %.3f, mean |difference| %.2f aligned against %.2f unaligned (means over %d pairs)"
               % (np.mean(q["coverage"]), np.mean(q["mean_abs"]), np.mean(q["mean_abs_unaligned"]), len(poses)))
+    if sweep_report is not None:
+        metrics["sweep_depth"] = sweep_report
+        for r in sweep_report:
+            print("keyframe %d from frames %s: coverage %.3f, %d selected, outcomes %s" % (r["keyframe"], r["views"], r["coverage"],
+                                                                                         r["n_selected"], r["outcomes"][1:]))
     if a.cloud:
         metrics["cloud_points"] = int(cloud.size)
         T.write_ply(a.cloud, cloud)

@@ -32,6 +32,10 @@ WARP_QUALITY = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("n_landed", "<
 CLOUD_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("tag", "<u4")])   # uwt_cloud_point
 CLOUD_INFO = np.dtype([("status", "<i4"), ("n_rows", "<i4"), ("n_selected", "<i4"), ("n_points", "<i4"), ("offset", "<i8"),
                        ("written", "<i8")])   # uwt_cloud_info
+SWEEP_INFO = np.dtype([("status", "<i4"), ("n_selected", "<i4"), ("n_outcome", "<i4", (8,)), ("sum_cost", "<i8"), ("sum_code", "<i8"),
+                       ("reserved", "<i8")])   # uwt_sweep_info
+# enum uwt_sweep_outcome
+SWEEP_NOT_SELECTED, SWEEP_ESTIMATED, SWEEP_BORDER, SWEEP_FEW, SWEEP_LOW_PARALLAX, SWEEP_EDGE, SWEEP_POOR, SWEEP_AMBIGUOUS = range(8)
 
 
 class Params(C.Structure):
@@ -115,6 +119,40 @@ def default_cloud_params(**over):
     return p
 
 
+class SweepParams(C.Structure):
+    """uwt_sweep_params: the level, the pixel source and its threshold, views, hypotheses, patch radius and the decision's constants"""
+    _fields_ = [("lvl", C.c_int32), ("source", C.c_int32), ("threshold", C.c_double), ("n_views", C.c_int32), ("n_hyp", C.c_int32),
+                ("radius", C.c_int32), ("max_mean_abs", C.c_int32), ("uniq_num", C.c_int32), ("uniq_den", C.c_int32),
+                ("min_parallax", C.c_int32), ("refine", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class SweepIO(C.Structure):
+    """uwt_sweep_io: device pointers of one uwt_sweep_depth_batch_async call"""
+    _fields_ = [("d_depth", C.c_void_p), ("d_cost", C.c_void_p), ("d_outcome", C.c_void_p), ("d_info", C.c_void_p)]
+
+
+def default_sweep_params(**over):
+    """uwt_default_sweep_params: {0, 1, 20.0, 1, 32, 2, 12, 3, 4, 4, 1}; keyword arguments override fields"""
+    p = SweepParams()
+    st = lib().uwt_default_sweep_params(C.byref(p))
+    if st:
+        raise UwtError(st, "uwt_default_sweep_params")
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def sweep_hypotheses(z_near, z_far, depth_scale, n):
+    """uwt_sweep_hypotheses: n u16 depth codes uniform in inverse depth from z_near to z_far (a host helper, no context)"""
+    codes = np.zeros(max(int(n), 1), np.uint16)
+    st = lib().uwt_sweep_hypotheses(C.c_double(z_near), C.c_double(z_far), C.c_double(depth_scale), int(n), _p(codes, C.c_uint16))
+    if st:
+        raise UwtError(st, "uwt_sweep_hypotheses: codes not strictly increasing, outside 1..32767, or an argument out of range")
+    return codes[:n]
+
+
 class TableOptions(C.Structure):
     """uwt_table_options: the weights (0 identity, 1 Tukey, 2 Huber) and sampler (0 round(), 1 bilinear) of one batched table call"""
     _fields_ = [("weights", C.c_int32), ("sampler", C.c_int32), ("reserved", C.c_int32 * 6)]
@@ -191,6 +229,7 @@ SYMBOLS = [
     "uwt_track_candidates_batch_seeded_async", "uwt_estimate_pose_candidates_batch_seeded",
     "uwt_tracking_batch_seeded_async", "uwt_tracking_orb_batch_seeded_async", "uwt_predict_seeds_device_async",
     "uwt_tracking_batch_seeded", "uwt_tracking_orb_batch_seeded", "uwt_predict_seeds",
+    "uwt_default_sweep_params", "uwt_sweep_hypotheses", "uwt_sweep_depth_batch_async", "uwt_sweep_depth_batch",
     "uwt_debug_guards", "uwt_debug_check_guards",
 ]
 
@@ -1438,6 +1477,45 @@ class Context:
         self._chk(lib().uwt_warp_mosaic(self._h, ref_slot, tgt_slot, lvl, _p(warped, C.c_uint8), _p(out, C.c_uint8)))
         return out
 
+    # -- EXTENSION: depth from tracked motion
+    def sweep_depth(self, ref_slots, view_slots, poses, codes, params=None, cost=True, outcome=True, raise_on_failure=False):
+        """The depth sweep for many jobs, host in and out (uwt_sweep_depth_batch): ref_slots [J], view_slots [J, n_views], poses
+        [J, n_views, 7] (X_view = T X_ref), codes [n_hyp] u16.  params: SweepParams (n_views and n_hyp are set from the arrays when
+        None).  Returns a dict: status (OK or ERR_PAIR_FAILED), depth, cost ([J, img_h, img_w] u16), outcome ([J, img_h, img_w] u8; cost /
+        outcome None when not asked for) and info ([J] SWEEP_INFO)."""
+        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
+        J = ref.size
+        views = np.ascontiguousarray(view_slots, np.int32).reshape(max(J, 1), -1) if J else np.zeros((0, 1), np.int32)
+        codes = np.ascontiguousarray(codes, np.uint16).reshape(-1)
+        if params is None:
+            params = default_sweep_params(n_views=views.shape[1], n_hyp=codes.size)
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
+        nl = self.params.n_levels
+        L = self.level_info(params.lvl if 0 <= params.lvl < nl else 0)
+        shape = (max(J, 1), L.img_h, L.img_w)
+        depth = np.zeros(shape, np.uint16)
+        cst = np.zeros(shape, np.uint16) if cost else None
+        out = np.zeros(shape, np.uint8) if outcome else None
+        info = np.zeros(max(J, 1), SWEEP_INFO)
+        st = lib().uwt_sweep_depth_batch(self._h, J, _p(ref, C.c_int32), _p(views, C.c_int32), _p(poses, C.c_float), _p(codes, C.c_uint16),
+                                         C.byref(params), _p(depth, C.c_uint16), _p(cst, C.c_uint16) if cost else None,
+                                         _p(out, C.c_uint8) if outcome else None, C.c_void_p(info.ctypes.data))
+        self._chk(st, allow=() if raise_on_failure else (ERR_PAIR_FAILED,))
+        return dict(status=st, depth=depth[:J], cost=cst[:J] if cost else None, outcome=out[:J] if outcome else None, info=info[:J])
+
+    def sweep_depth_async(self, ref_slots, view_slots, d_poses_ptr, codes, io, params=None):
+        """The same enqueued on the context stream with the poses and every result in device memory (uwt_sweep_depth_batch_async).
+        d_poses_ptr: J x n_views x 7 float32, e.g. the pose buffer of a tracking call enqueued before, with no sync() in between; io: a
+        dict of device addresses — depth (J x pitch x img_h u16; for one job the reference slot's own depth plane is valid), info
+        (J SWEEP_INFO) and optionally cost (u16), outcome (u8).  Never waits for the device; sync() to wait."""
+        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
+        views = np.ascontiguousarray(view_slots, np.int32).reshape(-1)
+        codes = np.ascontiguousarray(codes, np.uint16).reshape(-1)
+        if params is None:
+            params = default_sweep_params(n_views=views.size // max(ref.size, 1), n_hyp=codes.size)
+        rec = SweepIO(*[io.get(k) or None for k in ("depth", "cost", "outcome", "info")])
+        self._chk(lib().uwt_sweep_depth_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(views, C.c_int32), C.c_void_p(d_poses_ptr),
+                                                    _p(codes, C.c_uint16), C.byref(params), C.byref(rec)))
 
     # -- the map: Visualizer::AddPointCloudFromRGBD
     def point_cloud_batch(self, slots, traj, params=None, cap=None, raise_on_failure=False):

@@ -1199,7 +1199,7 @@ static std::vector<NamedBuf> growable(uwt_ctx* c) {
           {"cand_cnt", &c->cand_cnt}, {"cand_work", &c->cand_work}, {"cand_recs", &c->cand_recs}, {"match_desc", &c->match_desc},
           {"match_cnt", &c->match_cnt}, {"match_part", &c->match_part}, {"match_out", &c->match_out}, {"ransac_buf", &c->ransac_buf},
           {"surf_buf", &c->surf_buf}, {"orb_buf", &c->orb_buf}, {"orb_pat", &c->orb_pat}, {"track_buf", &c->track_buf},
-          {"warp_buf", &c->warp_buf}, {"cloud_buf", &c->cloud_buf}};
+          {"warp_buf", &c->warp_buf}, {"cloud_buf", &c->cloud_buf}, {"sweep_buf", &c->sweep_buf}};
 }
 
 static void drain_streams(uwt_ctx* c) {
@@ -1263,7 +1263,7 @@ int uwt_destroy(uwt_ctx* c) {
                   (void*)c->feat_tab, (void*)c->feat_cnt, (void*)c->feat_kp, (void*)c->feat_nkp, (void*)c->feat_recs,
                   (void*)c->ransac_need})
     (void)hipFree(p);
-  for (void* p : {(void*)c->h_small, (void*)c->h_active, (void*)c->h_pairs, (void*)c->h_feat, (void*)c->h_cloud, (void*)c->h_seeds}) (void)hipHostFree(p);
+  for (void* p : {(void*)c->h_small, (void*)c->h_active, (void*)c->h_pairs, (void*)c->h_feat, (void*)c->h_cloud, (void*)c->h_sweep, (void*)c->h_seeds}) (void)hipHostFree(p);
   auto drop = [](hipEvent_t e) { if (e) (void)hipEventDestroy(e); };
   for (hipEvent_t e : c->ev_poll) drop(e);
   for (hipEvent_t e : c->ev_feat) drop(e);
@@ -1271,6 +1271,7 @@ int uwt_destroy(uwt_ctx* c) {
   for (hipEvent_t e : c->ev_join) drop(e);
   for (hipEvent_t e : c->ev_pairs) drop(e);
   for (hipEvent_t e : c->ev_cloud) drop(e);
+  for (hipEvent_t e : c->ev_sweep) drop(e);
   for (hipEvent_t e : c->ev_level) drop(e);
   for (hipEvent_t e : c->ev_window) drop(e);
   for (hipEvent_t e : {c->ev_fork, c->ev_pyramids, c->ev_side_done, c->ev_entry, c->ev_first_end}) drop(e);

@@ -213,6 +213,12 @@ struct uwt_ctx {
   int* h_cloud = nullptr;
   hipEvent_t ev_cloud[kPairStages] = {};
   int cloud_stage = 0;
+  // the depth sweep (uwt_sweep_depth_batch*): the slot lists, the codes, the selection's gradient_ planes and sums and, for the host
+  // form, its inputs and results — grown on use; and a pinned staging ring for the lists and the codes (as h_cloud), made on first use
+  DevBuf sweep_buf;
+  int* h_sweep = nullptr;
+  hipEvent_t ev_sweep[kPairStages] = {};
+  int sweep_stage = 0;
   DevBuf stage[2];                      // uploads of frames whose rows are pitched on the device: [0] context stream, [1] copy stream
   bool profiling = false;
   int spec_budget = 0;                  // speculative launching: evaluations a level gets (0: first_poll + 1); doubled when an alignment

@@ -342,6 +342,24 @@ class Tracker:
         r = self._ctx.point_cloud_batch(slots, traj, params)
         return r["points"], r["info"], r["call"]
 
+    def SweepDepth(self, keyframe, views, poses, codes, params=None):
+        """EXTENSION (no reference counterpart): the keyframe's depth codes from the 1..4 frames `views` tracked against it and their
+        poses ([n_views, 7], X_view = T X_keyframe — what the tracking calls return), one job of uwt_sweep_depth_batch.  codes: the u16
+        hypotheses (capi.sweep_hypotheses).  Returns (depth u16, cost u16, outcome u8 — the level's img_h x img_w — and the job's
+        capi.SWEEP_INFO record)."""
+        frames = [keyframe] + list(views)
+        codes = np.ascontiguousarray(codes, np.uint16).reshape(-1)
+        if params is None:
+            params = capi.default_sweep_params(n_views=len(views), n_hyp=codes.size)
+        slots = [self._bind(f) for f in frames]
+        for f, s in zip(frames, slots):   # binding a later frame may have taken an earlier frame's slot
+            if f._slot != s:
+                raise RuntimeError("SweepDepth: more frames than slots (max_frames)")
+        if params.source == 1 and not keyframe.obtained_gradients_:
+            raise RuntimeError("SweepDepth: the candidate source needs ApplyGradient on the keyframe (or its slot was reused since)")
+        r = self._ctx.sweep_depth([slots[0]], [slots[1:]], poses, codes, params)
+        return r["depth"][0], r["cost"][0], r["outcome"][0], r["info"][0]
+
 
 class Map:
     """include/Map.h — Map::AddPointCloudFromRGBD (src/Map.cpp:33-45): recent_cloud_points_ is the x y z columns of the frame's
