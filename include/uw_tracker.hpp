@@ -261,7 +261,8 @@ class Tracker {
   // EstimatePose from a start pose (uwt_estimate_pose_batch_seeded; no reference counterpart: the reference always starts at the
   // identity, src/Tracker.cpp:385): _seed is the pose in front of the first evaluation, used as given — a keyframe's prediction
   // (PredictSeeds), the previous pair's pose, another stage's result.  handoff 0: the reference's level hand-off; 1: the pose crosses
-  // the levels unchanged (uwt_seed_options).
+  // the levels unchanged (uwt_seed_options).  A seed with a non-finite entry, or with |tx|, |ty| or |tz| above UWT_TRANSLATION_MAX (2^125,
+  // the range of the dense warp's division, uwt.h), is refused: the call throws with UWT_ERR_PAIR_FAILED, UWT_ERR_INVALID_ARG in last_stats_.
   void EstimatePoseSeeded(Frame* _previous_frame, Frame* _current_frame, const SE3& _seed, int32_t handoff = 0) {
     const int32_t a = bind(_previous_frame), b = bind(_current_frame);
     if (!_previous_frame->obtained_gradients_)
@@ -689,6 +690,7 @@ class Tracker {
   }
   uwt_ctx* ctx() {
     if (!ctx_) {
+      // (throws for parameters uwt_create refuses; with depth: a depth_scale whose depths leave [UWT_DEPTH_MIN, UWT_DEPTH_MAX], uwt.h)
       check(uwt_create(&params_, &ctx_), "uwt_create");
       // the per-frame sequence (upload + pyramid in bind(), ApplyGradient, EstimatePose) waits once, in EstimatePose
       check(uwt_set_deferred(ctx_, 1), "uwt_set_deferred");

@@ -20,6 +20,10 @@ extern "C" {
 #endif
 
 #define UWT_MAX_LEVELS 8
+/* The domain of the dense warp ("the dense warp's division" below): what a caller may pass.  Outside it the entries that can refuse, do. */
+#define UWT_TRANSLATION_MAX 0x1p125f   /* |tx|, |ty|, |tz| of a seed at most */
+#define UWT_DEPTH_MAX 0x1p100          /* depth_scale * 32767: the largest depth of level 0, at most */
+#define UWT_DEPTH_MIN 0x1p-100         /* depth_scale / 2^(n_levels - 1): the smallest depth of the coarsest level, at least */
 #define UWT_ABI_VERSION 4   /* 2: uwt_params::arith; 3: uwt_tuning (no environment variables are read any more); 4: any frame size
                                (uwt_level::img_w / img_h / pitch, uwt_resize_half_*) */
 
@@ -302,6 +306,47 @@ int uwt_resize_half_u8(uwt_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, u
 int uwt_resize_half_u16(uwt_ctx* ctx, const uint16_t* src, int32_t w, int32_t h, uint16_t* dst);
 /* cv::Scharr(src, dst, CV_16S, 1|0, 0|1, scale=3, 0, BORDER_DEFAULT) as used at src/Tracker.cpp:1133-1134 */
 int uwt_scharr3(uwt_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, int16_t* gx, int16_t* gy);
+/* The dense warp's division.  Every entry that walks a level's point GRID (uwt_residual_jacobian*, uwt_estimate_pose_batch*,
+ * uwt_track_batch*; not the explicit tables, the image warp or the sweep, which divide with the IEEE operator) forms the three quotients of
+ * a pixel — u' = (x' fx) / z2, v' = (y' fy) / z2 (src/Tracker.cpp:1455, :1460) and inv_z2 = 1 / z2 (:447) — from ONE hardware reciprocal:
+ *     r0 = v_rcp_f32(z2);   e = fma(-z2, r0, 1);   r = fma(e, r0, r0)                                  -> inv_z2 = r
+ *     q = n * r;   e = fma(-z2, q, n);   q = fma(e, r, q);   e = fma(-z2, q, n);   q = fma(e, r, q)     -> n / z2
+ * which is the sequence the compiler emits for the IEEE `/` without its scaling of the operands into range (div_scale / div_fixup).
+ * Where the two agree — derived from the sequence, measured by tests/test_gpu_validity.py's range cases on gfx950:
+ *   - v_rcp_f32 is accurate to 1 ulp for a normal operand with a normal result and FLUSHES subnormals on both sides: a subnormal z2 is
+ *     read as zero (r0 infinite, r = NaN), and 1 / z2 for |z2| > 2^126, a subnormal number, comes back as a zero of z2's sign.
+ *   - For 2^-126 <= |z2| <= 2^126 every step of the first line scales exactly with the exponent of z2 (r0 by 2^-k, e not at all), so r is
+ *     the same function of the mantissa at every exponent: the correctly rounded 1 / z2 for all 2^23 mantissas (checked exhaustively at
+ *     nine exponents and both signs).  inv_z2 equals the IEEE quotient on exactly that range.
+ *   - Given such an r, the second line is Markstein's correction: the result is the correctly rounded n / z2 as long as no
+ *     intermediate leaves the normal range — n = 0 (every step is an exact zero), or |n| and |n / z2| in [2^-100, 2^126]: the residuals
+ *     e are about 2^-24 |n| and must keep their bits.  A quotient that underflows against cx (|n / z2| < 2^-126: u = cx either way) is
+ *     covered by the measurement at |z2| = 2^125 and 2^126, not by the derivation.
+ *   - z2 = 0, infinite or NaN: r is NaN here and the quotients NaN, where IEEE gives infinities or NaN: the pixel fails 0 < u < cols
+ *     either way, which is all the loop asks; uwt_warp (an IEEE division) shows the reference's own values.
+ * Outside 2^-126 <= |z2| <= 2^126 the dense entries differ from the reference: for |z2| > 2^126 inv_z2 is +-0 instead of a subnormal
+ * (a pixel stays valid, its Jacobian row is zero where the reference's is about 1e-33 times the gradient, and a negative z2 leaves
+ * zeros of the other sign in the dumps of the legacy set); for a subnormal z2 the pixel is invalid where the reference's is valid.
+ * From the range to what a caller passes.  The derivation has three CONDITIONS which the library does not test:
+ *   (a) the rays are moderate: |(col - cx) / fx|, |(row - cy) / fy| <= r_max = 2^20 over the image (uwt_create does not compare the
+ *       size with the focal lengths);
+ *   (b) the rotation is one: |R_ij| <= 3, true of a quaternion of norm at most 1 + 2^-3 — a seed's quaternion is read as it is and
+ *       its norm is not tested;
+ *   (c) the bound on the translation holds for the pose in front of EVERY evaluation, not only the seed: the solver's own updates move
+ *       it, and under handoff 0 with uwt_params::handoff_scale_t = 1 the hand-off doubles t at every level boundary — a seed with
+ *       |tz| = 2^125 is 2^127 two levels further down.  There a caller keeps |t| <= 2^(125 - (first_level - last_level)).
+ * Under them |z2| <= |R20 X| + |R21 Y| + |R22 z| + |tz| <= 9 * 2^20 * z_max + |tz|, so
+ *     |tx|, |ty|, |tz| <= UWT_TRANSLATION_MAX = 2^125   and   z_max = depth_scale * 32767 <= UWT_DEPTH_MAX = 2^100
+ * give |z2| <= 9 * 2^120 + 2^125 < 2^126 (the same sum bounds x' and y'; a valid pixel has |n / z2| < cols + |cx|); and
+ *     z_min = depth_scale / 2^(n_levels - 1) >= UWT_DEPTH_MIN = 2^-100   (depth code 1 on the coarsest level; without depth z = 1)
+ * keeps every depth, every X = ray * z and every numerator that is not an exact zero normal with 24 bits to spare.  A z2 that CANCELS
+ * to a subnormal (z2 = R22 z + tz + ... within 2^-126 of zero without being zero) needs an operand below 2^-102 and is excluded by
+ * the same bounds for a pose whose translation entries are zero or at least 2^-100 in magnitude; the library does not test that either.
+ * What the library does test — two necessary conditions, not the whole domain: uwt_create refuses (UWT_ERR_INVALID_ARG) a context with
+ * has_depth != 0 whose depth_scale is not finite or, being non-zero, breaks one of the two depth bounds (both tested in double:
+ * fabs(depth_scale) * 32767 and fabs(depth_scale) / 2^(n_levels - 1)); uwt_update_params cannot change depth_scale.  A SEED whose
+ * translation exceeds UWT_TRANSLATION_MAX in magnitude fails its pair like a seed with a non-finite entry ("seeded calls" below); the
+ * pose behind the seed is not tested again.  The per-stage entries take their pose as given. */
 /* Tracker::WarpFunction(points, T, lvl) (src/Tracker.cpp:1417-1471): n x 4 in, n x 4 out */
 int uwt_warp(uwt_ctx* ctx, int32_t lvl, const float* pts, int32_t n, const float pose[7], float* warped_out);
 /* one pass of the per-point loop of EstimatePose (src/Tracker.cpp:432-490) + the reduction, for one pair at one
@@ -1262,7 +1307,8 @@ int uwt_accumulate_trajectory_device_from_async(uwt_ctx* ctx, const float* d_pos
  * seeds_or_null, sopt_or_null):
  *   - seeds_or_null null: every pair starts at the identity; with handoff 0 the results are the unseeded entry's byte for byte.
  *     sopt_or_null null: {0}.  handoff outside 0..1 or a non-zero reserved word: UWT_ERR_INVALID_ARG with nothing enqueued.
- *   - per-pair failure: a seed with a non-finite entry gives that pair alone uwt_stats {UWT_ERR_INVALID_ARG, iterations 0, n_valid 0,
+ *   - per-pair failure: a seed with a non-finite entry, or with |tx|, |ty| or |tz| above UWT_TRANSLATION_MAX (2^125: beyond it the dense
+ *     warp's division leaves the reference's arithmetic, see "the dense warp's division"), gives that pair alone uwt_stats {UWT_ERR_INVALID_ARG, iterations 0, n_valid 0,
  *     error 0} and the identity as its pose (a non-finite value is never echoed); the pair runs no evaluation, the other pairs' bits
  *     are what they are without it, and the synchronous forms return UWT_ERR_PAIR_FAILED.  The test is made on the device (device
  *     seeds are invisible to the host), in the synchronous forms too.  Every other failure is reported as in the unseeded entry.

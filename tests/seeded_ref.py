@@ -12,6 +12,7 @@ import numpy as np
 
 IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)
 ERR_INVALID_ARG, ERR_NO_VALID_POINTS = 1, 2
+TRANSLATION_MAX = np.float32(2.0 ** 125)   # include/uwt.h: UWT_TRANSLATION_MAX
 
 
 def frame_planes(O, p, gray, depth=None):
@@ -26,8 +27,10 @@ def align(O, p, ref_gray, tgt_gray, ref_depth=None, seed=None, keep=False, table
     """Tracker::EstimatePose over dense points (tables None) or explicit per-level tables ({level: n x 4}) from `seed`.
     Returns (status, pose [7] float32, trace): trace one dict per evaluation — level, iter, n_valid, error, exited, pose (the pose
     behind the evaluation's update, or the unchanged one where it exited), as oracle.align_pair's.
-    A seed with a non-finite entry: (ERR_INVALID_ARG, the identity, []) — the pair runs no evaluation."""
-    if seed is not None and not np.isfinite(np.asarray(seed, np.float32)).all():
+    A seed with a non-finite entry, or with a translation entry above UWT_TRANSLATION_MAX = 2^125 in magnitude: (ERR_INVALID_ARG, the
+    identity, []) — the pair runs no evaluation."""
+    if seed is not None and not (np.isfinite(np.asarray(seed, np.float32)).all() and
+                                 (np.abs(np.asarray(seed, np.float32).reshape(7)[4:]) <= TRANSLATION_MAX).all()):
         return ERR_INVALID_ARG, IDENTITY.copy(), []
     prev = O.set_arith(p.arith)
     try:

@@ -13,6 +13,10 @@ LIB_PATH = os.path.join(_HERE, "libuwt_hip.so")
 OK, ERR_INVALID_ARG, ERR_NO_VALID_POINTS, ERR_HIP, ERR_NO_DEVICE, ERR_CAPACITY, ERR_PAIR_FAILED = range(7)
 PLANE_IMAGE, PLANE_DEPTH, PLANE_GRADX, PLANE_GRADY = range(4)
 MAX_LEVELS = 8
+# the domain of the dense warp (include/uwt.h "the dense warp's division"): a seed's |tx|, |ty|, |tz| at most TRANSLATION_MAX or the pair
+# fails with ERR_INVALID_ARG; with depth, |depth_scale| * 32767 <= DEPTH_MAX and |depth_scale| / 2^(n_levels - 1) >= DEPTH_MIN or
+# uwt_create refuses the context
+TRANSLATION_MAX, DEPTH_MAX, DEPTH_MIN = 2.0 ** 125, 2.0 ** 100, 2.0 ** -100
 ARITH_OPENCV, ARITH_LEGACY = 0, 1   # uwt_params.arith (include/uwt.h: enum uwt_arith)
 NORM_L2, NORM_HAMMING = 0, 1        # enum uwt_norm
 MATCH_MAX_ROWS, MATCH_MAX_ROW_BYTES = 4096, 512
@@ -329,7 +333,8 @@ def seed_options(handoff=None):
 
 
 def _host_seeds(seeds, n):
-    """Host seeds as the synchronous seeded calls take them: None, or n x 7 float32"""
+    """Host seeds as the synchronous seeded calls take them: None, or n x 7 float32 (a row with a non-finite entry or a translation entry
+    above TRANSLATION_MAX in magnitude is refused by the device, for its pair alone)"""
     if seeds is None:
         return None, None
     a = np.ascontiguousarray(seeds, np.float32).reshape(-1, 7)
@@ -489,7 +494,8 @@ class Context:
 
     def __init__(self, params, tuning=None):
         """tuning: dict of uwt_tuning fields to change from their defaults (launch shapes only; the A/B tools and the tests
-        that run one form against another use it)."""
+        that run one form against another use it).  UwtError(ERR_INVALID_ARG) for parameters uwt_create refuses — with has_depth, a
+        depth_scale outside [DEPTH_MIN * 2^(n_levels - 1), DEPTH_MAX / 32767] in magnitude (zero apart) among them."""
         self.params = params
         self._h = C.c_void_p()
         st = lib().uwt_create(C.byref(params), C.byref(self._h))

@@ -1095,6 +1095,11 @@ int uwt_create(const uwt_params* p, uwt_ctx** out) {
   if (p->sampler < 0 || p->sampler > 1 || p->weights < 0 || p->weights > 2) return UWT_ERR_INVALID_ARG;
   if (p->sampler == 1 && p->weights == 1) return UWT_ERR_INVALID_ARG;  // the reference's Tukey medians are defined on integer residuals
   if (p->arith != UWT_ARITH_OPENCV && p->arith != UWT_ARITH_LEGACY) return UWT_ERR_INVALID_ARG;
+  if (p->has_depth) {   // every depth of every level inside the dense warp's domain (uwt.h "the dense warp's division")
+    const double ds = std::fabs((double)p->depth_scale);
+    if (!std::isfinite(ds)) return UWT_ERR_INVALID_ARG;
+    if (ds != 0.0 && (ds * 32767.0 > UWT_DEPTH_MAX || ds / (double)(1 << (p->n_levels - 1)) < UWT_DEPTH_MIN)) return UWT_ERR_INVALID_ARG;
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || p->device < 0 || p->device >= ndev) return UWT_ERR_NO_DEVICE;
   hipDeviceProp_t prop;

@@ -2603,8 +2603,9 @@ static __global__ __launch_bounds__(kUpdateBlock) void k_gn_update(const UpdateA
 // Where an alignment starts and how its pose crosses a level boundary (the seeded entries, uwt.h "seeded calls").
 // first_state: the state in front of the first evaluation of the first iterated level.  seeds null: the identity of
 // src/Tracker.cpp:385.  Else pair's row of seeds (7 floats qx qy qz qw tx ty tz, read as they are: nothing normalises or
-// scales them); a row with a non-finite entry starts nothing: the pair carries UWT_ERR_INVALID_ARG and the identity from
-// here on, and every launch returns at once for it (status != 0), as for any failed pair.
+// scales them); a row with a non-finite entry, or with a translation entry above 2^125 in magnitude (uwt.h:
+// UWT_TRANSLATION_MAX, the dense warp's domain), starts nothing: the pair carries UWT_ERR_INVALID_ARG and the identity
+// from here on, and every launch returns at once for it (status != 0), as for any failed pair.
 // level_handoff: scale_t 0 / 1 = the reference's hand-off (se3_handoff under uwt_params::handoff_scale_t), kHandoffKeep =
 // uwt_seed_options::handoff 1: the pose crosses unchanged.  Both sit in the block-uniform preamble and the update tail.
 // level_end: the one body of the level-end rule, for every launch form that ends a level.
@@ -2640,13 +2641,13 @@ __device__ __forceinline__ PairState first_state(const StartRec& s, int pair, bo
   PairState st = fresh_state(id, s.initial_error);
   if (s.seeds && seeded) {
     float v[7];
-    bool finite = true;
+    bool usable = true;   // every entry finite, |tx|, |ty|, |tz| <= 2^125 (bits 0x7E000000)
 #pragma unroll
     for (int k = 0; k < 7; k++) {
       v[k] = s.seeds[7 * (size_t)pair + k];
-      finite = finite && (__float_as_uint(v[k]) & 0x7f800000u) != 0x7f800000u;
+      usable = usable && (__float_as_uint(v[k]) & 0x7fffffffu) < (k < 4 ? 0x7f800000u : 0x7E000001u);
     }
-    if (finite) {
+    if (usable) {
 #pragma unroll
       for (int k = 0; k < 4; k++) st.pose.q[k] = v[k];
 #pragma unroll

@@ -59,6 +59,7 @@ class Tracker:
                     has_depth=int(self.depth_available_), device=self._device)
         over.update(self._over)
         p = capi.default_params(int(_width), int(_height), float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), **over)
+        # (UwtError for parameters uwt_create refuses; with depth: a depth_scale whose depths leave [capi.DEPTH_MIN, capi.DEPTH_MAX])
         self._ctx = capi.Context(p)
         if LS._default_ctx is None or not LS._default_ctx._h:
             LS.bind(self._ctx)                  # `LS ls;` inside the tracking loop folds on the tracker's context
@@ -123,7 +124,9 @@ class Tracker:
     def EstimatePoseSeeded(self, _previous_frame, _current_frame, seed, handoff=0):
         """EstimatePose from a start pose (uwt_estimate_pose_batch_seeded): seed = qx qy qz qw tx ty tz, the pose in front of the first
         evaluation, used as given — a keyframe's prediction (PredictSeeds), the previous pair's pose, another stage's result.
-        handoff: 0 / "reference" the reference's level hand-off, 1 / "keep" the pose crosses the levels unchanged."""
+        handoff: 0 / "reference" the reference's level hand-off, 1 / "keep" the pose crosses the levels unchanged.  A seed with a
+        non-finite entry, or with |tx|, |ty| or |tz| above capi.TRANSLATION_MAX (2^125, the range of the dense warp's division), is
+        refused: UwtError with ERR_PAIR_FAILED, ERR_INVALID_ARG in the pair's stats."""
         a, b = self._bind(_previous_frame), self._bind(_current_frame)
         if not _previous_frame.obtained_gradients_:
             raise RuntimeError("ApplyGradient(previous_frame) must run before EstimatePoseSeeded (or its slot was reused since)")
