@@ -1560,6 +1560,15 @@ int uwt_sweep_depth_batch(uwt_ctx* ctx, int32_t n_jobs, const int32_t* ref_slots
 int uwt_debug_guards(uwt_ctx* ctx, int64_t guard_bytes);
 int uwt_debug_check_guards(uwt_ctx* ctx, int64_t* damaged_bytes_out);
 
+/* uwt_debug_window_open(ctx, out): *out = 1 while the early-preparation window of the last uwt_track_batch_async /
+ * uwt_track_batch_seeded_async is open (a fixed-schedule batch call that ended on level 0, and no entry since that enqueues device
+ * work on the context stream, reads a plane back or changes a setting), else 0.  Serves tests/test_gpu_history.py, which asserts that
+ * every such entry leaves it closed.  A call refused on its arguments alone, before anything is enqueued, read back or changed
+ * (UWT_ERR_CAPACITY for n_pairs > max_pairs or a cap above UWT_MATCH_MAX_ROWS, a null argument), has not touched the context and may
+ * leave it as it was; uwt_sync and uwt_wait_ticket only wait and leave it too.  Host only: it reads one flag, enqueues nothing, waits for nothing and changes nothing.  No
+ * reference counterpart.  A null argument: UWT_ERR_INVALID_ARG. */
+int uwt_debug_window_open(const uwt_ctx* ctx, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,7 +234,7 @@ SYMBOLS = [
     "uwt_tracking_batch_seeded_async", "uwt_tracking_orb_batch_seeded_async", "uwt_predict_seeds_device_async",
     "uwt_tracking_batch_seeded", "uwt_tracking_orb_batch_seeded", "uwt_predict_seeds",
     "uwt_default_sweep_params", "uwt_sweep_hypotheses", "uwt_sweep_depth_batch_async", "uwt_sweep_depth_batch",
-    "uwt_debug_guards", "uwt_debug_check_guards",
+    "uwt_debug_guards", "uwt_debug_check_guards", "uwt_debug_window_open",
 ]
 
 _lib = None
@@ -558,6 +558,12 @@ class Context:
         n = C.c_int64(-1)
         self._chk(lib().uwt_debug_check_guards(self._h, C.byref(n)))
         return int(n.value), (lib().uwt_last_error(self._h).decode() if n.value else "")
+
+    def debug_window_open(self):
+        """Test instrumentation (uwt_debug_window_open): True while the early-preparation window of the last batch call is open."""
+        out = C.c_int32(-1)
+        self._chk(lib().uwt_debug_window_open(self._h, C.byref(out)))
+        return bool(out.value)
 
     def update_params(self, **over):
         """Change solver constants of the live context (uwt_update_params)."""

@@ -1255,6 +1255,12 @@ int uwt_debug_check_guards(uwt_ctx* c, int64_t* damaged_bytes_out) {
   return UWT_OK;
 }
 
+int uwt_debug_window_open(const uwt_ctx* c, int32_t* out) {
+  if (!c || !out) return UWT_ERR_INVALID_ARG;   // (a const context: no last_error to set)
+  *out = c->win_open ? 1 : 0;
+  return UWT_OK;
+}
+
 int uwt_destroy(uwt_ctx* c) {
   if (!c) return UWT_ERR_INVALID_ARG;
   (void)hipSetDevice(c->p.device);

@@ -308,7 +308,8 @@ int dep_wait(uwt_ctx* c, const uwt_ctx::SlotDep* ring, int next, bool dropped, h
 // Early preparation: whatever enqueues device work on the context, reads planes back or changes its settings between two batch calls
 // closes the window the first one left (uwt_ctx::win_open) — the next call is then enqueued in one piece behind it.  Called by the
 // helpers such entries pass through: compute_begin / compute_begin_pairs, upload_pairs, DevBuf::reserve / adopt on any stream but
-// the copy stream, the read-back helpers, and by the entries that pass through none of them.
+// the copy stream, the read-back helpers, and by the entries that pass through none of them.  A call refused on its arguments before it
+// reaches a helper has touched nothing and may leave the window as it was (uwt.h at uwt_debug_window_open).
 inline void close_window(uwt_ctx* c) { c->win_open = false; }
 int compute_begin(uwt_ctx* c, int first, int n);
 int compute_end(uwt_ctx* c, int first, int n);
