@@ -443,7 +443,12 @@ int uwt_robust_weights(uwt_ctx* ctx, const float* residuals, int32_t n, int32_t 
 int uwt_gradient_magnitude(uwt_ctx* ctx, int32_t slot, int32_t lvl, uint8_t* mag_out);
 /* Tracker::ObtainCandidatePoints for one level (src/Tracker.cpp:1314-1362): gradient_ > mean + threshold
  * (GRADIENT_THRESHOLD = 20, src/Options.cpp:27), x-major order; needs uwt_apply_gradient on the slot first.
- * Writes min(count, cap) points; *count_out is the full count. */
+ * Writes min(count, cap) points; *count_out is the full count.
+ * The comparison is one of doubles, strict: a cell whose magnitude equals fl(mean + threshold) is not a candidate; the mean is the
+ * integer sum of the level's img_w x img_h image (not of its pitched rows, not of the point grid) divided once.  A frame's table has
+ * at most w x h rows, and exactly that many when every cell passes (any threshold below -255 on a context without a depth plane).
+ * threshold must be finite, here and in uwt_obtain_candidate_points_batch as in the batched tracking calls: NaN or an infinity is
+ * UWT_ERR_INVALID_ARG with nothing enqueued (+-1e300 is finite: no cell, every cell). */
 int uwt_obtain_candidate_points(uwt_ctx* ctx, int32_t slot, int32_t lvl, double threshold, float* pts_out, int32_t cap,
                                 int32_t* count_out);
 /* The same for frames first_slot .. first_slot + n_frames - 1 in one call (many blocks per frame: per-column counts by
@@ -451,7 +456,13 @@ int uwt_obtain_candidate_points(uwt_ctx* ctx, int32_t slot, int32_t lvl, double 
  * f's points start at f * cap * 4), counts_out: n_frames full counts. */
 int uwt_obtain_candidate_points_batch(uwt_ctx* ctx, int32_t first_slot, int32_t n_frames, int32_t lvl, double threshold,
                                       float* pts_out, int32_t cap, int32_t* counts_out);
-/* Tracker::ObtainPatchesPoints (src/Tracker.cpp:1178-1257): 11x11 level-0 patches around <= 200 key points (x, y). */
+/* Tracker::ObtainPatchesPoints (src/Tracker.cpp:1178-1257): 11x11 level-0 patches around <= 200 key points (x, y).
+ * The key-point domain, of this entry and of every call that takes key points for patches (uwt_obtain_patch_points_batch, the
+ * uwt_estimate_pose_features_batch / uwt_track_features_batch family): 0 <= x < w and 0 <= y < h of level 0, -0.0 accepted as 0; the
+ * depth is read at ((int)y, (int)x), by truncation.  A used key point outside the domain (x == w, a negative coordinate, a NaN) is
+ * UWT_ERR_INVALID_ARG with nothing enqueued; key points past the first 200 are not looked at.  Inside the domain a patch may reach
+ * over any border: its cells with 0 < i < w and 0 < j < h are kept (column 0 and row 0 never are), from (int)(x - 5) while
+ * (float)i <= x + 5.  The depth is a signed short: 0 drops the key point, 0x8000..0xffff give a negative z. */
 int uwt_obtain_patch_points(uwt_ctx* ctx, int32_t slot, const float* keypoints_xy, int32_t n_keypoints, float* pts_out,
                             int32_t cap, int32_t* count_out);
 /* Tracker::AddPatchPointsFeatures(candidatePoints, lvl) (src/Tracker.cpp:599-629; include/Tracker.h:126; its only call,

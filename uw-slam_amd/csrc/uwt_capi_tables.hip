@@ -95,6 +95,8 @@ int uwt_obtain_candidate_points_batch(uwt_ctx* c, int32_t first_slot, int32_t n_
   if (!c || !counts_out || cap < 0 || (cap > 0 && !pts_out) || n_frames < 1 || !slot_range_ok(c, first_slot, n_frames) || lvl < 0 ||
       lvl >= c->p.n_levels)
     return fail(c, UWT_ERR_INVALID_ARG, "uwt_obtain_candidate_points_batch");
+  if (!std::isfinite(threshold))   // as the batched tracking calls (candidates_enqueue), the cloud and the sweep refuse it
+    return fail(c, UWT_ERR_INVALID_ARG, "uwt_obtain_candidate_points_batch: threshold is not finite");
   const LevelK& L = c->lv[lvl];
   const size_t rows = (size_t)L.gw * L.gh;   // a frame's table: a row for every cell of the point grid (the bound is never reached)
   // scratch: [the producer's work area | slot list | counts | tables]
