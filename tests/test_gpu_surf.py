@@ -13,7 +13,7 @@ import surf_ref as S
 ARITH_INDEPENDENT = True   # SURF has no arithmetic set
 INVALID_ARG, CAPACITY = 1, 5   # uwt_status_code (include/uwt.h)
 INTR = {(160, 96): (131.25, 131.25, 79.5, 47.5), (97, 61): (80.0, 80.0, 48.0, 30.0), (256, 240): (210.0, 210.0, 127.5, 119.5),
-        (640, 480): (525.0, 525.0, 319.5, 239.5), (735, 479): (458.654, 457.296, 367.0, 239.0)}
+        (640, 480): (525.0, 525.0, 319.5, 239.5), (735, 479): (458.654, 457.296, 367.0, 239.0), (320, 256): (262.5, 262.5, 159.5, 127.5)}
 
 
 @pytest.fixture(scope="module")
@@ -50,11 +50,14 @@ def params_of(capi, **over):
 def frame_of(name, w, h):
     if name == "blobs":
         return K.blob_image(w, h)
+    if name == "lattice":   # blobs of sigma 2 every 8 pixels, alternating in sign: 1140 raw candidates, the only list over 1024 here
+        return K.blob_image(w, h, blobs=[(x, y, 2.0, 1 if (x // 8 + y // 8) % 2 == 0 else -1) for y in range(4, h, 8) for x in range(4, w, 8)])
     return K.texture(w, h, int(name[1:]))
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("w,h,name", [(160, 96, "t3"), (97, 61, "t11"), (256, 240, "blobs"), (640, 480, "t11"), (735, 479, "t12")])
+@pytest.mark.parametrize("w,h,name", [(160, 96, "t3"), (97, 61, "t11"), (256, 240, "blobs"), (640, 480, "t11"), (735, 479, "t12"),
+                                      (320, 256, "lattice")])
 def test_gpu_sizes_equal_restatement(capi, w, h, name):
     img = frame_of(name, w, h)
     ctx = make_ctx(capi, w, h)
@@ -67,6 +70,13 @@ def test_gpu_sizes_equal_restatement(capi, w, h, name):
     assert K.same_descriptors(desc, wd) is None, K.same_descriptors(desc, wd)
     if name == "blobs":
         assert set(kp["octave"].tolist()) == {0, 1, 2, 3}
+    if name == "lattice":   # k_surf_select walks its candidates in tiles of 1024: two tiles, and the capacity cut over them
+        assert len(wk) == 1140
+        ck, cd = ctx.surf_detect_describe_batch([0], cap=1030)[0]
+        wk, wd = ref_of("lattice_320x256", img, cap=1030)
+        assert len(wk) == 1030
+        assert K.same_keypoints(ck, wk) is None, K.same_keypoints(ck, wk)
+        assert K.same_descriptors(cd, wd) is None, K.same_descriptors(cd, wd)
     ctx.close()
 
 
