@@ -24,6 +24,56 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(uwt_[a-z0-9_]+)\s*\(", src)))
 
 
+def header_prototypes():
+    """{symbol: (return type, [parameter types])} of every uwt_* declaration in include/uwt.h, as C type text without the
+    parameter names: "int32_t", "const uwt_ctx*", "float[7]"."""
+    src = open(os.path.join(ROOT, "include", "uwt.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    out = {}
+    for ret, name, params in re.findall(r"^[ \t]*([A-Za-z_][\w \t\*]*?)\s*\b(uwt_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
+        assert name not in out, name
+        types = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            m = re.fullmatch(r"\s*(.*?)\s*\b[A-Za-z_]\w*\s*((?:\[\w*\])*)\s*", p, flags=re.S)   # type, parameter name, array extents
+            assert m and m.group(1), (name, p)
+            types.append(re.sub(r"\s*\*\s*", "*", " ".join(m.group(1).split())) + m.group(2))
+        out[name] = (re.sub(r"\s*\*\s*", "*", " ".join(ret.split())), types)
+    return out
+
+
+def test_prototype_table_is_the_header(capi):
+    """capi.PROTOTYPES against include/uwt.h, entry by entry and parameter by parameter, by one fixed rule: whatever has a * or an
+    array extent is c_void_p, a scalar has the ctypes type of its exact width; a type the rule does not know fails the test.  The
+    table is what types every foreign call of the binding, so a wrong width here is a truncated pointer, capacity or stride there."""
+    import ctypes as C
+    scalars = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+    returns = dict(scalars, **{"const char*": C.c_char_p})
+
+    def ctype(text, rule, where):
+        if rule is scalars and ("*" in text or "[" in text):
+            return C.c_void_p
+        assert text in rule, "%s: the rule knows no type %r" % (where, text)
+        return rule[text]
+
+    declared = header_prototypes()
+    assert sorted(declared) == header_symbols()          # the parse misses no declaration the looser search finds
+    for name, (ret, params) in declared.items():
+        assert name in capi.PROTOTYPES, "%s: declared in include/uwt.h, not in capi.PROTOTYPES" % name
+        restype, argtypes = capi.PROTOTYPES[name]
+        assert restype is ctype(ret, returns, name + " returns"), "%s: returns %s in the header, %s in the table" % (name, ret, restype)
+        assert len(argtypes) == len(params), "%s: %d parameters in the header, %d in the table" % (name, len(params), len(argtypes))
+        for i, (text, have) in enumerate(zip(params, argtypes)):
+            want = ctype(text, scalars, "%s parameter %d" % (name, i))
+            assert have is want, "%s parameter %d: %s in the header is %s, the table has %s" % (name, i, text, want.__name__, have.__name__)
+    assert sorted(capi.PROTOTYPES) == sorted(declared)   # and nothing the header does not declare
+    lib = capi.lib()
+    for name, (restype, argtypes) in capi.PROTOTYPES.items():   # lib() has put the table on the loaded library
+        fn = getattr(lib, name)
+        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes), name
+    assert capi.ABI_VERSION == int(re.search(r"#define\s+UWT_ABI_VERSION\s+(\d+)", open(os.path.join(ROOT, "include", "uwt.h")).read()).group(1))
+
+
 def test_library_exports_every_declared_symbol(capi):
     lib = capi.lib()
     declared = header_symbols()

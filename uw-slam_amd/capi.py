@@ -112,15 +112,7 @@ class CloudParams(C.Structure):
 
 def default_cloud_params(**over):
     """uwt_default_cloud_params: {0, 100, 0, 0, 20.0}, the reference's call; keyword arguments override fields"""
-    p = CloudParams()
-    st = lib().uwt_default_cloud_params(C.byref(p))
-    if st:
-        raise UwtError(st, "uwt_default_cloud_params")
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _defaults(CloudParams(), "uwt_default_cloud_params", over)
 
 
 class SweepParams(C.Structure):
@@ -137,21 +129,13 @@ class SweepIO(C.Structure):
 
 def default_sweep_params(**over):
     """uwt_default_sweep_params: {0, 1, 20.0, 1, 32, 2, 12, 3, 4, 4, 1}; keyword arguments override fields"""
-    p = SweepParams()
-    st = lib().uwt_default_sweep_params(C.byref(p))
-    if st:
-        raise UwtError(st, "uwt_default_sweep_params")
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _defaults(SweepParams(), "uwt_default_sweep_params", over)
 
 
 def sweep_hypotheses(z_near, z_far, depth_scale, n):
     """uwt_sweep_hypotheses: n u16 depth codes uniform in inverse depth from z_near to z_far (a host helper, no context)"""
     codes = np.zeros(max(int(n), 1), np.uint16)
-    st = lib().uwt_sweep_hypotheses(C.c_double(z_near), C.c_double(z_far), C.c_double(depth_scale), int(n), _p(codes, C.c_uint16))
+    st = lib().uwt_sweep_hypotheses(z_near, z_far, depth_scale, int(n), _p(codes, C.c_uint16))
     if st:
         raise UwtError(st, "uwt_sweep_hypotheses: codes not strictly increasing, outside 1..32767, or an argument out of range")
     return codes[:n]
@@ -196,46 +180,155 @@ PAIR_STATE_DTYPE = np.dtype([("pose", "<f4", (7,)), ("last_error", "<f4"), ("err
                              ("iters", "<i4"), ("n_valid", "<i4")])
 
 
-# every symbol include/uwt.h declares (tests check the library exports all of them)
 JACOBIAN_REFERENCE, JACOBIAN_METRIC = 0, 1   # enum uwt_jacobian
 
-SYMBOLS = [
-    "uwt_abi_version", "uwt_source_id", "uwt_status_string", "uwt_last_error", "uwt_default_params", "uwt_create", "uwt_destroy",
-    "uwt_level_info", "uwt_set_frame", "uwt_upload_frames", "uwt_upload_frames_async", "uwt_host_alloc", "uwt_host_free", "uwt_plane_device_ptr", "uwt_get_plane",
-    "uwt_build_pyramids", "uwt_apply_gradient", "uwt_estimate_pose_batch", "uwt_track_batch_async", "uwt_track_batch_host_async", "uwt_wait_ticket", "uwt_sync", "uwt_set_deferred",
-    "uwt_stream", "uwt_profile_enable", "uwt_profile_read", "uwt_profile_read_levels", "uwt_profile_clock", "uwt_halve_u8", "uwt_halve_u16", "uwt_scharr3",
-    "uwt_half_size", "uwt_resize_half_u8", "uwt_resize_half_u16",
-    "uwt_warp", "uwt_residual_jacobian", "uwt_ls_accumulate", "uwt_se3_exp", "uwt_se3_mul", "uwt_se3_matrix",
-    "uwt_se3_handoff", "uwt_solve_delta", "uwt_gn_update_records", "uwt_accumulate_trajectory", "uwt_accumulate_trajectory_scan",
-    "uwt_residual_jacobian_weighted", "uwt_estimate_pose_points", "uwt_gradient_magnitude",
-    "uwt_obtain_candidate_points", "uwt_obtain_candidate_points_batch", "uwt_obtain_patch_points", "uwt_add_patch_points",
-    "uwt_ingest_create", "uwt_ingest_destroy", "uwt_ingest_maps", "uwt_ingest_undistort", "uwt_ingest_calculate_roi",
-    "uwt_ingest_frame", "uwt_update_params", "uwt_get_params", "uwt_ls_accumulate_sse", "uwt_robust_weights",
-    "uwt_get_tuning", "uwt_set_tuning", "uwt_get_jacobian", "uwt_set_jacobian",
-    "uwt_knn_match_batch", "uwt_match_descriptors_batch", "uwt_match_descriptors_batch_async",
-    "uwt_default_ransac_params", "uwt_ransac_iterations", "uwt_ransac_inliers_batch", "uwt_ransac_inliers_batch_async",
-    "uwt_obtain_patch_points_batch", "uwt_track_features_batch_async", "uwt_estimate_pose_features_batch",
-    "uwt_track_candidates_batch_async", "uwt_estimate_pose_candidates_batch",
-    "uwt_default_table_options", "uwt_track_features_batch_opt_async", "uwt_estimate_pose_features_batch_opt",
-    "uwt_track_candidates_batch_opt_async", "uwt_estimate_pose_candidates_batch_opt",
-    "uwt_default_surf_params", "uwt_keypoint_angle_deg", "uwt_surf_detect_describe_batch", "uwt_surf_detect_describe_batch_async",
-    "uwt_surf_describe_batch", "uwt_surf_integral", "uwt_surf_response_layer",
-    "uwt_default_orb_params", "uwt_orb_level_quota", "uwt_orb_default_pattern", "uwt_orb_layer_size", "uwt_orb_set_pattern",
-    "uwt_orb_detect_describe_batch", "uwt_orb_detect_describe_batch_async", "uwt_orb_describe_batch", "uwt_orb_layer",
-    "uwt_orb_fast_scores", "uwt_orb_harris",
-    "uwt_default_tracking_params", "uwt_tracking_batch_async", "uwt_tracking_batch", "uwt_match_descriptors_device_async",
-    "uwt_default_tracking_orb_params", "uwt_tracking_orb_batch_async", "uwt_tracking_orb_batch",
-    "uwt_obtain_image_transformed", "uwt_warp_image_batch_async", "uwt_warp_image_batch", "uwt_warp_mosaic",
-    "uwt_default_cloud_params", "uwt_point_cloud_batch_async", "uwt_point_cloud_batch", "uwt_point_cloud_points",
-    "uwt_accumulate_trajectory_device_async", "uwt_accumulate_trajectory_device_from_async",
-    "uwt_default_seed_options", "uwt_estimate_pose_batch_seeded", "uwt_track_batch_seeded_async",
-    "uwt_track_features_batch_seeded_async", "uwt_estimate_pose_features_batch_seeded",
-    "uwt_track_candidates_batch_seeded_async", "uwt_estimate_pose_candidates_batch_seeded",
-    "uwt_tracking_batch_seeded_async", "uwt_tracking_orb_batch_seeded_async", "uwt_predict_seeds_device_async",
-    "uwt_tracking_batch_seeded", "uwt_tracking_orb_batch_seeded", "uwt_predict_seeds",
-    "uwt_default_sweep_params", "uwt_sweep_hypotheses", "uwt_sweep_depth_batch_async", "uwt_sweep_depth_batch",
-    "uwt_debug_guards", "uwt_debug_check_guards", "uwt_debug_window_open",
-]
+ABI_VERSION = 4   # UWT_ABI_VERSION of the include/uwt.h this table was written from
+# The prototype of every entry include/uwt.h declares, in the header's order: name -> (return type, argument types).  lib() sets them
+# on the library, so a call site passes plain Python values and ctypes converts each to the width the C side reads.  Every pointer
+# or array parameter is P (it takes None, an address as an int, byref(x), a ctypes array or pointer); a scalar has its exact type.
+# tests/test_abi_cpu.py compares the table with the header, declaration by declaration.
+ci, cs, i32, i64, f32, f64, sz, P = C.c_int, C.c_char_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t, C.c_void_p
+PROTOTYPES = {
+    "uwt_default_params": (ci, (P, i32, i32, f32, f32, f32, f32)),
+    "uwt_create": (ci, (P, P)),
+    "uwt_update_params": (ci, (P, P)),
+    "uwt_get_params": (ci, (P, P)),
+    "uwt_get_tuning": (ci, (P, P)),
+    "uwt_set_tuning": (ci, (P, P)),
+    "uwt_destroy": (ci, (P,)),
+    "uwt_level_info": (ci, (P, i32, P)),
+    "uwt_status_string": (cs, (ci,)),
+    "uwt_last_error": (cs, (P,)),
+    "uwt_abi_version": (ci, ()),
+    "uwt_source_id": (cs, ()),
+    "uwt_set_frame": (ci, (P, i32, P, sz, P, sz)),
+    "uwt_upload_frames": (ci, (P, i32, i32, P, P)),
+    "uwt_upload_frames_async": (ci, (P, i32, i32, P, P)),
+    "uwt_host_alloc": (ci, (sz, P)),
+    "uwt_host_free": (ci, (P,)),
+    "uwt_plane_device_ptr": (ci, (P, i32, i32, i32, P)),
+    "uwt_get_plane": (ci, (P, i32, i32, i32, P)),
+    "uwt_build_pyramids": (ci, (P, i32, i32)),
+    "uwt_apply_gradient": (ci, (P, i32, i32)),
+    "uwt_estimate_pose_batch": (ci, (P, i32, P, P, P, P)),
+    "uwt_track_batch_async": (ci, (P, i32, i32, i32, i32, P, P, P, P)),
+    "uwt_track_batch_host_async": (ci, (P, i32, i32, i32, i32, P, P, P, P, P)),
+    "uwt_wait_ticket": (ci, (P, i64)),
+    "uwt_sync": (ci, (P,)),
+    "uwt_set_deferred": (ci, (P, i32)),
+    "uwt_stream": (ci, (P, P)),
+    "uwt_profile_enable": (ci, (P, i32)),
+    "uwt_profile_read": (ci, (P, P, P, P)),
+    "uwt_profile_read_levels": (ci, (P, P, P, i32)),
+    "uwt_profile_clock": (ci, (P, P)),
+    "uwt_halve_u8": (ci, (P, P, i32, i32, P)),
+    "uwt_halve_u16": (ci, (P, P, i32, i32, P)),
+    "uwt_half_size": (ci, (i32,)),
+    "uwt_resize_half_u8": (ci, (P, P, i32, i32, P)),
+    "uwt_resize_half_u16": (ci, (P, P, i32, i32, P)),
+    "uwt_scharr3": (ci, (P, P, i32, i32, P, P)),
+    "uwt_warp": (ci, (P, i32, P, i32, P, P)),
+    "uwt_residual_jacobian": (ci, (P, i32, i32, i32, P, P, P, P, P)),
+    "uwt_residual_jacobian_weighted": (ci, (P, i32, i32, i32, P, P, P, P, P, P, P, P)),
+    "uwt_ls_accumulate": (ci, (P, P, P, P, i32, i32, P, P, P, P)),
+    "uwt_ls_accumulate_sse": (ci, (P, P, P, P, i32, i32, i32, P, P, P, P)),
+    "uwt_se3_exp": (ci, (P, P, P)),
+    "uwt_se3_mul": (ci, (P, P, P, P)),
+    "uwt_se3_matrix": (ci, (P, P, P)),
+    "uwt_se3_handoff": (ci, (P, P, i32)),
+    "uwt_solve_delta": (ci, (P, P, P, P, P, P)),
+    "uwt_gn_update_records": (ci, (P, i32, i32, i32, i32, i32, P, P, i32, i32, i32, f32, f32, i32, P, P, P)),
+    "uwt_estimate_pose_points": (ci, (P, i32, i32, P, P, P, P)),
+    "uwt_robust_weights": (ci, (P, P, i32, i32, P, P, P)),
+    "uwt_gradient_magnitude": (ci, (P, i32, i32, P)),
+    "uwt_obtain_candidate_points": (ci, (P, i32, i32, f64, P, i32, P)),
+    "uwt_obtain_candidate_points_batch": (ci, (P, i32, i32, i32, f64, P, i32, P)),
+    "uwt_obtain_patch_points": (ci, (P, i32, P, i32, P, i32, P)),
+    "uwt_add_patch_points": (ci, (P, i32, P, i32, i32, P, i32, P)),
+    "uwt_obtain_patch_points_batch": (ci, (P, i32, P, P, P, P, i32, P)),
+    "uwt_track_features_batch_async": (ci, (P, i32, P, P, P, P, P, P)),
+    "uwt_estimate_pose_features_batch": (ci, (P, i32, P, P, P, P, P, P)),
+    "uwt_default_table_options": (ci, (P,)),
+    "uwt_track_features_batch_opt_async": (ci, (P, i32, P, P, P, P, P, P, P)),
+    "uwt_estimate_pose_features_batch_opt": (ci, (P, i32, P, P, P, P, P, P, P)),
+    "uwt_track_candidates_batch_async": (ci, (P, i32, P, P, f64, P, P)),
+    "uwt_estimate_pose_candidates_batch": (ci, (P, i32, P, P, f64, P, P)),
+    "uwt_track_candidates_batch_opt_async": (ci, (P, i32, P, P, f64, P, P, P)),
+    "uwt_estimate_pose_candidates_batch_opt": (ci, (P, i32, P, P, f64, P, P, P)),
+    "uwt_knn_match_batch": (ci, (P, i32, i32, i32, P, P, P, P, i32, P)),
+    "uwt_match_descriptors_batch": (ci, (P, i32, i32, i32, P, P, P, P, i32, f32, P, P)),
+    "uwt_match_descriptors_batch_async": (ci, (P, i32, i32, i32, P, P, P, P, i32, f32, P, P)),
+    "uwt_default_ransac_params": (ci, (P,)),
+    "uwt_ransac_iterations": (i32, (f64, i32, i32, i32)),
+    "uwt_ransac_inliers_batch": (ci, (P, i32, P, P, i32, P, P, P, P, i32, P, P, P, P, P)),
+    "uwt_ransac_inliers_batch_async": (ci, (P, i32, P, P, i32, P, P, P, P, i32, P, P, P, P, P)),
+    "uwt_default_surf_params": (ci, (P,)),
+    "uwt_keypoint_angle_deg": (f64, (f32, f32)),
+    "uwt_surf_detect_describe_batch": (ci, (P, i32, P, P, i32, P, P, P)),
+    "uwt_surf_detect_describe_batch_async": (ci, (P, i32, P, P, i32, P, P, P)),
+    "uwt_surf_describe_batch": (ci, (P, i32, P, P, P, P, i32, P, P)),
+    "uwt_surf_integral": (ci, (P, i32, P)),
+    "uwt_surf_response_layer": (ci, (P, i32, i32, i32, P, P, P)),
+    "uwt_default_orb_params": (ci, (P,)),
+    "uwt_orb_level_quota": (ci, (i32, i32, P)),
+    "uwt_orb_default_pattern": (ci, (P,)),
+    "uwt_orb_layer_size": (ci, (i32, i32, i32, P, P)),
+    "uwt_orb_set_pattern": (ci, (P, P)),
+    "uwt_orb_detect_describe_batch": (ci, (P, i32, P, P, i32, P, P, P)),
+    "uwt_orb_detect_describe_batch_async": (ci, (P, i32, P, P, i32, P, P, P)),
+    "uwt_orb_describe_batch": (ci, (P, i32, P, P, P, P, i32, P, P)),
+    "uwt_orb_layer": (ci, (P, i32, i32, P, P, P)),
+    "uwt_orb_fast_scores": (ci, (P, i32, i32, P)),
+    "uwt_orb_harris": (ci, (P, i32, i32, P, i32, P)),
+    "uwt_default_tracking_params": (ci, (P,)),
+    "uwt_tracking_batch_async": (ci, (P, i32, P, P, P, i32, P)),
+    "uwt_tracking_batch": (ci, (P, i32, P, P, P, i32, P, P, P, P, P, P, P, P)),
+    "uwt_default_tracking_orb_params": (ci, (P,)),
+    "uwt_tracking_orb_batch_async": (ci, (P, i32, P, P, P, i32, P)),
+    "uwt_tracking_orb_batch": (ci, (P, i32, P, P, P, i32, P, P, P, P, P, P, P, P)),
+    "uwt_match_descriptors_device_async": (ci, (P, i32, i32, i32, P, P, P, P, i32, f32, P, P)),
+    "uwt_obtain_image_transformed": (ci, (P, i32, i32, P, P, i32, P, P)),
+    "uwt_warp_image_batch_async": (ci, (P, i32, P, P, i32, P, P)),
+    "uwt_warp_image_batch": (ci, (P, i32, P, P, i32, P, P, P, P, P)),
+    "uwt_warp_mosaic": (ci, (P, i32, i32, i32, P, P)),
+    "uwt_default_cloud_params": (ci, (P,)),
+    "uwt_point_cloud_batch_async": (ci, (P, i32, P, P, P, P, i64, P)),
+    "uwt_point_cloud_batch": (ci, (P, i32, P, P, P, P, i64, P)),
+    "uwt_point_cloud_points": (ci, (P, i32, P, i32, P, P, P, i64, P)),
+    "uwt_ingest_create": (ci, (P, P, i32, i32, i32, i32, i32, P, P)),
+    "uwt_ingest_destroy": (ci, (P,)),
+    "uwt_ingest_maps": (ci, (P, P, P)),
+    "uwt_ingest_undistort": (ci, (P, P, sz, P)),
+    "uwt_ingest_calculate_roi": (ci, (P, P, sz, P)),
+    "uwt_ingest_frame": (ci, (P, P, i32, P, sz, i32, i32)),
+    "uwt_accumulate_trajectory": (ci, (P, P, i32, P, f32, i32, P)),
+    "uwt_accumulate_trajectory_scan": (ci, (P, P, i32, P, f32, i32, P)),
+    "uwt_accumulate_trajectory_device_async": (ci, (P, P, i32, P, f32, i32, P)),
+    "uwt_accumulate_trajectory_device_from_async": (ci, (P, P, i32, P, f32, i32, P)),
+    "uwt_default_seed_options": (ci, (P,)),
+    "uwt_estimate_pose_batch_seeded": (ci, (P, i32, P, P, P, P, P, P)),
+    "uwt_track_batch_seeded_async": (ci, (P, i32, i32, i32, i32, P, P, P, P, P, P)),
+    "uwt_track_features_batch_seeded_async": (ci, (P, i32, P, P, P, P, P, P, P, P, P)),
+    "uwt_estimate_pose_features_batch_seeded": (ci, (P, i32, P, P, P, P, P, P, P, P, P)),
+    "uwt_track_candidates_batch_seeded_async": (ci, (P, i32, P, P, f64, P, P, P, P, P)),
+    "uwt_estimate_pose_candidates_batch_seeded": (ci, (P, i32, P, P, f64, P, P, P, P, P)),
+    "uwt_tracking_batch_seeded_async": (ci, (P, i32, P, P, P, i32, P, P, P)),
+    "uwt_tracking_orb_batch_seeded_async": (ci, (P, i32, P, P, P, i32, P, P, P)),
+    "uwt_tracking_batch_seeded": (ci, (P, i32, P, P, P, i32, P, P, P, P, P, P, P, P, P, P)),
+    "uwt_tracking_orb_batch_seeded": (ci, (P, i32, P, P, P, i32, P, P, P, P, P, P, P, P, P, P)),
+    "uwt_predict_seeds_device_async": (ci, (P, i32, P, P, P)),
+    "uwt_predict_seeds": (ci, (P, i32, P, P, P)),
+    "uwt_set_jacobian": (ci, (P, i32)),
+    "uwt_get_jacobian": (ci, (P, P)),
+    "uwt_default_sweep_params": (ci, (P,)),
+    "uwt_sweep_hypotheses": (ci, (f64, f64, f64, i32, P)),
+    "uwt_sweep_depth_batch_async": (ci, (P, i32, P, P, P, P, P, P)),
+    "uwt_sweep_depth_batch": (ci, (P, i32, P, P, P, P, P, P, P, P, P)),
+    "uwt_debug_guards": (ci, (P, i64)),
+    "uwt_debug_check_guards": (ci, (P, P)),
+    "uwt_debug_window_open": (ci, (P, P)),
+}
+SYMBOLS = list(PROTOTYPES)   # every symbol include/uwt.h declares (tests check the library exports all of them)
 
 _lib = None
 
@@ -263,22 +356,22 @@ def _share_torch_hip_runtime():
 
 
 def lib():
-    """Loads libuwt_hip.so; raises if it is missing (no fallback)."""
+    """Loads libuwt_hip.so and sets PROTOTYPES on it; raises if it is missing (no fallback) or was built from another ABI version."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ImportError("libuwt_hip.so not built at %s — run __graft_entry__.build()" % LIB_PATH)
         _share_torch_hip_runtime()
-        _lib = C.CDLL(LIB_PATH)
-        _lib.uwt_status_string.restype = C.c_char_p
-        _lib.uwt_last_error.restype = C.c_char_p
-        _lib.uwt_source_id.restype = C.c_char_p
-        _lib.uwt_source_id.argtypes = []
-        _lib.uwt_last_error.argtypes = [C.c_void_p]
-        _lib.uwt_ransac_iterations.restype = C.c_int32
-        _lib.uwt_ransac_iterations.argtypes = [C.c_double, C.c_int32, C.c_int32, C.c_int32]
-        _lib.uwt_keypoint_angle_deg.restype = C.c_double
-        _lib.uwt_keypoint_angle_deg.argtypes = [C.c_float, C.c_float]
+        loaded = C.CDLL(LIB_PATH)
+        stale = [name for name in PROTOTYPES if not hasattr(loaded, name)]
+        version = None if stale else loaded.uwt_abi_version()
+        if version != ABI_VERSION:
+            raise ImportError("libuwt_hip.so at %s is stale (%s; this binding is written for ABI version %d) — rebuild it: run "
+                              "__graft_entry__.build()" % (LIB_PATH, "no " + stale[0] if stale else "ABI version %d" % version, ABI_VERSION))
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(loaded, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = loaded
     return _lib
 
 
@@ -291,29 +384,39 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _ref(rec):
+    """byref of an optional record: None stays None (NULL, the entry's defaults)"""
+    return None if rec is None else C.byref(rec)
+
+
 DEFAULT_ARITH = None   # None: the library's default (ARITH_OPENCV); the parity suite sets it to run every test under both sets
 
 
-def default_params(width, height, fx, fy, cx, cy, **over):
-    p = Params()
-    st = lib().uwt_default_params(C.byref(p), width, height, C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy))
-    if st:
-        raise UwtError(st, "uwt_default_params")
-    if DEFAULT_ARITH is not None:
-        p.arith = DEFAULT_ARITH
+def _set_fields(rec, over):
     for k, v in over.items():
-        if not hasattr(p, k):
+        if not hasattr(rec, k):
             raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+        setattr(rec, k, v)
+
+
+def _defaults(rec, entry, over=None, *args):
+    """rec as the library's uwt_default_* entry fills it (args: what the entry takes besides the record), then the fields in over set"""
+    st = getattr(lib(), entry)(C.byref(rec), *args)
+    if st:
+        raise UwtError(st, entry)
+    _set_fields(rec, over or {})
+    return rec
+
+
+def default_params(width, height, fx, fy, cx, cy, **over):
+    if DEFAULT_ARITH is not None:
+        over = {"arith": DEFAULT_ARITH, **over}
+    return _defaults(Params(), "uwt_default_params", over, width, height, fx, fy, cx, cy)
 
 
 def table_options(weights=None, sampler=None):
     """uwt_default_table_options ({0, 0}) with the given fields set"""
-    o = TableOptions()
-    st = lib().uwt_default_table_options(C.byref(o))
-    if st:
-        raise UwtError(st, "uwt_default_table_options")
+    o = _defaults(TableOptions(), "uwt_default_table_options")
     if weights is not None:
         o.weights = weights
     if sampler is not None:
@@ -323,10 +426,7 @@ def table_options(weights=None, sampler=None):
 
 def seed_options(handoff=None):
     """uwt_default_seed_options ({0}) with the hand-off set (HANDOFF_REFERENCE / HANDOFF_KEEP, or "reference" / "keep")"""
-    o = SeedOptions()
-    st = lib().uwt_default_seed_options(C.byref(o))
-    if st:
-        raise UwtError(st, "uwt_default_seed_options")
+    o = _defaults(SeedOptions(), "uwt_default_seed_options")
     if handoff is not None:
         o.handoff = {"reference": HANDOFF_REFERENCE, "keep": HANDOFF_KEEP}.get(handoff, handoff)
     return o
@@ -349,43 +449,41 @@ def _sopt(handoff):
     return None if handoff is None else C.byref(seed_options(handoff))
 
 
+def _pair_lists(ref_slots, tgt_slots):
+    """The reference and the target slots of a batch call as flat int32 arrays"""
+    return np.ascontiguousarray(ref_slots, np.int32).reshape(-1), np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
+
+
+def _result_buffers(n):
+    """Host room for the results of n pairs, never of size zero: poses [n, 7] float32 and n uwt_stats"""
+    return np.empty((max(n, 1), 7), np.float32), (Stats * max(n, 1))()
+
+
+def _accum_fields(acc):
+    """A uwt_accum as the residual calls return it: A the full 6 x 6 matrix of the upper triangle the record holds row by row"""
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = acc.A   # (0, 0), (0, 1) .. (0, 5), (1, 1) .. (5, 5)
+    A += np.triu(A, 1).T
+    return dict(A=A, jtr=np.array(acc.jtr), sum_r2=int(acc.sum_r2), n_valid=int(acc.n_valid))
+
+
+def _stats_list(stats, n):
+    return [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:n]]
+
+
 def default_ransac_params(**over):
     """uwt_default_ransac_params: distance 3.0, confidence 0.99, max_hypotheses 1000, seed 0"""
-    p = RansacParams()
-    st = lib().uwt_default_ransac_params(C.byref(p))
-    if st:
-        raise UwtError(st, "uwt_default_ransac_params")
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _defaults(RansacParams(), "uwt_default_ransac_params", over)
 
 
 def default_surf_params(**over):
     """uwt_default_surf_params: hessian_threshold 100, n_octaves 4, n_octave_layers 2, upright 0"""
-    p = SurfParams()
-    st = lib().uwt_default_surf_params(C.byref(p))
-    if st:
-        raise UwtError(st, "uwt_default_surf_params")
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _defaults(SurfParams(), "uwt_default_surf_params", over)
 
 
 def default_orb_params(**over):
     """uwt_default_orb_params: n_features 500, n_levels 8, edge_threshold 31, fast_threshold 20, upright 0"""
-    p = OrbParams()
-    st = lib().uwt_default_orb_params(C.byref(p))
-    if st:
-        raise UwtError(st, "uwt_default_orb_params")
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _defaults(OrbParams(), "uwt_default_orb_params", over)
 
 
 def orb_level_quota(n_features, n_levels):
@@ -415,34 +513,28 @@ def orb_layer_size(w, h, level):
     return lw.value, lh.value
 
 
-def _tracking_params(p, fn, name, detector, detector_over, ransac, over):
-    st = fn(C.byref(p))
-    if st:
-        raise UwtError(st, name)
+def _tracking_params(p, entry, detector, detector_over, ransac, over):
+    _defaults(p, entry)
     for rec, d in ((getattr(p, detector), detector_over or {}), (p.ransac, ransac or {}), (p, over)):
-        for k, v in d.items():
-            if not hasattr(rec, k):
-                raise AttributeError(k)
-            setattr(rec, k, v)
+        _set_fields(rec, d)
     return p
 
 
 def default_tracking_params(surf=None, ransac=None, **over):
     """uwt_default_tracking_params: the SURF and RANSAC defaults, ratio 0.65, min_matches 110.  surf / ransac: dicts of fields of the
     nested records to change; the other keywords are fields of the record itself."""
-    return _tracking_params(TrackingParams(), lib().uwt_default_tracking_params, "uwt_default_tracking_params", "surf", surf, ransac, over)
+    return _tracking_params(TrackingParams(), "uwt_default_tracking_params", "surf", surf, ransac, over)
 
 
 def default_tracking_orb_params(orb=None, ransac=None, **over):
     """uwt_default_tracking_orb_params: the ORB and RANSAC defaults, ratio 0.65, min_matches 110; orb / ransac / the other keywords as
     in default_tracking_params."""
-    return _tracking_params(TrackingOrbParams(), lib().uwt_default_tracking_orb_params, "uwt_default_tracking_orb_params", "orb", orb,
-                            ransac, over)
+    return _tracking_params(TrackingOrbParams(), "uwt_default_tracking_orb_params", "orb", orb, ransac, over)
 
 
 def keypoint_angle_deg(dir_x, dir_y):
     """uwt_keypoint_angle_deg: cv::KeyPoint::angle of a key point's direction, degrees in [0, 360), on the host"""
-    return float(lib().uwt_keypoint_angle_deg(C.c_float(dir_x), C.c_float(dir_y)))
+    return float(lib().uwt_keypoint_angle_deg(dir_x, dir_y))
 
 
 def ransac_iterations(confidence, n, inliers, max_hypotheses):
@@ -455,7 +547,7 @@ class _Pinned:
 
     def __init__(self, nbytes):
         self.ptr = C.c_void_p()
-        st = lib().uwt_host_alloc(C.c_size_t(nbytes), C.byref(self.ptr))
+        st = lib().uwt_host_alloc(nbytes,C.byref(self.ptr))
         if st:
             raise UwtError(st, "uwt_host_alloc(%d)" % nbytes)
 
@@ -529,7 +621,7 @@ class Context:
         """uwt_set_jacobian: 0 / "reference" the reference's Jw (pixel coordinates in columns 2..5; the default), 1 / "metric" the
         3-D point's coordinates.  Applies to every later call that forms a Jacobian; metric is meant to run with handoff "keep"."""
         mode = {"reference": JACOBIAN_REFERENCE, "metric": JACOBIAN_METRIC}.get(mode, mode)
-        self._chk(lib().uwt_set_jacobian(self._h, C.c_int32(int(mode))))
+        self._chk(lib().uwt_set_jacobian(self._h, int(mode)))
 
     def close(self):
         if self._h:
@@ -547,10 +639,14 @@ class Context:
             raise UwtError(st, lib().uwt_last_error(self._h).decode())
         return st
 
+    def _chk_pairs(self, st, raise_on_pair_failure):
+        """_chk for a batch call: ERR_PAIR_FAILED (some pair's status says why) passes unless asked to raise"""
+        return self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+
     def debug_guards(self, guard_bytes):
         """Test instrumentation (uwt_debug_guards): guard gaps of guard_bytes around and inside every growable scratch block of the
         context from now on; 0 turns them off.  Waits for the context's work and releases the blocks."""
-        self._chk(lib().uwt_debug_guards(self._h, C.c_int64(int(guard_bytes))))
+        self._chk(lib().uwt_debug_guards(self._h, int(guard_bytes)))
 
     def debug_check_guards(self):
         """(damaged bytes, the library's description of the first damaged gap or "") over the gaps of every block's last use
@@ -569,10 +665,7 @@ class Context:
         """Change solver constants of the live context (uwt_update_params)."""
         p = Params()
         self._chk(lib().uwt_get_params(self._h, C.byref(p)))
-        for k, v in over.items():
-            if not hasattr(p, k):
-                raise AttributeError(k)
-            setattr(p, k, v)
+        _set_fields(p, over)
         self._chk(lib().uwt_update_params(self._h, C.byref(p)))
         self.params = p
 
@@ -590,7 +683,7 @@ class Context:
             depth = np.asarray(depth)
             assert depth.dtype == np.uint16 and depth.shape == (self.h, self.w) and depth.strides[1] == 2
             dp, ds = _p(depth, C.c_uint16), depth.strides[0]
-        self._chk(lib().uwt_set_frame(self._h, slot, _p(gray, C.c_uint8), C.c_size_t(gray.strides[0]), dp, C.c_size_t(ds)))
+        self._chk(lib().uwt_set_frame(self._h, slot, _p(gray, C.c_uint8), gray.strides[0], dp, ds))
 
     def upload_frames(self, first_slot, gray, depth=None):
         gray = np.ascontiguousarray(gray, np.uint8)
@@ -631,51 +724,40 @@ class Context:
 
     # -- tracking
     def estimate_pose_batch(self, ref_slots, tgt_slots, raise_on_pair_failure=False):
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         n = ref.size
-        poses = np.empty((n, 7), np.float32)
-        stats = (Stats * n)()
+        poses, stats = _result_buffers(n)
         st = lib().uwt_estimate_pose_batch(self._h, n, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(poses, C.c_float), stats)
-        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
-        return poses, [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats]
+        self._chk_pairs(st, raise_on_pair_failure)
+        return poses[:n], _stats_list(stats, n)
 
     def track_batch_async(self, first_slot, n_frames, ref_slots, tgt_slots, d_poses_ptr, d_stats_ptr=None, grad_refs_only=True):
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         self._chk(lib().uwt_track_batch_async(self._h, first_slot, n_frames, int(grad_refs_only), ref.size, _p(ref, C.c_int32),
-                                              _p(tgt, C.c_int32), C.c_void_p(d_poses_ptr),
-                                              C.c_void_p(d_stats_ptr) if d_stats_ptr else None))
+                                              _p(tgt, C.c_int32), d_poses_ptr, d_stats_ptr))
 
     def estimate_pose_batch_seeded(self, ref_slots, tgt_slots, seeds=None, handoff=None, raise_on_pair_failure=False):
         """estimate_pose_batch from start poses (uwt_estimate_pose_batch_seeded): seeds None (the identity) or [P, 7] float32 host
         poses; handoff: None / 0 / "reference", 1 / "keep", or a SeedOptions."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         n = ref.size
-        poses = np.empty((n, 7), np.float32)
-        stats = (Stats * n)()
+        poses, stats = _result_buffers(n)
         keep, sp = _host_seeds(seeds, n)
-        st = lib().uwt_estimate_pose_batch_seeded(self._h, n, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(poses, C.c_float), stats, sp,
-                                                  _sopt(handoff))
-        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
-        return poses, [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats]
+        st = lib().uwt_estimate_pose_batch_seeded(self._h, n, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(poses, C.c_float), stats, sp, _sopt(handoff))
+        self._chk_pairs(st, raise_on_pair_failure)
+        return poses[:n], _stats_list(stats, n)
 
     def track_batch_seeded_async(self, first_slot, n_frames, ref_slots, tgt_slots, d_poses_ptr, d_stats_ptr=None, grad_refs_only=True,
                                  d_seeds_ptr=None, handoff=None):
         """track_batch_async from seeds in device memory (uwt_track_batch_seeded_async): d_seeds_ptr None or P x 7 float32, e.g. the
         pose buffer of a call enqueued before, no wait between; it may overlap no output of this call."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         self._chk(lib().uwt_track_batch_seeded_async(self._h, first_slot, n_frames, int(grad_refs_only), ref.size, _p(ref, C.c_int32),
-                                                     _p(tgt, C.c_int32), C.c_void_p(d_poses_ptr),
-                                                     C.c_void_p(d_stats_ptr) if d_stats_ptr else None,
-                                                     C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+                                                     _p(tgt, C.c_int32), d_poses_ptr, d_stats_ptr, d_seeds_ptr, _sopt(handoff)))
 
     def predict_seeds_device_async(self, n, d_prev_ptr, d_cur_ptr, d_seed_ptr):
         """uwt_predict_seeds_device_async: seed = (cur * prev^-1) * cur per row, n x 7 float32 each in device memory, no wait."""
-        self._chk(lib().uwt_predict_seeds_device_async(self._h, int(n), C.c_void_p(d_prev_ptr), C.c_void_p(d_cur_ptr),
-                                                       C.c_void_p(d_seed_ptr)))
+        self._chk(lib().uwt_predict_seeds_device_async(self._h, int(n), d_prev_ptr, d_cur_ptr, d_seed_ptr))
 
     def predict_seeds(self, prev, cur):
         """uwt_predict_seeds: the constant-velocity seeds (cur * prev^-1) * cur of host poses [n, 7], computed on the device"""
@@ -689,17 +771,15 @@ class Context:
 
     def track_batch_host_async(self, first_slot, n_frames, ref_slots, tgt_slots, h_poses, h_stats=None, grad_refs_only=True):
         """h_poses: pinned float32 [n, 7]; h_stats: pinned int32 [n, 4] or None.  Returns the ticket for wait_ticket()."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         t = C.c_int64()
         self._chk(lib().uwt_track_batch_host_async(self._h, first_slot, n_frames, int(grad_refs_only), ref.size, _p(ref, C.c_int32),
                                                    _p(tgt, C.c_int32), _p(h_poses, C.c_float),
-                                                   h_stats.ctypes.data_as(C.c_void_p) if h_stats is not None else None,
-                                                   C.byref(t)))
+                                                   h_stats.ctypes.data if h_stats is not None else None, C.byref(t)))
         return t.value
 
     def wait_ticket(self, ticket):
-        self._chk(lib().uwt_wait_ticket(self._h, C.c_int64(ticket)))
+        self._chk(lib().uwt_wait_ticket(self._h, ticket))
 
     def sync(self):
         self._chk(lib().uwt_sync(self._h))
@@ -736,34 +816,26 @@ class Context:
         return ghz.value
 
     # -- per-stage entry points
-    def halve_u8(self, img):
-        img = np.ascontiguousarray(img, np.uint8)
+    def _half(self, fn, img, dtype, size):
+        """One of the four halving entries: img as dtype, out of size(h) x size(w)"""
+        img = np.ascontiguousarray(img, dtype)
         h, w = img.shape
-        out = np.empty((h // 2, w // 2), np.uint8)
-        self._chk(lib().uwt_halve_u8(self._h, _p(img, C.c_uint8), w, h, _p(out, C.c_uint8)))
+        out = np.empty((size(h), size(w)), dtype)
+        self._chk(fn(self._h, img.ctypes.data, w, h, out.ctypes.data))
         return out
 
+    def halve_u8(self, img):
+        return self._half(lib().uwt_halve_u8, img, np.uint8, lambda n: n // 2)
+
     def halve_u16(self, img):
-        img = np.ascontiguousarray(img, np.uint16)
-        h, w = img.shape
-        out = np.empty((h // 2, w // 2), np.uint16)
-        self._chk(lib().uwt_halve_u16(self._h, _p(img, C.c_uint16), w, h, _p(out, C.c_uint16)))
-        return out
+        return self._half(lib().uwt_halve_u16, img, np.uint16, lambda n: n // 2)
 
     def resize_half_u8(self, img):
         """cv::resize(img, Size(), 0.5, 0.5) on any size."""
-        img = np.ascontiguousarray(img, np.uint8)
-        h, w = img.shape
-        out = np.empty((lib().uwt_half_size(h), lib().uwt_half_size(w)), np.uint8)
-        self._chk(lib().uwt_resize_half_u8(self._h, _p(img, C.c_uint8), w, h, _p(out, C.c_uint8)))
-        return out
+        return self._half(lib().uwt_resize_half_u8, img, np.uint8, lib().uwt_half_size)
 
     def resize_half_u16(self, img):
-        img = np.ascontiguousarray(img, np.uint16)
-        h, w = img.shape
-        out = np.empty((lib().uwt_half_size(h), lib().uwt_half_size(w)), np.uint16)
-        self._chk(lib().uwt_resize_half_u16(self._h, _p(img, C.c_uint16), w, h, _p(out, C.c_uint16)))
-        return out
+        return self._half(lib().uwt_resize_half_u16, img, np.uint16, lib().uwt_half_size)
 
     def scharr3(self, img):
         img = np.ascontiguousarray(img, np.uint8)
@@ -791,29 +863,15 @@ class Context:
         self._chk(lib().uwt_residual_jacobian(self._h, ref_slot, tgt_slot, lvl, _p(pose, C.c_float), C.byref(acc),
                                               _p(J, C.c_float) if dump else None, _p(r, C.c_float) if dump else None,
                                               _p(v, C.c_uint8) if dump else None))
-        A = np.zeros((6, 6))
-        s = 0
-        for i in range(6):
-            for j in range(i, 6):
-                A[i, j] = A[j, i] = acc.A[s]
-                s += 1
-        return dict(A=A, jtr=np.array(acc.jtr), sum_r2=int(acc.sum_r2), n_valid=int(acc.n_valid), J=J, r=r, valid=v)
+        return dict(_accum_fields(acc), J=J, r=r, valid=v)
 
     def ls_accumulate(self, J, r, w=None, divide=False):
-        J = np.ascontiguousarray(J, np.float32)
-        r = np.ascontiguousarray(r, np.float32)
-        A = np.empty(36, np.float32)
-        b = np.empty(6, np.float32)
-        err, cnt = C.c_float(), C.c_int32()
-        wp = None
-        if w is not None:
-            w = np.ascontiguousarray(w, np.float32)
-            wp = _p(w, C.c_float)
-        self._chk(lib().uwt_ls_accumulate(self._h, _p(J, C.c_float), _p(r, C.c_float), wp, r.size, int(divide),
-                                          _p(A, C.c_float), _p(b, C.c_float), C.byref(err), C.byref(cnt)))
-        return A.reshape(6, 6), b, err.value, cnt.value
+        return self._ls_accumulate(lib().uwt_ls_accumulate, J, r, w, divide)
 
     def ls_accumulate_sse(self, J, r, w=None, divide=False, count_quirk=True):
+        return self._ls_accumulate(lib().uwt_ls_accumulate_sse, J, r, w, divide, int(count_quirk))
+
+    def _ls_accumulate(self, fn, J, r, w, divide, *quirk):
         J = np.ascontiguousarray(J, np.float32)
         r = np.ascontiguousarray(r, np.float32)
         A = np.empty(36, np.float32)
@@ -823,8 +881,8 @@ class Context:
         if w is not None:
             w = np.ascontiguousarray(w, np.float32)
             wp = _p(w, C.c_float)
-        self._chk(lib().uwt_ls_accumulate_sse(self._h, _p(J, C.c_float), _p(r, C.c_float), wp, r.size, int(divide),
-                                              int(count_quirk), _p(A, C.c_float), _p(b, C.c_float), C.byref(err), C.byref(cnt)))
+        self._chk(fn(self._h, _p(J, C.c_float), _p(r, C.c_float), wp, r.size, int(divide), *quirk, _p(A, C.c_float), _p(b, C.c_float),
+                     C.byref(err), C.byref(cnt)))
         return A.reshape(6, 6), b, err.value, cnt.value
 
     def se3_exp(self, xi):
@@ -876,7 +934,7 @@ class Context:
         active = C.c_int32(-1)
         self._chk(lib().uwt_gn_update_records(self._h, int(form), rows - int(pair_base), int(pair_base), stride, int(count),
                                               _p(records, C.c_uint32), states.ctypes.data_as(C.POINTER(PairState)), int(k), int(max_iters),
-                                              int(early_exit), C.c_float(epsilon), C.c_float(gain), int(general),
+                                              int(early_exit), epsilon, gain, int(general),
                                               out.ctypes.data_as(C.POINTER(PairState)), C.byref(active), _p(tickets, C.c_uint32)))
         return out, active.value, tickets
 
@@ -886,8 +944,8 @@ class Context:
         start = np.array([0, 0, 0, 1, 0, 0, 0], np.float32) if start is None else np.ascontiguousarray(start, np.float32)
         out = np.empty_like(poses)
         fn = lib().uwt_accumulate_trajectory_scan if scan else lib().uwt_accumulate_trajectory
-        self._chk(fn(self._h, _p(poses, C.c_float), poses.shape[0], _p(start, C.c_float), C.c_float(t_scale),
-                     int(bool(reference_axes)), _p(out, C.c_float)))
+        self._chk(fn(self._h, _p(poses, C.c_float), poses.shape[0], _p(start, C.c_float), t_scale, int(bool(reference_axes)),
+                     _p(out, C.c_float)))
         return out
 
     def estimate_pose_points(self, ref_slot, tgt_slot, tables):
@@ -905,7 +963,7 @@ class Context:
         st = Stats()
         rc = lib().uwt_estimate_pose_points(self._h, ref_slot, tgt_slot, ptrs, counts, _p(pose, C.c_float), C.byref(st))
         self._chk(rc, allow=(ERR_PAIR_FAILED,))
-        return pose, dict(status=st.status, iterations=st.iterations, n_valid=st.n_valid, error=st.error)
+        return pose, _stats_list([st], 1)[0]
 
     def robust_weights(self, residuals, kind=1, want_weights=True):
         """MedianMat / MedianAbsoluteDeviation / IdentityWeights (kind 0) / TukeyFunctionWeights (kind 1) of an N x 1 vector.
@@ -928,8 +986,7 @@ class Context:
         cap = L.w * L.h if cap is None else cap
         pts = np.empty((max(cap, 1), 4), np.float32)
         cnt = C.c_int32()
-        self._chk(lib().uwt_obtain_candidate_points(self._h, slot, lvl, C.c_double(threshold), _p(pts, C.c_float), cap,
-                                                    C.byref(cnt)))
+        self._chk(lib().uwt_obtain_candidate_points(self._h, slot, lvl, threshold, _p(pts, C.c_float), cap, C.byref(cnt)))
         return pts[:min(cnt.value, cap)].copy(), cnt.value
 
     def obtain_candidate_points_batch(self, first_slot, n_frames, lvl, threshold=20.0, cap=None):
@@ -938,8 +995,8 @@ class Context:
         cap = L.w * L.h if cap is None else cap
         pts = np.empty((n_frames, max(cap, 1), 4), np.float32)
         cnt = np.zeros(n_frames, np.int32)
-        self._chk(lib().uwt_obtain_candidate_points_batch(self._h, first_slot, n_frames, lvl, C.c_double(threshold), _p(pts, C.c_float),
-                                                          cap, _p(cnt, C.c_int32)))
+        self._chk(lib().uwt_obtain_candidate_points_batch(self._h, first_slot, n_frames, lvl, threshold, _p(pts, C.c_float), cap,
+                                                          _p(cnt, C.c_int32)))
         return [pts[f, :min(int(cnt[f]), cap)].copy() for f in range(n_frames)], cnt
 
     def obtain_patch_points(self, slot, keypoints, cap=200 * 144):
@@ -973,98 +1030,79 @@ class Context:
                                                       _p(pts, C.c_float), cap, _p(cnt, C.c_int32)))
         return [pts[f, :min(int(cnt[f]), cap)].copy() for f in range(sl.size)], cnt[:sl.size]
 
+    @staticmethod
+    def _table_entry(plain, opt, weights, sampler):
+        """(entry, its options argument) of a table tracker: the plain entry and no argument when neither weights nor sampler is
+        given, else the _opt entry and the uwt_table_options of the two"""
+        if weights is None and sampler is None:
+            return plain, ()
+        return opt, (C.byref(table_options(weights, sampler)),)
+
     def estimate_pose_features_batch(self, ref_slots, tgt_slots, keypoints_list, raise_on_pair_failure=False, weights=None,
                                      sampler=None):
         """System::Tracking's live call for many pairs: keypoints_list[i] are the key points of the frame in ref_slots[i].
         weights / sampler (either given): the call's own robust weights and sampler, uwt_estimate_pose_features_batch_opt.
         Returns (poses [P, 7], per-pair stats)."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         kp, n = self._keypoint_block(keypoints_list)
-        poses = np.empty((ref.size, 7), np.float32)
-        stats = (Stats * max(ref.size, 1))()
-        if weights is None and sampler is None:
-            st = lib().uwt_estimate_pose_features_batch(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
-                                                        _p(n, C.c_int32), _p(poses, C.c_float), stats)
-        else:
-            opt = table_options(weights, sampler)
-            st = lib().uwt_estimate_pose_features_batch_opt(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
-                                                            _p(n, C.c_int32), C.byref(opt), _p(poses, C.c_float), stats)
-        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
-        return poses, [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
+        poses, stats = _result_buffers(ref.size)
+        fn, opt = self._table_entry(lib().uwt_estimate_pose_features_batch, lib().uwt_estimate_pose_features_batch_opt, weights, sampler)
+        st = fn(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float), _p(n, C.c_int32), *opt, _p(poses, C.c_float), stats)
+        self._chk_pairs(st, raise_on_pair_failure)
+        return poses[:ref.size], _stats_list(stats, ref.size)
 
     def track_features_batch_async(self, ref_slots, tgt_slots, keypoints_list, d_poses_ptr, d_stats_ptr=None, weights=None,
                                    sampler=None):
         """The same enqueued on the context stream, results in device memory (d_poses_ptr: P x 7 float32, d_stats_ptr: P x 4
         int32-sized uwt_stats or None); sync() to wait."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         kp, n = self._keypoint_block(keypoints_list)
-        d_stats = C.c_void_p(d_stats_ptr) if d_stats_ptr else None
-        if weights is None and sampler is None:
-            self._chk(lib().uwt_track_features_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
-                                                           _p(n, C.c_int32), C.c_void_p(d_poses_ptr), d_stats))
-        else:
-            opt = table_options(weights, sampler)
-            self._chk(lib().uwt_track_features_batch_opt_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
-                                                               _p(kp, C.c_float), _p(n, C.c_int32), C.byref(opt),
-                                                               C.c_void_p(d_poses_ptr), d_stats))
+        fn, opt = self._table_entry(lib().uwt_track_features_batch_async, lib().uwt_track_features_batch_opt_async, weights, sampler)
+        self._chk(fn(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float), _p(n, C.c_int32), *opt, d_poses_ptr, d_stats_ptr))
 
     def estimate_pose_features_batch_seeded(self, ref_slots, tgt_slots, keypoints_list, seeds=None, handoff=None, weights=None,
                                             sampler=None, raise_on_pair_failure=False):
         """estimate_pose_features_batch from start poses (uwt_estimate_pose_features_batch_seeded; seeds, handoff: as
         estimate_pose_batch_seeded)."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         kp, n = self._keypoint_block(keypoints_list)
-        poses = np.empty((max(ref.size, 1), 7), np.float32)
-        stats = (Stats * max(ref.size, 1))()
-        opt = table_options(weights, sampler)
+        poses, stats = _result_buffers(ref.size)
         keep, sp = _host_seeds(seeds, ref.size)
         st = lib().uwt_estimate_pose_features_batch_seeded(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
-                                                           _p(n, C.c_int32), C.byref(opt), _p(poses, C.c_float), stats, sp,
-                                                           _sopt(handoff))
-        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
-        return poses[:ref.size], [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
+                                                           _p(n, C.c_int32), C.byref(table_options(weights, sampler)),
+                                                           _p(poses, C.c_float), stats, sp, _sopt(handoff))
+        self._chk_pairs(st, raise_on_pair_failure)
+        return poses[:ref.size], _stats_list(stats, ref.size)
 
     def track_features_batch_seeded_async(self, ref_slots, tgt_slots, keypoints_list, d_poses_ptr, d_stats_ptr=None, d_seeds_ptr=None,
                                           handoff=None, weights=None, sampler=None):
         """track_features_batch_async from seeds in device memory (uwt_track_features_batch_seeded_async)."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         kp, n = self._keypoint_block(keypoints_list)
-        opt = table_options(weights, sampler)
         self._chk(lib().uwt_track_features_batch_seeded_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _p(kp, C.c_float),
-                                                              _p(n, C.c_int32), C.byref(opt), C.c_void_p(d_poses_ptr),
-                                                              C.c_void_p(d_stats_ptr) if d_stats_ptr else None,
-                                                              C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+                                                              _p(n, C.c_int32), C.byref(table_options(weights, sampler)), d_poses_ptr,
+                                                              d_stats_ptr, d_seeds_ptr, _sopt(handoff)))
 
     def estimate_pose_candidates_batch_seeded(self, ref_slots, tgt_slots, seeds=None, handoff=None, threshold=20.0, weights=None,
                                               sampler=None, raise_on_pair_failure=False):
         """estimate_pose_candidates_batch from start poses (uwt_estimate_pose_candidates_batch_seeded); the weights and the sampler
         are the call's, as in the _opt entry."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
-        poses = np.empty((max(ref.size, 1), 7), np.float32)
-        stats = (Stats * max(ref.size, 1))()
-        opt = table_options(weights, sampler)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
+        poses, stats = _result_buffers(ref.size)
         keep, sp = _host_seeds(seeds, ref.size)
-        st = lib().uwt_estimate_pose_candidates_batch_seeded(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
-                                                             C.c_double(threshold), C.byref(opt), _p(poses, C.c_float), stats, sp,
+        st = lib().uwt_estimate_pose_candidates_batch_seeded(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), threshold,
+                                                             C.byref(table_options(weights, sampler)), _p(poses, C.c_float), stats, sp,
                                                              _sopt(handoff))
-        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
-        return poses[:ref.size], [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
+        self._chk_pairs(st, raise_on_pair_failure)
+        return poses[:ref.size], _stats_list(stats, ref.size)
 
     def track_candidates_batch_seeded_async(self, ref_slots, tgt_slots, d_poses_ptr, d_stats_ptr=None, d_seeds_ptr=None, handoff=None,
                                             threshold=20.0, weights=None, sampler=None):
         """track_candidates_batch_async from seeds in device memory (uwt_track_candidates_batch_seeded_async)."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
-        opt = table_options(weights, sampler)
-        self._chk(lib().uwt_track_candidates_batch_seeded_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
-                                                                C.c_double(threshold), C.byref(opt), C.c_void_p(d_poses_ptr),
-                                                                C.c_void_p(d_stats_ptr) if d_stats_ptr else None,
-                                                                C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
+        self._chk(lib().uwt_track_candidates_batch_seeded_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), threshold,
+                                                                C.byref(table_options(weights, sampler)), d_poses_ptr, d_stats_ptr,
+                                                                d_seeds_ptr, _sopt(handoff)))
 
     def estimate_pose_candidates_batch(self, ref_slots, tgt_slots, threshold=20.0, raise_on_pair_failure=False, weights=None,
                                        sampler=None):
@@ -1072,34 +1110,20 @@ class Context:
         (previous, current) over those tables, under the context's params.  weights / sampler (either given): the call's own robust
         weights and sampler, uwt_estimate_pose_candidates_batch_opt (the context's are then not looked at).
         Returns (poses [P, 7], per-pair stats)."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
-        poses = np.empty((max(ref.size, 1), 7), np.float32)
-        stats = (Stats * max(ref.size, 1))()
-        if weights is None and sampler is None:
-            st = lib().uwt_estimate_pose_candidates_batch(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.c_double(threshold),
-                                                          _p(poses, C.c_float), stats)
-        else:
-            opt = table_options(weights, sampler)
-            st = lib().uwt_estimate_pose_candidates_batch_opt(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
-                                                              C.c_double(threshold), C.byref(opt), _p(poses, C.c_float), stats)
-        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
-        return poses[:ref.size], [dict(status=s.status, iterations=s.iterations, n_valid=s.n_valid, error=s.error) for s in stats[:ref.size]]
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
+        poses, stats = _result_buffers(ref.size)
+        fn, opt = self._table_entry(lib().uwt_estimate_pose_candidates_batch, lib().uwt_estimate_pose_candidates_batch_opt, weights, sampler)
+        st = fn(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), threshold, *opt, _p(poses, C.c_float), stats)
+        self._chk_pairs(st, raise_on_pair_failure)
+        return poses[:ref.size], _stats_list(stats, ref.size)
 
     def track_candidates_batch_async(self, ref_slots, tgt_slots, d_poses_ptr, d_stats_ptr=None, threshold=20.0, weights=None,
                                      sampler=None):
         """The same enqueued on the context stream, results in device memory (d_poses_ptr: P x 7 float32, d_stats_ptr: P x 4
         int32-sized uwt_stats or None); sync() to wait."""
-        ref = np.ascontiguousarray(ref_slots, np.int32)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32)
-        d_stats = C.c_void_p(d_stats_ptr) if d_stats_ptr else None
-        if weights is None and sampler is None:
-            self._chk(lib().uwt_track_candidates_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
-                                                             C.c_double(threshold), C.c_void_p(d_poses_ptr), d_stats))
-        else:
-            opt = table_options(weights, sampler)
-            self._chk(lib().uwt_track_candidates_batch_opt_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32),
-                                                                 C.c_double(threshold), C.byref(opt), C.c_void_p(d_poses_ptr), d_stats))
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
+        fn, opt = self._table_entry(lib().uwt_track_candidates_batch_async, lib().uwt_track_candidates_batch_opt_async, weights, sampler)
+        self._chk(fn(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), threshold, *opt, d_poses_ptr, d_stats_ptr))
 
     @staticmethod
     def _descriptor_block(pairs, packed, cap):
@@ -1132,8 +1156,8 @@ class Context:
         per query descriptor: idx0, idx1 (-1: no such neighbour), d0, d1."""
         norm, dim, cap, q, nq, t, nt = self._descriptor_block(pairs, packed, cap)
         out = np.zeros((nq.size, cap), KNN2)
-        self._chk(lib().uwt_knn_match_batch(self._h, nq.size, norm, dim, C.c_void_p(q.ctypes.data), _p(nq, C.c_int32),
-                                            C.c_void_p(t.ctypes.data), _p(nt, C.c_int32), cap, C.c_void_p(out.ctypes.data)))
+        self._chk(lib().uwt_knn_match_batch(self._h, nq.size, norm, dim, q.ctypes.data, _p(nq, C.c_int32), t.ctypes.data,
+                                            _p(nt, C.c_int32), cap, out.ctypes.data))
         return [out[i, :nq[i]].copy() for i in range(nq.size)]
 
     def match_descriptors_batch(self, pairs=None, ratio=0.65, cap=None, packed=None):
@@ -1142,18 +1166,16 @@ class Context:
         norm, dim, cap, q, nq, t, nt = self._descriptor_block(pairs, packed, cap)
         out = np.zeros((nq.size, cap), MATCH)
         cnt = np.zeros(nq.size, np.int32)
-        self._chk(lib().uwt_match_descriptors_batch(self._h, nq.size, norm, dim, C.c_void_p(q.ctypes.data), _p(nq, C.c_int32),
-                                                    C.c_void_p(t.ctypes.data), _p(nt, C.c_int32), cap, C.c_float(ratio),
-                                                    C.c_void_p(out.ctypes.data), _p(cnt, C.c_int32)))
+        self._chk(lib().uwt_match_descriptors_batch(self._h, nq.size, norm, dim, q.ctypes.data, _p(nq, C.c_int32), t.ctypes.data,
+                                                    _p(nt, C.c_int32), cap, ratio, out.ctypes.data, _p(cnt, C.c_int32)))
         return [out[i, :cnt[i]].copy() for i in range(nq.size)]
 
     def match_descriptors_batch_async(self, d_matches_ptr, d_counts_ptr, pairs=None, ratio=0.65, cap=None, packed=None):
         """The same enqueued on the context stream, results in device memory (d_matches_ptr: P x cap MATCH records, d_counts_ptr: P
         int32); sync() to wait.  Returns cap.  Packed arrays from pinned_empty must stay untouched until the copy has run."""
         norm, dim, cap, q, nq, t, nt = self._descriptor_block(pairs, packed, cap)
-        self._chk(lib().uwt_match_descriptors_batch_async(self._h, nq.size, norm, dim, C.c_void_p(q.ctypes.data), _p(nq, C.c_int32),
-                                                          C.c_void_p(t.ctypes.data), _p(nt, C.c_int32), cap, C.c_float(ratio),
-                                                          C.c_void_p(d_matches_ptr), C.c_void_p(d_counts_ptr)))
+        self._chk(lib().uwt_match_descriptors_batch_async(self._h, nq.size, norm, dim, q.ctypes.data, _p(nq, C.c_int32), t.ctypes.data,
+                                                          _p(nt, C.c_int32), cap, ratio, d_matches_ptr, d_counts_ptr))
         return cap
 
     @staticmethod
@@ -1180,10 +1202,9 @@ class Context:
         P = nm.size
         mask, good = np.zeros((P, cap), np.uint8), np.zeros((P, cap), MATCH)
         cnt, info = np.zeros(P, np.int32), np.zeros(P, RANSAC_INFO)
-        self._chk(lib().uwt_ransac_inliers_batch(self._h, P, C.c_void_p(mt.ctypes.data), _p(nm, C.c_int32), cap, _p(k0, C.c_float),
-                                                 _p(n0, C.c_int32), _p(k1, C.c_float), _p(n1, C.c_int32), kp_cap,
-                                                 C.byref(params) if params is not None else None, C.c_void_p(mask.ctypes.data),
-                                                 C.c_void_p(good.ctypes.data), _p(cnt, C.c_int32), C.c_void_p(info.ctypes.data)))
+        self._chk(lib().uwt_ransac_inliers_batch(self._h, P, mt.ctypes.data, _p(nm, C.c_int32), cap, _p(k0, C.c_float), _p(n0, C.c_int32),
+                                                 _p(k1, C.c_float), _p(n1, C.c_int32), kp_cap, _ref(params), mask.ctypes.data,
+                                                 good.ctypes.data, _p(cnt, C.c_int32), info.ctypes.data))
         return [(mask[i, :nm[i]].copy(), good[i, :cnt[i]].copy(), info[i].copy()) for i in range(P)]
 
     def ransac_inliers_batch_async(self, d_matches_ptr, d_n_matches_ptr, cap, keypoints, d_mask_ptr, d_good_ptr, d_counts_ptr,
@@ -1193,11 +1214,9 @@ class Context:
         d_counts_ptr: P int32, d_info_ptr: P RANSAC_INFO); keypoints: a list of per-pair (kp_prev, kp_cur).  sync() to wait.
         Returns kp_cap."""
         _, kp_cap, _, _, k0, n0, k1, n1 = self._ransac_block([(np.zeros(0, MATCH), a, b) for a, b in keypoints], None, kp_cap)
-        self._chk(lib().uwt_ransac_inliers_batch_async(self._h, n0.size, C.c_void_p(d_matches_ptr), C.c_void_p(d_n_matches_ptr), cap,
-                                                       _p(k0, C.c_float), _p(n0, C.c_int32), _p(k1, C.c_float), _p(n1, C.c_int32),
-                                                       kp_cap, C.byref(params) if params is not None else None,
-                                                       C.c_void_p(d_mask_ptr), C.c_void_p(d_good_ptr), C.c_void_p(d_counts_ptr),
-                                                       C.c_void_p(d_info_ptr)))
+        self._chk(lib().uwt_ransac_inliers_batch_async(self._h, n0.size, d_matches_ptr, d_n_matches_ptr, cap, _p(k0, C.c_float),
+                                                       _p(n0, C.c_int32), _p(k1, C.c_float), _p(n1, C.c_int32), kp_cap, _ref(params),
+                                                       d_mask_ptr, d_good_ptr, d_counts_ptr, d_info_ptr))
         return kp_cap
 
     # ---- SURF and ORB detection and description: one helper per form; fn: the library's entry, dtype / row: a descriptor row
@@ -1207,14 +1226,13 @@ class Context:
         if out is None:
             out = (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, row), dtype) if describe else None, np.zeros(F, np.int32))
         kp, desc, cnt = out
-        self._chk(fn(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None, cap, C.c_void_p(kp.ctypes.data),
-                     C.c_void_p(desc.ctypes.data) if desc is not None else None, _p(cnt, C.c_int32)))
+        self._chk(fn(self._h, F, _p(slots, C.c_int32), _ref(params), cap, kp.ctypes.data, desc.ctypes.data if desc is not None else None,
+                     _p(cnt, C.c_int32)))
         return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy() if desc is not None else None) for i in range(F)]
 
     def _detect_describe_async(self, fn, slots, d_kp_ptr, d_desc_ptr, d_counts_ptr, params, cap):
         slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        self._chk(fn(self._h, slots.size, _p(slots, C.c_int32), C.byref(params) if params is not None else None, cap,
-                     C.c_void_p(d_kp_ptr), C.c_void_p(d_desc_ptr) if d_desc_ptr else None, C.c_void_p(d_counts_ptr)))
+        self._chk(fn(self._h, slots.size, _p(slots, C.c_int32), _ref(params), cap, d_kp_ptr, d_desc_ptr, d_counts_ptr))
 
     def _describe(self, fn, dtype, row, slots, keypoints_list, params, cap, out):
         slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
@@ -1225,8 +1243,8 @@ class Context:
         for i, k in enumerate(kin):
             kp[i, :len(k)], n[i] = k, len(k)
         res, desc = out if out is not None else (np.zeros((F, cap), KEYPOINT), np.zeros((F, cap, row), dtype))
-        self._chk(fn(self._h, F, _p(slots, C.c_int32), C.byref(params) if params is not None else None, C.c_void_p(kp.ctypes.data),
-                     _p(n, C.c_int32), cap, C.c_void_p(res.ctypes.data), C.c_void_p(desc.ctypes.data)))
+        self._chk(fn(self._h, F, _p(slots, C.c_int32), _ref(params), kp.ctypes.data, _p(n, C.c_int32), cap, res.ctypes.data,
+                     desc.ctypes.data))
         return [(res[i, :n[i]].copy(), desc[i, :n[i]].copy()) for i in range(F)]
 
     def surf_detect_describe_batch(self, slots, params=None, cap=UWT_MATCH_MAX_ROWS, describe=True, out=None):
@@ -1322,8 +1340,7 @@ class Context:
         (kp [P, cap] KEYPOINT, n [P] int32).  out: (poses [P, 7] float32, stats [P] STATS, info [P] TRACKING_INFO, good [P, cap]
         MATCH, kept_prev [P, cap] KEYPOINT, kept_cur [P, cap] KEYPOINT) to be written in place — the rows past a pair's count stay
         as they are.  Returns a dict: status (OK or ERR_PAIR_FAILED), poses, stats, info, and per pair good, kept_prev, kept_cur."""
-        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         P = ref.size
         kp = n = None
         if isinstance(prev, tuple):
@@ -1342,12 +1359,10 @@ class Context:
         if seeded is not None:
             keep, sp = _host_seeds(seeded[0], P)
             tail = (sp, _sopt(seeded[1]))
-        st = fn(self._h, P, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.byref(params) if params is not None else None,
-                cap, C.c_void_p(kp.ctypes.data) if kp is not None else None,
-                _p(n, C.c_int32) if n is not None else None, _p(poses, C.c_float), C.c_void_p(stats.ctypes.data),
-                C.c_void_p(info.ctypes.data), C.c_void_p(good.ctypes.data), C.c_void_p(kept_prev.ctypes.data),
-                C.c_void_p(kept_cur.ctypes.data), *tail)
-        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+        st = fn(self._h, P, _p(ref, C.c_int32), _p(tgt, C.c_int32), _ref(params), cap, kp.ctypes.data if kp is not None else None,
+                _p(n, C.c_int32) if n is not None else None, _p(poses, C.c_float), stats.ctypes.data, info.ctypes.data,
+                good.ctypes.data, kept_prev.ctypes.data, kept_cur.ctypes.data, *tail)
+        self._chk_pairs(st, raise_on_pair_failure)
         cnt = info["n_matches"]
         return dict(status=st, poses=poses[:P], stats=stats[:P], info=info[:P], good=[good[i, :cnt[i]].copy() for i in range(P)],
                     kept_prev=[kept_prev[i, :cnt[i]].copy() for i in range(P)], kept_cur=[kept_cur[i, :cnt[i]].copy() for i in range(P)])
@@ -1359,13 +1374,11 @@ class Context:
     def tracking_batch_seeded_async(self, ref_slots, tgt_slots, io, params=None, cap=2048, d_seeds_ptr=None, handoff=None):
         """tracking_batch_async from seeds in device memory (uwt_tracking_batch_seeded_async): d_seeds_ptr None or P x 7 float32 —
         a live loop passes the poses buffer of the call before (another buffer than io's)."""
-        self._tracking_batch_async(lib().uwt_tracking_batch_seeded_async, ref_slots, tgt_slots, io, params, cap,
-                                   (C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+        self._tracking_batch_async(lib().uwt_tracking_batch_seeded_async, ref_slots, tgt_slots, io, params, cap, (d_seeds_ptr, _sopt(handoff)))
 
     def tracking_orb_batch_seeded_async(self, ref_slots, tgt_slots, io, params=None, cap=2048, d_seeds_ptr=None, handoff=None):
         """tracking_batch_seeded_async for RobustMatcher(1) (uwt_tracking_orb_batch_seeded_async)."""
-        self._tracking_batch_async(lib().uwt_tracking_orb_batch_seeded_async, ref_slots, tgt_slots, io, params, cap,
-                                   (C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, _sopt(handoff)))
+        self._tracking_batch_async(lib().uwt_tracking_orb_batch_seeded_async, ref_slots, tgt_slots, io, params, cap, (d_seeds_ptr, _sopt(handoff)))
 
     def _tracking_batch_async(self, fn, ref_slots, tgt_slots, io, params, cap, tail=()):
         """The same enqueued on the context stream with every input and result in device memory (fn: uwt_tracking_batch_async or
@@ -1373,20 +1386,17 @@ class Context:
         dict of device addresses — poses (P x 7 float32), info (P TRACKING_INFO), good (P x cap MATCH), kept_prev, kept_cur (P x cap
         KEYPOINT), n_matches (P int32), optionally stats (P STATS) and prev_kp / n_prev (P x cap KEYPOINT, P int32: kept_cur /
         n_matches of the call before, of ANOTHER set of buffers).  Never waits for the device; sync() to wait."""
-        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         rec = TrackingIO(*[io.get(k) or None for k in ("prev_kp", "n_prev", "poses", "stats", "info", "good", "kept_prev", "kept_cur",
                                                         "n_matches")])
-        self._chk(fn(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), C.byref(params) if params is not None else None, cap,
-                     C.byref(rec), *tail))
+        self._chk(fn(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), _ref(params), cap, C.byref(rec), *tail))
 
     def match_descriptors_device_async(self, n_pairs, dim, cap, d_query_ptr, d_n_query_ptr, d_train_ptr, d_n_train_ptr, d_matches_ptr,
                                        d_counts_ptr, ratio=0.65, norm=NORM_L2):
         """match_descriptors_batch_async with both descriptor sets (P x cap x dim) and their counts (P int32) already in device
         memory, read in place (uwt_match_descriptors_device_async); a device count outside 0..cap is taken as 0.  sync() to wait."""
-        self._chk(lib().uwt_match_descriptors_device_async(self._h, n_pairs, norm, dim, C.c_void_p(d_query_ptr), C.c_void_p(d_n_query_ptr),
-                                                           C.c_void_p(d_train_ptr), C.c_void_p(d_n_train_ptr), cap, C.c_float(ratio),
-                                                           C.c_void_p(d_matches_ptr), C.c_void_p(d_counts_ptr)))
+        self._chk(lib().uwt_match_descriptors_device_async(self._h, n_pairs, norm, dim, d_query_ptr, d_n_query_ptr, d_train_ptr,
+                                                           d_n_train_ptr, cap, ratio, d_matches_ptr, d_counts_ptr))
 
     def surf_integral(self, slot):
         """The integral image of a slot's level-0 plane (uwt_surf_integral): (h + 1) x (w + 1) uint32"""
@@ -1424,14 +1434,7 @@ class Context:
         self._chk(lib().uwt_residual_jacobian_weighted(self._h, ref_slot, tgt_slot, lvl, _p(pose, C.c_float), C.byref(acc),
                                                        C.byref(err), C.byref(inv_mad), _p(J, C.c_float), _p(r, C.c_float),
                                                        _p(v, C.c_uint8), _p(w, C.c_float)))
-        A = np.zeros((6, 6))
-        s = 0
-        for i in range(6):
-            for j in range(i, 6):
-                A[i, j] = A[j, i] = acc.A[s]
-                s += 1
-        return dict(A=A, jtr=np.array(acc.jtr), sum_r2=int(acc.sum_r2), n_valid=int(acc.n_valid), J=J, r=r, valid=v, w=w,
-                    err_num=err.value, inv_mad=inv_mad.value)
+        return dict(_accum_fields(acc), J=J, r=r, valid=v, w=w, err_num=err.value, inv_mad=inv_mad.value)
 
     # -- did the alignment work: ObtainImageTransformed / DebugShowWarpedPerspective
     def obtain_image_transformed(self, slot, lvl, pts, warped, image=None):
@@ -1452,8 +1455,7 @@ class Context:
     def warp_image_batch(self, ref_slots, tgt_slots, poses, lvl=0, absdiff=True, raise_on_pair_failure=False):
         """The dense form for many pairs, host in and out (uwt_warp_image_batch): poses [P, 7].  Returns a dict: status (OK or
         ERR_PAIR_FAILED), warped, valid, absdiff ([P, img_h, img_w] u8; absdiff None when not asked for) and quality ([P] WARP_QUALITY)."""
-        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
         P = ref.size
         assert tgt.size == P and poses.shape[0] == P
@@ -1464,8 +1466,8 @@ class Context:
         quality = np.zeros(max(P, 1), WARP_QUALITY)
         st = lib().uwt_warp_image_batch(self._h, P, _p(ref, C.c_int32), _p(tgt, C.c_int32), lvl, _p(poses, C.c_float),
                                         _p(warped, C.c_uint8), _p(valid, C.c_uint8), _p(diff, C.c_uint8) if absdiff else None,
-                                        C.c_void_p(quality.ctypes.data))
-        self._chk(st, allow=() if raise_on_pair_failure else (ERR_PAIR_FAILED,))
+                                        quality.ctypes.data)
+        self._chk_pairs(st, raise_on_pair_failure)
         return dict(status=st, warped=warped[:P], valid=valid[:P], absdiff=diff[:P] if absdiff else None, quality=quality[:P])
 
     def warp_image_batch_async(self, ref_slots, tgt_slots, d_poses_ptr, io, lvl=0):
@@ -1473,11 +1475,9 @@ class Context:
         d_poses_ptr: P x 7 float32, e.g. the pose buffer of a tracking call enqueued before, with no sync() in between; io: a dict of
         device addresses — quality (P WARP_QUALITY) and optionally warped, valid, absdiff (P x pitch x img_h u8 each).  Never waits
         for the device; sync() to wait."""
-        ref = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
-        tgt = np.ascontiguousarray(tgt_slots, np.int32).reshape(-1)
+        ref, tgt = _pair_lists(ref_slots, tgt_slots)
         rec = WarpImageIO(*[io.get(k) or None for k in ("warped", "valid", "absdiff", "quality")])
-        self._chk(lib().uwt_warp_image_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), lvl,
-                                                   C.c_void_p(d_poses_ptr), C.byref(rec)))
+        self._chk(lib().uwt_warp_image_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(tgt, C.c_int32), lvl, d_poses_ptr, C.byref(rec)))
 
     def warp_mosaic(self, ref_slot, tgt_slot, lvl, warped):
         """The image of Tracker::DebugShowWarpedPerspective (src/Tracker.cpp:1694-1737) for one pair: [image1 | image2] over
@@ -1511,8 +1511,8 @@ class Context:
         info = np.zeros(max(J, 1), SWEEP_INFO)
         st = lib().uwt_sweep_depth_batch(self._h, J, _p(ref, C.c_int32), _p(views, C.c_int32), _p(poses, C.c_float), _p(codes, C.c_uint16),
                                          C.byref(params), _p(depth, C.c_uint16), _p(cst, C.c_uint16) if cost else None,
-                                         _p(out, C.c_uint8) if outcome else None, C.c_void_p(info.ctypes.data))
-        self._chk(st, allow=() if raise_on_failure else (ERR_PAIR_FAILED,))
+                                         _p(out, C.c_uint8) if outcome else None, info.ctypes.data)
+        self._chk_pairs(st, raise_on_failure)
         return dict(status=st, depth=depth[:J], cost=cst[:J] if cost else None, outcome=out[:J] if outcome else None, info=info[:J])
 
     def sweep_depth_async(self, ref_slots, view_slots, d_poses_ptr, codes, io, params=None):
@@ -1526,7 +1526,7 @@ class Context:
         if params is None:
             params = default_sweep_params(n_views=views.size // max(ref.size, 1), n_hyp=codes.size)
         rec = SweepIO(*[io.get(k) or None for k in ("depth", "cost", "outcome", "info")])
-        self._chk(lib().uwt_sweep_depth_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(views, C.c_int32), C.c_void_p(d_poses_ptr),
+        self._chk(lib().uwt_sweep_depth_batch_async(self._h, ref.size, _p(ref, C.c_int32), _p(views, C.c_int32), d_poses_ptr,
                                                     _p(codes, C.c_uint16), C.byref(params), C.byref(rec)))
 
     # -- the map: Visualizer::AddPointCloudFromRGBD
@@ -1544,8 +1544,8 @@ class Context:
             cap = F * (-(-(L.w * L.h) // max(int(params.stride), 1)))
         pts = np.zeros(max(cap, 1), CLOUD_POINT)
         info = np.zeros(F + 1, CLOUD_INFO)
-        st = lib().uwt_point_cloud_batch(self._h, F, _p(slots, C.c_int32), _p(traj, C.c_float), C.byref(params),
-                                         C.c_void_p(pts.ctypes.data), C.c_int64(cap), C.c_void_p(info.ctypes.data))
+        st = lib().uwt_point_cloud_batch(self._h, F, _p(slots, C.c_int32), _p(traj, C.c_float), C.byref(params), pts.ctypes.data, cap,
+                                         info.ctypes.data)
         self._chk(st, allow=() if raise_on_failure else (ERR_PAIR_FAILED, ERR_CAPACITY))
         return dict(status=st, points=pts[:int(info[F]["written"])], info=info[:F], call=info[F])
 
@@ -1555,8 +1555,8 @@ class Context:
         CLOUD_POINT records, d_info_ptr F + 1 CLOUD_INFO records.  Never waits for the device; sync() to wait."""
         slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
         params = default_cloud_params() if params is None else params
-        self._chk(lib().uwt_point_cloud_batch_async(self._h, slots.size, _p(slots, C.c_int32), C.c_void_p(d_traj_ptr), C.byref(params),
-                                                    C.c_void_p(d_points_ptr), C.c_int64(cap), C.c_void_p(d_info_ptr)))
+        self._chk(lib().uwt_point_cloud_batch_async(self._h, slots.size, _p(slots, C.c_int32), d_traj_ptr, C.byref(params),
+                                                    d_points_ptr, cap, d_info_ptr))
 
     def point_cloud_points(self, slot, pts, traj_pose, params=None, cap=None):
         """Visualizer::AddPointCloudFromRGBD (src/Visualizer.cpp:421-446) on one explicit N x 4 table (uwt_point_cloud_points); `slot`
@@ -1569,21 +1569,21 @@ class Context:
         out = np.zeros(max(cap, 1), CLOUD_POINT)
         cnt = C.c_int64()
         st = lib().uwt_point_cloud_points(self._h, slot, _p(pts, C.c_float), n, _p(pose, C.c_float), C.byref(params),
-                                          C.c_void_p(out.ctypes.data), C.c_int64(cap), C.byref(cnt))
+                                          out.ctypes.data, cap, C.byref(cnt))
         self._chk(st, allow=(ERR_CAPACITY,))
         return out[:min(cnt.value, cap)], cnt.value, st
 
     def accumulate_trajectory_device_async(self, d_poses_ptr, n, d_traj_ptr, start=None, t_scale=1.0, reference_axes=False):
         """uwt_accumulate_trajectory on device pointers (n x 7 float32 each), enqueued on the context stream: no copy, no wait."""
         start = np.array([0, 0, 0, 1, 0, 0, 0], np.float32) if start is None else np.ascontiguousarray(start, np.float32)
-        self._chk(lib().uwt_accumulate_trajectory_device_async(self._h, C.c_void_p(d_poses_ptr), int(n), _p(start, C.c_float),
-                                                               C.c_float(t_scale), int(bool(reference_axes)), C.c_void_p(d_traj_ptr)))
+        self._chk(lib().uwt_accumulate_trajectory_device_async(self._h, d_poses_ptr, int(n), _p(start, C.c_float), t_scale,
+                                                               int(bool(reference_axes)), d_traj_ptr))
 
     def accumulate_trajectory_device_from_async(self, d_poses_ptr, n, d_start_ptr, d_traj_ptr, t_scale=1.0, reference_axes=False):
         """The same behind a previous pose in device memory (uwt_accumulate_trajectory_device_from_async): d_start_ptr 7 float32, a row of
         an earlier accumulation made with reference_axes False."""
-        self._chk(lib().uwt_accumulate_trajectory_device_from_async(self._h, C.c_void_p(d_poses_ptr), int(n), C.c_void_p(d_start_ptr),
-                                                                    C.c_float(t_scale), int(bool(reference_axes)), C.c_void_p(d_traj_ptr)))
+        self._chk(lib().uwt_accumulate_trajectory_device_from_async(self._h, d_poses_ptr, int(n), d_start_ptr, t_scale,
+                                                                    int(bool(reference_axes)), d_traj_ptr))
 
 
 class Ingest:
@@ -1626,16 +1626,16 @@ class Ingest:
         raw = np.asarray(raw)
         assert raw.dtype == np.uint8 and raw.shape == (self.in_h, self.in_w) and raw.strides[1] == 1
         out = np.empty((self.out_h, self.out_w), np.uint8)
-        self._chk(lib().uwt_ingest_undistort(self._h, _p(raw, C.c_uint8), C.c_size_t(raw.strides[0]), _p(out, C.c_uint8)))
+        self._chk(lib().uwt_ingest_undistort(self._h, _p(raw, C.c_uint8), raw.strides[0], _p(out, C.c_uint8)))
         return out
 
     def calculate_roi(self, raw_first):
         raw = np.asarray(raw_first)
         roi = np.empty(4, np.int32)
-        self._chk(lib().uwt_ingest_calculate_roi(self._h, _p(raw, C.c_uint8), C.c_size_t(raw.strides[0]), _p(roi, C.c_int32)))
+        self._chk(lib().uwt_ingest_calculate_roi(self._h, _p(raw, C.c_uint8), raw.strides[0], _p(roi, C.c_int32)))
         return roi
 
     def frame(self, ctx, slot, raw, x0, y0):
         raw = np.asarray(raw)
         assert raw.dtype == np.uint8 and raw.shape == (self.in_h, self.in_w) and raw.strides[1] == 1
-        self._chk(lib().uwt_ingest_frame(self._h, ctx._h, slot, _p(raw, C.c_uint8), C.c_size_t(raw.strides[0]), x0, y0))
+        self._chk(lib().uwt_ingest_frame(self._h, ctx._h, slot, _p(raw, C.c_uint8), raw.strides[0], x0, y0))
